@@ -7,10 +7,13 @@ resident in HBM, through every operator of the path - appearance encoder, wav2ve
 (`--nfe` grid points: default 51 = 50 Euler evaluations per 50-frame window, 3-way CFG a=2 e=1), Synthesis decoder - to `T`
 fp32 frames in a freshly allocated pinned HOST tensor (the reference's destination, FLOAT.py:139; the frames of decode batch i
 leave inside the launches of batch i+1), stream synchronised.  `value` = frames of all ranks / wall-clock of the timed steps.
-The FMT sampling + decode part alone (frames left in HBM: round 1's headline) is reported beside it as `hot_path`, and the same
-step with bf16 FMT operands (BASELINE.json's wording for configs[1]) as `value_bf16`.
+A plain run sets up, warms up, times `--steps` steps, writes the last step's frames if `--dump-outputs DIR` is given, and prints
+the line.  With `--full` the same run goes on to the side measurements: the FMT sampling + decode part alone (frames left in HBM:
+round 1's headline) as `hot_path`, the stage split, the roofline pass with the measured peaks and the clock sample, the same step
+with bf16 FMT operands (BASELINE.json's wording for configs[1]) as `value_bf16`, the speech-emotion / nfe / host-input / stacked
+batch variants, the CPU baseline and, at N = 1, a one-rank RCCL communicator.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 without a launcher: this process starts N ranks itself (one per GPU, before it touches a GPU) and relays rank 0's line.
@@ -71,8 +74,12 @@ def parse():
     ap.add_argument("--overlap", default=None, help="prio | cu:N: decode window k on a second stream beside the FMT chain of window "
                     "k + 1 (FLOAT_AMD_OVERLAP; pipeline.generate_to_host_overlap).  Default: the product's default (sequential)")
     ap.add_argument("--quick", action="store_true", help="only the headline measurement (A/B runs): no extras / roofline / "
-                    "CPU baseline / bf16 / s2e / variants")
+                    "CPU baseline / bf16 / s2e / variants, even with --full (a plain run measures only the headline anyway)")
     ap.add_argument("--batches", default="4,8,16", help="stacked-clip throughput runs (value_batchB), comma separated; empty = none")
+    ap.add_argument("--full", action="store_true", help="besides the headline: stage split / hot path, roofline, CPU baseline, bf16, "
+                    "s2e, variants and batches (each still subject to its --no-* switch), and the one-rank RCCL communicator at N = 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the frames of the last step "
+                    "as DIR/<name>.npy (float32; at most 64 MB: a fixed sample of frames beside a seeded sample of all pixels)")
     return ap.parse_args()
 
 
@@ -240,9 +247,32 @@ def cpu_baseline(pkg, torch, cfg, fmt_sd, dec_sd, feats, cond, nfe_evals):
                       "encoders not included" % (n_eval, t_eval, n_frames, t_frame)}
 
 
+DUMP_LIMIT = 60 * 10**6  # bytes of arrays written by --dump-outputs, all ranks together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, frames, rank=None, world=1, limit=DUMP_LIMIT):
+    """The frames a caller of the timed path receives ((T,H,W,3) fp32 in [0,1]) as .npy files of at most `limit` / world bytes:
+    the whole tensor when it fits, otherwise `frames_sample` (evenly spaced whole frames, first and last included) and
+    `frames_pixels` (a seeded sample of 2**20 values over all frames).  The same arguments give the same samples."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank is None else "_rank%d" % rank
+    limit //= world
+    a = frames.numpy()
+    if a.nbytes <= limit:
+        np.save(os.path.join(out_dir, "frames%s.npy" % tag), a.astype(np.float32))
+        return
+    n_px = min(2**20, limit // 8)
+    k = max(1, min(len(a), (limit - 4 * n_px) // a[0].nbytes))
+    idx = np.unique(np.linspace(0, len(a) - 1, k).round().astype(np.int64))
+    np.save(os.path.join(out_dir, "frames_sample%s.npy" % tag), a[idx].astype(np.float32))
+    pick = np.random.default_rng(0).integers(0, a.size, n_px)
+    np.save(os.path.join(out_dir, "frames_pixels%s.npy" % tag), a.reshape(-1)[pick].astype(np.float32))
+
+
 def main():
     args = parse()
-    if args.quick:
+    if args.quick or not args.full:
         args.no_extras = args.no_roofline = args.no_cpu_baseline = args.no_bf16 = args.no_s2e = args.no_variants = True
     if args.overlap is not None:
         os.environ["FLOAT_AMD_OVERLAP"] = args.overlap
@@ -281,7 +311,7 @@ def main():
                 dist.init_process_group(backend, store=store, rank=rank, world_size=world)
         if dist.get_world_size() != world:
             raise RuntimeError("rendezvous gave %d ranks, expected %d" % (dist.get_world_size(), world))
-    elif backend == "nccl" and os.environ.get("FLOAT_BENCH_RCCL1", "1") != "0":
+    elif backend == "nccl" and args.full and os.environ.get("FLOAT_BENCH_RCCL1", "1") != "0":
         # N = 1: still bring RCCL up (a one-rank communicator on this GPU) so that the collective calls of the N > 1 modes have
         # run on the box at least once; a failure here is reported on the line, it does not fail the single-GPU measurement
         try:
@@ -399,6 +429,8 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 seam[key] = float(t.item())
     host = last["host"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, host, rank if world > 1 else None, world)
     per_rank = None
     if world > 1:
         # Every rank's own stage times (hipEvents, one more pass outside the timed region) and the latency of the job's one data-path

@@ -24,7 +24,7 @@ def _run(args, env=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    r = _run(SHORT + ["--batches", "4,8"])  # every leg of the default run: roofline pass, CPU baseline, speech-to-emotion, nfe / host-input variants
+    r = _run(SHORT + ["--full", "--batches", "4,8"])  # every leg of --full: roofline pass, CPU baseline, speech-to-emotion, nfe / host-input variants
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "stage_ms", "value_s2e", "value_nfe5", "value_from_host_inputs",
               "host_inputs_ms", "rccl_ranks", "fp16_range_hits", "value_batch4", "value_batch8", "roofline_batch", "host_threads_per_rank"):
@@ -49,6 +49,25 @@ def test_single_gpu_line_has_the_contract_fields():
     assert 2000 < d["hbm_read_GBps"] <= 8000 and 2000 < d["hbm_copy_GBps"] <= 8000 and d["compute_units"] >= 64
     assert 1000 < max(d["mfma_f16_16x16x32_TFLOPs"], d["mfma_f16_32x32x16_TFLOPs"]) <= 2600
     assert ro["peak"] in (8000.0, 2500.0) and ro["peak_measured"] > 0 and abs(ro["frac_measured"] - ro["achieved"] / ro["peak_measured"]) < 1e-3
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_frames(tmp_path):
+    """Without --full: the headline alone (no side measurement on the line), `--steps` timed steps, and with --dump-outputs the
+    last step's frames as float32 .npy files under 64 MB (50 frames of 512 x 512: a fixed sample of them)."""
+    import numpy as np
+    r = _run(["--seconds", "2", "--nfe", "6", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 2 and r["higher_is_better"] is True and r["unit"] == "frames/s" and r["dtype"] == "fp16"
+    assert abs(r["value"] - 50 / (r["ms_per_step"] * 1e-3)) < 0.01 * r["value"]
+    for k in ("cpu_baseline", "roofline", "stage_ms", "hot_path", "value_bf16", "value_s2e", "value_nfe5", "value_batch4"):
+        assert k not in r, k
+    assert r["rccl_ranks"] is None and r["fp16_range_hits"] == 0
+    out = {f: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["frames_pixels.npy", "frames_sample.npy"]
+    assert all(a.dtype == np.float32 for a in out.values()) and sum(os.path.getsize(os.path.join(tmp_path, f)) for f in out) < 64e6
+    s = out["frames_sample.npy"]
+    assert s.shape[1:] == (512, 512, 3) and len(s) >= 8 and 0.0 <= s.min() and s.max() <= 1.0 and s.mean() > 0.0
 
 
 @pytest.mark.parametrize("mode", ["replicas", "window", "shard"])

@@ -28,6 +28,24 @@ def golden(name):
     return {k: (torch.from_numpy(z[k]) if z[k].ndim else z[k].item()) for k in z.files}
 
 
+def golden_parts(name):
+    """A fixture that tools/make_goldens.py::save_parts wrote as name_0.npz, name_1.npz, ...: one dict of tensors, the pieces
+    `key@i` of a split array concatenated again along its second axis."""
+    out, pieces, i = {}, {}, 0
+    while os.path.exists(os.path.join(GOLDEN, "%s_%d.npz" % (name, i))):
+        for k, v in golden("%s_%d" % (name, i)).items():
+            if "@" in k:
+                key, j = k.split("@")
+                pieces.setdefault(key, {})[int(j)] = v
+            else:
+                out[k] = v
+        i += 1
+    assert i > 0, "no fixture %s_0.npz in %s" % (name, GOLDEN)
+    for key, p in pieces.items():
+        out[key] = torch.cat([p[j] for j in range(len(p))], dim=1)
+    return out
+
+
 def rel_l2(a, b):
     a, b = a.double(), b.double()
     return float((a - b).norm() / (b.norm() + 1e-30))

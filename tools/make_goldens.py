@@ -49,6 +49,27 @@ def save(name, **arrs):
     print("  wrote %-28s %7.1f KB" % (name + ".npz", os.path.getsize(path) / 1024))
 
 
+def save_parts(name, limit=960 * 1024, **arrs):
+    """save() into name_0.npz, name_1.npz, ... of at most `limit` bytes of arrays each, so that every committed fixture stays
+    under 1 MiB: an array larger than `limit` is cut along its second axis into pieces `key@0`, `key@1`, ...
+    (tests/util.py::golden_parts puts them together again)."""
+    items = []
+    for k, v in arrs.items():
+        v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        n = int(math.ceil(v.nbytes / limit))
+        if n <= 1:
+            items.append((k, v))
+        else:
+            items += [("%s@%d" % (k, i), c) for i, c in enumerate(np.array_split(v, n, axis=1))]
+    part, size, idx = {}, 0, 0
+    for k, v in items:
+        if part and size + v.nbytes > limit:
+            save("%s_%d" % (name, idx), **part)
+            part, size, idx = {}, 0, idx + 1
+        part[k], size = v, size + v.nbytes
+    save("%s_%d" % (name, idx), **part)
+
+
 def maxdiff(a, b):
     return float((a.double() - b.double()).abs().max()), float(
         (a.double() - b.double()).norm() / (b.double().norm() + 1e-30))
@@ -684,6 +705,41 @@ def gen_node_surface_va(ns):
     print("  wrote node_surface_va.json (%d classes)" % len(out))
 
 
+def gen_oracle_live(ns):
+    """tests/test_oracle_vs_reference_live.py: the reference on fresh seeds (not the other fixtures' seeds) - an FMT
+    evaluation with CFG, a 64 px Synthesis and a 64 px Encoder; inputs and outputs, the weights come from their seeds."""
+    cfg = config.small_fmt_config()
+    opt = ns.base_options.BaseOptions()
+    for k in ("dim_w", "dim_a", "dim_e", "dim_h", "fmt_depth", "num_heads", "mlp_ratio", "num_prev_frames", "attention_window"):
+        setattr(opt, k, getattr(cfg, k))
+    opt.rank = "cpu"
+    m = ns.FMT.FlowMatchingTransformer(opt)
+    m.load_state_dict(weights.synth_fmt_state(cfg, seed=77), strict=True)
+    m.eval()
+    g = torch.Generator().manual_seed(9)
+    r = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    x, wa, wr, we = r(2, 50, 128), r(2, 50, 128), r(2, 128), torch.softmax(r(2, 1, 7), -1)
+    px, pwa = r(2, 10, 128), r(2, 10, 128)
+    t = torch.tensor([0.81])
+    with torch.no_grad():
+        fmt_out = m.forward_with_cfv(t, x, wa, wr, we, px, pwa, None, a_cfg_scale=1.7, r_cfg_scale=1.0, e_cfg_scale=2.2)
+    d, _ = ref_dec(ns, 64, 78)
+    lat = torch.randn(2, 512, generator=torch.Generator().manual_seed(10))
+    feats = weights.synth_feats(64, seed=78)
+    with torch.no_grad():
+        img_out, flow = d(lat, None, [f.expand(2, -1, -1, -1) for f in feats])
+    e = ns.encoder.Encoder(64, 512, 20)
+    e.load_state_dict(weights.synth_encoder_state(64, seed=79), strict=True)
+    e.eval()
+    img = torch.rand(1, 3, 64, 64, generator=torch.Generator().manual_seed(3)) * 2 - 1
+    with torch.no_grad():
+        s_r, _, efeats = e(img, None)
+        lam = e.fc(s_r)
+    save_parts("oracle_live", fmt_x=x, fmt_wa=wa, fmt_wr=wr, fmt_we=we, fmt_px=px, fmt_pwa=pwa, fmt_t=t, fmt_out=fmt_out,
+               dec_lat=lat, dec_img=img_out, dec_flow=flow, enc_img=img, enc_s_r=s_r, enc_lam=lam,
+               **{"enc_feat%d" % i: f for i, f in enumerate(efeats)})
+
+
 def gen_full_configs(ns):
     """BASELINE.json configs[1] (10 s, 250 frames, 5 windows x 50 Euler evaluations, static emotion, a=2 e=1) and configs[4]
     (30 s, 750 frames, 15 windows, per-window dynamic emotion, a=1 e=3) through the reference's own sampler
@@ -702,6 +758,9 @@ def main():
         return
     if os.environ.get("GOLDENS_ONLY") == "configs":
         gen_full_configs(ns)
+        return
+    if os.environ.get("GOLDENS_ONLY") == "live":
+        gen_oracle_live(ns)
         return
     if os.environ.get("GOLDENS_ONLY") == "va":
         gen_node_surface_va(ns)
@@ -779,6 +838,7 @@ def main():
     gen_audio(ns, "base", config.AudioConfig(), seed=1300, seconds=2.0, T=50)
     gen_emotion(ns, "small", config.small_emotion_config(), seed=1400, seconds=1.3)
     gen_emotion(ns, "xlsr", config.emotion_audio_config(), seed=1500, seconds=1.0)
+    gen_oracle_live(ns)
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r06_prof}; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; cat $O/bench.json | cut -c1-300
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-roofline --no-bf16 > $O/stats.log 2>&1
+python bench.py --full > $O/bench.json 2> $O/bench.err; cat $O/bench.json | cut -c1-300
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-roofline --no-bf16 > $O/stats.log 2>&1
 find $O/stats -name "*kernel_trace.csv" -delete
 for w in fmt fmtb dec; do for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_${c}_$w -o p -- python3 tools/profile_hotpath.py --what $w > $O/pmc_${c}_$w.log 2>&1
@@ -17,5 +17,5 @@ python tools/make_traffic_json.py $O/pmc_FETCH_SIZE_fmt,$O/pmc_FETCH_SIZE_fmtb,$
 # the bench line that goes to profiles/: run with THIS round's counter files in place, so its counter-derived fields are live
 P=profiles/${2:-r06}
 cp $O/pmc_mfma.json ${P}_pmc_mfma.json; cp $O/pmc_traffic.json ${P}_pmc_traffic.json
-python bench.py > $O/bench_final.json 2> $O/bench_final.err; cut -c1-300 $O/bench_final.json
+python bench.py --full > $O/bench_final.json 2> $O/bench_final.err; cut -c1-300 $O/bench_final.json
 du -sh $O

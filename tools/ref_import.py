@@ -1,9 +1,8 @@
 """Import the upstream reference (read-only, /root/reference) as a numerical checker.
 
 BUILD-CONTAINER ONLY.  The reference never travels to the GPU box; this module is
-used by tools/make_goldens.py (fixture generation) and by the optional
-`-m "not gpu"` tests that cross-check oracle/ against the live reference when
-/root/reference exists.  Nothing under the product package imports this file.
+used by tools/make_goldens.py (fixture generation) only: the tests read what it
+recorded under tests/golden/.  Nothing under the product package imports this file.
 
 The reference depends on packages that are absent here (seconohe, comfy, timm,
 torchdiffeq, cv2, librosa, face_alignment, folder_paths).  Each is replaced by a
