@@ -79,3 +79,79 @@ def sample_inputs(cfg, seed, T, dynamic, noise_seed=15):
     g.manual_seed(int(noise_seed))
     noise = torch.stack([torch.randn(1, L, cfg.dim_w, generator=g) for _ in range(n_chunks)])
     return dict(wa=wa, r_s=r_s, we=we, noise=noise)
+
+
+# ---- decoder geometry cases (tests/test_dec_geometry_gpu.py; their conditioning is pinned by tests/test_oracle_golden.py) ----
+DEC_SIZE_FRAMES = 7
+# (cin, cout, R_in, upsample): conv16 NT = 2; two 64-channel blocks; zblur to 128 px (4 blocks, partial tile of 16); zblur to
+# 256 px (partial tile of 4); dec_zconv4_kernel at full channel count
+UNIT_CONV_CASES = [(32, 32, 64, 0), (128, 128, 32, 0), (256, 128, 64, 1), (128, 64, 128, 1), (512, 512, 8, 1)]
+# (C, R, prev): PIX = 4 with 8 lanes per pixel and several bands; 256 and 512 channels; a level without a pyramid below it
+UNIT_FLOW_CASES = [(64, 64, 1), (256, 64, 1), (512, 8, 1), (64, 128, 0)]
+UNIT_SEED = 4100
+
+
+def dec_size_inputs(size):
+    """The inputs of tests/test_dec_sizes_gpu.py: (state dict, feats, s_r (1,512), r_d (1,7,512))."""
+    W = load_pkg().weights
+    g = torch.Generator().manual_seed(1)
+    s_r, r_d = torch.randn(1, 512, generator=g), torch.randn(1, DEC_SIZE_FRAMES, 512, generator=g) * 0.5
+    return W.synth_decoder_state(size, seed=3), W.synth_feats(size, seed=3), s_r, r_d
+
+
+def unit_style():
+    return seeded_normal(UNIT_SEED + 1, 2, 512)
+
+
+def unit_conv_case(i):
+    """(state with the StyledConv module's key names, x (2,cin,R,R)) of UNIT_CONV_CASES[i]: the recipe of
+    tests/test_dec_units_gpu.py::test_styled_conv_routes.  The up-sampling cases take a low-pass x (noise of R/4, enlarged): the
+    blur of a transposed conv of WHITE noise is a sum that cancels, while the rounding of the K = cin sums before it does not -
+    the fp32 oracle itself then sits at rel-L2 6.5e-7 of the fp64 one at 512 channels, a third of the fp32 limit."""
+    cin, cout, R, up = UNIT_CONV_CASES[i]
+    k = UNIT_SEED + 100 * (i + 1)
+    rnd = seeded_normal
+    sd = {"conv.weight": rnd(k + 2, 1, cout, cin, 3, 3), "conv.modulation.weight": rnd(k + 3, cin, 512),
+          "conv.modulation.bias": 1 + rnd(k + 4, cin, std=0.1), "activate.bias": rnd(k + 5, 1, cout, 1, 1, std=0.1)}
+    return sd, (smooth_field(k + 6, 2, cin, R, R // 4) if up else rnd(k + 6, 2, cin, R, R))
+
+
+def smooth_field(seed, n, c, r, lo, hi=0.02):
+    """Low-pass random field like weights.synth_feats: (n,c,lo,lo) noise enlarged bilinearly to r x r plus `hi` of white noise."""
+    f = torch.nn.functional.interpolate(seeded_normal(seed, n, c, lo, lo), size=(r, r), mode="bilinear", align_corners=False)
+    return (f + seeded_normal(seed + 50, n, c, r, r, std=hi)).contiguous()
+
+
+def unit_flow_case(j):
+    """(state with `to_flow.*` / `to_rgb.*` keys, x (2,C,R,R), feat (1,C,R,R), prev_flow, prev_rgb) of UNIT_FLOW_CASES[j]: the
+    recipe of tests/test_dec_units_gpu.py::test_flow_level with a low-pass feature map like weights.synth_feats instead of white
+    noise, so that the fp32 rounding of a sampling position is not what a limit measures.  ToFlow weight gain 0.3 as there; 0.1
+    (the flow_gain of weights.synth_decoder_state) above 64 px, where a rounding of the flow is R / 2 times that in pixels."""
+    C, R, prev = UNIT_FLOW_CASES[j]
+    k = UNIT_SEED + 1000 * (j + 1)
+    rnd = seeded_normal
+    sd = {"to_flow.bias": rnd(k + 6, 1, 3, 1, 1, std=0.1),
+          "to_flow.conv.weight": rnd(k + 7, 1, 3, C, 1, 1, std=0.3 if R <= 64 else 0.1),
+          "to_flow.conv.modulation.weight": rnd(k + 8, C, 512), "to_flow.conv.modulation.bias": 1 + rnd(k + 9, C, std=0.1),
+          "to_rgb.bias": rnd(k + 13, 1, 3, 1, 1, std=0.1), "to_rgb.conv.0.weight": rnd(k + 14, 3, C, 1, 1),
+          "to_rgb.conv.1.bias": rnd(k + 15, 1, 3, 1, 1, std=0.1)}
+    x, feat = rnd(k + 10, 2, C, R, R), smooth_field(k + 11, 1, C, R, max(2, R // 8))
+    pflow = rnd(k + 12, 2, 3, R // 2, R // 2, std=0.5) if prev else None
+    prgb = rnd(k + 16, 2, 3, R // 2, R // 2) if prev else None
+    return sd, x, feat, pflow, prgb
+
+
+def unit_conv_oracle(i, dtype=torch.float64):
+    from oracle import float_oracle as O
+    sd, x = unit_conv_case(i)
+    return O.styled_conv(x.to(dtype), unit_style().to(dtype), {"c." + k: v for k, v in sd.items()}, "c",
+                         bool(UNIT_CONV_CASES[i][3]))
+
+
+def unit_flow_oracle(j, dtype=torch.float64):
+    """{"out": flow (2,3,R,R), "blend": (2,C,R,R), "rgb": (2,3,R,R)} of ToFlow + ToRGB in `dtype`."""
+    from oracle import float_oracle as O
+    sd, x, feat, pflow, prgb = unit_flow_case(j)
+    cast = lambda t: None if t is None else t.to(dtype)  # noqa: E731
+    fw, bl, o3, _ = O.to_flow(cast(x), unit_style().to(dtype), feat.repeat(2, 1, 1, 1), sd, "to_flow", cast(pflow))
+    return {"out": o3, "blend": bl, "rgb": O.to_rgb(fw, sd, "to_rgb", cast(prgb))}
