@@ -56,6 +56,8 @@ struct float_aud {
   void *x16 = nullptr, *hp16 = nullptr, *qkv16 = nullptr, *att16 = nullptr, *hid16 = nullptr, *stack16 = nullptr;
   float *hproj = nullptr, *pos = nullptr, *h = nullptr, *h1 = nullptr, *y = nullptr, *yproj = nullptr;
   unsigned long long* sat = nullptr;  // range counter of the 16-bit activation stores (float_aud_saturation)
+  FmtTune gemm_tune;  // what the GEMM service packs and tiles by: read at float_aud_create like `tune`, no FMT handle involved
+  AudTune tune;
 };
 
 namespace {
@@ -133,7 +135,7 @@ int create_impl(float_aud* h, const TensorTable& tt) {
   }
   // ---- feature projection (LayerNorm + Linear)
   if ((rc = load_ln(h, tt, W2 + "feature_projection.layer_norm", h->C, &h->fp_ln))) return rc;
-  if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {W2 + "feature_projection.projection"}, h->D, h->C, &h->fp_proj))) return rc;
+  if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {W2 + "feature_projection.projection"}, h->D, h->C, &h->fp_proj))) return rc;
   // ---- positional conv embedding, weight-norm folded: w = g * v / ||v||, norm over (out, in) per tap (dim = 2)
   {
     const std::string p = W2 + "encoder.pos_conv_embed.conv.";
@@ -193,11 +195,11 @@ int create_impl(float_aud* h, const TensorTable& tt) {
   for (int l = 0; l < c.layers; ++l) {
     const std::string p = W2 + "encoder.layers." + std::to_string(l) + ".";
     TLayer& L = h->layers[l];
-    if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {p + "attention.q_proj", p + "attention.k_proj", p + "attention.v_proj"}, h->D, h->D, &L.qkv)))
+    if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {p + "attention.q_proj", p + "attention.k_proj", p + "attention.v_proj"}, h->D, h->D, &L.qkv)))
       return rc;
-    if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {p + "attention.out_proj"}, h->D, h->D, &L.out))) return rc;
-    if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {p + "feed_forward.intermediate_dense"}, c.intermediate, h->D, &L.ff1))) return rc;
-    if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {p + "feed_forward.output_dense"}, h->D, c.intermediate, &L.ff2))) return rc;
+    if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {p + "attention.out_proj"}, h->D, h->D, &L.out))) return rc;
+    if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {p + "feed_forward.intermediate_dense"}, c.intermediate, h->D, &L.ff1))) return rc;
+    if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {p + "feed_forward.output_dense"}, h->D, c.intermediate, &L.ff2))) return rc;
     if ((rc = load_ln(h, tt, p + "layer_norm", h->D, &L.ln1))) return rc;
     if ((rc = load_ln(h, tt, p + "final_layer_norm", h->D, &L.ln2))) return rc;
   }
@@ -220,7 +222,7 @@ int create_impl(float_aud* h, const TensorTable& tt) {
   } else {
     // ---- audio projection: Linear(layers*D | D -> dim_w) + LayerNorm + SiLU (FLOAT.py:338-342)
     const int din = c.only_last ? h->D : c.layers * h->D;
-    if ((rc = fmt_pack_linear(&h->pool, c.dtype, tt, {"audio_projection.0"}, c.dim_w, din, &h->aproj))) return rc;
+    if ((rc = fmt_pack_linear(h->gemm_tune, &h->pool, c.dtype, tt, {"audio_projection.0"}, c.dim_w, din, &h->aproj))) return rc;
     if ((rc = load_ln(h, tt, "audio_projection.1", c.dim_w, &h->aproj_ln))) return rc;
   }
   fmt_gemm_prime(c.dtype);
@@ -374,7 +376,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
     g.sat = h->sat;
     g.out_f32 = h->hproj;
     g.ldo = D;
-    if ((rc = fmt_gemm_run(c.dtype, EPI_F32, g, st))) return rc;
+    if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_F32, g, st))) return rc;
   }
   // ---- encoder.  Post-LayerNorm (wav2vec2-base): hidden = LN(hidden + gelu(pos_conv(hidden))), then per layer
   // h = LN(h + attn(h)); h = LN(h + ffn(h)).  Stable (pre-)LayerNorm (the speech-emotion model): hidden += pos, per layer
@@ -418,11 +420,11 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
       g.sat = h->sat;
       g.out16 = reinterpret_cast<u16*>(h->qkv16);
       g.ldo16 = 3 * D;
-      if ((rc = fmt_gemm_run(c.dtype, EPI_T16, g, st))) return rc;
+      if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_T16, g, st))) return rc;
     }
     {
       // 16-bit operands: the matrix-pipe kernel (64 queries per workgroup, K / V shared); fp32 mode and FLOAT_AUD_ATTN_MFMA=0: one wave per query
-      static const bool mfma_on = !(getenv("FLOAT_AUD_ATTN_MFMA") && atoi(getenv("FLOAT_AUD_ATTN_MFMA")) == 0);
+      const bool mfma_on = h->tune.attn_mfma;
       if constexpr (!T::is32) {
         if (mfma_on)
           hipLaunchKernelGGL((aud_attn_mfma_kernel<T>), dim3((Tn + 63) / 64, c.heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D,
@@ -437,7 +439,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
       g.sat = h->sat;
       g.out_f32 = h->y;
       g.ldo = D;
-      if ((rc = fmt_gemm_run(c.dtype, EPI_F32, g, st))) return rc;
+      if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_F32, g, st))) return rc;
     }
     // post-LN: h1 = layer_norm(h + attn);  stable: h1 = h + attn, operand = final_layer_norm(h1)
     if ((rc = ln(h->y, h->h, c.stable_ln ? Ly.ln2 : Ly.ln1, h->h1, h->hp16, c.stable_ln, nullptr, 0))) return rc;
@@ -446,14 +448,14 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
       g.sat = h->sat;
       g.out16 = reinterpret_cast<u16*>(h->hid16);
       g.ldo16 = Ly.ff2.K / 32;
-      if ((rc = fmt_gemm_run(c.dtype, EPI_GELUERF_P16, g, st))) return rc;
+      if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_GELUERF_P16, g, st))) return rc;
     }
     {
       GemmArgs g = fmt_gemm_args(reinterpret_cast<const u16*>(h->hid16), Ly.ff2, Tn);
       g.sat = h->sat;
       g.out_f32 = h->y;
       g.ldo = D;
-      if ((rc = fmt_gemm_run(c.dtype, EPI_F32, g, st))) return rc;
+      if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_F32, g, st))) return rc;
     }
     if (c.stable_ln) {
       // h = h1 + ffn; operand = next layer's layer_norm(h), or, after the last layer, h = encoder.layer_norm(h)
@@ -478,7 +480,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
     g.sat = h->sat;
     g.out_f32 = h->yproj;
     g.ldo = c.dim_w;
-    if ((rc = fmt_gemm_run(c.dtype, EPI_F32, g, st))) return rc;
+    if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_F32, g, st))) return rc;
     AudLnArgs n;
     memset(&n, 0, sizeof(n));
     n.sat = h->sat;
@@ -516,6 +518,8 @@ int float_aud_create(const float_aud_cfg_t* cfg, const float_tensor_t* tensors, 
   FH_REQUIRE(cfg->num_labels >= 0 && cfg->num_labels <= 64, "num_labels %d unsupported", cfg->num_labels);
   FH_REQUIRE(cfg->dtype == FLOAT_DT_BF16 || cfg->dtype == FLOAT_DT_FP16 || cfg->dtype == FLOAT_DT_FP32, "unknown dtype %d", cfg->dtype);
   float_aud* h = new float_aud();
+  h->gemm_tune = FmtTune::from_env();
+  h->tune = AudTune::from_env();
   h->cfg = *cfg;
   TensorTable tt(tensors, n_tensors);
   int rc = (cfg->dtype == FLOAT_DT_BF16) ? create_impl<BF16>(h, tt)

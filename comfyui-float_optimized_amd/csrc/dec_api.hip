@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "dec_kernels.hpp"
+#include "tuning.hpp"
 
 namespace {
 
@@ -65,7 +66,7 @@ struct float_dec {
   void* wfrag = nullptr;
   float* oflow = nullptr;
   unsigned long long* sat = nullptr;  // [kDecSatSites] saturation counters (dec_kernels.hpp), device
-  bool style_norm = true;
+  DecTune tune;  // the environment's switches as float_dec_create found them (tuning.hpp)
   float *loFlow[2] = {nullptr, nullptr}, *loRgb[2] = {nullptr, nullptr};
   float *hiFlow[2] = {nullptr, nullptr}, *hiRgb[2] = {nullptr, nullptr};
   // float_dec_frames_host, ride-along mode: the frames of the previous high batch still to be copied to the host by copy
@@ -298,10 +299,9 @@ int pack_styled(DevicePool* pool, const TensorTable& tt, const std::string& p, i
 
 // dynamic LDS above the 64 KiB default: 64 KiB per workgroup with 16-bit operands (2 workgroups per CU), twice that in the
 // fp32 verification mode (the z tile of dec_zblur_kernel: 32 x 32 x 128 B)
-static int env_int(const char* name, int dflt, int lo, int hi);
 template <class T>
-int raise_lds_limits() {
-  const int lim = std::max(32 * 1024 * T::EB, env_int("FLOAT_DEC_LDS_PAD", 0, 0, 160 * 1024));
+int raise_lds_limits(const DecTune& tn) {
+  const int lim = std::max(32 * 1024 * T::EB, tn.lds_pad);
 #define CONV16_ATTR(NTv, TYv, TXv) \
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_conv16_kernel<T, NTv, TYv, TXv>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   CONV16_ATTR(4, 3, 3) CONV16_ATTR(2, 3, 3)
@@ -448,9 +448,8 @@ int create_impl(float_dec* h, const TensorTable& tt) {
   if ((rc = alloc_elem<T>(&h->pool, &h->hiB, FH * act_hi))) return rc;
   if ((rc = alloc_elem<T>(&h->pool, &h->hiZ, FH * act_hi))) return rc;
   {
-    static const bool flow_epi = env_int("FLOAT_DEC_FLOW_EPI", 1, 0, 1) != 0;
     const int cl = h->levels.back().C;
-    if (flow_epi && (cl == 32 || cl == 64) && size >= 16 && size % 16 == 0) {
+    if (h->tune.flow_epi && (cl == 32 || cl == 64) && size >= 16 && size % 16 == 0) {
       if ((rc = alloc_elem<T>(&h->pool, &h->wfrag, FH * (size_t)(cl / 32) * (T::is32 ? 1 : 2) * 64 * 8))) return rc;
       if ((rc = h->pool.alloc(&h->oflow, FH * (size_t)size * size * 4, true))) return rc;
     }
@@ -462,62 +461,28 @@ int create_impl(float_dec* h, const TensorTable& tt) {
     if ((rc = h->pool.alloc(&h->hiFlow[i], sk_hi, true))) return rc;
     if ((rc = h->pool.alloc(&h->hiRgb[i], sk_hi, true))) return rc;
   }
-  return raise_lds_limits<T>();
+  return raise_lds_limits<T>(h->tune);
 }
 
-// Copy workgroups per carrying launch (a multiple of 8), the lowest resolution whose launches carry a share, and the pause
-// between a wave's 1-KiB stores in units of 512 clocks.  Unpaced, the copy saturates PCIe (55 GB/s) and its posted writes
-// queue in front of the compute workgroups' memory traffic: the 512-px flow launch took 665 us instead of 508 with a 217 us
-// copy inside; at ~45 GB/s (16 workgroups, pace 4) it takes 548 (in-kernel stamps, -DDEC_STAMPS).  Round 3: the launches got
-// shorter (flow kernel -35 %), pace 3 (~52 GB/s) leaves less of the last share exposed: 27.66 vs 28.03 ms per 250 frames.
-static int env_int(const char* name, int dflt, int lo, int hi) {  // tuning knobs: anything outside [lo, hi] falls back to the default
-  const char* v = getenv(name);
-  if (!v || !*v) return dflt;
-  char* end = nullptr;
-  const long x = strtol(v, &end, 10);
-  return (end && *end == 0 && x >= lo && x <= hi) ? (int)x : dflt;
-}
-// FLOAT_DEC_LDS_PAD=<bytes>: every launch of the level kernels (3x3 conv, up-conv + blur, flow) asks for at least that much dynamic
-// LDS, i.e. the decoder's occupancy is capped (82 000: ONE workgroup per CU instead of two - room for a 98-KB workgroup of the FMT
-// chain beside it when the two stages overlap on two streams, pipeline.generate_to_host_overlap).  0 = off.
-static const int kLdsPad = env_int("FLOAT_DEC_LDS_PAD", 0, 0, 160 * 1024);
-static inline size_t dec_smem(size_t need) { return std::max(need, (size_t)kLdsPad); }
-static const unsigned kRideWgs = (unsigned)env_int("FLOAT_DEC_RIDE_WGS", 16, 0, 64) / 8 * 8;
-static const int kRideMinRes = env_int("FLOAT_DEC_RIDE_MIN_RES", 64, 64, 512);
-static const unsigned kRidePace = (unsigned)env_int("FLOAT_DEC_RIDE_PACE", 3, 0, 64);
+// dynamic LDS of a level-kernel launch: what it needs, or the occupancy cap (DecTune::lds_pad) where that is more
+static inline size_t dec_smem(const DecTune& tn, size_t need) { return std::max(need, (size_t)tn.lds_pad); }
 
 // Weight of a carrying launch (kind 0 = up-conv + blur, 1 = conv2, 2 = flow / warp / ToRGB) at resolution R: the share of the
 // pending copy it takes is proportional to it, so that every share ends inside its launch (per 32-frame batch, ~us; other
 // resolutions: equal shares).
-static double ride_weight(int R, int kind) {
-  static const bool equal = getenv("FLOAT_DEC_RIDE_EQUAL") != nullptr;
-  if (equal) return 1.0;
-  // launch durations (tools/probes/trace_sequence.py on the round-3 kernels: {203,155,61},{178,175,118},{242,226,215},{318,256,336})
-  // shifted toward the flow launches, which absorb a share without getting longer while the 512-px convs are stretched by theirs
-  // (a trace of the carrying batch: +49 / +56 us there, +6 on the flow launch): 26.35 vs 26.80 ms per 250 frames decode + hand-over
-  // round 6 (launches now {178,142,52},{158,155,99},{220,206,175},{277,235,146}: the last level's flow launch is a third of what it
-  // was): decode + hand-over per 250 frames 25.1-25.3 ms with the row below against 26.4-26.9 with round 5's {..,{290,225,370}},
-  // 25.4 / 25.7 / 25.3 / 25.6 for four neighbours, 26.8 with equal shares (tools/probes/dec_host2.py, FLOAT_DEC_RIDE_W)
-  static double w[4][3] = {{170, 140, 50}, {170, 155, 100}, {220, 200, 180}, {300, 250, 120}};
-  static const bool tuned = [] {  // tuning aid: FLOAT_DEC_RIDE_W="12 numbers", rows 64 / 128 / 256 / 512 px x (up-conv, conv2, flow)
-    const char* e = getenv("FLOAT_DEC_RIDE_W");
-    double t[12];
-    if (e && sscanf(e, "%lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf %lf", t, t + 1, t + 2, t + 3, t + 4, t + 5, t + 6, t + 7, t + 8, t + 9, t + 10, t + 11) == 12)
-      for (int i = 0; i < 12; ++i)
-        if (t[i] > 0.0 && t[i] < 1e6) w[i / 3][i % 3] = t[i];
-    return true;
-  }();
-  (void)tuned;
+static double ride_weight(const DecTune& tn, int R, int kind) {
+  if (tn.ride_equal) return 1.0;
   const int li = R == 64 ? 0 : R == 128 ? 1 : R == 256 ? 2 : R == 512 ? 3 : -1;
-  return li < 0 ? 250.0 : w[li][kind];
+  return li < 0 ? 250.0 : tn.ride_w[li][kind];
 }
 
 // The share of the pending device-to-host copy that the next carrying launch takes.
 static CopyTail take_ride(float_dec* h, int R, int kind) {
   CopyTail ct{};
   auto& r = h->ride;
-  if (!r.left16 || r.wleft <= 0.0 || !kRideWgs || R < kRideMinRes) return ct;
-  const double w = ride_weight(R, kind);
+  const DecTune& tn = h->tune;
+  if (!r.left16 || r.wleft <= 0.0 || !tn.ride_wgs || R < tn.ride_min_res) return ct;
+  const double w = ride_weight(tn, R, kind);
   size_t n = (size_t)((double)r.left16 * std::min(1.0, w / r.wleft)) + 1;
   n = std::min(n, r.left16);
   r.wleft -= w;
@@ -525,12 +490,11 @@ static CopyTail take_ride(float_dec* h, int R, int kind) {
   ct.src = reinterpret_cast<const u32x4*>(r.src);
   ct.dst = reinterpret_cast<u32x4*>(r.dst);
   ct.n16 = n;
-  ct.nwg = kRideWgs;
-  ct.pace = kRidePace;
+  ct.nwg = tn.ride_wgs;
+  ct.pace = tn.ride_pace;
 #ifdef DEC_STAMPS  // diagnostic build only: probes that give wrong frames
-  static const int test = env_int("FLOAT_DEC_RIDE_TEST", 0, 0, 2);
-  if (test == 1) ct.dst = const_cast<u32x4*>(ct.src);  // device -> device instead of device -> host
-  if (test == 2) ct.n16 = 1;                            // copy workgroups with nothing to do
+  if (tn.ride_test == 1) ct.dst = const_cast<u32x4*>(ct.src);  // device -> device instead of device -> host
+  if (tn.ride_test == 2) ct.n16 = 1;                            // copy workgroups with nothing to do
 #endif
   r.src += n * 4;
   r.dst += n * 4;
@@ -539,13 +503,10 @@ static CopyTail take_ride(float_dec* h, int R, int kind) {
   return ct;
 }
 
-// FLOAT_DEC_CB_ORDER=0: output-channel blocks as grid.y (the round-1 order; A/B switch of dec_group_cb)
-static const bool g_dec_cb_order = !(getenv("FLOAT_DEC_CB_ORDER") && atoi(getenv("FLOAT_DEC_CB_ORDER")) == 0);
-
 // h != nullptr: the launch may carry a share of the pending device-to-host copy (16x16-tile kernel only)
 template <class T>
-int launch_conv(float_dec* h, const void* X, int Hi, int Wi, const Styled& s, const void* Wt, int ntaps, const int* dy, const int* dx,
-                void* Y, int Ho, int Wo, int OH, int OW, int sy, int sx, int py, int px, int F, const float* demod, int ldd,
+int launch_conv(const DecTune& tn, float_dec* h, const void* X, int Hi, int Wi, const Styled& s, const void* Wt, int ntaps, const int* dy,
+                const int* dx, void* Y, int Ho, int Wo, int OH, int OW, int sy, int sx, int py, int px, int F, const float* demod, int ldd,
                 const float* bias, int act, const float* snext, int lds, unsigned long long* sat, hipStream_t st,
                 const void* wfrag = nullptr, float* oflow = nullptr) {
   constexpr size_t RB = 32 * T::EB;
@@ -602,12 +563,9 @@ int launch_conv(float_dec* h, const void* X, int Hi, int Wi, const Styled& s, co
   FH_REQUIRE(npix * 4 <= 9 * 256, "conv halo tile too large (%d pixels)", npix);
   // Output channels per workgroup: 64 (NT = 4) in the 16x16-tile kernel where the layer has them - each A fragment feeds twice
   // the MFMAs (22.75 vs 23.10 ms per 250 frames since the kernel's address arithmetic went; before that the 32-channel tiles'
-  // doubled workgroup count won, 33.9 vs 35.2) - and 32 in the generic low-resolution kernel; FLOAT_DEC_CONV_BN /
-  // FLOAT_DEC_CONV_BN_LO = 32 | 64 are the A/B switches.
-  static const int bn_hi = env_int("FLOAT_DEC_CONV_BN", 64, 32, 64);
-  static const int bn_lo = env_int("FLOAT_DEC_CONV_BN_LO", 32, 32, 64);
+  // doubled workgroup count won, 33.9 vs 35.2) - and 32 in the generic low-resolution kernel (DecTune::conv_bn, conv_bn_lo).
   const bool tile16 = tdim == 16;
-  const int bn = (s.cout >= 64 && (tile16 ? bn_hi : bn_lo) == 64) ? 64 : 32;
+  const int bn = (s.cout >= 64 && (tile16 ? tn.conv_bn : tn.conv_bn_lo) == 64) ? 64 : 32;
   FH_REQUIRE(s.cout % bn == 0 && s.cin % 32 == 0, "conv channels (%d -> %d) not tileable", s.cin, s.cout);
   const int ty_taps = dymax - dymin + 1, tx_taps = dxmax - dxmin + 1;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -615,19 +573,16 @@ int launch_conv(float_dec* h, const void* X, int Hi, int Wi, const Styled& s, co
   if (tdim == 16 && ty_taps == 3 && tx_taps == 3 && ntaps == 9 && Ho % 16 == 0 && Wo % 16 == 0 && Ho == Hi && Wo == Wi) {
     // dense TY x TX window on 16x16 tiles: compile-time geometry, swizzled LDS, register prefetch
     const int total = g.tiles_x * g.tiles_y * F;
-    static const int tpw_env = env_int("FLOAT_DEC_TPW", 0, 0, 4096);  // tuning aid
-    g.tpw = tpw_env ? tpw_env : (total >= 16384 ? 4 : (total >= 4096 ? 2 : 1));
+    g.tpw = tn.tpw ? tn.tpw : (total >= 16384 ? 4 : (total >= 4096 ? 2 : 1));
     const size_t smem = (size_t)(15 + ty_taps) * (15 + tx_taps) * RB + (size_t)ntaps * bn * RB + 3 * bn * sizeof(float);  // halo, weights, epilogue operands
     if (h) g.ct = take_ride(h, Ho, 1);
     dim3 grid((total + g.tpw - 1) / g.tpw + g.ct.nwg, s.cout / bn);
-    if (g_dec_cb_order && s.cout / bn > 1) {  // channel blocks of a tile group side by side on one XCD (dec_group_cb)
+    if (tn.cb_order && s.cout / bn > 1) {  // channel blocks of a tile group side by side on one XCD (dec_group_cb)
       g.ngroups = (unsigned)((total + g.tpw - 1) / g.tpw);
       g.ncb = (unsigned)(s.cout / bn);
       grid = dim3(g.ngroups * g.ncb + g.ct.nwg, 1);
     }
-    // FLOAT_DEC_CONV_DB bit mask: 1 = double-buffered LDS for the 64-channel tiles, 2 = for the 32-channel tiles (A/B switch)
-    static const int db_env = env_int("FLOAT_DEC_CONV_DB", 0, 0, 3);
-    const bool db = !oflow && !T::is32 && ((bn == 64 && (db_env & 1)) || (bn == 32 && (db_env & 2)));
+    const bool db = !oflow && !T::is32 && ((bn == 64 && (tn.conv_db & 1)) || (bn == 32 && (tn.conv_db & 2)));
     FH_REQUIRE(!oflow || s.cout == bn, "ToFlow epilogue needs the layer's %d output channels in one block of %d", s.cout, bn);
 #define CONV16(NTv, TYv, TXv)                                                                                    \
   if (bn == NTv * 16 && ty_taps == TYv && tx_taps == TXv) {                                                       \
@@ -638,11 +593,11 @@ int launch_conv(float_dec* h, const void* X, int Hi, int Wi, const Styled& s, co
       }                                                                                                           \
     }                                                                                                             \
     if (!db && oflow) { /* ToFlow in the epilogue: the whole channel range in one block (cout == bn) */           \
-      if (prof) hipExtLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv, 0, 1>), grid, dim3(256), dec_smem(smem), st, e0, e1, 0, g); \
-      else hipLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv, 0, 1>), grid, dim3(256), dec_smem(smem), st, g); \
+      if (prof) hipExtLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv, 0, 1>), grid, dim3(256), dec_smem(tn, smem), st, e0, e1, 0, g); \
+      else hipLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv, 0, 1>), grid, dim3(256), dec_smem(tn, smem), st, g); \
     } else if (!db) {                                                                                             \
-      if (prof) hipExtLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv>), grid, dim3(256), dec_smem(smem), st, e0, e1, 0, g); \
-      else hipLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv>), grid, dim3(256), dec_smem(smem), st, g);     \
+      if (prof) hipExtLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv>), grid, dim3(256), dec_smem(tn, smem), st, e0, e1, 0, g); \
+      else hipLaunchKernelGGL((dec_conv16_kernel<T, NTv, TYv, TXv>), grid, dim3(256), dec_smem(tn, smem), st, g);     \
     }                                                                                                             \
   }
     CONV16(4, 3, 3) CONV16(2, 3, 3)
@@ -671,15 +626,13 @@ static const int kDy9[9] = {-1, -1, -1, 0, 0, 0, 1, 1, 1}, kDx9[9] = {-1, 0, 1, 
 // result lands in Zb: x_in may alias U), all four parity classes in one launch + blur kernel from 16 px up, class by class
 // through the generic kernel below.  h != nullptr: the fused launch may carry a share of the pending device-to-host copy.
 template <class T>
-int launch_upconv(float_dec* h, const Styled& up, int Ri, int n, const void* x_in, void* Zb, void* U, void** U_out,
+int launch_upconv(const DecTune& tn, float_dec* h, const Styled& up, int Ri, int n, const void* x_in, void* Zb, void* U, void** U_out,
                   const float* demod, int ldd, const float* snext, int lds, unsigned long long* sat, hipStream_t st) {
   typedef typename T::elem E;
   constexpr size_t RB = 32 * T::EB;
   const int R = 2 * Ri;
   int rc;
-  static const bool fuse_z = !getenv("FLOAT_DEC_NO_ZFUSE");
-  static const int zblur_min = env_int("FLOAT_DEC_ZBLUR_MIN", 64, 16, 4096);
-  if (R >= zblur_min && up.cout % 32 == 0 && up.cin % 32 == 0) {
+  if (R >= tn.zblur_min && up.cout % 32 == 0 && up.cin % 32 == 0) {
     ConvArgs z;
     memset(&z, 0, sizeof(z));
     z.X = x_in;
@@ -703,19 +656,19 @@ int launch_upconv(float_dec* h, const Styled& up, int Ri, int n, const void* x_i
     const bool prof = fh_prof_pair(1, &e0, &e1);
     if (h) z.ct = take_ride(h, R, 0);
     dim3 grid(z.tiles_x * z.tiles_y * n + z.ct.nwg, up.cout / 32);
-    if (g_dec_cb_order && up.cout / 32 > 1) {
+    if (tn.cb_order && up.cout / 32 > 1) {
       z.ngroups = (unsigned)(z.tiles_x * z.tiles_y * n);
       z.ncb = (unsigned)(up.cout / 32);
       grid = dim3(z.ngroups * z.ncb + z.ct.nwg, 1);
     }
     const size_t smem = 32 * 32 * RB;
-    if (prof) hipExtLaunchKernelGGL((dec_zblur_kernel<T>), grid, dim3(256), dec_smem(smem), st, e0, e1, 0, z);
-    else hipLaunchKernelGGL((dec_zblur_kernel<T>), grid, dim3(256), dec_smem(smem), st, z);
+    if (prof) hipExtLaunchKernelGGL((dec_zblur_kernel<T>), grid, dim3(256), dec_smem(tn, smem), st, e0, e1, 0, z);
+    else hipLaunchKernelGGL((dec_zblur_kernel<T>), grid, dim3(256), dec_smem(tn, smem), st, z);
     *U_out = Zb;
     FH_CHECK_HIP(hipGetLastError());
     return FLOAT_OK;
   }
-  if (Ri + 1 > 8 && up.cout % 32 == 0 && fuse_z) {
+  if (Ri + 1 > 8 && up.cout % 32 == 0 && !tn.no_zfuse) {
     ConvArgs z;
     memset(&z, 0, sizeof(z));
     z.X = x_in;
@@ -741,7 +694,7 @@ int launch_upconv(float_dec* h, const Styled& up, int Ri, int n, const void* x_i
     for (int pu = 0; pu < 2; ++pu)
       for (int pv = 0; pv < 2; ++pv) {
         const ClassTaps c = class_taps(pu, pv);
-        if ((rc = launch_conv<T>(nullptr, x_in, Ri, Ri, up, reinterpret_cast<const E*>(up.W) + t0 * up.cout * up.cin, c.n, c.dy, c.dx, Zb,
+        if ((rc = launch_conv<T>(tn, nullptr, x_in, Ri, Ri, up, reinterpret_cast<const E*>(up.W) + t0 * up.cout * up.cin, c.n, c.dy, c.dx, Zb,
                                  Ri + 1 - pu, Ri + 1 - pv, R + 1, R + 1, 2, 2, pu, pv, n, demod, ldd, nullptr, 0, nullptr, 0, sat, st)))
           return rc;
         t0 += c.n;
@@ -760,29 +713,27 @@ int launch_upconv(float_dec* h, const Styled& up, int Ri, int n, const void* x_i
 // Grid: ~2048 workgroups in total (8 per CU) so that every lane group runs many pixel iterations and the per-workgroup
 // prologue (56 per-lane weight values) is amortised; one row of workgroups per frame.
 template <class T>
-int launch_flow(float_dec* h, FlowArgs g, hipStream_t st) {
+int launch_flow(const DecTune& tn, float_dec* h, FlowArgs g, hipStream_t st) {
   if (g.oflow) {  // one lane per pixel (dec_flowlast_kernel)
     const int runs = (g.R * g.R + 255) / 256;
     if (h) g.ct = take_ride(h, g.R, 2);
-    const size_t lpad = (size_t)kLdsPad;
+    const size_t lpad = (size_t)tn.lds_pad;
     hipLaunchKernelGGL((dec_flowlast_kernel<T>), dim3(runs * g.F + g.ct.nwg), dim3(256), lpad, st, g);
     FH_CHECK_HIP(hipGetLastError());
     return FLOAT_OK;
   }
   const int R = g.R, n = g.F;
   const int lpp = g.C / 8, gpb = 256 / lpp;
-  static const int pix_env = env_int("FLOAT_DEC_FLOW_PIX", 0, 0, 4);  // tuning aid
-  const int pix = (pix_env == 1 || pix_env == 2 || pix_env == 4) ? pix_env : (lpp <= 8 ? 4 : 2);
+  const int pix = (tn.flow_pix == 1 || tn.flow_pix == 2 || tn.flow_pix == 4) ? tn.flow_pix : (lpp <= 8 ? 4 : 2);
   const int step = gpb * pix;  // pixels one workgroup covers per iteration
   const int max_bx = (R * R + step - 1) / step;
-  static const int wg_env = env_int("FLOAT_DEC_FLOW_WGS", 2048, 8, 1 << 20);
-  int bx = std::max(1, std::min(max_bx, (wg_env + n - 1) / n));
+  int bx = std::max(1, std::min(max_bx, (tn.flow_wgs + n - 1) / n));
   if (bx >= 8) bx &= ~7;  // bands in multiples of 8: band <-> XCD affinity (dec_flow_kernel)
   g.band_pix = ((R * R + bx - 1) / bx + step - 1) / step * step;
   g.nbands = bx = (R * R + g.band_pix - 1) / g.band_pix;
   if (h) g.ct = take_ride(h, R, 2);
   // dynamic LDS only as an occupancy cap (FLOAT_DEC_LDS_PAD); the kernel's own 14 KB are static
-  const size_t pad = kLdsPad > 14 * 1024 ? (size_t)kLdsPad - 14 * 1024 : 0;
+  const size_t pad = tn.lds_pad > 14 * 1024 ? (size_t)tn.lds_pad - 14 * 1024 : 0;
   const dim3 grid(bx * n + g.ct.nwg);
 #define FLOW_LAUNCH(PIXv)                                                                                  \
   if (g.xnext) hipLaunchKernelGGL((dec_flow_kernel<T, PIXv, false>), grid, dim3(256), pad, st, g);         \
@@ -806,7 +757,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
   const Styled& c2 = h->convs[2 + 2 * li];
   const int R = L.R;
   int rc;
-  if ((rc = launch_upconv<T>(h, up, R / 2, n, x_in, Zb, U, &U, demod + up.demod_off, h->Dtot, styles + c2.style_off, h->Stot,
+  if ((rc = launch_upconv<T>(h->tune, h, up, R / 2, n, x_in, Zb, U, &U, demod + up.demod_off, h->Dtot, styles + c2.style_off, h->Stot,
                              h->sat + 1 + 2 * li, st)))
     return rc;
   // conv2 (plain 3x3); its unscaled output feeds ToFlow.  (Running the flow phase in conv2's epilogue at C <= 64 - the conv2
@@ -820,7 +771,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
     hipLaunchKernelGGL((dec_flowfrag_kernel<T>), dim3(n, c2.cout / 32), dim3(64), 0, st, reinterpret_cast<P8*>(h->wfrag), L.wflow,
                        styles + L.style_off, h->Stot, L.C);
   }
-  if ((rc = launch_conv<T>(h, U, R, R, c2, c2.W, 9, kDy9, kDx9, V, R, R, R, R, 1, 1, 0, 0, n, demod + c2.demod_off, h->Dtot,
+  if ((rc = launch_conv<T>(h->tune, h, U, R, R, c2, c2.W, 9, kDy9, kDx9, V, R, R, R, R, 1, 1, 0, 0, n, demod + c2.demod_off, h->Dtot,
                            c2.abias, 1, nullptr, 0, h->sat + 2 + 2 * li, st, epi ? h->wfrag : nullptr, epi ? h->oflow : nullptr)))
     return rc;
   FlowArgs g;
@@ -845,7 +796,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
   g.rgb_out = rgb_cur;
   g.final_out = last ? final_out : nullptr;
   g.final_mode = last ? final_mode : 0;
-  g.write_pyr = (!last || getenv("FLOAT_DEC_WRITE_PYR")) ? 1 : 0;
+  g.write_pyr = (!last || h->tune.write_pyr) ? 1 : 0;
   g.F = n;
   g.R = R;
   g.C = L.C;
@@ -858,7 +809,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
     FH_CHECK_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dec_stamps), init, sizeof(init), 0, hipMemcpyHostToDevice, st));
   }
 #endif
-  return launch_flow<T>(h, g, st);
+  return launch_flow<T>(h->tune, h, g, st);
 }
 
 // Low phase for `n` frames (n <= lo_frames): constant input, conv1, levels 8..32.  Leaves the
@@ -871,7 +822,7 @@ int run_low(float_dec* h, int n, const float* styles, const float* demod, int* s
   hipLaunchKernelGGL((dec_input_kernel<T>), dim3((tot + 255) / 256), dim3(256), 0, st, reinterpret_cast<typename T::elem*>(h->loB),
                      h->cin_hwc, styles + c1.style_off, h->Stot, n, 16, c1.cin, h->sat + 32);
   void* first_out = h->lo_levels > 0 ? h->loA : h->loX;
-  if ((rc = launch_conv<T>(nullptr, h->loB, 4, 4, c1, c1.W, 9, kDy9, kDx9, first_out, 4, 4, 4, 4, 1, 1, 0, 0, n, demod + c1.demod_off,
+  if ((rc = launch_conv<T>(h->tune, nullptr, h->loB, 4, 4, c1, c1.W, 9, kDy9, kDx9, first_out, 4, 4, 4, 4, 1, 1, 0, 0, n, demod + c1.demod_off,
                            h->Dtot, c1.abias, 1, styles + h->convs[1].style_off, h->Stot, h->sat + 0, st)))
     return rc;
   int cur = 0;
@@ -926,21 +877,20 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
                 float* host = nullptr, hipStream_t cs = nullptr, float* host_dev = nullptr) {
   const int S = h->cfg.size, sdim = h->cfg.style_dim, FH = h->cfg.max_frames, FL = h->lo_frames;
   size_t n_copy = 0;
+  const DecTune& tn = h->tune;
   // same-stream hand-over: copy workgroups ride along the next batch's launches unless FLOAT_DEC_COPY=memcpy
-  static const bool ride_on = !(getenv("FLOAT_DEC_COPY") && !strcmp(getenv("FLOAT_DEC_COPY"), "memcpy"));
   // the copy workgroups store straight through `host`: only when it is device-accessible (pinned / registered) host memory
   // (host_dev = its device-side address); a pageable destination takes the hipMemcpyAsync path, batch by batch, in order
-  const bool ride = host_dev && cs == st && ride_on && (((size_t)S * S * 3 * sizeof(float)) % 16 == 0) &&
+  const bool ride = host_dev && cs == st && !tn.copy_memcpy && (((size_t)S * S * 3 * sizeof(float)) % 16 == 0) &&
                     ((uintptr_t)host_dev % 16 == 0) && ((uintptr_t)out % 16 == 0);
   h->ride.left16 = 0;
   h->ride.wleft = 0.0;
   // Ragged clips put their SHORT piece first at every level (style chunk, low group, high batch): the last batch of the call is
   // then a full one.  A short last batch carried the previous full batch's copy in launches too short for it (its launches took
   // as long as a full batch's) and the short first batch carries nothing.  FLOAT_DEC_SHORT_FIRST=0: remainder last.
-  static const bool short_first = env_int("FLOAT_DEC_SHORT_FIRST", 1, 0, 1) != 0;
-  auto piece = [](int done, int total, int cap) {
+  auto piece = [&tn](int done, int total, int cap) {
     const int r = total % cap;
-    return (short_first && done == 0 && r) ? r : std::min(cap, total - done);
+    return (tn.short_first && done == 0 && r) ? r : std::min(cap, total - done);
   };
   for (int s0 = 0, ns = 0; s0 < n_frames; s0 += ns) {
     ns = piece(s0, n_frames, kStyleCap);
@@ -966,7 +916,7 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
       d.ld_s = h->Stot;
       d.ld_d = h->Dtot;
       d.F = ns;
-      d.normalise = h->style_norm ? 1 : 0;
+      d.normalise = tn.style_norm ? 1 : 0;
       d.sat = h->sat;
       // every StyledConv's style divided by its max |s| per frame, eps / max^2 left for the demodulation (dec_kernels.hpp)
       hipLaunchKernelGGL(dec_style_norm_kernel, dim3((unsigned)h->convs.size(), ns), dim3(256), 0, st, d);
@@ -985,16 +935,16 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
         // ride-along hand-over: the very last batch of the call has no successor to carry its copy.  Cutting it in two so that
         // only FLOAT_DEC_RIDE_TAIL frames' copy stays exposed was measured and is off: 30.1 ms per 250 frames without, 31.0-31.8
         // with a tail of 4..16 frames (the smaller launches lose more than the shorter copy gains)
-        static const int tail = getenv("FLOAT_DEC_RIDE_TAIL") ? atoi(getenv("FLOAT_DEC_RIDE_TAIL")) : 0;
+        const int tail = tn.ride_tail;
         const bool last_of_call = (s0 + a0 + b0 + nb == n_frames);
         if (host && ride && last_of_call && tail > 0 && nb > tail) nb -= tail;
         const size_t off = (size_t)(s0 + a0 + b0) * S * S * 3;
         if (host && ride) {
-          // launches of this batch that carry a share: up-conv, conv2 and flow kernel of every level from kRideMinRes up
+          // launches of this batch that carry a share: up-conv, conv2 and flow kernel of every level from ride_min_res up
           double wsum = 0.0;
           for (int li = h->lo_levels; li < h->n_levels; ++li)
-            if (h->levels[li].R >= kRideMinRes)
-              for (int kind = 0; kind < 3; ++kind) wsum += ride_weight(h->levels[li].R, kind);
+            if (h->levels[li].R >= tn.ride_min_res)
+              for (int kind = 0; kind < 3; ++kind) wsum += ride_weight(tn, h->levels[li].R, kind);
           h->ride.wleft = h->ride.left16 ? wsum : 0.0;
         }
         rc = run_high<T>(h, nb, b0, st_a + (size_t)b0 * h->Stot, dm_a + (size_t)b0 * h->Dtot, skip_idx, out + off, final_mode, st);
@@ -1099,8 +1049,9 @@ int unit_styled_conv(const float_dec_unit_t* cfg, const TensorTable& tt, const f
   const int cin = cfg->cin, cout = cfg->cout, Ri = cfg->res, F = cfg->n_frames, sdim = cfg->style_dim;
   const int Ro = cfg->upsample ? 2 * Ri : Ri;
   UnitCtx u;
+  const DecTune tn = DecTune::from_env();  // no handle: the switches as this call finds them
   int rc;
-  if ((rc = raise_lds_limits<T>())) return rc;
+  if ((rc = raise_lds_limits<T>(tn))) return rc;
   Styled s;
   std::vector<float> wm_rows, bm_host;
   if ((rc = pack_styled<T>(&u.pool, tt, "sc", cin, cout, cfg->upsample != 0, &s, &wm_rows, &bm_host, sdim))) return rc;
@@ -1136,9 +1087,9 @@ int unit_styled_conv(const float_dec_unit_t* cfg, const TensorTable& tt, const f
                      Ri * Ri, sat);
   void* Y = U;
   if (cfg->upsample) {
-    if ((rc = launch_upconv<T>(nullptr, s, Ri, F, X, Z, U, &Y, demod, cout, ones, cout, sat, st))) return rc;
+    if ((rc = launch_upconv<T>(tn, nullptr, s, Ri, F, X, Z, U, &Y, demod, cout, ones, cout, sat, st))) return rc;
   } else {
-    if ((rc = launch_conv<T>(nullptr, X, Ri, Ri, s, s.W, 9, kDy9, kDx9, U, Ri, Ri, Ri, Ri, 1, 1, 0, 0, F, demod, cout, s.abias, 1, nullptr,
+    if ((rc = launch_conv<T>(tn, nullptr, X, Ri, Ri, s, s.W, 9, kDy9, kDx9, U, Ri, Ri, Ri, Ri, 1, 1, 0, 0, F, demod, cout, s.abias, 1, nullptr,
                              0, sat, st)))
       return rc;
   }
@@ -1232,7 +1183,7 @@ int unit_flow_level(const float_dec_unit_t* cfg, const TensorTable& tt, const fl
   g.C = C;
   g.ld_s = C;
   g.sat = sat;
-  if ((rc = launch_flow<T>(nullptr, g, st))) return rc;
+  if ((rc = launch_flow<T>(DecTune::from_env(), nullptr, g, st))) return rc;
   if (out_flow) hipLaunchKernelGGL(dec_dbg_pyr_kernel, dim3((F * R * R + 255) / 256), dim3(256), 0, st, out_flow, fo, F, R * R, 1);
   if (out_rgb) hipLaunchKernelGGL(dec_dbg_pyr_kernel, dim3((F * R * R + 255) / 256), dim3(256), 0, st, out_rgb, ro, F, R * R, 1);
   if (out_blend)
@@ -1258,8 +1209,8 @@ int float_dec_create(const float_dec_cfg_t* cfg, const float_tensor_t* tensors, 
   FH_REQUIRE(cfg->dtype == FLOAT_DT_FP16 || cfg->dtype == FLOAT_DT_FP32,
              "the decoder supports FLOAT_DT_FP16 operands (and FLOAT_DT_FP32 for verification) only (got dtype %d)", cfg->dtype);
   float_dec* h = new float_dec();
+  h->tune = DecTune::from_env();
   h->cfg = *cfg;
-  h->style_norm = env_int("FLOAT_DEC_STYLE_NORM", 1, 0, 1) != 0;
   TensorTable tt(tensors, n_tensors);
   int rc = DEC_DISPATCH(cfg->dtype, create_impl<T>(h, tt));
   if (!rc) {

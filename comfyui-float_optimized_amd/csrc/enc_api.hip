@@ -5,6 +5,7 @@
 
 #include "dec_kernels.hpp"  // dec_conv16_kernel: the LDS-staged 3x3 conv of the decoder, used for the ResBlocks' conv1
 #include "enc_kernels.hpp"
+#include "tuning.hpp"
 
 namespace {
 
@@ -30,6 +31,7 @@ struct FcLayer {
 
 struct float_enc {
   float_enc_cfg_t cfg;
+  EncTune tune;
   DevicePool pool;
   int C0 = 0;
   float *w0 = nullptr, *b0 = nullptr;  // convs.0: [C0][3] scaled, [C0]
@@ -342,8 +344,7 @@ int forward_impl(float_enc* h, const float* img, float* s_r, float* lam, float* 
     }
     if ((rc = launch_conv<T>(B.skip, h->tb, R - 1, R - 1, 2, 0, h->tsk, nullptr, nullptr, st, h->sat))) return rc;
     // conv1 3x3 + act; conv2: Blur pad (2,2) -> 3x3 stride 2 + act; (out + skip) / sqrt(2)
-    static const bool tiles_on = !getenv("FLOAT_ENC_NO_TILES");
-    if (tiles_on && R >= 16 && B.conv1.cin % 32 == 0 && B.conv1.cout % 32 == 0) rc = launch_conv3x3_tiles<T>(h, B.conv1, x, R, h->t1, st);
+    if (!h->tune.no_tiles && R >= 16 && B.conv1.cin % 32 == 0 && B.conv1.cout % 32 == 0) rc = launch_conv3x3_tiles<T>(h, B.conv1, x, R, h->t1, st);
     else rc = launch_conv<T>(B.conv1, x, R, R, 1, 1, h->t1, nullptr, nullptr, st, h->sat);
     if (rc) return rc;
     {
@@ -399,6 +400,7 @@ int float_enc_create(const float_enc_cfg_t* cfg, const float_tensor_t* tensors, 
   FH_REQUIRE(cfg->dim > 0 && cfg->dim % 32 == 0 && cfg->dim_motion > 0 && cfg->dim_motion <= cfg->dim, "bad dim / dim_motion");
   FH_REQUIRE(cfg->dtype == FLOAT_DT_BF16 || cfg->dtype == FLOAT_DT_FP16 || cfg->dtype == FLOAT_DT_FP32, "unknown dtype %d", cfg->dtype);
   float_enc* h = new float_enc();
+  h->tune = EncTune::from_env();
   h->cfg = *cfg;
   TensorTable tt(tensors, n_tensors);
   int rc = (cfg->dtype == FLOAT_DT_BF16) ? create_impl<BF16>(h, tt)

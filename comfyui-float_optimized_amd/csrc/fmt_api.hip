@@ -36,9 +36,8 @@ struct float_fmt {
   float* slab = nullptr;  // [8][Mpad][D] split-K partial sums (EPI_PARTIAL; the fused attention + proj launch writes one slab per head)
   float *wa_c, *we_c, *prev_x, *prev_wa, *prev_we, *x0_c;
   int method = 0;          // FLOAT_ODE_*
-  int attnproj = 0;        // heads per workgroup of the fused attention + proj launch (FLOAT_FMT_ATTNPROJ), 0 = two launches
-  // the step chain of one evaluation as ONE persistent kernel (fmt_mega_kernel): stage table per CFG shape, barrier words
-  int mega_on = 0;         // FLOAT_FMT_MEGA=1 selects it; default 0 = the 59-launch chain (faster: fmt_kernels.hpp, fmt_mega_kernel)
+  FmtTune tune;            // the environment's switches as float_fmt_create found them (tuning.hpp)
+  // the step chain of one evaluation as ONE persistent kernel (fmt_mega_kernel, tune.mega): stage table per CFG shape, barrier words
   int n_cu = 0;
   struct MegaPlan {
     MegaStage* dev = nullptr;
@@ -119,14 +118,14 @@ __global__ __launch_bounds__(256) void fmt_pack_w_kernel(typename T::elem* __res
 }
 
 template <class T>
-int pack_linear_pool(DevicePool* pool, const TensorTable& tt, const std::vector<std::string>& names, int N_each, int K,
-                     Lin* out) {
+int pack_linear_pool(const FmtTune& tn, DevicePool* pool, const TensorTable& tt, const std::vector<std::string>& names, int N_each,
+                     int K, Lin* out) {
   // Concatenate the named Linear layers along N (used to fuse every adaLN projection into one GEMM).
   typedef typename T::elem E;
   constexpr size_t esz = sizeof(E) / sizeof(u16);  // u16 slots per element (Lin::W is typed u16* for every operand type)
   const int Kp = round_up(K, 128);
   const int N = N_each * (int)names.size();
-  static const bool on_host = getenv("FLOAT_PACK_HOST") && atoi(getenv("FLOAT_PACK_HOST")) != 0;
+  const bool on_host = tn.pack_host;
   std::vector<E> hw;
   if (on_host) hw.assign((size_t)N * Kp, (E)0);
   std::vector<float> hb(N, 0.f);
@@ -180,12 +179,11 @@ int pack_linear_pool(DevicePool* pool, const TensorTable& tt, const std::vector<
 
 template <class T>
 int pack_linear(float_fmt* h, const TensorTable& tt, const std::vector<std::string>& names, int N_each, int K, Lin* out) {
-  return pack_linear_pool<T>(&h->pool, tt, names, N_each, K, out);
+  return pack_linear_pool<T>(h->tune, &h->pool, tt, names, N_each, K, out);
 }
 
 constexpr int kWtRows = 256;  // LayerNorm / attention launches of at most this many rows store write-through (common.hpp, FMT_WT)
-// Wide-N path (fused adaLN projection): LDS-staged A, 128 columns per workgroup.
-int g_fmt_wide_variant = 7;  // FLOAT_FMT_WIDE_VARIANT: 6 / 7 = LDS-DMA 192 x 320 tile where the shape allows (else 2): lock step / wave rows half a step apart; register-staged 192 x 128 family: 0 = 96 rows x 4 k-blocks per chunk, 1 = 96 x 2, 2 = 192 x 2, 3 = 192 x 4, 4 / 5 = 8 waves
+// Wide-N path (fused adaLN projection): LDS-staged A, 128 columns per workgroup (FmtTune::wide_variant picks the kernel).
 template <class T, int MTW, int KCH, int NWV = 4>
 int launch_wide_t(GemmArgs g, bool prime, hipStream_t s) {
   constexpr int smem = 2 * MTW * KCH * 1024;
@@ -240,11 +238,10 @@ bool dma_shape_ok(const GemmArgs& g, int bn) { return g.N % bn == 0 && g.K % 64 
 // (fmt_big_kernels.hpp), one workgroup per CU.  N in column blocks of 256, eight of them per XCD group; an even number (>= 4) of
 // k-blocks (the K loop is unrolled by two behind four peeled steps).  Bitwise the numbers of fmt_gemm_dma_kernel.
 // FLOAT_FMT_BIG=0 keeps the one-tile-per-workgroup kernels on rows padded per evaluation (the A/B switch).
-int g_fmt_big = 1;
 constexpr int kBigMinRows = 1536;  // below 8 row blocks the padded layout's kernels stay (a single evaluation: 180 rows)
 constexpr int kBigSmem = 4 * 28 * 1024 + 4 * 4096;
-bool big_shape_ok(int rows_total, int N, int K, int n_cu) {
-  return g_fmt_big && rows_total >= kBigMinRows && N % 2048 == 0 && K % 64 == 0 && K >= 128 && n_cu >= 8;
+bool big_shape_ok(const FmtTune& tn, int rows_total, int N, int K, int n_cu) {
+  return tn.big && rows_total >= kBigMinRows && N % 2048 == 0 && K % 64 == 0 && K >= 128 && n_cu >= 8;
 }
 template <class T>
 int launch_big4(const u16* A, const FmtLin& L, float* out, int rows_total, int ldo, int n_cu, bool prime, hipStream_t s) {
@@ -269,7 +266,7 @@ int launch_big4(const u16* A, const FmtLin& L, float* out, int rows_total, int l
 }
 
 template <class T>
-int launch_wide(const GemmArgs& g, bool prime, hipStream_t s) {
+int launch_wide(const GemmArgs& g, int variant, bool prime, hipStream_t s) {
   const int mt = (g.M + 15) / 16;
   if (prime) {
     (void)launch_big4<T>(nullptr, FmtLin{}, nullptr, 0, 0, 0, true, s);
@@ -285,13 +282,13 @@ int launch_wide(const GemmArgs& g, bool prime, hipStream_t s) {
     (void)launch_wide_t<T, 12, 4, 8>(g, true, s);
     return FLOAT_OK;
   }
-  if (g_fmt_wide_variant == 6 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 0>(g, false, s);
-  if (g_fmt_wide_variant == 7 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 1>(g, false, s);
+  if (variant == 6 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 0>(g, false, s);
+  if (variant == 7 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 1>(g, false, s);
   if (mt <= 4) return launch_wide_t<T, 4, 4>(g, false, s);
   // 192-row blocks also for the stacked clips of a batch (mt > 12): the last block reads up to 11 row tiles past the batch (the
   // operand buffers are padded for it, the rows are never stored); 80-row blocks ran the batched projection at 240 TFLOP/s
   // against 700 for 192-row ones
-  const int variant = (g_fmt_wide_variant == 6 || g_fmt_wide_variant == 7) ? 2 : g_fmt_wide_variant;  // shapes the LDS-DMA tile does not take
+  if (variant == 6 || variant == 7) variant = 2;  // shapes the LDS-DMA tile does not take
   if (mt <= 12 || variant == 2 || variant >= 4) {
     switch (variant) {
       case 1: return launch_wide_t<T, 6, 2>(g, false, s);
@@ -304,7 +301,6 @@ int launch_wide(const GemmArgs& g, bool prime, hipStream_t s) {
   }
   return launch_wide_t<T, 5, 4>(g, false, s);
 }
-bool g_fmt_wide = true;  // FLOAT_FMT_WIDE=0 falls back to the generic tiling (A/B measurement)
 
 // ---- GEMM instantiation table: (row tiles, column tiles, waves splitting K) per workgroup ----
 template <class T, int MTW, int NT, int NW, int EPI>
@@ -416,27 +412,23 @@ int launch_rbs(const GemmArgs& g, int shape, bool prime, hipStream_t s) {
 //   2880    53.7 -> 31.7 (192x128) 22.2 -> 15.7 (192x128 /2) 74.5 -> 43.3 (192x128) 71.8 -> 39.1 (192x128)
 // FLOAT_FMT_RB=0 keeps the 48 x 64 tiling (the A/B switch); FLOAT_FMT_RB_QKV / _PROJ / _FC1 / _FC2 = "shape[,ksplit]" override.
 constexpr int kRbMinRows = 300;
-int g_fmt_rb = 1;
 struct RbPlan {
   int shape = -1, ksplit = 1;  // shape < 0: the weight-streaming tiling
 };
-enum { RB_QKV = 0, RB_PROJ, RB_FC1, RB_FC2 };
-RbPlan pick_rb(int layer, int M) {
-  static const char* const envs[4] = {"FLOAT_FMT_RB_QKV", "FLOAT_FMT_RB_PROJ", "FLOAT_FMT_RB_FC1", "FLOAT_FMT_RB_FC2"};
+RbPlan pick_rb(const FmtTune& tn, int layer, int M) {
   RbPlan p;
-  if (!g_fmt_rb || M < kRbMinRows) return p;
+  if (!tn.rb || M < kRbMinRows) return p;
   const int tier = M < 540 ? 0 : (M < 1100 ? 1 : (M < 2200 ? 2 : 3));
   static const int shapes[4][4] = {/* qkv */ {0, 1, 0, 2}, /* proj */ {-1, 0, 0, 2}, /* fc1 */ {0, 1, 2, 2}, /* fc2 */ {0, 1, 2, 2}};
   p.shape = shapes[layer][tier];
   // fc2: 4 K slices fill the CUs up to 1440 rows; from 2200 rows on 2 slices do (15 x 8 tiles x 2) and halve the fp32 slabs the
   // next LayerNorm folds (16 clips: 415.7 vs 438.6 ms per 250 evaluations; 8 clips the other way round: 251.6 vs 241.9)
   p.ksplit = layer == RB_PROJ ? 2 : (layer == RB_FC2 ? (tier == 3 ? 2 : 4) : 1);
-  if (const char* e = getenv(envs[layer])) {
-    int sh = p.shape, ks = p.ksplit;
-    if (sscanf(e, "%d,%d", &sh, &ks) >= 1) {
-      p.shape = sh;
-      if (layer == RB_PROJ || layer == RB_FC2) p.ksplit = (ks == 1 || ks == 2 || ks == 4 || ks == 8) ? ks : p.ksplit;
-    }
+  const FmtTune::Rb& o = tn.rb_layer[layer];
+  if (o.n >= 1) {
+    p.shape = o.shape;
+    const int ks = o.ksplit;
+    if (o.n >= 2 && (layer == RB_PROJ || layer == RB_FC2) && (ks == 1 || ks == 2 || ks == 4 || ks == 8)) p.ksplit = ks;
   }
   return p;
 }
@@ -477,7 +469,7 @@ void prime_kernels() {
   if constexpr (!T::is32) {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
-    (void)launch_wide<T>(g, true, nullptr);
+    (void)launch_wide<T>(g, 0, true, nullptr);
     (void)launch_rbs<T, EPI_T16>(g, 0, true, nullptr);
     (void)launch_rbs<T, EPI_GELU_P16>(g, 0, true, nullptr);
     (void)launch_rbs<T, EPI_PARTIAL>(g, 0, true, nullptr);
@@ -491,8 +483,6 @@ void prime_kernels() {
 struct Tiling {
   int mtw, nt, nw;
 };
-int g_fmt_full_nw = 8;  // FLOAT_FMT_FULL_NW: waves of the full-height (CFG epilogue) tiling
-int g_fmt_plan_override[6] = {0, 0, 0, 0, 0, 0};  // FLOAT_FMT_PLAN="mtw,nt,nw (narrow), mtw,nt,nw (wide)": tuning aid
 int pick_nw(int K, int forced) {
   const int KB = K / 32;
   if (forced && KB % forced == 0) return forced;
@@ -500,20 +490,20 @@ int pick_nw(int K, int forced) {
   if (KB >= 32 && KB % 8 == 0) return 8;
   return 4;
 }
-Tiling pick_tiling(int M, int N, int K, bool need_full_rows) {
+Tiling pick_tiling(const FmtTune& tn, int M, int N, int K, bool need_full_rows) {
   const int mt = (M + 15) / 16;
   if (need_full_rows) {
     if (mt <= 4) return {4, 1, pick_nw(K, 0)};
     // 16 columns per workgroup: twice the workgroups of the 32-column tile; 8 K-splitting waves keep twice
     // the operand bytes in flight (each of the 32 workgroups streams the whole 393 KB activation operand)
-    return {mt <= 12 ? 12 : 15, 1, (g_fmt_full_nw == 8 && (K / 32) % 8 == 0) ? 8 : 4};
+    return {mt <= 12 ? 12 : 15, 1, (tn.full_nw == 8 && (K / 32) % 8 == 0) ? 8 : 4};
   }
   int split = mt <= 4 ? 4 : (mt <= 12 ? 3 : 5);
   if (mt <= 2) split = mt;
   const int blocks = (mt + split - 1) / split;
   const bool wide = N >= 16384;  // the fused adaLN projection
   if (mt >= 12) {  // tuning overrides only apply to the CFG-batched shapes (buffers hold 240 rows)
-    const int* o = g_fmt_plan_override + (wide ? 3 : 0);
+    const int* o = tn.plan + (wide ? 3 : 0);
     if (o[0]) {
       int nw = o[0] >= 12 ? 4 : pick_nw(K, o[2]);
       while (nw > 4 && nw * o[0] * 16 * o[1] * 16 * 4 > 160 * 1024) nw >>= 1;
@@ -557,17 +547,9 @@ Tiling pick_tiling32(int M) {
   return {mt <= 5 ? mt : (mt <= 12 ? 3 : 5), 1, 4};
 }
 
-// Per-layer tiling overrides of the one-clip chain (tuning aid): FLOAT_FMT_PLAN_QKV / _PROJ / _FC1 / _FC2 = "mtw,nt,nw".
-struct LayerPlan {
-  int v[3] = {0, 0, 0};
-  explicit LayerPlan(const char* env) {
-    if (const char* e = getenv(env)) sscanf(e, "%d,%d,%d", &v[0], &v[1], &v[2]);
-  }
-  bool on() const { return v[0] > 0; }
-};
-
+// plan: a per-layer tiling override of the one-clip chain (FmtTune::plan_layer, tuning aid)
 template <class T, int EPI>
-int run_gemm(const GemmArgs& g, hipStream_t s, bool need_full_rows = false, const LayerPlan* plan = nullptr) {
+int run_gemm(const FmtTune& tn, const GemmArgs& g, hipStream_t s, bool need_full_rows = false, const LayerPlan* plan = nullptr) {
   if constexpr (T::is32) {
     FH_REQUIRE(!need_full_rows, "the fp32 mode has no all-rows CFG epilogue tiling (token-blocked head only)");
     const Tiling t = pick_tiling32(g.M);
@@ -580,15 +562,13 @@ int run_gemm(const GemmArgs& g, hipStream_t s, bool need_full_rows = false, cons
     g2.touch.W = nullptr;  // the touch descriptors follow the default block decode
     return launch_gemm<T, EPI>(g2, plan->v[0], plan->v[1], plan->v[2], false, s);
   }
-  const Tiling t = pick_tiling(g.M, g.N, g.K, need_full_rows);
+  const Tiling t = pick_tiling(tn, g.M, g.N, g.K, need_full_rows);
   return launch_gemm<T, EPI>(g, t.mtw, t.nt, t.nw, false, s);
 }
 
 // Split-K GEMM whose gated residual add happens in the next LayerNorm launch (EPI_PARTIAL + LnRed).
 // The tiling is the one a GEMM with ksplit * N columns and K / ksplit would get: same workgroup
-// count, a fraction of the activation bytes per workgroup.
-int g_fmt_fc2_split = 4;   // FLOAT_FMT_FC2_SPLIT: K slices of mlp.fc2 (0 = in-GEMM gate*residual epilogue)
-int g_fmt_proj_split = 0;  // FLOAT_FMT_PROJ_SPLIT: same for attn.proj
+// count, a fraction of the activation bytes per workgroup (FmtTune::fc2_split, proj_split).
 struct PendingRed {
   int ks = 0;
   LnRed red{};
@@ -604,7 +584,7 @@ int run_gemm_partial(float_fmt* h, GemmArgs g, int ksplit, hipStream_t s, const 
     g.touch.W = nullptr;
     return launch_gemm<T, EPI_PARTIAL>(g, plan->v[0], plan->v[1], plan->v[2], false, s);
   }
-  Tiling t = T::is32 ? pick_tiling32(g.M) : pick_tiling(g.M, g.N * ksplit, g.K / ksplit, false);
+  Tiling t = T::is32 ? pick_tiling32(g.M) : pick_tiling(h->tune, g.M, g.N * ksplit, g.K / ksplit, false);
   while (t.nt > 1 && g.N % (t.nt * 16)) t.nt >>= 1;
   if (T::is32) g.touch.W = nullptr;
   return launch_gemm<T, EPI_PARTIAL>(g, t.mtw, t.nt, t.nw, false, s);
@@ -612,17 +592,10 @@ int run_gemm_partial(float_fmt* h, GemmArgs g, int ksplit, hipStream_t s, const 
 
 // Touch descriptor for the weights of GEMM `L` as it will be launched for M rows (ksplit = 0: plain GEMM, else EPI_PARTIAL
 // with that many K slices), to be executed by `lanes` threads per XCD with at most `per_lane` lines each; W = nullptr when the
-// GEMM's block decode is not the XCD-affine one or the lanes cannot cover it.
-// FLOAT_FMT_TOUCH bit mask - who pulls whose weights: 1 LayerNorm -> qkv and fc1 (64: only LN2 -> fc1, 128: only LN1 -> qkv),
-// 2 attention -> proj, 4 fc1 -> fc2, 8 qkv -> proj, 16 proj -> fc1, 32 fc2 -> the next block's qkv / the head.
-// Default 2 + 4 + 32 + 128 (r01, ms per 250 evaluations, same box: none 90.8, 2+4 87.6, 4+32 86.0-86.7, 2+4+32 83.2-83.5 after the
-// head change, + LN1 -> qkv 82.5; touching fc1's weights - from LayerNorm, proj or qkv - never paid).
-// Round 2, with the adaLN weights out of the step (105 MB less cycling through the Infinity Cache per evaluation): LN2 -> fc1
-// now pays too: 230 = 166 + 64 gives 83.6 vs 84.9 ms (proj -> fc1 instead: 85.8; attention or qkv as extra pullers: 85.2-86.0).
-int g_fmt_touch = 230;
-TouchSpec make_touch(const Lin& L, int M, int ksplit, unsigned lanes, unsigned per_lane, int force_nt = 0) {
+// GEMM's block decode is not the XCD-affine one or the lanes cannot cover it.  Who pulls whose weights: FmtTune::touch.
+TouchSpec make_touch(const FmtTune& tn, const Lin& L, int M, int ksplit, unsigned lanes, unsigned per_lane, int force_nt = 0) {
   TouchSpec t{};
-  Tiling tl = ksplit ? pick_tiling(M, L.N * ksplit, L.K / ksplit, false) : pick_tiling(M, L.N, L.K, false);
+  Tiling tl = ksplit ? pick_tiling(tn, M, L.N * ksplit, L.K / ksplit, false) : pick_tiling(tn, M, L.N, L.K, false);
   if (force_nt) tl.nt = force_nt;
   if (ksplit)
     while (tl.nt > 1 && L.N % (tl.nt * 16)) tl.nt >>= 1;
@@ -649,14 +622,10 @@ TouchSpec make_touch(const Lin& L, int M, int ksplit, unsigned lanes, unsigned p
 
 // The same for a row-blocked GEMM (fmt_gemm_rbs_kernel, no K split): only the FIRST stages of every weight column tile - what
 // each of its workgroups waits for before it can start (1.5 of fc1's 10 us at 720 rows: every CU asks for cold lines at once).
-// Its block decode puts column block bx on XCD bx % 8, like the 48 x 64 tiling's.  FLOAT_FMT_RB_TOUCH = k-blocks to pull (0 = off).
-// Measured, ms per 250 evaluations of 4 / 16 clips: none 152.2 / 408.4, 4 k-blocks 151.8, 8: 151.4, 16: 150.6 / 404.6 (kept),
-// 32 (the whole K of every tile): 150.8 / 410.0.
-int g_fmt_rb_touch = 16;
-TouchSpec make_touch_rb(const Lin& L, int shape, unsigned lanes, unsigned per_lane) {
+// Its block decode puts column block bx on XCD bx % 8, like the 48 x 64 tiling's.  kb = k-blocks to pull (FmtTune::rb_touch, 0 = off).
+TouchSpec make_touch_rb(const Lin& L, int shape, int kb, unsigned lanes, unsigned per_lane) {
   TouchSpec t{};
   const int ct = shape == 0 ? 4 : 8;  // 16-column tiles per column block: 96 x 64 | 96 x 128, 192 x 128
-  const int kb = g_fmt_rb_touch;
   if (kb <= 0 || (kb & (kb - 1)) || L.N % (ct * 16) || (L.N / (ct * 16)) % 8 || L.K / 32 < kb) return t;
   const unsigned run_lines = (unsigned)kb * 8u;  // a k-block of a column tile is 1 KiB = 8 lines, consecutive k-blocks are consecutive
   auto lg = [](unsigned v) {
@@ -675,8 +644,8 @@ TouchSpec make_touch_rb(const Lin& L, int shape, unsigned lanes, unsigned per_la
 }
 
 // threads per XCD of the launch run_gemm makes for a plain (M, N, K) GEMM
-unsigned gemm_lanes_per_xcd(int M, int N, int K) {
-  const Tiling t = pick_tiling(M, N, K, false);
+unsigned gemm_lanes_per_xcd(const FmtTune& tn, int M, int N, int K) {
+  const Tiling t = pick_tiling(tn, M, N, K, false);
   const int mblk = ((M + 15) / 16 + t.mtw - 1) / t.mtw;
   return (unsigned)((N / (t.nt * 16)) * mblk / 8) * (unsigned)(t.nw * 64);
 }
@@ -686,7 +655,7 @@ int launch_lnmod(float_fmt* h, int M, const float* shift, const float* scale, hi
                  const Lin* next = nullptr, u16* out = nullptr, int perm = 0, int touch_bit = 1, int rb_shape = -1) {
   const int nv = h->D / 256;
   // one row (wave) per workgroup: 180 single-wave workgroups spread over 180 CUs (4 rows per workgroup: +0.4 %)
-  static const int rpw = getenv("FLOAT_FMT_LN_ROWS") ? std::max(1, std::min(4, atoi(getenv("FLOAT_FMT_LN_ROWS")))) : 1;
+  const int rpw = h->tune.ln_rows;
   // rpw == 1: the kernel maps ids to rows in groups of 8 rows per XCD -> 64 row slots per group of 64 ids
   dim3 grid(rpw == 1 ? ((M + 63) / 64) * 64 : (M + rpw - 1) / rpw), block(64 * rpw);
   const int ks = pend ? pend->ks : 0;
@@ -694,8 +663,9 @@ int launch_lnmod(float_fmt* h, int M, const float* shift, const float* scale, hi
   LnRed red{};
   if (ks) red = pend->red;
   TouchSpec pf{};
-  if (next && (g_fmt_touch & (1 | touch_bit)) && rpw == 1 && !T::is32)
-    pf = rb_shape >= 0 ? make_touch_rb(*next, rb_shape, (grid.x / 8) * 64, 6) : make_touch(*next, M, 0, (grid.x / 8) * 64, 6);
+  if (next && (h->tune.touch & (1 | touch_bit)) && rpw == 1 && !T::is32)
+    pf = rb_shape >= 0 ? make_touch_rb(*next, rb_shape, h->tune.rb_touch, (grid.x / 8) * 64, 6)
+                       : make_touch(h->tune, *next, M, 0, (grid.x / 8) * 64, 6);
 #define LN_LAUNCH(NV, KS)                                                                                                          \
   do {                                                                                                                             \
     if (pf.W && wt) hipLaunchKernelGGL((fmt_lnmod_kernel<T, NV, KS, true, true>), grid, block, 0, s, h->xres, M, shift, scale, h->Ntot, out ? out : h->h16, red, pf, h->ntok, perm, h->sat); \
@@ -730,18 +700,11 @@ template <class T>
 void launch_attn(float_fmt* h, int M, const Lin* pull, hipStream_t s) {
   const float_fmt_cfg_t& c = h->cfg;
   const int D = h->D, ntok = h->ntok;
-  // queries per workgroup / lanes per query (FLOAT_FMT_ATTN="qpw,lpq"): one 8-row output group per workgroup by default
-  static int qpw = 8, lpq = 16;  // r01: 16 lanes per query (8 dims each) 81.5-81.9 ms per 250 evaluations, 8 lanes 82.3-82.9
-  static const bool parsed = [] {
-    if (const char* v = getenv("FLOAT_FMT_ATTN")) sscanf(v, "%d,%d", &qpw, &lpq);
-    if (lpq != 16) lpq = 8;
-    qpw = std::max(1, std::min(512 / lpq, qpw));
-    return true;
-  }();
-  (void)parsed;
+  // queries per workgroup / lanes per query (FLOAT_FMT_ATTN): one 8-row output group per workgroup, 8 dims per lane by default
+  const int qpw = h->tune.attn_qpw, lpq = h->tune.attn_lpq;
   dim3 grid(c.heads, (M + qpw - 1) / qpw), block(qpw * lpq);
   TouchSpec pf{};
-  if (pull && !T::is32) pf = make_touch(*pull, M, 0, (grid.x * grid.y / 8) * block.x, 2);
+  if (pull && !T::is32) pf = make_touch(h->tune, *pull, M, 0, (grid.x * grid.y / 8) * block.x, 2);
 #define ATTN_LAUNCH(LPQ, TCH)                                                                                                  \
   do {                                                                                                                         \
     if (M <= kWtRows) hipLaunchKernelGGL((fmt_attn_kernel<T, LPQ, TCH, true>), grid, block, 0, s, h->qkv16, 3 * D, h->att16, ntok, M, D, c.attn_window, pf, h->sat); \
@@ -762,7 +725,7 @@ void launch_attn(float_fmt* h, int M, const Lin* pull, hipStream_t s) {
 // FLOAT_FMT_ATTNPROJ=1|2 (heads per workgroup; read at float_fmt_create) selects it; the default is the two-launch form
 // (fmt_attn_kernel, then the proj GEMM), which measured the same or faster - see the kernel's header.
 int attnproj_hpw(const float_fmt* h) {
-  const int hd = h->cfg.heads, hpw = h->attnproj;
+  const int hd = h->cfg.heads, hpw = h->tune.attnproj;
   if (hpw <= 0 || h->D != hd * 128 || hd % hpw) return 0;
   const int ks = hd / hpw;
   return (ks == 1 || ks == 2 || ks == 4 || ks == 8) && (hpw == 1 || hpw == 2) ? hpw : 0;
@@ -803,8 +766,6 @@ int launch_attnproj(float_fmt* h, int M, const Lin& proj, hipStream_t s) {
 // alone in the 256 MB Infinity Cache.  FLOAT_FMT_HOIST=0 launches the same kernel once per evaluation (n = 1) instead
 // (bitwise the same numbers; the A/B switch of the measurement).
 constexpr int kScSteps = 64;  // evaluations per modulation batch; longer grids run in batches of this many
-int g_fmt_hoist = 1;
-int g_fmt_zgroup = 0;  // FLOAT_FMT_ZGROUP: column blocks of an XCD that share activation tiles through L2; 0 = per kernel: 4 (fmt_gemm_wide_kernel), 2 (fmt_gemm_dma_kernel)
 
 static int stream_priority(hipStream_t s) {
   int prio = 0;
@@ -818,6 +779,7 @@ static int stream_priority(hipStream_t s) {
 template <class T>
 int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
   const int D = h->D;
+  const FmtTune& tn = h->tune;
   FH_REQUIRE(n >= 1 && n <= kScSteps, "modulation batch of %d evaluations (max %d)", n, kScSteps);
   // dense rows for the persistent kernel (row z * M + r of one packed image), else one padded image per evaluation
   // Not on a stream of non-default priority: with the chain on a HIGH-priority stream beside a decoder on a second stream
@@ -825,7 +787,7 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
   // tools/probes/overlap_check.py; the kernel alone passes the same stress in tools/probes/gemm_big_lab.hip, cause not found -
   // DESIGN.md section 7).  fmt_gemm_dma_kernel gives the same numbers bit for bit.
   const int prio = (s == h->cap_stream && s) ? h->cap_prio : stream_priority(s);
-  const bool big = !T::is32 && g_fmt_wide && prio == 0 && big_shape_ok(n * M, h->adaln_all.N, h->adaln_all.K, h->n_cu);
+  const bool big = !T::is32 && tn.wide && prio == 0 && big_shape_ok(tn, n * M, h->adaln_all.N, h->adaln_all.K, h->n_cu);
   hipLaunchKernelGGL((fmt_silu_c_kernel<T>), dim3((M * D / 8 + 255) / 256, n), dim3(256), 0, s, h->sc16, h->temb + (size_t)e0 * D,
                      h->ccond, M, D, (size_t)h->Mpad * D, big ? M : 0, h->sat);
   h->mod_zs = big ? (size_t)M * h->Ntot : (size_t)h->Mmod * h->Ntot;
@@ -837,19 +799,19 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
   g.out_f32 = h->modall;
   g.ldo = h->Ntot;
   g.zcount = n;
-  const bool dma = (g_fmt_wide_variant == 6 || g_fmt_wide_variant == 7) && (M + 15) / 16 > 4 && dma_shape_ok(g, 320);
-  g.zgroup = g_fmt_zgroup > 0 ? g_fmt_zgroup : (dma ? 2 : 4);
+  const bool dma = (tn.wide_variant == 6 || tn.wide_variant == 7) && (M + 15) / 16 > 4 && dma_shape_ok(g, 320);
+  g.zgroup = tn.zgroup > 0 ? tn.zgroup : (dma ? 2 : 4);
   g.a_zstride = (size_t)h->Mpad * D;
   g.o_zstride = (size_t)h->Mmod * h->Ntot;
   if constexpr (!T::is32) {
-    if (g_fmt_wide && g.N % 128 == 0 && g.K % 128 == 0) return launch_wide<T>(g, false, s);
+    if (tn.wide && g.N % 128 == 0 && g.K % 128 == 0) return launch_wide<T>(g, tn.wide_variant, false, s);
   }
   for (int z = 0; z < n; ++z) {  // shapes the wide kernel does not tile: the generic GEMM, one batch at a time
     GemmArgs gz = g;
     gz.A = g.A + (size_t)z * g.a_zstride * (sizeof(typename T::elem) / sizeof(u16));
     gz.out_f32 = g.out_f32 + (size_t)z * g.o_zstride;
     gz.zcount = 0;
-    int rc = run_gemm<T, EPI_F32>(gz, s);
+    int rc = run_gemm<T, EPI_F32>(tn, gz, s);
     if (rc) return rc;
   }
   return FLOAT_OK;
@@ -859,8 +821,7 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
 constexpr int kMegaWgs = 256, kMegaSmem = 8 * 48 * 64 * 4;
 MegaSync mega_sync_of(const float_fmt* h) {
   unsigned* m = h->mega_sync;
-  static const int wg = getenv("FLOAT_FMT_MEGA_STAMP_WG") ? atoi(getenv("FLOAT_FMT_MEGA_STAMP_WG")) : 0;
-  return MegaSync{m, m + 8 * 32, m + 9 * 32, m + 17 * 32, m + 18 * 32, h->mega_err_host, reinterpret_cast<unsigned long long*>(m + 20 * 32), (unsigned)wg};
+  return MegaSync{m, m + 8 * 32, m + 9 * 32, m + 17 * 32, m + 18 * 32, h->mega_err_host, reinterpret_cast<unsigned long long*>(m + 20 * 32), (unsigned)h->tune.mega_stamp_wg};
 }
 // The persistent kernel's barrier watchdog, looked at by EVERY FMT call of the handle before it queues new work (the flag is
 // host-mapped: no copy, no synchronisation when it is clear): a timeout in an earlier call means that call's results are
@@ -874,7 +835,7 @@ int mega_poll(float_fmt* h) {
   h->graphs.clear();
   if (h->mega_sync) FH_CHECK_HIP(hipMemset(h->mega_sync, 0, (size_t)(32 * 20) * sizeof(unsigned)));
   *reinterpret_cast<volatile unsigned*>(h->mega_err_host) = 0u;
-  h->mega_on = 0;
+  h->tune.mega = 0;
   h->job.active = false;
   fh_set_error("fmt_mega_kernel: a grid barrier timed out in an earlier call (not all %d workgroups were resident) - the results of "
                "that call are invalid; the handle falls back to the launch chain (FLOAT_FMT_MEGA=0 selects it from the start)", 256);
@@ -884,14 +845,15 @@ int mega_poll(float_fmt* h) {
 // options - i.e. exactly the tilings run_blocks would pick.  Anything else keeps the launch chain.
 template <class T>
 bool mega_shape_ok(const float_fmt* h, int nclip, int bc) {
-  if (T::is32 || !h->mega_on || nclip != 1 || bc != 3 || h->D != 1024 || h->cfg.heads != 8 || h->n_cu < kMegaWgs) return false;
-  if (attnproj_hpw(h) || g_fmt_fc2_split != 4 || g_fmt_proj_split != 0) return false;
+  const FmtTune& tn = h->tune;
+  if (T::is32 || !tn.mega || nclip != 1 || bc != 3 || h->D != 1024 || h->cfg.heads != 8 || h->n_cu < kMegaWgs) return false;
+  if (attnproj_hpw(h) || tn.fc2_split != 4 || tn.proj_split != 0) return false;
   const int M = bc * h->ntok;
   auto is = [](Tiling t, int a, int b, int c) { return t.mtw == a && t.nt == b && t.nw == c; };
   const Blk& B = h->blk[0];
   return (M + 15) / 16 == 12 && (h->ntok + 15) / 16 == 4 && h->x_embed.K % 256 == 0 && h->final_lin.K % 256 == 0 &&
-         is(pick_tiling(M, B.qkv.N, B.qkv.K, false), 3, 4, 8) && is(pick_tiling(M, B.proj.N, B.proj.K, false), 3, 1, 8) &&
-         is(pick_tiling(M, B.fc1.N, B.fc1.K, false), 3, 4, 8) && is(pick_tiling(M, B.fc2.N * 4, B.fc2.K / 4, false), 3, 4, 8) &&
+         is(pick_tiling(tn, M, B.qkv.N, B.qkv.K, false), 3, 4, 8) && is(pick_tiling(tn, M, B.proj.N, B.proj.K, false), 3, 1, 8) &&
+         is(pick_tiling(tn, M, B.fc1.N, B.fc1.K, false), 3, 4, 8) && is(pick_tiling(tn, M, B.fc2.N * 4, B.fc2.K / 4, false), 3, 4, 8) &&
          B.fc2.K % 512 == 0;
 }
 
@@ -907,11 +869,12 @@ int build_mega(float_fmt* h, int bc) {
       per_cu = 0;
     }
     if (per_cu * h->n_cu < kMegaWgs) {
-      h->mega_on = 0;  // the launch chain
+      h->tune.mega = 0;  // the launch chain
       return FLOAT_OK;
     }
   }
   const float_fmt_cfg_t& c = h->cfg;
+  const FmtTune& tn = h->tune;
   const int D = h->D, ntok = h->ntok, M = bc * ntok;
   std::vector<MegaStage> st;
   // A operands of the GEMM stages: one buffer per producing stage, written once per launch (see fmt_gemm_body, ldA)
@@ -948,7 +911,7 @@ int build_mega(float_fmt* h, int bc) {
     m.red_gate_off = (long long)b_mod * 6 * D + (long long)gate_col * D;
     m.ln_out = out ? out : h->h16;
     m.perm = perm;
-    if (next && (g_fmt_touch & (1 | touch_bit))) m.pf = make_touch(*next, M, 0, (m.nblk / 8) * 64, 6);
+    if (next && (tn.touch & (1 | touch_bit))) m.pf = make_touch(tn, *next, M, 0, (m.nblk / 8) * 64, 6);
     return m;
   };
   {  // x_embedder + pos_embed (run_blocks): 8 K-splitting waves here instead of 4 (every stage runs the 512-thread workgroup)
@@ -973,7 +936,7 @@ int build_mega(float_fmt* h, int bc) {
       GemmArgs g = base_args(ws_h1(b), B.qkv, M);
       g.out16 = h->qkv16;
       g.ldo16 = 3 * D;
-      if (g_fmt_touch & 8) g.touch = make_touch(B.proj, M, 0, gemm_lanes_per_xcd(M, g.N, g.K), 2);
+      if (tn.touch & 8) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       st.push_back(gemm_stage(MS_QKV, g, 3, 4));
     }
     {
@@ -981,7 +944,7 @@ int build_mega(float_fmt* h, int bc) {
       memset(&m, 0, sizeof(m));
       m.kind = MS_ATTN;
       m.nblk = (unsigned)(c.heads * ((M + 7) / 8));
-      if (g_fmt_touch & 2) m.pf = make_touch(B.proj, M, 0, (m.nblk / 8) * 128, 2);
+      if (tn.touch & 2) m.pf = make_touch(tn, B.proj, M, 0, (m.nblk / 8) * 128, 2);
       m.att_out = ws_att(b);
       st.push_back(m);
     }
@@ -990,7 +953,7 @@ int build_mega(float_fmt* h, int bc) {
       g.out_f32 = h->xres;
       g.ldo = D;
       g.ldg = h->Ntot;
-      if (g_fmt_touch & 16) g.touch = make_touch(B.fc1, M, 0, gemm_lanes_per_xcd(M, g.N, g.K), 2);
+      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       MegaStage m = gemm_stage(MS_PROJ, g, 3, 1);
       m.gate_off = (long long)b * 6 * D + 2LL * D;
       st.push_back(m);
@@ -1000,7 +963,7 @@ int build_mega(float_fmt* h, int bc) {
       GemmArgs g = base_args(ws_h2(b), B.fc1, M);
       g.out16 = ws_hid(b);
       g.ldo16 = B.fc2.K / 32;
-      if (g_fmt_touch & 4) g.touch = make_touch(B.fc2, M, 4, gemm_lanes_per_xcd(M, g.N, g.K), 2);
+      if (tn.touch & 4) g.touch = make_touch(tn, B.fc2, M, 4, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       st.push_back(gemm_stage(MS_FC1, g, 3, 4));
     }
     {
@@ -1009,10 +972,10 @@ int build_mega(float_fmt* h, int bc) {
       g.out_f32 = h->slab;
       g.ldo = g.N;
       g.slab_stride = (size_t)h->Mpad * g.N;
-      if (g_fmt_touch & 32) {
-        const unsigned lanes = gemm_lanes_per_xcd(M, g.N * 4, g.K / 4);
-        if (b + 1 < c.depth) g.touch = make_touch(h->blk[b + 1].qkv, M, 0, lanes, 2);
-        else g.touch = make_touch(h->final_lin, M, 0, lanes, 2, 1);
+      if (tn.touch & 32) {
+        const unsigned lanes = gemm_lanes_per_xcd(tn, M, g.N * 4, g.K / 4);
+        if (b + 1 < c.depth) g.touch = make_touch(tn, h->blk[b + 1].qkv, M, 0, lanes, 2);
+        else g.touch = make_touch(tn, h->final_lin, M, 0, lanes, 2, 1);
       }
       st.push_back(gemm_stage(MS_FC2, g, 3, 4));
     }
@@ -1066,6 +1029,7 @@ template <class T>
 int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler, float dt, float a, float r, float e, hipStream_t s,
                float* vout_to = nullptr) {
   const float_fmt_cfg_t& c = h->cfg;
+  const FmtTune& tn = h->tune;
   const int D = h->D, ntok = h->ntok, M = nclip * bc * ntok;
   int rc;
   if constexpr (!T::is32) {
@@ -1082,14 +1046,14 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
     g.pos = h->pos;
     g.bc = bc;
     g.ntok = ntok;
-    if ((rc = run_gemm<T, EPI_XEMBED>(g, s))) return rc;
+    if ((rc = run_gemm<T, EPI_XEMBED>(tn, g, s))) return rc;
   }
   PendingRed pend;  // residual update left to the next LayerNorm launch
   // stacked clips: the row-blocked LDS-DMA tile (fmt_rb_kernels.hpp); its launches carry no touch descriptors; the LayerNorm in
   // front of qkv / fc1 pulls the first stages of their weights into the XCDs' L2s (make_touch_rb)
   RbPlan rb_qkv, rb_proj, rb_fc1, rb_fc2;
   if constexpr (!T::is32) {
-    rb_qkv = pick_rb(RB_QKV, M), rb_proj = pick_rb(RB_PROJ, M), rb_fc1 = pick_rb(RB_FC1, M), rb_fc2 = pick_rb(RB_FC2, M);
+    rb_qkv = pick_rb(tn, RB_QKV, M), rb_proj = pick_rb(tn, RB_PROJ, M), rb_fc1 = pick_rb(tn, RB_FC1, M), rb_fc2 = pick_rb(tn, RB_FC2, M);
   }
   auto split_ok = [&](int ks, const Lin& L) { return (ks == 1 || ks == 2 || ks == 4) && L.K % (128 * ks) == 0; };
   for (int b = 0; b < c.depth; ++b) {
@@ -1101,11 +1065,10 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
       g.sat = h->sat;
       g.out16 = h->qkv16;
       g.ldo16 = 3 * D;
-      if ((g_fmt_touch & 8) && attnproj_hpw(h)) g.touch = make_touch(B.proj, M, c.heads / attnproj_hpw(h), gemm_lanes_per_xcd(M, g.N, g.K), 2, 8 / attnproj_hpw(h));  // k-slices <-> XCDs as the fused launch decodes them
-      else if ((g_fmt_touch & 8) && !split_ok(g_fmt_proj_split, B.proj)) g.touch = make_touch(B.proj, M, 0, gemm_lanes_per_xcd(M, g.N, g.K), 2);
-      static const LayerPlan plan("FLOAT_FMT_PLAN_QKV");
+      if ((tn.touch & 8) && attnproj_hpw(h)) g.touch = make_touch(tn, B.proj, M, c.heads / attnproj_hpw(h), gemm_lanes_per_xcd(tn, M, g.N, g.K), 2, 8 / attnproj_hpw(h));  // k-slices <-> XCDs as the fused launch decodes them
+      else if ((tn.touch & 8) && !split_ok(tn.proj_split, B.proj)) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       if (rb_qkv.shape >= 0) rc = launch_rbs<T, EPI_T16>(g, rb_qkv.shape, false, s);
-      else rc = run_gemm<T, EPI_T16>(g, s, false, &plan);
+      else rc = run_gemm<T, EPI_T16>(tn, g, s, false, &tn.plan_layer[RB_QKV]);
       if (rc) return rc;
     }
     if (rb_proj.shape >= 0) {
@@ -1122,23 +1085,22 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
       if ((rc = launch_attnproj<T>(h, M, B.proj, s))) return rc;
       pend.ks = c.heads / attnproj_hpw(h);
       pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.proj.b, mod + 2 * D};
-    } else if (split_ok(g_fmt_proj_split, B.proj)) {
+    } else if (split_ok(tn.proj_split, B.proj)) {
       launch_attn<T>(h, M, nullptr, s);
       GemmArgs gp = base_args(h->att16, B.proj, M);
-      if ((rc = run_gemm_partial<T>(h, gp, g_fmt_proj_split, s))) return rc;
-      pend.ks = g_fmt_proj_split;
+      if ((rc = run_gemm_partial<T>(h, gp, tn.proj_split, s))) return rc;
+      pend.ks = tn.proj_split;
       pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.proj.b, mod + 2 * D};
     } else {
-      launch_attn<T>(h, M, (g_fmt_touch & 2) ? &B.proj : nullptr, s);
+      launch_attn<T>(h, M, (tn.touch & 2) ? &B.proj : nullptr, s);
       GemmArgs g = base_args(h->att16, B.proj, M);
       g.sat = h->sat;
       g.out_f32 = h->xres;
       g.ldo = D;
       g.gate = mod + 2 * D;
       g.ldg = h->Ntot;
-      if (g_fmt_touch & 16) g.touch = make_touch(B.fc1, M, 0, gemm_lanes_per_xcd(M, g.N, g.K), 2);
-      static const LayerPlan plan("FLOAT_FMT_PLAN_PROJ");
-      if ((rc = run_gemm<T, EPI_GATE_RES>(g, s, false, &plan))) return rc;
+      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
+      if ((rc = run_gemm<T, EPI_GATE_RES>(tn, g, s, false, &tn.plan_layer[RB_PROJ]))) return rc;
     }
     if ((rc = launch_lnmod<T>(h, M, mod + 3 * D, mod + 4 * D, s, &pend, &B.fc1, nullptr, 0, 64, rb_fc1.shape))) return rc;
     {
@@ -1146,11 +1108,10 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
       g.sat = h->sat;
       g.out16 = h->hid16;
       g.ldo16 = B.fc2.K / 32;  // packed for fc2
-      if ((g_fmt_touch & 4) && rb_fc2.shape < 0)
-        g.touch = make_touch(B.fc2, M, split_ok(g_fmt_fc2_split, B.fc2) ? g_fmt_fc2_split : 0, gemm_lanes_per_xcd(M, g.N, g.K), 2);
-      static const LayerPlan plan("FLOAT_FMT_PLAN_FC1");
+      if ((tn.touch & 4) && rb_fc2.shape < 0)
+        g.touch = make_touch(tn, B.fc2, M, split_ok(tn.fc2_split, B.fc2) ? tn.fc2_split : 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       if (rb_fc1.shape >= 0) rc = launch_rbs<T, EPI_GELU_P16>(g, rb_fc1.shape, false, s);
-      else rc = run_gemm<T, EPI_GELU_P16>(g, s, false, &plan);
+      else rc = run_gemm<T, EPI_GELU_P16>(tn, g, s, false, &tn.plan_layer[RB_FC1]);
       if (rc) return rc;
     }
     if (rb_fc2.shape >= 0) {
@@ -1162,17 +1123,16 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
       if ((rc = launch_rbs<T, EPI_PARTIAL>(g, rb_fc2.shape, false, s))) return rc;
       pend.ks = rb_fc2.ksplit;
       pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.fc2.b, mod + 5 * D};
-    } else if (split_ok(g_fmt_fc2_split, B.fc2)) {
+    } else if (split_ok(tn.fc2_split, B.fc2)) {
       GemmArgs g = base_args(h->hid16, B.fc2, M);
       g.sat = h->sat;
-      if (g_fmt_touch & 32) {
-        const unsigned lanes = gemm_lanes_per_xcd(M, g.N * g_fmt_fc2_split, g.K / g_fmt_fc2_split);
-        if (b + 1 < c.depth) g.touch = make_touch(h->blk[b + 1].qkv, M, 0, lanes, 2);
-        else g.touch = make_touch(h->final_lin, M, 0, lanes, 2, 1);  // the head GEMM runs 16-column workgroups
+      if (tn.touch & 32) {
+        const unsigned lanes = gemm_lanes_per_xcd(tn, M, g.N * tn.fc2_split, g.K / tn.fc2_split);
+        if (b + 1 < c.depth) g.touch = make_touch(tn, h->blk[b + 1].qkv, M, 0, lanes, 2);
+        else g.touch = make_touch(tn, h->final_lin, M, 0, lanes, 2, 1);  // the head GEMM runs 16-column workgroups
       }
-      static const LayerPlan plan("FLOAT_FMT_PLAN_FC2");
-      if ((rc = run_gemm_partial<T>(h, g, g_fmt_fc2_split, s, &plan))) return rc;
-      pend.ks = g_fmt_fc2_split;
+      if ((rc = run_gemm_partial<T>(h, g, tn.fc2_split, s, &tn.plan_layer[RB_FC2]))) return rc;
+      pend.ks = tn.fc2_split;
       pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.fc2.b, mod + 5 * D};
     } else {
       GemmArgs g = base_args(h->hid16, B.fc2, M);
@@ -1181,15 +1141,14 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
       g.ldo = D;
       g.gate = mod + 5 * D;
       g.ldg = h->Ntot;
-      if ((rc = run_gemm<T, EPI_GATE_RES>(g, s))) return rc;
+      if ((rc = run_gemm<T, EPI_GATE_RES>(tn, g, s))) return rc;
     }
   }
   {
     const float* mod = modbuf + (size_t)c.depth * 6 * D;  // shift, scale (FMT.py:196)
     // head: token-blocked rows (every CFG row of 16 tokens in one workgroup: 4 x 32 workgroups of bc row tiles) unless the
     // CFG batch is not one of the combine's shapes; then all rows per workgroup (32 workgroups)
-    static const bool tokblk_on = !getenv("FLOAT_FMT_NO_TOKBLK");
-    const bool tokblk = (tokblk_on || nclip > 1) && (bc == 1 || bc == 3 || bc == 4) && h->final_lin.K % 256 == 0;
+    const bool tokblk = (!tn.no_tokblk || nclip > 1) && (bc == 1 || bc == 3 || bc == 4) && h->final_lin.K % 256 == 0;
     FH_REQUIRE(tokblk || nclip == 1, "batched sampling needs the token-blocked head GEMM");
     const int nblk = (ntok + 15) / 16, seqs = nclip * bc;
     if ((rc = launch_lnmod<T>(h, M, mod, mod + D, s, &pend, nullptr, tokblk ? h->hfin16 : nullptr, tokblk ? seqs * 16 : 0))) return rc;
@@ -1213,7 +1172,7 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
     }
     // token-blocked: a workgroup = the bc row tiles of one (token block, clip) pair; row blocks = token blocks x clips
     if (tokblk) rc = launch_gemm<T, EPI_CFG>(g, bc, 1, 8, false, s);
-    else rc = run_gemm<T, EPI_CFG>(g, s, true);
+    else rc = run_gemm<T, EPI_CFG>(tn, g, s, true);
     if (rc) return rc;
   }
   FH_CHECK_HIP(hipGetLastError());
@@ -1282,7 +1241,7 @@ int stage_window(float_fmt* h, const CfgMode& m, const float* x0, const float* w
   g.out_f32 = h->ccond;
   g.ldo = h->D;
   int rc;
-  if ((rc = run_gemm<T, EPI_F32>(g, s))) return rc;
+  if ((rc = run_gemm<T, EPI_F32>(h->tune, g, s))) return rc;
   const int n = m.nclip * h->ntok * c.dim_w;
   hipLaunchKernelGGL((fmt_init_x_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, h->xcur, h->xin16, h->Kx / 32, x0, prev_x,
                      c.n_prev, c.n_cur, c.dim_w, m.nclip, h->sat);
@@ -1341,7 +1300,7 @@ int run_window_steps(float_fmt* h, const CfgMode& m, int nfe, const std::vector<
   const float_fmt_cfg_t& c = h->cfg;
   const size_t kstride = (size_t)h->Bmax * kMaxTok * c.dim_w;  // one stage's velocities: [clip][ntok][dim_w]
   const int n = m.nclip * c.n_cur * c.dim_w, rows = m.nclip * m.bc * h->ntok;
-  const int nev = n_evals(h->method, nfe), batch = g_fmt_hoist ? kScSteps : 1;
+  const int nev = n_evals(h->method, nfe), batch = h->tune.hoist ? kScSteps : 1;
   const bool euler = h->method == FLOAT_ODE_EULER;
   int rc;
   for (int ev = 0; ev < nev; ++ev) {
@@ -1432,7 +1391,7 @@ int window_impl(float_fmt* h, const float* x0, const float* wa, const float* wr,
   CfgMode m = cfg_mode(a, r, e, include_r);
   m.nclip = nclip;
   // only the all-rows-per-workgroup head (FLOAT_FMT_NO_TOKBLK, a debugging aid) is limited to 15 row tiles
-  FH_REQUIRE(!getenv("FLOAT_FMT_NO_TOKBLK") || m.bc * h->ntok <= 240,
+  FH_REQUIRE(!h->tune.no_tokblk || m.bc * h->ntok <= 240,
              "%d-way CFG of %d tokens is %d rows; the all-rows CFG epilogue GEMM holds at most 240 (15 row tiles)", m.bc, h->ntok,
              m.bc * h->ntok);
   int rc = stage_window<T>(h, m, x0, wa, wr, we, we_len, prev_x, prev_wa, prev_we, s);
@@ -1460,7 +1419,7 @@ int eval_impl(float_fmt* h, float t, const float* x, const float* wa, const floa
   if (rc) return rc;
   const CfgMode m = cfg_mode(a, r, e, include_r);
   // only the all-rows-per-workgroup head (FLOAT_FMT_NO_TOKBLK, a debugging aid) is limited to 15 row tiles
-  FH_REQUIRE(!getenv("FLOAT_FMT_NO_TOKBLK") || m.bc * h->ntok <= 240,
+  FH_REQUIRE(!h->tune.no_tokblk || m.bc * h->ntok <= 240,
              "%d-way CFG of %d tokens is %d rows; the all-rows CFG epilogue GEMM holds at most 240 (15 row tiles)", m.bc, h->ntok,
              m.bc * h->ntok);
   if ((rc = stage_window<T>(h, m, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, s))) return rc;
@@ -1554,15 +1513,15 @@ int create_impl(float_fmt* h, const TensorTable& tt) {
 
 
 // ---------------------------------------------------------------- GEMM service (fmt_gemm.hpp)
-int fmt_pack_linear(DevicePool* pool, int dtype, const TensorTable& tt, const std::vector<std::string>& names, int N_each, int K,
-                    FmtLin* out) {
+int fmt_pack_linear(const FmtTune& tn, DevicePool* pool, int dtype, const TensorTable& tt, const std::vector<std::string>& names,
+                    int N_each, int K, FmtLin* out) {
   FH_REQUIRE(dtype == FLOAT_DT_BF16 || dtype == FLOAT_DT_FP16 || dtype == FLOAT_DT_FP32, "the GEMM service: unknown dtype %d", dtype);
-  if (dtype == FLOAT_DT_FP32) return pack_linear_pool<FP32>(pool, tt, names, N_each, K, out);
-  return dtype == FLOAT_DT_BF16 ? pack_linear_pool<BF16>(pool, tt, names, N_each, K, out)
-                                : pack_linear_pool<FP16>(pool, tt, names, N_each, K, out);
+  if (dtype == FLOAT_DT_FP32) return pack_linear_pool<FP32>(tn, pool, tt, names, N_each, K, out);
+  return dtype == FLOAT_DT_BF16 ? pack_linear_pool<BF16>(tn, pool, tt, names, N_each, K, out)
+                                : pack_linear_pool<FP16>(tn, pool, tt, names, N_each, K, out);
 }
 
-int fmt_pack_linear_raw(DevicePool* pool, int dtype, const float* w, const float* b, int N, int K, FmtLin* out) {
+int fmt_pack_linear_raw(const FmtTune& tn, DevicePool* pool, int dtype, const float* w, const float* b, int N, int K, FmtLin* out) {
   std::vector<float> zeros;
   if (!b) {
     zeros.assign(N, 0.f);
@@ -1580,7 +1539,7 @@ int fmt_pack_linear_raw(DevicePool* pool, int dtype, const float* w, const float
   t[1].ndim = 1;
   t[1].shape[0] = N;
   TensorTable tt(t, 2);
-  return fmt_pack_linear(pool, dtype, tt, {"raw"}, N, K, out);
+  return fmt_pack_linear(tn, pool, dtype, tt, {"raw"}, N, K, out);
 }
 
 GemmArgs fmt_gemm_args(const u16* A, const FmtLin& L, int M) { return base_args(A, L, M); }
@@ -1592,20 +1551,20 @@ void fmt_gemm_prime(int dtype) {
 }
 
 template <class T>
-static int gemm_run_t(int epi, const GemmArgs& g, hipStream_t s) {
+static int gemm_run_t(const FmtTune& tn, int epi, const GemmArgs& g, hipStream_t s) {
   switch (epi) {
-    case EPI_F32: return run_gemm<T, EPI_F32>(g, s);
-    case EPI_T16: return run_gemm<T, EPI_T16>(g, s);
-    case EPI_SILU_P16: return run_gemm<T, EPI_SILU_P16>(g, s);
-    case EPI_GELU_P16: return run_gemm<T, EPI_GELU_P16>(g, s);
-    case EPI_GELUERF_P16: return run_gemm<T, EPI_GELUERF_P16>(g, s);
+    case EPI_F32: return run_gemm<T, EPI_F32>(tn, g, s);
+    case EPI_T16: return run_gemm<T, EPI_T16>(tn, g, s);
+    case EPI_SILU_P16: return run_gemm<T, EPI_SILU_P16>(tn, g, s);
+    case EPI_GELU_P16: return run_gemm<T, EPI_GELU_P16>(tn, g, s);
+    case EPI_GELUERF_P16: return run_gemm<T, EPI_GELUERF_P16>(tn, g, s);
     default: fh_set_error("fmt_gemm_run: epilogue %d is not exported", epi); return FLOAT_E_INVALID;
   }
 }
 
-int fmt_gemm_run(int dtype, int epi, GemmArgs g, hipStream_t s) {
-  if (dtype == FLOAT_DT_FP32) return gemm_run_t<FP32>(epi, g, s);
-  return dtype == FLOAT_DT_BF16 ? gemm_run_t<BF16>(epi, g, s) : gemm_run_t<FP16>(epi, g, s);
+int fmt_gemm_run(const FmtTune& tn, int dtype, int epi, GemmArgs g, hipStream_t s) {
+  if (dtype == FLOAT_DT_FP32) return gemm_run_t<FP32>(tn, epi, g, s);
+  return dtype == FLOAT_DT_BF16 ? gemm_run_t<BF16>(tn, epi, g, s) : gemm_run_t<FP16>(tn, epi, g, s);
 }
 
 template <class T>
@@ -1647,6 +1606,7 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
   FH_REQUIRE(cfg->dtype == FLOAT_DT_BF16 || cfg->dtype == FLOAT_DT_FP16 || cfg->dtype == FLOAT_DT_FP32, "unknown dtype %d", cfg->dtype);
   FH_REQUIRE(cfg->max_batch >= 0 && cfg->max_batch <= 16, "max_batch must be in [0, 16] (got %d)", cfg->max_batch);
   float_fmt* h = new float_fmt();
+  h->tune = FmtTune::from_env();
   h->cfg = *cfg;
   h->D = cfg->dim_h;
   h->ntok = cfg->n_prev + cfg->n_cur;
@@ -1656,27 +1616,11 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
   h->Mpad = 16 * ((h->Bmax * 4 * h->ntok + 15) / 16 + 12);  // + the row tiles a 192-row block reads past the last row
   h->Kc = round_up(cfg->dim_w + cfg->dim_a + cfg->dim_e, 128);
   h->Kx = round_up(cfg->dim_w, 128);
-  if (const char* wd = getenv("FLOAT_FMT_WIDE")) g_fmt_wide = atoi(wd) != 0;
-  if (const char* v = getenv("FLOAT_FMT_FC2_SPLIT")) g_fmt_fc2_split = atoi(v);
-  if (const char* v = getenv("FLOAT_FMT_TOUCH")) g_fmt_touch = atoi(v);
-  if (const char* v = getenv("FLOAT_FMT_FULL_NW")) g_fmt_full_nw = atoi(v);
-  if (const char* v = getenv("FLOAT_FMT_WIDE_VARIANT")) g_fmt_wide_variant = atoi(v);
-  if (const char* v = getenv("FLOAT_FMT_PROJ_SPLIT")) g_fmt_proj_split = atoi(v);
-  if (const char* v = getenv("FLOAT_FMT_RB")) g_fmt_rb = atoi(v) != 0;
-  if (const char* v = getenv("FLOAT_FMT_RB_TOUCH")) g_fmt_rb_touch = atoi(v);
-  h->attnproj = getenv("FLOAT_FMT_ATTNPROJ") ? atoi(getenv("FLOAT_FMT_ATTNPROJ")) : 0;
-  h->mega_on = getenv("FLOAT_FMT_MEGA") ? atoi(getenv("FLOAT_FMT_MEGA")) : 0;
   {
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) h->n_cu = ncu;
     else (void)hipGetLastError();
   }
-  if (const char* v = getenv("FLOAT_FMT_HOIST")) g_fmt_hoist = atoi(v) != 0;
-  if (const char* v = getenv("FLOAT_FMT_ZGROUP")) g_fmt_zgroup = std::max(0, atoi(v));
-  if (const char* v = getenv("FLOAT_FMT_BIG")) g_fmt_big = atoi(v) != 0;
-  if (const char* pl = getenv("FLOAT_FMT_PLAN"))
-    sscanf(pl, "%d,%d,%d,%d,%d,%d", &g_fmt_plan_override[0], &g_fmt_plan_override[1], &g_fmt_plan_override[2],
-           &g_fmt_plan_override[3], &g_fmt_plan_override[4], &g_fmt_plan_override[5]);
   h->Ntot = cfg->depth * 6 * h->D + 2 * h->D;
   TensorTable tt(tensors, n_tensors);
   int rc = (cfg->dtype == FLOAT_DT_BF16) ? create_impl<BF16>(h, tt)

@@ -1,5 +1,6 @@
-"""The tuned launch variants against the plain ones: the tuning switches are read once per process (static), so each variant runs
-in its own child process and the results are compared here.
+"""The tuned launch variants against the plain ones: each variant runs in its own child process and the results are compared
+here.  (The switches are read when a handle is created and belong to that handle - csrc/tuning.hpp; the last test holds handles
+of two variants in ONE process.)
   * FMT: weight touch (FLOAT_FMT_TOUCH), the token-blocked head GEMM (FLOAT_FMT_NO_TOKBLK) and the hoisting of the adaLN
     projection out of the Euler step (FLOAT_FMT_HOIST, FLOAT_FMT_ZGROUP) only change WHERE and WHEN work is done - every output element is produced by the same arithmetic in the same order, so r_d must be bitwise identical.
   * decoder: the fused transposed-conv + blur kernel (FLOAT_DEC_ZBLUR_MIN) filters the same fp16-rounded z values as the separate
@@ -14,7 +15,7 @@ import sys
 import pytest
 import torch
 
-from .util import ROOT
+from .util import ROOT, load_pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -163,3 +164,37 @@ def test_toflow_in_the_conv_epilogue_matches_the_flow_kernel(tmp_path):
     psnr = float(-10 * torch.log10(((epi - old) ** 2).mean() + 1e-20))
     print("ToFlow in the epilogue vs flow kernel: %.1f dB, max %.2e, mean %.2e" % (psnr, float(d.max()), float(d.mean())))
     assert psnr > 80.0 and float(d.mean()) < 5e-5
+
+
+def test_switches_belong_to_the_handle_that_read_them(tmp_path, monkeypatch):
+    """The native switches are read at float_fmt_create and stay with that handle (csrc/tuning.hpp): in ONE process, handle A
+    (default environment), handle B (created under FLOAT_FMT_FC2_SPLIT=0: gate * residual in fc2's epilogue, K summed in one
+    accumulator instead of four fp32 slices folded by the next LayerNorm - other bits) and handle C (variable removed again).
+    B does not change what A launches from then on - a chain A captures only now included - C is not B's chain, and B is
+    bitwise the chain of a process that ran wholly under the switch."""
+    pkg = load_pkg()
+    cfg = pkg.config.FmtConfig()
+    sd = pkg.weights.synth_fmt_state(cfg, seed=3)
+    cond = pkg.pipeline.synth_conditions(cfg, 75, seed=2, device="cuda:0")
+    noise = pkg.fmt.draw_noise(2, 1, cfg, 15).cuda()
+    make = lambda: pkg.fmt.FlowMatchingTransformerHIP(sd, cfg, "cuda:0", "bf16")  # noqa: E731
+    r3 = lambda f, nfe=6: f.sample(cond["r_s"], cond["wa"], cond["we"], noise, nfe, 2.0, 1.0, 1.0).cpu()  # noqa: E731
+    r4 = lambda f: f.sample(cond["r_s"], cond["wa"], cond["we"], noise, 6, 2.0, 1.5, 1.0, include_r_cfg=True).cpu()  # noqa: E731
+    monkeypatch.delenv("FLOAT_FMT_FC2_SPLIT", raising=False)
+    A = make()
+    r_A = r3(A)
+    monkeypatch.setenv("FLOAT_FMT_FC2_SPLIT", "0")
+    B = make()
+    r_B, r_B4, r_B5 = r3(B), r4(B), r3(B, 5)
+    monkeypatch.delenv("FLOAT_FMT_FC2_SPLIT")
+    C = make()
+    r_C = r3(C)
+    r_A5 = r3(A, 5)  # a chain A has not captured yet: captured after B was created
+    r_A2 = r3(A)     # and the first one again
+    assert torch.isfinite(r_A).all() and torch.isfinite(r_B).all()
+    assert not torch.equal(r_A, r_B), "FLOAT_FMT_FC2_SPLIT=0 gave the default chain's bits: the switch proves nothing here"
+    assert torch.equal(r_C, r_A), "a handle created after the variable was removed still runs the variant"
+    assert torch.equal(r_A2, r_A)
+    assert not torch.equal(r_A5, r_B5) and torch.equal(r_A5, r3(C, 5)), "handle B changed what handle A captures"
+    whole = run_child(tmp_path, "fmt", "fc2split0", {"FLOAT_FMT_FC2_SPLIT": "0"})
+    assert torch.equal(r_B, whole["r3"]) and torch.equal(r_B4, whole["r4"])
