@@ -113,6 +113,9 @@ _SIGNATURES = {
     "float_fmt_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
     "float_enc_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
     "float_aud_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
+    "float_cmp_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    "float_cmp_work_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -198,6 +201,35 @@ def saturation(fn_name, handle, device=None, reset=False):
     tot = C.c_uint64(0)
     check(getattr(lib(), fn_name)(handle, C.byref(tot), 1 if reset else 0, stream_ptr(device)))
     return int(tot.value)
+
+
+CMP_STATS = ("sum_sq_diff", "sum_sq_ref", "max_abs", "beyond_thr", "non_finite")  # the columns of float_cmp_segments
+_cmp_work = {}
+
+
+def cmp_segments(a, b, seg_len, thr=2.0 / 255):
+    """float_cmp_segments: a, b fp32 device tensors of the same number of elements, read as n_seg = numel / seg_len contiguous
+    segments (b the trusted side; a slice of a larger tensor is fine).  Returns the (n_seg, 5) float64 DEVICE tensor of
+    CMP_STATS rows; enqueued on the current stream, nothing is synchronised.  The scratch buffer is cached per device and
+    stream (calls on one stream are ordered, so they can share it)."""
+    if not a.is_cuda or a.device != b.device or a.numel() != b.numel():
+        raise ValueError("cmp_segments: a and b must hold the same number of elements on one GPU")
+    seg_len = int(seg_len)
+    if seg_len <= 0 or a.numel() == 0 or a.numel() % seg_len:
+        raise ValueError("cmp_segments: %d elements are not whole segments of %d" % (a.numel(), seg_len))
+    n_seg = a.numel() // seg_len
+    L = lib()
+    need = int(L.float_cmp_work_bytes(n_seg, seg_len))
+    with torch.cuda.device(a.device):
+        s = stream_ptr(a.device)
+        key = (a.device.index, s.value)
+        work = _cmp_work.get(key)
+        if work is None or work.numel() * 8 < need:
+            work = _cmp_work[key] = torch.empty((need + 7) // 8, dtype=torch.float64, device=a.device)
+        stats = torch.empty(n_seg, len(CMP_STATS), dtype=torch.float64, device=a.device)
+        check(L.float_cmp_segments(dev_ptr(a, "a"), dev_ptr(b, "b"), n_seg, seg_len, float(thr), C.c_void_p(stats.data_ptr()),
+                                   C.c_void_p(work.data_ptr()), work.numel() * 8, s))
+    return stats
 
 
 def set_profiling(on):

@@ -36,13 +36,119 @@ def report_range(counts, where, mode=None):
     return bad
 
 
+class Fp16PrecisionError(ArithmeticError):
+    """The 16-bit operators stayed inside fp16's range but their rounding moved the frames further from the fp32 verification mode
+    of the same kernels than the stated tolerance: the result is not the reference's."""
+
+
+VERIFY_THR = 2.0 / 255  # the per-sample figure the tolerance tables quote ("share of the samples beyond 2/255")
+
+
+def precision_policy(checked=False, mode=None):
+    """What FLOAT_AMD_VERIFY asks for this clip: "skip" or "check".  off (default): never; first: the first clip after the
+    operators were built or rebuilt (`checked` = a clip has been checked since); always: every clip."""
+    mode = (mode if mode is not None else os.environ.get("FLOAT_AMD_VERIFY", "off")).lower() or "off"
+    if mode not in ("off", "first", "always"):
+        raise ValueError("FLOAT_AMD_VERIFY must be off, first or always (got %r)" % (mode,))
+    return "check" if mode == "always" or (mode == "first" and not checked) else "skip"
+
+
+def verify_frames_default():
+    return max(1, int(os.environ.get("FLOAT_AMD_VERIFY_FRAMES", "8")))
+
+
+def cmp_summary(rows, seg_len):
+    """rows: the (n_seg, 5) float_cmp_segments statistics on the host -> one comparison of a precision report, pooled over the
+    segments: psnr (peak 1.0; inf for identical buffers), psnr_min (worst segment), rel_l2, pct_beyond (share of the finite
+    pairs beyond the threshold, %), max, non_finite."""
+    rows = [[float(v) for v in r] for r in rows]
+    n_pairs = float(seg_len) * len(rows)
+    finite = n_pairs - sum(r[4] for r in rows)
+    d2, b2 = sum(r[0] for r in rows), sum(r[1] for r in rows)
+
+    def psnr(sq, n):
+        return float("inf") if sq <= 0 or n <= 0 else -10.0 * math.log10(sq / n)
+
+    return dict(psnr=psnr(d2, finite), psnr_min=min(psnr(r[0], seg_len - r[4]) for r in rows),
+                rel_l2=math.sqrt(d2 / b2) if b2 > 0 else (0.0 if d2 == 0 else float("inf")),
+                pct_beyond=100.0 * sum(r[3] for r in rows) / max(finite, 1.0), max=max(r[2] for r in rows),
+                non_finite=int(sum(r[4] for r in rows)), segments=len(rows))
+
+
+def report_precision(report, where, action=None, min_psnr=None):
+    """The sibling of report_range for the OTHER way 16-bit operands go wrong: nothing overflows, the rounding is too coarse for
+    this checkpoint.  report: {"decoder": cmp, "end_to_end": cmp or absent, "fmt": cmp or absent}, each a cmp_summary of the
+    product against the fp32 verification mode (FloatHotPath.verify_precision / verify_decoder).  The comparison held to
+    min_psnr (FLOAT_AMD_VERIFY_PSNR, default 40 dB: the project's end-to-end tolerance) is `end_to_end`, or `decoder` where
+    that is all the report has; a non-finite sample in any comparison fails whatever the PSNR.  Returns None when the report
+    passes, else the operator at fault: "decoder" (decoder + skip features: the decoder comparison alone is below the
+    threshold or non-finite) or "fmt".  FLOAT_AMD_VERIFY_ACTION = warn (default: RuntimeWarning + log) | raise
+    (Fp16PrecisionError) | auto (warn; the caller rebuilds the operator at fault in fp32)."""
+    action = (action or os.environ.get("FLOAT_AMD_VERIFY_ACTION", "warn")).lower()
+    if action not in ("warn", "raise", "auto"):
+        raise ValueError("FLOAT_AMD_VERIFY_ACTION must be warn, raise or auto (got %r)" % (action,))
+    min_psnr = float(min_psnr if min_psnr is not None else os.environ.get("FLOAT_AMD_VERIFY_PSNR", "40.0"))
+    dec, e2e, fmt = report.get("decoder"), report.get("end_to_end"), report.get("fmt")
+    held = e2e if e2e is not None else dec
+    if held is None:
+        raise ValueError("report_precision: the report holds neither an end_to_end nor a decoder comparison")
+    non_finite = sum(c["non_finite"] for c in (dec, e2e, fmt) if c is not None)
+    if held["psnr"] >= min_psnr and not non_finite:
+        return None
+    dec_bad = dec is not None and (dec["psnr"] < min_psnr or dec["non_finite"] > 0)
+    fault = "decoder" if dec_bad or e2e is None else "fmt"
+    msg = ("%s: fp16 precision check failed - the first %d frames are %.1f dB from the fp32 verification mode of the same "
+           "kernels (limit %.1f dB; %.2f %% of the samples beyond 2/255, max %.3f, %d non-finite) with nothing out of fp16's "
+           "range. At fault: %s%s. The frames are NOT the reference's within the stated tolerance: run this checkpoint with %s."
+           % (where, held["segments"], held["psnr"], min_psnr, held["pct_beyond"], held["max"], non_finite, fault,
+              "" if dec is None or e2e is None else " (decoder alone %.1f dB%s)" % (
+                  dec["psnr"], ", FMT latents rel-L2 %.2e" % fmt["rel_l2"] if fmt is not None else ""),
+              "dtype fp32 for the decoder and encoder (FLOAT_AMD_DEC_DTYPE=fp32)" if fault == "decoder"
+              else "dtype fp32 for the FMT (FLOAT_AMD_FMT_DTYPE=fp32)"))
+    if action == "raise":
+        raise Fp16PrecisionError(msg)
+    logging.getLogger("float_amd").error(msg)
+    warnings.warn(msg, RuntimeWarning, stacklevel=3)
+    return fault
+
+
+@torch.no_grad()
+def verify_decoder(dec_state, size, s_r, feats, r_d, frames_dev, k, device="cuda:0", style_dim=512, twin=None):
+    """The decoder half of the precision guard, callable on its own: decode the first k latents of `r_d` with an fp32 twin
+    of the decoder (verification mode, max_frames = k, skip features `feats` = fp32 NCHW through float_dec_set_feats) and
+    compare the product's frames `frames_dev[:k]` (device, (T, size, size, 3)) against them with float_cmp_segments.  Only the
+    k statistics rows cross to the host.  twin: an fp32 SynthesisHIP that already holds `feats` (kept open); else one is built
+    and closed.  Returns {"decoder": cmp_summary, "k", "build_ms", "hbm_bytes"}."""
+    import time
+    dev = torch.device(device)
+    rd = (r_d[0] if r_d.dim() == 3 else r_d).to(dev, torch.float32)
+    k = max(1, min(int(k), rd.shape[0], frames_dev.shape[0]))
+    own = twin is None
+    build_ms, hbm = 0.0, 0
+    if own:
+        torch.cuda.synchronize(dev)
+        free0, t0 = torch.cuda.mem_get_info(dev)[0], time.perf_counter()
+        twin = SynthesisHIP(dec_state, size, style_dim, dev, "fp32", k)
+        twin.set_feats(feats)
+        torch.cuda.synchronize(dev)
+        build_ms, hbm = (time.perf_counter() - t0) * 1e3, free0 - torch.cuda.mem_get_info(dev)[0]
+    try:
+        want = twin.decode_latent_into_processed_images(s_r, rd[:k])
+        seg = size * size * 3
+        rows = native.cmp_segments(frames_dev[:k].reshape(-1), want.reshape(-1), seg, VERIFY_THR).cpu()
+    finally:
+        if own:
+            twin.close()
+    return dict(decoder=cmp_summary(rows.tolist(), seg), k=k, build_ms=build_ms, hbm_bytes=int(hbm))
+
+
 class FloatHotPath:
     def __init__(self, fmt_state, dec_state, cfg: FmtConfig = None, device="cuda:0", size=512, fmt_dtype="fp16",
                  dec_dtype="fp16", max_frames=32, use_graph=2, max_batch=1):
         self.cfg = cfg or FmtConfig()
         self.device = torch.device(device)
         self.size = size
-        self._fmt_state, self._use_graph = fmt_state, use_graph
+        self._fmt_state, self._dec_state, self._use_graph = fmt_state, dec_state, use_graph
         self.fmt = FlowMatchingTransformerHIP(fmt_state, self.cfg, device, fmt_dtype, use_graph, max_batch)
         self.dec = SynthesisHIP(dec_state, size, self.cfg.dim_w, device, dec_dtype, max_frames)
 
@@ -82,6 +188,64 @@ class FloatHotPath:
             out["fmt"] = self.fmt.saturation(reset) + sum(f.saturation(reset) for f in self.__dict__.get("_fmt_batched", {}).values())
         if self.dec.dtype == "fp16":
             out["decoder"] = self.dec.saturation(reset)
+        return out
+
+    @torch.no_grad()
+    def verify_precision(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, noise, r_d, frames_dev, k,
+                         keep_twins=False):
+        """The fp16 precision guard for one clip (B = 1) that this object has just produced: `r_d` (1, T, dim_w) and
+        `frames_dev` (T, size, size, 3), both on the device.  Builds fp32 twins (verification mode: the same kernels with
+        4-byte operands, held to the reference at 1e-4) of the FMT (eager launches, max_batch 1) and of the decoder
+        (max_frames = k), samples WINDOW 0 ONLY in fp32 from the same conditions and the same noise, decodes the first k frames
+        twice with the fp32 decoder - from the product's latents and from the fp32 latents - and compares on the device
+        (float_cmp_segments; only the statistics rows are pulled to the host):
+          fmt         product r_d[:n] against fp32 r_d[:n], n = min(T, n_cur) (attribution and the log line);
+          decoder     product frames [0, k) against fp32-decoder frames of the PRODUCT's latents (decoder + skip features);
+          end_to_end  product frames [0, k) against the all-fp32 frames: the one report_precision holds to the threshold.
+        feats: the fp32 NCHW skip features (from an fp32 encoder).  wa / we are the product's on both sides: the audio
+        operators are not covered.  k is clipped to n.  The twins are closed before returning unless keep_twins (then they are
+        returned under "twins" and the caller closes them).  Also in the result: k, n, build_ms and hbm_bytes of the twins, ms
+        of the whole check."""
+        import time
+        dev, c = self.device, self.cfg
+        t_all = time.perf_counter()
+        rd16 = (r_d[0] if r_d.dim() == 3 else r_d).to(dev, torch.float32)
+        T = rd16.shape[0]
+        n = min(T, c.num_frames_for_clip)
+        k = max(1, min(int(k), n, frames_dev.shape[0]))
+        torch.cuda.synchronize(dev)
+        free0, t0 = torch.cuda.mem_get_info(dev)[0], time.perf_counter()
+        fmt32 = FlowMatchingTransformerHIP(self._fmt_state, c, dev, "fp32", 0, 1)
+        dec32 = None
+        try:
+            fmt32.set_method(getattr(self.fmt, "method", "euler"))
+            dec32 = SynthesisHIP(self._dec_state, self.size, c.dim_w, dev, "fp32", k)
+            dec32.set_feats(feats)
+            torch.cuda.synchronize(dev)
+            build_ms, hbm = (time.perf_counter() - t0) * 1e3, free0 - torch.cuda.mem_get_info(dev)[0]
+            wa0 = wa.to(dev, torch.float32)[:, :n]
+            we0 = we.to(dev, torch.float32)
+            we0 = we0[:, :n] if we0.shape[1] > 1 else we0
+            rd32 = fmt32.sample(r_s, wa0, we0, noise.to(dev, torch.float32)[:1], nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)[0]
+            seg = self.size * self.size * 3
+            got = frames_dev[:k].reshape(-1)
+            rows = [native.cmp_segments(rd16[:n].reshape(-1), rd32.reshape(-1), n * c.dim_w, VERIFY_THR),
+                    native.cmp_segments(got, dec32.decode_latent_into_processed_images(s_r, rd16[:k]).reshape(-1), seg, VERIFY_THR),
+                    native.cmp_segments(got, dec32.decode_latent_into_processed_images(s_r, rd32[:k]).reshape(-1), seg, VERIFY_THR)]
+            rows = torch.cat(rows).cpu().tolist()  # the one hand-over: (1 + 2 k) x 5 doubles
+        except BaseException:
+            keep_twins = False
+            raise
+        finally:
+            if not keep_twins:
+                fmt32.close()
+                if dec32 is not None:
+                    dec32.close()
+        out = dict(fmt=cmp_summary(rows[:1], n * c.dim_w), decoder=cmp_summary(rows[1:1 + k], seg),
+                   end_to_end=cmp_summary(rows[1 + k:], seg), k=k, n=n, build_ms=build_ms, hbm_bytes=int(hbm),
+                   ms=(time.perf_counter() - t_all) * 1e3)
+        if keep_twins:
+            out["twins"] = (fmt32, dec32)
         return out
 
     @torch.no_grad()

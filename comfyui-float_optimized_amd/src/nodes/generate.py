@@ -10,7 +10,7 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
-from ...pipeline import FloatHotPath, report_range
+from ...pipeline import FloatHotPath, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
 
 # key prefixes of the unified checkpoint (utils/downloader.py:35-42)
@@ -53,6 +53,7 @@ class InferenceAgent:
                            dec_dtype=canon(dec_dtype or os.environ.get("FLOAT_AMD_DEC_DTYPE", "fp16")),
                            aud_dtype=canon(aud_dtype or os.environ.get("FLOAT_AMD_AUD_DTYPE", "fp16")))
         self.G = None
+        self.last_precision_report = None  # check_precision (FLOAT_AMD_VERIFY) keeps its last report here
         self.to_target()
 
     # ------------------------------------------------------------------ residency (reference: model_to_target, nodes.py:173-175)
@@ -61,6 +62,7 @@ class InferenceAgent:
         if self.G is not None:
             return self
         opt, parts, b = self.opt, self._parts, self._build
+        self._precision_checked = False  # FLOAT_AMD_VERIFY=first: the first clip after the operators were (re)built
         # 16-bit MFMA operand types (fp32 accumulation): fp16 in both operators gives ~8x lower rounding error than
         # bf16 at the same rate (end-to-end 48.7 vs 34.1 dB on BASELINE configs[0]); FLOAT_AMD_FMT_DTYPE=bf16
         # selects the type BASELINE configs[1] names.
@@ -264,16 +266,23 @@ class InferenceAgent:
         n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
         noise = self._noise_to_device(n_chunks, seed if seed is not None else self.opt.seed)
         ov = os.environ.get("FLOAT_AMD_OVERLAP", "")  # "prio" | "cu:N": decode window k beside the chain of window k + 1 (pipeline.py)
+        verify = precision_policy(self._precision_checked) == "check"  # FLOAT_AMD_VERIFY, default off: nothing below changes
         if ov and ov != "0":
             host = self.G.generate_to_host_overlap(c["r_s"], c["wa"], c["we"], c["s_r"], self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                                   e_cfg_scale, noise=noise, out=out, mode=ov)
+                                                   e_cfg_scale, noise=noise, out=out, mode=ov, return_rd=verify)
         else:
             host = self.G.generate_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                           e_cfg_scale, noise=noise, out=out)
+                                           e_cfg_scale, noise=noise, out=out, return_rd=verify)
+        host, r_d = host if verify else (host, None)
         torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
         self.G.release_host_inflight()
-        if self.check_range("InferenceAgent.infer_device", allow_rebuild=True) == "rebuilt":
+        bad = self.check_range("InferenceAgent.infer_device", allow_rebuild=True)
+        if bad == "rebuilt":
             return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out)  # once more, in the wider types
+        if verify and not bad:  # a range failure has been reported already: the frames are wrong for a reason that is known
+            if self.check_precision("InferenceAgent.infer_device", s, c, noise, r_d, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                    allow_rebuild=True) == "rebuilt":
+                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out)  # once more, in fp32
         return host
 
     def range_counts(self, reset=True):
@@ -311,6 +320,61 @@ class InferenceAgent:
                 self.to_target()
                 return "rebuilt"
         return bad
+
+    @torch.no_grad()
+    def check_precision(self, where, s, c, noise, r_d, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, allow_rebuild=False):
+        """The fp16 PRECISION guard, the sibling of check_range (which sees only values beyond fp16's range): after a clip has
+        arrived, run the fp32 verification mode of the FMT and the decoder on a small sample of it and compare on the device
+        (FloatHotPath.verify_precision).  s: the portrait (1,3,H,W) of the clip, c: its conditions_device result, noise / r_d:
+        the noise it was sampled from and the latents it gave; the device-side frames are the hot path's staging buffer.
+          FLOAT_AMD_VERIFY         off (default: infer_device never calls this) | first (the first clip after the operators
+                                   were built or rebuilt) | always
+          FLOAT_AMD_VERIFY_ACTION  warn (default) | raise (Fp16PrecisionError) | auto: warn, REBUILD the operator at fault in
+                                   fp32 - decoder + encoder when the decoder comparison is below the threshold, otherwise the
+                                   FMT - and tell the caller to run the clip again ("rebuilt"); the agent keeps those types
+          FLOAT_AMD_VERIFY_FRAMES  frames compared (default 8, clipped to min(T, n_cur))
+          FLOAT_AMD_VERIFY_PSNR    the end-to-end limit in dB (default 40.0, the project's stated tolerance)
+        Covered: window 0 of the sampler and the first k frames.  The skip features of the fp32 side come from an fp32 twin of
+        the appearance encoder on the same image; s_r and r_s are the product's.  NOT covered: the audio and speech-emotion
+        operators - wa and we are taken from the product for both sides.  The twins are built for the check and closed after
+        it.  Returns the operator at fault, "rebuilt", or None; the report stays in self.last_precision_report."""
+        import time
+        t0 = time.perf_counter()
+        o, T = self.opt, c["T"]
+        k = min(verify_frames_default(), T, self.cfg.num_frames_for_clip)
+        enc32 = EncoderHIP(self._parts["enc"], o.input_size, o.dim_w, getattr(o, "dim_m", 20), self.rank, dtype="fp32",
+                           direction_weight=self._parts["dec"]["direction.weight"])
+        try:
+            feats = enc32.encode_image_into_latent(s, want_feats=True)[2]
+            rep = self.G.verify_precision(c["r_s"], c["wa"], c["we"], c["s_r"], feats, o.nfe, a_cfg_scale, r_cfg_scale,
+                                          e_cfg_scale, noise, r_d, self.G.staging(T), k)
+        finally:
+            enc32.close()
+        del feats
+        self._precision_checked = True
+        rep["ms"] = (time.perf_counter() - t0) * 1e3
+        rep["dtypes"] = dict(fmt=self.G.fmt.dtype, decoder=self.G.dec.dtype, encoder=self.enc.dtype)
+        self.last_precision_report = rep
+        main_logger.info(
+            "%s: precision check (fmt %s, decoder %s) on window 0 / %d frames: FMT latents rel-L2 %.2e | decoder %.1f dB | "
+            "end to end %.1f dB, %.2f %% beyond 2/255, max %.3f, %d non-finite | one-off cost %.0f ms (twins %.0f ms, %.2f GB)",
+            where, rep["dtypes"]["fmt"], rep["dtypes"]["decoder"], rep["k"], rep["fmt"]["rel_l2"], rep["decoder"]["psnr"],
+            rep["end_to_end"]["psnr"], rep["end_to_end"]["pct_beyond"], rep["end_to_end"]["max"],
+            rep["end_to_end"]["non_finite"], rep["ms"], rep["build_ms"], rep["hbm_bytes"] / 2**30)
+        fault = report_precision(rep, where)
+        if fault and allow_rebuild and os.environ.get("FLOAT_AMD_VERIFY_ACTION", "warn").lower() == "auto":
+            b, changed = self._build, False
+            if fault == "decoder" and b["dec_dtype"] != "fp32":
+                b["dec_dtype"], changed = "fp32", True
+            if fault == "fmt" and b["fmt_dtype"] != "fp32":
+                b["fmt_dtype"], changed = "fp32", True
+            if changed:
+                main_logger.warning("%s: rebuilding the operators as fmt=%s, decoder/encoder=%s and running the clip again",
+                                    where, b["fmt_dtype"], b["dec_dtype"])
+                self.offload()
+                self.to_target()
+                return "rebuilt"
+        return fault
 
     @torch.no_grad()
     def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None):

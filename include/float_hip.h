@@ -36,6 +36,8 @@
 extern "C" {
 #endif
 
+/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison) are purely additive - no
+ * existing signature, structure or behaviour changed, so a caller built against the earlier v6 header runs unchanged. */
 #define FLOAT_HIP_ABI_VERSION 6
 
 enum {
@@ -396,6 +398,27 @@ double float_profile_ms(int32_t which, int64_t* n_launches);
  * (v_mfma_f32_16x16x32_f16 / _32x32x16_f16) in TFLOP/s, compute-unit count.  Allocates and frees 4 GiB; ~0.1 s; synchronises
  * the NULL stream.  Every pointer optional. */
 int float_probe_peaks(float* hbm_read_gbps, float* hbm_copy_gbps, float* mfma16_tflops, float* mfma32_tflops, int32_t* n_cu);
+
+/* ---------------------------------------------------------------- comparison ------ */
+/* Segment-wise comparison of two fp32 device buffers, for the fp16 precision guard (pipeline.FloatHotPath.verify_precision; no
+ * reference counterpart: the reference is fp32).  a, b: n_seg contiguous segments of seg_len elements each, b the trusted side;
+ * a segment is one frame (size * size * 3) or one window of latents (n_cur * dim_w).  Any seg_len; a and b need 4-byte
+ * alignment only (a slice of a larger tensor): 16-byte loads on the aligned body of each segment, scalar head and tail.
+ *   stats: DEVICE memory, n_seg x 5 doubles, per segment
+ *     [0] sum of (a - b)^2 over the finite pairs     [1] sum of b^2 over the finite pairs
+ *     [2] max |a - b| over the finite pairs          [3] number of finite pairs with |a - b| > thr
+ *     [4] number of pairs where a or b is NaN or infinite (excluded from [0..3])
+ *   Differences, squares and sums are formed in fp64 from the first add, so a sum is within seg_len * 2^-53 relative of any
+ *   other summation order; counts and the maximum are exact.
+ *   work: DEVICE scratch of at least float_cmp_work_bytes(n_seg, seg_len) bytes, 8-byte aligned, no zeroing needed: workgroups
+ *   write per-(segment, slice) partials there and a second launch folds the slices of each segment in a fixed order - no
+ *   floating-point atomics, two calls on the same inputs give bitwise identical stats.
+ * Enqueues two kernels on `stream`; allocates nothing, synchronises nothing.  Bad arguments (NULL pointers, n_seg <= 0,
+ * seg_len <= 0, misaligned pointers, work_bytes too small) return FLOAT_E_INVALID before any HIP call.
+ * float_cmp_work_bytes returns 0 for n_seg <= 0 or seg_len <= 0. */
+int float_cmp_segments(const float* a, const float* b, int32_t n_seg, int64_t seg_len, float thr, double* stats, void* work,
+                       size_t work_bytes, void* stream);
+size_t float_cmp_work_bytes(int32_t n_seg, int64_t seg_len);
 
 #ifdef __cplusplus
 }
