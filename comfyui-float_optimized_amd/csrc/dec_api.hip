@@ -72,9 +72,9 @@ struct float_dec {
   // float_dec_frames_host, ride-along mode: the frames of the previous high batch still to be copied to the host by copy
   // workgroups inside the next batch's launches (CopyTail, dec_kernels.hpp)
   struct {
-    const float* src = nullptr;
-    float* dst = nullptr;       // device-side address of the pinned destination (what the copy workgroups store through)
-    float* dst_host = nullptr;  // the same position as the caller's host pointer (hipMemcpyAsync of what no launch took)
+    const char* src = nullptr;  // bytes: the frames are fp32 or uint8 (float_dec_frames_host / _host_u8)
+    char* dst = nullptr;        // device-side address of the pinned destination (what the copy workgroups store through)
+    char* dst_host = nullptr;   // the same position as the caller's host pointer (hipMemcpyAsync of what no launch took)
     size_t left16 = 0;   // 16-byte units not yet handed to a launch
     double wleft = 0.0;  // sum of the weights of the carrying launches still to come in this batch
   } ride;
@@ -309,6 +309,7 @@ int raise_lds_limits(const DecTune& tn) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_conv16_kernel<T, 4, 3, 3, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_conv16_kernel<T, 2, 3, 3, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_flowlast_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_flowlast_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   if constexpr (!T::is32) {  // the double-buffered form (FLOAT_DEC_CONV_DB): two buffer sets, up to 115 KB
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_conv16_kernel<T, 4, 3, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_conv16_kernel<T, 2, 3, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -496,9 +497,9 @@ static CopyTail take_ride(float_dec* h, int R, int kind) {
   if (tn.ride_test == 1) ct.dst = const_cast<u32x4*>(ct.src);  // device -> device instead of device -> host
   if (tn.ride_test == 2) ct.n16 = 1;                            // copy workgroups with nothing to do
 #endif
-  r.src += n * 4;
-  r.dst += n * 4;
-  r.dst_host += n * 4;
+  r.src += n * 16;
+  r.dst += n * 16;
+  r.dst_host += n * 16;
   r.left16 -= n;
   return ct;
 }
@@ -718,7 +719,9 @@ int launch_flow(const DecTune& tn, float_dec* h, FlowArgs g, hipStream_t st) {
     const int runs = (g.R * g.R + 255) / 256;
     if (h) g.ct = take_ride(h, g.R, 2);
     const size_t lpad = (size_t)tn.lds_pad;
-    hipLaunchKernelGGL((dec_flowlast_kernel<T>), dim3(runs * g.F + g.ct.nwg), dim3(256), lpad, st, g);
+    FH_REQUIRE(g.final_mode != 3 || (g.R * g.R) % 256 == 0, "8-bit frames: %d x %d pixels are not whole runs of 256", g.R, g.R);
+    if (g.final_mode == 3) hipLaunchKernelGGL((dec_flowlast_kernel<T, true>), dim3(runs * g.F + g.ct.nwg), dim3(256), lpad, st, g);
+    else hipLaunchKernelGGL((dec_flowlast_kernel<T>), dim3(runs * g.F + g.ct.nwg), dim3(256), lpad, st, g);
     FH_CHECK_HIP(hipGetLastError());
     return FLOAT_OK;
   }
@@ -751,7 +754,7 @@ int launch_flow(const DecTune& tn, float_dec* h, FlowArgs g, hipStream_t st) {
 template <class T>
 int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, void* V, void* xnext, const float* styles,
               const float* demod, const float* flow_prev, const float* rgb_prev, float* flow_cur, float* rgb_cur,
-              float* final_out, int final_mode, hipStream_t st) {
+              void* final_out, int final_mode, hipStream_t st) {
   const Level& L = h->levels[li];
   const Styled& up = h->convs[1 + 2 * li];
   const Styled& c2 = h->convs[2 + 2 * li];
@@ -842,7 +845,7 @@ int run_low(float_dec* h, int n, const float* styles, const float* demod, int* s
 
 // High phase for `n` frames (n <= max_frames) that sit at frame offset `off` inside the low batch.
 template <class T>
-int run_high(float_dec* h, int n, int off, const float* styles, const float* demod, int skip_idx, float* out, int final_mode,
+int run_high(float_dec* h, int n, int off, const float* styles, const float* demod, int skip_idx, void* out, int final_mode,
              hipStream_t st) {
   int rc;
   const int l0 = h->lo_levels;
@@ -871,17 +874,20 @@ int run_high(float_dec* h, int n, int off, const float* styles, const float* dem
 }
 
 // host != nullptr: every finished high batch is copied to host + (its offset) on `cs` while `st` renders the next one
-// (float_dec_frames_host); `st` is made to wait for the last copy before the call returns.
+// (float_dec_frames_host); `st` is made to wait for the last copy before the call returns.  out_v / host_v / host_dev_v hold
+// floats, or uint8_t with final_mode 3: every offset and byte count below goes by the output element size.
 template <class T>
-int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, float* out, int final_mode, hipStream_t st,
-                float* host = nullptr, hipStream_t cs = nullptr, float* host_dev = nullptr) {
+int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, void* out_v, int final_mode, hipStream_t st,
+                void* host_v = nullptr, hipStream_t cs = nullptr, void* host_dev_v = nullptr) {
   const int S = h->cfg.size, sdim = h->cfg.style_dim, FH = h->cfg.max_frames, FL = h->lo_frames;
+  const size_t esz = final_mode == 3 ? sizeof(uint8_t) : sizeof(float);
+  char *const out = static_cast<char*>(out_v), *const host = static_cast<char*>(host_v), *const host_dev = static_cast<char*>(host_dev_v);
   size_t n_copy = 0;
   const DecTune& tn = h->tune;
   // same-stream hand-over: copy workgroups ride along the next batch's launches unless FLOAT_DEC_COPY=memcpy
   // the copy workgroups store straight through `host`: only when it is device-accessible (pinned / registered) host memory
   // (host_dev = its device-side address); a pageable destination takes the hipMemcpyAsync path, batch by batch, in order
-  const bool ride = host_dev && cs == st && !tn.copy_memcpy && (((size_t)S * S * 3 * sizeof(float)) % 16 == 0) &&
+  const bool ride = host_dev && cs == st && !tn.copy_memcpy && (((size_t)S * S * 3 * esz) % 16 == 0) &&
                     ((uintptr_t)host_dev % 16 == 0) && ((uintptr_t)out % 16 == 0);
   h->ride.left16 = 0;
   h->ride.wleft = 0.0;
@@ -938,7 +944,7 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
         const int tail = tn.ride_tail;
         const bool last_of_call = (s0 + a0 + b0 + nb == n_frames);
         if (host && ride && last_of_call && tail > 0 && nb > tail) nb -= tail;
-        const size_t off = (size_t)(s0 + a0 + b0) * S * S * 3;
+        const size_t off = (size_t)(s0 + a0 + b0) * S * S * 3 * esz;  // bytes
         if (host && ride) {
           // launches of this batch that carry a share: up-conv, conv2 and flow kernel of every level from ride_min_res up
           double wsum = 0.0;
@@ -949,7 +955,7 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
         }
         rc = run_high<T>(h, nb, b0, st_a + (size_t)b0 * h->Stot, dm_a + (size_t)b0 * h->Dtot, skip_idx, out + off, final_mode, st);
         if (rc) return rc;
-        const size_t bytes = (size_t)nb * S * S * 3 * sizeof(float);
+        const size_t bytes = (size_t)nb * S * S * 3 * esz;
         if (host && ride) {
           if (h->ride.left16)  // what no launch took (a decoder without carrying levels): plain copy, in order
             FH_CHECK_HIP(hipMemcpyAsync(h->ride.dst_host, h->ride.src, h->ride.left16 * 16, hipMemcpyDeviceToHost, st));
@@ -1274,10 +1280,11 @@ int float_dec_set_feats16(float_dec_t* h, const void* const* feats16, int32_t n_
   return FLOAT_OK;
 }
 
-static int dec_run(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, float* out, int mode, void* stream) {
-  FH_REQUIRE(h && s_r && r_d && out, "null argument to float_dec_frames");
+static int dec_run(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, void* out, int mode, void* stream) {
+  FH_REQUIRE(h && s_r && r_d && out, "null argument to float_dec_frames%s", mode == 3 ? "_u8" : "");
   FH_REQUIRE(h->feats_set, "float_dec_set_feats must be called before decoding");
   FH_REQUIRE(n_frames >= 1, "n_frames must be >= 1 (got %d)", n_frames);
+  FH_REQUIRE(mode != 3 || (uintptr_t)out % 4 == 0, "float_dec_frames_u8: out_hwc must be 4-byte aligned (the last-level kernel stores dwords)");
   hipStream_t st = (hipStream_t)stream;
   return DEC_DISPATCH(h->cfg.dtype, frames_impl<T>(h, s_r, r_d, n_frames, out, mode, st));
 }
@@ -1286,24 +1293,40 @@ int float_dec_frames(float_dec_t* h, const float* s_r, const float* r_d, int32_t
   return dec_run(h, s_r, r_d, n_frames, out_hwc, 1, stream);
 }
 
-int float_dec_frames_host(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, float* out_hwc, float* host_hwc,
-                          void* stream, void* copy_stream) {
-  FH_REQUIRE(h && s_r && r_d && out_hwc && host_hwc, "null argument to float_dec_frames_host");
+// float_dec_frames_host (mode 1, float) and float_dec_frames_host_u8 (mode 3, uint8_t)
+static int dec_run_host(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, void* out_hwc, void* host_hwc, int mode,
+                        void* stream, void* copy_stream) {
+  FH_REQUIRE(h && s_r && r_d && out_hwc && host_hwc, "null argument to float_dec_frames_host%s", mode == 3 ? "_u8" : "");
   FH_REQUIRE(h->feats_set, "float_dec_set_feats must be called before decoding");
   FH_REQUIRE(n_frames >= 1, "n_frames must be >= 1 (got %d)", n_frames);
+  FH_REQUIRE(mode != 3 || (uintptr_t)out_hwc % 4 == 0, "float_dec_frames_host_u8: out_hwc must be 4-byte aligned (the last-level kernel stores dwords)");
   hipStream_t st = (hipStream_t)stream, cs = copy_stream ? (hipStream_t)copy_stream : st;
   // Is host_hwc memory a kernel may store through?  Only pinned (hipHostMalloc) or registered (hipHostRegister) host memory
   // has a device-side address; for anything else - pageable memory - the frames go by hipMemcpyAsync behind each batch.
-  float* host_dev = nullptr;
+  void* host_dev = nullptr;
   {
     hipPointerAttribute_t at;
     memset(&at, 0, sizeof(at));
     if (hipPointerGetAttributes(&at, host_hwc) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer)
-      host_dev = reinterpret_cast<float*>(at.devicePointer);
+      host_dev = at.devicePointer;
     else
       (void)hipGetLastError();  // "invalid value" for pageable memory: not an error of this call
   }
-  return DEC_DISPATCH(h->cfg.dtype, frames_impl<T>(h, s_r, r_d, n_frames, out_hwc, 1, st, host_hwc, cs, host_dev));
+  return DEC_DISPATCH(h->cfg.dtype, frames_impl<T>(h, s_r, r_d, n_frames, out_hwc, mode, st, host_hwc, cs, host_dev));
+}
+
+int float_dec_frames_host(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, float* out_hwc, float* host_hwc,
+                          void* stream, void* copy_stream) {
+  return dec_run_host(h, s_r, r_d, n_frames, out_hwc, host_hwc, 1, stream, copy_stream);
+}
+
+int float_dec_frames_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, uint8_t* out_hwc, void* stream) {
+  return dec_run(h, s_r, r_d, n_frames, out_hwc, 3, stream);
+}
+
+int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, uint8_t* out_hwc, uint8_t* host_hwc,
+                             void* stream, void* copy_stream) {
+  return dec_run_host(h, s_r, r_d, n_frames, out_hwc, host_hwc, 3, stream, copy_stream);
 }
 
 int float_dec_saturation(float_dec_t* h, uint64_t* total, uint64_t* per_site, int32_t reset, void* stream) {

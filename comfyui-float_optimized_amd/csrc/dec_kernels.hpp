@@ -357,8 +357,8 @@ struct FlowArgs {
   float* flow_out;     // [F][R][R][4]
   float* rgb_out;      // [F][R][R][4]
   const float* lin;    // [R] identity grid: np.linspace(-1, 1, R) (float64) cast to float32
-  float* final_out;    // last level: frames
-  int final_mode;      // 0: none, 1: HWC clamp(-1,1)*0.5+0.5 (FLOAT.py:149-152), 2: raw CHW
+  void* final_out;     // last level: frames (float, mode 3: uint8_t)
+  int final_mode;      // 0: none, 1: HWC clamp(-1,1)*0.5+0.5 (FLOAT.py:149-152), 2: raw CHW, 3: HWC uint8 = dec_quant8(mode 1's value)
   int write_pyr;       // store flow_out / rgb_out (0 on the last level: nobody reads them)
   int F, R, C, ld_s;
   int nbands, band_pix;  // the image is cut into nbands runs of band_pix consecutive pixels (multiple of gpb*PIX)
@@ -416,6 +416,14 @@ __device__ __forceinline__ float fh_sigmoid_t(float x) {
   return EXACT ? 1.f / d : __builtin_amdgcn_rcpf(d);
 }
 
+// final_mode 3: the 8-bit value of a frame sample.  y is exactly what final_mode 1 stores (the product by 0.5 is exact, so a
+// fused multiply-add changes nothing); one multiply and rintf (round half to even) are the only rounding steps, and there is
+// no add behind the multiply for the compiler to contract: bit-identical to torch.round(frames_fp32 * 255).to(torch.uint8).
+__device__ __forceinline__ unsigned dec_quant8(float v) {
+  const float y = fminf(fmaxf(v, -1.f), 1.f) * 0.5f + 0.5f;
+  return (unsigned)rintf(y * 255.0f);
+}
+
 // One run of PIX consecutive pixels of a row (first pixel p0 = Y * R + X0 of frame f) for one lane group: ToFlow (1x1
 // modulated conv + up-sampled previous flow -> tanh / sigmoid), grid_sample of the skip features, blend, ToRGB, the pyramids,
 // the next level's input, the final frame.  xu[k] = this lane's 8 channels (c0 ..) of conv2's output at pixel k.
@@ -429,6 +437,7 @@ struct FlowFrame {
   float *flow_out, *rgb_out;      // this frame's pyramids
   float* final_hwc;               // this frame's output image (final_mode 1)
   float* final_chw;               // this frame's raw output (final_mode 2)
+  unsigned char* final_u8;        // this frame's 8-bit output image (final_mode 3)
   typename T::elem* xnext;        // this frame's next-level input or nullptr
 };
 template <class T>
@@ -445,8 +454,9 @@ __device__ __forceinline__ FlowFrame<T> dec_flow_frame(const FlowArgs& g, int f)
   ff.prgb = g.prgb ? g.prgb + (size_t)f * npp * 4 : nullptr;
   ff.flow_out = g.flow_out ? g.flow_out + (size_t)f * npix * 4 : nullptr;
   ff.rgb_out = g.rgb_out ? g.rgb_out + (size_t)f * npix * 4 : nullptr;
-  ff.final_hwc = g.final_out ? g.final_out + (size_t)f * npix * 3 : nullptr;
+  ff.final_hwc = g.final_out ? reinterpret_cast<float*>(g.final_out) + (size_t)f * npix * 3 : nullptr;
   ff.final_chw = ff.final_hwc;
+  ff.final_u8 = g.final_out ? reinterpret_cast<unsigned char*>(g.final_out) + (size_t)f * npix * 3 : nullptr;
   ff.xnext = g.xnext ? reinterpret_cast<typename T::elem*>(g.xnext) + (size_t)f * npix * g.C : nullptr;
   return ff;
 }
@@ -630,6 +640,16 @@ __device__ __forceinline__ void dec_flow_pixels(const FlowArgs& g, const FlowFra
         fo[0] = v0;
         fo[npix] = v1;
         fo[2 * (size_t)npix] = v2;
+      }
+      if constexpr (LAST) {
+        // 8-bit frames of the models whose last level runs here (<= 256 px, or the ToFlow epilogue switched off): three byte
+        // stores per pixel, not packed - the 512-px product path (dec_flowlast_kernel) is the one that packs
+        if (g.final_mode == 3) {
+          unsigned char* fo = ff.final_u8 + po * 3u;
+          fo[0] = (unsigned char)dec_quant8(v0);
+          fo[1] = (unsigned char)dec_quant8(v1);
+          fo[2] = (unsigned char)dec_quant8(v2);
+        }
       }
     }
   }
@@ -1884,7 +1904,11 @@ __global__ __launch_bounds__(64) void dec_flowfrag_kernel(typename T::pack8* __r
 // The last level after dec_conv16_kernel<.., FLOWM = 1>: one lane per pixel, no channels anywhere.  ToFlow's sums come from
 // g.oflow, the warped-and-converted features are four taps of G (dec_feat_rgb_kernel), the rest is dec_flow_pixels' owner-lane
 // arithmetic: + bias + Upsample(previous flow) -> tanh / sigmoid -> sample position -> ToRGB -> + Upsample(previous rgb) -> frame.
-template <class T>
+// U8 (final_mode 3): the frame leaves as HWC uint8.  A lane's pixel is 3 bytes, a quad of lanes owns 12 contiguous bytes = three
+// aligned dwords (R * R is a multiple of 256 here and the frame base 4-byte aligned, float_dec_frames_u8): every lane packs
+// its pixel into 24 bits, takes its right-hand neighbour's through a quad-permute DPP move, and lanes 0..2 of the quad each
+// store one dword - 48 dword stores per wave over 192 contiguous bytes, no byte stores, no LDS, no barrier.
+template <class T, bool U8 = false>
 __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
   DEC_COPY_PROLOGUE(g, bid)
   const int R = g.R, npix = R * R, Rp = R >> 1;
@@ -1942,7 +1966,15 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
     *reinterpret_cast<float4*>(ff.flow_out + po * 4u) = float4{f0, f1, f2, 0.f};
     *reinterpret_cast<float4*>(ff.rgb_out + po * 4u) = float4{v0, v1, v2, 0.f};
   }
-  if (g.final_mode == 1) {
+  if constexpr (U8) {
+    const unsigned w = dec_quant8(v0) | (dec_quant8(v1) << 8) | (dec_quant8(v2) << 16);
+    // quad_perm [1, 2, 3, 3]: lane j of a quad reads lane j + 1's word (whole quads are live: npix % 4 == 0)
+    const unsigned wn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)w, 0xF9, 0xF, 0xF, false);
+    const unsigned j = threadIdx.x & 3u;
+    // the quad's 12 bytes are w0 w1 w2 w3 at 24 bits each; dword j = bits [32 j, 32 j + 32) = w_j >> 8 j | w_(j+1) << (24 - 8 j)
+    const unsigned d = (w >> (8u * j)) | (wn << (24u - 8u * j));
+    if (j < 3u) *reinterpret_cast<unsigned*>(ff.final_u8 + (po >> 2) * 12u + j * 4u) = d;
+  } else if (g.final_mode == 1) {
     typedef float f3v __attribute__((ext_vector_type(3)));
     f3v o3 = {fminf(fmaxf(v0, -1.f), 1.f) * 0.5f + 0.5f, fminf(fmaxf(v1, -1.f), 1.f) * 0.5f + 0.5f,
               fminf(fmaxf(v2, -1.f), 1.f) * 0.5f + 0.5f};

@@ -86,15 +86,15 @@ class SynthesisHIP:
             native.check(native.lib().float_dec_set_feats16(self._h, ptrs, len(bufs), native.DTYPES[dtype or self.dtype],
                                                             native.stream_ptr(self.device)))
 
-    def _run(self, fn, s_r, r_d, shape):
+    def _run(self, fn, s_r, r_d, shape, out_dtype=torch.float32):
         s_r = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         if s_r.numel() != self.style_dim:
             raise ValueError("s_r must have %d elements (decoder batch is 1, FLOAT.py:140)" % self.style_dim)
         T = r_d.shape[0]
-        out = torch.empty((T,) + shape, device=self.device, dtype=torch.float32)
+        out = torch.empty((T,) + shape, device=self.device, dtype=out_dtype)
         with torch.cuda.device(self.device):
-            native.check(fn(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, native.dev_ptr(out),
+            native.check(fn(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, C.c_void_p(out.data_ptr()),
                             native.stream_ptr(self.device)))
         return out
 
@@ -104,6 +104,14 @@ class SynthesisHIP:
         if s_r_feats is not None:
             self.set_feats(s_r_feats)
         return self._run(native.lib().float_dec_frames, s_r, r_d, (self.size, self.size, 3))
+
+    @torch.no_grad()
+    def decode_u8(self, s_r, r_d, s_r_feats=None):
+        """decode_latent_into_processed_images as 8-bit frames (float_dec_frames_u8): (T, H, W, 3) uint8 on the GPU, quantised
+        by the last-level kernel - bitwise torch.round(frames_fp32 * 255).to(torch.uint8) of the same handle."""
+        if s_r_feats is not None:
+            self.set_feats(s_r_feats)
+        return self._run(native.lib().float_dec_frames_u8, s_r, r_d, (self.size, self.size, 3), torch.uint8)
 
     def saturation(self, reset=False, per_site=False):
         """(thread, tile) groups of 16-bit activation stores that held an inf / NaN since create / the last reset
@@ -120,7 +128,8 @@ class SynthesisHIP:
     @torch.no_grad()
     def decode_into_host(self, s_r, r_d, host, staging=None, copy_stream=None):
         """decode_latent_into_processed_images with the reference's destination (a pre-allocated CPU tensor, FLOAT.py:139):
-        `host` (T, size, size, 3) fp32.  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
+        `host` (T, size, size, 3) fp32, or uint8 for 8-bit frames (float_dec_frames_host_u8; the staging tensor has the same
+        dtype, one of another dtype is replaced).  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
         workgroups inside the launches of batch i+1 (or, with `copy_stream`, copied on that stream while the next batch
         renders - see include/float_hip.h for why that form does not pay on MI355X).  Pageable: accepted, one staged
         hipMemcpyAsync behind each batch (the operator asks the runtime what `host` is, nothing is assumed).  Returns the
@@ -129,13 +138,18 @@ class SynthesisHIP:
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         T = r_d.shape[0]
         shape = (T, self.size, self.size, 3)
-        if tuple(host.shape) != shape or host.dtype != torch.float32 or host.is_cuda or not host.is_contiguous():
-            raise ValueError("host must be a contiguous CPU float32 tensor of shape %s" % (shape,))
-        if staging is None or tuple(staging.shape) != shape:
-            staging = torch.empty(shape, device=self.device, dtype=torch.float32)
+        if host.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("host must be float32 or uint8 (got %s)" % (host.dtype,))
+        if tuple(host.shape) != shape or host.is_cuda or not host.is_contiguous():
+            raise ValueError("host must be a contiguous CPU float32 or uint8 tensor of shape %s" % (shape,))
+        if (staging is None or tuple(staging.shape) != shape or staging.dtype != host.dtype or not staging.is_cuda
+                or not staging.is_contiguous()):
+            staging = torch.empty(shape, device=self.device, dtype=host.dtype)
+        L = native.lib()
+        fn = L.float_dec_frames_host_u8 if host.dtype == torch.uint8 else L.float_dec_frames_host
         with torch.cuda.device(self.device):
-            native.check(native.lib().float_dec_frames_host(
-                self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, native.dev_ptr(staging), C.c_void_p(host.data_ptr()),
+            native.check(fn(
+                self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, C.c_void_p(staging.data_ptr()), C.c_void_p(host.data_ptr()),
                 native.stream_ptr(self.device), C.c_void_p(copy_stream.cuda_stream) if copy_stream is not None else None))
         return staging
 

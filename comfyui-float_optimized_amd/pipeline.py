@@ -142,6 +142,23 @@ def verify_decoder(dec_state, size, s_r, feats, r_d, frames_dev, k, device="cuda
     return dict(decoder=cmp_summary(rows.tolist(), seg), k=k, build_ms=build_ms, hbm_bytes=int(hbm))
 
 
+def _frame_dtype(dtype):
+    """The two frame formats the decoder hands over: fp32 in [0,1], or uint8 quantised on the device."""
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError("frames leave the decoder as torch.float32 or torch.uint8 (got %r)" % (dtype,))
+    return dtype
+
+
+def _resolve_out_dtype(out, out_dtype):
+    """The frame format of a hand-over call: a caller-supplied `out` fixes it, `out_dtype` alone selects it (default fp32), and
+    the two must not contradict each other."""
+    if out is not None:
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError("out is %s but out_dtype asks for %s" % (out.dtype, out_dtype))
+        return _frame_dtype(out.dtype)
+    return _frame_dtype(torch.float32 if out_dtype is None else out_dtype)
+
+
 class FloatHotPath:
     def __init__(self, fmt_state, dec_state, cfg: FmtConfig = None, device="cuda:0", size=512, fmt_dtype="fp16",
                  dec_dtype="fp16", max_frames=32, use_graph=2, max_batch=1):
@@ -266,23 +283,26 @@ class FloatHotPath:
             rd = rd[frame_range[0]:frame_range[1]]
         return self.dec.decode_latent_into_processed_images(s_r, rd)
 
-    def staging(self, n_frames):
-        """Device-side frame buffer of float_dec_frames_host, cached per clip length (786 MB for 250 frames at 512 px;
-        sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
+    def staging(self, n_frames, dtype=torch.float32):
+        """Device-side frame buffer of float_dec_frames_host[_u8], cached per clip length and dtype (786 MB for 250 fp32 frames
+        at 512 px, 197 MB as uint8; sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
         hands the block of a released earlier result back without a new hipHostMalloc), because ComfyUI keeps node outputs
         alive across executions and a re-used buffer would silently overwrite them."""
         cache = self.__dict__.setdefault("_staging", {})
         shape = (n_frames, self.size, self.size, 3)
-        if shape not in cache:
-            cache.clear()  # one clip length at a time
-            cache[shape] = torch.empty(shape, device=self.device, dtype=torch.float32)
-        return cache[shape]
+        if (shape, dtype) not in cache:
+            cache.clear()  # one clip length and format at a time
+            cache[(shape, dtype)] = torch.empty(shape, device=self.device, dtype=_frame_dtype(dtype))
+        return cache[(shape, dtype)]
 
     @torch.no_grad()
-    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None):
+    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None, out_dtype=None):
         """Frames of one clip (r_d (T,512)) into pinned host memory through float_dec_frames_host: the frames of batch i cross
         PCIe inside the launches of batch i+1.  Returns the host tensor (T,H,W,3); it is complete once the current stream has
-        been synchronised (the callers that hand it to the user do that)."""
+        been synchronised (the callers that hand it to the user do that).  out_dtype: torch.float32 (default) or torch.uint8
+        (8-bit frames quantised on the device, a quarter of the bytes); a caller-supplied `out` fixes the dtype, and an
+        out_dtype that contradicts it is a ValueError."""
+        out_dtype = _resolve_out_dtype(out, out_dtype)
         if feats is not None:
             self.dec.set_feats(feats)
         rd = r_d[0] if r_d.dim() == 3 else r_d
@@ -297,10 +317,10 @@ class FloatHotPath:
         inflight = self.__dict__.setdefault("_host_inflight", [])
         inflight[:] = [(t, e) for t, e in inflight if not e.query()]
         if out is None:
-            out = torch.empty((n, self.size, self.size, 3), dtype=torch.float32, pin_memory=True)
+            out = torch.empty((n, self.size, self.size, 3), dtype=out_dtype, pin_memory=True)
         # (the frames by hipMemcpyAsync on a second stream instead of copy workgroups inside the next batch's launches: 121.4-122.1 vs
         # 105.7-106.8 ms per clip on the round-6 kernels, as in round 3 - decoder.decode_into_host(copy_stream=) keeps the form)
-        self.dec.decode_into_host(s_r, rd, out, self.staging(n))
+        self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype))
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         inflight.append((out, ev))
@@ -315,15 +335,17 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                         noise=None, frame_range=None, out=None, return_rd=False):
+                         noise=None, frame_range=None, out=None, return_rd=False, out_dtype=None):
         """The product's hot path for one clip (B = 1): conditioning tensors in HBM -> frames in pinned host memory, the
-        reference's destination (FLOAT.py:139,157-167).  This is what InferenceAgent.run_inference, FloatProcess and bench.py run."""
+        reference's destination (FLOAT.py:139,157-167).  This is what InferenceAgent.run_inference, FloatProcess and bench.py run.
+        out_dtype: as in decode_to_host (torch.uint8 = 8-bit frames)."""
+        out_dtype = _resolve_out_dtype(out, out_dtype)
         if feats is not None:
             self.dec.set_feats(feats)
         if noise is None:
             noise = draw_noise(self.n_chunks(wa.shape[1]), 1, self.cfg, seed)
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
-        host = self.decode_to_host(s_r, r_d, None, frame_range, out)
+        host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype)
         return (host, r_d) if return_rd else host
 
     def _overlap_streams(self, mode):
@@ -350,12 +372,14 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host_overlap(self, r_s, wa, we, s_r, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, noise=None,
-                                 out=None, mode="prio", return_rd=False):
+                                 out=None, mode="prio", return_rd=False, out_dtype=None):
         """generate_to_host with the two stages pipelined (FLOAT.py runs 209-253 then 113-169; here window k is decoded and
         handed to the host on a second stream while the chain samples window k + 1).  Same kernels on the same operands as
         the sequential order, per-window decode batches (50 frames = 32 + 18 instead of 250 = 7 x 32 + 26): frames bitwise
         equal to generate_to_host (decode batching does not change a frame, tests/test_dec_gpu.py).  FLOAT_AMD_OVERLAP
-        selects it in InferenceAgent.infer_device; what it measures against the sequential order: DESIGN.md section 7."""
+        selects it in InferenceAgent.infer_device; what it measures against the sequential order: DESIGN.md section 7.
+        out_dtype: as in decode_to_host (torch.uint8 = 8-bit frames)."""
+        out_dtype = _resolve_out_dtype(out, out_dtype)
         T = wa.shape[1]
         dev = self.device
         if noise is None:
@@ -367,8 +391,8 @@ class FloatHotPath:
         inflight = self.__dict__.setdefault("_host_inflight", [])
         inflight[:] = [(t, e) for t, e in inflight if not e.query()]
         if out is None:
-            out = torch.empty((T, self.size, self.size, 3), dtype=torch.float32, pin_memory=True)
-        staging = self.staging(T)
+            out = torch.empty((T, self.size, self.size, 3), dtype=out_dtype, pin_memory=True)
+        staging = self.staging(T, out_dtype)
         s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
         with torch.cuda.stream(s_fmt):
             ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)

@@ -257,10 +257,14 @@ class InferenceAgent:
         return self.conditions_device(s, a, emo)
 
     @torch.no_grad()
-    def infer_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out=None):
+    def infer_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out=None,
+                     out_dtype=None):
         """Portrait and waveform in HBM -> (T,H,W,3) fp32 frames in [0,1] in pinned host memory: every operator of the path and
         the hand-over (frames of decode batch i leave inside the launches of batch i+1, float_dec_frames_host).  bench.py
-        times exactly this call.  Like the reference, the grid size comes from opt.nfe (FLOAT.py:188)."""
+        times exactly this call.  Like the reference, the grid size comes from opt.nfe (FLOAT.py:188).
+        out_dtype=torch.uint8: 8-bit frames, quantised by the decoder's last kernel (round(255 * frame), bitwise what rounding the
+        fp32 frames gives) - a quarter of the staging, pinned and PCIe bytes; default (None) fp32.  A caller-supplied `out`
+        fixes the dtype; contradicting it is a ValueError."""
         self.to_target()  # no-op while resident
         c = self.conditions_device(s, a, emo)  # encoder kernels enqueued; nothing below waits for them on the host
         n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
@@ -269,20 +273,27 @@ class InferenceAgent:
         verify = precision_policy(self._precision_checked) == "check"  # FLOAT_AMD_VERIFY, default off: nothing below changes
         if ov and ov != "0":
             host = self.G.generate_to_host_overlap(c["r_s"], c["wa"], c["we"], c["s_r"], self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                                   e_cfg_scale, noise=noise, out=out, mode=ov, return_rd=verify)
+                                                   e_cfg_scale, noise=noise, out=out, mode=ov, return_rd=verify,
+                                                   out_dtype=out_dtype)
         else:
             host = self.G.generate_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                           e_cfg_scale, noise=noise, out=out, return_rd=verify)
+                                           e_cfg_scale, noise=noise, out=out, return_rd=verify, out_dtype=out_dtype)
         host, r_d = host if verify else (host, None)
         torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
         self.G.release_host_inflight()
         bad = self.check_range("InferenceAgent.infer_device", allow_rebuild=True)
         if bad == "rebuilt":
-            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out)  # once more, in the wider types
+            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype)  # once more, in the wider types
         if verify and not bad:  # a range failure has been reported already: the frames are wrong for a reason that is known
+            # 8-bit output: the staging buffer holds quantised frames, so the first k frames are decoded once more in the fp32
+            # form by the same handle (a frame does not depend on its batch: bitwise what the fp32 staging buffer would hold)
+            frames_dev = None
+            if host.dtype == torch.uint8:
+                k = min(verify_frames_default(), c["T"], self.cfg.num_frames_for_clip)
+                frames_dev = self.G.dec.decode_latent_into_processed_images(c["s_r"], r_d[0, :k])
             if self.check_precision("InferenceAgent.infer_device", s, c, noise, r_d, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                    allow_rebuild=True) == "rebuilt":
-                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out)  # once more, in fp32
+                                    allow_rebuild=True, frames_dev=frames_dev) == "rebuilt":
+                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype)  # once more, in fp32
         return host
 
     def range_counts(self, reset=True):
@@ -322,11 +333,13 @@ class InferenceAgent:
         return bad
 
     @torch.no_grad()
-    def check_precision(self, where, s, c, noise, r_d, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, allow_rebuild=False):
+    def check_precision(self, where, s, c, noise, r_d, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, allow_rebuild=False,
+                        frames_dev=None):
         """The fp16 PRECISION guard, the sibling of check_range (which sees only values beyond fp16's range): after a clip has
         arrived, run the fp32 verification mode of the FMT and the decoder on a small sample of it and compare on the device
         (FloatHotPath.verify_precision).  s: the portrait (1,3,H,W) of the clip, c: its conditions_device result, noise / r_d:
-        the noise it was sampled from and the latents it gave; the device-side frames are the hot path's staging buffer.
+        the noise it was sampled from and the latents it gave; the device-side frames are the hot path's fp32 staging buffer, or
+        `frames_dev` (fp32, at least the first k frames) where the clip left as 8-bit frames.
           FLOAT_AMD_VERIFY         off (default: infer_device never calls this) | first (the first clip after the operators
                                    were built or rebuilt) | always
           FLOAT_AMD_VERIFY_ACTION  warn (default) | raise (Fp16PrecisionError) | auto: warn, REBUILD the operator at fault in
@@ -347,7 +360,7 @@ class InferenceAgent:
         try:
             feats = enc32.encode_image_into_latent(s, want_feats=True)[2]
             rep = self.G.verify_precision(c["r_s"], c["wa"], c["we"], c["s_r"], feats, o.nfe, a_cfg_scale, r_cfg_scale,
-                                          e_cfg_scale, noise, r_d, self.G.staging(T), k)
+                                          e_cfg_scale, noise, r_d, frames_dev if frames_dev is not None else self.G.staging(T), k)
         finally:
             enc32.close()
         del feats
@@ -377,12 +390,13 @@ class InferenceAgent:
         return fault
 
     @torch.no_grad()
-    def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None):
+    def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None,
+                           out_dtype=None):
         """B clips of EQUAL length through one stacked FMT chain (float_fmt_sample_batch: every weight is read once per
         evaluation for all of them), then decoded one after the other.  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
         item (FloatProcess uses seed + i, nodes.py:189-209) - each item keeps its own noise stream, so item i is what
         infer_device gives for it alone (bit for bit where the GEMM tilings coincide, within the fp16 tolerance otherwise).
-        Returns a list of (T,H,W,3) pinned host tensors."""
+        Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device."""
         self.to_target()
         B = len(items)
         seeds = list(seeds) if seeds is not None else [self.opt.seed] * B
@@ -409,7 +423,7 @@ class InferenceAgent:
         for i in range(B):
             # decodes queue back to back: the last frames of item i cross PCIe inside the launches of item i + 1
             self.G.dec.set_feats16(feats[i], self.enc.dtype)
-            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i]))
+            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i], out_dtype=out_dtype))
         torch.cuda.current_stream(self.rank).synchronize()
         self.G.release_host_inflight()
         self.check_range("InferenceAgent.infer_device_batch")

@@ -22,7 +22,7 @@
  *     allocation happens inside the run-time calls (float_aud_reserve is the explicit exception).
  *     Every run-time call enqueues kernels only (device-to-device moves included: memcpy / memset
  *     nodes of a caller's stream capture did not replay reproducibly on ROCm 7.2), except
- *     float_dec_frames_host, whose last batch goes to the host by hipMemcpyAsync.  Capture by the
+ *     float_dec_frames_host[_u8], whose last batch goes to the host by hipMemcpyAsync.  Capture by the
  *     caller (hipStreamBeginCapture on `stream`) is tested for the float_fmt_* calls.
  *   - calls on one handle must be serialised by the caller; different handles are independent.
  */
@@ -36,8 +36,9 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison) are purely additive - no
- * existing signature, structure or behaviour changed, so a caller built against the earlier v6 header runs unchanged. */
+/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison) and float_dec_frames_u8 /
+ * float_dec_frames_host_u8 (8-bit frames) are purely additive - no existing signature, structure or behaviour changed, so a
+ * caller built against the earlier v6 header runs unchanged. */
 #define FLOAT_HIP_ABI_VERSION 6
 
 enum {
@@ -222,6 +223,18 @@ int float_dec_frames(float_dec_t* h, const float* s_r, const float* r_d, int32_t
  * Either way, synchronising `stream` (or an event recorded on it) means the frames are in host memory. */
 int float_dec_frames_host(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames,
                           float* out_hwc, float* host_hwc, void* stream, void* copy_stream);
+
+/* 8-bit frames: the same two calls with (n_frames, size, size, 3) uint8_t HWC output, quantised on the device by the kernel
+ * that forms the frame: with y the value float_dec_frames stores, q = (uint8_t) rintf(y * 255.0f) (round half to even) -
+ * bit-identical to rounding the fp32 frames on the host, at a quarter of the device staging, pinned memory and PCIe bytes.
+ * out_hwc must be 4-byte aligned (FLOAT_E_INVALID otherwise: the last-level kernel stores packed dwords).  host_hwc follows
+ * float_dec_frames_host's contract word for word: pinned and 16-byte aligned takes the copy workgroups, anything else
+ * (pageable, misaligned) one hipMemcpyAsync behind each batch; copy_stream as there; synchronising `stream` means the frames are
+ * in host memory.  Both work on FLOAT_DT_FP16 and FLOAT_DT_FP32 handles, and calls of either format may alternate on one handle. */
+int float_dec_frames_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames,
+                        uint8_t* out_hwc, void* stream);
+int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames,
+                             uint8_t* out_hwc, uint8_t* host_hwc, void* stream, void* copy_stream);
 
 /* Shape (channels, resolution) of skip feature i as float_dec_set_feats reads it: feats[i] must hold
  * channels * resolution * resolution floats.  Lets the caller validate tensors wired from an arbitrary encoder. */
