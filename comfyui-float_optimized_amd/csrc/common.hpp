@@ -409,5 +409,13 @@ struct ProfileSlot {
 };
 extern int g_fh_profiling;
 bool fh_prof_pair(int which, hipEvent_t* start, hipEvent_t* stop);
+// A launch that counts toward profiling class `which`: while profiling is on, fh_prof_pair's events go to
+// hipExtLaunchKernelGGL (stamped with the dispatch's own begin / end); otherwise it is a plain hipLaunchKernelGGL.
+template <class K, class... A>
+void fh_launch_prof(int which, K kern, dim3 grid, dim3 block, size_t smem, hipStream_t s, A... args) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (fh_prof_pair(which, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, block, smem, s, e0, e1, 0, args...);
+  else hipLaunchKernelGGL(kern, grid, block, smem, s, args...);
+}
 void fh_prof_begin(int which, hipStream_t s);
 void fh_prof_end(int which, hipStream_t s);

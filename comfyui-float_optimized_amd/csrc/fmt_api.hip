@@ -197,9 +197,7 @@ int launch_wide_t(GemmArgs g, bool prime, hipStream_t s) {
   g.mblk = (mt_total + MTW - 1) / MTW;
   g.ksplit = 1;
   const dim3 grid((g.N / 128) * g.mblk * (g.zcount > 1 ? g.zcount : 1));
-  hipEvent_t e0, e1;
-  if (fh_prof_pair(2, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(NWV * 64), smem, s, e0, e1, 0, g);
-  else hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), smem, s, g);
+  fh_launch_prof(2, kern, grid, dim3(NWV * 64), smem, s, g);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -226,9 +224,7 @@ int launch_dma_t(GemmArgs g, bool prime, hipStream_t s) {
   }
   g.mblk = ((g.M + 15) / 16 + 11) / 12;
   const dim3 grid((g.N / BN) * g.mblk * (g.zcount > 1 ? g.zcount : 1));
-  hipEvent_t e0, e1;
-  if (fh_prof_pair(2, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(NWC * 128), smem, s, e0, e1, 0, g);
-  else hipLaunchKernelGGL(kern, grid, dim3(NWC * 128), smem, s, g);
+  fh_launch_prof(2, kern, grid, dim3(NWC * 128), smem, s, g);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -257,9 +253,7 @@ int launch_big4(const u16* A, const FmtLin& L, float* out, int rows_total, int l
     }
     BigArgs g{A, L.W, L.b, out, rows_total, L.N, L.K, ldo, (rows_total + 191) / 192, L.N / 256};
     const dim3 grid((unsigned)((n_cu / 8) * 8));
-    hipEvent_t e0, e1;
-    if (fh_prof_pair(2, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(256), kBigSmem, s, e0, e1, 0, g);
-    else hipLaunchKernelGGL(kern, grid, dim3(256), kBigSmem, s, g);
+    fh_launch_prof(2, kern, grid, dim3(256), kBigSmem, s, g);
     FH_CHECK_HIP(hipGetLastError());
     return FLOAT_OK;
   }
@@ -320,9 +314,7 @@ int launch_gemm_t(GemmArgs g, bool prime, hipStream_t s) {
   g.mblk = (mt_total + MTW - 1) / MTW;
   if (EPI != EPI_PARTIAL || g.ksplit < 1) g.ksplit = 1;
   dim3 grid((g.N / (NT * 16)) * g.mblk * g.ksplit);
-  hipEvent_t e0, e1;
-  if (fh_prof_pair(0, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, s, e0, e1, 0, g);
-  else hipLaunchKernelGGL(kern, grid, dim3(NW * 64), smem, s, g);
+  fh_launch_prof(0, kern, grid, dim3(NW * 64), smem, s, g);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -377,9 +369,7 @@ int launch_rbs_t(GemmArgs g, bool prime, hipStream_t s) {
   g.mblk = (g.M + ROWS - 1) / ROWS;
   g.touch.W = nullptr;
   const dim3 grid((unsigned)((g.N / BN) * g.mblk * g.ksplit));
-  hipEvent_t e0, e1;
-  if (fh_prof_pair(3, &e0, &e1)) hipExtLaunchKernelGGL(kern, grid, dim3(512), smem, s, e0, e1, 0, g);
-  else hipLaunchKernelGGL(kern, grid, dim3(512), smem, s, g);
+  fh_launch_prof(3, kern, grid, dim3(512), smem, s, g);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -742,16 +732,8 @@ int launch_attnproj(float_fmt* h, int M, const Lin& proj, hipStream_t s) {
   g.ksplit = c.heads / hpw;
   g.mblk = ((M + 15) / 16 + 2) / 3;
   const dim3 grid((unsigned)(g.ksplit * (g.N / (128 / hpw)) * g.mblk));
-  hipEvent_t e0, e1;
-  const bool prof = fh_prof_pair(0, &e0, &e1);
-#define AP_LAUNCH(HPW)                                                                                                                              \
-  do {                                                                                                                                              \
-    if (prof) hipExtLaunchKernelGGL((fmt_attnproj_kernel<T, 3, HPW>), grid, dim3(512), 0, s, e0, e1, 0, h->qkv16, 3 * h->D, g, h->ntok, h->D, c.attn_window); \
-    else hipLaunchKernelGGL((fmt_attnproj_kernel<T, 3, HPW>), grid, dim3(512), 0, s, h->qkv16, 3 * h->D, g, h->ntok, h->D, c.attn_window);         \
-  } while (0)
-  if (hpw == 2) AP_LAUNCH(2);
-  else AP_LAUNCH(1);
-#undef AP_LAUNCH
+  fh_launch_prof(0, hpw == 2 ? fmt_attnproj_kernel<T, 3, 2> : fmt_attnproj_kernel<T, 3, 1>, grid, dim3(512), 0, s, h->qkv16, 3 * h->D, g,
+                 h->ntok, h->D, c.attn_window);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -1015,10 +997,7 @@ template <class T>
 int run_mega(float_fmt* h, int bc, const float* modbuf, bool euler, float dt, float a, float r, float e, hipStream_t s, float* vout_to) {
   float_fmt::MegaPlan& P = h->mega[bc];
   MegaDyn d{modbuf, dt, a, r, e, euler ? 1 : 0, vout_to ? vout_to : h->vout};
-  hipEvent_t e0, e1;
-  if (fh_prof_pair(0, &e0, &e1))
-    hipExtLaunchKernelGGL((fmt_mega_kernel<T>), dim3(kMegaWgs), dim3(512), kMegaSmem, s, e0, e1, 0, P.dev, P.nstage, d, P.ctx, mega_sync_of(h));
-  else hipLaunchKernelGGL((fmt_mega_kernel<T>), dim3(kMegaWgs), dim3(512), kMegaSmem, s, P.dev, P.nstage, d, P.ctx, mega_sync_of(h));
+  fh_launch_prof(0, (fmt_mega_kernel<T>), dim3(kMegaWgs), dim3(512), kMegaSmem, s, P.dev, P.nstage, d, P.ctx, mega_sync_of(h));
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }

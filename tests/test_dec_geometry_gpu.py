@@ -8,9 +8,10 @@ A. 128 / 256 px against the fp64 oracle (oracle/float_oracle.py, itself held to 
    (LIMITS of tests/test_dec_gpu.py).  That the fp32 limits mean something on these inputs is pinned without a GPU by
    tests/test_oracle_golden.py::test_dec_geometry_inputs_are_well_conditioned (fp32 oracle within a quarter of them).
 B. The 64-channel last level of a 256-px decoder: ToFlow in conv2's epilogue (dec_conv16_kernel<T, 4, 3, 3, 0, 1> +
-   dec_flowfrag_kernel + dec_flowlast_kernel) is taken by both element types (float_dec_create: `flow_epi && (cl == 32 ||
-   cl == 64)`), so part A at 256 px holds it to the oracle; the other side of the switch (FLOAT_DEC_FLOW_EPI=0,
-   dec_flow_kernel<.., Last = true> on the stored V, read once per process: child processes) is held here.
+   dec_flowfrag_kernel + dec_flowlast_kernel) is taken by both element types (float_dec_create: `flow_epi &&
+   conv_takes_flow_epi(..)`), so part A at 256 px holds it to the oracle; the other side of the switch (FLOAT_DEC_FLOW_EPI=0,
+   dec_flow_kernel<.., Last = true> on the stored V, read once per process: child processes) is held here, and so is the
+   same route taken because FLOAT_DEC_CONV_BN=32 splits conv2's 64 channels over two workgroups.
 C. A frame's pixels do not depend on the batch it was decoded in, bit for bit, at the frame counts where the geometry changes:
    launch_conv `g.tpw = total >= 16384 ? 4 : (total >= 4096 ? 2 : 1)` (total = 16 x 16 tiles x frames), the frame blocks of the
    generic low-resolution kernel (`g.lnf = 8 - 2 * g.lth`: 16 frames per workgroup at 4 px, 4 at 8 px), launch_flow's band
@@ -116,11 +117,11 @@ torch.save({"frames": frames, "raw": raw, "sat": dec.saturation()}, out)
 '''
 
 
-def run_child(tmp_path, size, dtype, flow_epi):
+def run_child(tmp_path, size, dtype, flow_epi, **switches):
     script = tmp_path / "child.py"
     script.write_text(CHILD % {"root": ROOT})
     out = tmp_path / ("dec_%d_%s_epi%s.pt" % (size, dtype, flow_epi))
-    env = dict(os.environ, FLOAT_DEC_FLOW_EPI=flow_epi)
+    env = dict(os.environ, FLOAT_DEC_FLOW_EPI=flow_epi, **switches)
     subprocess.run([sys.executable, str(script), str(size), dtype, str(out)], check=True, env=env, cwd=ROOT, timeout=600)
     return torch.load(out)
 
@@ -148,6 +149,17 @@ def test_flow_routes_agree_256_fp16(tmp_path):
     print("B 256 px fp16: ToFlow in the epilogue vs flow kernel %.1f dB (max %.2e, mean %.2e); oracle %.1f / %.1f dB" % (
         p, float(d.max()), float(d.mean()), p_epi, p_old))
     assert p >= max(p_epi, p_old) + 20.0
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "fp16"])
+def test_conv_bn32_takes_the_flow_kernel_256(tmp_path, dtype):
+    """FLOAT_DEC_CONV_BN=32 (read once per handle: a child process) on the 64-channel last level: conv2 runs in two 32-channel
+    blocks, so ToFlow cannot ride in its epilogue (it needs the whole channel range in one workgroup) and the level goes through
+    dec_flow_kernel on the stored V.  One function (conv_bn, dec_launch.hpp) now answers both launch_conv and run_level's `epi`;
+    before, `epi` did not know the block size and the decode failed with "ToFlow epilogue needs the layer's 64 output channels
+    in one block of 32".  Limits: part A's at 256 px."""
+    r = run_child(tmp_path, 256, dtype, "1", FLOAT_DEC_CONV_BN="32")
+    check_against_oracle(256, dtype, r["frames"], r["raw"], r["sat"], "B 32-channel blocks")
 
 
 # ---- C: frame-count geometry, bit for bit ----

@@ -8,7 +8,7 @@ C=comfyui-float_optimized_amd/csrc
 mkdir -p build_ab
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-pass-failed "$@" -c $C/$UNIT -o build_ab/$NAME.o
 OBJS=""
-for o in misc fmt_api dec_api enc_api aud_api; do
+for o in misc fmt_api dec_api enc_api aud_api cmp_api; do
   if [ "$o.hip" = "$UNIT" ]; then OBJS="$OBJS build_ab/$NAME.o"; else OBJS="$OBJS $C/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build_ab/$NAME.so $OBJS
