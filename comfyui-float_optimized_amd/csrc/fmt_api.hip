@@ -1,4 +1,6 @@
-// C-ABI entry points of the FMT operator (include/float_hip.h) and the host-side launch chain.
+// C-ABI entry points of the FMT operator (include/float_hip.h): the handle, the evaluation chain and its hipGraph cache, the
+// incremental sampler and the GEMM service.  Packing, launchers and the persistent kernel's host side: fmt_weights.hpp,
+// fmt_launch.hpp, fmt_mega.hpp.
 #include <math.h>
 #include <stdlib.h>
 
@@ -6,10 +8,9 @@
 #include "fmt_kernels.hpp"
 #include "fmt_rb_kernels.hpp"
 #include "fmt_big_kernels.hpp"
+#include "fmt_launch.hpp"
 
 namespace {
-
-typedef FmtLin Lin;
 
 struct Blk {
   Lin qkv, proj, fc1, fc2;
@@ -82,9 +83,9 @@ struct float_fmt {
   } job;
 };
 
-namespace {
+#include "fmt_mega.hpp"
 
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
+namespace {
 
 // Stream-ordered device copies as kernel launches (see fmt_copy_kernel: memcpy / memset nodes of a caller's capture did not
 // replay reproducibly).
@@ -96,647 +97,14 @@ int dev_copy2d(float* dst, size_t dpitch, const float* src, size_t spitch, int w
 }
 int dev_copy(float* dst, const float* src, size_t n, hipStream_t s) { return dev_copy2d(dst, n, src, n, (int)n, 1, s); }
 int dev_zero(float* dst, size_t n, hipStream_t s) { return dev_copy2d(dst, n, nullptr, n, (int)n, 1, s); }
+int copy_or_zero(float* dst, const float* src, size_t n, hipStream_t s) { return src ? dev_copy(dst, src, n, s) : dev_zero(dst, n, s); }
 
-
-// Weight packing ON THE DEVICE (round 6): the fp32 rows of a Linear cross PCIe once as they are and a kernel writes the
-// fragment-major image - 8 consecutive k of a row = one pack (fmt_pack_off), converted with the conversion every activation
-// store uses (round to nearest even, fp16 saturating at 65504).  On the host the same loop ran at ~5 ns per weight on ONE
-// thread: 0.86 s for the FMT, 1.74 s for the speech-emotion model, 3.4 s per InferenceAgent.to_target(); now the time of the
-// copies (tools/probes/retarget_time.py; INTEGRATION.md "Residency").  FLOAT_PACK_HOST=1 keeps the host loop (the A/B switch;
-// the two images are equal bit for bit for finite weights - tests/test_variants_gpu.py).
-template <class T>
-__global__ __launch_bounds__(256) void fmt_pack_w_kernel(typename T::elem* __restrict__ out, const float* __restrict__ w, int N_each,
-                                                         int K, int KB, int n0) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int gpr = KB * 4;  // packs per row
-  const int n = (int)(idx / gpr), k0 = (int)(idx % gpr) * 8;
-  if (n >= N_each) return;
-  typename T::pack8 p;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) T::set(p, i, k0 + i < K ? w[(size_t)n * K + k0 + i] : 0.f);
-  T::store8(out + fmt_pack_off(n0 + n, k0, KB), p);
+// What the launchers of fmt_launch.hpp see of the handle, for launches on stream `s`
+FmtLaunch launch_ctx(const float_fmt* h, hipStream_t s) {
+  return FmtLaunch{h->tune, s, h->sat, h->xres, h->slab, h->h16, h->qkv16, h->att16, h->D, h->ntok, h->Ntot, h->Mpad, h->cfg.heads,
+                   h->cfg.attn_window};
 }
 
-template <class T>
-int pack_linear_pool(const FmtTune& tn, DevicePool* pool, const TensorTable& tt, const std::vector<std::string>& names, int N_each,
-                     int K, Lin* out) {
-  // Concatenate the named Linear layers along N (used to fuse every adaLN projection into one GEMM).
-  typedef typename T::elem E;
-  constexpr size_t esz = sizeof(E) / sizeof(u16);  // u16 slots per element (Lin::W is typed u16* for every operand type)
-  const int Kp = round_up(K, 128);
-  const int N = N_each * (int)names.size();
-  const bool on_host = tn.pack_host;
-  std::vector<E> hw;
-  if (on_host) hw.assign((size_t)N * Kp, (E)0);
-  std::vector<float> hb(N, 0.f);
-  int rc;
-  if ((rc = pool->alloc(&out->W, (size_t)N * Kp * esz, false))) return rc;
-  if ((rc = pool->alloc(&out->b, hb.size(), false))) return rc;
-  float* stage = nullptr;  // one Linear's fp32 rows on the device
-  if (!on_host) FH_CHECK_HIP(hipMalloc(&stage, (size_t)N_each * K * sizeof(float)));
-  struct Free {
-    float* p;
-    ~Free() {
-      if (p) (void)hipFree(p);
-    }
-  } free_stage{stage};
-  int n0 = 0;
-  for (const std::string& nm : names) {
-    const float_tensor_t* w = tt.find(nm + ".weight");
-    const float_tensor_t* b = tt.find(nm + ".bias");
-    if (!w || !b) {
-      fh_set_error("missing checkpoint tensor '%s.weight/.bias'", nm.c_str());
-      return FLOAT_E_MISSING;
-    }
-    if (w->ndim != 2 || w->shape[0] != N_each || w->shape[1] != K || TensorTable::numel(b) != N_each) {
-      fh_set_error("tensor '%s.weight' has shape (%lld,%lld), expected (%d,%d)", nm.c_str(), (long long)w->shape[0],
-                   (long long)(w->ndim > 1 ? w->shape[1] : 0), N_each, K);
-      return FLOAT_E_INVALID;
-    }
-    if (on_host) {
-      for (int n = 0; n < N_each; ++n) {
-        const float* src = w->data + (size_t)n * K;
-        for (int k = 0; k < K; ++k) hw[fmt_pack_off(n0 + n, k, Kp / 32)] = T::host_from_float(src[k]);
-      }
-    } else {
-      // (null stream: the copy returns when the rows are on the device, the kernel runs before the next copy into `stage`)
-      FH_CHECK_HIP(hipMemcpy(stage, w->data, (size_t)N_each * K * sizeof(float), hipMemcpyHostToDevice));
-      const size_t packs = (size_t)N_each * (Kp / 8);
-      hipLaunchKernelGGL((fmt_pack_w_kernel<T>), dim3((unsigned)((packs + 255) / 256)), dim3(256), 0, nullptr,
-                         reinterpret_cast<E*>(out->W), stage, N_each, K, Kp / 32, n0);
-      FH_CHECK_HIP(hipGetLastError());
-    }
-    for (int n = 0; n < N_each; ++n) hb[n0 + n] = b->data[n];
-    n0 += N_each;
-  }
-  if (on_host) FH_CHECK_HIP(hipMemcpy(out->W, hw.data(), hw.size() * sizeof(E), hipMemcpyHostToDevice));
-  FH_CHECK_HIP(hipMemcpy(out->b, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!on_host) FH_CHECK_HIP(hipDeviceSynchronize());  // the packed image is complete (and `stage` idle) when the call returns
-  out->N = N;
-  out->K = Kp;
-  return FLOAT_OK;
-}
-
-template <class T>
-int pack_linear(float_fmt* h, const TensorTable& tt, const std::vector<std::string>& names, int N_each, int K, Lin* out) {
-  return pack_linear_pool<T>(h->tune, &h->pool, tt, names, N_each, K, out);
-}
-
-constexpr int kWtRows = 256;  // LayerNorm / attention launches of at most this many rows store write-through (common.hpp, FMT_WT)
-// Wide-N path (fused adaLN projection): LDS-staged A, 128 columns per workgroup (FmtTune::wide_variant picks the kernel).
-template <class T, int MTW, int KCH, int NWV = 4>
-int launch_wide_t(GemmArgs g, bool prime, hipStream_t s) {
-  constexpr int smem = 2 * MTW * KCH * 1024;
-  auto kern = fmt_gemm_wide_kernel<T, MTW, KCH, NWV>;
-  if (prime) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      (void)hipGetLastError();
-    return FLOAT_OK;
-  }
-  const int mt_total = (g.M + 15) / 16;
-  g.mblk = (mt_total + MTW - 1) / MTW;
-  g.ksplit = 1;
-  const dim3 grid((g.N / 128) * g.mblk * (g.zcount > 1 ? g.zcount : 1));
-  fh_launch_prof(2, kern, grid, dim3(NWV * 64), smem, s, g);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
-// 192 x 320 tiles with both operands by LDS-DMA (fmt_gemm_dma_kernel): 8 waves, ring of 4 stages, one workgroup per CU; N in
-// blocks of 320 columns and an even number (>= 4) of k-blocks.  Measured per launch of the hoisted projection (50 x 180 rows,
-// 0.944 TFLOP), rocprofv3, bitwise the same numbers in every form:
-//   register-staged 192 x 128 tile (variant 2)                                   1376 us  (686 TFLOP/s)
-//   LDS-DMA tile, waves in lock step, stores straight from the accumulators      1260
-//   + output through LDS (whole lines per store)                                 1150
-//   + 2 column blocks per XCD group instead of 4 (FLOAT_FMT_ZGROUP)              1045     (variant 6)
-//   + wave rows half a step apart (variant 7, the default)                       1021     (924 TFLOP/s, 37 % of the MFMA peak)
-//   the same with the DMA pieces issued between the MFMA rows                    1115
-// Not faster: 4 waves / 160 columns / ring of 3 with two workgroups per CU (1458), fragment reads spread between the MFMA rows
-// (1172), a staggered start of the first workgroup generation, non-temporal stores.  In-kernel clocks (s_memtime /
-// s_memrealtime) put a 32-step tile at ~49 000 clocks at 2.1 GHz, of which the bare barrier skeleton is a third.
-template <class T, int NWC, int NS, int STG>
-int launch_dma_t(GemmArgs g, bool prime, hipStream_t s) {
-  constexpr int smem = NS * (12 + 5 * NWC) * 1024, BN = 80 * NWC;
-  auto kern = fmt_gemm_dma_kernel<T, NWC, NS, STG>;
-  if (prime) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      (void)hipGetLastError();
-    return FLOAT_OK;
-  }
-  g.mblk = ((g.M + 15) / 16 + 11) / 12;
-  const dim3 grid((g.N / BN) * g.mblk * (g.zcount > 1 ? g.zcount : 1));
-  fh_launch_prof(2, kern, grid, dim3(NWC * 128), smem, s, g);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
-bool dma_shape_ok(const GemmArgs& g, int bn) { return g.N % bn == 0 && g.K % 64 == 0 && g.K >= 128; }
-
-// The hoisted projection of a whole batch of evaluations on DENSE rows: the persistent one-wave-per-SIMD kernel
-// (fmt_big_kernels.hpp), one workgroup per CU.  N in column blocks of 256, eight of them per XCD group; an even number (>= 4) of
-// k-blocks (the K loop is unrolled by two behind four peeled steps).  Bitwise the numbers of fmt_gemm_dma_kernel.
-// FLOAT_FMT_BIG=0 keeps the one-tile-per-workgroup kernels on rows padded per evaluation (the A/B switch).
-constexpr int kBigMinRows = 1536;  // below 8 row blocks the padded layout's kernels stay (a single evaluation: 180 rows)
-constexpr int kBigSmem = 4 * 28 * 1024 + 4 * 4096;
-bool big_shape_ok(const FmtTune& tn, int rows_total, int N, int K, int n_cu) {
-  return tn.big && rows_total >= kBigMinRows && N % 2048 == 0 && K % 64 == 0 && K >= 128 && n_cu >= 8;
-}
-template <class T>
-int launch_big4(const u16* A, const FmtLin& L, float* out, int rows_total, int ldo, int n_cu, bool prime, hipStream_t s) {
-  if constexpr (T::is32) {
-    fh_set_error("the fp32 verification mode has no persistent projection kernel");
-    return FLOAT_E_INVALID;
-  } else {
-    auto kern = fmt_gemm_big4_kernel<T, 4>;
-    if (prime) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kBigSmem) != hipSuccess)
-        (void)hipGetLastError();
-      return FLOAT_OK;
-    }
-    BigArgs g{A, L.W, L.b, out, rows_total, L.N, L.K, ldo, (rows_total + 191) / 192, L.N / 256};
-    const dim3 grid((unsigned)((n_cu / 8) * 8));
-    fh_launch_prof(2, kern, grid, dim3(256), kBigSmem, s, g);
-    FH_CHECK_HIP(hipGetLastError());
-    return FLOAT_OK;
-  }
-}
-
-template <class T>
-int launch_wide(const GemmArgs& g, int variant, bool prime, hipStream_t s) {
-  const int mt = (g.M + 15) / 16;
-  if (prime) {
-    (void)launch_big4<T>(nullptr, FmtLin{}, nullptr, 0, 0, 0, true, s);
-    (void)launch_dma_t<T, 4, 4, 0>(g, true, s);
-    (void)launch_dma_t<T, 4, 4, 1>(g, true, s);
-    (void)launch_wide_t<T, 4, 4>(g, true, s);
-    (void)launch_wide_t<T, 5, 4>(g, true, s);
-    (void)launch_wide_t<T, 6, 4>(g, true, s);
-    (void)launch_wide_t<T, 6, 2>(g, true, s);
-    (void)launch_wide_t<T, 12, 2>(g, true, s);
-    (void)launch_wide_t<T, 12, 4>(g, true, s);
-    (void)launch_wide_t<T, 12, 2, 8>(g, true, s);
-    (void)launch_wide_t<T, 12, 4, 8>(g, true, s);
-    return FLOAT_OK;
-  }
-  if (variant == 6 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 0>(g, false, s);
-  if (variant == 7 && mt > 4 && dma_shape_ok(g, 320)) return launch_dma_t<T, 4, 4, 1>(g, false, s);
-  if (mt <= 4) return launch_wide_t<T, 4, 4>(g, false, s);
-  // 192-row blocks also for the stacked clips of a batch (mt > 12): the last block reads up to 11 row tiles past the batch (the
-  // operand buffers are padded for it, the rows are never stored); 80-row blocks ran the batched projection at 240 TFLOP/s
-  // against 700 for 192-row ones
-  if (variant == 6 || variant == 7) variant = 2;  // shapes the LDS-DMA tile does not take
-  if (mt <= 12 || variant == 2 || variant >= 4) {
-    switch (variant) {
-      case 1: return launch_wide_t<T, 6, 2>(g, false, s);
-      case 2: return launch_wide_t<T, 12, 2>(g, false, s);
-      case 3: return launch_wide_t<T, 12, 4>(g, false, s);
-      case 4: return launch_wide_t<T, 12, 2, 8>(g, false, s);  // two waves per SIMD, rows split over the wave pairs
-      case 5: return launch_wide_t<T, 12, 4, 8>(g, false, s);
-      default: return launch_wide_t<T, 6, 4>(g, false, s);
-    }
-  }
-  return launch_wide_t<T, 5, 4>(g, false, s);
-}
-
-// ---- GEMM instantiation table: (row tiles, column tiles, waves splitting K) per workgroup ----
-template <class T, int MTW, int NT, int NW, int EPI>
-int launch_gemm_t(GemmArgs g, bool prime, hipStream_t s) {
-  constexpr int smem = NW * MTW * 16 * NT * 16 * (int)sizeof(float);
-  auto kern = fmt_gemm_kernel<T, MTW, NT, NW, EPI>;
-  if (smem > 160 * 1024) {  // gfx950: 160 KiB of LDS per workgroup
-    if (!prime) fh_set_error("GEMM tiling %dx%d tiles with %d waves needs %d B of LDS", MTW, NT, NW, smem);
-    return FLOAT_E_INVALID;
-  }
-  if (prime) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      (void)hipGetLastError();
-    return FLOAT_OK;
-  }
-  const int mt_total = (g.M + 15) / 16;
-  g.mblk = (mt_total + MTW - 1) / MTW;
-  if (EPI != EPI_PARTIAL || g.ksplit < 1) g.ksplit = 1;
-  dim3 grid((g.N / (NT * 16)) * g.mblk * g.ksplit);
-  fh_launch_prof(0, kern, grid, dim3(NW * 64), smem, s, g);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
-
-// Which tilings exist.  Split tilings (a quarter/third/half of the CFG rows per workgroup) carry every
-// epilogue and 4/8/16 K-splitting waves; full-height tilings (4 waves, LDS bound) only the two
-// epilogues that need them: EPI_CFG (all CFG rows of a token in one workgroup) and EPI_F32.
-#define FMT_SPLIT_SHAPES(X, NW, EPI) \
-  X(3, 1, NW, EPI) X(3, 2, NW, EPI) X(3, 4, NW, EPI) X(5, 1, NW, EPI) X(5, 2, NW, EPI) X(5, 4, NW, EPI) X(4, 1, NW, EPI) \
-  X(4, 2, NW, EPI) X(6, 2, NW, EPI) X(2, 1, NW, EPI) X(1, 1, NW, EPI)
-#define FMT_FOR_SPLIT(X, EPI) FMT_SPLIT_SHAPES(X, 4, EPI) FMT_SPLIT_SHAPES(X, 8, EPI) FMT_SPLIT_SHAPES(X, 16, EPI)
-#define FMT_FOR_FULL(X, EPI) X(12, 2, 4, EPI) X(15, 2, 4, EPI) X(12, 1, 4, EPI) X(15, 1, 4, EPI) X(12, 1, 8, EPI) X(15, 1, 8, EPI)
-
-template <class T, int EPI>
-int launch_gemm(const GemmArgs& g, int mtw, int nt, int nw, bool prime, hipStream_t s) {
-  if (!prime && (g.N % (nt * 16) || g.K % (32 * nw * ((EPI == EPI_PARTIAL && g.ksplit > 1) ? g.ksplit : 1)))) {
-    fh_set_error("gemm shape N=%d K=%d not tileable by %d columns / %d waves", g.N, g.K, nt * 16, nw);
-    return FLOAT_E_INVALID;
-  }
-#define FMT_CASE(MTW, NT, NW, E) \
-  if (mtw == MTW && nt == NT && nw == NW) return launch_gemm_t<T, MTW, NT, NW, E>(g, prime, s);
-  if constexpr (T::is32) {
-    // the fp32 verification mode runs a handful of 16-column tilings (pick_tiling): speed is not its point
-    FMT_CASE(1, 1, 4, EPI) FMT_CASE(2, 1, 4, EPI) FMT_CASE(3, 1, 4, EPI) FMT_CASE(4, 1, 4, EPI) FMT_CASE(5, 1, 4, EPI)
-    if constexpr (EPI == EPI_CFG) {
-      FMT_CASE(1, 1, 8, EPI) FMT_CASE(3, 1, 8, EPI) FMT_CASE(4, 1, 8, EPI)
-    }
-  } else {
-    FMT_FOR_SPLIT(FMT_CASE, EPI)
-    if constexpr (EPI == EPI_F32 || EPI == EPI_CFG) {
-      FMT_FOR_FULL(FMT_CASE, EPI)
-    }
-  }
-#undef FMT_CASE
-  fh_set_error("no GEMM tiling (%d x %d tiles, %d waves) for epilogue %d", mtw, nt, nw, EPI);
-  return FLOAT_E_INVALID;
-}
-
-// ---- stacked clips (>= kRbMinRows rows): the row-blocked LDS-DMA tile (fmt_rb_kernels.hpp) for qkv / proj / fc1 / fc2
-template <class T, int MI, int NJ, int KPS, int NS, int EPI>
-int launch_rbs_t(GemmArgs g, bool prime, hipStream_t s) {
-  constexpr int smem = fmt_rb_smem(MI, NJ, KPS, NS), ROWS = 32 * MI, BN = 32 * NJ;
-  auto kern = fmt_gemm_rbs_kernel<T, MI, NJ, KPS, NS, EPI>;
-  if (prime) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      (void)hipGetLastError();
-    return FLOAT_OK;
-  }
-  if (EPI != EPI_PARTIAL || g.ksplit < 1) g.ksplit = 1;
-  FH_REQUIRE(g.N % BN == 0 && (g.K / 32) % (g.ksplit * KPS) == 0 && g.K / 32 / g.ksplit / KPS >= 1,
-             "row-blocked GEMM: N=%d K=%d not tileable by %d columns / %d K slices of %d-k-block stages", g.N, g.K, BN, g.ksplit, KPS);
-  g.mblk = (g.M + ROWS - 1) / ROWS;
-  g.touch.W = nullptr;
-  const dim3 grid((unsigned)((g.N / BN) * g.mblk * g.ksplit));
-  fh_launch_prof(3, kern, grid, dim3(512), smem, s, g);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
-// tile shapes built: 0 = 96 x 64 (two workgroups per CU), 1 = 96 x 128, 2 = 192 x 128 (ring of 3)
-template <class T, int EPI>
-int launch_rbs(const GemmArgs& g, int shape, bool prime, hipStream_t s) {
-  if constexpr (T::is32) {
-    fh_set_error("the fp32 verification mode has no row-blocked tiling");
-    return FLOAT_E_INVALID;
-  } else {
-  if (prime) {
-    (void)launch_rbs_t<T, 3, 2, 2, 4, EPI>(g, true, s);
-    (void)launch_rbs_t<T, 3, 4, 2, 4, EPI>(g, true, s);
-    (void)launch_rbs_t<T, 6, 4, 2, 3, EPI>(g, true, s);
-    return FLOAT_OK;
-  }
-  switch (shape) {
-    case 0: return launch_rbs_t<T, 3, 2, 2, 4, EPI>(g, false, s);
-    case 1: return launch_rbs_t<T, 3, 4, 2, 4, EPI>(g, false, s);
-    default: return launch_rbs_t<T, 6, 4, 2, 3, EPI>(g, false, s);
-  }
-  }
-}
-// Which tile, per layer and row count (tools/probes/gemm_lab.hip on MI355X, us per launch incl. the launch boundary, weights
-// rotating over 8 buffers; 48 x 64 tiling -> best row-blocked tile):
-//   rows    qkv (3072 x 1024)     proj (1024 x 1024)      fc1 (4096 x 1024)      fc2 (1024 x 4096, 4 K slices)
-//    360     9.7 ->  6.7 (96x64)   5.1 (kept)             10.9 ->  8.0 (96x64)   10.9 ->  8.3 (96x64)
-//    720    14.4 ->  9.9 (96x128)  6.6 ->  6.4 (96x64 /2) 18.8 -> 13.2 (96x128)  19.0 -> 12.8 (96x128)
-//   1440    24.4 -> 16.4 (96x64)  11.6 ->  9.8 (96x64 /2) 33.1 -> 22.5 (192x128) 34.1 -> 20.9 (192x128)
-//   2880    53.7 -> 31.7 (192x128) 22.2 -> 15.7 (192x128 /2) 74.5 -> 43.3 (192x128) 71.8 -> 39.1 (192x128)
-// FLOAT_FMT_RB=0 keeps the 48 x 64 tiling (the A/B switch); FLOAT_FMT_RB_QKV / _PROJ / _FC1 / _FC2 = "shape[,ksplit]" override.
-constexpr int kRbMinRows = 300;
-struct RbPlan {
-  int shape = -1, ksplit = 1;  // shape < 0: the weight-streaming tiling
-};
-RbPlan pick_rb(const FmtTune& tn, int layer, int M) {
-  RbPlan p;
-  if (!tn.rb || M < kRbMinRows) return p;
-  const int tier = M < 540 ? 0 : (M < 1100 ? 1 : (M < 2200 ? 2 : 3));
-  static const int shapes[4][4] = {/* qkv */ {0, 1, 0, 2}, /* proj */ {-1, 0, 0, 2}, /* fc1 */ {0, 1, 2, 2}, /* fc2 */ {0, 1, 2, 2}};
-  p.shape = shapes[layer][tier];
-  // fc2: 4 K slices fill the CUs up to 1440 rows; from 2200 rows on 2 slices do (15 x 8 tiles x 2) and halve the fp32 slabs the
-  // next LayerNorm folds (16 clips: 415.7 vs 438.6 ms per 250 evaluations; 8 clips the other way round: 251.6 vs 241.9)
-  p.ksplit = layer == RB_PROJ ? 2 : (layer == RB_FC2 ? (tier == 3 ? 2 : 4) : 1);
-  const FmtTune::Rb& o = tn.rb_layer[layer];
-  if (o.n >= 1) {
-    p.shape = o.shape;
-    const int ks = o.ksplit;
-    if (o.n >= 2 && (layer == RB_PROJ || layer == RB_FC2) && (ks == 1 || ks == 2 || ks == 4 || ks == 8)) p.ksplit = ks;
-  }
-  return p;
-}
-
-template <class T, int EPI>
-void prime_epi() {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  if constexpr (T::is32) {
-    for (int mtw = 1; mtw <= 5; ++mtw) (void)launch_gemm<T, EPI>(g, mtw, 1, 4, true, nullptr);
-    if (EPI == EPI_CFG)
-      for (int mtw : {1, 3, 4}) (void)launch_gemm<T, EPI>(g, mtw, 1, 8, true, nullptr);
-    return;
-  }
-  static const int shapes[][2] = {{3, 1}, {3, 2}, {3, 4}, {5, 1}, {5, 2}, {5, 4}, {4, 1}, {4, 2}, {6, 2}, {2, 1}, {1, 1}};
-  for (auto& c : shapes)
-    for (int nw : {4, 8, 16}) (void)launch_gemm<T, EPI>(g, c[0], c[1], nw, true, nullptr);
-  if (EPI == EPI_F32 || EPI == EPI_CFG) {
-    for (int nt : {1, 2}) {
-      (void)launch_gemm<T, EPI>(g, 12, nt, 4, true, nullptr);
-      (void)launch_gemm<T, EPI>(g, 15, nt, 4, true, nullptr);
-    }
-    (void)launch_gemm<T, EPI>(g, 12, 1, 8, true, nullptr);
-    (void)launch_gemm<T, EPI>(g, 15, 1, 8, true, nullptr);
-  }
-}
-template <class T>
-void prime_kernels() {
-  prime_epi<T, EPI_F32>();
-  prime_epi<T, EPI_T16>();
-  prime_epi<T, EPI_SILU_P16>();
-  prime_epi<T, EPI_GELU_P16>();
-  prime_epi<T, EPI_GATE_RES>();
-  prime_epi<T, EPI_XEMBED>();
-  prime_epi<T, EPI_CFG>();
-  prime_epi<T, EPI_PARTIAL>();
-  prime_epi<T, EPI_GELUERF_P16>();
-  if constexpr (!T::is32) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    (void)launch_wide<T>(g, 0, true, nullptr);
-    (void)launch_rbs<T, EPI_T16>(g, 0, true, nullptr);
-    (void)launch_rbs<T, EPI_GELU_P16>(g, 0, true, nullptr);
-    (void)launch_rbs<T, EPI_PARTIAL>(g, 0, true, nullptr);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fmt_mega_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 48 * 64 * 4) != hipSuccess)
-      (void)hipGetLastError();
-  }
-}
-
-// Tiling choice: split the rows over row blocks so that narrow layers still fill the 256 CUs, and
-// split K over as many waves as keeps >= 4 k-steps per wave (one prefetch round per wave).
-struct Tiling {
-  int mtw, nt, nw;
-};
-int pick_nw(int K, int forced) {
-  const int KB = K / 32;
-  if (forced && KB % forced == 0) return forced;
-  if (KB >= 128 && KB % 16 == 0) return 16;
-  if (KB >= 32 && KB % 8 == 0) return 8;
-  return 4;
-}
-Tiling pick_tiling(const FmtTune& tn, int M, int N, int K, bool need_full_rows) {
-  const int mt = (M + 15) / 16;
-  if (need_full_rows) {
-    if (mt <= 4) return {4, 1, pick_nw(K, 0)};
-    // 16 columns per workgroup: twice the workgroups of the 32-column tile; 8 K-splitting waves keep twice
-    // the operand bytes in flight (each of the 32 workgroups streams the whole 393 KB activation operand)
-    return {mt <= 12 ? 12 : 15, 1, (tn.full_nw == 8 && (K / 32) % 8 == 0) ? 8 : 4};
-  }
-  int split = mt <= 4 ? 4 : (mt <= 12 ? 3 : 5);
-  if (mt <= 2) split = mt;
-  const int blocks = (mt + split - 1) / split;
-  const bool wide = N >= 16384;  // the fused adaLN projection
-  if (mt >= 12) {  // tuning overrides only apply to the CFG-batched shapes (buffers hold 240 rows)
-    const int* o = tn.plan + (wide ? 3 : 0);
-    if (o[0]) {
-      int nw = o[0] >= 12 ? 4 : pick_nw(K, o[2]);
-      while (nw > 4 && nw * o[0] * 16 * o[1] * 16 * 4 > 160 * 1024) nw >>= 1;
-      return {o[0], o[1], nw};
-    }
-  }
-  if (wide) return {mt <= 4 ? 4 : 6, 2, std::min(8, pick_nw(K, 0))};
-  // stacked clips (float_fmt_sample_batch, more than 15 row tiles): the one-clip tile (48 x 64) with 4 K-splitting waves, so that
-  // two or three workgroups share a CU (49 KB of LDS each instead of 98).  Measured per 250 evaluations, B = 2 / 4 clips:
-  // 120.7 / 184.5 ms against 136.4 / 200.6 with the 80-row tiles this function would pick below, 130.1 / 208.1 with 8 waves
-  // (one clip: 85.0).  Operands come straight from L2 per workgroup, so the traffic grows with rows x column blocks: the
-  // batched chain wants an LDS-staged large-tile kernel like fmt_gemm_wide_kernel with these epilogues.
-  if (mt > 15 && N % 64 == 0) return {3, 4, 4};
-  // column tiles per workgroup: the widest (<= 4) that still gives >= ~200 workgroups, so that each CU
-  // runs ONE workgroup (two back-to-back workgroups per CU double the latency chain of the layer)
-  int nt = 1;
-  if (mt >= 5) {
-    if ((N / 64) * blocks >= 192 && N % 64 == 0) nt = 4;
-    else if ((N / 32) * blocks >= 192 && N % 32 == 0) nt = 2;
-  } else if ((N / 16) * blocks > 512) {
-    nt = 2;
-  }
-  return {split, nt, pick_nw(K, 0)};
-}
-
-GemmArgs base_args(const u16* A, const Lin& L, int M) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A = A;
-  g.W = L.W;
-  g.bias = L.b;
-  g.K = L.K;
-  g.N = L.N;
-  g.M = M;
-  return g;
-}
-
-// fp32 verification mode: 16 columns per workgroup, 4 K-splitting waves, the row split of the 16-bit tilings capped at 5 tiles
-Tiling pick_tiling32(int M) {
-  const int mt = (M + 15) / 16;
-  return {mt <= 5 ? mt : (mt <= 12 ? 3 : 5), 1, 4};
-}
-
-// plan: a per-layer tiling override of the one-clip chain (FmtTune::plan_layer, tuning aid)
-template <class T, int EPI>
-int run_gemm(const FmtTune& tn, const GemmArgs& g, hipStream_t s, bool need_full_rows = false, const LayerPlan* plan = nullptr) {
-  if constexpr (T::is32) {
-    FH_REQUIRE(!need_full_rows, "the fp32 mode has no all-rows CFG epilogue tiling (token-blocked head only)");
-    const Tiling t = pick_tiling32(g.M);
-    GemmArgs g2 = g;
-    g2.touch.W = nullptr;
-    return launch_gemm<T, EPI>(g2, t.mtw, t.nt, t.nw, false, s);
-  }
-  if (plan && plan->on() && (g.M + 15) / 16 <= 15) {
-    GemmArgs g2 = g;
-    g2.touch.W = nullptr;  // the touch descriptors follow the default block decode
-    return launch_gemm<T, EPI>(g2, plan->v[0], plan->v[1], plan->v[2], false, s);
-  }
-  const Tiling t = pick_tiling(tn, g.M, g.N, g.K, need_full_rows);
-  return launch_gemm<T, EPI>(g, t.mtw, t.nt, t.nw, false, s);
-}
-
-// Split-K GEMM whose gated residual add happens in the next LayerNorm launch (EPI_PARTIAL + LnRed).
-// The tiling is the one a GEMM with ksplit * N columns and K / ksplit would get: same workgroup
-// count, a fraction of the activation bytes per workgroup (FmtTune::fc2_split, proj_split).
-struct PendingRed {
-  int ks = 0;
-  LnRed red{};
-};
-
-template <class T>
-int run_gemm_partial(float_fmt* h, GemmArgs g, int ksplit, hipStream_t s, const LayerPlan* plan = nullptr) {
-  g.ksplit = ksplit;
-  g.out_f32 = h->slab;
-  g.ldo = g.N;
-  g.slab_stride = (size_t)h->Mpad * g.N;
-  if (plan && plan->on() && !T::is32 && (g.M + 15) / 16 <= 15) {
-    g.touch.W = nullptr;
-    return launch_gemm<T, EPI_PARTIAL>(g, plan->v[0], plan->v[1], plan->v[2], false, s);
-  }
-  Tiling t = T::is32 ? pick_tiling32(g.M) : pick_tiling(h->tune, g.M, g.N * ksplit, g.K / ksplit, false);
-  while (t.nt > 1 && g.N % (t.nt * 16)) t.nt >>= 1;
-  if (T::is32) g.touch.W = nullptr;
-  return launch_gemm<T, EPI_PARTIAL>(g, t.mtw, t.nt, t.nw, false, s);
-}
-
-// Touch descriptor for the weights of GEMM `L` as it will be launched for M rows (ksplit = 0: plain GEMM, else EPI_PARTIAL
-// with that many K slices), to be executed by `lanes` threads per XCD with at most `per_lane` lines each; W = nullptr when the
-// GEMM's block decode is not the XCD-affine one or the lanes cannot cover it.  Who pulls whose weights: FmtTune::touch.
-TouchSpec make_touch(const FmtTune& tn, const Lin& L, int M, int ksplit, unsigned lanes, unsigned per_lane, int force_nt = 0) {
-  TouchSpec t{};
-  Tiling tl = ksplit ? pick_tiling(tn, M, L.N * ksplit, L.K / ksplit, false) : pick_tiling(tn, M, L.N, L.K, false);
-  if (force_nt) tl.nt = force_nt;
-  if (ksplit)
-    while (tl.nt > 1 && L.N % (tl.nt * 16)) tl.nt >>= 1;
-  const int ks = ksplit ? ksplit : 1;
-  if (L.N % (tl.nt * 16) || L.K % (32 * ks) || 8 % ks) return t;
-  const int nbn = L.N / (tl.nt * 16);
-  if ((nbn * ks) % 8) return t;
-  auto lg = [](unsigned v) {  // log2 of a power of two, else -1
-    int n = 0;
-    while ((1u << n) < v) ++n;
-    return (1u << n) == v ? n : -1;
-  };
-  const unsigned P = 8 / ks, run_lines = (unsigned)(L.K / 32 / ks) * 8u;
-  if (lg(run_lines) < 0 || lg((unsigned)tl.nt) < 0) return t;
-  t.run_shift = (unsigned)lg(run_lines);
-  t.nt_shift = (unsigned)lg((unsigned)tl.nt);
-  t.p_shift = (unsigned)lg(P);
-  t.tile_bytes = (unsigned)(L.K / 32) * 1024u;
-  t.total = ((unsigned)nbn / P) * (unsigned)tl.nt * run_lines;
-  if ((size_t)t.total > (size_t)lanes * per_lane) return t;
-  t.W = reinterpret_cast<const char*>(L.W);
-  return t;
-}
-
-// The same for a row-blocked GEMM (fmt_gemm_rbs_kernel, no K split): only the FIRST stages of every weight column tile - what
-// each of its workgroups waits for before it can start (1.5 of fc1's 10 us at 720 rows: every CU asks for cold lines at once).
-// Its block decode puts column block bx on XCD bx % 8, like the 48 x 64 tiling's.  kb = k-blocks to pull (FmtTune::rb_touch, 0 = off).
-TouchSpec make_touch_rb(const Lin& L, int shape, int kb, unsigned lanes, unsigned per_lane) {
-  TouchSpec t{};
-  const int ct = shape == 0 ? 4 : 8;  // 16-column tiles per column block: 96 x 64 | 96 x 128, 192 x 128
-  if (kb <= 0 || (kb & (kb - 1)) || L.N % (ct * 16) || (L.N / (ct * 16)) % 8 || L.K / 32 < kb) return t;
-  const unsigned run_lines = (unsigned)kb * 8u;  // a k-block of a column tile is 1 KiB = 8 lines, consecutive k-blocks are consecutive
-  auto lg = [](unsigned v) {
-    int n = 0;
-    while ((1u << n) < v) ++n;
-    return n;
-  };
-  t.run_shift = (unsigned)lg(run_lines);
-  t.nt_shift = (unsigned)lg((unsigned)ct);
-  t.p_shift = 3;
-  t.tile_bytes = (unsigned)(L.K / 32) * 1024u;
-  t.total = (unsigned)(L.N / (ct * 16) / 8) * (unsigned)ct * run_lines;
-  if ((size_t)t.total > (size_t)lanes * per_lane) return t;
-  t.W = reinterpret_cast<const char*>(L.W);
-  return t;
-}
-
-// threads per XCD of the launch run_gemm makes for a plain (M, N, K) GEMM
-unsigned gemm_lanes_per_xcd(const FmtTune& tn, int M, int N, int K) {
-  const Tiling t = pick_tiling(tn, M, N, K, false);
-  const int mblk = ((M + 15) / 16 + t.mtw - 1) / t.mtw;
-  return (unsigned)((N / (t.nt * 16)) * mblk / 8) * (unsigned)(t.nw * 64);
-}
-
-template <class T>
-int launch_lnmod(float_fmt* h, int M, const float* shift, const float* scale, hipStream_t s, PendingRed* pend = nullptr,
-                 const Lin* next = nullptr, u16* out = nullptr, int perm = 0, int touch_bit = 1, int rb_shape = -1) {
-  const int nv = h->D / 256;
-  // one row (wave) per workgroup: 180 single-wave workgroups spread over 180 CUs (4 rows per workgroup: +0.4 %)
-  const int rpw = h->tune.ln_rows;
-  // rpw == 1: the kernel maps ids to rows in groups of 8 rows per XCD -> 64 row slots per group of 64 ids
-  dim3 grid(rpw == 1 ? ((M + 63) / 64) * 64 : (M + rpw - 1) / rpw), block(64 * rpw);
-  const int ks = pend ? pend->ks : 0;
-  const bool wt = M <= kWtRows;  // write-through outputs for one clip's rows only (common.hpp, FMT_WT)
-  LnRed red{};
-  if (ks) red = pend->red;
-  TouchSpec pf{};
-  if (next && (h->tune.touch & (1 | touch_bit)) && rpw == 1 && !T::is32)
-    pf = rb_shape >= 0 ? make_touch_rb(*next, rb_shape, h->tune.rb_touch, (grid.x / 8) * 64, 6)
-                       : make_touch(h->tune, *next, M, 0, (grid.x / 8) * 64, 6);
-#define LN_LAUNCH(NV, KS)                                                                                                          \
-  do {                                                                                                                             \
-    if (pf.W && wt) hipLaunchKernelGGL((fmt_lnmod_kernel<T, NV, KS, true, true>), grid, block, 0, s, h->xres, M, shift, scale, h->Ntot, out ? out : h->h16, red, pf, h->ntok, perm, h->sat); \
-    else if (pf.W) hipLaunchKernelGGL((fmt_lnmod_kernel<T, NV, KS, true, false>), grid, block, 0, s, h->xres, M, shift, scale, h->Ntot, out ? out : h->h16, red, pf, h->ntok, perm, h->sat); \
-    else if (wt) hipLaunchKernelGGL((fmt_lnmod_kernel<T, NV, KS, false, true>), grid, block, 0, s, h->xres, M, shift, scale, h->Ntot, out ? out : h->h16, red, pf, h->ntok, perm, h->sat); \
-    else hipLaunchKernelGGL((fmt_lnmod_kernel<T, NV, KS, false, false>), grid, block, 0, s, h->xres, M, shift, scale, h->Ntot, out ? out : h->h16, red, pf, h->ntok, perm, h->sat);   \
-  } while (0)
-#define LN_CASE(NV)                     \
-  case NV:                              \
-    if (ks == 0) LN_LAUNCH(NV, 0);      \
-    else if (ks == 1) LN_LAUNCH(NV, 1); \
-    else if (ks == 2) LN_LAUNCH(NV, 2); \
-    else if (ks == 4) LN_LAUNCH(NV, 4); \
-    else LN_LAUNCH(NV, 8);              \
-    break;
-  switch (nv) {
-    LN_CASE(1) LN_CASE(2) LN_CASE(4) LN_CASE(8)
-    default:
-      fh_set_error("dim_h %d unsupported (must be 256*{1,2,4,8})", h->D);
-      return FLOAT_E_INVALID;
-  }
-#undef LN_CASE
-#undef LN_LAUNCH
-  if (pend) pend->ks = 0;
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
-
-// Banded attention over the M rows of qkv16 -> att16 (packed operand of attn.proj); `pull`: the GEMM whose weights the
-// workgroups touch meanwhile (TouchSpec), or nullptr.
-template <class T>
-void launch_attn(float_fmt* h, int M, const Lin* pull, hipStream_t s) {
-  const float_fmt_cfg_t& c = h->cfg;
-  const int D = h->D, ntok = h->ntok;
-  // queries per workgroup / lanes per query (FLOAT_FMT_ATTN): one 8-row output group per workgroup, 8 dims per lane by default
-  const int qpw = h->tune.attn_qpw, lpq = h->tune.attn_lpq;
-  dim3 grid(c.heads, (M + qpw - 1) / qpw), block(qpw * lpq);
-  TouchSpec pf{};
-  if (pull && !T::is32) pf = make_touch(h->tune, *pull, M, 0, (grid.x * grid.y / 8) * block.x, 2);
-#define ATTN_LAUNCH(LPQ, TCH)                                                                                                  \
-  do {                                                                                                                         \
-    if (M <= kWtRows) hipLaunchKernelGGL((fmt_attn_kernel<T, LPQ, TCH, true>), grid, block, 0, s, h->qkv16, 3 * D, h->att16, ntok, M, D, c.attn_window, pf, h->sat); \
-    else hipLaunchKernelGGL((fmt_attn_kernel<T, LPQ, TCH, false>), grid, block, 0, s, h->qkv16, 3 * D, h->att16, ntok, M, D, c.attn_window, pf, h->sat);             \
-  } while (0)
-  if (lpq == 16) {
-    if (pf.W) ATTN_LAUNCH(16, true);
-    else ATTN_LAUNCH(16, false);
-  } else {
-    if (pf.W) ATTN_LAUNCH(8, true);
-    else ATTN_LAUNCH(8, false);
-  }
-#undef ATTN_LAUNCH
-}
-
-// Banded attention + attn.proj as one launch (fmt_attnproj_kernel): slab[head] = attention_head(qkv16) @ W_proj[:, head]^T for
-// the M rows; the caller hands the fold (bias, gate, residual) to the next LayerNorm launch through PendingRed with ks = heads.
-// FLOAT_FMT_ATTNPROJ=1|2 (heads per workgroup; read at float_fmt_create) selects it; the default is the two-launch form
-// (fmt_attn_kernel, then the proj GEMM), which measured the same or faster - see the kernel's header.
-int attnproj_hpw(const float_fmt* h) {
-  const int hd = h->cfg.heads, hpw = h->tune.attnproj;
-  if (hpw <= 0 || h->D != hd * 128 || hd % hpw) return 0;
-  const int ks = hd / hpw;
-  return (ks == 1 || ks == 2 || ks == 4 || ks == 8) && (hpw == 1 || hpw == 2) ? hpw : 0;
-}
-template <class T>
-int launch_attnproj(float_fmt* h, int M, const Lin& proj, hipStream_t s) {
-  const float_fmt_cfg_t& c = h->cfg;
-  const int hpw = attnproj_hpw(h);
-  GemmArgs g = base_args(nullptr, proj, M);
-  g.sat = h->sat;
-  g.out_f32 = h->slab;
-  g.ldo = g.N;
-  g.slab_stride = (size_t)h->Mpad * g.N;
-  g.ksplit = c.heads / hpw;
-  g.mblk = ((M + 15) / 16 + 2) / 3;
-  const dim3 grid((unsigned)(g.ksplit * (g.N / (128 / hpw)) * g.mblk));
-  fh_launch_prof(0, hpw == 2 ? fmt_attnproj_kernel<T, 3, 2> : fmt_attnproj_kernel<T, 3, 1>, grid, dim3(512), 0, s, h->qkv16, 3 * h->D, g,
-                 h->ntok, h->D, c.attn_window);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
-}
 
 // Modulation half of the evaluations [e0, e0 + n) of a window: depends only on t and the window's conditions, NOT on x
 // (c = t_emb + c_embedder([wr, wa, we]), FMT.py:333-335; adaLN_modulation = Linear(SiLU(c)), FMT.py:163-166, 187-190), so it is
@@ -774,19 +142,16 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
                      h->ccond, M, D, (size_t)h->Mpad * D, big ? M : 0, h->sat);
   h->mod_zs = big ? (size_t)M * h->Ntot : (size_t)h->Mmod * h->Ntot;
   if constexpr (!T::is32) {
-    if (big) return launch_big4<T>(h->sc16, h->adaln_all, h->modall, n * M, h->Ntot, h->n_cu, false, s);
+    if (big) return launch_big4<T>(h->sc16, h->adaln_all, h->modall, n * M, h->Ntot, h->n_cu, s);
   }
   GemmArgs g = base_args(h->sc16, h->adaln_all, M);
-  g.sat = h->sat;
-  g.out_f32 = h->modall;
-  g.ldo = h->Ntot;
-  g.zcount = n;
+  g.sat = h->sat, g.out_f32 = h->modall, g.ldo = h->Ntot, g.zcount = n;
   const bool dma = (tn.wide_variant == 6 || tn.wide_variant == 7) && (M + 15) / 16 > 4 && dma_shape_ok(g, 320);
   g.zgroup = tn.zgroup > 0 ? tn.zgroup : (dma ? 2 : 4);
   g.a_zstride = (size_t)h->Mpad * D;
   g.o_zstride = (size_t)h->Mmod * h->Ntot;
   if constexpr (!T::is32) {
-    if (tn.wide && g.N % 128 == 0 && g.K % 128 == 0) return launch_wide<T>(g, tn.wide_variant, false, s);
+    if (tn.wide && g.N % 128 == 0 && g.K % 128 == 0) return launch_wide<T>(g, tn.wide_variant, s);
   }
   for (int z = 0; z < n; ++z) {  // shapes the wide kernel does not tile: the generic GEMM, one batch at a time
     GemmArgs gz = g;
@@ -799,207 +164,61 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
   return FLOAT_OK;
 }
 
-// ---- the persistent evaluation kernel (fmt_mega_kernel): stage table of run_blocks' chain for one clip
-constexpr int kMegaWgs = 256, kMegaSmem = 8 * 48 * 64 * 4;
-MegaSync mega_sync_of(const float_fmt* h) {
-  unsigned* m = h->mega_sync;
-  return MegaSync{m, m + 8 * 32, m + 9 * 32, m + 17 * 32, m + 18 * 32, h->mega_err_host, reinterpret_cast<unsigned long long*>(m + 20 * 32), (unsigned)h->tune.mega_stamp_wg};
-}
-// The persistent kernel's barrier watchdog, looked at by EVERY FMT call of the handle before it queues new work (the flag is
-// host-mapped: no copy, no synchronisation when it is clear): a timeout in an earlier call means that call's results are
-// invalid.  This call fails with the message; the device is drained, the cached window graphs (they hold the persistent
-// kernel) are destroyed, the barrier words are cleared (their generation counters are out of step for good otherwise) and the
-// handle runs the launch chain from here on.
-int mega_poll(float_fmt* h) {
-  if (!h->mega_err_host || *reinterpret_cast<volatile unsigned*>(h->mega_err_host) == 0u) return FLOAT_OK;
-  FH_CHECK_HIP(hipDeviceSynchronize());  // graphs may be queued on other streams than the caller's
-  for (auto& gr : h->graphs) (void)hipGraphExecDestroy(gr.exec);
-  h->graphs.clear();
-  if (h->mega_sync) FH_CHECK_HIP(hipMemset(h->mega_sync, 0, (size_t)(32 * 20) * sizeof(unsigned)));
-  *reinterpret_cast<volatile unsigned*>(h->mega_err_host) = 0u;
-  h->tune.mega = 0;
-  h->job.active = false;
-  fh_set_error("fmt_mega_kernel: a grid barrier timed out in an earlier call (not all %d workgroups were resident) - the results of "
-               "that call are invalid; the handle falls back to the launch chain (FLOAT_FMT_MEGA=0 selects it from the start)", 256);
-  return FLOAT_E_HIP;
-}
-// The chain's shapes this kernel is built for: one clip, 3 CFG rows of 60 tokens (M = 180), dim_h 1024, the default launch
-// options - i.e. exactly the tilings run_blocks would pick.  Anything else keeps the launch chain.
-template <class T>
-bool mega_shape_ok(const float_fmt* h, int nclip, int bc) {
-  const FmtTune& tn = h->tune;
-  if (T::is32 || !tn.mega || nclip != 1 || bc != 3 || h->D != 1024 || h->cfg.heads != 8 || h->n_cu < kMegaWgs) return false;
-  if (attnproj_hpw(h) || tn.fc2_split != 4 || tn.proj_split != 0) return false;
-  const int M = bc * h->ntok;
-  auto is = [](Tiling t, int a, int b, int c) { return t.mtw == a && t.nt == b && t.nw == c; };
-  const Blk& B = h->blk[0];
-  return (M + 15) / 16 == 12 && (h->ntok + 15) / 16 == 4 && h->x_embed.K % 256 == 0 && h->final_lin.K % 256 == 0 &&
-         is(pick_tiling(tn, M, B.qkv.N, B.qkv.K, false), 3, 4, 8) && is(pick_tiling(tn, M, B.proj.N, B.proj.K, false), 3, 1, 8) &&
-         is(pick_tiling(tn, M, B.fc1.N, B.fc1.K, false), 3, 4, 8) && is(pick_tiling(tn, M, B.fc2.N * 4, B.fc2.K / 4, false), 3, 4, 8) &&
-         B.fc2.K % 512 == 0;
-}
+bool split_ok(int ks, const Lin& L) { return (ks == 1 || ks == 2 || ks == 4) && L.K % (128 * ks) == 0; }
 
+// Attention and attn.proj of block B on the M rows of qkv16, by the first that applies: the row-blocked tile (stacked clips),
+// the fused attention + proj launch, a split-K proj, the proj GEMM with gate * residual in its epilogue.  *pend: the reduction
+// left to LN2 by the first three (`gate` = gate_msa).
 template <class T>
-int build_mega(float_fmt* h, int bc) {
-  float_fmt::MegaPlan& P = h->mega[bc];
-  P.tried = 1;
-  {
-    // every one of the 256 workgroups must be resident at once (a plain launch: nothing else checks it)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fmt_mega_kernel<T>), 512, kMegaSmem) != hipSuccess) {
-      (void)hipGetLastError();
-      per_cu = 0;
-    }
-    if (per_cu * h->n_cu < kMegaWgs) {
-      h->tune.mega = 0;  // the launch chain
-      return FLOAT_OK;
-    }
-  }
-  const float_fmt_cfg_t& c = h->cfg;
-  const FmtTune& tn = h->tune;
-  const int D = h->D, ntok = h->ntok, M = bc * ntok;
-  std::vector<MegaStage> st;
-  // A operands of the GEMM stages: one buffer per producing stage, written once per launch (see fmt_gemm_body, ldA)
-  const size_t esz = sizeof(typename T::elem) / sizeof(u16);
-  const size_t n_h = (size_t)h->Mpad * D * esz, n_hid = (size_t)h->Mpad * c.mlp_hidden * esz;
-  if (!h->mega_ws) {
-    int rc0 = h->pool.alloc(&h->mega_ws, (size_t)c.depth * (3 * n_h + n_hid), true);
-    if (rc0) return rc0;
-  }
-  auto ws_h1 = [&](int b) { return h->mega_ws + (size_t)b * (3 * n_h + n_hid); };
-  auto ws_h2 = [&](int b) { return ws_h1(b) + n_h; };
-  auto ws_att = [&](int b) { return ws_h1(b) + 2 * n_h; };
-  auto ws_hid = [&](int b) { return ws_h1(b) + 3 * n_h; };
-  auto gemm_stage = [&](int kind, GemmArgs g, int mtw, int nt) {
-    MegaStage m;
-    memset(&m, 0, sizeof(m));
-    m.kind = kind;
-    g.sat = h->sat;
-    g.mblk = ((g.M + 15) / 16 + mtw - 1) / mtw;
-    if (g.ksplit < 1) g.ksplit = 1;
-    m.g = g;
-    m.nblk = (unsigned)((g.N / (nt * 16)) * g.mblk * g.ksplit);
-    return m;
-  };
-  auto ln_stage = [&](int b_mod, int which, int ks, const float* bias, int gate_col, const Lin* next, int touch_bit, u16* out, int perm) {
-    MegaStage m;
-    memset(&m, 0, sizeof(m));
-    m.kind = MS_LN;
-    m.nblk = (unsigned)(((M + 63) / 64) * 64);
-    m.shift_off = (long long)b_mod * 6 * D + (long long)which * D;
-    m.scale_off = m.shift_off + D;
-    m.ks = ks;
-    m.red_bias = bias;
-    m.red_gate_off = (long long)b_mod * 6 * D + (long long)gate_col * D;
-    m.ln_out = out ? out : h->h16;
-    m.perm = perm;
-    if (next && (tn.touch & (1 | touch_bit))) m.pf = make_touch(tn, *next, M, 0, (m.nblk / 8) * 64, 6);
-    return m;
-  };
-  {  // x_embedder + pos_embed (run_blocks): 8 K-splitting waves here instead of 4 (every stage runs the 512-thread workgroup)
-    GemmArgs g = base_args(h->xin16, h->x_embed, ntok);
-    g.out_f32 = h->xres;
-    g.ldo = D;
-    g.pos = h->pos;
-    g.bc = bc;
-    g.ntok = ntok;
-    st.push_back(gemm_stage(MS_XEMBED, g, 4, 1));
-  }
-  for (int b = 0; b < c.depth; ++b) {
-    const Blk& B = h->blk[b];
-    // LN1: folds the previous block's fc2 slabs (gate_mlp of block b - 1)
-    if (b == 0) st.push_back(ln_stage(b, 0, 0, nullptr, 0, &B.qkv, 128, ws_h1(b), 0));
-    else {
-      MegaStage m = ln_stage(b, 0, 4, h->blk[b - 1].fc2.b, 0, &B.qkv, 128, ws_h1(b), 0);
-      m.red_gate_off = (long long)(b - 1) * 6 * D + 5LL * D;
-      st.push_back(m);
-    }
-    {
-      GemmArgs g = base_args(ws_h1(b), B.qkv, M);
-      g.out16 = h->qkv16;
-      g.ldo16 = 3 * D;
-      if (tn.touch & 8) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      st.push_back(gemm_stage(MS_QKV, g, 3, 4));
-    }
-    {
-      MegaStage m;
-      memset(&m, 0, sizeof(m));
-      m.kind = MS_ATTN;
-      m.nblk = (unsigned)(c.heads * ((M + 7) / 8));
-      if (tn.touch & 2) m.pf = make_touch(tn, B.proj, M, 0, (m.nblk / 8) * 128, 2);
-      m.att_out = ws_att(b);
-      st.push_back(m);
-    }
-    {
-      GemmArgs g = base_args(ws_att(b), B.proj, M);
-      g.out_f32 = h->xres;
-      g.ldo = D;
-      g.ldg = h->Ntot;
-      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      MegaStage m = gemm_stage(MS_PROJ, g, 3, 1);
-      m.gate_off = (long long)b * 6 * D + 2LL * D;
-      st.push_back(m);
-    }
-    st.push_back(ln_stage(b, 3, 0, nullptr, 0, &B.fc1, 64, ws_h2(b), 0));
-    {
-      GemmArgs g = base_args(ws_h2(b), B.fc1, M);
-      g.out16 = ws_hid(b);
-      g.ldo16 = B.fc2.K / 32;
-      if (tn.touch & 4) g.touch = make_touch(tn, B.fc2, M, 4, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      st.push_back(gemm_stage(MS_FC1, g, 3, 4));
-    }
-    {
-      GemmArgs g = base_args(ws_hid(b), B.fc2, M);
-      g.ksplit = 4;
-      g.out_f32 = h->slab;
-      g.ldo = g.N;
-      g.slab_stride = (size_t)h->Mpad * g.N;
-      if (tn.touch & 32) {
-        const unsigned lanes = gemm_lanes_per_xcd(tn, M, g.N * 4, g.K / 4);
-        if (b + 1 < c.depth) g.touch = make_touch(tn, h->blk[b + 1].qkv, M, 0, lanes, 2);
-        else g.touch = make_touch(tn, h->final_lin, M, 0, lanes, 2, 1);
-      }
-      st.push_back(gemm_stage(MS_FC2, g, 3, 4));
-    }
-  }
-  {
-    const int nblk = (ntok + 15) / 16, seqs = bc;
-    MegaStage m = ln_stage(c.depth, 0, 4, h->blk[c.depth - 1].fc2.b, 0, nullptr, 0, h->hfin16, seqs * 16);
-    m.red_gate_off = (long long)(c.depth - 1) * 6 * D + 5LL * D;
-    st.push_back(m);
-    GemmArgs g = base_args(h->hfin16, h->final_lin, nblk * seqs * 16);
-    g.tokblk = 1;
-    g.nclip = 1;
-    g.bc = bc;
-    g.ntok = ntok;
-    g.n_prev = c.n_prev;
-    g.xcur = h->xcur;
-    g.xin16 = h->xin16;
-    g.ldx = h->Kx / 32;
-    st.push_back(gemm_stage(MS_HEAD, g, bc, 1));
-  }
-  for (const MegaStage& m : st) FH_REQUIRE(m.nblk <= (unsigned)kMegaWgs, "persistent kernel: a stage needs %u workgroups", m.nblk);
+int run_proj(const FmtLaunch& cx, const Blk& B, int M, const float* gate, const RbPlan& rb, PendingRed* pend) {
+  const FmtTune& tn = cx.tn;
+  const int hpw = attnproj_hpw(tn, cx.D, cx.heads);
+  const int ks = rb.shape >= 0 ? rb.ksplit : (hpw ? cx.heads / hpw : (split_ok(tn.proj_split, B.proj) ? tn.proj_split : 0));
   int rc;
-  if (!h->mega_sync && (rc = h->pool.alloc(&h->mega_sync, 32 * 20 + 2 * 3 * 64, true))) return rc;  // + stamps of <= 64 stages
-  if (!h->mega_err_host) {
-    FH_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->mega_err_host), 64, hipHostMallocMapped));
-    memset(h->mega_err_host, 0, 64);
+  if (rb.shape < 0 && hpw) {
+    rc = launch_attnproj<T>(cx, M, B.proj);
+  } else {
+    launch_attn<T>(cx, M, (!ks && (tn.touch & 2)) ? &B.proj : nullptr);
+    GemmArgs g = base_args(cx.att16, B.proj, M);
+    if (rb.shape >= 0) {
+      to_slab(g, cx.slab, cx.Mpad, ks);
+      rc = launch_rbs<T, EPI_PARTIAL>(g, rb.shape, cx.s);
+    } else if (ks) {
+      rc = run_gemm_partial<T>(cx, g, ks);
+    } else {
+      g.sat = cx.sat, g.out_f32 = cx.xres, g.ldo = cx.D;
+      g.gate = gate, g.ldg = cx.Ntot;
+      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
+      rc = run_gemm<T, EPI_GATE_RES>(tn, g, cx.s, false, &tn.plan_layer[RB_PROJ]);
+    }
   }
-  if ((rc = h->pool.alloc(&P.dev, st.size(), false))) return rc;
-  FH_CHECK_HIP(hipMemcpy(P.dev, st.data(), st.size() * sizeof(MegaStage), hipMemcpyHostToDevice));
-  P.nstage = (int)st.size();
-  P.bc = bc;
-  P.ctx = MegaCtx{h->xres, h->qkv16, h->slab, (size_t)h->Mpad * D, M, D, ntok, h->Ntot, c.attn_window, c.heads, h->sat};
-  return FLOAT_OK;
+  if (!rc && ks) *pend = pending_red(cx.slab, cx.Mpad, cx.D, B.proj.b, gate, ks);
+  return rc;
 }
 
+// mlp.fc2 of block B on the M rows of hid16, likewise: the row-blocked tile, a split-K GEMM (whose workgroups touch the weights
+// of `after`, the GEMM behind the next LayerNorm, under touch bit 32), or gate * residual in the epilogue (`gate` = gate_mlp).
 template <class T>
-int run_mega(float_fmt* h, int bc, const float* modbuf, bool euler, float dt, float a, float r, float e, hipStream_t s, float* vout_to) {
-  float_fmt::MegaPlan& P = h->mega[bc];
-  MegaDyn d{modbuf, dt, a, r, e, euler ? 1 : 0, vout_to ? vout_to : h->vout};
-  fh_launch_prof(0, (fmt_mega_kernel<T>), dim3(kMegaWgs), dim3(512), kMegaSmem, s, P.dev, P.nstage, d, P.ctx, mega_sync_of(h));
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
+int run_fc2(const FmtLaunch& cx, const Blk& B, const u16* hid16, int M, const float* gate, const RbPlan& rb, const Lin& after,
+            int after_nt, PendingRed* pend) {
+  const FmtTune& tn = cx.tn;
+  const int ks = rb.shape >= 0 ? rb.ksplit : (split_ok(tn.fc2_split, B.fc2) ? tn.fc2_split : 0);
+  GemmArgs g = base_args(hid16, B.fc2, M);
+  int rc;
+  if (rb.shape >= 0) {
+    to_slab(g, cx.slab, cx.Mpad, ks);
+    rc = launch_rbs<T, EPI_PARTIAL>(g, rb.shape, cx.s);
+  } else if (ks) {
+    g.sat = cx.sat;
+    if (tn.touch & 32) g.touch = make_touch(tn, after, M, 0, gemm_lanes_per_xcd(tn, M, g.N * ks, g.K / ks), 2, after_nt);
+    rc = run_gemm_partial<T>(cx, g, ks, &tn.plan_layer[RB_FC2]);
+  } else {
+    g.sat = cx.sat, g.out_f32 = cx.xres, g.ldo = cx.D;
+    g.gate = gate, g.ldg = cx.Ntot;
+    rc = run_gemm<T, EPI_GATE_RES>(tn, g, cx.s);
+  }
+  if (!rc && ks) *pend = pending_red(cx.slab, cx.Mpad, cx.D, B.fc2.b, gate, ks);
+  return rc;
 }
 
 // Block chain of an evaluation on the rows staged in the workspace, using the modulations in modbuf.
@@ -1009,6 +228,7 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
                float* vout_to = nullptr) {
   const float_fmt_cfg_t& c = h->cfg;
   const FmtTune& tn = h->tune;
+  const FmtLaunch cx = launch_ctx(h, s);
   const int D = h->D, ntok = h->ntok, M = nclip * bc * ntok;
   int rc;
   if constexpr (!T::is32) {
@@ -1019,12 +239,8 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
   // x_embedder + pos_embed; the CFG rows share x, so 60 rows are computed and broadcast
   {
     GemmArgs g = base_args(h->xin16, h->x_embed, nclip * ntok);
-    g.sat = h->sat;
-    g.out_f32 = h->xres;
-    g.ldo = D;
-    g.pos = h->pos;
-    g.bc = bc;
-    g.ntok = ntok;
+    g.sat = h->sat, g.out_f32 = h->xres, g.ldo = D;
+    g.pos = h->pos, g.bc = bc, g.ntok = ntok;
     if ((rc = run_gemm<T, EPI_XEMBED>(tn, g, s))) return rc;
   }
   PendingRed pend;  // residual update left to the next LayerNorm launch
@@ -1034,94 +250,34 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
   if constexpr (!T::is32) {
     rb_qkv = pick_rb(tn, RB_QKV, M), rb_proj = pick_rb(tn, RB_PROJ, M), rb_fc1 = pick_rb(tn, RB_FC1, M), rb_fc2 = pick_rb(tn, RB_FC2, M);
   }
-  auto split_ok = [&](int ks, const Lin& L) { return (ks == 1 || ks == 2 || ks == 4) && L.K % (128 * ks) == 0; };
+  const int hpw = attnproj_hpw(tn, D, c.heads);
   for (int b = 0; b < c.depth; ++b) {
     const float* mod = modbuf + (size_t)b * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
     const Blk& B = h->blk[b];
-    if ((rc = launch_lnmod<T>(h, M, mod, mod + D, s, &pend, &B.qkv, nullptr, 0, 128, rb_qkv.shape))) return rc;
+    const bool last = b + 1 == c.depth;
+    if ((rc = launch_lnmod<T>(cx, M, mod, mod + D, &pend, &B.qkv, nullptr, 0, 128, rb_qkv.shape))) return rc;
     {
       GemmArgs g = base_args(h->h16, B.qkv, M);
-      g.sat = h->sat;
-      g.out16 = h->qkv16;
-      g.ldo16 = 3 * D;
-      if ((tn.touch & 8) && attnproj_hpw(h)) g.touch = make_touch(tn, B.proj, M, c.heads / attnproj_hpw(h), gemm_lanes_per_xcd(tn, M, g.N, g.K), 2, 8 / attnproj_hpw(h));  // k-slices <-> XCDs as the fused launch decodes them
+      g.sat = h->sat, g.out16 = h->qkv16, g.ldo16 = 3 * D;
+      if ((tn.touch & 8) && hpw) g.touch = make_touch(tn, B.proj, M, c.heads / hpw, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2, 8 / hpw);  // k-slices <-> XCDs as the fused launch decodes them
       else if ((tn.touch & 8) && !split_ok(tn.proj_split, B.proj)) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      if (rb_qkv.shape >= 0) rc = launch_rbs<T, EPI_T16>(g, rb_qkv.shape, false, s);
+      if (rb_qkv.shape >= 0) rc = launch_rbs<T, EPI_T16>(g, rb_qkv.shape, s);
       else rc = run_gemm<T, EPI_T16>(tn, g, s, false, &tn.plan_layer[RB_QKV]);
       if (rc) return rc;
     }
-    if (rb_proj.shape >= 0) {
-      launch_attn<T>(h, M, nullptr, s);
-      GemmArgs gp = base_args(h->att16, B.proj, M);
-      gp.ksplit = rb_proj.ksplit;
-      gp.out_f32 = h->slab;
-      gp.ldo = gp.N;
-      gp.slab_stride = (size_t)h->Mpad * gp.N;
-      if ((rc = launch_rbs<T, EPI_PARTIAL>(gp, rb_proj.shape, false, s))) return rc;
-      pend.ks = rb_proj.ksplit;
-      pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.proj.b, mod + 2 * D};
-    } else if (attnproj_hpw(h)) {
-      if ((rc = launch_attnproj<T>(h, M, B.proj, s))) return rc;
-      pend.ks = c.heads / attnproj_hpw(h);
-      pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.proj.b, mod + 2 * D};
-    } else if (split_ok(tn.proj_split, B.proj)) {
-      launch_attn<T>(h, M, nullptr, s);
-      GemmArgs gp = base_args(h->att16, B.proj, M);
-      if ((rc = run_gemm_partial<T>(h, gp, tn.proj_split, s))) return rc;
-      pend.ks = tn.proj_split;
-      pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.proj.b, mod + 2 * D};
-    } else {
-      launch_attn<T>(h, M, (tn.touch & 2) ? &B.proj : nullptr, s);
-      GemmArgs g = base_args(h->att16, B.proj, M);
-      g.sat = h->sat;
-      g.out_f32 = h->xres;
-      g.ldo = D;
-      g.gate = mod + 2 * D;
-      g.ldg = h->Ntot;
-      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      if ((rc = run_gemm<T, EPI_GATE_RES>(tn, g, s, false, &tn.plan_layer[RB_PROJ]))) return rc;
-    }
-    if ((rc = launch_lnmod<T>(h, M, mod + 3 * D, mod + 4 * D, s, &pend, &B.fc1, nullptr, 0, 64, rb_fc1.shape))) return rc;
+    if ((rc = run_proj<T>(cx, B, M, mod + 2 * D, rb_proj, &pend))) return rc;
+    if ((rc = launch_lnmod<T>(cx, M, mod + 3 * D, mod + 4 * D, &pend, &B.fc1, nullptr, 0, 64, rb_fc1.shape))) return rc;
     {
       GemmArgs g = base_args(h->h16, B.fc1, M);
-      g.sat = h->sat;
-      g.out16 = h->hid16;
-      g.ldo16 = B.fc2.K / 32;  // packed for fc2
+      g.sat = h->sat, g.out16 = h->hid16, g.ldo16 = B.fc2.K / 32;  // packed for fc2
       if ((tn.touch & 4) && rb_fc2.shape < 0)
         g.touch = make_touch(tn, B.fc2, M, split_ok(tn.fc2_split, B.fc2) ? tn.fc2_split : 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      if (rb_fc1.shape >= 0) rc = launch_rbs<T, EPI_GELU_P16>(g, rb_fc1.shape, false, s);
+      if (rb_fc1.shape >= 0) rc = launch_rbs<T, EPI_GELU_P16>(g, rb_fc1.shape, s);
       else rc = run_gemm<T, EPI_GELU_P16>(tn, g, s, false, &tn.plan_layer[RB_FC1]);
       if (rc) return rc;
     }
-    if (rb_fc2.shape >= 0) {
-      GemmArgs g = base_args(h->hid16, B.fc2, M);
-      g.ksplit = rb_fc2.ksplit;
-      g.out_f32 = h->slab;
-      g.ldo = g.N;
-      g.slab_stride = (size_t)h->Mpad * g.N;
-      if ((rc = launch_rbs<T, EPI_PARTIAL>(g, rb_fc2.shape, false, s))) return rc;
-      pend.ks = rb_fc2.ksplit;
-      pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.fc2.b, mod + 5 * D};
-    } else if (split_ok(tn.fc2_split, B.fc2)) {
-      GemmArgs g = base_args(h->hid16, B.fc2, M);
-      g.sat = h->sat;
-      if (tn.touch & 32) {
-        const unsigned lanes = gemm_lanes_per_xcd(tn, M, g.N * tn.fc2_split, g.K / tn.fc2_split);
-        if (b + 1 < c.depth) g.touch = make_touch(tn, h->blk[b + 1].qkv, M, 0, lanes, 2);
-        else g.touch = make_touch(tn, h->final_lin, M, 0, lanes, 2, 1);  // the head GEMM runs 16-column workgroups
-      }
-      if ((rc = run_gemm_partial<T>(h, g, tn.fc2_split, s, &tn.plan_layer[RB_FC2]))) return rc;
-      pend.ks = tn.fc2_split;
-      pend.red = LnRed{h->slab, (size_t)h->Mpad * D, B.fc2.b, mod + 5 * D};
-    } else {
-      GemmArgs g = base_args(h->hid16, B.fc2, M);
-      g.sat = h->sat;
-      g.out_f32 = h->xres;
-      g.ldo = D;
-      g.gate = mod + 5 * D;
-      g.ldg = h->Ntot;
-      if ((rc = run_gemm<T, EPI_GATE_RES>(tn, g, s))) return rc;
-    }
+    // fc2's workgroups touch the next block's qkv, or the head GEMM (which runs 16-column workgroups)
+    if ((rc = run_fc2<T>(cx, B, h->hid16, M, mod + 5 * D, rb_fc2, last ? h->final_lin : h->blk[b + 1].qkv, last ? 1 : 0, &pend))) return rc;
   }
   {
     const float* mod = modbuf + (size_t)c.depth * 6 * D;  // shift, scale (FMT.py:196)
@@ -1130,27 +286,15 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
     const bool tokblk = (!tn.no_tokblk || nclip > 1) && (bc == 1 || bc == 3 || bc == 4) && h->final_lin.K % 256 == 0;
     FH_REQUIRE(tokblk || nclip == 1, "batched sampling needs the token-blocked head GEMM");
     const int nblk = (ntok + 15) / 16, seqs = nclip * bc;
-    if ((rc = launch_lnmod<T>(h, M, mod, mod + D, s, &pend, nullptr, tokblk ? h->hfin16 : nullptr, tokblk ? seqs * 16 : 0))) return rc;
+    if ((rc = launch_lnmod<T>(cx, M, mod, mod + D, &pend, nullptr, tokblk ? h->hfin16 : nullptr, tokblk ? seqs * 16 : 0))) return rc;
     GemmArgs g = base_args(tokblk ? h->hfin16 : h->h16, h->final_lin, tokblk ? nblk * seqs * 16 : M);
-    g.sat = h->sat;
-    g.tokblk = tokblk ? 1 : 0;
-    g.nclip = nclip;
-    g.bc = bc;
-    g.ntok = ntok;
-    g.n_prev = c.n_prev;
-    g.a_cfg = a;
-    g.r_cfg = r;
-    g.e_cfg = e;
-    g.dt = dt;
-    if (euler) {
-      g.xcur = h->xcur;
-      g.xin16 = h->xin16;
-      g.ldx = h->Kx / 32;
-    } else {
-      g.vout = vout_to ? vout_to : h->vout;
-    }
+    g.sat = h->sat, g.tokblk = tokblk ? 1 : 0;
+    g.nclip = nclip, g.bc = bc, g.ntok = ntok, g.n_prev = c.n_prev;
+    g.a_cfg = a, g.r_cfg = r, g.e_cfg = e, g.dt = dt;
+    if (euler) g.xcur = h->xcur, g.xin16 = h->xin16, g.ldx = h->Kx / 32;
+    else g.vout = vout_to ? vout_to : h->vout;
     // token-blocked: a workgroup = the bc row tiles of one (token block, clip) pair; row blocks = token blocks x clips
-    if (tokblk) rc = launch_gemm<T, EPI_CFG>(g, bc, 1, 8, false, s);
+    if (tokblk) rc = launch_gemm<T, EPI_CFG>(g, bc, 1, 8, s);
     else rc = run_gemm<T, EPI_CFG>(tn, g, s, true);
     if (rc) return rc;
   }
@@ -1183,15 +327,11 @@ int prepare_time(float_fmt* h, const TimeSpec& ts, int n, hipStream_t s) {
   hipLaunchKernelGGL((fmt_tsin_kernel<T>), dim3(n), dim3(256), 0, s, h->tsin16, h->freqs, n, ts.t, ts.nfe, ts.stages, ts.c[0],
                      ts.c[1], ts.c[2], ts.c[3]);
   GemmArgs g = base_args(h->tsin16, h->t0, n);
-  g.sat = h->sat;
-  g.out16 = h->th16;
-  g.ldo16 = h->t2.K / 32;
-  if ((rc = launch_gemm<T, EPI_SILU_P16>(g, 4, 1, T::is32 ? 4 : pick_nw(g.K, 0), false, s))) return rc;
+  g.sat = h->sat, g.out16 = h->th16, g.ldo16 = h->t2.K / 32;
+  if ((rc = launch_gemm<T, EPI_SILU_P16>(g, 4, 1, T::is32 ? 4 : pick_nw(g.K, 0), s))) return rc;
   GemmArgs g2 = base_args(h->th16, h->t2, n);
-  g2.sat = h->sat;
-  g2.out_f32 = h->temb;
-  g2.ldo = h->D;
-  if ((rc = launch_gemm<T, EPI_F32>(g2, 4, 1, T::is32 ? 4 : pick_nw(g2.K, 0), false, s))) return rc;
+  g2.sat = h->sat, g2.out_f32 = h->temb, g2.ldo = h->D;
+  if ((rc = launch_gemm<T, EPI_F32>(g2, 4, 1, T::is32 ? 4 : pick_nw(g2.K, 0), s))) return rc;
   return FLOAT_OK;
 }
 
@@ -1216,15 +356,21 @@ int stage_window(float_fmt* h, const CfgMode& m, const float* x0, const float* w
   hipLaunchKernelGGL((fmt_build_cond_kernel<T>), dim3(M), dim3(256), 0, s, h->cond16, h->Kc, m.bc, h->ntok, c.n_prev,
                      c.dim_w, c.dim_a, c.dim_e, wr, wa, prev_wa, we, we_len, prev_we, m.wr_mask, m.wa_mask, m.we_mask, h->sat);
   GemmArgs g = base_args(h->cond16, h->c_embed, M);
-  g.sat = h->sat;
-  g.out_f32 = h->ccond;
-  g.ldo = h->D;
+  g.sat = h->sat, g.out_f32 = h->ccond, g.ldo = h->D;
   int rc;
   if ((rc = run_gemm<T, EPI_F32>(h->tune, g, s))) return rc;
   const int n = m.nclip * h->ntok * c.dim_w;
   hipLaunchKernelGGL((fmt_init_x_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, h->xcur, h->xin16, h->Kx / 32, x0, prev_x,
                      c.n_prev, c.n_cur, c.dim_w, m.nclip, h->sat);
   FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
+// only the all-rows-per-workgroup head (FLOAT_FMT_NO_TOKBLK, a debugging aid) is limited to 15 row tiles
+int check_cfg_rows(const float_fmt* h, const CfgMode& m) {
+  FH_REQUIRE(!h->tune.no_tokblk || m.bc * h->ntok <= 240,
+             "%d-way CFG of %d tokens is %d rows; the all-rows CFG epilogue GEMM holds at most 240 (15 row tiles)", m.bc, h->ntok,
+             m.bc * h->ntok);
   return FLOAT_OK;
 }
 
@@ -1369,12 +515,9 @@ int window_impl(float_fmt* h, const float* x0, const float* wa, const float* wr,
                 float a, float r, float e, int include_r, hipStream_t s, int nclip = 1) {
   CfgMode m = cfg_mode(a, r, e, include_r);
   m.nclip = nclip;
-  // only the all-rows-per-workgroup head (FLOAT_FMT_NO_TOKBLK, a debugging aid) is limited to 15 row tiles
-  FH_REQUIRE(!h->tune.no_tokblk || m.bc * h->ntok <= 240,
-             "%d-way CFG of %d tokens is %d rows; the all-rows CFG epilogue GEMM holds at most 240 (15 row tiles)", m.bc, h->ntok,
-             m.bc * h->ntok);
-  int rc = stage_window<T>(h, m, x0, wa, wr, we, we_len, prev_x, prev_wa, prev_we, s);
+  int rc = check_cfg_rows(h, m);
   if (rc) return rc;
+  if ((rc = stage_window<T>(h, m, x0, wa, wr, we, we_len, prev_x, prev_wa, prev_we, s))) return rc;
   if (nfe <= 1) return FLOAT_OK;  // a one-point grid has no evaluation: the sample is x0 (FLOAT.py:188,247-248)
   // A caller that is itself capturing `s` gets the chain launched straight into its capture (a graph cannot be launched or
   // captured from inside another capture); so does the profiling pass, whose events need eager launches.
@@ -1397,10 +540,7 @@ int eval_impl(float_fmt* h, float t, const float* x, const float* wa, const floa
   int rc = prepare_time<T>(h, tsp, 1, s);
   if (rc) return rc;
   const CfgMode m = cfg_mode(a, r, e, include_r);
-  // only the all-rows-per-workgroup head (FLOAT_FMT_NO_TOKBLK, a debugging aid) is limited to 15 row tiles
-  FH_REQUIRE(!h->tune.no_tokblk || m.bc * h->ntok <= 240,
-             "%d-way CFG of %d tokens is %d rows; the all-rows CFG epilogue GEMM holds at most 240 (15 row tiles)", m.bc, h->ntok,
-             m.bc * h->ntok);
+  if ((rc = check_cfg_rows(h, m))) return rc;
   if ((rc = stage_window<T>(h, m, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, s))) return rc;
   if ((rc = run_mod_all<T>(h, m.bc * h->ntok, 0, 1, s))) return rc;
   if ((rc = run_blocks<T>(h, 1, m.bc, h->modall, false, 0.f, a, r, e, s))) return rc;
@@ -1420,15 +560,9 @@ int sample_window(float_fmt* h, int k, hipStream_t s) {
     if ((rc = prepare_time<T>(h, time_spec(h->method, J.nfe), std::max(1, n_evals(h->method, J.nfe)), s))) return rc;
     // chunk 0 starts from zero history (FLOAT.py:217-219, nodes_adv.py:591-593); a job that starts at a later window
     // (float_fmt_sample_begin_range) from the history its caller hands over, or from zeros too
-    if (J.hist_x) rc = dev_copy(h->prev_x, J.hist_x, (size_t)B * P * c.dim_w, s);
-    else rc = dev_zero(h->prev_x, (size_t)B * P * c.dim_w, s);
-    if (rc) return rc;
-    if (J.hist_wa) rc = dev_copy(h->prev_wa, J.hist_wa, (size_t)B * P * c.dim_a, s);
-    else rc = dev_zero(h->prev_wa, (size_t)B * P * c.dim_a, s);
-    if (rc) return rc;
-    if (J.hist_we) rc = dev_copy(h->prev_we, J.hist_we, (size_t)B * P * c.dim_e, s);
-    else rc = dev_zero(h->prev_we, (size_t)B * P * c.dim_e, s);
-    if (rc) return rc;
+    if ((rc = copy_or_zero(h->prev_x, J.hist_x, (size_t)B * P * c.dim_w, s))) return rc;
+    if ((rc = copy_or_zero(h->prev_wa, J.hist_wa, (size_t)B * P * c.dim_a, s))) return rc;
+    if ((rc = copy_or_zero(h->prev_we, J.hist_we, (size_t)B * P * c.dim_e, s))) return rc;
   } else if (P > 0) {
     // AR hand-off: last P frames of the previous final sample / (padded) wa window / we window, per clip
     hipLaunchKernelGGL(fmt_tail_kernel, blocks(B * P * c.dim_w), dim3(256), 0, s, h->prev_x, h->xcur, P, L, c.dim_w, B);
@@ -1452,39 +586,29 @@ int create_impl(float_fmt* h, const TensorTable& tt) {
   const int D = c.dim_h;
   int rc;
   prime_kernels<T>();
-  if ((rc = pack_linear<T>(h, tt, {"x_embedder.proj"}, D, c.dim_w, &h->x_embed))) return rc;
-  if ((rc = pack_linear<T>(h, tt, {"t_embedder.mlp.0"}, D, 256, &h->t0))) return rc;
-  if ((rc = pack_linear<T>(h, tt, {"t_embedder.mlp.2"}, D, D, &h->t2))) return rc;
-  if ((rc = pack_linear<T>(h, tt, {"c_embedder"}, D, c.dim_w + c.dim_a + c.dim_e, &h->c_embed))) return rc;
+  auto pack = [&](const std::vector<std::string>& names, int N_each, int K, Lin* out) {
+    return pack_linear_pool<T>(h->tune, &h->pool, tt, names, N_each, K, out);
+  };
+  if ((rc = pack({"x_embedder.proj"}, D, c.dim_w, &h->x_embed))) return rc;
+  if ((rc = pack({"t_embedder.mlp.0"}, D, 256, &h->t0))) return rc;
+  if ((rc = pack({"t_embedder.mlp.2"}, D, D, &h->t2))) return rc;
+  if ((rc = pack({"c_embedder"}, D, c.dim_w + c.dim_a + c.dim_e, &h->c_embed))) return rc;
   h->blk.resize(c.depth);
   std::vector<std::string> ada;
   for (int b = 0; b < c.depth; ++b) {
     const std::string p = "blocks." + std::to_string(b) + ".";
-    if ((rc = pack_linear<T>(h, tt, {p + "attn.qkv"}, 3 * D, D, &h->blk[b].qkv))) return rc;
-    if ((rc = pack_linear<T>(h, tt, {p + "attn.proj"}, D, D, &h->blk[b].proj))) return rc;
-    if ((rc = pack_linear<T>(h, tt, {p + "mlp.fc1"}, c.mlp_hidden, D, &h->blk[b].fc1))) return rc;
-    if ((rc = pack_linear<T>(h, tt, {p + "mlp.fc2"}, D, c.mlp_hidden, &h->blk[b].fc2))) return rc;
+    if ((rc = pack({p + "attn.qkv"}, 3 * D, D, &h->blk[b].qkv))) return rc;
+    if ((rc = pack({p + "attn.proj"}, D, D, &h->blk[b].proj))) return rc;
+    if ((rc = pack({p + "mlp.fc1"}, c.mlp_hidden, D, &h->blk[b].fc1))) return rc;
+    if ((rc = pack({p + "mlp.fc2"}, D, c.mlp_hidden, &h->blk[b].fc2))) return rc;
     ada.push_back(p + "adaLN_modulation.1");
   }
-  if ((rc = pack_linear<T>(h, tt, ada, 6 * D, D, &h->adaln_all))) return rc;
+  if ((rc = pack(ada, 6 * D, D, &h->adaln_all))) return rc;
   // the head's adaLN (2D outputs) rides at the end of the same fused projection
-  {
-    Lin tail;
-    if ((rc = pack_linear<T>(h, tt, {"decoder.adaLN_modulation.1"}, 2 * D, D, &tail))) return rc;
-    Lin fused;
-    fused.N = h->adaln_all.N + tail.N;
-    fused.K = h->adaln_all.K;
-    constexpr size_t esz = sizeof(typename T::elem) / sizeof(u16);
-    if ((rc = h->pool.alloc(&fused.W, (size_t)fused.N * fused.K * esz, false))) return rc;
-    if ((rc = h->pool.alloc(&fused.b, (size_t)fused.N, false))) return rc;
-    FH_CHECK_HIP(hipMemcpy(fused.W, h->adaln_all.W, (size_t)h->adaln_all.N * fused.K * esz * sizeof(u16), hipMemcpyDeviceToDevice));
-    FH_CHECK_HIP(hipMemcpy(fused.W + (size_t)h->adaln_all.N * fused.K * esz, tail.W, (size_t)tail.N * fused.K * esz * sizeof(u16),
-                           hipMemcpyDeviceToDevice));
-    FH_CHECK_HIP(hipMemcpy(fused.b, h->adaln_all.b, (size_t)h->adaln_all.N * sizeof(float), hipMemcpyDeviceToDevice));
-    FH_CHECK_HIP(hipMemcpy(fused.b + h->adaln_all.N, tail.b, (size_t)tail.N * sizeof(float), hipMemcpyDeviceToDevice));
-    h->adaln_all = fused;  // the two source copies stay in the pool until destroy (small: ~100 MB, freed with handle)
-  }
-  if ((rc = pack_linear<T>(h, tt, {"decoder.linear"}, c.dim_w, D, &h->final_lin))) return rc;
+  Lin tail;
+  if ((rc = pack(std::vector<std::string>{"decoder.adaLN_modulation.1"}, 2 * D, D, &tail))) return rc;
+  if ((rc = concat_linear_rows<T>(&h->pool, h->adaln_all, tail, &h->adaln_all))) return rc;
+  if ((rc = pack({"decoder.linear"}, c.dim_w, D, &h->final_lin))) return rc;
   return FLOAT_OK;
 }
 
@@ -1495,9 +619,7 @@ int create_impl(float_fmt* h, const TensorTable& tt) {
 int fmt_pack_linear(const FmtTune& tn, DevicePool* pool, int dtype, const TensorTable& tt, const std::vector<std::string>& names,
                     int N_each, int K, FmtLin* out) {
   FH_REQUIRE(dtype == FLOAT_DT_BF16 || dtype == FLOAT_DT_FP16 || dtype == FLOAT_DT_FP32, "the GEMM service: unknown dtype %d", dtype);
-  if (dtype == FLOAT_DT_FP32) return pack_linear_pool<FP32>(tn, pool, tt, names, N_each, K, out);
-  return dtype == FLOAT_DT_BF16 ? pack_linear_pool<BF16>(tn, pool, tt, names, N_each, K, out)
-                                : pack_linear_pool<FP16>(tn, pool, tt, names, N_each, K, out);
+  return fmt_by_dtype(dtype, [&](auto t) { return pack_linear_pool<decltype(t)>(tn, pool, tt, names, N_each, K, out); });
 }
 
 int fmt_pack_linear_raw(const FmtTune& tn, DevicePool* pool, int dtype, const float* w, const float* b, int N, int K, FmtLin* out) {
@@ -1524,9 +646,7 @@ int fmt_pack_linear_raw(const FmtTune& tn, DevicePool* pool, int dtype, const fl
 GemmArgs fmt_gemm_args(const u16* A, const FmtLin& L, int M) { return base_args(A, L, M); }
 
 void fmt_gemm_prime(int dtype) {
-  if (dtype == FLOAT_DT_BF16) prime_kernels<BF16>();
-  else if (dtype == FLOAT_DT_FP32) prime_kernels<FP32>();
-  else prime_kernels<FP16>();
+  fmt_by_dtype(dtype, [](auto t) { prime_kernels<decltype(t)>(); });
 }
 
 template <class T>
@@ -1542,8 +662,7 @@ static int gemm_run_t(const FmtTune& tn, int epi, const GemmArgs& g, hipStream_t
 }
 
 int fmt_gemm_run(const FmtTune& tn, int dtype, int epi, GemmArgs g, hipStream_t s) {
-  if (dtype == FLOAT_DT_FP32) return gemm_run_t<FP32>(tn, epi, g, s);
-  return dtype == FLOAT_DT_BF16 ? gemm_run_t<BF16>(tn, epi, g, s) : gemm_run_t<FP16>(tn, epi, g, s);
+  return fmt_by_dtype(dtype, [&](auto t) { return gemm_run_t<decltype(t)>(tn, epi, g, s); });
 }
 
 template <class T>
@@ -1566,9 +685,17 @@ static int debug_impl(float_fmt* h, int what, const float* in, float* out, hipSt
   FH_REQUIRE(what == 1 && in != nullptr, "float_fmt_debug: unknown request %d (or null input)", what);
   const int n = ntok * 3 * D;
   hipLaunchKernelGGL((fmt_dbg_to16_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, h->qkv16, in, n);
-  launch_attn<T>(h, ntok, nullptr, s);
+  launch_attn<T>(launch_ctx(h, s), ntok, nullptr);
   hipLaunchKernelGGL((fmt_dbg_unpack_kernel<T>), dim3((ntok * D + 255) / 256), dim3(256), 0, s, out, h->att16, ntok, D);
   FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
+// the windows of the job float_fmt_sample_begin set up, one after the other
+static int drain_job(float_fmt_t* h, void* stream) {
+  int32_t left = 1;
+  while (left > 0)
+    if (int rc = float_fmt_sample_next(h, stream, nullptr, &left)) return rc;
   return FLOAT_OK;
 }
 
@@ -1602,8 +729,7 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
   }
   h->Ntot = cfg->depth * 6 * h->D + 2 * h->D;
   TensorTable tt(tensors, n_tensors);
-  int rc = (cfg->dtype == FLOAT_DT_BF16) ? create_impl<BF16>(h, tt)
-           : (cfg->dtype == FLOAT_DT_FP16) ? create_impl<FP16>(h, tt) : create_impl<FP32>(h, tt);
+  int rc = fmt_by_dtype(cfg->dtype, [&](auto t) { return create_impl<decltype(t)>(h, tt); });
   const int D = h->D, Mp = h->Mpad;
   const size_t esz = cfg->dtype == FLOAT_DT_FP32 ? 2 : 1;  // u16 slots per operand element
   auto A = [&](auto** p, size_t n) {
@@ -1662,12 +788,8 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
       rc = FLOAT_E_HIP;
     }
   }
-  if (!rc && cfg->dtype != FLOAT_DT_FP32) {
-    // stage table of the persistent evaluation kernel for the 3-way CFG shape, built now: the first evaluation may already
-    // run under stream capture, where nothing can be allocated or copied
-    const bool ok = cfg->dtype == FLOAT_DT_BF16 ? mega_shape_ok<BF16>(h, 1, 3) : mega_shape_ok<FP16>(h, 1, 3);
-    if (ok) rc = cfg->dtype == FLOAT_DT_BF16 ? build_mega<BF16>(h, 3) : build_mega<FP16>(h, 3);
-  }
+  // stage table of the persistent evaluation kernel for the 3-way CFG shape, built now (prepare_mega)
+  if (!rc) rc = fmt_by_dtype(cfg->dtype, [&](auto t) { return prepare_mega<decltype(t)>(h, 3); });
   if (rc) {
     float_fmt_destroy(h);
     return rc;
@@ -1693,11 +815,9 @@ int float_fmt_eval(float_fmt_t* h, float t, const float* x, const float* wa, con
   if ((rc = mega_poll(h))) return rc;
   FH_REQUIRE(x && wa && wr && we && prev_x && prev_wa && out, "null tensor argument to float_fmt_eval");
   hipStream_t s = (hipStream_t)stream;
-  return h->cfg.dtype == FLOAT_DT_BF16
-             ? eval_impl<BF16>(h, t, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, a_cfg, r_cfg, e_cfg, include_r_cfg, out, s)
-         : h->cfg.dtype == FLOAT_DT_FP16
-             ? eval_impl<FP16>(h, t, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, a_cfg, r_cfg, e_cfg, include_r_cfg, out, s)
-             : eval_impl<FP32>(h, t, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, a_cfg, r_cfg, e_cfg, include_r_cfg, out, s);
+  return fmt_by_dtype(h->cfg.dtype, [&](auto tag) {
+    return eval_impl<decltype(tag)>(h, t, x, wa, wr, we, we_len, prev_x, prev_wa, prev_we, a_cfg, r_cfg, e_cfg, include_r_cfg, out, s);
+  });
 }
 
 int float_fmt_sample_chunk(float_fmt_t* h, const float* x0, const float* wa, const float* wr, const float* we,
@@ -1725,25 +845,19 @@ int float_fmt_sample_chunk(float_fmt_t* h, const float* x0, const float* wa, con
   const float* pwe_p = we_len > 1 ? h->prev_we : nullptr;
   const TimeSpec tsp = time_spec(h->method, nfe);
   const int nev = std::max(1, n_evals(h->method, nfe));
-#define FMT_CHUNK(TT)                                                                                                          \
-  do {                                                                                                                           \
-    if ((rc = prepare_time<TT>(h, tsp, nev, s))) return rc;                                                                      \
-    rc = window_impl<TT>(h, h->x0_c, h->wa_c, wr, we_p, we_len, h->prev_x, h->prev_wa, pwe_p, nfe, ts, a_cfg, r_cfg, e_cfg,      \
-                         include_r_cfg, s);                                                                                      \
-  } while (0)
-  if (c.dtype == FLOAT_DT_BF16) FMT_CHUNK(BF16);
-  else if (c.dtype == FLOAT_DT_FP16) FMT_CHUNK(FP16);
-  else FMT_CHUNK(FP32);
-#undef FMT_CHUNK
+  rc = fmt_by_dtype(c.dtype, [&](auto t) {
+    typedef decltype(t) T;
+    if (int prc = prepare_time<T>(h, tsp, nev, s)) return prc;
+    return window_impl<T>(h, h->x0_c, h->wa_c, wr, we_p, we_len, h->prev_x, h->prev_wa, pwe_p, nfe, ts, a_cfg, r_cfg, e_cfg,
+                          include_r_cfg, s);
+  });
   if (rc) return rc;
   return dev_copy(out, h->xcur, (size_t)c.n_cur * c.dim_w, s);
 }
 
 int float_fmt_debug(float_fmt_t* h, int32_t what, const float* in, float* out, void* stream) {
   FH_REQUIRE(h != nullptr && out != nullptr, "null argument to float_fmt_debug");
-  return h->cfg.dtype == FLOAT_DT_BF16   ? debug_impl<BF16>(h, what, in, out, (hipStream_t)stream)
-         : h->cfg.dtype == FLOAT_DT_FP16 ? debug_impl<FP16>(h, what, in, out, (hipStream_t)stream)
-                                         : debug_impl<FP32>(h, what, in, out, (hipStream_t)stream);
+  return fmt_by_dtype(h->cfg.dtype, [&](auto t) { return debug_impl<decltype(t)>(h, what, in, out, (hipStream_t)stream); });
 }
 
 int float_fmt_saturation(float_fmt_t* h, uint64_t* total, int32_t reset, void* stream) {
@@ -1828,9 +942,7 @@ int float_fmt_sample_next(float_fmt_t* h, void* stream, int32_t* window_done, in
   auto& J = h->job;
   hipStream_t s = (hipStream_t)stream;
   const int k = J.next;
-  int rc = h->cfg.dtype == FLOAT_DT_BF16   ? sample_window<BF16>(h, k, s)
-           : h->cfg.dtype == FLOAT_DT_FP16 ? sample_window<FP16>(h, k, s)
-                                           : sample_window<FP32>(h, k, s);
+  int rc = fmt_by_dtype(h->cfg.dtype, [&](auto t) { return sample_window<decltype(t)>(h, k, s); });
   if (rc) {
     J.active = false;
     return rc;
@@ -1850,10 +962,7 @@ int float_fmt_sample_batch(float_fmt_t* h, int32_t n_clips, const float* wr, con
   int rc = float_fmt_sample_begin(h, wr, wa, T, we, we_len, noise, nfe, a_cfg, r_cfg, e_cfg, include_r_cfg, r_d);
   if (rc) return rc;
   h->job.B = n_clips;
-  int32_t left = 1;
-  while (left > 0)
-    if ((rc = float_fmt_sample_next(h, stream, nullptr, &left))) return rc;
-  return FLOAT_OK;
+  return drain_job(h, stream);
 }
 
 int float_fmt_sample(float_fmt_t* h, const float* wr, const float* wa, int32_t T, const float* we, int32_t we_len,
@@ -1861,10 +970,7 @@ int float_fmt_sample(float_fmt_t* h, const float* wr, const float* wa, int32_t T
                      float* r_d, void* stream) {
   int rc = float_fmt_sample_begin(h, wr, wa, T, we, we_len, noise, nfe, a_cfg, r_cfg, e_cfg, include_r_cfg, r_d);
   if (rc) return rc;
-  int32_t left = 1;
-  while (left > 0)
-    if ((rc = float_fmt_sample_next(h, stream, nullptr, &left))) return rc;
-  return FLOAT_OK;
+  return drain_job(h, stream);
 }
 
 }  // extern "C"

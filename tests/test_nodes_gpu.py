@@ -171,7 +171,7 @@ def test_float_process_batch_runs_stacked_chains(pipe, monkeypatch):
 
 def test_float_process_batch_of_16_runs_tier3_chain(pipe, monkeypatch):
     """16 items x 25 frames through FloatProcess (nodes.py:189-209): ONE stacked chain of 16 x 180 = 2 880 rows, i.e. tier 3 of
-    `pick_rb` (csrc/fmt_api.hip) - the default cap of FLOAT_AMD_FMT_MAX_BATCH.  Every item against the per-item loop at the fp16
+    `pick_rb` (csrc/fmt_launch.hpp) - the default cap of FLOAT_AMD_FMT_MAX_BATCH.  Every item against the per-item loop at the fp16
     limit of the path (>= 45 dB), the range counters silent, and the stacked handle really sized for 16."""
     g = torch.Generator().manual_seed(5)
     img, audio = _inputs()
