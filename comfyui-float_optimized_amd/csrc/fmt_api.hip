@@ -36,6 +36,7 @@ struct float_fmt {
   unsigned long long* sat = nullptr;  // range counter of every 16-bit activation store of the handle's launches (float_fmt_saturation)
   float* slab = nullptr;  // [8][Mpad][D] split-K partial sums (EPI_PARTIAL; the fused attention + proj launch writes one slab per head)
   float *wa_c, *we_c, *prev_x, *prev_wa, *prev_we, *x0_c;
+  float* wr_c = nullptr;   // [clip][dim_w]: wr of a ragged job in slot order
   int method = 0;          // FLOAT_ODE_*
   FmtTune tune;            // the environment's switches as float_fmt_create found them (tuning.hpp)
   // the step chain of one evaluation as ONE persistent kernel (fmt_mega_kernel, tune.mega): stage table per CFG shape, barrier words
@@ -54,16 +55,18 @@ struct float_fmt {
   float* modall = nullptr;
   int Mmod = 0;
   size_t mod_zs = 0;  // floats between two evaluations' modulations in modall, as the last run_mod_all laid them out
-  // hipGraph cache for the per-window chain, keyed by (nfe, bc, we_len, method, scales); least recently used entry evicted
+  // hipGraph cache for the per-window chain: one entry per chain SETTING (nfe, bc, we_len, method, scales, priority), least
+  // recently used setting evicted; an entry holds one executable per stack height (clips in the chain) it has met, so the
+  // shrinking stack of a ragged job stays inside its entry and never evicts
   struct GraphKey {
-    int nfe, bc, we_len, method, nclip;
+    int nfe, bc, we_len, method;
     int prio;  // priority of the stream the graph is launched on (run_mod_all picks its kernel by it)
     float a, r, e;
     bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
   };
   struct GraphEntry {
     GraphKey key;
-    hipGraphExec_t exec;
+    hipGraphExec_t exec[kFmtMaxClips + 1];  // by nclip; nullptr = not captured yet
     uint64_t used;
   };
   std::vector<GraphEntry> graphs;
@@ -80,6 +83,12 @@ struct float_fmt {
     float a, r, e;
     std::vector<float> ts;
     bool active = false;
+    // ragged job (float_fmt_sample_begin_ragged): per-clip pointers and lengths in SLOT order - window count descending,
+    // stable - so that the clips active in window k are the first n_active(k) slots
+    bool ragged = false;
+    FmtClipTab<const float*> rg_wr, rg_wa, rg_we, rg_noise;
+    FmtClipTab<float*> rg_rd;
+    int rg_win[kFmtMaxClips];  // windows per slot, non-increasing
   } job;
 };
 
@@ -455,9 +464,19 @@ int run_window_steps(float_fmt* h, const CfgMode& m, int nfe, const std::vector<
 }
 
 // Same chain, replayed from a cached hipGraph (all pointers are workspace-internal, so the graph is reusable across windows
-// and clips for a given (nfe, method, cfg mode, scales)).  The cache holds kMaxGraphs executables; the least recently used
-// one is destroyed when a new key arrives (a caller sweeping a CFG scale would otherwise keep a ~3000-node graph per value).
+// and clips for a given (nfe, method, cfg mode, scales) and stack height).  The cache holds kMaxGraphs SETTINGS; the least
+// recently used one is destroyed, with the graphs of all its stack heights, when a new setting arrives (a caller sweeping a
+// CFG scale would otherwise keep a ~3000-node graph per value).  The stack height is not part of the key: a ragged job on a
+// max_batch = 16 handle presents up to 16 heights of ONE setting, which live in one entry (6.5 ms of capture and about 1 MB
+// each at 50 evaluations), so no number of heights evicts - only a ninth setting does.
 constexpr size_t kMaxGraphs = 8;
+void destroy_graphs(float_fmt::GraphEntry& g) {
+  for (hipGraphExec_t& e : g.exec)
+    if (e) {
+      (void)hipGraphExecDestroy(e);
+      e = nullptr;
+    }
+}
 template <class T>
 int run_window_steps_graph(float_fmt* h, const CfgMode& m, int we_len, int nfe, const std::vector<float>& ts, float a,
                            float r, float e, hipStream_t s) {
@@ -466,16 +485,16 @@ int run_window_steps_graph(float_fmt* h, const CfgMode& m, int we_len, int nfe, 
   key.nfe = nfe;
   key.method = h->method;
   key.bc = m.bc;
-  key.nclip = m.nclip;
   key.we_len = we_len;
   key.a = a;
   key.r = r;
   key.e = e;
   key.prio = stream_priority(s);
+  FH_REQUIRE(m.nclip >= 1 && m.nclip <= kFmtMaxClips, "chain of %d clips (max %d)", m.nclip, kFmtMaxClips);
   float_fmt::GraphEntry* hit = nullptr;
   for (auto& g : h->graphs)
     if (g.key == key) hit = &g;
-  if (!hit) {
+  if (!hit || !hit->exec[m.nclip]) {
     if (!h->cap_stream) FH_CHECK_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     hipGraph_t graph = nullptr;
     h->cap_prio = key.prio;
@@ -490,22 +509,32 @@ int run_window_steps_graph(float_fmt* h, const CfgMode& m, int we_len, int nfe, 
     hipGraphExec_t exec = nullptr;
     FH_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    if (h->graphs.size() >= kMaxGraphs) {
-      size_t lru = 0;
-      for (size_t i = 1; i < h->graphs.size(); ++i)
-        if (h->graphs[i].used < h->graphs[lru].used) lru = i;
-      // an executable that is still queued must not be destroyed under it - and it may be queued on ANOTHER stream than `s`
-      // (the window sampler and the overlapped pipeline run the chain on side streams): eviction is rare (a ninth distinct
-      // chain shape), so wait for the whole device
-      FH_CHECK_HIP(hipDeviceSynchronize());
-      (void)hipGraphExecDestroy(h->graphs[lru].exec);
-      h->graphs.erase(h->graphs.begin() + lru);
+    if (!hit) {
+      if (h->graphs.size() >= kMaxGraphs) {
+        size_t lru = 0;
+        for (size_t i = 1; i < h->graphs.size(); ++i)
+          if (h->graphs[i].used < h->graphs[lru].used) lru = i;
+        // an executable that is still queued must not be destroyed under it - and it may be queued on ANOTHER stream than `s`
+        // (the window sampler and the overlapped pipeline run the chain on side streams): eviction is rare (a ninth distinct
+        // chain setting), so wait for the whole device
+        hipError_t se = hipDeviceSynchronize();
+        if (se != hipSuccess) {
+          (void)hipGraphExecDestroy(exec);
+          FH_CHECK_HIP(se);
+        }
+        destroy_graphs(h->graphs[lru]);
+        h->graphs.erase(h->graphs.begin() + lru);
+      }
+      float_fmt::GraphEntry fresh;
+      memset(&fresh, 0, sizeof(fresh));
+      fresh.key = key;
+      h->graphs.push_back(fresh);
+      hit = &h->graphs.back();
     }
-    h->graphs.push_back({key, exec, 0});
-    hit = &h->graphs.back();
+    hit->exec[m.nclip] = exec;
   }
   hit->used = ++h->graph_clock;
-  FH_CHECK_HIP(hipGraphLaunch(hit->exec, s));
+  FH_CHECK_HIP(hipGraphLaunch(hit->exec[m.nclip], s));
   return FLOAT_OK;
 }
 
@@ -578,6 +607,45 @@ int sample_window(float_fmt* h, int k, hipStream_t s) {
   if (rc) return rc;
   const int rows = (k == J.total - 1) ? (Tn - k * L) : L;  // trim to T (FLOAT.py:252)
   return dev_copy2d(J.r_d + (size_t)k * L * c.dim_w, (size_t)Tn * c.dim_w, h->xcur, (size_t)L * c.dim_w, rows * c.dim_w, B, s);
+}
+
+// One window of a ragged job: the clips that still have a window k are the first `nact` slots, and the chain runs on them alone.
+// A clip that has left the stack keeps its rows of the workspace, unread.  The staging is one launch per tensor whatever the
+// clip count: the per-clip pointers and lengths are kernel arguments (FmtClipTab).
+template <class T>
+int sample_window_ragged(float_fmt* h, int k, hipStream_t s) {
+  const float_fmt_cfg_t& c = h->cfg;
+  auto& J = h->job;
+  const int L = c.n_cur, P = c.n_prev;
+  const bool dynamic = J.we_len > 1;
+  int nact = 0;
+  while (nact < J.B && J.rg_win[nact] > k) ++nact;
+  int rc;
+  auto blocks = [](int n) { return dim3((n + 255) / 256); };
+  auto grid = [nact](int n) { return dim3((n + 255) / 256, nact); };
+  if (k == 0) {
+    if ((rc = prepare_time<T>(h, time_spec(h->method, J.nfe), std::max(1, n_evals(h->method, J.nfe)), s))) return rc;
+    if ((rc = dev_zero(h->prev_x, (size_t)nact * P * c.dim_w, s))) return rc;
+    if ((rc = dev_zero(h->prev_wa, (size_t)nact * P * c.dim_a, s))) return rc;
+    if ((rc = dev_zero(h->prev_we, (size_t)nact * P * c.dim_e, s))) return rc;
+    // the slot order holds for the whole job: wr and a static we are staged once
+    hipLaunchKernelGGL(fmt_gather_pad_kernel, grid(c.dim_w), dim3(256), 0, s, h->wr_c, J.rg_wr, 0, 1, c.dim_w);
+    if (!dynamic) hipLaunchKernelGGL(fmt_gather_pad_kernel, grid(c.dim_e), dim3(256), 0, s, h->we_c, J.rg_we, 0, 1, c.dim_e);
+  } else if (P > 0) {
+    hipLaunchKernelGGL(fmt_tail_kernel, blocks(nact * P * c.dim_w), dim3(256), 0, s, h->prev_x, h->xcur, P, L, c.dim_w, nact);
+    hipLaunchKernelGGL(fmt_tail_kernel, blocks(nact * P * c.dim_a), dim3(256), 0, s, h->prev_wa, h->wa_c, P, L, c.dim_a, nact);
+    if (dynamic) hipLaunchKernelGGL(fmt_tail_kernel, blocks(nact * P * c.dim_e), dim3(256), 0, s, h->prev_we, h->we_c, P, L, c.dim_e, nact);
+  }
+  hipLaunchKernelGGL(fmt_gather_pad_kernel, grid(L * c.dim_a), dim3(256), 0, s, h->wa_c, J.rg_wa, k * L, L, c.dim_a);
+  if (dynamic) hipLaunchKernelGGL(fmt_gather_pad_kernel, grid(L * c.dim_e), dim3(256), 0, s, h->we_c, J.rg_we, k * L, L, c.dim_e);
+  hipLaunchKernelGGL(fmt_gather_pad_kernel, grid(L * c.dim_w), dim3(256), 0, s, h->x0_c, J.rg_noise, k * L, L, c.dim_w);
+  FH_CHECK_HIP(hipGetLastError());
+  rc = window_impl<T>(h, h->x0_c, h->wa_c, h->wr_c, h->we_c, dynamic ? L : 1, h->prev_x, h->prev_wa,
+                      dynamic ? h->prev_we : nullptr, J.nfe, J.ts, J.a, J.r, J.e, J.include_r, s, nact);
+  if (rc) return rc;
+  hipLaunchKernelGGL(fmt_scatter_trim_kernel, grid(L * c.dim_w), dim3(256), 0, s, J.rg_rd, h->xcur, k * L, L, c.dim_w);
+  FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
 }
 
 template <class T>
@@ -763,6 +831,7 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
   A(&h->wa_c, (size_t)h->Bmax * cfg->n_cur * cfg->dim_a);
   A(&h->we_c, (size_t)h->Bmax * cfg->n_cur * cfg->dim_e);
   A(&h->x0_c, (size_t)h->Bmax * cfg->n_cur * cfg->dim_w);
+  A(&h->wr_c, (size_t)h->Bmax * cfg->dim_w);
   A(&h->prev_x, (size_t)h->Bmax * cfg->n_cur * cfg->dim_w);
   A(&h->prev_wa, (size_t)h->Bmax * cfg->n_cur * cfg->dim_a);
   A(&h->prev_we, (size_t)h->Bmax * cfg->n_cur * cfg->dim_e);
@@ -800,7 +869,7 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
 
 void float_fmt_destroy(float_fmt_t* h) {
   if (!h) return;
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+  for (auto& g : h->graphs) destroy_graphs(g);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
   if (h->mega_err_host) (void)hipHostFree(h->mega_err_host);
   h->pool.release();
@@ -905,6 +974,7 @@ int float_fmt_sample_begin(float_fmt_t* h, const float* wr, const float* wa, int
   J.r = r_cfg;
   J.e = e_cfg;
   J.B = 1;
+  J.ragged = false;
   J.next = 0;
   J.n_chunks = (T + h->cfg.n_cur - 1) / h->cfg.n_cur;
   J.first = 0;
@@ -942,7 +1012,9 @@ int float_fmt_sample_next(float_fmt_t* h, void* stream, int32_t* window_done, in
   auto& J = h->job;
   hipStream_t s = (hipStream_t)stream;
   const int k = J.next;
-  int rc = fmt_by_dtype(h->cfg.dtype, [&](auto t) { return sample_window<decltype(t)>(h, k, s); });
+  int rc = fmt_by_dtype(h->cfg.dtype, [&](auto t) {
+    return J.ragged ? sample_window_ragged<decltype(t)>(h, k, s) : sample_window<decltype(t)>(h, k, s);
+  });
   if (rc) {
     J.active = false;
     return rc;
@@ -962,6 +1034,67 @@ int float_fmt_sample_batch(float_fmt_t* h, int32_t n_clips, const float* wr, con
   int rc = float_fmt_sample_begin(h, wr, wa, T, we, we_len, noise, nfe, a_cfg, r_cfg, e_cfg, include_r_cfg, r_d);
   if (rc) return rc;
   h->job.B = n_clips;
+  return drain_job(h, stream);
+}
+
+int float_fmt_sample_begin_ragged(float_fmt_t* h, int32_t n_clips, const int32_t* T, const float* const* wr,
+                                  const float* const* wa, const float* const* we, int32_t we_dynamic,
+                                  const float* const* noise, int32_t nfe, float a_cfg, float r_cfg, float e_cfg,
+                                  int32_t include_r_cfg, float* const* r_d) {
+  FH_REQUIRE(h != nullptr, "null FMT handle");
+  FH_REQUIRE(T && wr && wa && we && noise && r_d, "null array argument to float_fmt_sample_begin_ragged");
+  FH_REQUIRE(n_clips >= 1 && n_clips <= h->Bmax, "batch of %d clips, the handle was created with max_batch = %d", n_clips, h->Bmax);
+  for (int i = 0; i < n_clips; ++i) {
+    FH_REQUIRE(wr[i] && wa[i] && we[i] && noise[i] && r_d[i], "null tensor argument to float_fmt_sample_begin_ragged (clip %d)", i);
+    FH_REQUIRE(T[i] >= 1, "T must be >= 1 (got %d for clip %d)", T[i], i);
+  }
+  FH_REQUIRE(nfe >= 1 && n_evals(h->method, nfe) < kMaxSteps, "nfe=%d: too many evaluations (max %d)", nfe, kMaxSteps);
+  auto& J = h->job;
+  J.active = false;
+  const int L = h->cfg.n_cur;
+  // slots by window count, descending and stable: equal lengths keep the caller's order
+  int order[kFmtMaxClips];
+  for (int i = 0; i < n_clips; ++i) order[i] = i;
+  std::stable_sort(order, order + n_clips, [&](int x, int y) { return (T[x] + L - 1) / L > (T[y] + L - 1) / L; });
+  memset(&J.rg_wr, 0, sizeof(J.rg_wr));
+  memset(&J.rg_wa, 0, sizeof(J.rg_wa));
+  memset(&J.rg_we, 0, sizeof(J.rg_we));
+  memset(&J.rg_noise, 0, sizeof(J.rg_noise));
+  memset(&J.rg_rd, 0, sizeof(J.rg_rd));
+  for (int q = 0; q < n_clips; ++q) {
+    const int i = order[q], Ti = T[i], win = (Ti + L - 1) / L;
+    J.rg_win[q] = win;
+    J.rg_wr.p[q] = wr[i], J.rg_wr.T[q] = 1;
+    J.rg_wa.p[q] = wa[i], J.rg_wa.T[q] = Ti;
+    J.rg_we.p[q] = we[i], J.rg_we.T[q] = we_dynamic ? Ti : 1;
+    J.rg_noise.p[q] = noise[i], J.rg_noise.T[q] = win * L;
+    J.rg_rd.p[q] = r_d[i], J.rg_rd.T[q] = Ti;
+  }
+  J.wr = J.wa = J.we = J.noise = nullptr;
+  J.r_d = nullptr;
+  J.T = 0;
+  J.we_len = we_dynamic ? L : 1;  // per window, as the chain sees it
+  J.nfe = nfe;
+  J.include_r = include_r_cfg;
+  J.a = a_cfg;
+  J.r = r_cfg;
+  J.e = e_cfg;
+  J.B = n_clips;
+  J.ragged = true;
+  J.next = J.first = 0;
+  J.n_chunks = J.total = J.rg_win[0];
+  J.hist_x = J.hist_wa = J.hist_we = nullptr;
+  linspace01(nfe, &J.ts);
+  J.active = true;
+  return FLOAT_OK;
+}
+
+int float_fmt_sample_batch_ragged(float_fmt_t* h, int32_t n_clips, const int32_t* T, const float* const* wr,
+                                  const float* const* wa, const float* const* we, int32_t we_dynamic,
+                                  const float* const* noise, int32_t nfe, float a_cfg, float r_cfg, float e_cfg,
+                                  int32_t include_r_cfg, float* const* r_d, void* stream) {
+  int rc = float_fmt_sample_begin_ragged(h, n_clips, T, wr, wa, we, we_dynamic, noise, nfe, a_cfg, r_cfg, e_cfg, include_r_cfg, r_d);
+  if (rc) return rc;
   return drain_job(h, stream);
 }
 

@@ -1483,6 +1483,36 @@ __global__ void fmt_tail_kernel(float* __restrict__ dst, const float* __restrict
   dst[idx] = src[((size_t)q * n_cur + (n_cur - n_prev)) * dim + r];
 }
 
+// Ragged jobs (float_fmt_sample_begin_ragged): clips of their own lengths, each behind its own device pointer.  The table of a
+// launch travels BY VALUE in the kernel arguments (192 bytes), so no host table is read by the stream and a caller's capture
+// records the pointers themselves; slot q of the launch is blockIdx.y, so the table is indexed uniformly per workgroup.
+constexpr int kFmtMaxClips = 16;  // the operator's clip limit (float_fmt_cfg_t::max_batch)
+template <class P>
+struct FmtClipTab {
+  P p[kFmtMaxClips];
+  int T[kFmtMaxClips];  // rows behind p[q]
+};
+
+// Ragged counterpart of fmt_slice_pad_kernel: dst[q][i] = src.p[q][min(t0 + i, src.T[q] - 1)] for i < n, per clip q < gridDim.y
+// (replicate padding along time, FLOAT.py:224-227).  n = 1, t0 = 0 stages one row per clip (wr, a static we) in slot order.
+__global__ void fmt_gather_pad_kernel(float* __restrict__ dst, const FmtClipTab<const float*> src, int t0, int n, int dim) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y;
+  if (r >= n * dim) return;
+  const int i = r / dim, c = r - i * dim;
+  const int t = min(t0 + i, src.T[q] - 1);
+  dst[(size_t)q * n * dim + r] = src.p[q][(size_t)t * dim + c];
+}
+
+// Ragged counterpart of the r_d copy: dst.p[q][t0 + i] = src[q][i] for the rows i < n with t0 + i < dst.T[q] (trim to T,
+// FLOAT.py:252): the padded rows of a clip's last window never leave the workspace.
+__global__ void fmt_scatter_trim_kernel(const FmtClipTab<float*> dst, const float* __restrict__ src, int t0, int n, int dim) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y;
+  if (r >= n * dim) return;
+  const int i = r / dim, c = r - i * dim;
+  if (t0 + i >= dst.T[q]) return;
+  dst.p[q][(size_t)(t0 + i) * dim + c] = src[(size_t)q * n * dim + r];
+}
+
 // Test hook (float_fmt_debug): fp32 rows -> the row-major 16-bit q|k|v operand of fmt_attn_kernel, and its packed output back.
 template <class T>
 __global__ void fmt_dbg_to16_kernel(u16* __restrict__ dst, const float* __restrict__ src, int n) {

@@ -18,7 +18,9 @@ MegaSync mega_sync_of(const float_fmt* h) {
 int mega_poll(float_fmt* h) {
   if (!h->mega_err_host || *reinterpret_cast<volatile unsigned*>(h->mega_err_host) == 0u) return FLOAT_OK;
   FH_CHECK_HIP(hipDeviceSynchronize());  // graphs may be queued on other streams than the caller's
-  for (auto& gr : h->graphs) (void)hipGraphExecDestroy(gr.exec);
+  for (auto& gr : h->graphs)
+    for (hipGraphExec_t e : gr.exec)
+      if (e) (void)hipGraphExecDestroy(e);
   h->graphs.clear();
   if (h->mega_sync) FH_CHECK_HIP(hipMemset(h->mega_sync, 0, (size_t)(32 * 20) * sizeof(unsigned)));
   *reinterpret_cast<volatile unsigned*>(h->mega_err_host) = 0u;

@@ -13,8 +13,9 @@ from .config import FmtConfig
 @native.rebuildable
 class FlowMatchingTransformerHIP:
     """Holds packed weights + workspace on one GPU.  `sample` stacks up to `max_batch` clips per launch chain
-    (float_fmt_sample_batch); the single-evaluation / single-window calls loop batch items on the host, like the
-    reference's FloatProcess (nodes.py:189-209)."""
+    (float_fmt_sample_batch), `sample_ragged` clips of different lengths (float_fmt_sample_batch_ragged); the
+    single-evaluation / single-window calls loop batch items on the host, like the reference's FloatProcess
+    (nodes.py:189-209)."""
 
     def __init__(self, state_dict, cfg: FmtConfig = None, device="cuda:0", dtype="fp16", use_graph=2, max_batch=1):
         """max_batch: clips `sample` may run through one launch chain (float_fmt_sample_batch); larger batches are cut
@@ -173,6 +174,68 @@ class FlowMatchingTransformerHIP:
                     native.dev_ptr(we[b0:b0 + nb]), we.shape[1], native.dev_ptr(nz), int(nfe), a_cfg_scale, r_cfg_scale,
                     e_cfg_scale, 1 if include_r_cfg else 0, native.dev_ptr(r_d[b0:b0 + nb]), s))
         return r_d
+
+    @torch.no_grad()
+    def sample_ragged(self, r_s, wa_list, we_list, noise_list, nfe=10, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0,
+                      include_r_cfg=False, out=None):
+        """The AR window loop for B clips of their OWN lengths in one stacked chain (float_fmt_sample_batch_ragged): a clip
+        leaves the stack after its last window.  r_s (B,dim_w); wa_list[i] (T_i,dim_a); we_list[i] (1,dim_e) for every clip or
+        (T_i,dim_e) for every clip; noise_list[i] (ceil(T_i/n_cur),n_cur,dim_w), the clip's own sequential draws (a leading or
+        middle batch axis of 1, as `sample` and draw_noise have it, is accepted).  Clips are grouped by `ragged_groups`, up
+        to max_batch per chain.  Returns the list of r_d[i] (T_i,dim_w) on the GPU, in caller order; out: such a list to write
+        into (contiguous fp32 device tensors)."""
+        c, L = self.cfg, native.lib()
+        n_cur = c.num_frames_for_clip
+        B = len(wa_list)
+        r_s = self._f(r_s).reshape(-1, c.dim_w)
+        if r_s.shape[0] != B or len(we_list) != B or len(noise_list) != B or B < 1:
+            raise ValueError("sample_ragged: %d wa, %d we, %d noise entries for r_s %s" % (B, len(we_list), len(noise_list),
+                                                                                        tuple(r_s.shape)))
+        wa = [self._f(t).reshape(-1, c.dim_a) for t in wa_list]
+        we = [self._f(t).reshape(-1, c.dim_e) for t in we_list]
+        Ts = [int(t.shape[0]) for t in wa]
+        if min(Ts) < 1:
+            raise ValueError("sample_ragged: every clip needs at least one frame (lengths %s)" % Ts)
+        dynamic = any(t.shape[0] > 1 for t in we)
+        for i in range(B):
+            if we[i].shape[0] != (Ts[i] if dynamic else 1):
+                raise ValueError("Dynamic emotion latent `we` time dimension (%d) does not match audio latent `wa` "
+                                 "time dimension (%d)." % (we[i].shape[0], Ts[i]))
+        noise = []
+        for i, t in enumerate(noise_list):
+            t, n_chunks = self._f(t), int(math.ceil(Ts[i] / n_cur))
+            if t.numel() != n_chunks * n_cur * c.dim_w or t.shape[-1] != c.dim_w:
+                raise ValueError("noise[%d] must be (%d,%d,%d), got %s" % (i, n_chunks, n_cur, c.dim_w, tuple(t.shape)))
+            noise.append(t.reshape(n_chunks, n_cur, c.dim_w))
+        if out is None:
+            out = [torch.empty(T, c.dim_w, device=self.device, dtype=torch.float32) for T in Ts]
+        else:
+            if len(out) != B:
+                raise ValueError("out must be %d tensors of (T_i,%d), got %d" % (B, c.dim_w, len(out)))
+            for i, (o, T) in enumerate(zip(out, Ts)):
+                if (tuple(o.shape) != (T, c.dim_w) or not o.is_cuda or o.device.index != (self.device.index or 0)
+                        or o.dtype != torch.float32 or not o.is_contiguous()):
+                    raise ValueError("out[%d] must be a contiguous float32 tensor of (%d,%d) on %s, got %s %s on %s%s" % (
+                        i, T, c.dim_w, self.device, tuple(o.shape), o.dtype, o.device,
+                        "" if o.is_contiguous() else ", not contiguous"))
+        with torch.cuda.device(self.device):
+            s = native.stream_ptr(self.device)
+            for grp in ragged_groups(Ts, n_cur, self.max_batch):
+                arr = lambda ts, name: native.dev_ptr_array([ts[i] for i in grp], name)  # noqa: E731
+                native.check(L.float_fmt_sample_batch_ragged(
+                    self._h, len(grp), (C.c_int32 * len(grp))(*[Ts[i] for i in grp]), arr(r_s, "r_s"), arr(wa, "wa"),
+                    arr(we, "we"), 1 if dynamic else 0, arr(noise, "noise"), int(nfe), a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                    1 if include_r_cfg else 0, arr(out, "out"), s))
+        return out
+
+
+def ragged_groups(lengths, n_cur, max_batch):
+    """Which clips share one chain of `sample_ragged`: caller indices ordered by window count ceil(T / n_cur), descending and
+    stable - the clips still active in window k are then a prefix of their group - and cut into consecutive runs of max_batch,
+    so a group holds clips of similar length.  Equal lengths give the caller order in runs of max_batch, as `sample` cuts."""
+    n_cur, max_batch = int(n_cur), max(1, int(max_batch))
+    order = sorted(range(len(lengths)), key=lambda i: -((int(lengths[i]) + n_cur - 1) // n_cur))
+    return [order[i:i + max_batch] for i in range(0, len(order), max_batch)]
 
 
 class WindowSampler:

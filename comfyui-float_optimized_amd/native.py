@@ -80,6 +80,12 @@ _SIGNATURES = {
                                    C.c_int32] + [C.c_float] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),
     "float_fmt_sample_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_int32] + [C.c_float] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "float_fmt_sample_begin_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)] + [C.POINTER(C.c_void_p)] * 3 +
+                                      [C.c_int32, C.POINTER(C.c_void_p), C.c_int32] + [C.c_float] * 3 +
+                                      [C.c_int32, C.POINTER(C.c_void_p)]),
+    "float_fmt_sample_batch_ragged": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)] + [C.POINTER(C.c_void_p)] * 3 +
+                                      [C.c_int32, C.POINTER(C.c_void_p), C.c_int32] + [C.c_float] * 3 +
+                                      [C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
     "float_fmt_sample_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_int32] + [C.c_float] * 3 + [C.c_int32, C.c_void_p]),
     "float_fmt_sample_next": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -185,6 +191,11 @@ def dev_ptr(t, name="tensor"):
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise TypeError("%s must be contiguous float32" % name)
     return C.c_void_p(t.data_ptr())
+
+
+def dev_ptr_array(tensors, name="tensor"):
+    """fp32 contiguous device tensors -> a host array of their device pointers (float_dec_set_feats' convention)."""
+    return (C.c_void_p * len(tensors))(*[dev_ptr(t, "%s[%d]" % (name, i)).value for i, t in enumerate(tensors)])
 
 
 def stream_ptr(device=None):

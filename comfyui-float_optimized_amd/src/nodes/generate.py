@@ -174,6 +174,25 @@ class InferenceAgent:
                 torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=buf[k, i:i + 1])
         return buf.to(self.rank, non_blocking=True)
 
+    def _noise_ragged_to_device(self, n_chunks, seeds):
+        """[(n_chunks[i], L, W)]: item i draws what _noise_to_device draws for it alone (seeds[i], n_chunks[i] sequential draws);
+        the CPU streams are written into one pinned buffer and sent by ONE non-blocking copy."""
+        c = self.cfg
+        if os.environ.get("FLOAT_AMD_NOISE", "cpu").lower() == "device":
+            return [self._noise_to_device(n, sd).reshape(n, c.num_frames_for_clip, c.dim_w) for n, sd in zip(n_chunks, seeds)]
+        shape = (sum(n_chunks), c.num_frames_for_clip, c.dim_w)
+        buf = self.__dict__.get("_noise_pin_r")
+        if buf is None or tuple(buf.shape) != shape:
+            buf = self._noise_pin_r = torch.empty(shape, dtype=torch.float32, pin_memory=True)
+        k = 0
+        for n, sd in zip(n_chunks, seeds):
+            g = torch.Generator("cpu")
+            g.manual_seed(int(sd))
+            for _ in range(n):
+                torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=buf[k:k + 1])
+                k += 1
+        return list(buf.to(self.rank, non_blocking=True).split(list(n_chunks)))
+
     def _noise_to_device(self, n_chunks, seed):
         """The reference's sequential CPU draws (fmt.draw_noise; FLOAT.py:203-215) written straight into a pinned buffer and sent
         by a non-blocking copy: the host neither waits for the encoder kernels queued in front of the copy nor leaves the GPU
@@ -392,8 +411,9 @@ class InferenceAgent:
     @torch.no_grad()
     def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None,
                            out_dtype=None):
-        """B clips of EQUAL length through one stacked FMT chain (float_fmt_sample_batch: every weight is read once per
-        evaluation for all of them), then decoded one after the other.  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
+        """B clips through one stacked FMT chain (every weight is read once per evaluation for all of them), then decoded one
+        after the other.  Clips of equal length run float_fmt_sample_batch; clips of different lengths run its ragged sibling
+        (FlowMatchingTransformerHIP.sample_ragged: a clip leaves the stack after its last window).  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
         item (FloatProcess uses seed + i, nodes.py:189-209) - each item keeps its own noise stream, so item i is what
         infer_device gives for it alone (bit for bit where the GEMM tilings coincide, within the fp16 tolerance otherwise).
         Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device."""
@@ -411,14 +431,20 @@ class InferenceAgent:
             slots[i] = self.enc.export_feats16(slots[i])
             feats.append(slots[i])
         T = conds[0]["T"]
-        if any(c["T"] != T for c in conds):
-            raise ValueError("infer_device_batch needs clips of equal length")
-        n_chunks = int(math.ceil(T / self.cfg.num_frames_for_clip))
-        noise = self._noise_batch_to_device(n_chunks, seeds)
         r_s = torch.cat([c["r_s"].reshape(1, -1) for c in conds])
-        wa = torch.cat([c["wa"].reshape(1, T, -1) for c in conds])
-        we = torch.cat([c["we"].reshape(1, 1, -1) for c in conds])
-        r_d = self.G.batched_fmt(B).sample(r_s, wa, we, noise, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
+        if any(c["T"] != T for c in conds):
+            # clips of different lengths: one chain whose stack shrinks as clips end (float_fmt_sample_batch_ragged)
+            n_chunks = [int(math.ceil(c["T"] / self.cfg.num_frames_for_clip)) for c in conds]
+            noise = self._noise_ragged_to_device(n_chunks, seeds)
+            r_d = self.G.batched_fmt(B).sample_ragged(r_s, [c["wa"].reshape(c["T"], -1) for c in conds],
+                                                      [c["we"].reshape(1, -1) for c in conds], noise, self.opt.nfe,
+                                                      a_cfg_scale, r_cfg_scale, e_cfg_scale)
+        else:
+            n_chunks = int(math.ceil(T / self.cfg.num_frames_for_clip))
+            noise = self._noise_batch_to_device(n_chunks, seeds)
+            wa = torch.cat([c["wa"].reshape(1, T, -1) for c in conds])
+            we = torch.cat([c["we"].reshape(1, 1, -1) for c in conds])
+            r_d = self.G.batched_fmt(B).sample(r_s, wa, we, noise, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
         out = []
         for i in range(B):
             # decodes queue back to back: the last frames of item i cross PCIe inside the launches of item i + 1

@@ -16,8 +16,9 @@
  *     (the reference's tensors are fp32 everywhere); `stream` is a hipStream_t passed as void*.
  *     All work is enqueued on that stream; nothing synchronises the device.
  *   - batch size is 1 at this level, exactly like the reference decode loop (FLOAT.py:140);
- *     the host mirror loops over batch items as FloatProcess does (nodes.py:189-209).  The one
- *     batched entry is float_fmt_sample_batch (the reference's samplers take a batch).
+ *     the host mirror loops over batch items as FloatProcess does (nodes.py:189-209).  The
+ *     batched entries are float_fmt_sample_batch (the reference's samplers take a batch) and its
+ *     ragged sibling float_fmt_sample_batch_ragged.
  *   - a handle owns its packed weights and a fixed workspace allocated at create time; no
  *     allocation happens inside the run-time calls (float_aud_reserve is the explicit exception).
  *     Every run-time call enqueues kernels only (device-to-device moves included: memcpy / memset
@@ -36,8 +37,9 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison) and float_dec_frames_u8 /
- * float_dec_frames_host_u8 (8-bit frames) are purely additive - no existing signature, structure or behaviour changed, so a
+/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
+ * float_dec_frames_host_u8 (8-bit frames) and float_fmt_sample_begin_ragged / float_fmt_sample_batch_ragged (clips of different
+ * lengths in one chain) are purely additive - no existing signature, structure or behaviour changed, so a
  * caller built against the earlier v6 header runs unchanged. */
 #define FLOAT_HIP_ABI_VERSION 6
 
@@ -74,8 +76,9 @@ typedef struct {
   int32_t n_prev, n_cur;   /* num_prev_frames, int(wav2vec_sec*fps); n_prev + n_cur <= 80 */
   int32_t attn_window;     /* |i-j| <= window is visible (FMT.py:15-19) */
   int32_t dtype;           /* FLOAT_DT_* */
-  int32_t use_graph;       /* 0: eager launches; != 0: replay each window's chain from a cached hipGraph (at most 8
-                              graphs per handle, least recently used evicted).  1 and 2 are the same (1 used to put the
+  int32_t use_graph;       /* 0: eager launches; != 0: replay each window's chain from a cached hipGraph (the graphs of at
+                              most 8 chain settings per handle - nfe, CFG shape, scales, method, stream priority - least recently
+                              used setting evicted, which synchronises the device; one graph per stack height of a setting).  1 and 2 are the same (1 used to put the
                               adaLN GEMM on a parallel branch; that GEMM now runs once per window, not per step). */
   int32_t max_batch;       /* clips float_fmt_sample_batch may stack per launch chain (sizes the workspace: rows = max_batch x 4 CFG
                               rows x tokens; the per-window modulation slab is 64 x rows x (depth * 6 + 2) * dim_h fp32, 3.1 GB per
@@ -140,6 +143,30 @@ int float_fmt_sample(float_fmt_t* h, const float* wr, const float* wa, int32_t T
 int float_fmt_sample_batch(float_fmt_t* h, int32_t n_clips, const float* wr, const float* wa, int32_t T,
                            const float* we, int32_t we_len, const float* noise, int32_t nfe, float a_cfg,
                            float r_cfg, float e_cfg, int32_t include_r_cfg, float* r_d, void* stream);
+
+/* B independent clips of their OWN lengths T[i] through one stacked chain, window by window: a clip leaves the stack after its
+ * last window, so no window is computed for padding and clips need not be grouped by length.  Each clip's result is what
+ * float_fmt_sample gives for it alone, within the rounding stated for float_fmt_sample_batch.  No reference counterpart (the
+ * reference's batches share one length); the window body is FLOAT.py:214-251 unchanged.
+ *   T, wr, wa, we, noise, r_d: HOST arrays of n_clips entries (the convention of float_dec_set_feats), read during _begin only;
+ *   the entries are device pointers that must stay valid until the last window has run:
+ *     wr[i]: (dim_w)   wa[i]: (T[i], dim_a)   we[i]: (1, dim_e) for every clip, or - we_dynamic != 0 - (T[i], dim_e) for every clip
+ *     noise[i]: (ceil(T[i] / n_cur), n_cur, dim_w), the clip's own sequential draws   r_d[i]: (T[i], dim_w)
+ * Caller order is arbitrary: the operator orders its slots by window count (descending, stable), so the clips active in
+ * window k are a prefix of the stack; with equal lengths the launches are those of float_fmt_sample_batch.  The pointers and
+ * lengths reach the staging kernels as by-value kernel arguments: nothing is allocated, uploaded or synchronised, and the calls
+ * may be captured like the others.  n_clips <= max_batch of the handle.
+ * _begin_ragged records the job; float_fmt_sample_next then enqueues one window per call (windows_left counts down from the
+ * longest clip's window count; rows [k*n_cur, min(T[i], (k+1)*n_cur)) of every r_d[i] that has a window k are complete once
+ * that stream work is done).  _batch_ragged = _begin_ragged + every window, like float_fmt_sample_batch. */
+int float_fmt_sample_begin_ragged(float_fmt_t* h, int32_t n_clips, const int32_t* T, const float* const* wr,
+                                  const float* const* wa, const float* const* we, int32_t we_dynamic,
+                                  const float* const* noise, int32_t nfe, float a_cfg, float r_cfg, float e_cfg,
+                                  int32_t include_r_cfg, float* const* r_d);
+int float_fmt_sample_batch_ragged(float_fmt_t* h, int32_t n_clips, const int32_t* T, const float* const* wr,
+                                  const float* const* wa, const float* const* we, int32_t we_dynamic,
+                                  const float* const* noise, int32_t nfe, float a_cfg, float r_cfg, float e_cfg,
+                                  int32_t include_r_cfg, float* const* r_d, void* stream);
 
 /* The same loop one window at a time, so the caller can overlap the decode of window k (on another
  * stream) with the sampling of window k+1: _begin only records the job (pointers must stay valid
