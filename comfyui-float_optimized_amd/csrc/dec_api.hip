@@ -34,6 +34,10 @@ struct float_dec {
   // fragments and the [max_frames][size][size][4] sums that replace the stored V; FLOAT_DEC_FLOW_EPI=0 keeps dec_flow_kernel there
   void* wfrag = nullptr;
   float* oflow = nullptr;
+  // I420 frames of a last level that does not end in dec_flowlast_kernel's I420 form (i420_fused false): [max_frames][size][size][3]
+  // 8-bit RGB, which dec_rgb8_to_i420_kernel turns into the caller's planes behind the level
+  bool i420_fused = false;
+  unsigned char* rgb8 = nullptr;
   unsigned long long* sat = nullptr;  // [kDecSatSites] saturation counters (dec_kernels.hpp), device
   DecTune tune;  // the environment's switches as float_dec_create found them (tuning.hpp)
   float *loFlow[2] = {nullptr, nullptr}, *loRgb[2] = {nullptr, nullptr};
@@ -137,6 +141,8 @@ int create_impl(float_dec* h, const TensorTable& tt) {
     if ((rc = alloc_elem<T>(&h->pool, &h->wfrag, FH * (size_t)(cl / 32) * (T::is32 ? 1 : 2) * 64 * 8))) return rc;
     if ((rc = h->pool.alloc(&h->oflow, FH * (size_t)size * size * 4, true))) return rc;
   }
+  h->i420_fused = h->oflow && h->tune.yuv_fused && flowlast_takes_i420(size) && h->levels.back().C == h->convs.back().cout;
+  if (!h->i420_fused && (rc = h->pool.alloc(&h->rgb8, FH * (size_t)size * size * 3, true))) return rc;
   const size_t sk_lo = FL * 32 * 32 * 4, sk_hi = FH * (size_t)size * size * 4;  // flow / rgb pyramids: 4 floats per pixel
   for (int i = 0; i < 2; ++i) {
     if ((rc = h->pool.alloc(&h->loFlow[i], sk_lo, true))) return rc;
@@ -184,8 +190,11 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
   g.xnext = last ? nullptr : xnext;
   g.flow_out = flow_cur;
   g.rgb_out = rgb_cur;
-  g.final_out = last ? final_out : nullptr;
-  g.final_mode = last ? final_mode : kOutNone;
+  // I420: in the last-level kernel itself where it has the form for it, else 8-bit RGB into rgb8 and the converter behind it
+  const bool via_rgb8 = last && final_mode == kOutI420 && !(epi && h->i420_fused);
+  FH_REQUIRE(!via_rgb8 || h->rgb8, "I420 frames: the handle has no 8-bit RGB scratch");
+  g.final_out = last ? (via_rgb8 ? h->rgb8 : final_out) : nullptr;
+  g.final_mode = last ? (via_rgb8 ? kOutU8 : final_mode) : kOutNone;
   g.write_pyr = (!last || h->tune.write_pyr) ? 1 : 0;
   g.sat = h->sat + 16 + li;
   g.oflow = epi ? h->oflow : nullptr;
@@ -195,7 +204,8 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
     FH_CHECK_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_dec_stamps), init, sizeof(init), 0, hipMemcpyHostToDevice, st));
   }
 #endif
-  return launch_flow<T>(cx, g);
+  if ((rc = launch_flow<T>(cx, g))) return rc;
+  return via_rgb8 ? launch_rgb8_to_i420(cx, h->rgb8, final_out, n, R) : FLOAT_OK;
 }
 
 // Low phase for `n` frames (n <= lo_frames): constant input, conv1, levels 8..32.  Leaves the
@@ -259,19 +269,19 @@ int run_high(float_dec* h, int n, int off, const float* styles, const float* dem
 
 // host != nullptr: every finished high batch is copied to host + (its offset) on `cs` while `st` renders the next one
 // (float_dec_frames_host); `st` is made to wait for the last copy before the call returns.  out_v / host_v / host_dev_v hold
-// floats, or uint8_t with kOutU8: every offset and byte count below goes by the output element size.
+// floats, or uint8_t with kOutU8 / kOutI420: every offset and byte count below goes by the bytes of one frame.
 template <class T>
 int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, void* out_v, DecOut final_mode, hipStream_t st,
                 void* host_v = nullptr, hipStream_t cs = nullptr, void* host_dev_v = nullptr) {
   const int S = h->cfg.size, sdim = h->cfg.style_dim, FH = h->cfg.max_frames, FL = h->lo_frames;
-  const size_t esz = final_mode == kOutU8 ? sizeof(uint8_t) : sizeof(float);
+  const size_t fbytes = out_frame_bytes(final_mode, S);
   char *const out = static_cast<char*>(out_v), *const host = static_cast<char*>(host_v), *const host_dev = static_cast<char*>(host_dev_v);
   size_t n_copy = 0;
   const DecTune& tn = h->tune;
   // same-stream hand-over: copy workgroups ride along the next batch's launches unless FLOAT_DEC_COPY=memcpy
   // the copy workgroups store straight through `host`: only when it is device-accessible (pinned / registered) host memory
   // (host_dev = its device-side address); a pageable destination takes the hipMemcpyAsync path, batch by batch, in order
-  const bool ride = host_dev && cs == st && !tn.copy_memcpy && (((size_t)S * S * 3 * esz) % 16 == 0) &&
+  const bool ride = host_dev && cs == st && !tn.copy_memcpy && (fbytes % 16 == 0) &&
                     ((uintptr_t)host_dev % 16 == 0) && ((uintptr_t)out % 16 == 0);
   h->ride.reset();
   const StyleTable table{h->WmT, h->bm, h->Stot, h->Dtot, h->styles, h->eps, h->demod};
@@ -301,11 +311,11 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
         const int tail = tn.ride_tail;
         const bool last_of_call = (s0 + a0 + b0 + nb == n_frames);
         if (host && ride && last_of_call && tail > 0 && nb > tail) nb -= tail;
-        const size_t off = (size_t)(s0 + a0 + b0) * S * S * 3 * esz;  // bytes
+        const size_t off = (size_t)(s0 + a0 + b0) * fbytes;
         if (host && ride) h->ride.open_batch(tn, h->levels, h->lo_levels);  // this batch's launches carry the previous one's frames
         rc = run_high<T>(h, nb, b0, st_a + (size_t)b0 * h->Stot, dm_a + (size_t)b0 * h->Dtot, skip_idx, out + off, final_mode, st);
         if (rc) return rc;
-        const size_t bytes = (size_t)nb * S * S * 3 * esz;
+        const size_t bytes = (size_t)nb * fbytes;
         if (host && ride) {
           if ((rc = h->ride.hand_over(out + off, host_dev + off, host + off, bytes, st))) return rc;
         } else if (host && cs == st) {  // in-order copy behind the batch's last kernel
@@ -567,10 +577,12 @@ int float_dec_set_feats16(float_dec_t* h, const void* const* feats16, int32_t n_
 
 // What every float_dec_frames* entry point `fn` checks before it decodes (`ptrs`: its pointer arguments are all there)
 static int dec_check_run(float_dec_t* h, bool ptrs, int32_t n_frames, const void* out, DecOut mode, const char* fn) {
-  FH_REQUIRE(h && ptrs, "null argument to %s%s", fn, mode == kOutU8 ? "_u8" : "");
+  const char* sfx = mode == kOutU8 ? "_u8" : mode == kOutI420 ? "_i420" : "";
+  FH_REQUIRE(h && ptrs, "null argument to %s%s", fn, sfx);
   FH_REQUIRE(h->feats_set, "float_dec_set_feats must be called before decoding");
   FH_REQUIRE(n_frames >= 1, "n_frames must be >= 1 (got %d)", n_frames);
-  FH_REQUIRE(mode != kOutU8 || (uintptr_t)out % 4 == 0, "%s_u8: out_hwc must be 4-byte aligned (the last-level kernel stores dwords)", fn);
+  FH_REQUIRE((mode != kOutU8 && mode != kOutI420) || (uintptr_t)out % 4 == 0,
+             "%s%s: the output must be 4-byte aligned (the last-level kernel stores dwords)", fn, sfx);
   return FLOAT_OK;
 }
 
@@ -615,6 +627,24 @@ int float_dec_frames_u8(float_dec_t* h, const float* s_r, const float* r_d, int3
 int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, uint8_t* out_hwc, uint8_t* host_hwc,
                              void* stream, void* copy_stream) {
   return dec_run_host(h, s_r, r_d, n_frames, out_hwc, host_hwc, kOutU8, stream, copy_stream);
+}
+
+// The colour matrix of the I420 calls: 0 = BT.601 limited range, the only one there is (refused before anything else is looked at)
+#define DEC_REQUIRE_MATRIX(fn, matrix) \
+  FH_REQUIRE((matrix) == FLOAT_DEC_MATRIX_BT601_LIMITED, fn ": matrix %d unknown (0 = BT.601 limited range is the only one)", (int)(matrix))
+
+int float_dec_frames_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix, uint8_t* out,
+                          void* stream) {
+  FH_REQUIRE(h && s_r && r_d && out, "null argument to float_dec_frames_i420");
+  DEC_REQUIRE_MATRIX("float_dec_frames_i420", matrix);
+  return dec_run(h, s_r, r_d, n_frames, out, kOutI420, stream);
+}
+
+int float_dec_frames_host_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix, uint8_t* out,
+                               uint8_t* host, void* stream, void* copy_stream) {
+  FH_REQUIRE(h && s_r && r_d && out && host, "null argument to float_dec_frames_host_i420");
+  DEC_REQUIRE_MATRIX("float_dec_frames_host_i420", matrix);
+  return dec_run_host(h, s_r, r_d, n_frames, out, host, kOutI420, stream, copy_stream);
 }
 
 int float_dec_saturation(float_dec_t* h, uint64_t* total, uint64_t* per_site, int32_t reset, void* stream) {

@@ -357,8 +357,9 @@ struct FlowArgs {
   float* flow_out;     // [F][R][R][4]
   float* rgb_out;      // [F][R][R][4]
   const float* lin;    // [R] identity grid: np.linspace(-1, 1, R) (float64) cast to float32
-  void* final_out;     // last level: frames (float, mode 3: uint8_t)
-  int final_mode;      // 0: none, 1: HWC clamp(-1,1)*0.5+0.5 (FLOAT.py:149-152), 2: raw CHW, 3: HWC uint8 = dec_quant8(mode 1's value)
+  void* final_out;     // last level: frames (float, modes 3 and 4: uint8_t)
+  int final_mode;      // 0: none, 1: HWC clamp(-1,1)*0.5+0.5 (FLOAT.py:149-152), 2: raw CHW, 3: HWC uint8 = dec_quant8(mode 1's value),
+                       // 4: planar I420 of mode 3's samples (dec_flowlast_kernel's I420 instantiation only)
   int write_pyr;       // store flow_out / rgb_out (0 on the last level: nobody reads them)
   int F, R, C, ld_s;
   int nbands, band_pix;  // the image is cut into nbands runs of band_pix consecutive pixels (multiple of gpb*PIX)
@@ -424,6 +425,12 @@ __device__ __forceinline__ unsigned dec_quant8(float v) {
   return (unsigned)rintf(y * 255.0f);
 }
 
+// I420 (final_mode 4, float_dec_frames_i420): 8-bit BT.601 limited range from the 8-bit RGB samples, int32 throughout (>> of a
+// negative sum is an arithmetic shift = floor).  Chroma takes the rounded mean of the 2 x 2 block, sited at its centre.
+__device__ __forceinline__ unsigned dec_i420_y(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
+__device__ __forceinline__ unsigned dec_i420_u(int mr, int mg, int mb) { return (unsigned)(((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128); }
+__device__ __forceinline__ unsigned dec_i420_v(int mr, int mg, int mb) { return (unsigned)(((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128); }
+
 // One run of PIX consecutive pixels of a row (first pixel p0 = Y * R + X0 of frame f) for one lane group: ToFlow (1x1
 // modulated conv + up-sampled previous flow -> tanh / sigmoid), grid_sample of the skip features, blend, ToRGB, the pyramids,
 // the next level's input, the final frame.  xu[k] = this lane's 8 channels (c0 ..) of conv2's output at pixel k.
@@ -438,6 +445,7 @@ struct FlowFrame {
   float* final_hwc;               // this frame's output image (final_mode 1)
   float* final_chw;               // this frame's raw output (final_mode 2)
   unsigned char* final_u8;        // this frame's 8-bit output image (final_mode 3)
+  unsigned char *final_y, *final_u, *final_v;  // this frame's I420 planes (final_mode 4): R x R, then R/2 x R/2 twice, contiguous
   typename T::elem* xnext;        // this frame's next-level input or nullptr
 };
 template <class T>
@@ -457,6 +465,9 @@ __device__ __forceinline__ FlowFrame<T> dec_flow_frame(const FlowArgs& g, int f)
   ff.final_hwc = g.final_out ? reinterpret_cast<float*>(g.final_out) + (size_t)f * npix * 3 : nullptr;
   ff.final_chw = ff.final_hwc;
   ff.final_u8 = g.final_out ? reinterpret_cast<unsigned char*>(g.final_out) + (size_t)f * npix * 3 : nullptr;
+  ff.final_y = g.final_out ? reinterpret_cast<unsigned char*>(g.final_out) + (size_t)f * (npix + (npix >> 1)) : nullptr;
+  ff.final_u = ff.final_y + npix;
+  ff.final_v = ff.final_u + (npix >> 2);
   ff.xnext = g.xnext ? reinterpret_cast<typename T::elem*>(g.xnext) + (size_t)f * npix * g.C : nullptr;
   return ff;
 }
@@ -1908,8 +1919,16 @@ __global__ __launch_bounds__(64) void dec_flowfrag_kernel(typename T::pack8* __r
 // aligned dwords (R * R is a multiple of 256 here and the frame base 4-byte aligned, float_dec_frames_u8): every lane packs
 // its pixel into 24 bits, takes its right-hand neighbour's through a quad-permute DPP move, and lanes 0..2 of the quad each
 // store one dword - 48 dword stores per wave over 192 contiguous bytes, no byte stores, no LDS, no barrier.
-template <class T, bool U8 = false>
+// I420 (final_mode 4): the frame leaves as planar YUV 4:2:0 of the U8 samples.  A 2 x 2 chroma block must sit in one wave, so this
+// instantiation has its own lane map: a wave covers 2 rows x 32 columns (lane l: row l >> 5, column l & 31), a workgroup 2 rows x
+// 128 columns (R % 128 == 0: launch_flow), in the same frame-major, XCD-affine block order.  The horizontal neighbour is lane ^ 1
+// of the quad (DPP quad_perm), the vertical one lane ^ 32 (v_permlane32_swap): the three block sums travel in one word at 10 bits
+// each.  Stores: a quad's four Y bytes in one dword from its lane 0 (8 dwords = 32 contiguous bytes per wave and row), the
+// wave's 16 U bytes as 4 dwords from lanes 0 / 8 / 16 / 24 and its 16 V bytes from lanes 32 / 40 / 48 / 56 (two quads' pairs meet
+// through a row_shl:4 DPP move).  No byte stores, no LDS, no barrier.
+template <class T, bool U8 = false, bool I420 = false>
 __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
+  static_assert(!(U8 && I420), "one output format per instantiation");
   DEC_COPY_PROLOGUE(g, bid)
   const int R = g.R, npix = R * R, Rp = R >> 1;
   // block -> (frame, run of 256 pixels): all frames of a run back to back on one XCD (ids congruent mod 8), like dec_flow_kernel
@@ -1923,10 +1942,18 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
     f = (int)bid / runs;
     run = (int)bid % runs;
   }
-  const int p = run * 256 + (int)threadIdx.x;
-  if (p >= npix) return;
+  int p, Y, X;
+  if constexpr (I420) {  // run -> (row pair, block of 128 columns); R % 128 == 0, so every lane has a pixel
+    const int cbs = R >> 7, rp = run / cbs, cb = run - rp * cbs;
+    Y = 2 * rp + ((int)threadIdx.x >> 5 & 1);
+    X = cb * 128 + ((int)threadIdx.x >> 6) * 32 + ((int)threadIdx.x & 31);
+    p = Y * R + X;
+  } else {
+    p = run * 256 + (int)threadIdx.x;
+    if (p >= npix) return;
+    Y = p / R, X = p - Y * R;
+  }
   const FlowFrame<T> ff = dec_flow_frame<T>(g, f);
-  const int Y = p / R, X = p - Y * R;
   const float4 o = *reinterpret_cast<const float4*>(g.oflow + (((size_t)f * npix + p) << 2));
   float upf[3] = {0.f, 0.f, 0.f};
   if (ff.pflow) up2_tap3(ff.pflow, 0, Rp, Y, X, upf, g.upk_flow);
@@ -1974,6 +2001,30 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
     // the quad's 12 bytes are w0 w1 w2 w3 at 24 bits each; dword j = bits [32 j, 32 j + 32) = w_j >> 8 j | w_(j+1) << (24 - 8 j)
     const unsigned d = (w >> (8u * j)) | (wn << (24u - 8u * j));
     if (j < 3u) *reinterpret_cast<unsigned*>(ff.final_u8 + (po >> 2) * 12u + j * 4u) = d;
+  } else if constexpr (I420) {
+    const unsigned q0 = dec_quant8(v0), q1 = dec_quant8(v1), q2 = dec_quant8(v2), lane = threadIdx.x & 63u;
+    // Y: bytes of lanes (0, 1) and (2, 3) pair up (quad_perm [1, 0, 3, 2]), then the pairs (quad_perm [2, 3, 0, 1]); lane 0 stores
+    const unsigned y = dec_i420_y((int)q0, (int)q1, (int)q2);
+    const unsigned y2 = y | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)y, 0xB1, 0xF, 0xF, false) << 8);
+    const unsigned y4 = y2 | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)y2, 0x4E, 0xF, 0xF, false) << 16);
+    if ((lane & 3u) == 0u) *reinterpret_cast<unsigned*>(ff.final_y + po) = y4;
+    // block sums of R, G, B at 10 bits each (4 * 255 < 1024: no carry between the fields): + horizontal neighbour, + the other row
+    unsigned s = q0 | (q1 << 10) | (q2 << 20);
+    s += (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0xB1, 0xF, 0xF, false);
+    // v_permlane32_swap of s with itself: one result holds lanes 0..31 of s in both halves, the other lanes 32..63
+    const auto sw = __builtin_amdgcn_permlane32_swap(s, s, false, false);
+    s = sw[0] + sw[1];
+    const int mr = (int)((s & 1023u) + 2u) >> 2, mg = (int)((s >> 10 & 1023u) + 2u) >> 2, mb = (int)((s >> 20) + 2u) >> 2;
+    // U in bits 0..7, V in bits 16..23; the quad's two blocks side by side (quad_perm [2, 3, 0, 1]), then the next quad's
+    // pair from four lanes up (row_shl:4, within the row of 16 lanes): lanes with (lane & 7) == 0 hold four U and four V bytes
+    const unsigned c = dec_i420_u(mr, mg, mb) | (dec_i420_v(mr, mg, mb) << 16);
+    const unsigned c2 = c | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)c, 0x4E, 0xF, 0xF, false) << 8);
+    const unsigned cn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)c2, 0x104, 0xF, 0xF, false);
+    if ((lane & 7u) == 0u) {
+      const unsigned co = (unsigned)(Y >> 1) * (unsigned)Rp + ((unsigned)X >> 1);  // X is the wave's column of lane & 31
+      if (lane < 32u) *reinterpret_cast<unsigned*>(ff.final_u + co) = (c2 & 0xFFFFu) | (cn << 16);
+      else *reinterpret_cast<unsigned*>(ff.final_v + co) = (c2 >> 16) | (cn & 0xFFFF0000u);
+    }
   } else if (g.final_mode == 1) {
     typedef float f3v __attribute__((ext_vector_type(3)));
     f3v o3 = {fminf(fmaxf(v0, -1.f), 1.f) * 0.5f + 0.5f, fminf(fmaxf(v1, -1.f), 1.f) * 0.5f + 0.5f,
@@ -1986,6 +2037,49 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
     fo[2 * (size_t)npix] = v2;
   }
   DEC_STAMP_MAX(3);
+}
+
+// I420 from finished 8-bit RGB frames (final_mode 3 of a last level that runs in dec_flow_kernel, or FLOAT_DEC_YUV_FUSED=0): one
+// lane takes 8 columns of a row pair - six dwords per row, so a wave reads two runs of 1536 contiguous bytes - and stores the
+// 2 x 8 Y bytes as two dwords per row, its four U bytes and its four V bytes as one dword each.  R % 8 == 0, rgb and out 4-byte
+// aligned.
+static __global__ __launch_bounds__(256) void dec_rgb8_to_i420_kernel(const unsigned char* __restrict__ rgb, unsigned char* __restrict__ out,
+                                                                      int F, int R) {
+  const unsigned cols = (unsigned)R >> 3, per = cols * ((unsigned)R >> 1);
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= per * (unsigned)F) return;
+  const unsigned f = idx / per, rem = idx - f * per, rp = rem / cols, xb = rem - rp * cols;
+  const size_t npix = (size_t)R * R;
+  const unsigned char* src = rgb + f * npix * 3 + ((size_t)(2u * rp) * R + 8u * xb) * 3;
+  unsigned w[2][6];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) w[a][k] = reinterpret_cast<const unsigned*>(src + (size_t)a * R * 3)[k];
+  auto byte = [&](int a, int k) { return (int)(w[a][k >> 2] >> (8 * (k & 3)) & 255u); };
+  unsigned char* const fy = out + f * (npix + (npix >> 1));
+  unsigned yw[2][2] = {{0u, 0u}, {0u, 0u}}, uw = 0u, vw = 0u;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int x = 0; x < 8; ++x)
+      yw[a][x >> 2] |= dec_i420_y(byte(a, 3 * x), byte(a, 3 * x + 1), byte(a, 3 * x + 2)) << (8 * (x & 3));
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    int m[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) m[c] = (byte(0, 6 * b + c) + byte(0, 6 * b + 3 + c) + byte(1, 6 * b + c) + byte(1, 6 * b + 3 + c) + 2) >> 2;
+    uw |= dec_i420_u(m[0], m[1], m[2]) << (8 * b);
+    vw |= dec_i420_v(m[0], m[1], m[2]) << (8 * b);
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    unsigned* const yo = reinterpret_cast<unsigned*>(fy + (size_t)(2u * rp + a) * R + 8u * xb);
+    yo[0] = yw[a][0], yo[1] = yw[a][1];
+  }
+  unsigned char* const fu = fy + npix + (size_t)rp * (R >> 1) + 4u * xb;
+  *reinterpret_cast<unsigned*>(fu) = uw;
+  *reinterpret_cast<unsigned*>(fu + (npix >> 2)) = vw;
 }
 
 // G = ToRGB's 1x1 conv (styledecoder.py:368-386: unmodulated, weight / sqrt(C) folded into wrgb) applied to a level's skip

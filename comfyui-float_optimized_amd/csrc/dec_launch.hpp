@@ -8,7 +8,12 @@
 namespace {
 
 // FlowArgs::final_mode: what the last level's flow kernel writes beside (or instead of) the pyramids
-enum DecOut : int { kOutNone = 0, kOutHWC = 1, kOutRawCHW = 2, kOutU8 = 3 };
+enum DecOut : int { kOutNone = 0, kOutHWC = 1, kOutRawCHW = 2, kOutU8 = 3, kOutI420 = 4 };
+// bytes of one size x size frame as the frames calls hand it over
+inline size_t out_frame_bytes(DecOut mode, int size) {
+  const size_t npix = (size_t)size * size;
+  return mode == kOutI420 ? npix + npix / 2 : npix * 3 * (mode == kOutU8 ? sizeof(uint8_t) : sizeof(float));
+}
 
 // The launches of a high batch that may carry a share of the pending copy, per level
 enum RideKind : int { kRideUpconv = 0, kRideConv2 = 1, kRideFlow = 2, kRideKinds = 3 };
@@ -17,7 +22,7 @@ enum RideKind : int { kRideUpconv = 0, kRideConv2 = 1, kRideFlow = 2, kRideKinds
 // workgroups inside the next batch's launches (CopyTail, dec_kernels.hpp).  Per call: reset, then per high batch open_batch ->
 // the launchers' take -> hand_over, and flush behind the last batch.
 struct RideCopy {
-  const char* src = nullptr;  // bytes: the frames are fp32 or uint8 (float_dec_frames_host / _host_u8)
+  const char* src = nullptr;  // bytes: the frames are fp32, uint8 or I420 (float_dec_frames_host / _host_u8 / _host_i420)
   char* dst = nullptr;        // device-side address of the pinned destination (what the copy workgroups store through)
   char* dst_host = nullptr;   // the same position as the caller's host pointer (hipMemcpyAsync of what no launch took)
   size_t left16 = 0;   // 16-byte units not yet handed to a launch
@@ -101,6 +106,12 @@ void for_each_conv16(F&& f) {  // f(kernel, output channels per workgroup, doubl
   }
 }
 template <class T, class F>
+void for_each_flowlast(F&& f) {  // f(kernel, the final_mode it is for: kOutNone = every mode but the listed ones); raise_lds_limits walks it
+  f(dec_flowlast_kernel<T>, kOutNone);
+  f(dec_flowlast_kernel<T, true>, kOutU8);
+  f(dec_flowlast_kernel<T, false, true>, kOutI420);
+}
+template <class T, class F>
 void for_each_flow(F&& f) {  // f(kernel, pixels per lane group and iteration, last level)
   f(dec_flow_kernel<T, 4, false>, 4, false);
   f(dec_flow_kernel<T, 2, false>, 2, false);
@@ -119,8 +130,7 @@ int raise_lds_limits(const DecTune& tn) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   };
   for_each_conv16<T>([&](auto kern, int, bool db, bool) { raise(kern, db ? 128 * 1024 : lim); });
-  raise(dec_flowlast_kernel<T>, lim);
-  raise(dec_flowlast_kernel<T, true>, lim);
+  for_each_flowlast<T>([&](auto kern, DecOut) { raise(kern, lim); });
   raise(dec_conv_kernel<T, 4>, lim);
   raise(dec_conv_kernel<T, 2>, lim);
   raise(dec_zconv4_kernel<T>, lim);
@@ -328,6 +338,19 @@ inline FlowArgs flow_args_of(const Level& L, const float* styles, int ld_s, int 
   return g;
 }
 
+// dec_flowlast_kernel's I420 instantiation covers 2 rows x 128 columns per workgroup
+inline bool flowlast_takes_i420(int R) { return R >= 128 && R % 128 == 0; }
+
+// I420 frames from `n` finished 8-bit RGB frames of R x R (dec_rgb8_to_i420_kernel), behind the level that rendered them.
+inline int launch_rgb8_to_i420(const DecLaunch& cx, const unsigned char* rgb, void* out, int n, int R) {
+  FH_REQUIRE(R % 8 == 0, "I420 frames: %d px is not a multiple of 8", R);
+  const size_t lanes = (size_t)n * (R / 2) * (R / 8);
+  hipLaunchKernelGGL(dec_rgb8_to_i420_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, cx.st, rgb,
+                     static_cast<unsigned char*>(out), n, R);
+  FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
 // ToFlow + warp + blend + ToRGB of one level (dec_flow_kernel); g holds everything but the grid.
 // Grid: ~2048 workgroups in total (8 per CU) so that every lane group runs many pixel iterations and the per-workgroup
 // prologue (56 per-lane weight values) is amortised; one row of workgroups per frame.
@@ -338,7 +361,13 @@ int launch_flow(const DecLaunch& cx, FlowArgs g) {
     const int runs = (g.R * g.R + 255) / 256;
     g.ct = cx.take(g.R, kRideFlow);
     FH_REQUIRE(g.final_mode != kOutU8 || (g.R * g.R) % 256 == 0, "8-bit frames: %d x %d pixels are not whole runs of 256", g.R, g.R);
-    void (*kern)(FlowArgs) = g.final_mode == kOutU8 ? dec_flowlast_kernel<T, true> : dec_flowlast_kernel<T>;
+    FH_REQUIRE(g.final_mode != kOutI420 || flowlast_takes_i420(g.R), "I420 frames: %d px is not whole blocks of 128 columns", g.R);
+    void (*kern)(FlowArgs);
+    switch (g.final_mode) {
+      case kOutU8: kern = dec_flowlast_kernel<T, true>; break;
+      case kOutI420: kern = dec_flowlast_kernel<T, false, true>; break;
+      default: kern = dec_flowlast_kernel<T>;
+    }
     hipLaunchKernelGGL(kern, dim3(runs * g.F + g.ct.nwg), dim3(256), (size_t)tn.lds_pad, cx.st, g);
     FH_CHECK_HIP(hipGetLastError());
     return FLOAT_OK;

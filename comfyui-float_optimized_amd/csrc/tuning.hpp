@@ -165,6 +165,7 @@ struct DecTune {
   int flow_pix = 0;        // FLOAT_DEC_FLOW_PIX = 1 | 2 | 4: pixels per lane group and iteration of dec_flow_kernel (0 = by channel count), tuning aid
   int flow_wgs = 2048;     // FLOAT_DEC_FLOW_WGS, 8..2^20: workgroups of a dec_flow_kernel launch (8 per CU)
   bool flow_epi = true;    // FLOAT_DEC_FLOW_EPI=0 keeps dec_flow_kernel on the last level instead of ToFlow in conv2's epilogue
+  bool yuv_fused = true;   // FLOAT_DEC_YUV_FUSED=0: I420 frames through u8 RGB + dec_rgb8_to_i420_kernel on the product path too (A/B switch, tests)
   bool write_pyr = false;  // FLOAT_DEC_WRITE_PYR (set at all): the last level stores its flow / rgb pyramids too
   bool copy_memcpy = false;  // FLOAT_DEC_COPY=memcpy: same-stream hand-over by hipMemcpyAsync instead of ride-along copy workgroups
   bool short_first = true;   // FLOAT_DEC_SHORT_FIRST=0: the short piece of a ragged clip last instead of first
@@ -195,6 +196,7 @@ struct DecTune {
     t.flow_pix = env_int("FLOAT_DEC_FLOW_PIX", 0, 0, 4);
     t.flow_wgs = env_int("FLOAT_DEC_FLOW_WGS", 2048, 8, 1 << 20);
     t.flow_epi = env_int("FLOAT_DEC_FLOW_EPI", 1, 0, 1) != 0;
+    t.yuv_fused = env_int("FLOAT_DEC_YUV_FUSED", 1, 0, 1) != 0;
     t.write_pyr = env_set("FLOAT_DEC_WRITE_PYR");
     const char* copy = getenv("FLOAT_DEC_COPY");
     t.copy_memcpy = copy && !strcmp(copy, "memcpy");

@@ -113,6 +113,21 @@ class SynthesisHIP:
             self.set_feats(s_r_feats)
         return self._run(native.lib().float_dec_frames_u8, s_r, r_d, (self.size, self.size, 3), torch.uint8)
 
+    @torch.no_grad()
+    def decode_i420(self, s_r, r_d, s_r_feats=None):
+        """decode_latent_into_processed_images as planar YUV 4:2:0 frames (float_dec_frames_i420): (T, 3 * size / 2, size) uint8 on
+        the GPU - per frame the Y plane, then U and V at half the size, what ffmpeg calls yuv420p and OpenCV's *_I420 conversions
+        use.  BT.601 limited range from the 8-bit samples, in integers: bitwise host_models.rgb8_to_i420(decode_u8(...))."""
+        if s_r_feats is not None:
+            self.set_feats(s_r_feats)
+        L = native.lib()
+        return self._run(lambda h, s, r, T, out, st: L.float_dec_frames_i420(h, s, r, T, native.MATRIX_BT601_LIMITED, out, st),
+                         s_r, r_d, (3 * self.size // 2, self.size), torch.uint8)
+
+    def frame_shape(self, out_format="rgb"):
+        """Shape of one frame as the hand-over calls store it: (size, size, 3), or (3 * size / 2, size) for "i420"."""
+        return (3 * self.size // 2, self.size) if out_format == "i420" else (self.size, self.size, 3)
+
     def saturation(self, reset=False, per_site=False):
         """(thread, tile) groups of 16-bit activation stores that held an inf / NaN since create / the last reset
         (float_dec_saturation; the decoder stores an out-of-range value as inf - loud - instead of clamping it):
@@ -126,10 +141,13 @@ class SynthesisHIP:
         return (tot.value, list(sites)) if per_site else tot.value
 
     @torch.no_grad()
-    def decode_into_host(self, s_r, r_d, host, staging=None, copy_stream=None):
+    def decode_into_host(self, s_r, r_d, host, staging=None, copy_stream=None, out_format=None):
         """decode_latent_into_processed_images with the reference's destination (a pre-allocated CPU tensor, FLOAT.py:139):
         `host` (T, size, size, 3) fp32, or uint8 for 8-bit frames (float_dec_frames_host_u8; the staging tensor has the same
-        dtype, one of another dtype is replaced).  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
+        dtype, one of another dtype is replaced).  out_format "i420": `host` (T, 3 * size / 2, size) uint8, planar YUV 4:2:0 as
+        decode_i420 gives it (float_dec_frames_host_i420); "rgb": the (T, size, size, 3) forms; None: by the number of dimensions
+        of a uint8 `host`.  A `host` of the wrong shape for the stated format is a ValueError; a staging tensor of another format
+        is replaced, never reinterpreted.  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
         workgroups inside the launches of batch i+1 (or, with `copy_stream`, copied on that stream while the next batch
         renders - see include/float_hip.h for why that form does not pay on MI355X).  Pageable: accepted, one staged
         hipMemcpyAsync behind each batch (the operator asks the runtime what `host` is, nothing is assumed).  Returns the
@@ -137,20 +155,31 @@ class SynthesisHIP:
         s_r = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         T = r_d.shape[0]
-        shape = (T, self.size, self.size, 3)
+        if out_format not in (None, "rgb", "i420"):
+            raise ValueError("out_format must be None, 'rgb' or 'i420' (got %r)" % (out_format,))
         if host.dtype not in (torch.float32, torch.uint8):
             raise ValueError("host must be float32 or uint8 (got %s)" % (host.dtype,))
+        if out_format is None:
+            out_format = "i420" if host.dtype == torch.uint8 and host.dim() == 3 else "rgb"
+        if out_format == "i420" and host.dtype != torch.uint8:
+            raise ValueError("I420 frames are uint8 (host is %s)" % (host.dtype,))
+        shape = (T,) + self.frame_shape(out_format)
         if tuple(host.shape) != shape or host.is_cuda or not host.is_contiguous():
-            raise ValueError("host must be a contiguous CPU float32 or uint8 tensor of shape %s" % (shape,))
+            raise ValueError("host must be a contiguous CPU %s tensor of shape %s for out_format %r"
+                             % ("uint8" if out_format == "i420" else "float32 or uint8", shape, out_format))
         if (staging is None or tuple(staging.shape) != shape or staging.dtype != host.dtype or not staging.is_cuda
                 or not staging.is_contiguous()):
             staging = torch.empty(shape, device=self.device, dtype=host.dtype)
         L = native.lib()
         fn = L.float_dec_frames_host_u8 if host.dtype == torch.uint8 else L.float_dec_frames_host
+        tail = (C.c_void_p(staging.data_ptr()), C.c_void_p(host.data_ptr()), native.stream_ptr(self.device),
+                C.c_void_p(copy_stream.cuda_stream) if copy_stream is not None else None)
         with torch.cuda.device(self.device):
-            native.check(fn(
-                self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, C.c_void_p(staging.data_ptr()), C.c_void_p(host.data_ptr()),
-                native.stream_ptr(self.device), C.c_void_p(copy_stream.cuda_stream) if copy_stream is not None else None))
+            if out_format == "i420":
+                native.check(L.float_dec_frames_host_i420(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T,
+                                                          native.MATRIX_BT601_LIMITED, *tail))
+            else:
+                native.check(fn(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, *tail))
         return staging
 
     @torch.no_grad()

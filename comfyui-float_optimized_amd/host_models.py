@@ -7,7 +7,10 @@ this package).  What is left is tensor plumbing:
   * image / audio pre-processing of the simple node (generate.py:29-39, 69-73), the face-aligned crop (utils/image.py:135-180;
     detector optional) and the band-limited resampler in front of wav2vec2
   * the one-hot emotion vector of a named emotion (FLOAT.py:196-200)
+  * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
+    writer for handing such frames to an encoder
 """
+import fractions
 import math
 
 import torch
@@ -169,3 +172,67 @@ def emotion_one_hot(name, device="cpu"):
     if idx is None:
         raise ValueError("%r is not one of %s" % (name, EMOTION_LABELS))
     return F.one_hot(torch.tensor(idx, device=device), num_classes=len(EMOTION_LABELS)).float()[None, None]
+
+
+def rgb8_to_i420(frames_u8):
+    """(T, R, R, 3) or (R, R, 3) uint8 RGB -> (T, 3R/2, R) or (3R/2, R) uint8 planar YUV 4:2:0 (I420: the Y plane R x R, then U and
+    V at R/2 x R/2 each, row-major, contiguous - OpenCV's *_I420 layout, ffmpeg's yuv420p).  8-bit BT.601 limited range, all in
+    int32 with >> an arithmetic shift (floor):
+        Y  = ((66 R + 129 G + 25 B + 128) >> 8) + 16                        per pixel, in [16, 235]
+        Mc = (c00 + c01 + c10 + c11 + 2) >> 2                               per 2 x 2 block and channel c
+        U  = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128                   in [16, 240]
+        V  = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128                    in [16, 240]
+    Chroma is sited at the block centre (Y4M's C420jpeg).  This is the definition of what SynthesisHIP.decode_i420 and
+    float_dec_frames[_host]_i420 produce: bitwise rgb8_to_i420(decode_u8(...)).  Works on any device."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (3, 4) or frames_u8.shape[-1] != 3:
+        raise ValueError("rgb8_to_i420 takes (T, H, W, 3) or (H, W, 3) uint8 frames, got %s %s" % (frames_u8.dtype, tuple(frames_u8.shape)))
+    single = frames_u8.dim() == 3
+    x = (frames_u8[None] if single else frames_u8).to(torch.int32)
+    T, H, W, _ = x.shape
+    if H % 2 or W % 2:
+        raise ValueError("rgb8_to_i420 needs even sizes for 4:2:0 chroma (got %d x %d)" % (H, W))
+    r, g, b = x[..., 0], x[..., 1], x[..., 2]
+    y = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+    m = (x.reshape(T, H // 2, 2, W // 2, 2, 3).sum(dim=(2, 4)) + 2) >> 2
+    mr, mg, mb = m[..., 0], m[..., 1], m[..., 2]
+    u = ((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128
+    v = ((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128
+    out = torch.cat([y.reshape(T, -1), u.reshape(T, -1), v.reshape(T, -1)], dim=1).to(torch.uint8)
+    out = out.reshape(T, H * 3 // 2, W)
+    return out[0] if single else out
+
+
+def y4m_rate(fps):
+    """The frame rate of a Y4M header as a fraction.
+    Rule 1 (NTSC family): a non-integer float fps with |fps * 1.001 - n| < 1e-4 for an integer n >= 1 is n * 1000 / 1001:
+    23.976 -> 24000/1001, 29.97 -> 30000/1001, 59.94 -> 60000/1001 (the decimal shorthands mean the rate they abbreviate; the
+    closest fraction alone would write 2997/100).  29.9, 30.0 and 29.98 are not within 1e-4 and do not snap.
+    Rule 2 (everything else, and every fractions.Fraction): fractions.Fraction(fps).limit_denominator(1001), so 25 -> 25/1,
+    12.5 -> 25/2, 29.9 -> 299/10."""
+    k = float(fps) * 1001.0 / 1000.0
+    if not isinstance(fps, fractions.Fraction) and round(k) >= 1 and abs(k - round(k)) < 1e-4 and float(fps) != round(float(fps)):
+        return fractions.Fraction(int(round(k)) * 1000, 1001)
+    return fractions.Fraction(fps).limit_denominator(1001)
+
+
+def write_y4m(path_or_file, frames_i420, fps):
+    """Write (T, 3R/2, R) uint8 I420 frames (rgb8_to_i420 / SynthesisHIP.decode_i420 / out_format="i420") as a YUV4MPEG2
+    stream, which ffmpeg, x264 and mpv read as it is: the header `YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420jpeg
+    XCOLORRANGE=LIMITED`, then `FRAME` + the frame's bytes per frame.  fps: as y4m_rate reads it (25 -> 25:1, 29.97 ->
+    30000:1001).  path_or_file: a path, or an object with write() (a pipe to an encoder's stdin)."""
+    if frames_i420.dtype != torch.uint8 or frames_i420.dim() != 3 or frames_i420.shape[1] * 2 != frames_i420.shape[2] * 3:
+        raise ValueError("write_y4m takes (T, 3R/2, R) uint8 I420 frames, got %s %s" % (frames_i420.dtype, tuple(frames_i420.shape)))
+    T, H32, W = frames_i420.shape
+    rate = y4m_rate(fps)
+    header = "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (W, H32 * 2 // 3, rate.numerator, rate.denominator)
+    data = frames_i420.detach().cpu().contiguous().numpy()
+    own = not hasattr(path_or_file, "write")
+    f = open(path_or_file, "wb") if own else path_or_file
+    try:
+        f.write(header.encode("ascii"))
+        for t in range(T):
+            f.write(b"FRAME\n")
+            f.write(data[t].tobytes())
+    finally:
+        if own:
+            f.close()

@@ -159,6 +159,26 @@ def _resolve_out_dtype(out, out_dtype):
     return _frame_dtype(torch.float32 if out_dtype is None else out_dtype)
 
 
+def resolve_out_format(out, out_dtype, out_format):
+    """(dtype, format) of a hand-over call.  out_format: None | "rgb" ((T, R, R, 3) frames, fp32 or uint8 as _resolve_out_dtype
+    decides) | "i420" ((T, 3R/2, R) uint8 planar YUV 4:2:0, host_models.rgb8_to_i420).  "i420" implies uint8: with
+    out_dtype=torch.float32 or an fp32 `out` it is a ValueError.  A caller-supplied `out` fixes the format by its dimensions (a
+    3-d uint8 tensor is I420), and a stated format that contradicts it is a ValueError."""
+    if out_format not in (None, "rgb", "i420"):
+        raise ValueError("out_format must be None, 'rgb' or 'i420' (got %r)" % (out_format,))
+    if out_format == "i420" and out is None and out_dtype is None:
+        out_dtype = torch.uint8
+    dtype = _resolve_out_dtype(out, out_dtype)
+    fmt = out_format
+    if fmt is None:
+        fmt = "i420" if out is not None and out.dtype == torch.uint8 and out.dim() == 3 else "rgb"
+    if fmt == "i420" and dtype != torch.uint8:
+        raise ValueError("I420 frames are uint8: out_format='i420' contradicts %s" % (dtype,))
+    if out is not None and out.dim() != (3 if fmt == "i420" else 4):
+        raise ValueError("out has %d dimensions, out_format %r takes %s" % (out.dim(), fmt, "(T, 3R/2, R)" if fmt == "i420" else "(T, R, R, 3)"))
+    return dtype, fmt
+
+
 class FloatHotPath:
     def __init__(self, fmt_state, dec_state, cfg: FmtConfig = None, device="cuda:0", size=512, fmt_dtype="fp16",
                  dec_dtype="fp16", max_frames=32, use_graph=2, max_batch=1):
@@ -283,26 +303,27 @@ class FloatHotPath:
             rd = rd[frame_range[0]:frame_range[1]]
         return self.dec.decode_latent_into_processed_images(s_r, rd)
 
-    def staging(self, n_frames, dtype=torch.float32):
-        """Device-side frame buffer of float_dec_frames_host[_u8], cached per clip length and dtype (786 MB for 250 fp32 frames
-        at 512 px, 197 MB as uint8; sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
+    def staging(self, n_frames, dtype=torch.float32, out_format="rgb"):
+        """Device-side frame buffer of float_dec_frames_host[_u8|_i420], cached per clip length, dtype and format (786 MB for 250
+        fp32 frames at 512 px, 197 MB as uint8, 98 MB as I420; sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
         hands the block of a released earlier result back without a new hipHostMalloc), because ComfyUI keeps node outputs
         alive across executions and a re-used buffer would silently overwrite them."""
         cache = self.__dict__.setdefault("_staging", {})
-        shape = (n_frames, self.size, self.size, 3)
-        if (shape, dtype) not in cache:
+        shape = (n_frames,) + self.dec.frame_shape(out_format)
+        if (shape, dtype, out_format) not in cache:
             cache.clear()  # one clip length and format at a time
-            cache[(shape, dtype)] = torch.empty(shape, device=self.device, dtype=_frame_dtype(dtype))
-        return cache[(shape, dtype)]
+            cache[(shape, dtype, out_format)] = torch.empty(shape, device=self.device, dtype=_frame_dtype(dtype))
+        return cache[(shape, dtype, out_format)]
 
     @torch.no_grad()
-    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None, out_dtype=None):
+    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None, out_dtype=None, out_format=None):
         """Frames of one clip (r_d (T,512)) into pinned host memory through float_dec_frames_host: the frames of batch i cross
         PCIe inside the launches of batch i+1.  Returns the host tensor (T,H,W,3); it is complete once the current stream has
         been synchronised (the callers that hand it to the user do that).  out_dtype: torch.float32 (default) or torch.uint8
         (8-bit frames quantised on the device, a quarter of the bytes); a caller-supplied `out` fixes the dtype, and an
-        out_dtype that contradicts it is a ValueError."""
-        out_dtype = _resolve_out_dtype(out, out_dtype)
+        out_dtype that contradicts it is a ValueError.  out_format="i420": (T, 3H/2, W) uint8 planar YUV 4:2:0, converted on the
+        device (half the bytes of uint8 RGB; resolve_out_format has the rules)."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
         if feats is not None:
             self.dec.set_feats(feats)
         rd = r_d[0] if r_d.dim() == 3 else r_d
@@ -317,10 +338,10 @@ class FloatHotPath:
         inflight = self.__dict__.setdefault("_host_inflight", [])
         inflight[:] = [(t, e) for t, e in inflight if not e.query()]
         if out is None:
-            out = torch.empty((n, self.size, self.size, 3), dtype=out_dtype, pin_memory=True)
+            out = torch.empty((n,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
         # (the frames by hipMemcpyAsync on a second stream instead of copy workgroups inside the next batch's launches: 121.4-122.1 vs
         # 105.7-106.8 ms per clip on the round-6 kernels, as in round 3 - decoder.decode_into_host(copy_stream=) keeps the form)
-        self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype))
+        self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype, out_format), out_format=out_format)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         inflight.append((out, ev))
@@ -335,17 +356,17 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                         noise=None, frame_range=None, out=None, return_rd=False, out_dtype=None):
+                         noise=None, frame_range=None, out=None, return_rd=False, out_dtype=None, out_format=None):
         """The product's hot path for one clip (B = 1): conditioning tensors in HBM -> frames in pinned host memory, the
         reference's destination (FLOAT.py:139,157-167).  This is what InferenceAgent.run_inference, FloatProcess and bench.py run.
-        out_dtype: as in decode_to_host (torch.uint8 = 8-bit frames)."""
-        out_dtype = _resolve_out_dtype(out, out_dtype)
+        out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
         if feats is not None:
             self.dec.set_feats(feats)
         if noise is None:
             noise = draw_noise(self.n_chunks(wa.shape[1]), 1, self.cfg, seed)
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
-        host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype)
+        host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype, out_format)
         return (host, r_d) if return_rd else host
 
     def _overlap_streams(self, mode):
@@ -372,14 +393,14 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host_overlap(self, r_s, wa, we, s_r, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, noise=None,
-                                 out=None, mode="prio", return_rd=False, out_dtype=None):
+                                 out=None, mode="prio", return_rd=False, out_dtype=None, out_format=None):
         """generate_to_host with the two stages pipelined (FLOAT.py runs 209-253 then 113-169; here window k is decoded and
         handed to the host on a second stream while the chain samples window k + 1).  Same kernels on the same operands as
         the sequential order, per-window decode batches (50 frames = 32 + 18 instead of 250 = 7 x 32 + 26): frames bitwise
         equal to generate_to_host (decode batching does not change a frame, tests/test_dec_gpu.py).  FLOAT_AMD_OVERLAP
         selects it in InferenceAgent.infer_device; what it measures against the sequential order: DESIGN.md section 7.
-        out_dtype: as in decode_to_host (torch.uint8 = 8-bit frames)."""
-        out_dtype = _resolve_out_dtype(out, out_dtype)
+        out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
         T = wa.shape[1]
         dev = self.device
         if noise is None:
@@ -391,8 +412,8 @@ class FloatHotPath:
         inflight = self.__dict__.setdefault("_host_inflight", [])
         inflight[:] = [(t, e) for t, e in inflight if not e.query()]
         if out is None:
-            out = torch.empty((T, self.size, self.size, 3), dtype=out_dtype, pin_memory=True)
-        staging = self.staging(T, out_dtype)
+            out = torch.empty((T,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
+        staging = self.staging(T, out_dtype, out_format)
         s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
         with torch.cuda.stream(s_fmt):
             ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
@@ -403,7 +424,7 @@ class FloatHotPath:
                 ev.record(s_fmt)
             with torch.cuda.stream(s_dec):
                 s_dec.wait_event(ev)
-                self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], out[f0:f1], staging[f0:f1])
+                self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], out[f0:f1], staging[f0:f1], out_format=out_format)
         cur.wait_stream(s_dec)
         cur.wait_stream(s_fmt)
         done = torch.cuda.Event()

@@ -10,7 +10,7 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
-from ...pipeline import FloatHotPath, precision_policy, report_precision, report_range, verify_frames_default
+from ...pipeline import FloatHotPath, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
 
 # key prefixes of the unified checkpoint (utils/downloader.py:35-42)
@@ -277,13 +277,17 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out=None,
-                     out_dtype=None):
+                     out_dtype=None, out_format=None):
         """Portrait and waveform in HBM -> (T,H,W,3) fp32 frames in [0,1] in pinned host memory: every operator of the path and
         the hand-over (frames of decode batch i leave inside the launches of batch i+1, float_dec_frames_host).  bench.py
         times exactly this call.  Like the reference, the grid size comes from opt.nfe (FLOAT.py:188).
         out_dtype=torch.uint8: 8-bit frames, quantised by the decoder's last kernel (round(255 * frame), bitwise what rounding the
         fp32 frames gives) - a quarter of the staging, pinned and PCIe bytes; default (None) fp32.  A caller-supplied `out`
-        fixes the dtype; contradicting it is a ValueError."""
+        fixes the dtype; contradicting it is a ValueError.
+        out_format="i420": (T, 3H/2, W) uint8 planar YUV 4:2:0 (BT.601 limited range, host_models.rgb8_to_i420 of the 8-bit
+        frames, converted by the decoder's last kernel) - what a video encoder reads, half the bytes of uint8 RGB
+        (host_models.write_y4m pipes it).  It implies uint8; with out_dtype=torch.float32 or an fp32 `out` it is a ValueError."""
+        resolve_out_format(out, out_dtype, out_format)  # a contradiction is refused before anything runs
         self.to_target()  # no-op while resident
         c = self.conditions_device(s, a, emo)  # encoder kernels enqueued; nothing below waits for them on the host
         n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
@@ -293,18 +297,19 @@ class InferenceAgent:
         if ov and ov != "0":
             host = self.G.generate_to_host_overlap(c["r_s"], c["wa"], c["we"], c["s_r"], self.opt.nfe, a_cfg_scale, r_cfg_scale,
                                                    e_cfg_scale, noise=noise, out=out, mode=ov, return_rd=verify,
-                                                   out_dtype=out_dtype)
+                                                   out_dtype=out_dtype, out_format=out_format)
         else:
             host = self.G.generate_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                           e_cfg_scale, noise=noise, out=out, return_rd=verify, out_dtype=out_dtype)
+                                           e_cfg_scale, noise=noise, out=out, return_rd=verify, out_dtype=out_dtype,
+                                           out_format=out_format)
         host, r_d = host if verify else (host, None)
         torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
         self.G.release_host_inflight()
         bad = self.check_range("InferenceAgent.infer_device", allow_rebuild=True)
         if bad == "rebuilt":
-            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype)  # once more, in the wider types
+            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format)  # once more, in the wider types
         if verify and not bad:  # a range failure has been reported already: the frames are wrong for a reason that is known
-            # 8-bit output: the staging buffer holds quantised frames, so the first k frames are decoded once more in the fp32
+            # 8-bit output (RGB or I420): the staging buffer holds quantised frames, so the first k frames are decoded once more in the fp32
             # form by the same handle (a frame does not depend on its batch: bitwise what the fp32 staging buffer would hold)
             frames_dev = None
             if host.dtype == torch.uint8:
@@ -312,7 +317,7 @@ class InferenceAgent:
                 frames_dev = self.G.dec.decode_latent_into_processed_images(c["s_r"], r_d[0, :k])
             if self.check_precision("InferenceAgent.infer_device", s, c, noise, r_d, a_cfg_scale, r_cfg_scale, e_cfg_scale,
                                     allow_rebuild=True, frames_dev=frames_dev) == "rebuilt":
-                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype)  # once more, in fp32
+                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format)  # once more, in fp32
         return host
 
     def range_counts(self, reset=True):
@@ -410,13 +415,15 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None,
-                           out_dtype=None):
+                           out_dtype=None, out_format=None):
         """B clips through one stacked FMT chain (every weight is read once per evaluation for all of them), then decoded one
         after the other.  Clips of equal length run float_fmt_sample_batch; clips of different lengths run its ragged sibling
         (FlowMatchingTransformerHIP.sample_ragged: a clip leaves the stack after its last window).  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
         item (FloatProcess uses seed + i, nodes.py:189-209) - each item keeps its own noise stream, so item i is what
         infer_device gives for it alone (bit for bit where the GEMM tilings coincide, within the fp16 tolerance otherwise).
-        Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device."""
+        Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device; out_format="i420":
+        (T,3H/2,W) uint8 planar YUV 4:2:0 as there."""
+        resolve_out_format(None, out_dtype, out_format)  # a contradiction is refused before anything runs
         self.to_target()
         B = len(items)
         seeds = list(seeds) if seeds is not None else [self.opt.seed] * B
@@ -449,7 +456,7 @@ class InferenceAgent:
         for i in range(B):
             # decodes queue back to back: the last frames of item i cross PCIe inside the launches of item i + 1
             self.G.dec.set_feats16(feats[i], self.enc.dtype)
-            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i], out_dtype=out_dtype))
+            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i], out_dtype=out_dtype, out_format=out_format))
         torch.cuda.current_stream(self.rank).synchronize()
         self.G.release_host_inflight()
         self.check_range("InferenceAgent.infer_device_batch")
@@ -457,8 +464,9 @@ class InferenceAgent:
 
     @torch.no_grad()
     def run_inference(self, res_video_path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0,
-                      emo="S2E", nfe=10, no_crop=False, seed=25):
-        """Reference signature (generate.py:154-173).  Returns (T,H,W,3) fp32 in [0,1] on the CPU (pinned).
+                      emo="S2E", nfe=10, no_crop=False, seed=25, out_format=None):
+        """Reference signature (generate.py:154-173).  Returns (T,H,W,3) fp32 in [0,1] on the CPU (pinned); out_format="i420":
+        (T,3H/2,W) uint8 planar YUV 4:2:0 as in infer_device.
         Like the reference, the grid size comes from opt.nfe, not from the `nfe` argument (FLOAT.py:188)."""
         s, a = self.host_inputs(ref_img, ref_audio, no_crop)
-        return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed)
+        return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format=out_format)

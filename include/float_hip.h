@@ -23,7 +23,7 @@
  *     allocation happens inside the run-time calls (float_aud_reserve is the explicit exception).
  *     Every run-time call enqueues kernels only (device-to-device moves included: memcpy / memset
  *     nodes of a caller's stream capture did not replay reproducibly on ROCm 7.2), except
- *     float_dec_frames_host[_u8], whose last batch goes to the host by hipMemcpyAsync.  Capture by the
+ *     float_dec_frames_host[_u8|_i420], whose last batch goes to the host by hipMemcpyAsync.  Capture by the
  *     caller (hipStreamBeginCapture on `stream`) is tested for the float_fmt_* calls.
  *   - calls on one handle must be serialised by the caller; different handles are independent.
  */
@@ -38,7 +38,8 @@ extern "C" {
 #endif
 
 /* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
- * float_dec_frames_host_u8 (8-bit frames) and float_fmt_sample_begin_ragged / float_fmt_sample_batch_ragged (clips of different
+ * float_dec_frames_host_u8 (8-bit frames), float_dec_frames_i420 / float_dec_frames_host_i420 (planar YUV 4:2:0 frames) and
+ * float_fmt_sample_begin_ragged / float_fmt_sample_batch_ragged (clips of different
  * lengths in one chain) are purely additive - no existing signature, structure or behaviour changed, so a
  * caller built against the earlier v6 header runs unchanged. */
 #define FLOAT_HIP_ABI_VERSION 6
@@ -262,6 +263,24 @@ int float_dec_frames_u8(float_dec_t* h, const float* s_r, const float* r_d, int3
                         uint8_t* out_hwc, void* stream);
 int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames,
                              uint8_t* out_hwc, uint8_t* host_hwc, void* stream, void* copy_stream);
+
+/* Planar YUV 4:2:0 frames (I420), converted on the device from the 8-bit samples R8, G8, B8 that float_dec_frames_u8 stores.
+ * One frame is 3 * size * size / 2 bytes: the Y plane size x size, then U and V at size/2 x size/2 each, row-major, contiguous.
+ * `matrix` selects the conversion; FLOAT_DEC_MATRIX_BT601_LIMITED (0) is the only one, anything else is FLOAT_E_INVALID.  For it,
+ * in int32 with >> an arithmetic shift (floor):
+ *   Y = ((66 R8 + 129 G8 + 25 B8 + 128) >> 8) + 16                                    per pixel, in [16, 235]
+ *   Mc = (c00 + c01 + c10 + c11 + 2) >> 2                                             per 2 x 2 block and channel c
+ *   U = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128,  V = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128      in [16, 240]
+ * (chroma sited at the block centre, Y4M's C420jpeg).  The definition starts from the 8-bit samples, so the bytes are those a
+ * caller gets by converting float_dec_frames_u8's frames this way, whichever kernel forms them.  `out` must be 4-byte aligned;
+ * `host`, `copy_stream` and what synchronising `stream` means follow float_dec_frames_host_u8's contract word for word (pinned and
+ * 16-byte aligned: copy workgroups; anything else: one hipMemcpyAsync behind each batch).  Calls of all three formats may
+ * alternate on one handle. */
+enum { FLOAT_DEC_MATRIX_BT601_LIMITED = 0 };
+int float_dec_frames_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix,
+                          uint8_t* out, void* stream);
+int float_dec_frames_host_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix,
+                               uint8_t* out, uint8_t* host, void* stream, void* copy_stream);
 
 /* Shape (channels, resolution) of skip feature i as float_dec_set_feats reads it: feats[i] must hold
  * channels * resolution * resolution floats.  Lets the caller validate tensors wired from an arbitrary encoder. */
