@@ -215,24 +215,66 @@ def y4m_rate(fps):
     return fractions.Fraction(fps).limit_denominator(1001)
 
 
+class Y4MWriter:
+    """A YUV4MPEG2 stream written block by block, for frames that arrive in pieces (InferenceAgent.stream_device with
+    out_format="i420"): the header `YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420jpeg XCOLORRANGE=LIMITED` goes out once, when the
+    writer is made, and every write(frames) appends `FRAME` + the frame's bytes per frame.  path_or_file: a path (opened here
+    and closed by close() / on leaving the `with` block), or an object with write() (a pipe to an encoder's stdin), which is
+    left open.  fps: as y4m_rate reads it.  write() has handed the bytes on when it returns, so a view of a ring slot may be
+    given back right after it."""
+
+    def __init__(self, path_or_file, width, height, fps):
+        width, height = int(width), int(height)
+        if width < 2 or height < 2 or width % 2 or height % 2:
+            raise ValueError("Y4MWriter: 4:2:0 frames have even sides (got %d x %d)" % (width, height))
+        self.width, self.height = width, height
+        rate = y4m_rate(fps)
+        header = "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (width, height, rate.numerator, rate.denominator)
+        self.frames = 0
+        self._own = not hasattr(path_or_file, "write")
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        try:
+            self._f.write(header.encode("ascii"))
+        except BaseException:
+            self.close()
+            raise
+
+    def write(self, frames_i420):
+        """Append (n, 3 * height / 2, width) uint8 I420 frames; returns the number of frames written so far."""
+        if self._f is None:
+            raise ValueError("Y4MWriter.write after close()")
+        want = (3 * self.height // 2, self.width)
+        if frames_i420.dtype != torch.uint8 or frames_i420.dim() != 3 or tuple(frames_i420.shape[1:]) != want:
+            raise ValueError("Y4MWriter.write takes (n, %d, %d) uint8 I420 frames, got %s %s"
+                             % (want + (frames_i420.dtype, tuple(frames_i420.shape))))
+        data = frames_i420.detach().cpu().contiguous().numpy()
+        for t in range(data.shape[0]):
+            self._f.write(b"FRAME\n")
+            self._f.write(data[t].tobytes())
+        self.frames += data.shape[0]
+        return self.frames
+
+    def close(self):
+        f, self._f = self._f, None
+        if f is not None and self._own:
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def write_y4m(path_or_file, frames_i420, fps):
     """Write (T, 3R/2, R) uint8 I420 frames (rgb8_to_i420 / SynthesisHIP.decode_i420 / out_format="i420") as a YUV4MPEG2
     stream, which ffmpeg, x264 and mpv read as it is: the header `YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420jpeg
     XCOLORRANGE=LIMITED`, then `FRAME` + the frame's bytes per frame.  fps: as y4m_rate reads it (25 -> 25:1, 29.97 ->
-    30000:1001).  path_or_file: a path, or an object with write() (a pipe to an encoder's stdin)."""
+    30000:1001).  path_or_file: a path, or an object with write() (a pipe to an encoder's stdin).  Y4MWriter is the
+    block-by-block form."""
     if frames_i420.dtype != torch.uint8 or frames_i420.dim() != 3 or frames_i420.shape[1] * 2 != frames_i420.shape[2] * 3:
         raise ValueError("write_y4m takes (T, 3R/2, R) uint8 I420 frames, got %s %s" % (frames_i420.dtype, tuple(frames_i420.shape)))
     T, H32, W = frames_i420.shape
-    rate = y4m_rate(fps)
-    header = "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (W, H32 * 2 // 3, rate.numerator, rate.denominator)
-    data = frames_i420.detach().cpu().contiguous().numpy()
-    own = not hasattr(path_or_file, "write")
-    f = open(path_or_file, "wb") if own else path_or_file
-    try:
-        f.write(header.encode("ascii"))
-        for t in range(T):
-            f.write(b"FRAME\n")
-            f.write(data[t].tobytes())
-    finally:
-        if own:
-            f.close()
+    with Y4MWriter(path_or_file, W, H32 * 2 // 3, fps) as w:
+        w.write(frames_i420)

@@ -1,6 +1,7 @@
 """The hot path as one object: (conditioning tensors in HBM) -> r_d -> frames.
 Mirrors FLOAT.sample + decode_latent_into_processed_images (reference FLOAT.py:172-253, 113-169)
 with the noise stream explicit."""
+import collections
 import logging
 import math
 import os
@@ -179,6 +180,13 @@ def resolve_out_format(out, out_dtype, out_format):
     return dtype, fmt
 
 
+class FrameBlock(collections.namedtuple("FrameBlock", "first last frames")):
+    """One FMT window of a streamed clip (FloatHotPath.stream_to_host): frames [first, last) of the clip, `frames` a view of
+    a pinned ring slot - (last - first, H, W, 3), or (last - first, 3H/2, W) for I420 - complete when the block is yielded and
+    OVERWRITTEN after the generator has been advanced again: copy it to keep it."""
+    __slots__ = ()
+
+
 class FloatHotPath:
     def __init__(self, fmt_state, dec_state, cfg: FmtConfig = None, device="cuda:0", size=512, fmt_dtype="fp16",
                  dec_dtype="fp16", max_frames=32, use_graph=2, max_batch=1):
@@ -191,6 +199,13 @@ class FloatHotPath:
 
     def n_chunks(self, T):
         return int(math.ceil(T / self.cfg.num_frames_for_clip))
+
+    def require_no_stream(self, what):
+        """One FMT handle carries one job, and the decoder holds one clip's skip features: while a stream_to_host generator is
+        open on this object every other producer is refused."""
+        opened = self.__dict__.get("_open_stream")
+        if opened:
+            raise RuntimeError("%s: %s is still open on this FloatHotPath - exhaust it or close() it first" % (what, opened))
 
     def batched_fmt(self, n_clips):
         """An FMT handle whose workspace holds `n_clips` stacked clips (float_fmt_sample_batch), built on first use from the
@@ -289,6 +304,7 @@ class FloatHotPath:
     def sample(self, r_s, wa, we, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
                include_r_cfg=False):
         """r_d (B,T,512).  `noise` (n_chunks,B,50,512) overrides the seeded CPU-generator draw."""
+        self.require_no_stream("sample")
         if noise is None:
             noise = draw_noise(self.n_chunks(wa.shape[1]), wa.shape[0], self.cfg, seed)
         return self.fmt.sample(r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, include_r_cfg)
@@ -296,6 +312,7 @@ class FloatHotPath:
     @torch.no_grad()
     def decode(self, s_r, feats, r_d, frame_range=None):
         """(T,H,W,3) fp32 in [0,1] on the GPU for batch item 0; frame_range=(t0,t1) decodes a shard."""
+        self.require_no_stream("decode")
         if feats is not None:
             self.dec.set_feats(feats)
         rd = r_d[0] if r_d.dim() == 3 else r_d
@@ -324,6 +341,7 @@ class FloatHotPath:
         out_dtype that contradicts it is a ValueError.  out_format="i420": (T, 3H/2, W) uint8 planar YUV 4:2:0, converted on the
         device (half the bytes of uint8 RGB; resolve_out_format has the rules)."""
         out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        self.require_no_stream("decode_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
         rd = r_d[0] if r_d.dim() == 3 else r_d
@@ -361,6 +379,7 @@ class FloatHotPath:
         reference's destination (FLOAT.py:139,157-167).  This is what InferenceAgent.run_inference, FloatProcess and bench.py run.
         out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
         out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        self.require_no_stream("generate_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
         if noise is None:
@@ -368,6 +387,93 @@ class FloatHotPath:
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
         host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype, out_format)
         return (host, r_d) if return_rd else host
+
+    def stream_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
+                       noise=None, out_dtype=None, out_format=None, slots=3):
+        """generate_to_host for one clip (B = 1) as a generator: one FrameBlock(first, last, frames) per FMT window, in frame
+        order, the same bytes as the whole-clip call (same kernels on the same operands; decode batching does not change a
+        frame).  `frames` is a view of one of `slots` pinned ring buffers and is complete when it is yielded: the generator has
+        waited on that block's own event, never on the whole stream.
+
+        Everything runs on the stream that is current at the first next(): sample(k), decode(k) into the slot of block k,
+        event(k), sample(k + 1), ...  Window k + 1 (and further windows, as far as free slots allow) is enqueued BEFORE the wait
+        for event(k), so the device works while the consumer holds block k.
+
+        Lifetime: the slot of block k belongs to the consumer from the yield of block k until the generator is advanced
+        again.  After that it is OVERWRITTEN by block k + slots - a consumer that wants to keep a block copies it
+        (`blk.frames.clone()`).  Work that writes a slot is enqueued only after the consumer has given that slot back.
+
+        Memory: `slots` pinned buffers and ONE device staging buffer of num_frames_for_clip frames each, allocated once and kept
+        on the generator (the whole-clip staging() cache is not touched) - slots x 50 frames whatever T is, where
+        generate_to_host holds T frames on both sides.  The latents, conditions and noise still grow with T (about 6 KB per
+        frame against 786 KB for an fp32 frame at 512 px).  The last block may be short: it is a prefix view of its slot.
+        The buffers are allocated inside the first next() of every stream: where the host allocator has no cached block of that
+        size (the first stream of a process, or of a format) the pinned allocation - 472 MB for fp32 at 512 px and 3 slots - is
+        part of the time to the first block; later streams get the cached blocks back.
+
+        slots >= 2, B = 1 and the resolve_out_format rules are checked here, at the call (ValueError); nothing is enqueued before the
+        first next().  While the generator is open (first next() until exhaustion, close(), garbage collection or an exception
+        thrown into it) sample, decode*, generate* and a second stream on this object raise RuntimeError.  Leaving early waits
+        for the work already enqueued, drops the slots and clears that flag.  The FMT handle's unfinished job needs no abort
+        call: float_fmt_sample_begin overwrites every field of the handle's job record, the first window of a job re-stages the
+        time table and the history rows of the workspace, and the only call that reads an unfinished job is
+        float_fmt_sample_next, which is reachable only through the WindowSampler this generator drops - so the next sample /
+        sample_begin starts clean."""
+        if int(slots) < 2:
+            raise ValueError("stream_to_host needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
+        out_dtype, out_format = resolve_out_format(None, out_dtype, out_format)
+        if wa.dim() != 3 or wa.shape[0] != 1:
+            raise ValueError("stream_to_host streams one clip (B = 1): wa must be (1, T, dim_a), got %s" % (tuple(wa.shape),))
+        self.require_no_stream("stream_to_host")
+        return self._stream_blocks(r_s, wa, we, s_r, feats, nfe, (a_cfg_scale, r_cfg_scale, e_cfg_scale), seed, noise,
+                                   out_dtype, out_format, int(slots))
+
+    def _stream_blocks(self, r_s, wa, we, s_r, feats, nfe, scales, seed, noise, out_dtype, out_format, slots):
+        self.require_no_stream("stream_to_host")  # another stream may have been started since the call
+        dev, L = self.device, self.cfg.num_frames_for_clip
+        T = wa.shape[1]
+        self._open_stream = "stream_to_host (%d frames, %d slots)" % (T, slots)
+        pending = collections.deque()  # (first, last, slot view, event) of the blocks enqueued and not yet yielded
+        ring = staging = ws = None
+        try:
+            st = torch.cuda.current_stream(dev)
+            with torch.cuda.stream(st):
+                if feats is not None:
+                    self.dec.set_feats(feats)
+                if noise is None:
+                    noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
+                fshape = self.dec.frame_shape(out_format)
+                ring = [torch.empty((L,) + fshape, dtype=out_dtype, pin_memory=True) for _ in range(slots)]
+                staging = torch.empty((L,) + fshape, device=dev, dtype=out_dtype)
+                s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
+                ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, *scales)
+            n_win, enqueued = ws.n_chunks, 0
+            for j in range(n_win):
+                # block j is about to go to the consumer, who holds nothing now: blocks j .. j + slots - 1 sit in `slots` different
+                # slots, and every earlier block has been given back
+                with torch.cuda.stream(st):
+                    while enqueued < min(n_win, j + slots):
+                        k, (f0, f1) = ws.next()
+                        view = ring[k % slots][:f1 - f0]
+                        self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], view, staging[:f1 - f0], out_format=out_format)
+                        ev = torch.cuda.Event()
+                        ev.record(st)
+                        pending.append((f0, f1, view, ev))
+                        enqueued += 1
+                f0, f1, view, ev = pending.popleft()
+                ev.synchronize()
+                yield FrameBlock(f0, f1, view)
+        finally:
+            # early exit (close(), garbage collection, an exception thrown in or raised above): the copy workgroups of the blocks
+            # still in flight store into the ring, so it is dropped only after the last of them has run.  Events complete in
+            # stream order: the last one covers the others, and the job's tensors with them.
+            try:
+                if pending:
+                    pending[-1][3].synchronize()
+            finally:
+                pending.clear()
+                del ring, staging, ws
+                self._open_stream = None
 
     def _overlap_streams(self, mode):
         """(chain stream, decoder stream) of the stage-overlapped form.  mode "prio": two streams of one device queue set, the
@@ -401,6 +507,7 @@ class FloatHotPath:
         selects it in InferenceAgent.infer_device; what it measures against the sequential order: DESIGN.md section 7.
         out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
         out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        self.require_no_stream("generate_to_host_overlap")
         T = wa.shape[1]
         dev = self.device
         if noise is None:
@@ -444,6 +551,7 @@ class FloatHotPath:
         clip): the decoder's grids own every CU, so each of the chain's ~3000 tiny dependent kernels per
         window queues behind running decoder workgroups; kept as an option for CU-partitioned streams.
         frame_range=(t0,t1) decodes only that shard of the clip (multi-GPU frame sharding)."""
+        self.require_no_stream("generate")
         if feats is not None:
             self.dec.set_feats(feats)
         T = wa.shape[1]

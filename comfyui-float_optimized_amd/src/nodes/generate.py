@@ -221,6 +221,8 @@ class InferenceAgent:
         decoder, r_s); a (N,) the normalised 16 kHz waveform -> (wa, T); and for any `emo` that is not one of the seven labels
         (None, 'none', 'S2E', ...) the speech-emotion scores (FLOAT.py:196-198)."""
         o = self.opt
+        if self.G is not None:
+            self.G.require_no_stream("conditions_device")  # it hands this clip's skip features to the decoder an open stream reads
         if host_models.emotion_index(emo) is None and self.emotion_predictor is None:
             raise NotImplementedError(
                 "emotion='none' asks the speech-emotion model for scores (FLOAT.py:196-198) but the checkpoint has "
@@ -319,6 +321,66 @@ class InferenceAgent:
                                     allow_rebuild=True, frames_dev=frames_dev) == "rebuilt":
                 return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format)  # once more, in fp32
         return host
+
+    def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,
+                      out_format=None, slots=3):
+        """The streaming sibling of infer_device: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
+        frame order - concatenated, bit for bit the frames infer_device returns for the same inputs and seed, in both
+        FLOAT_AMD_NOISE modes and all three formats (out_dtype / out_format as there).  `frames` is a view of one of `slots`
+        pinned buffers (FloatHotPath.stream_to_host has the contract): complete when yielded, OVERWRITTEN once the generator has
+        been advanced again - copy what is to be kept.  Pinned memory is slots x 50 frames whatever the clip's length, and the
+        first block arrives after one window instead of after the clip.  slots < 2 or contradicting formats raise ValueError here,
+        at the call; nothing runs before the first next().  While the stream is open every other call that produces frames on
+        this agent raises RuntimeError; close() (or dropping) the generator early leaves the agent usable.
+        After the last block FLOAT_AMD_RANGE is applied once: warn, raise (Fp16RangeError from the next() that ends the stream)
+        and off as in infer_device; auto cannot run frames again that were consumed already and acts as warn.  A stream left
+        early (close(), dropped, an exception in the consumer) is not reported, and its range counters are read and reset so
+        that they are not held against the next clip.  FLOAT_AMD_VERIFY is NOT applied in a stream, and FLOAT_AMD_OVERLAP is ignored (the stream is
+        windowed already, on one queue)."""
+        self._check_stream_call("stream_device", slots, out_dtype, out_format)
+        return self._stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, int(slots))
+
+    def _check_stream_call(self, what, slots, out_dtype, out_format):
+        """What a stream refuses at the call, before its generator exists (a generator's body runs at the first next())."""
+        if int(slots) < 2:
+            raise ValueError("%s needs slots >= 2 (one block with the consumer, one in flight), got %r" % (what, slots))
+        resolve_out_format(None, out_dtype, out_format)
+        if self.G is not None:
+            self.G.require_no_stream(what)
+
+    def _stream_device(self, s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots):
+        self.to_target()  # no-op while resident
+        with torch.no_grad():
+            c = self.conditions_device(s, a, emo)
+            n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
+            noise = self._noise_to_device(n_chunks, seed if seed is not None else self.opt.seed)
+        done = False
+        try:
+            yield from self.G.stream_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
+                                             e_cfg_scale, noise=noise, out_dtype=out_dtype, out_format=out_format, slots=slots)
+            done = True
+        finally:
+            # left early: the inner generator has waited for its work; what the abandoned windows counted is not the next clip's
+            if not done and self.G is not None and not self.G.__dict__.get("_open_stream") and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
+                self.range_counts(reset=True)
+        where = "InferenceAgent.stream_device"
+        if os.environ.get("FLOAT_AMD_RANGE", "warn").lower() == "auto":
+            where += " (FLOAT_AMD_RANGE=auto acts as warn in a stream: the frames have been consumed and are not run again)"
+        self.check_range(where)
+
+    def stream_inference(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False,
+                         seed=25, out_dtype=None, out_format=None, slots=3):
+        """The streaming sibling of run_inference: host inputs as there, blocks as stream_device yields them.  There is no
+        `nfe` argument: the grid size comes from opt.nfe (run_inference keeps the reference's argument and ignores it)."""
+        self._check_stream_call("stream_inference", slots, out_dtype, out_format)
+        return self._stream_inference(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, out_dtype,
+                                      out_format, int(slots))
+
+    def _stream_inference(self, ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, out_dtype,
+                          out_format, slots):
+        with torch.no_grad():
+            s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+        yield from self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots)
 
     def range_counts(self, reset=True):
         """{operator: clamped / non-finite 16-bit stores since the last call} over every fp16 handle of the agent."""
