@@ -86,24 +86,28 @@ class SynthesisHIP:
             native.check(native.lib().float_dec_set_feats16(self._h, ptrs, len(bufs), native.DTYPES[dtype or self.dtype],
                                                             native.stream_ptr(self.device)))
 
-    def _run(self, fn, s_r, r_d, shape, out_dtype=torch.float32):
+    def _run(self, fn, s_r, r_d, shape, out_dtype=torch.float32, out=None):
+        """out: a contiguous (T,) + shape device tensor of out_dtype to write into (else a new one)."""
         s_r = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         if s_r.numel() != self.style_dim:
             raise ValueError("s_r must have %d elements (decoder batch is 1, FLOAT.py:140)" % self.style_dim)
         T = r_d.shape[0]
-        out = torch.empty((T,) + shape, device=self.device, dtype=out_dtype)
+        if out is None:
+            out = torch.empty((T,) + shape, device=self.device, dtype=out_dtype)
+        elif (tuple(out.shape) != (T,) + shape or out.dtype != out_dtype or out.device != r_d.device or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (out_dtype, (T,) + shape, r_d.device))
         with torch.cuda.device(self.device):
             native.check(fn(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, C.c_void_p(out.data_ptr()),
                             native.stream_ptr(self.device)))
         return out
 
     @torch.no_grad()
-    def decode_latent_into_processed_images(self, s_r, r_d, s_r_feats=None):
-        """FLOAT.py:113-169: (T, H, W, 3) fp32 in [0,1]; stays on the GPU (the caller copies out)."""
+    def decode_latent_into_processed_images(self, s_r, r_d, s_r_feats=None, out=None):
+        """FLOAT.py:113-169: (T, H, W, 3) fp32 in [0,1]; stays on the GPU (the caller copies out), in `out` where one is given."""
         if s_r_feats is not None:
             self.set_feats(s_r_feats)
-        return self._run(native.lib().float_dec_frames, s_r, r_d, (self.size, self.size, 3))
+        return self._run(native.lib().float_dec_frames, s_r, r_d, (self.size, self.size, 3), out=out)
 
     @torch.no_grad()
     def decode_u8(self, s_r, r_d, s_r_feats=None):

@@ -113,6 +113,12 @@ def report_precision(report, where, action=None, min_psnr=None):
     return fault
 
 
+def _rows(r_d, frame_range=None):
+    """The (T, dim_w) latent rows of one clip from r_d (1, T, dim_w) or (T, dim_w); frame_range=(t0, t1): that shard of them."""
+    rd = r_d[0] if r_d.dim() == 3 else r_d
+    return rd if frame_range is None else rd[frame_range[0]:frame_range[1]]
+
+
 @torch.no_grad()
 def verify_decoder(dec_state, size, s_r, feats, r_d, frames_dev, k, device="cuda:0", style_dim=512, twin=None):
     """The decoder half of the precision guard, callable on its own: decode the first k latents of `r_d` with an fp32 twin
@@ -122,7 +128,7 @@ def verify_decoder(dec_state, size, s_r, feats, r_d, frames_dev, k, device="cuda
     and closed.  Returns {"decoder": cmp_summary, "k", "build_ms", "hbm_bytes"}."""
     import time
     dev = torch.device(device)
-    rd = (r_d[0] if r_d.dim() == 3 else r_d).to(dev, torch.float32)
+    rd = _rows(r_d).to(dev, torch.float32)
     k = max(1, min(int(k), rd.shape[0], frames_dev.shape[0]))
     own = twin is None
     build_ms, hbm = 0.0, 0
@@ -196,6 +202,12 @@ class FloatHotPath:
         self._fmt_state, self._dec_state, self._use_graph = fmt_state, dec_state, use_graph
         self.fmt = FlowMatchingTransformerHIP(fmt_state, self.cfg, device, fmt_dtype, use_graph, max_batch)
         self.dec = SynthesisHIP(dec_state, size, self.cfg.dim_w, device, dec_dtype, max_frames)
+        self._fmt_batched = {}     # {max_batch: FMT handle for stacked clips} (batched_fmt; at most one)
+        self._staging = {}         # {(shape, dtype, format): device frame buffer of the hand-over} (staging; at most one)
+        self._host_inflight = []   # [(pinned host tensor, event)] of hand-overs that may still be storing (_hold_inflight)
+        self._ov_streams = {}      # {mode: (chain stream, decoder stream)} (_overlap_streams)
+        self._open_stream = None   # description of the stream_to_host generator open on this object (require_no_stream)
+        self._last_job = None      # the WindowSampler of the last windowed job: keeps its tensors alive (_windows)
 
     def n_chunks(self, T):
         return int(math.ceil(T / self.cfg.num_frames_for_clip))
@@ -203,9 +215,8 @@ class FloatHotPath:
     def require_no_stream(self, what):
         """One FMT handle carries one job, and the decoder holds one clip's skip features: while a stream_to_host generator is
         open on this object every other producer is refused."""
-        opened = self.__dict__.get("_open_stream")
-        if opened:
-            raise RuntimeError("%s: %s is still open on this FloatHotPath - exhaust it or close() it first" % (what, opened))
+        if self._open_stream:
+            raise RuntimeError("%s: %s is still open on this FloatHotPath - exhaust it or close() it first" % (what, self._open_stream))
 
     def batched_fmt(self, n_clips):
         """An FMT handle whose workspace holds `n_clips` stacked clips (float_fmt_sample_batch), built on first use from the
@@ -214,7 +225,7 @@ class FloatHotPath:
         batches run in chunks of that size.  Per clip the chain costs 79 / 52 / 36 / 28 / 24 ms at 1 / 2 / 4 / 8 / 16 clips."""
         cap = max(1, min(16, int(os.environ.get("FLOAT_AMD_FMT_MAX_BATCH", "16"))))
         mb = min(cap, max(1, int(n_clips)))
-        if mb > self.fmt.max_batch and mb not in self.__dict__.get("_fmt_batched", {}):
+        if mb > self.fmt.max_batch and mb not in self._fmt_batched:
             # 3.1 GB of workspace per stacked clip + the weights once more: size the handle for what the device has free (another
             # model resident in ComfyUI, a smaller GPU) instead of failing with out-of-memory inside the create call
             free, _ = torch.cuda.mem_get_info(self.device)
@@ -225,7 +236,7 @@ class FloatHotPath:
                 mb = max(1, fit)
         if mb <= self.fmt.max_batch:
             return self.fmt
-        cache = self.__dict__.setdefault("_fmt_batched", {})
+        cache = self._fmt_batched
         if mb not in cache:
             for k in list(cache):
                 cache.pop(k).close()
@@ -237,7 +248,7 @@ class FloatHotPath:
         """{operator: float_*_saturation total} of this object's 16-bit handles (synchronises the current stream)."""
         out = {}
         if self.fmt.dtype == "fp16":
-            out["fmt"] = self.fmt.saturation(reset) + sum(f.saturation(reset) for f in self.__dict__.get("_fmt_batched", {}).values())
+            out["fmt"] = self.fmt.saturation(reset) + sum(f.saturation(reset) for f in self._fmt_batched.values())
         if self.dec.dtype == "fp16":
             out["decoder"] = self.dec.saturation(reset)
         return out
@@ -261,7 +272,7 @@ class FloatHotPath:
         import time
         dev, c = self.device, self.cfg
         t_all = time.perf_counter()
-        rd16 = (r_d[0] if r_d.dim() == 3 else r_d).to(dev, torch.float32)
+        rd16 = _rows(r_d).to(dev, torch.float32)
         T = rd16.shape[0]
         n = min(T, c.num_frames_for_clip)
         k = max(1, min(int(k), n, frames_dev.shape[0]))
@@ -315,17 +326,14 @@ class FloatHotPath:
         self.require_no_stream("decode")
         if feats is not None:
             self.dec.set_feats(feats)
-        rd = r_d[0] if r_d.dim() == 3 else r_d
-        if frame_range is not None:
-            rd = rd[frame_range[0]:frame_range[1]]
-        return self.dec.decode_latent_into_processed_images(s_r, rd)
+        return self.dec.decode_latent_into_processed_images(s_r, _rows(r_d, frame_range))
 
     def staging(self, n_frames, dtype=torch.float32, out_format="rgb"):
         """Device-side frame buffer of float_dec_frames_host[_u8|_i420], cached per clip length, dtype and format (786 MB for 250
         fp32 frames at 512 px, 197 MB as uint8, 98 MB as I420; sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
         hands the block of a released earlier result back without a new hipHostMalloc), because ComfyUI keeps node outputs
         alive across executions and a re-used buffer would silently overwrite them."""
-        cache = self.__dict__.setdefault("_staging", {})
+        cache = self._staging
         shape = (n_frames,) + self.dec.frame_shape(out_format)
         if (shape, dtype, out_format) not in cache:
             cache.clear()  # one clip length and format at a time
@@ -344,33 +352,35 @@ class FloatHotPath:
         self.require_no_stream("decode_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
-        rd = r_d[0] if r_d.dim() == 3 else r_d
-        if frame_range is not None:
-            rd = rd[frame_range[0]:frame_range[1]]
+        rd = _rows(r_d, frame_range)
         n = rd.shape[0]
-        # The copy workgroups / hipMemcpyAsync of the PREVIOUS call may still be writing its host tensor, and torch's caching
-        # host allocator knows nothing about writes it did not issue: this object keeps a reference to that tensor until its
-        # event has completed, so the block cannot be handed out again (e.g. as `out` below) while the GPU stores into it.
-        # No host wait here: a batch of clips queues its decodes back to back.  Entries leave the list once their event has
-        # completed (query, not synchronize); the device-side staging buffer is shared, which is safe in stream order.
-        inflight = self.__dict__.setdefault("_host_inflight", [])
-        inflight[:] = [(t, e) for t, e in inflight if not e.query()]
+        self._prune_inflight()
         if out is None:
             out = torch.empty((n,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
         # (the frames by hipMemcpyAsync on a second stream instead of copy workgroups inside the next batch's launches: 121.4-122.1 vs
         # 105.7-106.8 ms per clip on the round-6 kernels, as in round 3 - decoder.decode_into_host(copy_stream=) keeps the form)
         self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype, out_format), out_format=out_format)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        inflight.append((out, ev))
+        self._hold_inflight(out, torch.cuda.current_stream(self.device))
         return out
+
+    def _hold_inflight(self, host, stream):
+        """The copy workgroups / hipMemcpyAsync of a hand-over may still be writing its host tensor when the call returns, and
+        torch's caching host allocator knows nothing about writes it did not issue: this object keeps a reference to that tensor
+        until an event recorded on `stream` behind them has completed, so the block cannot be handed out again (e.g. as the
+        next call's `out`) while the GPU stores into it.  No host wait: a batch of clips queues its decodes back to back; the
+        device-side staging buffer is shared, which is safe in stream order."""
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._host_inflight.append((host, ev))
+
+    def _prune_inflight(self):
+        """Entries leave the list once their event has completed (query, not synchronize)."""
+        self._host_inflight[:] = [(t, e) for t, e in self._host_inflight if not e.query()]
 
     def release_host_inflight(self):
         """Drop the references decode_to_host keeps on host tensors whose copies have completed (call after the stream has been
         synchronised: a batch of 16 clips would otherwise pin 12.6 GB here until the next decode)."""
-        inflight = self.__dict__.get("_host_inflight")
-        if inflight:
-            inflight[:] = [(t, e) for t, e in inflight if not e.query()]
+        self._prune_inflight()
 
     @torch.no_grad()
     def generate_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
@@ -382,9 +392,7 @@ class FloatHotPath:
         self.require_no_stream("generate_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
-        if noise is None:
-            noise = draw_noise(self.n_chunks(wa.shape[1]), 1, self.cfg, seed)
-        r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
+        r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)  # noise=None: drawn there from `seed`
         host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype, out_format)
         return (host, r_d) if return_rd else host
 
@@ -428,13 +436,38 @@ class FloatHotPath:
         return self._stream_blocks(r_s, wa, we, s_r, feats, nfe, (a_cfg_scale, r_cfg_scale, e_cfg_scale), seed, noise,
                                    out_dtype, out_format, int(slots))
 
+    def _windows(self, job, s_fmt, s_dec, frame_range=None):
+        """The window pipeline of every windowed producer.  job = (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
+        goes to a WindowSampler built on the chain stream `s_fmt`; each next() enqueues one window there and, where the decoder
+        stream `s_dec` is another one, an event behind it that `s_dec` waits on, then yields (ws, f0, f1): the caller decodes
+        ws.r_d[0, f0:f1] on `s_dec` into its own destination.  It makes `s_dec` current itself: a `with` held across a yield
+        would restore a stale stream when an abandoned generator is closed.  frame_range=(t0, t1) clips [f0, f1) to the shard;
+        a window outside it is sampled and not yielded.  Keep-alive: the job's tensors are allocated on `s_fmt` and read on
+        `s_dec`, so the object holds the job (_last_job) until the next one replaces it or a producer that has waited drops it."""
+        two = s_dec != s_fmt
+        with torch.cuda.stream(s_fmt):
+            ws = self._last_job = WindowSampler(self.fmt, *job)
+        while ws.left > 0:
+            with torch.cuda.stream(s_fmt):
+                _, (f0, f1) = ws.next()
+                if two:
+                    ev = torch.cuda.Event()
+                    ev.record(s_fmt)
+            if frame_range is not None:
+                f0, f1 = max(f0, frame_range[0]), min(f1, frame_range[1])
+                if f0 >= f1:
+                    continue
+            if two:
+                s_dec.wait_event(ev)
+            yield ws, f0, f1
+
     def _stream_blocks(self, r_s, wa, we, s_r, feats, nfe, scales, seed, noise, out_dtype, out_format, slots):
         self.require_no_stream("stream_to_host")  # another stream may have been started since the call
         dev, L = self.device, self.cfg.num_frames_for_clip
         T = wa.shape[1]
         self._open_stream = "stream_to_host (%d frames, %d slots)" % (T, slots)
         pending = collections.deque()  # (first, last, slot view, event) of the blocks enqueued and not yet yielded
-        ring = staging = ws = None
+        ring = staging = wins = None
         try:
             st = torch.cuda.current_stream(dev)
             with torch.cuda.stream(st):
@@ -446,15 +479,15 @@ class FloatHotPath:
                 ring = [torch.empty((L,) + fshape, dtype=out_dtype, pin_memory=True) for _ in range(slots)]
                 staging = torch.empty((L,) + fshape, device=dev, dtype=out_dtype)
                 s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-                ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, *scales)
-            n_win, enqueued = ws.n_chunks, 0
+            wins = self._windows((r_s, wa, we, noise, nfe) + scales, st, st)  # one stream: no events between the stages
+            n_win, enqueued = self.n_chunks(T), 0
             for j in range(n_win):
                 # block j is about to go to the consumer, who holds nothing now: blocks j .. j + slots - 1 sit in `slots` different
                 # slots, and every earlier block has been given back
                 with torch.cuda.stream(st):
                     while enqueued < min(n_win, j + slots):
-                        k, (f0, f1) = ws.next()
-                        view = ring[k % slots][:f1 - f0]
+                        ws, f0, f1 = next(wins)
+                        view = ring[enqueued % slots][:f1 - f0]
                         self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], view, staging[:f1 - f0], out_format=out_format)
                         ev = torch.cuda.Event()
                         ev.record(st)
@@ -472,13 +505,13 @@ class FloatHotPath:
                     pending[-1][3].synchronize()
             finally:
                 pending.clear()
-                del ring, staging, ws
-                self._open_stream = None
+                del ring, staging, wins
+                self._last_job = self._open_stream = None
 
     def _overlap_streams(self, mode):
-        """(chain stream, decoder stream) of the stage-overlapped form.  mode "prio": two streams of one device queue set, the
+        """(chain stream, decoder stream) of the stage-overlapped forms.  mode "prio": two streams of one device queue set, the
         chain on the higher priority; "cu:N": disjoint CU sets (hipExtStreamCreateWithCUMask), the decoder on the last N CUs."""
-        cache = self.__dict__.setdefault("_ov_streams", {})
+        cache = self._ov_streams
         if mode not in cache:
             dev = self.device
             if mode.startswith("cu:"):
@@ -488,7 +521,7 @@ class FloatHotPath:
                     cache[mode] = (native.cu_range_stream(0, n_cu - n_dec, dev), native.cu_range_stream(n_cu - n_dec, n_cu, dev))
             elif mode in ("prio", "plain", "hi", "lo"):
                 # (least, greatest) priority: the greater priority is the SMALLER number; 0 is the default.  "hi" / "lo" raise the
-                # chain / lower the decoder only (tools/probes/overlap_check.py)
+                # chain / lower the decoder only (tools/probes/overlap_check.py; "hi" is what generate(overlap=True) runs on)
                 lo, hi = torch.cuda.Stream.priority_range()
                 pf = hi if mode in ("prio", "hi") else 0
                 pd = lo if mode in ("prio", "lo") else 0
@@ -499,7 +532,7 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host_overlap(self, r_s, wa, we, s_r, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, noise=None,
-                                 out=None, mode="prio", return_rd=False, out_dtype=None, out_format=None):
+                                 out=None, mode="prio", return_rd=False, out_dtype=None, out_format=None, seed=15):
         """generate_to_host with the two stages pipelined (FLOAT.py runs 209-253 then 113-169; here window k is decoded and
         handed to the host on a second stream while the chain samples window k + 1).  Same kernels on the same operands as
         the sequential order, per-window decode batches (50 frames = 32 + 18 instead of 250 = 7 x 32 + 26): frames bitwise
@@ -511,45 +544,34 @@ class FloatHotPath:
         T = wa.shape[1]
         dev = self.device
         if noise is None:
-            noise = draw_noise(self.n_chunks(T), 1, self.cfg, 15)
+            noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
         s_fmt, s_dec = self._overlap_streams(mode)
         cur = torch.cuda.current_stream(dev)
         s_fmt.wait_stream(cur)
         s_dec.wait_stream(cur)
-        inflight = self.__dict__.setdefault("_host_inflight", [])
-        inflight[:] = [(t, e) for t, e in inflight if not e.query()]
+        self._prune_inflight()
         if out is None:
             out = torch.empty((T,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
         staging = self.staging(T, out_dtype, out_format)
         s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-        with torch.cuda.stream(s_fmt):
-            ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
-        while ws.left > 0:
-            with torch.cuda.stream(s_fmt):
-                _, (f0, f1) = ws.next()
-                ev = torch.cuda.Event()
-                ev.record(s_fmt)
+        for ws, f0, f1 in self._windows((r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_fmt, s_dec):
             with torch.cuda.stream(s_dec):
-                s_dec.wait_event(ev)
                 self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], out[f0:f1], staging[f0:f1], out_format=out_format)
         cur.wait_stream(s_dec)
         cur.wait_stream(s_fmt)
-        done = torch.cuda.Event()
-        done.record(cur)
-        inflight.append((out, done))
-        self._last_job = ws  # the job's tensors were allocated on the side streams: alive until the caller has synchronised
-        return (out, ws.r_d) if return_rd else out
+        self._hold_inflight(out, cur)
+        return (out, self._last_job.r_d) if return_rd else out
 
     @torch.no_grad()
     def generate(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
                  noise=None, overlap=False, frame_range=None, return_rd=False):
         """Whole hot path for one clip (B = 1): frames (T,H,W,3) on the GPU.
 
-        overlap=True pipelines the two stages on two HIP streams: the FMT chain of window k+1 runs while
-        the decoder renders the 50 frames of window k.  Results are identical to the sequential order
-        (same kernels, same operands).  Measured on MI355X it does NOT pay (r01: 183 vs 174 ms per 10 s
-        clip): the decoder's grids own every CU, so each of the chain's ~3000 tiny dependent kernels per
-        window queues behind running decoder workgroups; kept as an option for CU-partitioned streams.
+        overlap=True pipelines the two stages on two HIP streams (_overlap_streams("hi"): the chain on the greatest priority):
+        the FMT chain of window k+1 runs while the decoder renders the 50 frames of window k.  Results are identical to the
+        sequential order (same kernels, same operands).  Measured on MI355X it does NOT pay (r01: 183 vs 174 ms per 10 s
+        clip): the decoder's grids own every CU, so each of the chain's ~3000 tiny dependent kernels per window queues behind
+        running decoder workgroups; generate_to_host_overlap(mode="cu:N") is the form with disjoint CU sets.
         frame_range=(t0,t1) decodes only that shard of the clip (multi-GPU frame sharding)."""
         self.require_no_stream("generate")
         if feats is not None:
@@ -563,42 +585,19 @@ class FloatHotPath:
             return (frames, r_d) if return_rd else frames
         t0, t1 = frame_range if frame_range is not None else (0, T)
         dev = self.device
-        if not hasattr(self, "_s_fmt"):
-            split = getattr(self, "cu_split", None)
-            if split:  # disjoint CU sets: chain on CUs [0, split), decoder on [split, n_cu)
-                n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-                with torch.cuda.device(dev):
-                    self._s_fmt = native.cu_range_stream(0, split, dev)
-                    self._s_dec = native.cu_range_stream(split, n_cu, dev)
-            else:
-                self._s_fmt = torch.cuda.Stream(dev, priority=getattr(self, "fmt_stream_priority", -1))
-                self._s_dec = torch.cuda.Stream(dev, priority=0)
+        s_fmt, s_dec = self._overlap_streams("hi")
         cur = torch.cuda.current_stream(dev)
-        self._s_fmt.wait_stream(cur)
-        self._s_dec.wait_stream(cur)
+        s_fmt.wait_stream(cur)
+        s_dec.wait_stream(cur)
         out = torch.empty(t1 - t0, self.size, self.size, 3, device=dev, dtype=torch.float32)
         s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-        with torch.cuda.stream(self._s_fmt):
-            ws = WindowSampler(self.fmt, r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
-        L = native.lib()
-        while ws.left > 0:
-            with torch.cuda.stream(self._s_fmt):
-                _, (f0, f1) = ws.next()
-                ev = torch.cuda.Event()
-                ev.record(self._s_fmt)
-            a, b = max(f0, t0), min(f1, t1)
-            if a >= b:
-                continue
-            with torch.cuda.stream(self._s_dec):
-                self._s_dec.wait_event(ev)
-                rd = ws.r_d[0, a:b]
-                native.check(L.float_dec_frames(self.dec._h, native.dev_ptr(s_r_d), native.dev_ptr(rd), b - a,
-                                                native.dev_ptr(out[a - t0:b - t0]), native.stream_ptr(dev)))
-        cur.wait_stream(self._s_dec)
-        cur.wait_stream(self._s_fmt)
-        # keep the job's tensors alive until the streams have been joined
-        self._last_job = ws
-        return (out, ws.r_d) if return_rd else out
+        job = (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
+        for ws, a, b in self._windows(job, s_fmt, s_dec, (t0, t1)):
+            with torch.cuda.stream(s_dec):
+                self.dec.decode_latent_into_processed_images(s_r_d, ws.r_d[0, a:b], out=out[a - t0:b - t0])
+        cur.wait_stream(s_dec)
+        cur.wait_stream(s_fmt)
+        return (out, self._last_job.r_d) if return_rd else out
 
 
 def synth_conditions(cfg: FmtConfig, T, seed=0, dynamic_we=False, device="cpu"):

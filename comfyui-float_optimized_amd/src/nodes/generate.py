@@ -53,6 +53,7 @@ class InferenceAgent:
                            dec_dtype=canon(dec_dtype or os.environ.get("FLOAT_AMD_DEC_DTYPE", "fp16")),
                            aud_dtype=canon(aud_dtype or os.environ.get("FLOAT_AMD_AUD_DTYPE", "fp16")))
         self.G = None
+        self._drop_caches()
         self.last_precision_report = None  # check_precision (FLOAT_AMD_VERIFY) keeps its last report here
         self.to_target()
 
@@ -90,18 +91,22 @@ class InferenceAgent:
         if self.G is None:
             return
         torch.cuda.current_stream(self.rank).synchronize()
-        for op in [self.G.fmt, self.G.dec, self.enc, self.audio_encoder, self.emotion_encoder] + list(self.G.__dict__.get("_fmt_batched", {}).values()):
+        for op in [self.G.fmt, self.G.dec, self.enc, self.audio_encoder, self.emotion_encoder] + list(self.G._fmt_batched.values()):
             if op is not None:
                 op.close()
         if self.emotion_encoder is not None:
             self.emotion_predictor = None
         self.G = self.enc = self.audio_encoder = self.emotion_encoder = None
-        self.__dict__.pop("_we_cache", None)
-        self.__dict__.pop("_noise_pin", None)
-        self.__dict__.pop("_noise_pin_b", None)
-        self.__dict__.pop("_feat_slots", None)
+        self._drop_caches()
         with torch.cuda.device(self.rank):
             torch.cuda.empty_cache()
+
+    def _drop_caches(self):
+        """Everything the agent caches between clips besides the operators, empty: what __init__ declares and offload() frees."""
+        self._we_cache = {}        # {emotion index: (1,1,7) one-hot on the device} (_one_hot)
+        self._noise_pin = self._noise_pin_b = self._noise_pin_r = None  # pinned noise of one clip / a batch / a ragged batch (_draw_noise)
+        self._feat_slots = []      # per batch item, the encoder's skip maps copied aside (infer_device_batch)
+        self._side_stream = None   # the speech-emotion model's stream (_cond_stream)
 
     @property
     def resident(self):
@@ -151,69 +156,55 @@ class InferenceAgent:
     # ------------------------------------------------------------------ inference
     def _one_hot(self, emo):
         """(1,1,7) one-hot of a label on the device, made once per label (a fresh one costs a blocking scalar upload per clip)."""
-        cache = self.__dict__.setdefault("_we_cache", {})
+        cache = self._we_cache
         idx = host_models.emotion_index(emo)
         if idx not in cache:
             cache[idx] = host_models.emotion_one_hot(emo, "cpu").to(self.rank)
         return cache[idx]
 
-    def _noise_batch_to_device(self, n_chunks, seeds):
-        """(n_chunks, B, L, W): item i draws its own sequential stream from seeds[i] (what infer_device draws for it alone),
-        written straight into one pinned buffer and sent by ONE non-blocking copy."""
+    def _draw_noise(self, pin, shape, clips, at):
+        """The noise of `clips` = [(seed, n_windows)] as ONE fp32 device tensor of `shape`; at(buf, i, k) is the (1, L, W) view
+        of it that window k of clip i goes to.  Every clip draws what it would draw alone: a generator seeded once per clip and
+        drawn window after window in (1, L, W) pieces - the reference's sequential draws (fmt.draw_noise; FLOAT.py:203-215).
+        Default: the CPU generator's stream (the reference run on the CPU, what the goldens and the oracle use), written
+        straight into the pinned buffer kept under the attribute `pin` and sent by ONE non-blocking copy: the host neither waits
+        for the encoder kernels queued in front of the copy nor leaves the GPU idle behind them.  The buffer is kept until the
+        next draw of that layout (which starts after this clip was synchronised).  FLOAT_AMD_NOISE=device: "the reference on
+        this device", torch.Generator(rank) + randn on the device per window - the stream a user of the reference on ROCm
+        gets.  The two streams differ, the sampler does not."""
         c = self.cfg
-        shape = (n_chunks, len(seeds), c.num_frames_for_clip, c.dim_w)
-        if os.environ.get("FLOAT_AMD_NOISE", "cpu").lower() == "device":  # per item what _noise_to_device draws for it alone
-            return torch.cat([self._noise_to_device(n_chunks, sd) for sd in seeds], dim=1)
-        buf = self.__dict__.get("_noise_pin_b")
-        if buf is None or tuple(buf.shape) != shape:
-            buf = self._noise_pin_b = torch.empty(shape, dtype=torch.float32, pin_memory=True)
-        for i, sd in enumerate(seeds):
-            g = torch.Generator("cpu")
-            g.manual_seed(int(sd))
-            for k in range(n_chunks):
-                torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=buf[k, i:i + 1])
-        return buf.to(self.rank, non_blocking=True)
-
-    def _noise_ragged_to_device(self, n_chunks, seeds):
-        """[(n_chunks[i], L, W)]: item i draws what _noise_to_device draws for it alone (seeds[i], n_chunks[i] sequential draws);
-        the CPU streams are written into one pinned buffer and sent by ONE non-blocking copy."""
-        c = self.cfg
-        if os.environ.get("FLOAT_AMD_NOISE", "cpu").lower() == "device":
-            return [self._noise_to_device(n, sd).reshape(n, c.num_frames_for_clip, c.dim_w) for n, sd in zip(n_chunks, seeds)]
-        shape = (sum(n_chunks), c.num_frames_for_clip, c.dim_w)
-        buf = self.__dict__.get("_noise_pin_r")
-        if buf is None or tuple(buf.shape) != shape:
-            buf = self._noise_pin_r = torch.empty(shape, dtype=torch.float32, pin_memory=True)
-        k = 0
-        for n, sd in zip(n_chunks, seeds):
-            g = torch.Generator("cpu")
-            g.manual_seed(int(sd))
-            for _ in range(n):
-                torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=buf[k:k + 1])
-                k += 1
-        return list(buf.to(self.rank, non_blocking=True).split(list(n_chunks)))
+        on_device = os.environ.get("FLOAT_AMD_NOISE", "cpu").lower() == "device"
+        if on_device:
+            buf = torch.empty(shape, dtype=torch.float32, device=self.rank)
+        else:
+            buf = getattr(self, pin)
+            if buf is None or tuple(buf.shape) != shape:
+                buf = torch.empty(shape, dtype=torch.float32, pin_memory=True)
+                setattr(self, pin, buf)
+        for i, (seed, n) in enumerate(clips):
+            g = torch.Generator(self.rank if on_device else "cpu")
+            g.manual_seed(int(seed))
+            for k in range(n):
+                torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=at(buf, i, k))
+        return buf if on_device else buf.to(self.rank, non_blocking=True)
 
     def _noise_to_device(self, n_chunks, seed):
-        """The reference's sequential CPU draws (fmt.draw_noise; FLOAT.py:203-215) written straight into a pinned buffer and sent
-        by a non-blocking copy: the host neither waits for the encoder kernels queued in front of the copy nor leaves the GPU
-        idle behind them.  The buffer is kept until the next clip (which starts after this one was synchronised)."""
+        """(n_chunks, 1, L, W): the noise of one clip (_draw_noise)."""
         c = self.cfg
-        shape = (n_chunks, 1, c.num_frames_for_clip, c.dim_w)
-        if os.environ.get("FLOAT_AMD_NOISE", "cpu").lower() == "device":
-            # "the reference on this device": torch.Generator(self.opt.rank) + randn(..., device=rank) per window (FLOAT.py:203-215) -
-            # the stream a user of the reference on ROCm gets.  Default: the CPU generator's stream (the reference run on the CPU,
-            # what the goldens and the oracle use); the two streams differ, the sampler does not.
-            g = torch.Generator(self.rank)
-            g.manual_seed(int(seed))
-            return torch.stack([torch.randn(1, c.num_frames_for_clip, c.dim_w, device=self.rank, generator=g) for _ in range(n_chunks)])
-        buf = self.__dict__.get("_noise_pin")
-        if buf is None or tuple(buf.shape) != shape:
-            buf = self._noise_pin = torch.empty(shape, dtype=torch.float32, pin_memory=True)
-        g = torch.Generator("cpu")
-        g.manual_seed(int(seed))
-        for k in range(n_chunks):
-            torch.randn(1, c.num_frames_for_clip, c.dim_w, generator=g, out=buf[k])
-        return buf.to(self.rank, non_blocking=True)
+        return self._draw_noise("_noise_pin", (n_chunks, 1, c.num_frames_for_clip, c.dim_w), [(seed, n_chunks)], lambda buf, i, k: buf[k])
+
+    def _noise_batch_to_device(self, n_chunks, seeds):
+        """(n_chunks, B, L, W): item i draws what _noise_to_device draws for it alone from seeds[i]."""
+        c = self.cfg
+        return self._draw_noise("_noise_pin_b", (n_chunks, len(seeds), c.num_frames_for_clip, c.dim_w), [(sd, n_chunks) for sd in seeds],
+                                lambda buf, i, k: buf[k, i:i + 1])
+
+    def _noise_ragged_to_device(self, n_chunks, seeds):
+        """[(n_chunks[i], L, W)]: item i draws what _noise_to_device draws for it alone (seeds[i], n_chunks[i] sequential draws)."""
+        c, first = self.cfg, [sum(n_chunks[:i]) for i in range(len(n_chunks))]
+        noise = self._draw_noise("_noise_pin_r", (sum(n_chunks), c.num_frames_for_clip, c.dim_w), list(zip(seeds, n_chunks)),
+                                 lambda buf, i, k: buf[first[i] + k:first[i] + k + 1])
+        return list(noise.split(list(n_chunks)))
 
     @torch.no_grad()
     def conditions_device(self, s, a, emo=None):
@@ -253,10 +244,9 @@ class InferenceAgent:
         return dict(s_r=s_r, feats=None, r_s=r_s, wa=wa, we=we, T=T)  # feats: already in the decoder (NHWC 16-bit)
 
     def _cond_stream(self):
-        st = self.__dict__.get("_side_stream")
-        if st is None:
-            st = self._side_stream = torch.cuda.Stream(self.rank)
-        return st
+        if self._side_stream is None:
+            self._side_stream = torch.cuda.Stream(self.rank)
+        return self._side_stream
 
     def host_inputs(self, ref_img, ref_audio, no_crop=True):
         """Host plumbing of the reference's DataProcessor (generate.py:34-81): optional face crop, area resize to the model
@@ -278,6 +268,14 @@ class InferenceAgent:
         return self.conditions_device(s, a, emo)
 
     @torch.no_grad()
+    def _clip_inputs(self, s, a, emo, seed):
+        """(conditions, noise) of one clip: operators resident, encoder kernels enqueued (nothing waits for them on the host)
+        and the clip's noise on its way to the device."""
+        self.to_target()  # no-op while resident
+        c = self.conditions_device(s, a, emo)
+        return c, self._noise_to_device(self.G.n_chunks(c["T"]), seed if seed is not None else self.opt.seed)
+
+    @torch.no_grad()
     def infer_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out=None,
                      out_dtype=None, out_format=None):
         """Portrait and waveform in HBM -> (T,H,W,3) fp32 frames in [0,1] in pinned host memory: every operator of the path and
@@ -290,10 +288,7 @@ class InferenceAgent:
         frames, converted by the decoder's last kernel) - what a video encoder reads, half the bytes of uint8 RGB
         (host_models.write_y4m pipes it).  It implies uint8; with out_dtype=torch.float32 or an fp32 `out` it is a ValueError."""
         resolve_out_format(out, out_dtype, out_format)  # a contradiction is refused before anything runs
-        self.to_target()  # no-op while resident
-        c = self.conditions_device(s, a, emo)  # encoder kernels enqueued; nothing below waits for them on the host
-        n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
-        noise = self._noise_to_device(n_chunks, seed if seed is not None else self.opt.seed)
+        c, noise = self._clip_inputs(s, a, emo, seed)
         ov = os.environ.get("FLOAT_AMD_OVERLAP", "")  # "prio" | "cu:N": decode window k beside the chain of window k + 1 (pipeline.py)
         verify = precision_policy(self._precision_checked) == "check"  # FLOAT_AMD_VERIFY, default off: nothing below changes
         if ov and ov != "0":
@@ -349,11 +344,7 @@ class InferenceAgent:
             self.G.require_no_stream(what)
 
     def _stream_device(self, s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots):
-        self.to_target()  # no-op while resident
-        with torch.no_grad():
-            c = self.conditions_device(s, a, emo)
-            n_chunks = int(math.ceil(c["T"] / self.cfg.num_frames_for_clip))
-            noise = self._noise_to_device(n_chunks, seed if seed is not None else self.opt.seed)
+        c, noise = self._clip_inputs(s, a, emo, seed)
         done = False
         try:
             yield from self.G.stream_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
@@ -361,7 +352,7 @@ class InferenceAgent:
             done = True
         finally:
             # left early: the inner generator has waited for its work; what the abandoned windows counted is not the next clip's
-            if not done and self.G is not None and not self.G.__dict__.get("_open_stream") and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
+            if not done and self.G is not None and not self.G._open_stream and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
                 self.range_counts(reset=True)
         where = "InferenceAgent.stream_device"
         if os.environ.get("FLOAT_AMD_RANGE", "warn").lower() == "auto":
@@ -403,20 +394,26 @@ class InferenceAgent:
             return {}
         bad = report_range(self.range_counts(), where, mode="warn" if mode == "auto" else mode)
         if mode == "auto" and bad and allow_rebuild:
-            b, changed = self._build, False
+            b, changes = self._build, {}
             if ("decoder" in bad or "encoder" in bad) and b["dec_dtype"] != "fp32":
-                b["dec_dtype"], changed = "fp32", True
+                changes["dec_dtype"] = "fp32"
             if "fmt" in bad and b["fmt_dtype"] == "fp16":
-                b["fmt_dtype"], changed = "bf16", True
+                changes["fmt_dtype"] = "bf16"
             if ("audio" in bad or "speech_emotion" in bad) and b["aud_dtype"] == "fp16":
-                b["aud_dtype"], changed = "bf16", True
-            if changed:
-                main_logger.warning("%s: rebuilding the operators as fmt=%s, decoder/encoder=%s, audio=%s and running the clip again",
-                                    where, b["fmt_dtype"], b["dec_dtype"], b["aud_dtype"])
-                self.offload()
-                self.to_target()
-                return "rebuilt"
+                changes["aud_dtype"] = "bf16"
+            return self._rebuild(where, changes, "fmt=%(fmt_dtype)s, decoder/encoder=%(dec_dtype)s, audio=%(aud_dtype)s") or bad
         return bad
+
+    def _rebuild(self, where, changes, types):
+        """Apply `changes` ({key of _build: dtype}) and rebuild the operators in the new types (`types`: how the caller's log
+        line names them).  Returns "rebuilt" - the caller runs the clip again - or None where nothing changes."""
+        if not changes:
+            return None
+        self._build.update(changes)
+        main_logger.warning("%s: rebuilding the operators as %s and running the clip again", where, types % self._build)
+        self.offload()
+        self.to_target()
+        return "rebuilt"
 
     @torch.no_grad()
     def check_precision(self, where, s, c, noise, r_d, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, allow_rebuild=False,
@@ -462,17 +459,9 @@ class InferenceAgent:
             rep["end_to_end"]["non_finite"], rep["ms"], rep["build_ms"], rep["hbm_bytes"] / 2**30)
         fault = report_precision(rep, where)
         if fault and allow_rebuild and os.environ.get("FLOAT_AMD_VERIFY_ACTION", "warn").lower() == "auto":
-            b, changed = self._build, False
-            if fault == "decoder" and b["dec_dtype"] != "fp32":
-                b["dec_dtype"], changed = "fp32", True
-            if fault == "fmt" and b["fmt_dtype"] != "fp32":
-                b["fmt_dtype"], changed = "fp32", True
-            if changed:
-                main_logger.warning("%s: rebuilding the operators as fmt=%s, decoder/encoder=%s and running the clip again",
-                                    where, b["fmt_dtype"], b["dec_dtype"])
-                self.offload()
-                self.to_target()
-                return "rebuilt"
+            key = {"decoder": "dec_dtype", "fmt": "fmt_dtype"}[fault]
+            changes = {key: "fp32"} if self._build[key] != "fp32" else {}
+            return self._rebuild(where, changes, "fmt=%(fmt_dtype)s, decoder/encoder=%(dec_dtype)s") or fault
         return fault
 
     @torch.no_grad()
@@ -492,7 +481,7 @@ class InferenceAgent:
         # once-per-clip producers of every item; the encoder's skip maps of item i are copied aside (33 MB, a D2D copy) so
         # that no item needs a second encoder pass when its turn to decode comes
         conds, feats = [], []
-        slots = self.__dict__.setdefault("_feat_slots", [])
+        slots = self._feat_slots
         for i, (s, a) in enumerate(items):
             conds.append(self.conditions_device(s, a, emo))
             if i >= len(slots):
@@ -503,14 +492,12 @@ class InferenceAgent:
         r_s = torch.cat([c["r_s"].reshape(1, -1) for c in conds])
         if any(c["T"] != T for c in conds):
             # clips of different lengths: one chain whose stack shrinks as clips end (float_fmt_sample_batch_ragged)
-            n_chunks = [int(math.ceil(c["T"] / self.cfg.num_frames_for_clip)) for c in conds]
-            noise = self._noise_ragged_to_device(n_chunks, seeds)
+            noise = self._noise_ragged_to_device([self.G.n_chunks(c["T"]) for c in conds], seeds)
             r_d = self.G.batched_fmt(B).sample_ragged(r_s, [c["wa"].reshape(c["T"], -1) for c in conds],
                                                       [c["we"].reshape(1, -1) for c in conds], noise, self.opt.nfe,
                                                       a_cfg_scale, r_cfg_scale, e_cfg_scale)
         else:
-            n_chunks = int(math.ceil(T / self.cfg.num_frames_for_clip))
-            noise = self._noise_batch_to_device(n_chunks, seeds)
+            noise = self._noise_batch_to_device(self.G.n_chunks(T), seeds)
             wa = torch.cat([c["wa"].reshape(1, T, -1) for c in conds])
             we = torch.cat([c["we"].reshape(1, 1, -1) for c in conds])
             r_d = self.G.batched_fmt(B).sample(r_s, wa, we, noise, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)

@@ -212,3 +212,37 @@ def test_device_noise_stream_is_the_reference_on_this_device(pipe, monkeypatch):
     monkeypatch.delenv("FLOAT_AMD_NOISE")
     cpu_frames, _, _ = node.floatprocess(img, audio, pipe, 2.0, 1.0, 25.0, "happy", False, 7)
     assert dev_frames.shape == cpu_frames.shape and torch.isfinite(dev_frames).all() and not torch.equal(dev_frames, cpu_frames)
+
+
+def test_noise_layouts_agree_and_offload_drops_the_caches(pipe, monkeypatch):
+    """The three noise layouts are one draw: in both FLOAT_AMD_NOISE modes item i of a batch, stacked or ragged, is bit for bit
+    what _noise_to_device draws for it alone, and the default mode is fmt.draw_noise (the reference's CPU stream).  After
+    offload() none of the agent's caches holds a tensor.  Last in the file: the module's agent is left offloaded."""
+    cfg, seeds, counts = pipe.cfg, [11, 12, 13], [3, 1, 2]
+
+    def settled(t):
+        torch.cuda.synchronize()  # the next draw of the same layout re-uses the pinned buffer this copy reads
+        return t
+
+    for mode in ("cpu", "device"):
+        monkeypatch.setenv("FLOAT_AMD_NOISE", mode)
+        batch = settled(pipe._noise_batch_to_device(3, seeds))
+        ragged = settled(pipe._noise_ragged_to_device(counts, seeds))
+        assert batch.shape == (3, 3, 50, 512) and [tuple(t.shape) for t in ragged] == [(n, 50, 512) for n in counts]
+        for i, (n, sd) in enumerate(zip(counts, seeds)):
+            assert torch.equal(batch[:, i:i + 1], settled(pipe._noise_to_device(3, sd))), (mode, i)
+            assert torch.equal(ragged[i], settled(pipe._noise_to_device(n, sd)).reshape(n, 50, 512)), (mode, i)
+        if mode == "cpu":
+            assert torch.equal(settled(pipe._noise_to_device(3, 11)), pkg.fmt.draw_noise(3, 1, cfg, 11).to(pipe.rank))
+
+    def holds_tensor(v):
+        if isinstance(v, dict):
+            v = list(v.values())
+        return torch.is_tensor(v) or (isinstance(v, (list, tuple)) and any(holds_tensor(x) for x in v))
+
+    caches = ("_we_cache", "_noise_pin", "_noise_pin_b", "_noise_pin_r", "_feat_slots", "_side_stream")
+    pipe.to_target()
+    pipe._one_hot("happy")
+    assert all(holds_tensor(getattr(pipe, k)) for k in ("_we_cache", "_noise_pin", "_noise_pin_b", "_noise_pin_r"))
+    pipe.offload()
+    assert not pipe.resident and not any(holds_tensor(getattr(pipe, k)) for k in caches)

@@ -60,6 +60,60 @@ def test_overlapped_hand_over_is_bitwise_sequential(mode, nfe):
         hp.generate_to_host_overlap(*a, 6, noise=noise, mode="both")
 
 
+@pytest.fixture(scope="module")
+def clip130():
+    """One FloatHotPath and one clip of T = 130 (three windows, the last one short) with the frames and latents of
+    generate_to_host as the reference bytes, shared by the tests below and left unchanged."""
+    cfg, _, _, hp, feats = _hot_path()
+    T = 130
+    cond = pkg.pipeline.synth_conditions(cfg, T, seed=3)
+    noise = pkg.fmt.draw_noise(hp.n_chunks(T), 1, cfg, seed=15).to("cuda:0")
+    a = (cond["r_s"], cond["wa"], cond["we"], cond["s_r"])
+    ref, rd = hp.generate_to_host(*a, feats, 6, noise=noise, return_rd=True)
+    torch.cuda.synchronize()
+    return dict(hp=hp, a=a, noise=noise, ref=ref.clone(), rd=rd.clone())
+
+
+def test_producers_share_one_object(clip130):
+    """Every windowed producer on ONE FloatHotPath, one after the other - they share the window pipeline, the stream cache and
+    the job keep-alive: each gives the bytes of generate_to_host, frames and latents, whatever ran before it."""
+    hp, a, noise, ref, rd = (clip130[k] for k in ("hp", "a", "noise", "ref", "rd"))
+
+    def device_overlap():
+        frames, r_d = hp.generate(*a, None, 6, noise=noise, overlap=True, return_rd=True)
+        torch.cuda.synchronize()
+        return frames.cpu(), r_d
+
+    def host_overlap(mode):
+        frames, r_d = hp.generate_to_host_overlap(*a, 6, noise=noise, mode=mode, return_rd=True)
+        torch.cuda.synchronize()
+        return frames, r_d
+
+    def stream():
+        blocks = [(b.first, b.last, b.frames.clone()) for b in hp.stream_to_host(*a, None, 6, noise=noise, slots=2)]
+        assert [b[:2] for b in blocks] == [(0, 50), (50, 100), (100, 130)]
+        return torch.cat([b[2] for b in blocks]), None
+
+    for name, run in [("generate(overlap=True)", device_overlap), ("prio", lambda: host_overlap("prio")), ("stream", stream),
+                      ("cu:64", lambda: host_overlap("cu:64")), ("generate(overlap=True) again", device_overlap)]:
+        frames, r_d = run()
+        assert torch.equal(frames, ref), name
+        assert r_d is None or torch.equal(r_d, rd), name
+
+
+def test_shard_that_skips_whole_windows(clip130):
+    """generate(overlap=True, frame_range=(55, 95)) lies inside window 1: windows 0 and 2 are sampled and decode nothing.  The
+    shard is rows 55 to 95 of the sequential result, and (0, 130) is all of it."""
+    hp, a, noise = (clip130[k] for k in ("hp", "a", "noise"))
+    seq = hp.generate(*a, None, 6, noise=noise, overlap=False)
+    shard = hp.generate(*a, None, 6, noise=noise, overlap=True, frame_range=(55, 95))
+    whole = hp.generate(*a, None, 6, noise=noise, overlap=True, frame_range=(0, 130))
+    torch.cuda.synchronize()
+    assert torch.equal(seq.cpu(), clip130["ref"])
+    assert shard.shape[0] == 40 and torch.equal(shard, seq[55:95])
+    assert torch.equal(whole, seq)
+
+
 def test_end_to_end_vs_oracle_short_clip():
     cfg, fmt_sd, dec_sd, hp, feats = _hot_path()
     T = 30
