@@ -9,6 +9,39 @@ from . import native
 from .config import AudioConfig
 
 
+@torch.no_grad()
+def preprocess_audio_device(waveform, sample_rate, target_rate=16000, device="cuda:0", normalize=True, zeros=24, rolloff=0.945):
+    """host_models.preprocess_audio on the device (`float_aud_front`): a (C,N) or (N,) waveform on any device -> the
+    (1, n_out) fp32 mono waveform at target_rate, zero-mean / unit-variance when `normalize`.  The raw samples cross PCIe
+    (non_blocking) and the channel mean, the band-limited resampler (host_models.resample_sinc_direct is its definition: any
+    pair of rates, nothing snapped) and the statistics run as HIP kernels on the current stream; the output and the scratch
+    come from torch's allocator, nothing synchronises."""
+    device = torch.device(device)
+    w = waveform.detach().to(device, non_blocking=True)
+    if w.dim() == 1:
+        w = w[None]
+    if w.dim() != 2:
+        raise ValueError("preprocess_audio_device: waveform must be (C, N) or (N,), got %s" % (tuple(waveform.shape),))
+    if w.dtype != torch.float32:
+        w = w.float()
+    if w.shape[1] > 1 and w.stride(1) != 1:
+        w = w.contiguous()
+    C_, n_in = int(w.shape[0]), int(w.shape[1])
+    if n_in == 0:
+        raise ValueError("preprocess_audio_device: the waveform is empty")
+    L = native.lib()
+    n_out = int(L.float_aud_front_len(n_in, int(sample_rate), int(target_rate)))
+    need = int(L.float_aud_front_work_bytes(n_in, int(sample_rate), int(target_rate)))
+    with torch.cuda.device(device):
+        a = torch.empty(1, n_out, dtype=torch.float32, device=device)
+        work = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=device)
+        native.check(L.float_aud_front(C.c_void_p(w.data_ptr()), C_, int(w.stride(0)) if C_ > 1 else n_in, n_in, int(sample_rate),
+                                       int(target_rate), int(zeros), float(rolloff), native.AUD_FRONT_NORMALIZE if normalize else 0,
+                                       C.c_void_p(a.data_ptr()), n_out, C.c_void_p(work.data_ptr()), work.numel() * 8,
+                                       native.stream_ptr(device)))
+    return a
+
+
 @native.rebuildable
 class AudioEncoderHIP:
     """state_dict keys: `wav2vec2.*`, `audio_projection.{0,1}.*` (an `audio_encoder.` prefix is stripped) - the

@@ -76,6 +76,36 @@ def resample_sinc(w, orig_rate, new_rate, zeros=24, rolloff=0.945):
     return y[: int(math.ceil(n * up / down))]
 
 
+def resample_sinc_direct(w, orig_rate, new_rate, zeros=24, rolloff=0.945):
+    """The closed form of what `resample_sinc` computes, in fp64 torch ops for ANY pair of rates (no polyphase table, so
+    nothing is snapped): with g = gcd, up = new_rate / g, down = orig_rate / g, c = rolloff * min(1, up / down),
+        y[m] = sum_j w[j] * sinc(t) * cos^2(pi t / (2 zeros)) * c,   t = clamp((j - m * down / up) * c, -zeros, zeros),
+    for m = 0 ... ceil(n * up / down) - 1, w zero outside the clip.  The definition `float_aud_front` (the resampler on the
+    device, audio.preprocess_audio_device) is held to, as rgb8_to_i420 is for the I420 kernels.  Returns fp64; equal rates
+    return the input unchanged, like resample_sinc."""
+    orig_rate, new_rate = int(orig_rate), int(new_rate)
+    if orig_rate == new_rate:
+        return w
+    g = math.gcd(orig_rate, new_rate)
+    up, down = new_rate // g, orig_rate // g
+    c = rolloff * min(1.0, up / down)
+    W = int(math.ceil(zeros / c))                    # taps j = q - W ... q + W + 1 cover every |j - pos| <= zeros / c
+    n = w.shape[-1]
+    n_out = -((-n * up) // down)
+    x = F.pad(w.double(), (W, W + 2))                # x[j + W] = w[j]
+    k = torch.arange(-W, W + 2, dtype=torch.int64)
+    out = torch.empty(n_out, dtype=torch.float64, device=w.device)
+    step = max(1, (1 << 22) // k.numel())
+    for m0 in range(0, n_out, step):
+        num = torch.arange(m0, min(m0 + step, n_out), dtype=torch.int64) * down  # exact integers: pos = q + r / up
+        q, r = num // up, num % up
+        t = ((k[None, :] * up - r[:, None]).double() / up * c).clamp(-zeros, zeros)
+        tpi = t * math.pi
+        ker = torch.where(tpi == 0, torch.ones_like(tpi), torch.sin(tpi) / tpi) * torch.cos(tpi / (2 * zeros)) ** 2 * c
+        out[m0:m0 + step] = (x[(q[:, None] + (k[None, :] + W)).to(x.device)] * ker.to(x.device)).sum(dim=1)
+    return out
+
+
 def preprocess_audio(waveform, sample_rate, target_rate=16000, device=None):
     """ComfyUI AUDIO item (C,N) -> mono 16 kHz, zero-mean / unit-variance like
     Wav2Vec2FeatureExtractor(do_normalize=True) (generate.py:69-73).  A different source rate goes through a band-limited

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libfloat_hip.so")
 
 FLOAT_DT_BF16, FLOAT_DT_FP16, FLOAT_DT_FP32 = 0, 1, 2
+AUD_FRONT_NORMALIZE = 1  # FLOAT_AUD_FRONT_NORMALIZE: the `flags` bit of float_aud_front
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "heun2": 3, "heun3": 4}
 DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP16, "float16": FLOAT_DT_FP16,
@@ -129,6 +130,10 @@ _SIGNATURES = {
     "float_cmp_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
     "float_cmp_work_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "float_aud_front_len": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "float_aud_front_work_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "float_aud_front": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

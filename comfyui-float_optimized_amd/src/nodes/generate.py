@@ -7,7 +7,7 @@ import os
 import torch
 
 from ... import host_models, weights
-from ...audio import Audio2EmotionHIP, AudioEncoderHIP
+from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
 from ...pipeline import FloatHotPath, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
@@ -259,7 +259,15 @@ class InferenceAgent:
         # device: on the host the same ops cost 1-29 ms per clip (torch's 128-thread intra-op pool on sub-megabyte tensors),
         # as much as a quarter of the whole clip.  The reference moves its slices to the device first too (nodes.py:193-201).
         s = host_models.preprocess_image(img[..., :3].to(self.rank, non_blocking=True), o.input_size)
-        a = host_models.preprocess_audio(ref_audio["waveform"][0], ref_audio["sample_rate"], o.sampling_rate, device=self.rank)
+        # Audio at another rate than the model's (a ComfyUI AUDIO item: 44.1 / 48 kHz stereo) takes the same route: the raw planar
+        # samples cross PCIe and the mono mix, the band-limited resampler and the normalisation are HIP kernels
+        # (float_aud_front) instead of a polyphase conv1d on the host.  At the model's rate nothing changes.
+        # FLOAT_AMD_AUDIO_FRONT=0 (read here, per call): the host resampler.
+        wav, rate = ref_audio["waveform"][0], ref_audio["sample_rate"]
+        if int(rate) != o.sampling_rate and os.environ.get("FLOAT_AMD_AUDIO_FRONT", "1") != "0":
+            a = preprocess_audio_device(wav, int(rate), o.sampling_rate, device=self.rank)
+        else:
+            a = host_models.preprocess_audio(wav, rate, o.sampling_rate, device=self.rank)
         return s, a
 
     @torch.no_grad()

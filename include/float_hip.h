@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
+/* Stays 6: float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
+ * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
  * float_dec_frames_host_u8 (8-bit frames), float_dec_frames_i420 / float_dec_frames_host_i420 (planar YUV 4:2:0 frames) and
  * float_fmt_sample_begin_ragged / float_fmt_sample_batch_ragged (clips of different
  * lengths in one chain) are purely additive - no existing signature, structure or behaviour changed, so a
@@ -478,6 +479,37 @@ int float_probe_peaks(float* hbm_read_gbps, float* hbm_copy_gbps, float* mfma16_
 int float_cmp_segments(const float* a, const float* b, int32_t n_seg, int64_t seg_len, float thr, double* stats, void* work,
                        size_t work_bytes, void* stream);
 size_t float_cmp_work_bytes(int32_t n_seg, int64_t seg_len);
+
+/* ---------------------------------------------------------------- audio front end -- */
+/* The raw planar waveform of a node's AUDIO input, already in HBM, -> the mono waveform at rate_out (16 kHz) that
+ * float_aud_inference / float_aud_classify read: channel mean, band-limited resampling, zero-mean / unit-variance
+ * (host_models.preprocess_audio of the host mirror; the reference: librosa soxr_hq + Wav2Vec2FeatureExtractor, generate.py:69-73).
+ * With g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g:
+ *     x[j]  = mean over channels of w[c * ch_stride + j], 0 <= j < n_in; 0 elsewhere
+ *     n_out = ceil(n_in * up / down)                                  = float_aud_front_len(n_in, rate_in, rate_out)
+ *     c     = rolloff * min(1, up / down),   pos_m = m * down / up    (an exact rational)
+ *     t     = clamp((j - pos_m) * c, -zeros, +zeros)
+ *     y[m]  = sum over j of x[j] * sinc(t) * cos^2(pi t / (2 zeros)) * c
+ *   (host_models.resample_sinc_direct is this in fp64).  The filter is evaluated where it is used - no polyphase table - so
+ *   any pair of rates is served exactly.  rate_in == rate_out: no filter, y is the mono mix, bitwise (sum of the channels in
+ *   order, divided by their number).
+ *   flags & FLOAT_AUD_FRONT_NORMALIZE: a = (y - mean(y)) / sqrt(var(y) + 1e-7), biased variance, the statistics in fp64 from
+ *   per-tile partials added in a fixed order (no atomics: bitwise repeatable); a constant y gives zeros.  Otherwise a = y.
+ *   w: channel c starts at w + c * ch_stride (a time slice of a (C, N) tensor needs no copy); 4-byte alignment.
+ *   channels 1..8, zeros 1..32, 0 < rolloff <= 1, both rates 1..2^20, 1 <= n_in <= 2^34, n_out == float_aud_front_len(...)
+ *   <= 2^34; a pair of rates whose 256-output tile of input does not fit the LDS (rate_in / rate_out * 256 + 2 zeros / c + 3
+ *   samples of 4 bytes in 160000 bytes: every ratio from 1/64 to 64 at the default zeros = 24, rolloff = 0.945 fits) is refused.
+ *   work: DEVICE scratch of at least float_aud_front_work_bytes(...) bytes, 8-byte aligned, no zeroing needed.
+ * Enqueues one kernel on `stream`, three when normalising (tile partials, their fold, the normalisation); allocates nothing,
+ * synchronises nothing; kernel launches only, so a caller may capture it (no test captures it; the one host-side call beside
+ * the launches is hipFuncSetAttribute, once the staged tile passes 64 KiB).  An argument outside these rules returns
+ * FLOAT_E_INVALID, with a message naming the function and the argument, before any HIP call.  float_aud_front_len and float_aud_front_work_bytes return 0 for an invalid argument. */
+enum { FLOAT_AUD_FRONT_NORMALIZE = 1 };
+int64_t float_aud_front_len(int64_t n_in, int32_t rate_in, int32_t rate_out);
+size_t float_aud_front_work_bytes(int64_t n_in, int32_t rate_in, int32_t rate_out);
+int float_aud_front(const float* w, int32_t channels, int64_t ch_stride, int64_t n_in, int32_t rate_in, int32_t rate_out,
+                    int32_t zeros, float rolloff, int32_t flags, float* a, int64_t n_out, void* work, size_t work_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }
