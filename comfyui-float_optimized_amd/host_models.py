@@ -7,14 +7,19 @@ this package).  What is left is tensor plumbing:
   * image / audio pre-processing of the simple node (generate.py:29-39, 69-73), the face-aligned crop (utils/image.py:135-180;
     detector optional) and the band-limited resampler in front of wav2vec2
   * the one-hot emotion vector of a named emotion (FLOAT.py:196-200)
+  * the image front end in exact arithmetic (hex_to_rgb8, image_to_rgb8, resize_rgb8): the definition the kernels of
+    `float_img_front` (image.py in this package) are held to bit for bit
   * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
     writer for handing such frames to an encoder
 """
 import fractions
+import logging
 import math
 
 import torch
 import torch.nn.functional as F
+
+logger = logging.getLogger(__name__)
 
 
 def preprocess_image(image_hwc, size=512):
@@ -29,6 +34,146 @@ def preprocess_image(image_hwc, size=512):
         else:
             x = F.interpolate(x, size=(size, size), mode="bilinear", align_corners=False)
     return x / 127.5 - 1.0
+
+
+RGBA_CONVERSIONS = ("discard_alpha", "blend_with_color", "replace_with_color")
+
+
+def hex_to_rgb8(hex_color):
+    """'#RRGGBB' -> (R, G, B) in 0 ... 255 (the reference's hex_to_rgb_uint8, utils/image.py:25-35): a string that is not six
+    hexadecimal digits after the leading '#'s gives (0, 0, 0) and a logged warning."""
+    h = str(hex_color).lstrip("#")
+    if len(h) != 6:
+        logger.warning("Invalid hex color string: %r. Defaulting to black." % (h,))
+        return (0, 0, 0)
+    try:
+        return tuple(int(h[i:i + 2], 16) for i in (0, 2, 4))
+    except ValueError:
+        logger.warning("Invalid characters in hex color string: %r. Defaulting to black." % (h,))
+        return (0, 0, 0)
+
+
+def _quant8(x):
+    """clip(x * 255.0, 0, 255) in fp32, truncated towards zero (img_tensor_2_np_array, utils/image.py:123); NaN gives 0 - the
+    reference leaves that cast undefined, 0 is this project's choice."""
+    t = x.float() * 255.0
+    return torch.where(torch.isnan(t), torch.zeros_like(t), t).clamp(0.0, 255.0).to(torch.uint8)
+
+
+def image_to_rgb8(img, rgba_conversion="blend_with_color", bkg_rgb8=(0, 0, 0)):
+    """(H, W, 3|4) float (a ComfyUI IMAGE item) -> (H, W, 3) uint8: the reference's img_tensor_2_np_array +
+    convert_rgba_to_rgb_numpy (utils/image.py:38-131), bitwise (tests/golden/img_front.npz holds the reference's own outputs).
+    Every channel, alpha included, is quantised first (_quant8).  With 4 channels:
+      discard_alpha       the RGB as it is
+      replace_with_color  the background colour where the quantised alpha is 0
+      blend_with_color    rgb * (a / 255.0) + bkg * (1.0 - a / 255.0) in fp32, every operation rounded on its own (no fused
+                          multiply-add), clipped to 0 ... 255 and truncated
+      anything else       a logged warning, then discard_alpha - as in the reference.
+    Torch on the CPU; this is the definition `float_img_front` is held to, as rgb8_to_i420 is for the I420 kernels."""
+    if img.dim() != 3 or img.shape[-1] not in (3, 4) or not img.is_floating_point():
+        raise ValueError("image_to_rgb8 takes an (H, W, 3) or (H, W, 4) float image, got %s %s" % (img.dtype, tuple(img.shape)))
+    q = _quant8(img.detach().cpu())
+    if q.shape[-1] == 3:
+        return q
+    rgb, a = q[..., :3], q[..., 3]
+    if rgba_conversion == "discard_alpha":
+        return rgb.contiguous()
+    bkg = torch.tensor([int(c) for c in bkg_rgb8], dtype=torch.uint8)
+    if rgba_conversion == "replace_with_color":
+        return torch.where((a == 0)[..., None], bkg, rgb)
+    if rgba_conversion == "blend_with_color":
+        af = (a.float() / 255.0)[..., None]
+        fg = rgb.float() * af
+        bg = bkg.float() * (1.0 - af)
+        return (fg + bg).clamp(0.0, 255.0).to(torch.uint8)
+    logger.warning("Unknown RGBA conversion strategy: %r. Defaulting to 'discard_alpha'." % (rgba_conversion,))
+    return rgb.contiguous()
+
+
+def _axis_scale(n, dst, scale):
+    num, den = (int(scale[0]), int(scale[1])) if scale is not None else (int(n), int(dst))
+    if num < 1 or den < 1:
+        raise ValueError("resize_rgb8: scale %d / %d must be positive" % (num, den))
+    g = math.gcd(num, den)
+    P, Q = num // g, den // g
+    if (dst - 1) * P >= n * Q:
+        raise ValueError("resize_rgb8: destination cell %d starts outside the window (extent %d at scale %d / %d)" % (dst - 1, n, P, Q))
+    return P, Q
+
+
+def _area_axis(x, axis, n, dst, P, Q):
+    """sum over the samples of a cell of v * (integer length of the overlap), per destination cell; also the cell lengths"""
+    x = x.movedim(axis, 0)
+    out = torch.zeros((dst,) + tuple(x.shape[1:]), dtype=torch.int64)
+    lens = torch.zeros(dst, dtype=torch.int64)
+    for d in range(dst):
+        c0, c1 = d * P, min((d + 1) * P, n * Q)
+        lo, hi = c0 // Q, -((-c1) // Q)  # samples lo ... hi - 1 overlap the cell
+        i = torch.arange(lo, hi, dtype=torch.int64)
+        w = torch.minimum((i + 1) * Q, torch.tensor(c1)) - torch.maximum(i * Q, torch.tensor(c0))
+        out[d] = (x[lo:hi] * w.reshape((-1,) + (1,) * (x.dim() - 1))).sum(dim=0)
+        lens[d] = c1 - c0
+    return out.movedim(0, axis), lens
+
+
+def _linear_axis(x, axis, n, dst, P, Q):
+    """v[sx] * (P - f) + v[min(sx + 1, n - 1)] * f per destination index (cv2's INTER_AREA magnification taps, in integers)"""
+    d = torch.arange(dst, dtype=torch.int64)
+    sx = (d * P) // Q
+    num = (d + 1) * P - (sx + 1) * Q
+    f = torch.where(num <= 0, torch.zeros_like(num), num % P)
+    f = torch.where(sx >= n - 1, torch.zeros_like(f), f)
+    sx = sx.clamp(max=n - 1)
+    s1 = (sx + 1).clamp(max=n - 1)
+    x = x.movedim(axis, 0)
+    shape = (-1,) + (1,) * (x.dim() - 1)
+    out = x[sx] * (P - f).reshape(shape) + x[s1] * f.reshape(shape)
+    return out.movedim(0, axis)
+
+
+def resize_rgb8(rgb8, rect=None, dst_h=None, dst_w=None, scale=None):
+    """(H, W, 3) uint8 -> (dst_h, dst_w, 3) uint8: an exact area resize of a window of the image, in 64-bit integers - what
+    cv2.resize(..., INTER_AREA) of the reference computes in fp32 / fixed point (generate.py:35, utils/image.py:144,178).
+      rect = (x0, y0, w, h): the window in source coordinates (default: the whole image).  It may reach outside the image;
+        samples there are 0 in all three channels (cv2.copyMakeBorder(value=0) of process_img).
+      Scale per axis, a rational P / Q reduced by the gcd: w / dst_w and h / dst_h, or scale = (P, Q) on both axes (the
+        fx = fy form of the detector's 360-px copy).  With n the window's extent, source sample i covers [i Q, (i + 1) Q).
+      Area rule (P >= Q on both axes): destination cell d covers [d P, min((d + 1) P, n Q)), a sample's weight is the integer
+        length of the overlap, out = sum(v wx wy) / (cell length x * cell length y), rounded half to even.
+      Linear rule (P < Q on either axis, then on both - cv2's INTER_AREA magnification branch): sx = floor(d P / Q),
+        num = (d + 1) P - (sx + 1) Q, f = 0 if num <= 0 else num mod P; if sx >= n - 1 then sx = n - 1, f = 0; taps (sx, P - f)
+        and (min(sx + 1, n - 1), f); out = sum(v wx wy) / (Px Py), rounded half to even.
+    Every destination cell must start inside the window.  Torch on the CPU; with image_to_rgb8 the definition
+    `float_img_front` is held to bit for bit.  cv2 itself accumulates in fp32 (area) and 11-bit fixed point (linear) and can
+    land one level away near a tie: parity with the package is not pinned."""
+    if rgb8.dtype != torch.uint8 or rgb8.dim() != 3 or rgb8.shape[-1] != 3:
+        raise ValueError("resize_rgb8 takes an (H, W, 3) uint8 image, got %s %s" % (rgb8.dtype, tuple(rgb8.shape)))
+    H, W = int(rgb8.shape[0]), int(rgb8.shape[1])
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(v) for v in rect)
+    dst_h, dst_w = int(dst_h), int(dst_w)
+    if w < 1 or h < 1 or dst_h < 1 or dst_w < 1:
+        raise ValueError("resize_rgb8: window %d x %d and destination %d x %d must be at least 1 x 1" % (h, w, dst_h, dst_w))
+    Px, Qx = _axis_scale(w, dst_w, scale)
+    Py, Qy = _axis_scale(h, dst_h, scale)
+    win = torch.zeros(h, w, 3, dtype=torch.int64)  # the zero-bordered window
+    ya, yb, xa, xb = max(0, y0), min(H, y0 + h), max(0, x0), min(W, x0 + w)
+    if yb > ya and xb > xa:
+        win[ya - y0:yb - y0, xa - x0:xb - x0] = rgb8[ya:yb, xa:xb].cpu().to(torch.int64)
+    if Px < Qx or Py < Qy:
+        S = _linear_axis(_linear_axis(win, 1, w, dst_w, Px, Qx), 0, h, dst_h, Py, Qy)
+        D = torch.full((dst_h, dst_w, 1), Px * Py, dtype=torch.int64)
+    else:
+        rows, lx = _area_axis(win, 1, w, dst_w, Px, Qx)
+        S, ly = _area_axis(rows, 0, h, dst_h, Py, Qy)
+        D = (ly[:, None] * lx[None, :])[..., None]
+    q = S // D
+    r2 = 2 * (S - q * D)
+    return (q + ((r2 > D) | ((r2 == D) & (q % 2 == 1))).to(torch.int64)).to(torch.uint8)
+
+
+def rgb8_to_model_input(q):
+    """(H, W, 3) uint8 -> (1, 3, H, W) fp32 in [-1, 1]: q / 127.5 - 1.0 in fp32 (CustomTransform, generate.py:36-38)."""
+    return (q.float() / 127.5 - 1.0).permute(2, 0, 1)[None].contiguous()
 
 
 def resample_sinc(w, orig_rate, new_rate, zeros=24, rolloff=0.945):
@@ -123,14 +268,21 @@ def preprocess_audio(waveform, sample_rate, target_rate=16000, device=None):
     return ((w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7))[None]
 
 
-def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None):
+def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=None):
     """The reference's face-aligned crop (utils/image.py:135-180) on an (H,W,3) float image in [0,1]: detect faces on a
     360-px-high copy, take box `index`, crop a square of `margin` x the larger half side around its centre from the
     zero-bordered image, resize to input_size.  The detector (`face_alignment`, SFD) is an optional dependency: without it
     - or when it finds no face, exactly like the reference (utils/image.py:151-158) - the centre square is cropped and a
-    warning is logged.  Returns (crop (S,S,3) float in [0,1], bbox (x, y, w, h))."""
+    warning is logged.  Returns (crop (S,S,3) float in [0,1], bbox (x, y, w, h)).
+    front: a callable view_h -> the (view_h, round(W view_h / H), 3) uint8 copy of the image for the detector
+    (image.detector_view_device of the image on the device).  With it, for an image more than 360 px high, that copy is the
+    only thing that reaches the host, nothing is cropped or resized here (only the shape of img_hwc is read), and the function
+    returns (rect, bbox): rect = (x0, y0, w, h), the crop window in source coordinates, which may reach outside the image -
+    what image.preprocess_image_device takes.  Images of 360 px height or less (the reference's INTER_CUBIC route) ignore
+    `front` and take the host route above."""
     H, Wd = int(img_hwc.shape[0]), int(img_hwc.shape[1])
     mult = 360.0 / H
+    use_front = front is not None and mult < 1.0
     bboxes = None
     fa = None
     try:  # ANY failure to obtain a detector (package absent, a stub or broken install, model files unreachable) takes the
@@ -141,8 +293,11 @@ def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None):
                            "of the image is used (install face_alignment for the reference's crop)" % (type(e).__name__, e))
     if fa is not None:
         import numpy as np
-        small = F.interpolate(img_hwc.permute(2, 0, 1)[None], scale_factor=mult, mode="area" if mult < 1.0 else "bicubic")
-        small = (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
+        if use_front:
+            small = front(360).cpu().numpy()
+        else:
+            small = F.interpolate(img_hwc.permute(2, 0, 1)[None], scale_factor=mult, mode="area" if mult < 1.0 else "bicubic")
+            small = (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
         det = fa.face_detector.detect_from_image(np.ascontiguousarray(small))
         bboxes = [(int(x1 / mult), int(y1 / mult), int(x2 / mult), int(y2 / mult), sc) for (x1, y1, x2, y2, sc) in (det or []) if sc > 0.95]
     if not bboxes:
@@ -161,9 +316,12 @@ def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None):
         bsy, bsx = int((b[3] - b[1]) / 2), int((b[2] - b[0]) / 2)
         my, mx = int((b[1] + b[3]) / 2), int((b[0] + b[2]) / 2)
         bs = int(max(bsy, bsx) * margin)
-        img = F.pad(img_hwc.permute(2, 0, 1), (bs, bs, bs, bs)).permute(1, 2, 0)  # cv2.copyMakeBorder(..., value=0)
         bbox_r = (mx - bs, my - bs, 2 * bs, 2 * bs)
+        if not use_front:
+            img = F.pad(img_hwc.permute(2, 0, 1), (bs, bs, bs, bs)).permute(1, 2, 0)  # cv2.copyMakeBorder(..., value=0)
         my, mx = my + bs, mx + bs
+    if use_front:
+        return bbox_r, bbox_r  # the crop is the window bbox_r of the zero-bordered image in both branches
     crop = img[my - bs:my + bs, mx - bs:mx + bs]
     if crop.shape[0] != input_size or crop.shape[1] != input_size:
         c = crop.permute(2, 0, 1)[None].float()

@@ -1,0 +1,102 @@
+"""The image front end on the device (`float_img_front`, include/float_hip.h): the reference's DataProcessor image half -
+img_tensor_2_np_array, process_img's zero-bordered crop, cv2.resize(INTER_AREA), / 127.5 - 1 (utils/image.py, generate.py:29-39) -
+as HIP kernels on the raw ComfyUI IMAGE tensor.  The definition is host_models.image_to_rgb8 + host_models.resize_rgb8; the
+kernels work in integers from the quantiser on and give its bytes."""
+import ctypes as C
+import fractions
+import logging
+import math
+
+import torch
+
+from . import host_models, native
+
+logger = logging.getLogger(__name__)
+
+
+def image_to_device(img, device=None):
+    """A ComfyUI IMAGE item - (H, W, 3|4) or (1, H, W, 3|4), any float dtype, host or device - as the contiguous fp32 device
+    tensor `float_img_front` reads.  The one copy across PCIe (non_blocking); a tensor that is already in that form is returned
+    as it is, so the functions below can be chained without moving anything twice."""
+    if img.dim() == 4:
+        if img.shape[0] != 1:
+            raise ValueError("image front end: a batch of %d images (one image per call)" % img.shape[0])
+        img = img[0]
+    if img.dim() != 3 or img.shape[-1] not in (3, 4) or not img.is_floating_point():
+        raise ValueError("image front end: expected an (H, W, 3) or (H, W, 4) float image, got %s %s" % (img.dtype, tuple(img.shape)))
+    device = torch.device(device if device is not None else (img.device if img.is_cuda else "cuda:0"))
+    x = img.detach().to(device, non_blocking=True)
+    if x.dtype != torch.float32:
+        x = x.float()
+    return x.contiguous()
+
+
+def _rgba_mode(rgba_conversion):
+    mode = native.IMG_RGBA_MODES.get(rgba_conversion)
+    if mode is None:  # utils/image.py:81-83
+        logger.warning("Unknown RGBA conversion strategy: %r. Defaulting to 'discard_alpha'." % (rgba_conversion,))
+        mode = native.IMG_RGBA_MODES["discard_alpha"]
+    return mode
+
+
+@torch.no_grad()
+def image_front_device(img, dst_h, dst_w, rect=None, scale=None, rgba_conversion="blend_with_color", bkg_color_hex="#000000",
+                       out_u8=False, device=None):
+    """float_img_front on one image: the window `rect` = (x0, y0, w, h) of it (default: the whole image; it may reach outside,
+    where the image is black) resized to dst_h x dst_w at w / dst_w by h / dst_h or at the shared `scale` = (P, Q) ->
+    (dst_h, dst_w, 3) uint8 when out_u8, else (1, 3, dst_h, dst_w) fp32 in [-1, 1].  Runs on the current stream of the image's
+    device; output and scratch come from torch's allocator, nothing synchronises."""
+    x = image_to_device(img, device)
+    H, W, ch = (int(v) for v in x.shape)
+    x0, y0, w, h = (0, 0, W, H) if rect is None else (int(v) for v in rect)
+    sn, sd = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+    bkg = host_models.hex_to_rgb8(bkg_color_hex)
+    mode = _rgba_mode(rgba_conversion)
+    L = native.lib()
+    dst_h, dst_w = int(dst_h), int(dst_w)
+    need = int(L.float_img_front_work_bytes(H, W, dst_h, dst_w))
+    with torch.cuda.device(x.device):
+        if out_u8:
+            out = torch.empty(dst_h, dst_w, 3, dtype=torch.uint8, device=x.device)
+        else:
+            out = torch.empty(1, 3, dst_h, dst_w, dtype=torch.float32, device=x.device)
+        work = torch.empty(max(1, need // 4), dtype=torch.int32, device=x.device)
+        native.check(L.float_img_front(C.c_void_p(x.data_ptr()), H, W, ch, x0, y0, w, h, sn, sd, mode, bkg[0], bkg[1], bkg[2],
+                                       native.IMG_OUT_HWC_U8 if out_u8 else native.IMG_OUT_NCHW_PM1, C.c_void_p(out.data_ptr()),
+                                       dst_h, dst_w, C.c_void_p(work.data_ptr()), work.numel() * 4, native.stream_ptr(x.device)))
+    return out
+
+
+def preprocess_image_device(img, size, rect=None, rgba_conversion="blend_with_color", bkg_color_hex="#000000", device=None):
+    """The model's source image from a ComfyUI IMAGE item: RGBA conversion, the optional crop `rect` (x0, y0, w, h - what
+    host_models.process_img(..., front=...) returns), area resize to size x size, 8-bit rounding, / 127.5 - 1 -> (1, 3, size,
+    size) fp32 on the device.  Bitwise host_models.rgb8_to_model_input(resize_rgb8(image_to_rgb8(img, ...), rect, size, size))."""
+    return image_front_device(img, size, size, rect, None, rgba_conversion, bkg_color_hex, False, device)
+
+
+def detector_view_size(H, W, view_h=360):
+    """(rows, columns) of cv2.resize(img, (0, 0), fx=view_h / H, fy=view_h / H): both rounded half to even."""
+    return int(view_h), max(1, round(fractions.Fraction(int(W) * int(view_h), int(H))))
+
+
+def front_takes(H, W, size, crop=False, view_h=360):
+    """Whether `float_img_front` takes an H x W source for a size x size model input - and, with `crop`, for the detector's
+    view_h-row copy too.  Its limits (source sides 1 ... 16384, destination sides 1 ... 4096: float_hip.h) are asked of the
+    library (`float_img_front_work_bytes` is 0 outside them), not repeated here.  A 4K or 8K portrait is far inside; a side
+    above 16384 or, with `crop`, a panorama beyond about 11 : 1 is not, and InferenceAgent.host_inputs keeps the host route
+    for those."""
+    L = native.lib()
+    if not L.float_img_front_work_bytes(int(H), int(W), int(size), int(size)):
+        return False
+    return not crop or bool(L.float_img_front_work_bytes(int(H), int(W), *detector_view_size(H, W, view_h)))
+
+
+def detector_view_device(img, view_h=360, rgba_conversion="blend_with_color", bkg_color_hex="#000000", device=None):
+    """The copy of the image the face detector looks at (utils/image.py:142-146): view_h rows, round(W view_h / H) columns, both
+    axes at the one scale H / view_h -> (view_h, columns, 3) uint8 on the device.  Bitwise
+    resize_rgb8(image_to_rgb8(img, ...), None, view_h, columns, scale=(H, view_h))."""
+    x = image_to_device(img, device)
+    H, W = int(x.shape[0]), int(x.shape[1])
+    vh, vw = detector_view_size(H, W, view_h)
+    g = math.gcd(H, vh)
+    return image_front_device(x, vh, vw, None, (H // g, vh // g), rgba_conversion, bkg_color_hex, True, device)

@@ -10,6 +10,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfloat_hip.so")
 
 FLOAT_DT_BF16, FLOAT_DT_FP16, FLOAT_DT_FP32 = 0, 1, 2
 AUD_FRONT_NORMALIZE = 1  # FLOAT_AUD_FRONT_NORMALIZE: the `flags` bit of float_aud_front
+IMG_RGBA_MODES = {"discard_alpha": 0, "blend_with_color": 1, "replace_with_color": 2}  # FLOAT_IMG_RGBA_*: float_img_front's `rgba_mode`
+IMG_OUT_NCHW_PM1, IMG_OUT_HWC_U8 = 0, 1  # FLOAT_IMG_OUT_*: float_img_front's `out_mode`
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "heun2": 3, "heun3": 4}
 DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP16, "float16": FLOAT_DT_FP16,
@@ -134,6 +136,8 @@ _SIGNATURES = {
     "float_aud_front_work_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "float_aud_front": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "float_img_front_work_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "float_img_front": (C.c_int, [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

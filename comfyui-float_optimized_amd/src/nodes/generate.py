@@ -10,6 +10,7 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
+from ...image import detector_view_device, front_takes, image_to_device, preprocess_image_device
 from ...pipeline import FloatHotPath, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
 
@@ -253,12 +254,43 @@ class InferenceAgent:
         size, [-1,1]; mono, resample to 16 kHz, normalise.  Returns (s (1,3,H,W), a (N,)) on the device."""
         o = self.opt
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
+        # The image front end on the device (float_img_front): the raw IMAGE tensor crosses PCIe once, and RGBA conversion
+        # (opt.rgba_conversion, opt.bkg_color_hex), the zero-bordered crop, the exact area resize, the 8-bit rounding and the
+        # normalisation are HIP kernels; with face_align only the detector's 360-px copy comes back to the host.  Taken when
+        # there is something to convert, crop or resize; a 3-channel image at the model's size without a crop takes the
+        # lines below, as do images of 360 px height or less with face_align (the reference's INTER_CUBIC route) and images
+        # outside the kernels' size limits (a side above 16384; with face_align a detector copy wider than 4096 columns).
+        # FLOAT_AMD_IMAGE_FRONT=0 (read here, per call): the host route for everything, alpha discarded.
+        front_on = os.environ.get("FLOAT_AMD_IMAGE_FRONT", "1") != "0"
+        H, Wd, ch = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+        cubic = not no_crop and H <= 360
+        rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+        if (front_on and not cubic and (ch == 4 or H != o.input_size or Wd != o.input_size or not no_crop)
+                and front_takes(H, Wd, o.input_size, crop=not no_crop)):
+            dimg = image_to_device(img, self.rank)
+            rect = None
+            if not no_crop:  # generate.py:77-78
+                rect, _ = host_models.process_img(dimg, o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger,
+                                                  front=lambda view_h: detector_view_device(dimg, view_h, rgba, bkg))
+            if ch == 3 and (H, Wd) == (o.input_size, o.input_size) and rect is not None and tuple(rect) == (0, 0, Wd, H):
+                # the crop turned out to be the whole image (a square portrait without a detected face): nothing to convert,
+                # crop or resize after all, so this is the case of the lines below, bitwise
+                s = host_models.preprocess_image(dimg, o.input_size)
+            else:
+                s = preprocess_image_device(dimg, o.input_size, rect, rgba, bkg)
+            return s, self._host_audio(ref_audio)
+        if front_on and ch == 4:  # the cubic route, an image beyond the size limits: the widgets are honoured there too
+            img = host_models.image_to_rgb8(img, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0
         if not no_crop:  # generate.py:77-78
             img, _ = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger)
         # The raw tensors cross PCIe first (3 MB + 0.6 MB for a 10-s clip) and the elementwise / reduction plumbing runs on the
         # device: on the host the same ops cost 1-29 ms per clip (torch's 128-thread intra-op pool on sub-megabyte tensors),
         # as much as a quarter of the whole clip.  The reference moves its slices to the device first too (nodes.py:193-201).
         s = host_models.preprocess_image(img[..., :3].to(self.rank, non_blocking=True), o.input_size)
+        return s, self._host_audio(ref_audio)
+
+    def _host_audio(self, ref_audio):
+        o = self.opt
         # Audio at another rate than the model's (a ComfyUI AUDIO item: 44.1 / 48 kHz stereo) takes the same route: the raw planar
         # samples cross PCIe and the mono mix, the band-limited resampler and the normalisation are HIP kernels
         # (float_aud_front) instead of a polyphase conv1d on the host.  At the model's rate nothing changes.
@@ -268,7 +300,7 @@ class InferenceAgent:
             a = preprocess_audio_device(wav, int(rate), o.sampling_rate, device=self.rank)
         else:
             a = host_models.preprocess_audio(wav, rate, o.sampling_rate, device=self.rank)
-        return s, a
+        return a
 
     @torch.no_grad()
     def conditions(self, ref_img, ref_audio, emo=None, no_crop=True):

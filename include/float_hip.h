@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
+/* Stays 6: float_img_front / float_img_front_work_bytes (the image front end on the device),
+ * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
  * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
  * float_dec_frames_host_u8 (8-bit frames), float_dec_frames_i420 / float_dec_frames_host_i420 (planar YUV 4:2:0 frames) and
  * float_fmt_sample_begin_ragged / float_fmt_sample_batch_ragged (clips of different
@@ -510,6 +511,46 @@ size_t float_aud_front_work_bytes(int64_t n_in, int32_t rate_in, int32_t rate_ou
 int float_aud_front(const float* w, int32_t channels, int64_t ch_stride, int64_t n_in, int32_t rate_in, int32_t rate_out,
                     int32_t zeros, float rolloff, int32_t flags, float* a, int64_t n_out, void* work, size_t work_bytes,
                     void* stream);
+
+/* ---------------------------------------------------------------- image front end -- */
+/* The raw (src_h, src_w, channels) fp32 tensor of a node's IMAGE input, already in HBM, -> the model's input: RGBA conversion,
+ * a window that may reach outside the image (zero border), area resize, 8-bit rounding, normalisation (the reference:
+ * img_tensor_2_np_array -> process_img's crop -> cv2.resize(INTER_AREA) -> / 127.5 - 1, utils/image.py, generate.py:29-39).
+ * Everything after the quantiser is integer arithmetic, so the result is bitwise the definition in the host mirror
+ * (host_models.image_to_rgb8 + host_models.resize_rgb8).
+ *   Quantiser, every channel, alpha included: q = trunc(clip(x * 255.0f, 0, 255)) in fp32; NaN gives 0.
+ *   channels == 4, rgba_mode:
+ *     FLOAT_IMG_RGBA_DISCARD  the RGB as it is
+ *     FLOAT_IMG_RGBA_BLEND    trunc(clip(c * (a / 255.0f) + bkg * (1.0f - a / 255.0f), 0, 255)), every operation rounded to fp32 on its
+ *                             own (no fused multiply-add)
+ *     FLOAT_IMG_RGBA_REPLACE  the background colour where a == 0
+ *   Window: samples rect_x ... rect_x + rect_w - 1 by rect_y ... rect_y + rect_h - 1 in source coordinates; a sample outside the
+ *   image is 0 in all three channels.
+ *   Scale per axis, a rational P / Q reduced by the gcd: scale_num / scale_den on both axes, or, with 0, 0, rect_w / dst_w and
+ *   rect_h / dst_h.  With n the window's extent on the axis, source sample i covers [i Q, (i + 1) Q):
+ *     area rule (P >= Q on both axes): destination cell d covers [d P, min((d + 1) P, n Q)); a sample's weight is the integer
+ *       length of the overlap; out = sum(v wx wy) / (cell length x * cell length y)
+ *     linear rule (P < Q on either axis, then on both): sx = floor(d P / Q), num = (d + 1) P - (sx + 1) Q, f = 0 if num <= 0 else
+ *       num mod P; if sx >= n - 1 then sx = n - 1, f = 0; taps (sx, P - f) and (min(sx + 1, n - 1), f); out = sum(v wx wy) / (Px Py)
+ *     both rounded half to even by one integer division; 32-bit row sums (at most 255 P), 64-bit totals.
+ *   out_mode: FLOAT_IMG_OUT_NCHW_PM1  (3, dst_h, dst_w) fp32, q / 127.5f - 1.0f (division, then subtraction)
+ *             FLOAT_IMG_OUT_HWC_U8    (dst_h, dst_w, 3) uint8, q
+ *   Source sides 1..16384, destination sides 1..4096, window extents and both terms of a reduced scale 1..32768, |rect_x|, |rect_y|
+ *   <= 65536; every destination cell must start inside the window ((dst - 1) P < n Q); background channels 0..255.  img and out
+ *   are contiguous; img is 16-byte aligned for 4 channels and 4-byte aligned for 3, an fp32 out 4-byte aligned.
+ *   work: DEVICE scratch of at least float_img_front_work_bytes(src_h, src_w, dst_h, dst_w) = src_h * dst_w * 12 bytes, 4-byte
+ *   aligned, no zeroing needed: (source row, dst_w, 3) int32 row sums.
+ * Enqueues two kernels on `stream` (one when the window misses the image): the first reads every source pixel of the window once
+ * and writes the row sums, the second forms the outputs; no atomics, two calls give equal bytes.  Allocates nothing,
+ * synchronises nothing; kernel launches only, so a caller may capture it (no test captures it).  An argument outside these rules
+ * returns FLOAT_E_INVALID, with a message naming the function and the argument, before any HIP call; float_img_front_work_bytes
+ * returns 0 for a side out of range. */
+enum { FLOAT_IMG_RGBA_DISCARD = 0, FLOAT_IMG_RGBA_BLEND = 1, FLOAT_IMG_RGBA_REPLACE = 2 };
+enum { FLOAT_IMG_OUT_NCHW_PM1 = 0, FLOAT_IMG_OUT_HWC_U8 = 1 };
+size_t float_img_front_work_bytes(int32_t src_h, int32_t src_w, int32_t dst_h, int32_t dst_w);
+int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t channels, int32_t rect_x, int32_t rect_y, int32_t rect_w,
+                    int32_t rect_h, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g, int32_t bkg_b,
+                    int32_t out_mode, void* out, int32_t dst_h, int32_t dst_w, void* work, size_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }
