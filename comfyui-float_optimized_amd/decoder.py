@@ -128,6 +128,14 @@ class SynthesisHIP:
         return self._run(lambda h, s, r, T, out, st: L.float_dec_frames_i420(h, s, r, T, native.MATRIX_BT601_LIMITED, out, st),
                          s_r, r_d, (3 * self.size // 2, self.size), torch.uint8)
 
+    @torch.no_grad()
+    def decode_jpeg(self, s_r, r_d, quality=90, restart=None, s_r_feats=None, out=None):
+        """decode_u8, then float_jpg_encode on the 8-bit frames: (data, offsets) on the GPU as jpeg.encode_jpeg_device returns
+        them - frame i is data[offsets[i]:offsets[i + 1]], a complete baseline JPEG file, bitwise
+        host_models.jpeg_encode_rgb8(decode_u8(...), quality, restart)[i].  Reads offsets[-1] on the host (one synchronisation)."""
+        from .jpeg import encode_jpeg_device
+        return encode_jpeg_device(self.decode_u8(s_r, r_d, s_r_feats), quality, restart, out)
+
     def frame_shape(self, out_format="rgb"):
         """Shape of one frame as the hand-over calls store it: (size, size, 3), or (3 * size / 2, size) for "i420"."""
         return (3 * self.size // 2, self.size) if out_format == "i420" else (self.size, self.size, 3)

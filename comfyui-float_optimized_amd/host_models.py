@@ -11,6 +11,8 @@ this package).  What is left is tensor plumbing:
     `float_img_front` (image.py in this package) are held to bit for bit
   * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
     writer for handing such frames to an encoder
+  * baseline JPEG in integer arithmetic (jpeg_tables, jpeg_header, jpeg_encode_rgb8: the definition the kernels of
+    `float_jpg_encode` are held to bit for bit; numpy, no imaging library) and a Motion-JPEG AVI writer (AviMjpegWriter)
 """
 import fractions
 import logging
@@ -466,3 +468,365 @@ def write_y4m(path_or_file, frames_i420, fps):
     T, H32, W = frames_i420.shape
     with Y4MWriter(path_or_file, W, H32 * 2 // 3, fps) as w:
         w.write(frames_i420)
+
+
+# ---------------------------------------------------------------- baseline JPEG in integers (the definition of float_jpg_encode)
+# ITU-T T.81 Annex K.1 / K.2 (quantiser tables, row-major) and K.3 (the four Huffman tables as BITS + HUFFVAL)
+_JPEG_Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
+                103, 99)
+_JPEG_Q_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + \
+    (99,) * 32
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
+               57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_JPEG_AC_LUMA_VALS = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748494a"
+    "535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7"
+    "c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_JPEG_AC_CHROMA_VALS = bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a43444546474849"
+    "4a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5"
+    "c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+# (class << 4 | id, BITS[1..16], HUFFVAL) in the order the header writes them: DC0, AC0, DC1, AC1
+JPEG_HUFFMAN = ((0x00, (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),
+                (0x10, (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D), _JPEG_AC_LUMA_VALS),
+                (0x01, (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),
+                (0x11, (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), _JPEG_AC_CHROMA_VALS))
+
+
+def jpeg_tables(quality):
+    """(luma, chroma) quantiser tables of a quality in 1 ... 100 as (64,) int32 arrays in row-major order: Annex K.1 / K.2 of
+    ITU-T T.81 under the common scaling s = 5000 // q below 50, else 200 - 2 q; v = clamp((base s + 50) // 100, 1, 255)."""
+    import numpy as np
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError("JPEG quality must be an integer in 1 ... 100 (got %r)" % (quality,))
+    q = int(quality)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.array(base, dtype=np.int64) * s + 50) // 100, 1, 255).astype(np.int32) for base in (_JPEG_Q_LUMA, _JPEG_Q_CHROMA))
+
+
+def jpeg_huffman_codes(bits, vals):
+    """{symbol: (code, length)} of a BITS / HUFFVAL pair (T.81 Annex C: codes of one length count up, and double to the next)."""
+    codes, code, k = {}, 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            codes[vals[k]] = (code, length)
+            code, k = code + 1, k + 1
+        code <<= 1
+    return codes
+
+
+def _jpeg_geometry(h, w, restart):
+    h, w = int(h), int(w)
+    if h < 16 or w < 16 or h % 16 or w % 16 or h > 65520 or w > 65520:
+        raise ValueError("JPEG 4:2:0 frames have sides that are multiples of 16 (got %d x %d)" % (h, w))
+    restart = w // 16 if restart is None else int(restart)
+    if not 0 <= restart <= 65535:
+        raise ValueError("JPEG restart interval must be 0 ... 65535 MCUs (got %r)" % (restart,))
+    return h, w, restart
+
+
+def jpeg_header(h, w, quality, restart):
+    """Everything of the file in front of the scan data: SOI, APP0 (JFIF 1.1, density 1:1), DQT 0 and 1 (8-bit, zigzag order),
+    SOF0 (8 bits, h x w, Y 2x2 with table 0, Cb and Cr 1x1 with table 1), DHT DC0, AC0, DC1, AC1 (Annex K.3), DRI when
+    restart > 0, SOS (one interleaved scan, Ss 0, Se 63).  restart: MCUs per interval, 0 none, None one MCU row."""
+    import struct
+    h, w, restart = _jpeg_geometry(h, w, restart)
+    out = [b"\xff\xd8", b"\xff\xe0", struct.pack(">H5sBBBHHBB", 16, b"JFIF\0", 1, 1, 0, 1, 1, 0, 0)]
+    for i, t in enumerate(jpeg_tables(quality)):
+        out += [b"\xff\xdb", struct.pack(">HB", 67, i), bytes(int(t[z]) for z in JPEG_ZIGZAG)]
+    out += [b"\xff\xc0", struct.pack(">HBHHB", 17, 8, h, w, 3), bytes((1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1))]
+    for tc_th, bits, vals in JPEG_HUFFMAN:
+        out += [b"\xff\xc4", struct.pack(">HB", 19 + len(vals), tc_th), bytes(bits), vals]
+    if restart > 0:
+        out += [b"\xff\xdd", struct.pack(">HH", 4, restart)]
+    out += [b"\xff\xda", struct.pack(">HB", 12, 3), bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0))]
+    return b"".join(out)
+
+
+def jpeg_dct_matrix():
+    """M = rint(2^14 A), A the orthonormal 8-point DCT-II matrix, as (8, 8) int64."""
+    import numpy as np
+    k, n = np.arange(8)[:, None], np.arange(8)[None, :]
+    A = 0.5 * np.cos((2 * n + 1) * k * np.pi / 16)
+    A[0, :] = math.sqrt(1.0 / 8.0)
+    return np.rint(A * 2.0**14).astype(np.int64)
+
+
+def jpeg_quantised_blocks(frames_u8, quality):
+    """The quantised DCT coefficients jpeg_encode_rgb8 codes: (T, MCUs, 6, 64) int32 in zigzag order, MCUs in raster order, per
+    MCU the four Y blocks (raster), then Cb, then Cr.  frames_u8: (T, H, W, 3) uint8 as a numpy array."""
+    import numpy as np
+    x = frames_u8.astype(np.int64)
+    T, H, W, _ = x.shape
+    r, g, b = x[..., 0], x[..., 1], x[..., 2]
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16
+    sub = lambda c: (c.reshape(T, H // 2, 2, W // 2, 2).sum(axis=(2, 4)) + 2) >> 2
+    my, mx = H // 16, W // 16
+    yb = (y - 128).reshape(T, my, 2, 8, mx, 2, 8).transpose(0, 1, 4, 2, 5, 3, 6).reshape(T, my * mx, 4, 8, 8)
+    cbb, crb = ((sub(c) - 128).reshape(T, my, 8, mx, 8).transpose(0, 1, 3, 2, 4).reshape(T, my * mx, 1, 8, 8) for c in (cb, cr))
+    X = np.concatenate([yb, cbb, crb], axis=2)
+    M = jpeg_dct_matrix()
+    p1 = M @ X
+    assert np.abs(p1).max() < 2**24
+    t = (p1 + 2**10) >> 11
+    p2 = t @ M.T
+    assert np.abs(p2).max() < 2**28
+    f8 = (p2 + 2**13) >> 14  # the coefficient x 8
+    ql, qc = jpeg_tables(quality)
+    q = np.stack([ql] * 4 + [qc] * 2).astype(np.int64).reshape(6, 8, 8)
+    c = np.sign(f8) * ((np.abs(f8) + 4 * q) // (8 * q))
+    return c.reshape(T, my * mx, 6, 64)[..., list(JPEG_ZIGZAG)].astype(np.int32)
+
+
+def jpeg_encode_rgb8(frames_u8, quality=90, restart=None, stats=False):
+    """(T, H, W, 3) or (H, W, 3) uint8 RGB (a torch tensor on any device, or a numpy array) -> a list of `bytes`, one complete
+    baseline JFIF file per frame (4:2:0, one interleaved scan, the standard Huffman tables).  H and W are multiples of 16.  This
+    is the definition of what float_jpg_encode writes: all of it is integer arithmetic, `>>` an arithmetic shift.
+      colour   full-range BT.601 per pixel: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+               Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16;
+               chroma subsampled 2 x 2 by (c00 + c01 + c10 + c11 + 2) >> 2 on the converted planes; level shift -128
+      DCT      M = rint(2^14 A): t = (M X + 2^10) >> 11, F8 = (t M^T + 2^13) >> 14 (the coefficient x 8; |M X| < 2^24, |t M^T| < 2^28)
+      quant    c = sign(F8) ((|F8| + 4 q) // (8 q)), q from jpeg_tables(quality)
+      entropy  MCU = 4 Y blocks, Cb, Cr; DC differences per component; ZRL for runs above 15; EOB unless coefficient 63 is
+               non-zero; `restart` MCUs per interval (0: none, None: one MCU row): before MCU m > 0 with m % restart == 0 the bit
+               buffer is padded with 1-bits to a byte, RSTk follows (k cycling 0 ... 7) and the three predictors return to 0;
+               every 0xFF data byte is followed by 0x00; the last byte of the scan is padded with 1-bits
+    stats=True: also returns a dict of what the streams exercised: stuffed_bytes, zrl, blocks_without_eob, max_dc_category,
+    max_ac_category, restart_markers (sums / maxima over the frames)."""
+    import numpy as np
+    x = frames_u8
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.uint8:
+            raise ValueError("jpeg_encode_rgb8 takes uint8 frames, got %s" % (x.dtype,))
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
+        raise ValueError("jpeg_encode_rgb8 takes (T, H, W, 3) or (H, W, 3) uint8 frames, got %s %s" % (x.dtype, tuple(x.shape)))
+    if x.ndim == 3:
+        x = x[None]
+    T, H, W, _ = x.shape
+    H, W, ri = _jpeg_geometry(H, W, restart)
+    header = jpeg_header(H, W, quality, ri)
+    zz = jpeg_quantised_blocks(x, quality).astype(np.int64)
+    nmcu = zz.shape[1]
+    nblk = nmcu * 6
+    span = ri if ri > 0 else nmcu
+    n_int = -(-nmcu // span)
+    comp = np.tile(np.array([0, 0, 0, 0, 1, 2]), nmcu)
+    interval = np.repeat(np.arange(nmcu) // span, 6)
+    cat_of = np.zeros(4096, dtype=np.int64)
+    for k in range(1, 13):
+        cat_of[1 << (k - 1):1 << k] = k
+    code_tabs = [jpeg_huffman_codes(bits, vals) for _, bits, vals in JPEG_HUFFMAN]
+    lut = np.zeros((4, 256, 2), dtype=np.int64)  # [DC0, AC0, DC1, AC1][symbol] = (code, length)
+    for i, tab in enumerate(code_tabs):
+        for sym, cl in tab.items():
+            lut[i, sym] = cl
+    tsel = (comp > 0).astype(np.int64) * 2  # index of the block's DC table; + 1 its AC table
+    pos = np.arange(1, 64)
+    st = dict(stuffed_bytes=0, zrl=0, blocks_without_eob=0, max_dc_category=0, max_ac_category=0, restart_markers=0)
+    files = []
+    for f in range(T):
+        z = zz[f].reshape(nblk, 64)
+        val = np.zeros((nblk, 129), dtype=np.uint64)  # slots: DC | (ZRLs, code + amplitude) per AC position | EOB | interval padding
+        length = np.zeros((nblk, 129), dtype=np.int64)
+        diff = np.zeros(nblk, dtype=np.int64)
+        for c in range(3):
+            idx = np.nonzero(comp == c)[0]
+            dc = z[idx, 0]
+            prev = np.concatenate([[0], dc[:-1]])
+            prev[np.concatenate([[True], interval[idx][1:] != interval[idx][:-1]])] = 0
+            diff[idx] = dc - prev
+        cat = cat_of[np.abs(diff)]
+        amp = np.where(diff < 0, diff + (1 << cat) - 1, diff)
+        val[:, 0] = ((lut[tsel, cat, 0] << cat) | amp).astype(np.uint64)
+        length[:, 0] = lut[tsel, cat, 1] + cat
+        st["max_dc_category"] = max(st["max_dc_category"], int(cat.max()))
+        ac = z[:, 1:]
+        nz = ac != 0
+        last = np.maximum.accumulate(np.where(nz, pos[None, :], 0), axis=1)
+        run = pos[None, :] - np.concatenate([np.zeros((nblk, 1), dtype=np.int64), last[:, :-1]], axis=1) - 1
+        acat = cat_of[np.abs(ac)]
+        assert int(acat.max()) <= 10
+        aamp = np.where(ac < 0, ac + (1 << acat) - 1, ac)
+        sym = ((run & 15) << 4) | acat
+        tac = (tsel + 1)[:, None]
+        n_zrl = np.where(nz, run >> 4, 0)
+        zc, zl = lut[tac, 0xF0, 0], lut[tac, 0xF0, 1]
+        zv = np.zeros_like(run)
+        for _ in range(3):
+            zv = np.where(n_zrl > _, (zv << zl) | zc, zv)
+        val[:, 1:127:2] = zv.astype(np.uint64)
+        length[:, 1:127:2] = n_zrl * zl
+        val[:, 2:127:2] = np.where(nz, (lut[tac, sym, 0] << acat) | aamp, 0).astype(np.uint64)
+        length[:, 2:127:2] = np.where(nz, lut[tac, sym, 1] + acat, 0)
+        eob = last[:, -1] < 63
+        val[:, 127] = np.where(eob, lut[tsel + 1, 0, 0], 0).astype(np.uint64)
+        length[:, 127] = np.where(eob, lut[tsel + 1, 0, 1], 0)
+        st["zrl"] += int(n_zrl.sum())
+        st["blocks_without_eob"] += int((~eob).sum())
+        st["max_ac_category"] = max(st["max_ac_category"], int(acat.max()))
+        bits_int = np.bincount(interval, weights=length.sum(axis=1), minlength=n_int).astype(np.int64)
+        pad = (-bits_int) % 8
+        ends = np.minimum((np.arange(n_int) + 1) * span, nmcu) * 6 - 1  # the last block of every interval
+        val[ends, 128] = ((1 << pad) - 1).astype(np.uint64)
+        length[ends, 128] = pad
+        keep = length.reshape(-1) > 0
+        v, n = val.reshape(-1)[keep], length.reshape(-1)[keep]
+        start = np.cumsum(n) - n
+        tok = np.repeat(np.arange(n.size), n)
+        shift = (n[tok] - 1 - (np.arange(int(n.sum())) - start[tok])).astype(np.uint64)
+        data = np.packbits(((v[tok] >> shift) & np.uint64(1)).astype(np.uint8)).tobytes()
+        edge = np.concatenate([[0], np.cumsum(bits_int + pad) // 8])
+        parts = [header]
+        for i in range(n_int):
+            if i:
+                parts.append(bytes((0xFF, 0xD0 + ((i - 1) & 7))))
+                st["restart_markers"] += 1
+            piece = data[int(edge[i]):int(edge[i + 1])]
+            st["stuffed_bytes"] += piece.count(b"\xff")
+            parts.append(piece.replace(b"\xff", b"\xff\x00"))
+        parts.append(b"\xff\xd9")
+        files.append(b"".join(parts))
+    return (files, st) if stats else files
+
+
+def pcm16(samples):
+    """Float samples in [-1, 1] -> little-endian 16-bit PCM bytes: rint(32767 x) after clipping x to [-1, 1].  (n,) or
+    (n, channels) - interleaved as stored; a torch tensor or a numpy array."""
+    import numpy as np
+    x = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
+    return np.rint(np.clip(x.astype(np.float64), -1.0, 1.0) * 32767.0).astype("<i2").tobytes()
+
+
+class AviMjpegWriter:
+    """A Motion-JPEG clip in an AVI container (RIFF `AVI `), written block by block: what ffmpeg, VLC, mpv and editors open.
+    `hdrl` holds `avih`, a `strl` for the video stream (`vids` / `MJPG`, a BITMAPINFOHEADER) and, with audio_rate, a `strl` for
+    16-bit PCM (`auds`); `movi` holds one `00dc` chunk per frame and one `01wb` chunk per write_audio call, word-aligned; `idx1`
+    follows.  The rate is y4m_rate(fps) as dwRate / dwScale.  path_or_file: a path (opened here, closed by close()), or a
+    SEEKABLE binary file object, left open: close() goes back and writes the sizes and counts that were unknown at open
+    (ValueError at open for a sink that cannot seek).  write() has handed the bytes on when it returns, so a JpegFrames over a
+    ring slot may be given back right after it.  A file that would pass 2^31 - 2^20 bytes is refused (ValueError from write /
+    write_audio; OpenDML is not written)."""
+    LIMIT = 2**31 - 2**20
+
+    def __init__(self, path_or_file, width, height, fps, audio_rate=None, audio_channels=1):
+        self.width, self.height = int(width), int(height)
+        if self.width < 1 or self.height < 1:
+            raise ValueError("AviMjpegWriter: sides must be positive (got %d x %d)" % (self.width, self.height))
+        self.rate = y4m_rate(fps)
+        self.audio_rate = None if audio_rate is None else int(audio_rate)
+        self.audio_channels = int(audio_channels)
+        if self.audio_rate is not None and (self.audio_rate < 1 or self.audio_channels < 1):
+            raise ValueError("AviMjpegWriter: audio_rate and audio_channels must be positive")
+        self.frames = self.audio_samples = 0
+        self._index, self._max_chunk, self._max_audio = [], 0, 0
+        self._own = not hasattr(path_or_file, "write")
+        if not self._own and not (hasattr(path_or_file, "seekable") and path_or_file.seekable()):
+            raise ValueError("AviMjpegWriter needs a seekable sink: close() writes the sizes and frame counts into the header")
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        try:
+            self._base = self._f.tell()
+            self._f.write(self._header(0))
+            self._movi = self._f.tell() - 4  # idx1 offsets count from the `movi` fourcc
+            self._pos = self._f.tell()
+        except BaseException:
+            f, self._f = self._f, None
+            if self._own:
+                f.close()
+            raise
+
+    def _header(self, movi_bytes):
+        import struct
+        r, w, h = self.rate, self.width, self.height
+        usec = (1000000 * r.denominator + r.numerator // 2) // r.numerator
+        audio = self.audio_rate is not None
+        align = 2 * self.audio_channels
+        per_sec = int(self._max_chunk * r.numerator / r.denominator) + (self.audio_rate * align if audio else 0)
+        avih = struct.pack("<14I", usec, per_sec, 0, 0x10, self.frames, 0, 2 if audio else 1, self._max_chunk, w, h, 0, 0, 0, 0)
+        strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, r.denominator, r.numerator, 0, self.frames, self._max_chunk,
+                           0xFFFFFFFF, 0, 0, 0, w, h)
+        strf = struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0)
+        chunk = lambda cc, body: cc + struct.pack("<I", len(body)) + body
+        lst = lambda kind, body: b"LIST" + struct.pack("<I", 4 + len(body)) + kind + body
+        strls = lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf))
+        if audio:
+            strh_a = struct.pack("<4s4sIHHIIIIIIII4h", b"auds", b"\0\0\0\0", 0, 0, 0, 0, align, self.audio_rate * align, 0, self.audio_samples,
+                                 self._max_audio, 0xFFFFFFFF, align, 0, 0, 0, 0)
+            strf_a = struct.pack("<HHIIHH", 1, self.audio_channels, self.audio_rate, self.audio_rate * align, align, 16)
+            strls += lst(b"strl", chunk(b"strh", strh_a) + chunk(b"strf", strf_a))
+        hdrl = lst(b"hdrl", chunk(b"avih", avih) + strls)
+        idx_bytes = 8 + 16 * len(self._index)
+        riff = 4 + len(hdrl) + 12 + movi_bytes + idx_bytes
+        return b"RIFF" + struct.pack("<I", riff) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", 4 + movi_bytes) + b"movi"
+
+    def _chunk(self, cc, data, flags):
+        import struct
+        if self._f is None:
+            raise ValueError("AviMjpegWriter.write after close()")
+        n = len(data)
+        if self._pos - self._base + 8 + n + (n & 1) + 8 + 16 * (len(self._index) + 1) > self.LIMIT:
+            raise ValueError("AviMjpegWriter: the file would pass %d bytes (an AVI without OpenDML extensions ends below 2 GiB)" % self.LIMIT)
+        self._f.write(cc + struct.pack("<I", n))
+        self._f.write(data)
+        if n & 1:
+            self._f.write(b"\0")
+        self._index.append((cc, flags, self._pos - self._movi, n))
+        self._pos += 8 + n + (n & 1)
+
+    def write(self, frames):
+        """Append frames: a jpeg.JpegFrames or an iterable of bytes-likes, one complete JPEG file each.  Returns the number of
+        frames written so far."""
+        if self._f is None:
+            raise ValueError("AviMjpegWriter.write after close()")
+        for fr in frames:
+            self._video(fr)
+        return self.frames
+
+    def _video(self, fr):
+        fr = memoryview(fr)
+        self._chunk(b"00dc", fr, 0x10)
+        self._max_chunk = max(self._max_chunk, fr.nbytes)
+        self.frames += 1
+
+    def write_audio(self, samples):
+        """Append float samples in [-1, 1] - (n,), or (n, audio_channels) - as one `01wb` chunk of 16-bit PCM (pcm16).  Returns
+        the number of samples per channel written so far."""
+        if self._f is None:
+            raise ValueError("AviMjpegWriter.write_audio after close()")
+        if self.audio_rate is None:
+            raise ValueError("AviMjpegWriter.write_audio: the writer was opened without audio_rate")
+        data = pcm16(samples)
+        if len(data) % (2 * self.audio_channels):
+            raise ValueError("AviMjpegWriter.write_audio: %d samples are not whole frames of %d channels" % (len(data) // 2, self.audio_channels))
+        if data:
+            self._chunk(b"01wb", data, 0x10)
+            self._max_audio = max(self._max_audio, len(data))
+            self.audio_samples += len(data) // (2 * self.audio_channels)
+        return self.audio_samples
+
+    def close(self):
+        import struct
+        f, self._f = self._f, None
+        if f is None:
+            return
+        try:
+            f.write(b"idx1" + struct.pack("<I", 16 * len(self._index)))
+            f.write(b"".join(struct.pack("<4sIII", *e) for e in self._index))
+            end = f.tell()
+            f.seek(self._base)
+            f.write(self._header(self._pos - self._movi - 4))
+            f.seek(end)
+        finally:
+            if self._own:
+                f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

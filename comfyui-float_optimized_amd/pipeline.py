@@ -9,7 +9,7 @@ import warnings
 
 import torch
 
-from . import native
+from . import jpeg, native
 from .config import FmtConfig
 from .decoder import SynthesisHIP
 from .fmt import FlowMatchingTransformerHIP, WindowSampler, draw_noise
@@ -190,6 +190,13 @@ class FrameBlock(collections.namedtuple("FrameBlock", "first last frames")):
     """One FMT window of a streamed clip (FloatHotPath.stream_to_host): frames [first, last) of the clip, `frames` a view of
     a pinned ring slot - (last - first, H, W, 3), or (last - first, 3H/2, W) for I420 - complete when the block is yielded and
     OVERWRITTEN after the generator has been advanced again: copy it to keep it."""
+    __slots__ = ()
+
+
+class JpegBlock(collections.namedtuple("JpegBlock", "first last frames")):
+    """One FMT window of a clip streamed as JPEG files (FloatHotPath.stream_to_jpeg): frames [first, last) of the clip, `frames` a
+    jpeg.JpegFrames over a pinned ring slot - complete when the block is yielded and OVERWRITTEN after the generator has been
+    advanced again: write it out or copy it (`bytes(blk.frames[i])`) to keep it."""
     __slots__ = ()
 
 
@@ -506,6 +513,103 @@ class FloatHotPath:
             finally:
                 pending.clear()
                 del ring, staging, wins
+                self._last_job = self._open_stream = None
+
+    @torch.no_grad()
+    def generate_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
+                         quality=90, restart=None, return_rd=False):
+        """generate_to_host for one clip (B = 1) with the frames leaving as baseline JPEG files (jpeg.JpegFrames in pinned host
+        memory): the chain, decode_u8 of the whole clip, float_jpg_encode on the 8-bit frames in HBM, ONE host read of the
+        offsets, then offsets[T] bytes across PCIe - the files, not the frames.  File i is bitwise
+        host_models.jpeg_encode_rgb8(frame i of generate_to_host(out_dtype=torch.uint8), quality, restart).  Complete on return
+        (the stream has been synchronised).  The 8-bit frames stay on the device: T * size * size * 3 bytes of HBM while it runs."""
+        self.require_no_stream("generate_to_jpeg")
+        if feats is not None:
+            self.dec.set_feats(feats)
+        r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
+        with torch.cuda.device(self.device):
+            frames = jpeg.encode_jpeg_host(self.dec.decode_u8(s_r, _rows(r_d)), quality, restart)
+        return (frames, r_d) if return_rd else frames
+
+    def stream_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
+                       quality=90, restart=None, slots=3):
+        """generate_to_jpeg as a generator: one JpegBlock(first, last, frames) per FMT window, in frame order, the same files as the
+        whole-clip call.  The contract is stream_to_host's: `frames` (a jpeg.JpegFrames) lives in one of `slots` pinned ring
+        buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (AviMjpegWriter.write
+        has handed the bytes on when it returns); window k + 1 and further windows, as far as free slots allow, are enqueued
+        before the wait for window k; slots >= 2 and B = 1 are checked at the call (ValueError), nothing is enqueued before the
+        first next(); while the generator is open every other producer on this object raises RuntimeError, and leaving early
+        waits for the enqueued work and clears that flag.
+        Per slot: a device buffer of 50 8-bit frames, a device and a pinned buffer of their I420 size for the files, and the
+        offsets on both sides.  Per window the chain, decode_u8, float_jpg_encode and the copy of the 51 offsets are enqueued on
+        the current stream; when the block's turn comes the generator waits on that block's event, reads offsets[-1] from pinned
+        memory and copies that many bytes on a second stream.  Files beyond the slot's room (noise at quality 100) are encoded
+        once more into a larger buffer."""
+        if int(slots) < 2:
+            raise ValueError("stream_to_jpeg needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
+        if wa.dim() != 3 or wa.shape[0] != 1:
+            raise ValueError("stream_to_jpeg streams one clip (B = 1): wa must be (1, T, dim_a), got %s" % (tuple(wa.shape),))
+        quality = int(quality)
+        if not 1 <= quality <= 100:
+            raise ValueError("stream_to_jpeg: quality (%d) must be 1 ... 100" % quality)
+        self.require_no_stream("stream_to_jpeg")
+        return self._stream_jpeg_blocks(r_s, wa, we, s_r, feats, nfe, (a_cfg_scale, r_cfg_scale, e_cfg_scale), seed, noise, quality,
+                                        jpeg.default_restart(self.size) if restart is None else int(restart), int(slots))
+
+    def _stream_jpeg_blocks(self, r_s, wa, we, s_r, feats, nfe, scales, seed, noise, quality, restart, slots):
+        self.require_no_stream("stream_to_jpeg")  # another stream may have been started since the call
+        dev, L, R = self.device, self.cfg.num_frames_for_clip, self.size
+        T = wa.shape[1]
+        self._open_stream = "stream_to_jpeg (%d frames, %d slots)" % (T, slots)
+        pending = collections.deque()  # (first, last, slot index, event) of the windows enqueued and not yet yielded
+        ring = wins = work = None
+        try:
+            st = torch.cuda.current_stream(dev)
+            with torch.cuda.stream(st):
+                if feats is not None:
+                    self.dec.set_feats(feats)
+                if noise is None:
+                    noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
+                cap = jpeg.default_capacity(L, R, R)
+                ring = [dict(u8=torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
+                             off=torch.empty(L + 1, dtype=torch.int64, device=dev), host=torch.empty(cap, dtype=torch.uint8, pin_memory=True),
+                             off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True)) for _ in range(slots)]
+                s_copy = torch.cuda.Stream(dev)
+                s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
+            wins = self._windows((r_s, wa, we, noise, nfe) + scales, st, st)
+            n_win, enqueued = self.n_chunks(T), 0
+            for j in range(n_win):
+                with torch.cuda.stream(st):
+                    while enqueued < min(n_win, j + slots):
+                        ws, f0, f1 = next(wins)
+                        slot, n = ring[enqueued % slots], f1 - f0
+                        self.dec._run(native.lib().float_dec_frames_u8, s_r_d, ws.r_d[0, f0:f1], (R, R, 3), torch.uint8, out=slot["u8"][:n])
+                        work = jpeg.enqueue_encode(slot["u8"][:n], quality, restart, slot["data"], slot["off"][:n + 1], work)
+                        slot["off_host"][:n + 1].copy_(slot["off"][:n + 1], non_blocking=True)
+                        ev = torch.cuda.Event()
+                        ev.record(st)
+                        pending.append((f0, f1, enqueued % slots, ev))
+                        enqueued += 1
+                f0, f1, k, ev = pending.popleft()
+                slot, n = ring[k], f1 - f0
+                ev.synchronize()
+                edges = slot["off_host"][:n + 1]
+                total = int(edges[-1])
+                if total > slot["data"].numel():  # the files did not fit: once more, with room (behind the windows already enqueued)
+                    with torch.cuda.stream(st):
+                        slot["data"] = torch.empty(total, dtype=torch.uint8, device=dev)
+                        slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+                        work = jpeg.enqueue_encode(slot["u8"][:n], quality, restart, slot["data"], slot["off"][:n + 1], work)
+                    st.synchronize()
+                s_copy.wait_event(ev)
+                yield JpegBlock(f0, f1, jpeg.to_host(slot["data"], edges.clone(), slot["host"], s_copy))
+        finally:
+            try:
+                if pending:
+                    pending[-1][3].synchronize()
+            finally:
+                pending.clear()
+                del ring, wins, work
                 self._last_job = self._open_stream = None
 
     def _overlap_streams(self, mode):

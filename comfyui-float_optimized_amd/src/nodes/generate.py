@@ -413,6 +413,75 @@ class InferenceAgent:
             s, a = self.host_inputs(ref_img, ref_audio, no_crop)
         yield from self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots)
 
+    @torch.no_grad()
+    def infer_device_jpeg(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, quality=90, restart=None):
+        """infer_device with the frames leaving as baseline JPEG files: a jpeg.JpegFrames in pinned host memory, file i bitwise
+        host_models.jpeg_encode_rgb8(infer_device(out_dtype=torch.uint8)[i], quality, restart) (FloatHotPath.generate_to_jpeg: the
+        encoder runs on the 8-bit frames in HBM and only the files cross PCIe).  FLOAT_AMD_RANGE applies as in infer_device (auto
+        rebuilds and runs the clip again); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        c, noise = self._clip_inputs(s, a, emo, seed)
+        frames = self.G.generate_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                         noise=noise, quality=quality, restart=restart)
+        if self.check_range("InferenceAgent.infer_device_jpeg", allow_rebuild=True) == "rebuilt":
+            return self.infer_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality, restart)  # once more, in the wider types
+        return frames
+
+    def stream_device_jpeg(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, quality=90, restart=None,
+                           slots=3):
+        """The streaming sibling of infer_device_jpeg: a generator of JpegBlock(first, last, frames), one per 50-frame FMT window, in
+        frame order - concatenated, the files infer_device_jpeg returns for the same inputs and seed.  `frames` lives in one of
+        `slots` pinned ring buffers (FloatHotPath.stream_to_jpeg has the contract): complete when yielded, OVERWRITTEN once the
+        generator has been advanced again.  slots < 2 or a quality outside 1 ... 100 raise ValueError here, at the call; nothing
+        runs before the first next().  While the stream is open every other call that produces frames on this agent raises
+        RuntimeError; close() (or dropping) the generator early leaves the agent usable.  After the last block FLOAT_AMD_RANGE is
+        applied once, as in stream_device: warn, raise and off, and auto acts as warn.  FLOAT_AMD_VERIFY is NOT applied."""
+        if int(slots) < 2:
+            raise ValueError("stream_device_jpeg needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("stream_device_jpeg: quality (%r) must be 1 ... 100" % (quality,))
+        if self.G is not None:
+            self.G.require_no_stream("stream_device_jpeg")
+        return self._stream_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, int(quality), restart, int(slots))
+
+    def _stream_device_jpeg(self, s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality, restart, slots):
+        c, noise = self._clip_inputs(s, a, emo, seed)
+        done = False
+        try:
+            yield from self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
+                                             e_cfg_scale, noise=noise, quality=quality, restart=restart, slots=slots)
+            done = True
+        finally:
+            # left early: as in _stream_device, what the abandoned windows counted is not the next clip's
+            if not done and self.G is not None and not self.G._open_stream and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
+                self.range_counts(reset=True)
+        where = "InferenceAgent.stream_device_jpeg"
+        if os.environ.get("FLOAT_AMD_RANGE", "warn").lower() == "auto":
+            where += " (FLOAT_AMD_RANGE=auto acts as warn in a stream: the frames have been consumed and are not run again)"
+        self.check_range(where)
+
+    def write_video(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                    quality=90, fps=None):
+        """A playable file: host_inputs, stream_device_jpeg, and host_models.AviMjpegWriter on `path` (a path or a seekable binary
+        file object) - Motion JPEG in an AVI container with the clip's audio as a 16-bit PCM track: the AUDIO item's own samples
+        at its own rate, channels mixed to mono (not the normalised 16 kHz waveform the model hears), one `01wb` chunk behind the
+        frames of every window.  fps defaults to opt.fps.  Returns the number of frames written."""
+        o = self.opt
+        fps = o.fps if fps is None else fps
+        with torch.no_grad():
+            s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+        audio = ref_audio["waveform"][0].detach().float().cpu()
+        audio = (audio.mean(dim=0) if audio.dim() == 2 else audio).reshape(-1)
+        rate = int(ref_audio["sample_rate"])
+        with host_models.AviMjpegWriter(path, o.input_size, o.input_size, fps, audio_rate=rate) as w:
+            sent = 0
+            for blk in self.stream_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality):
+                w.write(blk.frames)
+                upto = min(audio.numel(), int(round(blk.last * rate / float(fps))))
+                w.write_audio(audio[sent:upto])
+                sent = max(sent, upto)
+            w.write_audio(audio[sent:])
+            return w.frames
+
     def range_counts(self, reset=True):
         """{operator: clamped / non-finite 16-bit stores since the last call} over every fp16 handle of the agent."""
         if self.G is None:

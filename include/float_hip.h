@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_front / float_img_front_work_bytes (the image front end on the device),
+/* Stays 6: float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
+ * float_img_front / float_img_front_work_bytes (the image front end on the device),
  * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
  * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
  * float_dec_frames_host_u8 (8-bit frames), float_dec_frames_i420 / float_dec_frames_host_i420 (planar YUV 4:2:0 frames) and
@@ -551,6 +552,33 @@ size_t float_img_front_work_bytes(int32_t src_h, int32_t src_w, int32_t dst_h, i
 int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t channels, int32_t rect_x, int32_t rect_y, int32_t rect_w,
                     int32_t rect_h, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g, int32_t bkg_b,
                     int32_t out_mode, void* out, int32_t dst_h, int32_t dst_w, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------- JPEG encoder -- */
+/* n_frames 8-bit RGB frames in HBM - the (n, h, w, 3) buffer float_dec_frames_u8 writes - -> n complete baseline JPEG files
+ * (JFIF 1.1, 4:2:0, one interleaved scan, the Huffman tables of ITU-T T.81 Annex K.3), back to back in `out`: file i is
+ * out[offsets[i] : offsets[i + 1]].  Every step is integer arithmetic, so the bytes are bitwise the definition in the host mirror,
+ * host_models.jpeg_encode_rgb8, which states the colour matrix (full-range BT.601), the 2 x 2 chroma mean, the two DCT passes
+ * (M = rint(2^14 A)), the quantiser (Annex K.1 / K.2 scaled by `quality`), the entropy coding and the file layout.
+ *   h, w      multiples of 16 in 16 ... 16384; quality 1 ... 100
+ *   restart   MCUs per restart interval, 0 ... 65535.  The intervals of a frame are coded in parallel, one workgroup each: one
+ *             MCU row (w / 16) is the intended value.  0 writes no restart markers: a frame is then one serial chain coded by ONE
+ *             workgroup - supported, bitwise the definition, and slow.
+ *   out       DEVICE, out_cap bytes.  offsets: DEVICE, n_frames + 1 int64, 8-byte aligned; ALWAYS complete and exact, also when
+ *             offsets[n_frames] > out_cap: then nothing at or beyond out + out_cap is written (what lies below is valid), and the
+ *             caller reads offsets[n_frames] and calls again with room.
+ *   work      DEVICE scratch of at least float_jpg_work_bytes(n_frames, h, w, restart) bytes, 16-byte aligned, no zeroing needed.
+ *             Frames are coded in groups of 16 that share it in stream order: with g = min(n_frames, 16) frames, i intervals per
+ *             frame and m MCUs per interval it is g i (12 + 2496 m) bytes rounded up - 12 for an interval's length and place, and a
+ *             slot of the provable worst case, 6 blocks x 64 coefficients x 26 bits, doubled by byte stuffing (40.9 MB at 512 x 512).
+ *   rgb8      2-byte aligned.
+ * The header bytes, the quantiser and the Huffman code tables are built on the host inside the call and passed as kernel
+ * arguments.  Enqueues three kernels per group on `stream`; allocates nothing, synchronises nothing, kernel launches only; the
+ * only atomics are ORs into an LDS bit buffer, so two calls give equal bytes.  An argument outside these rules (a null pointer,
+ * a side that is no multiple of 16, a quality outside 1 ... 100, a short or misaligned work) returns FLOAT_E_INVALID, with a
+ * message naming the function and the argument, before any HIP call; float_jpg_work_bytes returns 0 for such sizes. */
+size_t float_jpg_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t restart);
+int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out, size_t out_cap,
+                     int64_t* offsets, void* work, size_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }
