@@ -20,6 +20,20 @@ def blur_taps(blur_kernel):
     return None if k.tolist() == [1.0, 3.0, 3.0, 1.0] else k
 
 
+def infer_out_format(t, out_format, dtype=None):
+    """The frame format of a hand-over, "rgb" or "i420", from its destination tensor `t` and the stated `out_format` (None |
+    "rgb" | "i420").  Unstated, a 3-d uint8 tensor is I420 and everything else RGB; I420 frames are uint8, so "i420" with any other
+    dtype is a ValueError.  dtype: the frames' dtype where there is no tensor (`t` None)."""
+    if out_format not in (None, "rgb", "i420"):
+        raise ValueError("out_format must be None, 'rgb' or 'i420' (got %r)" % (out_format,))
+    dtype = t.dtype if t is not None else dtype
+    if out_format is None:
+        out_format = "i420" if t is not None and dtype == torch.uint8 and t.dim() == 3 else "rgb"
+    if out_format == "i420" and dtype != torch.uint8:
+        raise ValueError("I420 frames are uint8: out_format='i420' contradicts %s" % (dtype,))
+    return out_format
+
+
 @native.rebuildable
 class SynthesisHIP:
     def __init__(self, state_dict, size=512, style_dim=512, device="cuda:0", dtype="fp16", max_frames=16, blur_kernel=None):
@@ -110,15 +124,15 @@ class SynthesisHIP:
         return self._run(native.lib().float_dec_frames, s_r, r_d, (self.size, self.size, 3), out=out)
 
     @torch.no_grad()
-    def decode_u8(self, s_r, r_d, s_r_feats=None):
+    def decode_u8(self, s_r, r_d, s_r_feats=None, out=None):
         """decode_latent_into_processed_images as 8-bit frames (float_dec_frames_u8): (T, H, W, 3) uint8 on the GPU, quantised
         by the last-level kernel - bitwise torch.round(frames_fp32 * 255).to(torch.uint8) of the same handle."""
         if s_r_feats is not None:
             self.set_feats(s_r_feats)
-        return self._run(native.lib().float_dec_frames_u8, s_r, r_d, (self.size, self.size, 3), torch.uint8)
+        return self._run(native.lib().float_dec_frames_u8, s_r, r_d, (self.size, self.size, 3), torch.uint8, out)
 
     @torch.no_grad()
-    def decode_i420(self, s_r, r_d, s_r_feats=None):
+    def decode_i420(self, s_r, r_d, s_r_feats=None, out=None):
         """decode_latent_into_processed_images as planar YUV 4:2:0 frames (float_dec_frames_i420): (T, 3 * size / 2, size) uint8 on
         the GPU - per frame the Y plane, then U and V at half the size, what ffmpeg calls yuv420p and OpenCV's *_I420 conversions
         use.  BT.601 limited range from the 8-bit samples, in integers: bitwise host_models.rgb8_to_i420(decode_u8(...))."""
@@ -126,7 +140,7 @@ class SynthesisHIP:
             self.set_feats(s_r_feats)
         L = native.lib()
         return self._run(lambda h, s, r, T, out, st: L.float_dec_frames_i420(h, s, r, T, native.MATRIX_BT601_LIMITED, out, st),
-                         s_r, r_d, (3 * self.size // 2, self.size), torch.uint8)
+                         s_r, r_d, (3 * self.size // 2, self.size), torch.uint8, out)
 
     @torch.no_grad()
     def decode_jpeg(self, s_r, r_d, quality=90, restart=None, s_r_feats=None, out=None):
@@ -167,14 +181,9 @@ class SynthesisHIP:
         s_r = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         T = r_d.shape[0]
-        if out_format not in (None, "rgb", "i420"):
-            raise ValueError("out_format must be None, 'rgb' or 'i420' (got %r)" % (out_format,))
+        out_format = infer_out_format(host, out_format)
         if host.dtype not in (torch.float32, torch.uint8):
             raise ValueError("host must be float32 or uint8 (got %s)" % (host.dtype,))
-        if out_format is None:
-            out_format = "i420" if host.dtype == torch.uint8 and host.dim() == 3 else "rgb"
-        if out_format == "i420" and host.dtype != torch.uint8:
-            raise ValueError("I420 frames are uint8 (host is %s)" % (host.dtype,))
         shape = (T,) + self.frame_shape(out_format)
         if tuple(host.shape) != shape or host.is_cuda or not host.is_contiguous():
             raise ValueError("host must be a contiguous CPU %s tensor of shape %s for out_format %r"

@@ -11,7 +11,7 @@ import torch
 
 from . import jpeg, native
 from .config import FmtConfig
-from .decoder import SynthesisHIP
+from .decoder import SynthesisHIP, infer_out_format
 from .fmt import FlowMatchingTransformerHIP, WindowSampler, draw_noise
 
 
@@ -171,16 +171,10 @@ def resolve_out_format(out, out_dtype, out_format):
     decides) | "i420" ((T, 3R/2, R) uint8 planar YUV 4:2:0, host_models.rgb8_to_i420).  "i420" implies uint8: with
     out_dtype=torch.float32 or an fp32 `out` it is a ValueError.  A caller-supplied `out` fixes the format by its dimensions (a
     3-d uint8 tensor is I420), and a stated format that contradicts it is a ValueError."""
-    if out_format not in (None, "rgb", "i420"):
-        raise ValueError("out_format must be None, 'rgb' or 'i420' (got %r)" % (out_format,))
     if out_format == "i420" and out is None and out_dtype is None:
         out_dtype = torch.uint8
     dtype = _resolve_out_dtype(out, out_dtype)
-    fmt = out_format
-    if fmt is None:
-        fmt = "i420" if out is not None and out.dtype == torch.uint8 and out.dim() == 3 else "rgb"
-    if fmt == "i420" and dtype != torch.uint8:
-        raise ValueError("I420 frames are uint8: out_format='i420' contradicts %s" % (dtype,))
+    fmt = infer_out_format(out, out_format, dtype)
     if out is not None and out.dim() != (3 if fmt == "i420" else 4):
         raise ValueError("out has %d dimensions, out_format %r takes %s" % (out.dim(), fmt, "(T, 3R/2, R)" if fmt == "i420" else "(T, R, R, 3)"))
     return dtype, fmt
@@ -198,6 +192,68 @@ class JpegBlock(collections.namedtuple("JpegBlock", "first last frames")):
     jpeg.JpegFrames over a pinned ring slot - complete when the block is yielded and OVERWRITTEN after the generator has been
     advanced again: write it out or copy it (`bytes(blk.frames[i])`) to keep it."""
     __slots__ = ()
+
+
+class _FrameSink:
+    """What FloatHotPath._ring does per slot for stream_to_host: a slot is a pinned (L,) + frame_shape buffer, and the one device
+    staging buffer is shared by all of them (safe in stream order)."""
+    name = "stream_to_host"
+
+    def __init__(self, hot, out_dtype, out_format):
+        self.hot, self.dtype, self.fmt = hot, out_dtype, out_format
+
+    def open(self, slots):
+        shape = (self.hot.cfg.num_frames_for_clip,) + self.hot.dec.frame_shape(self.fmt)
+        ring = [torch.empty(shape, dtype=self.dtype, pin_memory=True) for _ in range(slots)]
+        self.staging = torch.empty(shape, device=self.hot.device, dtype=self.dtype)
+        return ring
+
+    def enqueue(self, slot, s_r_d, rows):
+        n = rows.shape[0]
+        self.hot.dec.decode_into_host(s_r_d, rows, slot[:n], self.staging[:n], out_format=self.fmt)
+
+    def block(self, slot, f0, f1, ev, st):
+        return FrameBlock(f0, f1, slot[:f1 - f0])
+
+
+class _JpegSink:
+    """What FloatHotPath._ring does per slot for stream_to_jpeg: a slot holds the 8-bit frames of a window on the device, the
+    files and their offsets on both sides; the copy stream and the encoder's scratch are shared."""
+    name = "stream_to_jpeg"
+
+    def __init__(self, hot, quality, restart):
+        self.hot, self.quality, self.restart = hot, quality, restart
+
+    def open(self, slots):
+        dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
+        cap = jpeg.default_capacity(L, R, R)
+        ring = [dict(u8=torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
+                     off=torch.empty(L + 1, dtype=torch.int64, device=dev), host=torch.empty(cap, dtype=torch.uint8, pin_memory=True),
+                     off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True)) for _ in range(slots)]
+        self.s_copy, self.work = torch.cuda.Stream(dev), None
+        return ring
+
+    def _encode(self, slot, n):
+        self.work = jpeg.enqueue_encode(slot["u8"][:n], self.quality, self.restart, slot["data"], slot["off"][:n + 1], self.work)
+
+    def enqueue(self, slot, s_r_d, rows):
+        n = rows.shape[0]
+        self.hot.dec.decode_u8(s_r_d, rows, out=slot["u8"][:n])
+        self._encode(slot, n)
+        slot["off_host"][:n + 1].copy_(slot["off"][:n + 1], non_blocking=True)
+
+    def block(self, slot, f0, f1, ev, st):
+        n = f1 - f0
+        edges = slot["off_host"][:n + 1]
+        total = int(edges[-1])
+        if total > slot["data"].numel():  # the files did not fit: once more, with room (behind the windows already enqueued)
+            with torch.cuda.stream(st):
+                slot["data"] = torch.empty(total, dtype=torch.uint8, device=self.hot.device)
+                slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+                self._encode(slot, n)
+            st.synchronize()
+        self.s_copy.wait_event(ev)
+        return JpegBlock(f0, f1, jpeg.to_host(slot["data"], edges.clone(), slot["host"], self.s_copy))
 
 
 class FloatHotPath:
@@ -434,14 +490,17 @@ class FloatHotPath:
         time table and the history rows of the workspace, and the only call that reads an unfinished job is
         float_fmt_sample_next, which is reachable only through the WindowSampler this generator drops - so the next sample /
         sample_begin starts clean."""
+        sink = _FrameSink(self, *resolve_out_format(None, out_dtype, out_format))
+        self._check_stream_call(sink.name, slots, wa)
+        return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
+
+    def _check_stream_call(self, what, slots, wa):
+        """What every stream refuses at the call, before its generator exists (a generator's body runs at the first next())."""
         if int(slots) < 2:
-            raise ValueError("stream_to_host needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
-        out_dtype, out_format = resolve_out_format(None, out_dtype, out_format)
+            raise ValueError("%s needs slots >= 2 (one block with the consumer, one in flight), got %r" % (what, slots))
         if wa.dim() != 3 or wa.shape[0] != 1:
-            raise ValueError("stream_to_host streams one clip (B = 1): wa must be (1, T, dim_a), got %s" % (tuple(wa.shape),))
-        self.require_no_stream("stream_to_host")
-        return self._stream_blocks(r_s, wa, we, s_r, feats, nfe, (a_cfg_scale, r_cfg_scale, e_cfg_scale), seed, noise,
-                                   out_dtype, out_format, int(slots))
+            raise ValueError("%s streams one clip (B = 1): wa must be (1, T, dim_a), got %s" % (what, tuple(wa.shape)))
+        self.require_no_stream(what)
 
     def _windows(self, job, s_fmt, s_dec, frame_range=None):
         """The window pipeline of every windowed producer.  job = (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
@@ -468,25 +527,26 @@ class FloatHotPath:
                 s_dec.wait_event(ev)
             yield ws, f0, f1
 
-    def _stream_blocks(self, r_s, wa, we, s_r, feats, nfe, scales, seed, noise, out_dtype, out_format, slots):
-        self.require_no_stream("stream_to_host")  # another stream may have been started since the call
-        dev, L = self.device, self.cfg.num_frames_for_clip
-        T = wa.shape[1]
-        self._open_stream = "stream_to_host (%d frames, %d slots)" % (T, slots)
-        pending = collections.deque()  # (first, last, slot view, event) of the blocks enqueued and not yet yielded
-        ring = staging = wins = None
+    def _ring(self, sink, job, s_r, feats, seed, noise, slots):
+        """The bounded ring of every stream.  job = (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale).  `sink` is what the
+        forms differ in (_FrameSink, _JpegSink): open(slots) makes the slots and the per-stream scratch, inside the first next();
+        enqueue(slot, s_r_d, rows) enqueues the work of one window on the stream; block(slot, first, last, event, stream) turns a
+        slot whose event has been waited on into the block that is yielded."""
+        self.require_no_stream(sink.name)  # another stream may have been started since the call
+        T = job[1].shape[1]
+        self._open_stream = "%s (%d frames, %d slots)" % (sink.name, T, slots)
+        pending = collections.deque()  # (first, last, slot, event) of the blocks enqueued and not yet yielded
+        ring = wins = slot = None
         try:
-            st = torch.cuda.current_stream(dev)
+            st = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(st):
                 if feats is not None:
                     self.dec.set_feats(feats)
                 if noise is None:
                     noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
-                fshape = self.dec.frame_shape(out_format)
-                ring = [torch.empty((L,) + fshape, dtype=out_dtype, pin_memory=True) for _ in range(slots)]
-                staging = torch.empty((L,) + fshape, device=dev, dtype=out_dtype)
-                s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-            wins = self._windows((r_s, wa, we, noise, nfe) + scales, st, st)  # one stream: no events between the stages
+                ring = sink.open(slots)
+                s_r_d = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
+            wins = self._windows(job[:3] + (noise,) + job[3:], st, st)  # one stream: no events between the stages
             n_win, enqueued = self.n_chunks(T), 0
             for j in range(n_win):
                 # block j is about to go to the consumer, who holds nothing now: blocks j .. j + slots - 1 sit in `slots` different
@@ -494,25 +554,24 @@ class FloatHotPath:
                 with torch.cuda.stream(st):
                     while enqueued < min(n_win, j + slots):
                         ws, f0, f1 = next(wins)
-                        view = ring[enqueued % slots][:f1 - f0]
-                        self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], view, staging[:f1 - f0], out_format=out_format)
+                        sink.enqueue(ring[enqueued % slots], s_r_d, ws.r_d[0, f0:f1])
                         ev = torch.cuda.Event()
                         ev.record(st)
-                        pending.append((f0, f1, view, ev))
+                        pending.append((f0, f1, ring[enqueued % slots], ev))
                         enqueued += 1
-                f0, f1, view, ev = pending.popleft()
+                f0, f1, slot, ev = pending.popleft()
                 ev.synchronize()
-                yield FrameBlock(f0, f1, view)
+                yield sink.block(slot, f0, f1, ev, st)
         finally:
-            # early exit (close(), garbage collection, an exception thrown in or raised above): the copy workgroups of the blocks
-            # still in flight store into the ring, so it is dropped only after the last of them has run.  Events complete in
-            # stream order: the last one covers the others, and the job's tensors with them.
+            # early exit (close(), garbage collection, an exception thrown in or raised above): the work of the blocks still in
+            # flight stores into the ring, so it is dropped only after the last of it has run.  Events complete in stream order:
+            # the last one covers the others, and the job's tensors with them.
             try:
                 if pending:
                     pending[-1][3].synchronize()
             finally:
                 pending.clear()
-                del ring, staging, wins
+                del ring, wins, sink, slot
                 self._last_job = self._open_stream = None
 
     @torch.no_grad()
@@ -545,72 +604,12 @@ class FloatHotPath:
         the current stream; when the block's turn comes the generator waits on that block's event, reads offsets[-1] from pinned
         memory and copies that many bytes on a second stream.  Files beyond the slot's room (noise at quality 100) are encoded
         once more into a larger buffer."""
-        if int(slots) < 2:
-            raise ValueError("stream_to_jpeg needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
-        if wa.dim() != 3 or wa.shape[0] != 1:
-            raise ValueError("stream_to_jpeg streams one clip (B = 1): wa must be (1, T, dim_a), got %s" % (tuple(wa.shape),))
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError("stream_to_jpeg: quality (%d) must be 1 ... 100" % quality)
-        self.require_no_stream("stream_to_jpeg")
-        return self._stream_jpeg_blocks(r_s, wa, we, s_r, feats, nfe, (a_cfg_scale, r_cfg_scale, e_cfg_scale), seed, noise, quality,
-                                        jpeg.default_restart(self.size) if restart is None else int(restart), int(slots))
-
-    def _stream_jpeg_blocks(self, r_s, wa, we, s_r, feats, nfe, scales, seed, noise, quality, restart, slots):
-        self.require_no_stream("stream_to_jpeg")  # another stream may have been started since the call
-        dev, L, R = self.device, self.cfg.num_frames_for_clip, self.size
-        T = wa.shape[1]
-        self._open_stream = "stream_to_jpeg (%d frames, %d slots)" % (T, slots)
-        pending = collections.deque()  # (first, last, slot index, event) of the windows enqueued and not yet yielded
-        ring = wins = work = None
-        try:
-            st = torch.cuda.current_stream(dev)
-            with torch.cuda.stream(st):
-                if feats is not None:
-                    self.dec.set_feats(feats)
-                if noise is None:
-                    noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
-                cap = jpeg.default_capacity(L, R, R)
-                ring = [dict(u8=torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
-                             off=torch.empty(L + 1, dtype=torch.int64, device=dev), host=torch.empty(cap, dtype=torch.uint8, pin_memory=True),
-                             off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True)) for _ in range(slots)]
-                s_copy = torch.cuda.Stream(dev)
-                s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-            wins = self._windows((r_s, wa, we, noise, nfe) + scales, st, st)
-            n_win, enqueued = self.n_chunks(T), 0
-            for j in range(n_win):
-                with torch.cuda.stream(st):
-                    while enqueued < min(n_win, j + slots):
-                        ws, f0, f1 = next(wins)
-                        slot, n = ring[enqueued % slots], f1 - f0
-                        self.dec._run(native.lib().float_dec_frames_u8, s_r_d, ws.r_d[0, f0:f1], (R, R, 3), torch.uint8, out=slot["u8"][:n])
-                        work = jpeg.enqueue_encode(slot["u8"][:n], quality, restart, slot["data"], slot["off"][:n + 1], work)
-                        slot["off_host"][:n + 1].copy_(slot["off"][:n + 1], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(st)
-                        pending.append((f0, f1, enqueued % slots, ev))
-                        enqueued += 1
-                f0, f1, k, ev = pending.popleft()
-                slot, n = ring[k], f1 - f0
-                ev.synchronize()
-                edges = slot["off_host"][:n + 1]
-                total = int(edges[-1])
-                if total > slot["data"].numel():  # the files did not fit: once more, with room (behind the windows already enqueued)
-                    with torch.cuda.stream(st):
-                        slot["data"] = torch.empty(total, dtype=torch.uint8, device=dev)
-                        slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-                        work = jpeg.enqueue_encode(slot["u8"][:n], quality, restart, slot["data"], slot["off"][:n + 1], work)
-                    st.synchronize()
-                s_copy.wait_event(ev)
-                yield JpegBlock(f0, f1, jpeg.to_host(slot["data"], edges.clone(), slot["host"], s_copy))
-        finally:
-            try:
-                if pending:
-                    pending[-1][3].synchronize()
-            finally:
-                pending.clear()
-                del ring, wins, work
-                self._last_job = self._open_stream = None
+        sink = _JpegSink(self, quality, jpeg.default_restart(self.size) if restart is None else int(restart))
+        self._check_stream_call(sink.name, slots, wa)
+        return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     def _overlap_streams(self, mode):
         """(chain stream, decoder stream) of the stage-overlapped forms.  mode "prio": two streams of one device queue set, the
@@ -631,8 +630,25 @@ class FloatHotPath:
                 pd = lo if mode in ("prio", "lo") else 0
                 cache[mode] = (torch.cuda.Stream(dev, priority=pf), torch.cuda.Stream(dev, priority=pd))
             else:
-                raise ValueError("overlap mode must be 'prio' or 'cu:N', got %r" % (mode,))
+                raise ValueError("overlap mode must be 'prio', 'hi', 'lo', 'plain' or 'cu:N', got %r" % (mode,))
         return cache[mode]
+
+    def _overlapped(self, mode, job, s_r, decode, frame_range=None):
+        """The two-stream loop of the stage-overlapped forms: the chain of window k + 1 on one stream of _overlap_streams(mode)
+        while decode(s_r_d, rows, f0, f1) runs for window k with the other one current.  The caller has produced everything
+        `decode` touches (noise, destination, staging) on the current stream BEFORE this call: both streams wait for the current
+        one only here, behind that work and behind s_r_d, and the current one waits for both at the end.  Returns r_d."""
+        s_r_d = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
+        s_fmt, s_dec = self._overlap_streams(mode)
+        cur = torch.cuda.current_stream(self.device)
+        s_fmt.wait_stream(cur)
+        s_dec.wait_stream(cur)
+        for ws, f0, f1 in self._windows(job, s_fmt, s_dec, frame_range):
+            with torch.cuda.stream(s_dec):
+                decode(s_r_d, ws.r_d[0, f0:f1], f0, f1)
+        cur.wait_stream(s_dec)
+        cur.wait_stream(s_fmt)
+        return self._last_job.r_d
 
     @torch.no_grad()
     def generate_to_host_overlap(self, r_s, wa, we, s_r, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, noise=None,
@@ -646,25 +662,17 @@ class FloatHotPath:
         out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
         self.require_no_stream("generate_to_host_overlap")
         T = wa.shape[1]
-        dev = self.device
         if noise is None:
             noise = draw_noise(self.n_chunks(T), 1, self.cfg, seed)
-        s_fmt, s_dec = self._overlap_streams(mode)
-        cur = torch.cuda.current_stream(dev)
-        s_fmt.wait_stream(cur)
-        s_dec.wait_stream(cur)
         self._prune_inflight()
         if out is None:
             out = torch.empty((T,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
         staging = self.staging(T, out_dtype, out_format)
-        s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-        for ws, f0, f1 in self._windows((r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_fmt, s_dec):
-            with torch.cuda.stream(s_dec):
-                self.dec.decode_into_host(s_r_d, ws.r_d[0, f0:f1], out[f0:f1], staging[f0:f1], out_format=out_format)
-        cur.wait_stream(s_dec)
-        cur.wait_stream(s_fmt)
-        self._hold_inflight(out, cur)
-        return (out, self._last_job.r_d) if return_rd else out
+        r_d = self._overlapped(mode, (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r,
+                               lambda s_r_d, rows, f0, f1: self.dec.decode_into_host(s_r_d, rows, out[f0:f1], staging[f0:f1],
+                                                                                     out_format=out_format))
+        self._hold_inflight(out, torch.cuda.current_stream(self.device))
+        return (out, r_d) if return_rd else out
 
     @torch.no_grad()
     def generate(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
@@ -688,20 +696,11 @@ class FloatHotPath:
             frames = self.decode(s_r, None, r_d, frame_range)
             return (frames, r_d) if return_rd else frames
         t0, t1 = frame_range if frame_range is not None else (0, T)
-        dev = self.device
-        s_fmt, s_dec = self._overlap_streams("hi")
-        cur = torch.cuda.current_stream(dev)
-        s_fmt.wait_stream(cur)
-        s_dec.wait_stream(cur)
-        out = torch.empty(t1 - t0, self.size, self.size, 3, device=dev, dtype=torch.float32)
-        s_r_d = s_r.to(dev, torch.float32).reshape(-1).contiguous()
-        job = (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
-        for ws, a, b in self._windows(job, s_fmt, s_dec, (t0, t1)):
-            with torch.cuda.stream(s_dec):
-                self.dec.decode_latent_into_processed_images(s_r_d, ws.r_d[0, a:b], out=out[a - t0:b - t0])
-        cur.wait_stream(s_dec)
-        cur.wait_stream(s_fmt)
-        return (out, self._last_job.r_d) if return_rd else out
+        out = torch.empty(t1 - t0, self.size, self.size, 3, device=self.device, dtype=torch.float32)
+        r_d = self._overlapped("hi", (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r,
+                               lambda s_r_d, rows, a, b: self.dec.decode_latent_into_processed_images(s_r_d, rows, out=out[a - t0:b - t0]),
+                               (t0, t1))
+        return (out, r_d) if return_rd else out
 
 
 def synth_conditions(cfg: FmtConfig, T, seed=0, dynamic_we=False, device="cpu"):

@@ -373,9 +373,13 @@ class InferenceAgent:
         that they are not held against the next clip.  FLOAT_AMD_VERIFY is NOT applied in a stream, and FLOAT_AMD_OVERLAP is ignored (the stream is
         windowed already, on one queue)."""
         self._check_stream_call("stream_device", slots, out_dtype, out_format)
-        return self._stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, int(slots))
 
-    def _check_stream_call(self, what, slots, out_dtype, out_format):
+        def _stream_device(c, noise):
+            return self.G.stream_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                         noise=noise, out_dtype=out_dtype, out_format=out_format, slots=int(slots))
+        return self._stream_clip("InferenceAgent.stream_device", s, a, emo, seed, _stream_device)
+
+    def _check_stream_call(self, what, slots, out_dtype=None, out_format=None):
         """What a stream refuses at the call, before its generator exists (a generator's body runs at the first next())."""
         if int(slots) < 2:
             raise ValueError("%s needs slots >= 2 (one block with the consumer, one in flight), got %r" % (what, slots))
@@ -383,18 +387,18 @@ class InferenceAgent:
         if self.G is not None:
             self.G.require_no_stream(what)
 
-    def _stream_device(self, s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots):
+    def _stream_clip(self, where, s, a, emo, seed, start):
+        """The generator behind every stream of the agent: the clip's inputs, the blocks of start(conditions, noise) - a
+        FloatHotPath stream - and FLOAT_AMD_RANGE once after the last of them."""
         c, noise = self._clip_inputs(s, a, emo, seed)
         done = False
         try:
-            yield from self.G.stream_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                             e_cfg_scale, noise=noise, out_dtype=out_dtype, out_format=out_format, slots=slots)
+            yield from start(c, noise)
             done = True
         finally:
             # left early: the inner generator has waited for its work; what the abandoned windows counted is not the next clip's
             if not done and self.G is not None and not self.G._open_stream and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
                 self.range_counts(reset=True)
-        where = "InferenceAgent.stream_device"
         if os.environ.get("FLOAT_AMD_RANGE", "warn").lower() == "auto":
             where += " (FLOAT_AMD_RANGE=auto acts as warn in a stream: the frames have been consumed and are not run again)"
         self.check_range(where)
@@ -435,29 +439,14 @@ class InferenceAgent:
         runs before the first next().  While the stream is open every other call that produces frames on this agent raises
         RuntimeError; close() (or dropping) the generator early leaves the agent usable.  After the last block FLOAT_AMD_RANGE is
         applied once, as in stream_device: warn, raise and off, and auto acts as warn.  FLOAT_AMD_VERIFY is NOT applied."""
-        if int(slots) < 2:
-            raise ValueError("stream_device_jpeg needs slots >= 2 (one block with the consumer, one in flight), got %r" % (slots,))
+        self._check_stream_call("stream_device_jpeg", slots)
         if not 1 <= int(quality) <= 100:
             raise ValueError("stream_device_jpeg: quality (%r) must be 1 ... 100" % (quality,))
-        if self.G is not None:
-            self.G.require_no_stream("stream_device_jpeg")
-        return self._stream_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, int(quality), restart, int(slots))
 
-    def _stream_device_jpeg(self, s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality, restart, slots):
-        c, noise = self._clip_inputs(s, a, emo, seed)
-        done = False
-        try:
-            yield from self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                             e_cfg_scale, noise=noise, quality=quality, restart=restart, slots=slots)
-            done = True
-        finally:
-            # left early: as in _stream_device, what the abandoned windows counted is not the next clip's
-            if not done and self.G is not None and not self.G._open_stream and os.environ.get("FLOAT_AMD_RANGE", "warn").lower() != "off":
-                self.range_counts(reset=True)
-        where = "InferenceAgent.stream_device_jpeg"
-        if os.environ.get("FLOAT_AMD_RANGE", "warn").lower() == "auto":
-            where += " (FLOAT_AMD_RANGE=auto acts as warn in a stream: the frames have been consumed and are not run again)"
-        self.check_range(where)
+        def _stream_device_jpeg(c, noise):
+            return self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                         noise=noise, quality=int(quality), restart=restart, slots=int(slots))
+        return self._stream_clip("InferenceAgent.stream_device_jpeg", s, a, emo, seed, _stream_device_jpeg)
 
     def write_video(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
                     quality=90, fps=None):

@@ -98,6 +98,29 @@ def test_u8_equals_rounded_fp32_512_without_the_epilogue(monkeypatch):
     _exact(dec, g["s_r"], g["r_d"], W.synth_feats(512, seed=g["seed"]))
 
 
+def test_u8_and_i420_into_a_callers_buffer():
+    """decode_u8 / decode_i420 with out=: 3 frames at 64 px in batches of 2 land in the caller's tensor, which is returned, bitwise
+    the call without it; a buffer of another shape, dtype or device, or a strided one, is refused before anything runs."""
+    g = golden("dec_64")
+    dec = pkg.decoder.SynthesisHIP(W.synth_decoder_state(64, seed=g["seed"]), 64, 512, "cuda:0", max_frames=2)
+    try:
+        dec.set_feats(W.synth_feats(64, seed=g["seed"]))
+        s_r, r_d = g["s_r"], g["r_d"]
+        for fn, shape in ((dec.decode_u8, (3, 64, 64, 3)), (dec.decode_i420, (3, 96, 64))):
+            want = fn(s_r, r_d)
+            assert tuple(want.shape) == shape
+            buf = torch.full(shape, 7, dtype=torch.uint8, device="cuda:0")
+            assert fn(s_r, r_d, out=buf) is buf and torch.equal(buf, want)
+            part = torch.full((5,) + shape[1:], 7, dtype=torch.uint8, device="cuda:0")  # a prefix view, as the stream ring passes
+            assert torch.equal(fn(s_r, r_d, out=part[:3]), want) and int(part[3:].min()) == int(part[3:].max()) == 7
+            for bad in (torch.empty((2,) + shape[1:], dtype=torch.uint8, device="cuda:0"), torch.empty(shape, device="cuda:0"),
+                        torch.empty(shape, dtype=torch.uint8), torch.empty((6,) + shape[1:], dtype=torch.uint8, device="cuda:0")[::2]):
+                with pytest.raises(ValueError):
+                    fn(s_r, r_d, out=bad)
+    finally:
+        dec.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. against the reference's frames
 # ---------------------------------------------------------------------------------------------------------------------------

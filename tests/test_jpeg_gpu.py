@@ -180,6 +180,7 @@ def _agent():
         _state["img"] = torch.from_numpy(np.random.RandomState(5).rand(1, 3, 64, 64).astype(np.float32)).cuda() * 2 - 1
         _state["wav35"] = W.synth_waveform(1.4, seed=9).cuda()   # 35 frames: one window
         _state["wav60"] = W.synth_waveform(2.4, seed=10).cuda()  # 60 frames: two windows, the second short
+        _state["wav185"] = W.synth_waveform(7.4, seed=10).cuda()  # 185 frames: four windows, the last short
     return _state["agent"]
 
 
@@ -230,6 +231,45 @@ def test_stream_blocks_are_the_whole_clip(slots):
         spans.append((blk.first, blk.last))
         got += [bytes(f) for f in blk.frames]
     assert spans == [(0, 50), (50, 60)] and got == want
+
+
+@pytest.mark.parametrize("slots", [2, 3])
+def test_jpeg_ring_is_bounded_and_no_slot_is_written_before_it_is_given_back(slots):
+    """The ring contract of tests/test_stream_gpu.py for the JPEG sink: 7.4 s = 185 frames = 4 windows (last block 35) through
+    `slots` slots - the smallest clip with more windows than slots and a short tail.  On receiving a block the whole device is
+    synchronised, so that everything the generator has enqueued ahead has landed, and only then are its files compared with the
+    same rows of infer_device_jpeg; exactly `slots` distinct pinned addresses, blocks k and k + slots share one."""
+    agent = _agent()
+    want = _whole("wav185")
+    assert len(want) == 185
+    ptrs, spans = [], []
+    for blk in agent.stream_device_jpeg(_state["img"], _state["wav185"], 2.0, 1.0, 1.0, emo="happy", seed=SEED, slots=slots):
+        torch.cuda.synchronize()
+        assert [bytes(f) for f in blk.frames] == want[blk.first:blk.last], (slots, blk.first)
+        ptrs.append(blk.frames.data.data_ptr())
+        spans.append((blk.first, blk.last))
+    assert spans == [(0, 50), (50, 100), (100, 150), (150, 185)]
+    assert len(set(ptrs)) == slots
+    assert all(ptrs[k] == ptrs[k + slots] for k in range(4 - slots))
+
+
+def test_stream_overflow_is_encoded_once_more(monkeypatch):
+    """Room for 1024 bytes per slot and per whole-clip call: every block of the stream takes "the files did not fit: once more,
+    with room", behind the windows already enqueued, and the whole-clip call takes its own second encode.  float_jpg_encode
+    reports exact offsets when nothing fits (test_capacity_rule), so both give the files of the roomy run - and so does a plain
+    call after the patch has gone."""
+    agent = _agent()
+    want = _whole("wav60")
+    args = (_state["img"], _state["wav60"], 2.0, 1.0, 1.0)
+    with monkeypatch.context() as m:
+        m.setattr(pkg.jpeg, "default_capacity", lambda *a: 1024)
+        got = []
+        for blk in agent.stream_device_jpeg(*args, emo="happy", seed=SEED, slots=2):
+            assert blk.frames.nbytes > 1024
+            got += [bytes(f) for f in blk.frames]
+        assert got == want
+        assert [bytes(f) for f in agent.infer_device_jpeg(*args, emo="happy", seed=SEED)] == want
+    assert [bytes(f) for f in agent.infer_device_jpeg(*args, emo="happy", seed=SEED)] == want
 
 
 def test_stream_left_early_and_one_stream_at_a_time():
