@@ -108,6 +108,22 @@ class AudioEncoderHIP:
         self._reserved = (max(cap[0], int(n_samples)), max(cap[1], frames))
 
     @torch.no_grad()
+    def attention_probe(self, qkv):
+        """Test hook (float_aud_debug): qkv (Tn, 3*hidden) = [q | k | v] -> (Tn, hidden), the attention launch of this handle
+        (operand type, FLOAT_AUD_ATTN_MFMA as read at create) on caller data: softmax(q k^T / 8) v per head of 64, no mask."""
+        D = self.cfg.hidden_size
+        if qkv.dim() != 2 or qkv.shape[0] < 1 or qkv.shape[1] != 3 * D:
+            raise ValueError("qkv must be (Tn >= 1, %d), got %s" % (3 * D, tuple(qkv.shape)))
+        qkv = qkv.to(self.device, torch.float32).contiguous()
+        Tn = int(qkv.shape[0])
+        self.reserve(400, Tn)  # 400 samples: the shortest clip the feature extractor takes; the hook only uses the frame buffers
+        out = torch.empty(Tn, D, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().float_aud_debug(self._h, 1, native.dev_ptr(qkv), Tn, native.dev_ptr(out),
+                                                      native.stream_ptr(self.device)))
+        return out
+
+    @torch.no_grad()
     def inference(self, a, seq_len):
         """AudioEncoder.inference (FLOAT.py:370-375): a (B,N) normalised 16 kHz waveform -> wa (B,seq_len,dim_w)."""
         a = a.to(self.device, torch.float32)

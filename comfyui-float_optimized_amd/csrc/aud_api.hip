@@ -304,6 +304,24 @@ int feature_len(const float_aud_cfg_t& c, int n_samples) {
   return (int)L;
 }
 
+// The attention launch of one layer: h->qkv16 (Tn, 3*D) = [q | k | v] -> h->att16, the packed operand of out_proj.  16-bit
+// operands: the matrix-pipe kernel (64 queries per workgroup, K / V shared); fp32 mode and FLOAT_AUD_ATTN_MFMA=0: one wave per
+// query.  The one place that dispatch is written: inference_impl and the test hook (float_aud_debug) both launch through it.
+template <class T>
+void launch_attn(float_aud* h, int Tn, hipStream_t st) {
+  typedef typename T::elem E;
+  const int D = h->D, heads = h->cfg.heads;
+  const bool mfma_on = h->tune.attn_mfma;
+  if constexpr (!T::is32) {
+    if (mfma_on)
+      hipLaunchKernelGGL((aud_attn_mfma_kernel<T>), dim3((Tn + 63) / 64, heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D,
+                         heads, reinterpret_cast<E*>(h->att16), h->sat);
+  }
+  if (T::is32 || !mfma_on)
+    hipLaunchKernelGGL((aud_attn_kernel<T>), dim3((Tn + 3) / 4, heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D, heads,
+                       reinterpret_cast<E*>(h->att16), h->sat);
+}
+
 // Tn: number of frames fed to the transformer: seq_len (interpolated, audio conditioning) or, Tn <= 0, the
 // extractor's own length (speech-emotion model, no interpolation).  wa: (Tn, dim_w) or scores: (num_labels).
 template <class T>
@@ -422,18 +440,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
       g.ldo16 = 3 * D;
       if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_T16, g, st))) return rc;
     }
-    {
-      // 16-bit operands: the matrix-pipe kernel (64 queries per workgroup, K / V shared); fp32 mode and FLOAT_AUD_ATTN_MFMA=0: one wave per query
-      const bool mfma_on = h->tune.attn_mfma;
-      if constexpr (!T::is32) {
-        if (mfma_on)
-          hipLaunchKernelGGL((aud_attn_mfma_kernel<T>), dim3((Tn + 63) / 64, c.heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D,
-                             c.heads, reinterpret_cast<E*>(h->att16), h->sat);
-      }
-      if (T::is32 || !mfma_on)
-        hipLaunchKernelGGL((aud_attn_kernel<T>), dim3((Tn + 3) / 4, c.heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D, c.heads,
-                         reinterpret_cast<E*>(h->att16), h->sat);
-    }
+    launch_attn<T>(h, Tn, st);
     {
       GemmArgs g = fmt_gemm_args(reinterpret_cast<const u16*>(h->att16), Ly.out, Tn);
       g.sat = h->sat;
@@ -493,6 +500,19 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
     n.silu = 1;
     if ((rc = launch_ln<T>(c.dim_w, n, st))) return rc;
   }
+  FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
+// float_aud_debug, what = 1: the attention launch of inference_impl on caller data (fp32 in, rounded to the operand type; the
+// packed result unpacked to fp32).  The conversion kernels are the FMT hook's.
+template <class T>
+int debug_attn_impl(float_aud* h, const float* in, int Tn, float* out, hipStream_t st) {
+  const int D = h->D;
+  const int n = Tn * 3 * D;  // < 2^31: Tn <= kAudMaxFrames (ensure_workspace)
+  hipLaunchKernelGGL((fmt_dbg_to16_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, st, reinterpret_cast<u16*>(h->qkv16), in, n);
+  launch_attn<T>(h, Tn, st);
+  hipLaunchKernelGGL((fmt_dbg_unpack_kernel<T>), dim3((Tn * D + 255) / 256), dim3(256), 0, st, out, reinterpret_cast<const u16*>(h->att16), Tn, D);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -589,6 +609,17 @@ int float_aud_inference(float_aud_t* h, const float* a, int32_t n_samples, int32
   if (h->cfg.dtype == FLOAT_DT_FP32) return inference_impl<FP32>(h, a, n_samples, seq_len, wa, st);
   return h->cfg.dtype == FLOAT_DT_BF16 ? inference_impl<BF16>(h, a, n_samples, seq_len, wa, st)
                                        : inference_impl<FP16>(h, a, n_samples, seq_len, wa, st);
+}
+
+int float_aud_debug(float_aud_t* h, int32_t what, const float* in, int32_t Tn, float* out, void* stream) {
+  FH_REQUIRE(h && in && out, "null argument to float_aud_debug");
+  FH_REQUIRE(what == 1, "float_aud_debug: unknown request %d", what);
+  FH_REQUIRE(Tn >= 1, "float_aud_debug: Tn must be >= 1 (got %d)", Tn);
+  FH_REQUIRE(Tn <= h->cap_T, "float_aud_debug: %d frames exceed the reserved workspace (%d frames): call float_aud_reserve first "
+             "(run-time calls do not allocate)", Tn, h->cap_T);
+  hipStream_t st = (hipStream_t)stream;
+  if (h->cfg.dtype == FLOAT_DT_FP32) return debug_attn_impl<FP32>(h, in, Tn, out, st);
+  return h->cfg.dtype == FLOAT_DT_BF16 ? debug_attn_impl<BF16>(h, in, Tn, out, st) : debug_attn_impl<FP16>(h, in, Tn, out, st);
 }
 
 }  // extern "C"

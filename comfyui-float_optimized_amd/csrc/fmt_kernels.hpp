@@ -1513,19 +1513,7 @@ __global__ void fmt_scatter_trim_kernel(const FmtClipTab<float*> dst, const floa
   dst.p[q][(size_t)(t0 + i) * dim + c] = src[(size_t)q * n * dim + r];
 }
 
-// Test hook (float_fmt_debug): fp32 rows -> the row-major 16-bit q|k|v operand of fmt_attn_kernel, and its packed output back.
-template <class T>
-__global__ void fmt_dbg_to16_kernel(u16* __restrict__ dst, const float* __restrict__ src, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) reinterpret_cast<typename T::elem*>(dst)[i] = T::from_float(src[i]);
-}
-template <class T>
-__global__ void fmt_dbg_unpack_kernel(float* __restrict__ dst, const u16* __restrict__ src, int rows, int D) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * D) return;
-  const int r = i / D, c = i - r * D;
-  dst[i] = T::to_float(reinterpret_cast<const typename T::elem*>(src)[fmt_pack_off(r, c, D / 32)]);
-}
+// (the test hook's conversion kernels fmt_dbg_to16_kernel / fmt_dbg_unpack_kernel live in fmt_pack.hpp: the audio hook shares them)
 
 // Device-side copies / fills of the sampling calls.  Kernels, not hipMemcpyAsync / hipMemsetAsync: when the caller captures the
 // stream those become memcpy / memset NODES, and replays of such a graph were not reproducible on ROCm 7.2 (the r_d copy of

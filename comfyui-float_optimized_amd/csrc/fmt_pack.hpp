@@ -21,6 +21,21 @@ __host__ __device__ __forceinline__ size_t fmt_pack_off(int row, int k, int KB) 
   return ((size_t)((row >> 4) * KB + (k >> 5)) * 64 + (row & 15) + 16 * ((k >> 3) & 3)) * 8 + (k & 7);
 }
 
+// Test hooks (float_fmt_debug, float_aud_debug): fp32 rows -> the row-major q|k|v operand of an attention kernel in the operand
+// type, and its packed output (the A operand of the projection GEMM, KB = D / 32) back to fp32 rows.
+template <class T>
+__global__ void fmt_dbg_to16_kernel(u16* __restrict__ dst, const float* __restrict__ src, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) reinterpret_cast<typename T::elem*>(dst)[i] = T::from_float(src[i]);
+}
+template <class T>
+__global__ void fmt_dbg_unpack_kernel(float* __restrict__ dst, const u16* __restrict__ src, int rows, int D) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * D) return;
+  const int r = i / D, c = i - r * D;
+  dst[i] = T::to_float(reinterpret_cast<const typename T::elem*>(src)[fmt_pack_off(r, c, D / 32)]);
+}
+
 // Weights of a LATER GEMM of the chain, touched one dword per 128-byte line by the workgroups of a kernel that runs
 // before it, so that the GEMM finds them in its XCD's L2 (clean L2 lines survive a kernel boundary; r01: LayerNorm touching
 // qkv / fc1 took the chain from 91.3 to 88.4 ms).  Mirrors fmt_gemm_kernel's block decode: column block bx (nt 16-column

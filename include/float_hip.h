@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
+/* Stays 6: float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
  * float_img_front / float_img_front_work_bytes (the image front end on the device),
  * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
  * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
@@ -441,6 +441,13 @@ int float_aud_inference(float_aud_t* h, const float* a, int32_t n_samples, int32
  * keys `wav2vec2.*`, `classifier.dense.*`, `classifier.out_proj.*` (prefix `emotion_encoder.wav2vec2_for_emotion.`
  * stripped).  scores: (num_labels) fp32 device. */
 int float_aud_classify(float_aud_t* h, const float* a, int32_t n_samples, float* scores, void* stream);
+
+/* Test hook for one stage of the encoder on caller data (additive: the ABI version does not change).
+ *   what = 1: the attention launch exactly as float_aud_inference / float_aud_classify dispatch it for this handle (by operand
+ *             type and by FLOAT_AUD_ATTN_MFMA as read at create): in (Tn, 3 * hidden) = [q | k | v] rows, rounded to the
+ *             operand type; out (Tn, hidden) = softmax(q k^T / 8) v per head of 64, no mask, as the handle stores it.
+ * in / out are fp32 device pointers.  Allocation-free: Tn beyond the reserved frames is refused - call float_aud_reserve first. */
+int float_aud_debug(float_aud_t* h, int32_t what, const float* in, int32_t Tn, float* out, void* stream);
 
 /* ---------------------------------------------------------------- misc ------------ */
 int float_hip_abi_version(void);

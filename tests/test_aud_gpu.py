@@ -52,6 +52,47 @@ def test_audio_live_oracle_lengths_and_determinism():
     assert rel_l2(enc2.inference(a, 25).cpu(), O.audio_encoder_inference(sd2, cfg2, a, 25)) < TOL["fp16"]
 
 
+def test_fp32_mode_past_one_key_tile():
+    """The verification mode (fp32 handles run aud_attn_kernel, 2048-key tiles) on 2100 frames = 84 s: the second key tile and
+    its online-softmax rescale, against the fp32 oracle at the fp32 limit of the goldens."""
+    cfg = C.small_audio_config()
+    sd = W.synth_audio_state(cfg, seed=24)
+    enc = pkg.audio.AudioEncoderHIP(sd, cfg, "cuda:0", "fp32")
+    a = W.synth_waveform(84.0, seed=11)
+    wa = enc.inference(a, 2100).cpu()
+    e = rel_l2(wa, O.audio_encoder_inference(sd, cfg, a, 2100))
+    print("fp32 mode, 2100 frames: wa rel-L2 %.3e" % e)
+    assert wa.shape == (1, 2100, cfg.dim_w) and e < TOL["fp32"]
+    assert enc.saturation() == 0
+
+
+def test_bf16_several_key_tiles_and_row_blocks():
+    """bf16 beyond one 64-key tile of the matrix-pipe attention (the goldens stop at 50 frames): 300 frames, 5 tiles."""
+    cfg = C.small_audio_config()
+    sd = W.synth_audio_state(cfg, seed=25)
+    enc = pkg.audio.AudioEncoderHIP(sd, cfg, "cuda:0", "bf16")
+    a = W.synth_waveform(12.0, seed=12)
+    wa = enc.inference(a, 300).cpu()
+    e = rel_l2(wa, O.audio_encoder_inference(sd, cfg, a, 300))
+    print("bf16, 300 frames: wa rel-L2 %.3e" % e)
+    assert wa.shape == (1, 300, cfg.dim_w) and e < TOL["bf16"]
+    assert enc.saturation() == 0
+
+
+def test_fp16_one_wave_attention_route(monkeypatch):
+    """FLOAT_AUD_ATTN_MFMA=0 (read at create): the one-wave-per-query attention kernel under 16-bit operands, 78 frames."""
+    monkeypatch.setenv("FLOAT_AUD_ATTN_MFMA", "0")
+    cfg = C.small_audio_config()
+    sd = W.synth_audio_state(cfg, seed=26)
+    enc = pkg.audio.AudioEncoderHIP(sd, cfg, "cuda:0", "fp16")
+    a = W.synth_waveform(3.1, seed=13)
+    wa = enc.inference(a, 78).cpu()
+    e = rel_l2(wa, O.audio_encoder_inference(sd, cfg, a, 78))
+    print("fp16, FLOAT_AUD_ATTN_MFMA=0, 78 frames: wa rel-L2 %.3e" % e)
+    assert wa.shape == (1, 78, cfg.dim_w) and e < TOL["fp16"]
+    assert enc.saturation() == 0
+
+
 def test_audio_weight_norm_key_variants_and_errors():
     cfg = C.small_audio_config()
     sd = W.synth_audio_state(cfg, seed=23)

@@ -1,4 +1,5 @@
 """Shared test helpers: load the hyphen-named package by path, locate fixtures."""
+import functools
 import importlib.util
 import os
 import sys
@@ -79,6 +80,101 @@ def sample_inputs(cfg, seed, T, dynamic, noise_seed=15):
     g.manual_seed(int(noise_seed))
     noise = torch.stack([torch.randn(1, L, cfg.dim_w, generator=g) for _ in range(n_chunks)])
     return dict(wa=wa, r_s=r_s, we=we, noise=noise)
+
+
+# ---- attention unit tests (tests/test_aud_attn.py, tests/test_aud_attn_gpu.py, tests/test_fmt_tables.py) ----
+TORCH_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}
+# (Tn, heads) of the audio attention cases: a single frame; a partial 16-key sub-tile and the clamped loads; a one-key second
+# 64-key tile; the production pack stride D / 32 = 24 (hidden 768); several tiles; the second 2048-key tile of the one-wave
+# kernel = the 33rd and 34th tile of the matrix-pipe kernel
+AUD_ATTN_CASES = [(1, 4), (17, 4), (65, 4), (130, 12), (300, 4), (2049, 4), (2120, 4)]
+# 16-bit limits against attention_fp64 of the rounded inputs: at most two roundings of half-ulp size (P where the matrix pipe
+# takes it, and the output).  max|d| <= 2 * (ulp / 2) * max|v|: 2^-10 (fp16), 2^-7 (bf16) times max|v|.  Each rounding has an
+# rms of 2^-11 / sqrt(3) (2^-8 / sqrt(3)) relative, and two add in quadrature: rel-L2 <= 2^-11 (2^-8).
+ATTN_LIMITS = {"fp16": (2.0 ** -10, 2.0 ** -11), "bf16": (2.0 ** -7, 2.0 ** -8)}  # (max|d| / max|v|, rel-L2)
+
+
+def attn_structural_keys(Tn):
+    s = {0, 15, 16, 31, 32, 47, 48, 63, 64, 2047, 2048, 64 * ((Tn - 1) // 64), Tn - 2, Tn - 1}
+    return sorted(j for j in s if 0 <= j < Tn)
+
+
+def peaked_qkv(Tn, heads, head_dim, seed, dtype, pairs=None):
+    """Peaked attention inputs: q, k = 2 * N(0,1), v = N(0,1), each (Tn, heads, head_dim) fp32 (logits are N(0, 16)); then key j of
+    every pair (i, j[, logit = 24]) is planted on query i in every head: k[j] = q[i] * logit * sqrt(head_dim) / |q[i]|^2, which
+    makes logit(i, j) = `logit`.  pairs = None: the n-th structural key (tile and sub-tile edges, attn_structural_keys) goes to
+    query (37 n + 5) % Tn.  All three tensors are then rounded to the operand type `dtype` ("fp16" | "bf16" | "fp32"), so input
+    rounding is part of no error.  Returns (q, k, v, [(i, j), ...])."""
+    shape = (Tn, heads, head_dim)
+    q, k, v = 2 * seeded_normal(seed, *shape), 2 * seeded_normal(seed + 1, *shape), seeded_normal(seed + 2, *shape)
+    if pairs is None:
+        pairs = [((37 * n + 5) % Tn, j) for n, j in enumerate(attn_structural_keys(Tn))]
+    assert len({p[1] for p in pairs}) == len(pairs), "a key can be planted on one query only"
+    for p in pairs:
+        i, j, logit = p[0], p[1], (p[2] if len(p) > 2 else 24.0)
+        k[j] = q[i] * (logit * head_dim ** 0.5 / (q[i] * q[i]).sum(-1, keepdim=True))
+    td = TORCH_DTYPE[dtype]
+    q, k, v = (t.to(td).float() for t in (q, k, v))
+    return q, k, v, [(p[0], p[1]) for p in pairs]
+
+
+def qkv_rows(q, k, v):
+    """(Tn, heads, head_dim) x 3 -> the (Tn, 3 * hidden) = [q | k | v] rows the attention hooks take."""
+    return torch.cat([t.reshape(t.shape[0], -1) for t in (q, k, v)], dim=1).contiguous()
+
+
+def attention_probs(q, k, mask=None, dtype=torch.float64):
+    """softmax(q k^T / sqrt(head_dim)) per head, (heads, Tn, Tn), in `dtype`; mask (Tn, Tn) bool, True = blocked."""
+    q, k = q.to(dtype).transpose(0, 1), k.to(dtype).transpose(0, 1)
+    s = q @ k.transpose(1, 2) * (q.shape[-1] ** -0.5)
+    if mask is not None:
+        s = s.masked_fill(mask[None], float("-inf"))
+    return torch.softmax(s, dim=-1)
+
+
+def attention_fp64(q, k, v, mask=None, dtype=torch.float64):
+    """The plain softmax attention in float64 (`dtype` = torch.float32: the same formula in fp32, for the fp32 limit):
+    (Tn, heads, head_dim) inputs -> (Tn, heads * head_dim)."""
+    o = attention_probs(q, k, mask, dtype) @ v.to(dtype).transpose(0, 1)
+    return o.transpose(0, 1).reshape(q.shape[0], -1)
+
+
+@functools.lru_cache(maxsize=None)
+def aud_attn_case(Tn, heads, dtype):
+    """One audio attention case, made once per process and shared (read-only) by the CPU and the GPU tests: inputs of
+    peaked_qkv (head_dim 64, seed 7000 + Tn), their fp64 reference, the smallest fp64 weight of a planted pair over all heads
+    and e32 = max|d| of the same formula evaluated by torch in fp32 (what the fp32 limit is made from)."""
+    q, k, v, pairs = peaked_qkv(Tn, heads, 64, 7000 + Tn, dtype)
+    p = attention_probs(q, k)
+    ref = (p @ v.double().transpose(0, 1)).transpose(0, 1).reshape(Tn, -1)
+    wmin = min(float(p[:, i, j].min()) for i, j in pairs)
+    return {"q": q, "k": k, "v": v, "pairs": pairs, "ref": ref, "vmax": float(v.abs().max()), "pair_weight": wmin,
+            "e32": max_abs(attention_fp64(q, k, v, dtype=torch.float32), ref)}
+
+
+def attention_16bit_model(q, k, v, dtype, tile=64, drop=(), rescale=True):
+    """The matrix-pipe kernel's rounding, modelled in torch - NOT the code under test; it shows that ATTN_LIMITS belong to the
+    arithmetic.  fp32 logits; running max and sum over `tile`-key tiles; P rounded to `dtype` before the PV product (its fp32
+    values go into the sum); fp32 sums; the result rounded to `dtype`.  Defects for the tests of the limits themselves: keys in
+    `drop` are never seen; rescale = False leaves accumulator and sum alone when a tile raises the max."""
+    td = TORCH_DTYPE[dtype]
+    Tn, hd = q.shape[0], q.shape[-1]
+    qh, kh, vh = (t.float().transpose(0, 1) for t in (q, k, v))
+    s = qh @ kh.transpose(1, 2) * (hd ** -0.5)
+    for j in drop:
+        s[:, :, j] = float("-inf")
+    m = torch.full(s.shape[:2] + (1,), float("-inf"))
+    l, acc = torch.zeros_like(m), torch.zeros_like(qh)
+    for j0 in range(0, Tn, tile):
+        st = s[:, :, j0:j0 + tile]
+        mn = torch.maximum(m, st.max(dim=-1, keepdim=True).values)
+        live = torch.isfinite(mn)  # a tile whose every key was dropped, in front of any other
+        p = torch.where(live, torch.exp(st - torch.where(live, mn, torch.zeros_like(mn))), torch.zeros_like(st))
+        alpha = torch.where(live & torch.isfinite(m), torch.exp(m - mn), torch.zeros_like(m)) if rescale else torch.ones_like(m)
+        l = l * alpha + p.sum(dim=-1, keepdim=True)
+        acc = acc * alpha + p.to(td).float() @ vh[:, j0:j0 + tile]
+        m = mn
+    return (acc / l).to(td).float().transpose(0, 1).reshape(Tn, -1)
 
 
 # ---- decoder geometry cases (tests/test_dec_geometry_gpu.py; their conditioning is pinned by tests/test_oracle_golden.py) ----
