@@ -9,6 +9,8 @@ this package).  What is left is tensor plumbing:
   * the one-hot emotion vector of a named emotion (FLOAT.py:196-200)
   * the image front end in exact arithmetic (hex_to_rgb8, image_to_rgb8, resize_rgb8): the definition the kernels of
     `float_img_front` (image.py in this package) are held to bit for bit
+  * the paste of the generated frames back into the source portrait (paste_alpha, paste_rgb8): the definition the kernel of
+    `float_img_paste` is held to bit for bit
   * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
     writer for handing such frames to an encoder
   * baseline JPEG in integer arithmetic (jpeg_tables, jpeg_header, jpeg_encode_rgb8: the definition the kernels of
@@ -176,6 +178,65 @@ def resize_rgb8(rgb8, rect=None, dst_h=None, dst_w=None, scale=None):
 def rgb8_to_model_input(q):
     """(H, W, 3) uint8 -> (1, 3, H, W) fp32 in [-1, 1]: q / 127.5 - 1.0 in fp32 (CustomTransform, generate.py:36-38)."""
     return (q.float() / 127.5 - 1.0).permute(2, 0, 1)[None].contiguous()
+
+
+def default_feather(rect):
+    """The feather a caller gets who passes None: rect_w // 16 source pixels.  A visual choice, not a measurement - there is no
+    checkpoint here to judge a seam on."""
+    return max(0, int(rect[2]) // 16)
+
+
+def paste_alpha(H, W, rect, feather):
+    """(h, w) int64: the weight 0 ... 255 of the generated face in every cell of the box `rect` = (x0, y0, w, h) over an H x W
+    image.  d = the cell's distance to the nearest OPEN side of the box (u, w - 1 - u, v, h - 1 - v); a side is open only where
+    the box edge lies strictly inside the image (x0 > 0, x0 + w < W, y0 > 0, y0 + h < H) - a side on or beyond the image's edge
+    does not feather, so no static rim of the source sits at the picture's border and rect = whole image is a plain resize.
+    a = min(255, 255 (d + 1) // (feather + 1)); no open side or feather == 0 gives 255."""
+    x0, y0, w, h = (int(v) for v in rect)
+    f = int(feather)
+    big = 1 << 30
+
+    def axis(n, lo_open, hi_open):
+        u = torch.arange(n, dtype=torch.int64)
+        return torch.minimum(u if lo_open else torch.full_like(u, big), (n - 1 - u) if hi_open else torch.full_like(u, big))
+
+    d = torch.minimum(axis(h, y0 > 0, y0 + h < H)[:, None], axis(w, x0 > 0, x0 + w < W)[None, :])
+    return torch.clamp((255 * (d + 1)) // (f + 1), max=255)
+
+
+def paste_rgb8(src8, frames8, rect, feather):
+    """The generated frames back in the source portrait: src8 (H, W, 3) uint8, frames8 (T, h_f, w_f, 3) uint8, rect = (x0, y0, w,
+    h) in source coordinates (it may reach outside the image or miss it), feather >= 0 in source pixels -> (T, H, W, 3) uint8.
+      outside rect & image   out[t] = src8
+      inside                 face = resize_rgb8(frames8[t], None, h, w) - the rule of the image front end unchanged, already
+                             rounded to 8 bits - and out = (a face + (255 - a) src + 127) // 255 with a = paste_alpha (255 is odd:
+                             no ties, this is round-to-nearest).
+    The parts of the generated frame that map outside the image are discarded: they are the zero border the model was shown.
+    Integer arithmetic in torch on the CPU; the definition `float_img_paste` (image.paste_frames_device) is held to bit for
+    bit, as resize_rgb8 is for the front end."""
+    if src8.dtype != torch.uint8 or src8.dim() != 3 or src8.shape[-1] != 3:
+        raise ValueError("paste_rgb8 takes an (H, W, 3) uint8 source, got %s %s" % (src8.dtype, tuple(src8.shape)))
+    if frames8.dtype != torch.uint8 or frames8.dim() != 4 or frames8.shape[-1] != 3 or 0 in frames8.shape:
+        raise ValueError("paste_rgb8 takes (T, h, w, 3) uint8 frames, got %s %s" % (frames8.dtype, tuple(frames8.shape)))
+    if len(rect) != 4:
+        raise ValueError("paste_rgb8: rect must be (x0, y0, w, h), got %r" % (rect,))
+    x0, y0, w, h = (int(v) for v in rect)
+    f = int(feather)
+    if w < 1 or h < 1 or f < 0 or src8.shape[0] < 1 or src8.shape[1] < 1:
+        raise ValueError("paste_rgb8: box %d x %d and source %d x %d must be at least 1 x 1, feather (%d) >= 0"
+                         % (h, w, src8.shape[0], src8.shape[1], f))
+    H, W = int(src8.shape[0]), int(src8.shape[1])
+    src8, frames8 = src8.cpu(), frames8.cpu()
+    out = src8[None].repeat(frames8.shape[0], 1, 1, 1)
+    ya, yb, xa, xb = max(0, y0), min(H, y0 + h), max(0, x0), min(W, x0 + w)
+    if yb <= ya or xb <= xa:
+        return out
+    a = paste_alpha(H, W, (x0, y0, w, h), f)[ya - y0:yb - y0, xa - x0:xb - x0, None]
+    s = src8[ya:yb, xa:xb].to(torch.int64)
+    for t in range(frames8.shape[0]):
+        face = resize_rgb8(frames8[t], None, h, w)[ya - y0:yb - y0, xa - x0:xb - x0].to(torch.int64)
+        out[t, ya:yb, xa:xb] = ((a * face + (255 - a) * s + 127) // 255).to(torch.uint8)
+    return out
 
 
 def resample_sinc(w, orig_rate, new_rate, zeros=24, rolloff=0.945):

@@ -100,3 +100,70 @@ def detector_view_device(img, view_h=360, rgba_conversion="blend_with_color", bk
     vh, vw = detector_view_size(H, W, view_h)
     g = math.gcd(H, vh)
     return image_front_device(x, vh, vw, None, (H // g, vh // g), rgba_conversion, bkg_color_hex, True, device)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the step after the decoder: the generated frames back in the source portrait (`float_img_paste`, include/float_hip.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+JPEG_SIDE_MULTIPLE = 16  # float_jpg_encode codes frames whose sides are multiples of 16
+
+
+def source_rgb8_device(img, rgba_conversion="blend_with_color", bkg_color_hex="#000000", device=None):
+    """A ComfyUI IMAGE item as the (H, W, 3) uint8 portrait on the device that the frames are pasted into: bitwise
+    host_models.image_to_rgb8(img, rgba_conversion, hex_to_rgb8(bkg_color_hex)).  Inside float_img_front's limits it is the
+    identity-scale call of image_front_device(out_u8=True) - the quantiser and the RGBA conversion alone; beyond them (a side
+    above 4096, that operator's destination limit) it is the host definition and one upload."""
+    x = img[0] if img.dim() == 4 and img.shape[0] == 1 else img
+    if x.dim() != 3 or x.shape[-1] not in (3, 4) or not x.is_floating_point():
+        raise ValueError("source_rgb8_device: expected an (H, W, 3) or (H, W, 4) float image, got %s %s" % (img.dtype, tuple(img.shape)))
+    H, W = int(x.shape[0]), int(x.shape[1])
+    if native.lib().float_img_front_work_bytes(H, W, H, W):
+        return image_front_device(x, H, W, None, None, rgba_conversion, bkg_color_hex, True, device)
+    device = torch.device(device if device is not None else (x.device if x.is_cuda else "cuda:0"))
+    return host_models.image_to_rgb8(x, rgba_conversion, host_models.hex_to_rgb8(bkg_color_hex)).to(device, non_blocking=True)
+
+
+def _u8_device(t, what, dims, device):
+    if t.dtype != torch.uint8 or t.dim() != dims or t.shape[-1] != 3 or 0 in t.shape:
+        raise ValueError("paste_frames_device: %s must be %s uint8, got %s %s"
+                         % (what, "(H, W, 3)" if dims == 3 else "(T, h, w, 3)", t.dtype, tuple(t.shape)))
+    return t.detach().to(device, non_blocking=True).contiguous()
+
+
+@torch.no_grad()
+def paste_frames_device(src8, frames8, rect, feather=None, out=None):
+    """float_img_paste: frames8 (T, h, w, 3) uint8 - what the decoder's decode_u8 leaves in HBM - back in the portrait src8 (H, W,
+    3) uint8 at the box rect = (x0, y0, w, h) in source coordinates (what InferenceAgent.host_inputs_placed returns; it may reach
+    outside the image) -> (T, H, W, 3) uint8 on the device, bitwise host_models.paste_rgb8(src8, frames8, rect, feather).
+    feather: the width in source pixels over which the box's open sides fade into the portrait; None = rect_w // 16
+    (host_models.default_feather: a visual choice, not a measurement).  Host tensors are uploaded; the device is that of frames8,
+    else of src8, else cuda:0.  out: a contiguous (T, H, W, 3) uint8 tensor on that device to write into.  One launch on the
+    current stream; nothing is allocated besides `out`, nothing synchronises."""
+    device = frames8.device if frames8.is_cuda else (src8.device if src8.is_cuda else torch.device("cuda:0"))
+    s = _u8_device(src8, "src8", 3, device)
+    f = _u8_device(frames8, "frames8", 4, device)
+    if len(rect) != 4:
+        raise ValueError("paste_frames_device: rect must be (x0, y0, w, h), got %r" % (rect,))
+    x0, y0, w, h = (int(v) for v in rect)
+    if max(abs(x0), abs(y0)) > 1 << 30 or not (0 < w <= 1 << 30 and 0 < h <= 1 << 30):
+        raise ValueError("paste_frames_device: rect %r is outside float_img_paste's limits" % (tuple(rect),))
+    feather = host_models.default_feather((x0, y0, w, h)) if feather is None else int(feather)
+    if not 0 <= feather <= 1 << 30:
+        raise ValueError("paste_frames_device: feather (%d) must be 0 ... 16384" % feather)
+    T, H, W = int(f.shape[0]), int(s.shape[0]), int(s.shape[1])
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != (T, H, W, 3) or out.device != device or not out.is_contiguous()):
+            raise ValueError("paste_frames_device: out must be a contiguous (%d, %d, %d, 3) uint8 tensor on %s, got %s %s on %s"
+                             % (T, H, W, device, out.dtype, tuple(out.shape), out.device))
+        native.check(native.lib().float_img_paste(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
+                                                  x0, y0, w, h, feather, C.c_void_p(out.data_ptr()), native.stream_ptr(device)))
+    return out
+
+
+def require_jpeg_sides(what, H, W):
+    """float_jpg_encode takes frames whose sides are multiples of 16; a pasted clip has the portrait's size.  Nothing is padded."""
+    if H % JPEG_SIDE_MULTIPLE or W % JPEG_SIDE_MULTIPLE:
+        raise ValueError("%s: a %d x %d portrait cannot leave as JPEG - float_jpg_encode needs sides that are multiples of 16 "
+                         "(crop or resize the portrait, or take the frames with infer_pasted)" % (what, H, W))

@@ -139,6 +139,7 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_img_front_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_img_front": (C.c_int, [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "float_img_paste": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]),
     "float_jpg_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_jpg_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }

@@ -9,7 +9,7 @@ import warnings
 
 import torch
 
-from . import jpeg, native
+from . import image, jpeg, native
 from .config import FmtConfig
 from .decoder import SynthesisHIP, infer_out_format
 from .fmt import FlowMatchingTransformerHIP, WindowSampler, draw_noise
@@ -194,6 +194,27 @@ class JpegBlock(collections.namedtuple("JpegBlock", "first last frames")):
     __slots__ = ()
 
 
+class Placement(collections.namedtuple("Placement", "src8 rect")):
+    """Where the generated frames belong in the user's portrait (InferenceAgent.host_inputs_placed): `src8` the (H, W, 3) uint8
+    portrait on the device (image.source_rgb8_device), `rect` = (x0, y0, w, h) the box of the crop in its coordinates - it may
+    reach outside the image.  What the *_pasted producers and the `place` argument of the JPEG producers take."""
+    __slots__ = ()
+
+    @property
+    def size(self):
+        """(H, W) of the pasted frames"""
+        return int(self.src8.shape[0]), int(self.src8.shape[1])
+
+
+def _check_place(what, place, device):
+    s = getattr(place, "src8", None)
+    if not isinstance(place, Placement) or not isinstance(s, torch.Tensor) or s.dtype != torch.uint8 or s.dim() != 3 or s.shape[-1] != 3 \
+            or s.device != device or not s.is_contiguous() or len(place.rect) != 4:
+        raise ValueError("%s: place must be a Placement of a contiguous (H, W, 3) uint8 portrait on %s and a rect (x0, y0, w, h)"
+                         % (what, device))
+    return place
+
+
 class _FrameSink:
     """What FloatHotPath._ring does per slot for stream_to_host: a slot is a pinned (L,) + frame_shape buffer, and the one device
     staging buffer is shared by all of them (safe in stream order)."""
@@ -216,21 +237,49 @@ class _FrameSink:
         return FrameBlock(f0, f1, slot[:f1 - f0])
 
 
+class _PasteSink:
+    """What FloatHotPath._ring does per slot for stream_to_host_pasted: a slot is a pinned (L, H, W, 3) uint8 buffer of pasted
+    frames; the device buffers of L 8-bit crops and of L pasted frames are shared by all of them (safe in stream order)."""
+    name = "stream_to_host_pasted"
+
+    def __init__(self, hot, place, feather):
+        self.hot, self.place, self.feather = hot, place, feather
+
+    def open(self, slots):
+        dev, L, R, (H, W) = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size, self.place.size
+        ring = [torch.empty(L, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+        self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev)
+        self.pasted = torch.empty(L, H, W, 3, dtype=torch.uint8, device=dev)
+        return ring
+
+    def enqueue(self, slot, s_r_d, rows):
+        n = rows.shape[0]
+        self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
+        image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n])
+        slot[:n].copy_(self.pasted[:n], non_blocking=True)
+
+    def block(self, slot, f0, f1, ev, st):
+        return FrameBlock(f0, f1, slot[:f1 - f0])
+
+
 class _JpegSink:
     """What FloatHotPath._ring does per slot for stream_to_jpeg: a slot holds the 8-bit frames of a window on the device, the
-    files and their offsets on both sides; the copy stream and the encoder's scratch are shared."""
+    files and their offsets on both sides; the copy stream and the encoder's scratch are shared.  With `place` the slot's frames
+    are the pasted H x W ones, and the window's 8-bit crops go through one shared device buffer."""
     name = "stream_to_jpeg"
 
-    def __init__(self, hot, quality, restart):
-        self.hot, self.quality, self.restart = hot, quality, restart
+    def __init__(self, hot, quality, restart, place=None, feather=None):
+        self.hot, self.quality, self.restart, self.place, self.feather = hot, quality, restart, place, feather
 
     def open(self, slots):
         dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
-        cap = jpeg.default_capacity(L, R, R)
-        ring = [dict(u8=torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
+        H, W = self.place.size if self.place is not None else (R, R)
+        cap = jpeg.default_capacity(L, H, W)
+        ring = [dict(u8=torch.empty(L, H, W, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
                      off=torch.empty(L + 1, dtype=torch.int64, device=dev), host=torch.empty(cap, dtype=torch.uint8, pin_memory=True),
                      off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True)) for _ in range(slots)]
         self.s_copy, self.work = torch.cuda.Stream(dev), None
+        self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev) if self.place is not None else None
         return ring
 
     def _encode(self, slot, n):
@@ -238,7 +287,11 @@ class _JpegSink:
 
     def enqueue(self, slot, s_r_d, rows):
         n = rows.shape[0]
-        self.hot.dec.decode_u8(s_r_d, rows, out=slot["u8"][:n])
+        if self.place is None:
+            self.hot.dec.decode_u8(s_r_d, rows, out=slot["u8"][:n])
+        else:
+            self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
+            image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=slot["u8"][:n])
         self._encode(slot, n)
         slot["off_host"][:n + 1].copy_(slot["off"][:n + 1], non_blocking=True)
 
@@ -494,6 +547,49 @@ class FloatHotPath:
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
+    def stream_to_host_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
+                              noise=None, place=None, feather=None, slots=3):
+        """stream_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: a generator of
+        FrameBlock(first, last, frames), `frames` a (last - first, H, W, 3) uint8 view of a pinned ring slot, bitwise
+        host_models.paste_rgb8(place.src8, the window's 8-bit crops, place.rect, feather).  place: a Placement (the portrait on
+        this device and the box); feather: source pixels, None = rect_w // 16 (host_models.default_feather).  Per window:
+        the chain, decode_u8 into a shared device buffer of 50 crops, float_img_paste into a shared device buffer of 50 pasted
+        frames, one non-blocking copy into the slot.  The ring rules, lifetime and early exit are stream_to_host's; pinned memory
+        is slots x 50 x H x W x 3 bytes (940 MB at 1920 x 1088 and 3 slots)."""
+        place = _check_place("stream_to_host_pasted", place, self.device)
+        sink = _PasteSink(self, place, feather)
+        self._check_stream_call(sink.name, slots, wa)
+        return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
+
+    @torch.no_grad()
+    def generate_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
+                        place=None, feather=None, out=None, return_rd=False):
+        """generate_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: the chain of the
+        whole clip, then per group of num_frames_for_clip frames decode_u8, float_img_paste and one non-blocking copy into the
+        pinned (T, H, W, 3) uint8 result - device memory stays at 50 crops and 50 pasted frames whatever T is.  The result is
+        complete once the current stream has been synchronised (the callers that hand it to the user do that)."""
+        place = _check_place("generate_pasted", place, self.device)
+        self.require_no_stream("generate_pasted")
+        if feats is not None:
+            self.dec.set_feats(feats)
+        r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
+        rd = _rows(r_d)
+        T, L, R, (H, W) = rd.shape[0], self.cfg.num_frames_for_clip, self.size, place.size
+        if out is None:
+            out = torch.empty(T, H, W, 3, dtype=torch.uint8, pin_memory=True)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (T, H, W, 3) or out.is_cuda or not out.is_contiguous():
+            raise ValueError("generate_pasted: out must be a contiguous CPU uint8 tensor of shape %s" % ((T, H, W, 3),))
+        s_r_d = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
+        with torch.cuda.device(self.device):
+            crops = torch.empty(min(T, L), R, R, 3, dtype=torch.uint8, device=self.device)
+            pasted = torch.empty(min(T, L), H, W, 3, dtype=torch.uint8, device=self.device)
+            for f0 in range(0, T, L):
+                n = min(L, T - f0)
+                self.dec.decode_u8(s_r_d, rd[f0:f0 + n], out=crops[:n])
+                image.paste_frames_device(place.src8, crops[:n], place.rect, feather, out=pasted[:n])
+                out[f0:f0 + n].copy_(pasted[:n], non_blocking=True)
+        return (out, r_d) if return_rd else out
+
     def _check_stream_call(self, what, slots, wa):
         """What every stream refuses at the call, before its generator exists (a generator's body runs at the first next())."""
         if int(slots) < 2:
@@ -576,22 +672,32 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                         quality=90, restart=None, return_rd=False):
+                         quality=90, restart=None, return_rd=False, place=None, feather=None):
         """generate_to_host for one clip (B = 1) with the frames leaving as baseline JPEG files (jpeg.JpegFrames in pinned host
         memory): the chain, decode_u8 of the whole clip, float_jpg_encode on the 8-bit frames in HBM, ONE host read of the
         offsets, then offsets[T] bytes across PCIe - the files, not the frames.  File i is bitwise
         host_models.jpeg_encode_rgb8(frame i of generate_to_host(out_dtype=torch.uint8), quality, restart).  Complete on return
-        (the stream has been synchronised).  The 8-bit frames stay on the device: T * size * size * 3 bytes of HBM while it runs."""
+        (the stream has been synchronised).  The 8-bit frames stay on the device: T * size * size * 3 bytes of HBM while it runs.
+        place (a Placement; default None: nothing above changes): the 8-bit crops are pasted back into the portrait on the device
+        (float_img_paste, `feather` as in generate_pasted) and the encoder codes the H x W frames - file i is jpeg_encode_rgb8 of
+        frame i of generate_pasted, and T * H * W * 3 more bytes of HBM are held while it runs.  float_jpg_encode takes sides that
+        are multiples of 16: another portrait size is a ValueError here, before anything runs; nothing is padded."""
+        if place is not None:
+            place = _check_place("generate_to_jpeg", place, self.device)
+            image.require_jpeg_sides("generate_to_jpeg", *place.size)
         self.require_no_stream("generate_to_jpeg")
         if feats is not None:
             self.dec.set_feats(feats)
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
         with torch.cuda.device(self.device):
-            frames = jpeg.encode_jpeg_host(self.dec.decode_u8(s_r, _rows(r_d)), quality, restart)
+            u8 = self.dec.decode_u8(s_r, _rows(r_d))
+            if place is not None:
+                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather)
+            frames = jpeg.encode_jpeg_host(u8, quality, restart)
         return (frames, r_d) if return_rd else frames
 
     def stream_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                       quality=90, restart=None, slots=3):
+                       quality=90, restart=None, slots=3, place=None, feather=None):
         """generate_to_jpeg as a generator: one JpegBlock(first, last, frames) per FMT window, in frame order, the same files as the
         whole-clip call.  The contract is stream_to_host's: `frames` (a jpeg.JpegFrames) lives in one of `slots` pinned ring
         buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (AviMjpegWriter.write
@@ -603,11 +709,18 @@ class FloatHotPath:
         offsets on both sides.  Per window the chain, decode_u8, float_jpg_encode and the copy of the 51 offsets are enqueued on
         the current stream; when the block's turn comes the generator waits on that block's event, reads offsets[-1] from pinned
         memory and copies that many bytes on a second stream.  Files beyond the slot's room (noise at quality 100) are encoded
-        once more into a larger buffer."""
+        once more into a larger buffer.
+        place, feather: as in generate_to_jpeg - the files are those of the pasted H x W frames, a slot's device buffer holds 50 of
+        them and one more buffer of 50 crops is shared; a portrait whose sides are no multiples of 16 is a ValueError at the call."""
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError("stream_to_jpeg: quality (%d) must be 1 ... 100" % quality)
-        sink = _JpegSink(self, quality, jpeg.default_restart(self.size) if restart is None else int(restart))
+        width = self.size
+        if place is not None:
+            place = _check_place("stream_to_jpeg", place, self.device)
+            image.require_jpeg_sides("stream_to_jpeg", *place.size)
+            width = place.size[1]
+        sink = _JpegSink(self, quality, jpeg.default_restart(width) if restart is None else int(restart), place, feather)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 

@@ -10,8 +10,8 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
-from ...image import detector_view_device, front_takes, image_to_device, preprocess_image_device
-from ...pipeline import FloatHotPath, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
+from ...image import detector_view_device, front_takes, image_to_device, preprocess_image_device, require_jpeg_sides, source_rgb8_device
+from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
 
 # key prefixes of the unified checkpoint (utils/downloader.py:35-42)
@@ -252,6 +252,27 @@ class InferenceAgent:
     def host_inputs(self, ref_img, ref_audio, no_crop=True):
         """Host plumbing of the reference's DataProcessor (generate.py:34-81): optional face crop, area resize to the model
         size, [-1,1]; mono, resample to 16 kHz, normalise.  Returns (s (1,3,H,W), a (N,)) on the device."""
+        return self._host_inputs(ref_img, ref_audio, no_crop, False)[:2]
+
+    def host_inputs_placed(self, ref_img, ref_audio, no_crop=True):
+        """host_inputs that keeps what it learns about the crop: (s, a, place).  s and a are host_inputs' own, on every route;
+        place is a pipeline.Placement - `src8` the (H, W, 3) uint8 portrait on the device as the model's input was cut from it
+        (image.source_rgb8_device: opt.rgba_conversion and opt.bkg_color_hex honoured; with FLOAT_AMD_IMAGE_FRONT=0 the alpha is
+        discarded, as on that route), `rect` = (x0, y0, w, h) the crop window in its coordinates: the one process_img(...,
+        front=...) gives on the device-front route, the bbox process_img returns on the host routes (H <= 360 with face_align,
+        beyond the size limits, FLOAT_AMD_IMAGE_FRONT=0), (0, 0, W, H) with no_crop.  It may reach outside the image.  What
+        infer_pasted, stream_pasted and their JPEG forms paste the generated frames back with."""
+        return self._host_inputs(ref_img, ref_audio, no_crop, True)
+
+    def _source_rgb8(self, img, front_on):
+        """The portrait of a Placement: the definition's 8-bit RGB of the IMAGE item, on the device."""
+        o = self.opt
+        if front_on:
+            return source_rgb8_device(img, getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000"), self.rank)
+        return host_models.image_to_rgb8(img, "discard_alpha").to(self.rank, non_blocking=True).contiguous()
+
+    def _host_inputs(self, ref_img, ref_audio, no_crop, placed):
+        """The one body of host_inputs and host_inputs_placed: (s, a, place), place None unless `placed`."""
         o = self.opt
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         # The image front end on the device (float_img_front): the raw IMAGE tensor crosses PCIe once, and RGBA conversion
@@ -278,16 +299,20 @@ class InferenceAgent:
                 s = host_models.preprocess_image(dimg, o.input_size)
             else:
                 s = preprocess_image_device(dimg, o.input_size, rect, rgba, bkg)
-            return s, self._host_audio(ref_audio)
+            place = Placement(self._source_rgb8(dimg, True), tuple(int(v) for v in rect) if rect is not None else (0, 0, Wd, H)) if placed else None
+            return s, self._host_audio(ref_audio), place
+        src = img
         if front_on and ch == 4:  # the cubic route, an image beyond the size limits: the widgets are honoured there too
             img = host_models.image_to_rgb8(img, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0
+        bbox = (0, 0, Wd, H)
         if not no_crop:  # generate.py:77-78
-            img, _ = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger)
+            img, bbox = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger)
         # The raw tensors cross PCIe first (3 MB + 0.6 MB for a 10-s clip) and the elementwise / reduction plumbing runs on the
         # device: on the host the same ops cost 1-29 ms per clip (torch's 128-thread intra-op pool on sub-megabyte tensors),
         # as much as a quarter of the whole clip.  The reference moves its slices to the device first too (nodes.py:193-201).
         s = host_models.preprocess_image(img[..., :3].to(self.rank, non_blocking=True), o.input_size)
-        return s, self._host_audio(ref_audio)
+        place = Placement(self._source_rgb8(src, front_on), tuple(int(v) for v in bbox)) if placed else None
+        return s, self._host_audio(ref_audio), place
 
     def _host_audio(self, ref_audio):
         o = self.opt
@@ -449,27 +474,117 @@ class InferenceAgent:
         return self._stream_clip("InferenceAgent.stream_device_jpeg", s, a, emo, seed, _stream_device_jpeg)
 
     def write_video(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                    quality=90, fps=None):
+                    quality=90, fps=None, paste_back=False, feather=None):
         """A playable file: host_inputs, stream_device_jpeg, and host_models.AviMjpegWriter on `path` (a path or a seekable binary
         file object) - Motion JPEG in an AVI container with the clip's audio as a 16-bit PCM track: the AUDIO item's own samples
         at its own rate, channels mixed to mono (not the normalised 16 kHz waveform the model hears), one `01wb` chunk behind the
-        frames of every window.  fps defaults to opt.fps.  Returns the number of frames written."""
+        frames of every window.  fps defaults to opt.fps.  Returns the number of frames written.
+        paste_back=True: the frames are the user's portrait with the generated face pasted back (stream_pasted_jpeg, `feather` as
+        in infer_pasted) and the file is written at the portrait's size, whose sides must be multiples of 16 (ValueError
+        otherwise, before the file is opened)."""
         o = self.opt
         fps = o.fps if fps is None else fps
-        with torch.no_grad():
-            s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+        if paste_back:
+            img = ref_img[0] if ref_img.dim() == 4 else ref_img
+            height, width = int(img.shape[0]), int(img.shape[1])
+            blocks = self.stream_pasted_jpeg(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, quality)
+        else:
+            height = width = o.input_size
+            with torch.no_grad():
+                s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+            blocks = self.stream_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality)
         audio = ref_audio["waveform"][0].detach().float().cpu()
         audio = (audio.mean(dim=0) if audio.dim() == 2 else audio).reshape(-1)
         rate = int(ref_audio["sample_rate"])
-        with host_models.AviMjpegWriter(path, o.input_size, o.input_size, fps, audio_rate=rate) as w:
+        with host_models.AviMjpegWriter(path, width, height, fps, audio_rate=rate) as w:
             sent = 0
-            for blk in self.stream_device_jpeg(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, quality):
+            for blk in blocks:
                 w.write(blk.frames)
                 upto = min(audio.numel(), int(round(blk.last * rate / float(fps))))
                 w.write_audio(audio[sent:upto])
                 sent = max(sent, upto)
             w.write_audio(audio[sent:])
             return w.frames
+
+    # ------------------------------------------------------------------ paste back: the frames in the user's portrait
+    def _paste_call(self, what, ref_img, jpeg_out=False):
+        """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take."""
+        img = ref_img[0] if ref_img.dim() == 4 else ref_img
+        if jpeg_out:
+            require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]))
+
+    @torch.no_grad()
+    def infer_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                     feather=None, out=None):
+        """run_inference whose frames are the user's portrait with the generated face pasted back: (T, H, W, 3) uint8 in pinned host
+        memory at the portrait's own size, bitwise host_models.paste_rgb8(place.src8, infer_device(s, a, out_dtype=torch.uint8),
+        place.rect, feather) with (s, a, place) = host_inputs_placed(ref_img, ref_audio, no_crop).  The 8-bit crops never leave
+        the device (FloatHotPath.generate_pasted: decode_u8, float_img_paste, one copy per 50 frames).  feather: the width in
+        source pixels over which the box fades into the portrait where its edge lies inside the image; None = rect_w // 16, a
+        visual choice, not a measurement.  With no_crop the box is the whole image: the frames resized to the portrait's size.
+        FLOAT_AMD_RANGE applies as in infer_device (auto rebuilds and runs the clip again); FLOAT_AMD_VERIFY is NOT applied and
+        FLOAT_AMD_OVERLAP is ignored."""
+        s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
+        while True:
+            c, noise = self._clip_inputs(s, a, emo, seed)
+            host = self.G.generate_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                          noise=noise, place=place, feather=feather, out=out)
+            torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
+            if self.check_range("InferenceAgent.infer_pasted", allow_rebuild=True) != "rebuilt":
+                return host  # otherwise once more, in the wider types
+
+    def stream_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                      feather=None, slots=3):
+        """The streaming sibling of infer_pasted: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
+        frame order - concatenated, the frames infer_pasted returns for the same inputs and seed.  The ring rules are
+        stream_device's: `frames` is a (last - first, H, W, 3) uint8 view of one of `slots` pinned buffers, complete when yielded,
+        OVERWRITTEN once the generator has been advanced again; slots < 2 raises ValueError at the call; while the stream is open
+        every other producer on this agent raises RuntimeError.  FLOAT_AMD_RANGE is applied once after the last block (auto acts
+        as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        self._check_stream_call("stream_pasted", slots)
+
+        def _stream_pasted(c, noise, place):
+            return self.G.stream_to_host_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
+                                                e_cfg_scale, noise=noise, place=place, feather=feather, slots=int(slots))
+        return self._stream_placed("InferenceAgent.stream_pasted", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted)
+
+    def _stream_placed(self, where, ref_img, ref_audio, no_crop, emo, seed, start):
+        with torch.no_grad():
+            s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
+        yield from self._stream_clip(where, s, a, emo, seed, lambda c, noise: start(c, noise, place))
+
+    @torch.no_grad()
+    def infer_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                          feather=None, quality=90, restart=None):
+        """infer_pasted with the frames leaving as baseline JPEG files: a jpeg.JpegFrames in pinned host memory, file i bitwise
+        host_models.jpeg_encode_rgb8(infer_pasted(...)[i], quality, restart).  Paste and encoder run on the device and only the
+        files cross PCIe.  float_jpg_encode takes sides that are multiples of 16: a portrait of another size is a ValueError at
+        this call, before anything runs - nothing is padded.  FLOAT_AMD_RANGE applies as in infer_device_jpeg; FLOAT_AMD_VERIFY is
+        NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        self._paste_call("infer_pasted_jpeg", ref_img, jpeg_out=True)
+        s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
+        while True:
+            c, noise = self._clip_inputs(s, a, emo, seed)
+            frames = self.G.generate_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                             noise=noise, quality=quality, restart=restart, place=place, feather=feather)
+            if self.check_range("InferenceAgent.infer_pasted_jpeg", allow_rebuild=True) != "rebuilt":
+                return frames  # otherwise once more, in the wider types
+
+    def stream_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                           feather=None, quality=90, restart=None, slots=3):
+        """The streaming sibling of infer_pasted_jpeg: a generator of JpegBlock(first, last, frames) under the ring rules of
+        stream_device_jpeg - concatenated, the files infer_pasted_jpeg returns.  slots < 2, a quality outside 1 ... 100 or a portrait
+        whose sides are no multiples of 16 raise ValueError here, at the call.  FLOAT_AMD_RANGE is applied once after the last block
+        (auto acts as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        self._check_stream_call("stream_pasted_jpeg", slots)
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("stream_pasted_jpeg: quality (%r) must be 1 ... 100" % (quality,))
+        self._paste_call("stream_pasted_jpeg", ref_img, jpeg_out=True)
+
+        def _stream_pasted_jpeg(c, noise, place):
+            return self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                         noise=noise, quality=int(quality), restart=restart, slots=int(slots), place=place, feather=feather)
+        return self._stream_placed("InferenceAgent.stream_pasted_jpeg", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_jpeg)
 
     def range_counts(self, reset=True):
         """{operator: clamped / non-finite 16-bit stores since the last call} over every fp16 handle of the agent."""

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
+/* Stays 6: float_img_paste (the generated frames back in the source portrait on the device),
+ * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
  * float_img_front / float_img_front_work_bytes (the image front end on the device),
  * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
  * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
@@ -559,6 +560,30 @@ size_t float_img_front_work_bytes(int32_t src_h, int32_t src_w, int32_t dst_h, i
 int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t channels, int32_t rect_x, int32_t rect_y, int32_t rect_w,
                     int32_t rect_h, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g, int32_t bkg_b,
                     int32_t out_mode, void* out, int32_t dst_h, int32_t dst_w, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------- paste back -- */
+/* The step after the decoder: n_frames generated 8-bit frames (n_frames, fr_h, fr_w, 3) - the buffer float_dec_frames_u8 writes -
+ * back in the 8-bit source portrait src8 (src_h, src_w, 3), both in HBM -> out (n_frames, src_h, src_w, 3) uint8.  Integer
+ * arithmetic, bitwise the definition in the host mirror, host_models.paste_rgb8:
+ *   box     cells rect_x ... rect_x + rect_w - 1 by rect_y ... rect_y + rect_h - 1 in source coordinates; it may reach outside the
+ *           image or miss it.  A pixel outside box & image is the source's.  The parts of a frame that map outside the image are
+ *           discarded.
+ *   face    the frame resized to rect_h x rect_w by the rule of float_img_front above at the scales fr_w / rect_w and fr_h /
+ *           rect_h (area rule when both axes shrink or keep their size, else the linear rule on both), rounded half to even.
+ *   alpha   d = the cell's distance to the nearest OPEN side of the box (u, rect_w - 1 - u, v, rect_h - 1 - v); a side is open
+ *           only where the box edge lies strictly inside the image (rect_x > 0, rect_x + rect_w < src_w, rect_y > 0, rect_y +
+ *           rect_h < src_h).  a = min(255, 255 (d + 1) / (feather + 1)) (integer division); no open side or feather == 0: a = 255.
+ *   blend   out = (a face + (255 - a) src + 127) / 255 (integer division: round to nearest, 255 is odd).
+ * Limits: source and box sides 1 ... 16384, frame sides 1 ... 1024 (with them every sum of the resize fits 32 bits: S <= 255 *
+ * 2^20, positions <= 2^24), feather 0 ... 16384, n_frames >= 1, |rect_x|, |rect_y| <= 2^30.  All three pointers are DEVICE
+ * pointers to contiguous HWC bytes of any alignment; out must not overlap the inputs.  An output frame is 3 src_h src_w < 2^31
+ * bytes; frame bases are formed in 64 bits, so out may exceed 4 GiB.
+ * Enqueues one kernel on `stream` (one per 2^30 workgroups: thousands of frames); no scratch, no atomics, allocates nothing,
+ * synchronises nothing, two calls give equal bytes.  An argument outside these rules returns FLOAT_E_INVALID, with a message
+ * naming the function and the argument, before any HIP call. */
+int float_img_paste(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* frames8, int32_t n_frames, int32_t fr_h,
+                    int32_t fr_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t feather, uint8_t* out,
+                    void* stream);
 
 /* ---------------------------------------------------------------- JPEG encoder -- */
 /* n_frames 8-bit RGB frames in HBM - the (n, h, w, 3) buffer float_dec_frames_u8 writes - -> n complete baseline JPEG files

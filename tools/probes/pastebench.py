@@ -1,0 +1,128 @@
+"""What pasting the generated frames back into the portrait costs, on the 512-px synthetic model (bench.py config 1: a 10-s clip,
+51 grid points, decode batches of 32, seeded weights of the checkpoint's shapes) with a 1024 x 1024 and a 1920 x 1088 portrait,
+face_align on and a stub detector whose box gives a crop of about 0.6 of the portrait's height.  Per portrait three forms take
+turns in one process:
+  u8      host_inputs + InferenceAgent.infer_device(out_dtype=torch.uint8): the crop clip, the yardstick of the same process;
+  pasted  InferenceAgent.infer_pasted;
+  jpeg    InferenceAgent.infer_pasted_jpeg(quality=QUALITY).
+Each call is timed on the host clock between device synchronisations, REPS (default 10) repetitions per form after WARMUP
+(default 2), taking turns.  The paste launch alone (image.paste_frames_device on 50 crops in HBM, the product's group) is timed by
+device events, LAUNCH_REPS (default 30) times after 3, and held to the bytes it moves - 50 H W 3 written, 50 H W 3 of the source
+and 50 x 512 x 512 x 3 of the frames read - over the copy bandwidth float_probe_peaks measures in this process (bytes read +
+bytes written per second).  Prints one JSON line: median, min, max and spread (max - min) per form, ms; the launch's median, its
+GB/s and its fraction of the copy peak.  Run from the repository root.  Environment: REPS, WARMUP, LAUNCH_REPS, QUALITY."""
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+from tests.util import load_pkg  # noqa: E402
+
+pkg = load_pkg()
+hm = pkg.host_models
+REPS, WARMUP, QUALITY = int(os.environ.get("REPS", "10")), int(os.environ.get("WARMUP", "2")), int(os.environ.get("QUALITY", "90"))
+LAUNCH_REPS = int(os.environ.get("LAUNCH_REPS", "30"))
+SIZE, SECONDS, NFE, MAX_FRAMES = 512, 10.0, 51, 32
+dev = "cuda:0"
+
+
+class _Detector:
+    """a box in the middle of the 360-px view, half side 0.19 of its height: at margin 1.6 a crop of 0.6 of the portrait's height"""
+    def detect_from_image(self, arr):
+        h, w = arr.shape[0], arr.shape[1]
+        r = 0.19 * h
+        return [(w / 2 - r, h / 2 - r, w / 2 + r, h / 2 + r, 0.99)]
+
+
+class _FA:
+    face_detector = _Detector()
+
+
+hm._FA = _FA()
+
+cfg = pkg.config.FmtConfig()
+gen = importlib.import_module(pkg.__name__ + ".src.nodes.generate")
+opt = importlib.import_module(pkg.__name__ + ".src.nodes.options.base_options").BaseOptions()
+opt.nfe, opt.input_size, opt.fps, opt.rank = NFE, SIZE, 25.0, dev
+acfg = pkg.config.AudioConfig()
+parts = dict(enc=pkg.weights.synth_encoder_state(SIZE, seed=1), dec=pkg.weights.synth_decoder_state(SIZE, seed=1),
+             fmt=pkg.weights.synth_fmt_state(cfg, seed=1), audio_encoder=(pkg.weights.synth_audio_state(acfg, seed=1), acfg))
+agent = gen.InferenceAgent(opt, parts, dev, max_frames=MAX_FRAMES, use_graph=2)
+audio = {"waveform": pkg.weights.synth_waveform(SECONDS, seed=1).reshape(1, 1, -1).cpu(), "sample_rate": 16000}
+FORMS = ("u8", "pasted", "jpeg")
+KW = dict(emo="neutral", seed=15)
+last = {}
+
+
+def run(form, img):
+    if form == "u8":
+        s, a = agent.host_inputs(img, audio, no_crop=False)
+        last[form] = agent.infer_device(s, a, 2.0, 1.0, 1.0, out_dtype=torch.uint8, **KW)
+    elif form == "pasted":
+        last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, **KW)
+    else:
+        last[form] = agent.infer_pasted_jpeg(img, audio, 2.0, 1.0, 1.0, no_crop=False, quality=QUALITY, **KW)
+
+
+def wall_ms(form, img):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run(form, img)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    agent.G.release_host_inflight()
+    return ms
+
+
+def stats(v):
+    return dict(median=round(statistics.median(v), 3), min=round(min(v), 3), max=round(max(v), 3), spread=round(max(v) - min(v), 3))
+
+
+def launch_alone(place, peaks):
+    n, (H, W) = 50, place.size
+    crops = torch.randint(0, 256, (n, SIZE, SIZE, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+    feather = hm.default_feather(place.rect)
+    ms = []
+    for i in range(3 + LAUNCH_REPS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out)
+        e1.record()
+        e1.synchronize()
+        if i >= 3:
+            ms.append(e0.elapsed_time(e1))
+    moved = 2 * n * H * W * 3 + n * SIZE * SIZE * 3
+    res = stats(ms)
+    res.update(frames=n, bytes_moved=moved, GBps=round(moved / 1e9 / (res["median"] * 1e-3), 1),
+               fraction_of_copy_peak=round(moved / 1e9 / (res["median"] * 1e-3) / peaks["hbm_copy_GBps"], 3),
+               equals_definition=bool(torch.equal(out[:1].cpu(), hm.paste_rgb8(place.src8.cpu(), crops[:1].cpu(), place.rect, feather))))
+    return res
+
+
+peaks = pkg.native.probe_peaks(dev)
+res = dict(probe="pastebench", size=SIZE, frames=250, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP, quality=QUALITY, peaks=peaks)
+for H, W in ((1024, 1024), (1088, 1920)):
+    img = torch.from_numpy(np.random.RandomState(H).rand(1, H, W, 3).astype("float32"))
+    for _ in range(WARMUP):
+        for form in FORMS:
+            wall_ms(form, img)
+    ms = {form: [] for form in FORMS}
+    for _ in range(REPS):
+        for form in FORMS:  # taking turns: drift of the box lands on all three
+            ms[form].append(wall_ms(form, img))
+    out = {form: stats(v) for form, v in ms.items()}
+    out["pasted"]["minus_u8_ms"] = round(out["pasted"]["median"] - out["u8"]["median"], 3)
+    out["jpeg"]["minus_u8_ms"] = round(out["jpeg"]["median"] - out["u8"]["median"], 3)
+    _, _, place = agent.host_inputs_placed(img, audio, no_crop=False)
+    out["rect"] = list(place.rect)
+    out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), jpeg=last["jpeg"].nbytes)
+    out["paste_launch_50_frames"] = launch_alone(place, peaks)
+    res["%dx%d" % (W, H)] = out
+print(json.dumps(res))
