@@ -39,34 +39,10 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
   const int r16 = lane & 15, q = lane >> 4;
-  // 1-D grid of (column blocks) x (row blocks).  Row blocks of one column block read the same
-  // weights: give them consecutive slots on ONE XCD (ids congruent mod 8 share an XCD's L2).
-  int bx, by, ks = 0;
-  {
-    const int nbn = g.N / BN, id = (int)bid;
-    const int nbx = (EPI == EPI_PARTIAL) ? nbn * g.ksplit : nbn;  // (column block, K slice) pairs
-    if ((nbx & 7) == 0) {
-      const int slot = id >> 3;
-      by = slot % g.mblk;
-      bx = (slot / g.mblk) * 8 + (id & 7);
-    } else {
-      bx = id % nbx;
-      by = id / nbx;
-    }
-    if constexpr (EPI == EPI_PARTIAL) {
-      if ((nbx & 7) == 0 && (8 % g.ksplit) == 0) {
-        // K slice <-> XCD affinity: the 8/ksplit XCDs that own slice ks fetch only that slice of the
-        // activations (r01 PMC: with slices spread over all XCDs fc2 fetched its 1.5 MB operand 8 times,
-        // 12.6 MB against 8.4 MB of weights)
-        const int P = 8 / g.ksplit, x = bx & 7;
-        ks = x / P;
-        bx = (bx >> 3) * P + (x % P);
-      } else {
-        ks = bx / nbn;
-        bx = bx % nbn;
-      }
-    }
-  }
+  // 1-D grid of (column blocks) x (row blocks) x (K slices): fmt_decode.hpp.  Everything up to the first operand load reads the
+  // head of the argument block only (GemmHead, preloaded into SGPRs for fmt_gemm_kernel); the tail is first read behind them.
+  const GemmBlock blk = fmt_block_decode(g.dec, (unsigned)g.mblk, bid, EPI == EPI_PARTIAL);
+  const int bx = blk.bx, by = blk.by, ks = blk.ks;
   const int nb0 = bx * NT;
   const int mt0 = by * MTW;
   const int n0 = nb0 * 16, m0 = mt0 * 16;
@@ -78,12 +54,24 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
     for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int KB = g.K >> 5;
-  const int KBs = (EPI == EPI_PARTIAL) ? KB / g.ksplit : KB;  // k-blocks of this workgroup's K slice
-  const int KBw = KBs / NW;                                   // k-blocks per wave
+  const int KBs = (EPI == EPI_PARTIAL) ? g.kbs : KB;  // k-blocks of this workgroup's K slice
+  const int KBw = (int)((unsigned)KBs / NW);          // k-blocks per wave
   const E* Ap = reinterpret_cast<const E*>(g.A) + ((size_t)mt0 * KB + ks * KBs + w * KBw) * 512 + lane * 8;
   const E* Wp = reinterpret_cast<const E*>(g.W) + ((size_t)nb0 * KB + ks * KBs + w * KBw) * 512 + lane * 8;
   const size_t tstride = (size_t)KB * 512;
-  // EPI_GATE_RES with one epilogue item per thread: fetch residual and gate now, not after the K loop
+
+  P8 a[PF][MTW], b[PF][NT];
+#pragma unroll
+  for (int p = 0; p < PF; ++p) {
+    if (p < KBw) {
+#pragma unroll
+      for (int j = 0; j < NT; ++j) b[p][j] = T::load8_nt(Wp + j * tstride + (size_t)p * 512);
+#pragma unroll
+      for (int i = 0; i < MTW; ++i) a[p][i] = ldA(Ap + i * tstride + (size_t)p * 512);
+    }
+  }
+  // EPI_GATE_RES with one epilogue item per thread: fetch residual and gate now, not after the K loop (behind the operand
+  // loads: their addresses are the first thing that needs the tail of the argument block)
   constexpr bool kEarlyRes = (EPI == EPI_GATE_RES) && (MTW * 16 * (NT * 2) <= NW * 64);
   float4 res_pf[2], gate_pf[2];
   if constexpr (kEarlyRes) {
@@ -96,17 +84,6 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
       res_pf[1] = fh_load_f4<COH>(o + 4);
       gate_pf[0] = fh_load_f4_stream(gt);
       gate_pf[1] = fh_load_f4_stream(gt + 4);
-    }
-  }
-
-  P8 a[PF][MTW], b[PF][NT];
-#pragma unroll
-  for (int p = 0; p < PF; ++p) {
-    if (p < KBw) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j) b[p][j] = T::load8_nt(Wp + j * tstride + (size_t)p * 512);
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) a[p][i] = ldA(Ap + i * tstride + (size_t)p * 512);
     }
   }
   // only the epilogue kinds whose launches are given a TouchSpec carry the code (2 registers, a branch)
@@ -277,8 +254,22 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
 }
 
 template <class T, int MTW, int NT, int NW, int EPI>
-__global__ __launch_bounds__(NW * 64) void fmt_gemm_kernel(GemmArgs g) {
+__global__ __launch_bounds__(NW * 64) void fmt_gemm_kernel(const u16* A, const u16* W, int K, int kbs, int ksplit, int mblk,
+                                                           unsigned mblk_mul, unsigned nbx, unsigned nbx_mul, unsigned nbn,
+                                                           unsigned nbn_mul, unsigned bits, GemmTail t) {
+  // GemmHead member by member: scalar parameters are preloaded, a by-value struct never is (and it ends the preloaded run)
+  GemmArgs g;
+  static_cast<GemmHead&>(g) = GemmHead{A, W, K, kbs, ksplit, mblk, GemmDecode{mblk_mul, nbx, nbx_mul, nbn, nbn_mul, bits}};
+  static_cast<GemmTail&>(g) = t;
   fmt_gemm_body<T, MTW, NT, NW, EPI, false>(g, blockIdx.x, gridDim.x);
+}
+// the host's side of that parameter list: launches fmt_gemm_kernel<...> `kern` with the head's members and the tail of `g`
+// (whose head fmt_gemm_head has completed); `prof` as fh_launch_prof
+template <class K>
+void fmt_gemm_launch(int prof, K kern, dim3 grid, dim3 block, size_t smem, hipStream_t s, const GemmArgs& g) {
+  const GemmTail& t = g;
+  fh_launch_prof(prof, kern, grid, block, smem, s, g.A, g.W, g.K, g.kbs, g.ksplit, g.mblk, g.dec.mblk_mul, g.dec.nbx, g.dec.nbx_mul,
+                 g.dec.nbn, g.dec.nbn_mul, g.dec.bits, t);
 }
 
 // Wide-N variant for the fused adaLN projection (N = depth*6D + 2D = 51 200, K = D): here re-reading
@@ -706,8 +697,9 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
   const int lane = threadIdx.x & 63;
   int row = bid * wpb + (threadIdx.x >> 6);
   unsigned touched[kLnTouch] = {};
-  const unsigned tfirst = (bid >> 3) * 64 + lane, tstride = (nblk >> 3) * 64;
   const bool touch = TOUCH && wpb == 1;
+  // (`pf` and `nblk` belong to the tail of fmt_lnmod_kernel's parameters: nothing of them is needed before the row's loads)
+  auto touch_lines = [&]() { fmt_touch(pf, bid & 7, (bid >> 3) * 64 + lane, (nblk >> 3) * 64, touched); };
   if (wpb == 1) {
     // One row per workgroup: a 128-byte line of the packed output holds the 16-byte pieces of 8 consecutive rows, so give
     // those 8 rows to workgroups of ONE XCD (ids congruent mod 8 share an XCD's L2, where the pieces merge into full lines
@@ -717,7 +709,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
   }
   if (row >= M) {
     if (touch) {
-      fmt_touch(pf, bid & 7, tfirst, tstride, touched);
+      touch_lines();
       fmt_touch_retire(touched);
     }
     return;
@@ -739,7 +731,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
     a[i] = fh_load_f4_stream(sh + c);
     b[i] = fh_load_f4_stream(sc + c);
   }
-  if (KS == 0 && touch) fmt_touch(pf, bid & 7, tfirst, tstride, touched);  // behind the row's own loads (in-order retirement)
+  if (KS == 0 && touch) touch_lines();  // behind the row's own loads (in-order retirement)
   if constexpr (KS > 0) {
     float4 p[KS][NV], gt[NV], bi[NV];
 #pragma unroll
@@ -752,9 +744,10 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
         else p[k][i] = fh_load_f4_stream(ps);  // the slab's only read
       }
       gt[i] = fh_load_f4_stream(red.gate + mrow * ldm + c);
-      bi[i] = *reinterpret_cast<const float4*>(red.bias + c);
     }
-    if (touch) fmt_touch(pf, bid & 7, tfirst, tstride, touched);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) bi[i] = *reinterpret_cast<const float4*>(red.bias + i * 256 + lane * 4);  // tail (fmt_lnmod_kernel)
+    if (touch) touch_lines();
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       float4 t = p[0][i];
@@ -802,11 +795,16 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
 }
 
 template <class T, int NV, int KS, bool TOUCH, bool WT>
-__global__ __launch_bounds__(256) void fmt_lnmod_kernel(float* __restrict__ x, int M, const float* __restrict__ shift,
-                                                        const float* __restrict__ scale, int ldm, u16* __restrict__ out,
-                                                        LnRed red, TouchSpec pf, int ntok, int perm, unsigned long long* sat) {
-  fmt_lnmod_body<T, NV, KS, TOUCH, WT, false>(x, M, shift, scale, ldm, out, red, pf, ntok, perm, sat, blockIdx.x, gridDim.x,
-                                              (int)(blockDim.x >> 6));
+__global__ __launch_bounds__(256) void fmt_lnmod_kernel(float* __restrict__ x, const float* __restrict__ shift,
+                                                        const float* __restrict__ scale, const float* __restrict__ slab,
+                                                        const float* __restrict__ gate, int M, int ldm, int wpb, unsigned slab_stride,
+                                                        u16* __restrict__ out, const float* __restrict__ red_bias, TouchSpec pf,
+                                                        int ntok, int perm, unsigned long long* sat) {
+  // The first 14 dwords - every pointer and size behind the addresses of the row's loads and of the slabs folded into it, the
+  // rows per workgroup included (blockDim would be a load from the kernarg segment) - are preloaded into SGPRs at dispatch; the
+  // output, the fold's bias, the touch and the permutation come behind and are first read once those loads are in flight.
+  const LnRed red{slab, (size_t)slab_stride, red_bias, gate};
+  fmt_lnmod_body<T, NV, KS, TOUCH, WT, false>(x, M, shift, scale, ldm, out, red, pf, ntok, perm, sat, blockIdx.x, gridDim.x, wpb);
 }
 
 // Banded attention (FMT.py:71-88 with the mask of FMT.py:15-19): query i sees keys |i-j| <= window.
@@ -819,8 +817,8 @@ __global__ __launch_bounds__(256) void fmt_lnmod_kernel(float* __restrict__ x, i
 // Body: head `h`, run `run` of `qpw` queries (nthr = qpw * LPQ threads take part), `lin` of `nwg` workgroups for the touch.
 template <class T, int LPQ, bool TOUCH, bool WT_, bool COH>
 __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int ld, u16* __restrict__ out, int ntok, int M, int D,
-                                              int window, const TouchSpec& pf, unsigned long long* sat, const int h, const int run,
-                                              const int nthr, const unsigned lin, const unsigned nwg) {
+                                              int window, const FmtDiv ntok_div, const TouchSpec& pf, unsigned long long* sat,
+                                              const int h, const int run, const int nthr, const unsigned lin, const unsigned nwg) {
   constexpr int HD = 128, PD = HD / LPQ, NU = PD / 8;
   constexpr bool WT = WT_ || COH;
   auto ld8 = [](const typename T::elem* p) -> typename T::pack8 {
@@ -843,19 +841,25 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
     if constexpr (TOUCH) fmt_touch_retire(touched);
     return;
   }
-  const int b = row_ / ntok, qi = row_ - b * ntok;
+  const int b = (int)fmt_div((unsigned)row_, ntok_div), qi = row_ - b * ntok;  // row_ / ntok, the host's constant
   const int d0 = h * HD + part * PD;
   const float scale = rsqrtf((float)HD);
   typedef typename T::elem E;
   typedef typename T::pack8 P8;
   const E* base = reinterpret_cast<const E*>(qkv) + (size_t)(b * ntok) * ld + d0;
   float qf[PD], o[PD];
+  P8 qq[NU];
 #pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    const P8 uu = ld8(base + (size_t)qi * ld + u * 8);
+  for (int u = 0; u < NU; ++u) qq[u] = ld8(base + (size_t)qi * ld + u * 8);
+  // converted behind the first k / v loads of either branch below: in front of the branch the conversion made the wave wait for
+  // q (a whole memory round trip) before it asked for k and v
+  auto scale_q = [&]() {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) qf[u * 8 + j] = T::get(uu, j) * scale;
-  }
+    for (int u = 0; u < NU; ++u) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) qf[u * 8 + j] = T::get(qq[u], j) * scale;
+    }
+  };
 #pragma unroll
   for (int i = 0; i < PD; ++i) o[i] = 0.f;
   float m = -INFINITY, l = 0.f;
@@ -892,6 +896,7 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
       }
     }
     touch();
+    scale_q();
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
       const int kj = qi + t - 2;
@@ -900,6 +905,7 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
     }
   } else {
     touch();
+    scale_q();
     for (int kj = qi - window; kj <= qi + window; ++kj) {
       const int kc = min(max(kj, 0), ntok - 1);
       const E* kp = base + (size_t)kc * ld + D;
@@ -928,10 +934,13 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
 }
 
 template <class T, int LPQ, bool TOUCH, bool WT>
-__global__ __launch_bounds__(512) void fmt_attn_kernel(const u16* __restrict__ qkv, int ld, u16* __restrict__ out, int ntok,
-                                                       int M, int D, int window, TouchSpec pf, unsigned long long* sat) {
-  fmt_attn_body<T, LPQ, TOUCH, WT, false>(qkv, ld, out, ntok, M, D, window, pf, sat, blockIdx.x, blockIdx.y, blockDim.x,
-                                          blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
+__global__ __launch_bounds__(512) void fmt_attn_kernel(const u16* __restrict__ qkv, u16* __restrict__ out, int ld, int ntok, int M,
+                                                       int D, int window, int nthr, unsigned ntok_mul, unsigned ntok_sh, int heads,
+                                                       int nrun, unsigned long long* sat, TouchSpec pf) {
+  // 14 preloaded dwords in front of the TouchSpec: the launch's block and grid sizes are among them (blockDim / gridDim would
+  // be loads from the kernarg segment), so the q / k / v loads are issued without a scalar-memory round trip in front of them
+  fmt_attn_body<T, LPQ, TOUCH, WT, false>(qkv, ld, out, ntok, M, D, window, FmtDiv{ntok_mul, ntok_sh}, pf, sat, blockIdx.x, blockIdx.y,
+                                          nthr, blockIdx.x + (unsigned)heads * blockIdx.y, (unsigned)(heads * nrun));
 }
 
 // Banded attention AND attn.proj in one launch (FMT.py:71-89): attention is per head, the projection sums over heads, so a
@@ -1185,6 +1194,7 @@ struct MegaCtx {                 // per handle and CFG shape
   size_t slab_stride;
   int M, D, ntok, ldm, window, heads;
   unsigned long long* sat;
+  FmtDiv ntok_div;  // row / ntok (fmt_attn_body)
 };
 struct MegaDyn {                 // per launch
   const float* mod;
@@ -1270,7 +1280,7 @@ __global__ __launch_bounds__(512) void fmt_mega_kernel(const MegaStage* __restri
           break;
         case MS_ATTN:
           if (threadIdx.x < 128)
-            fmt_attn_body<T, 16, true, true, true>(c.qkv16, 3 * c.D, st.att_out, c.ntok, c.M, c.D, c.window, st.pf, c.sat,
+            fmt_attn_body<T, 16, true, true, true>(c.qkv16, 3 * c.D, st.att_out, c.ntok, c.M, c.D, c.window, c.ntok_div, st.pf, c.sat,
                                                    (int)(bid % (unsigned)c.heads), (int)(bid / (unsigned)c.heads), 128, bid, st.nblk);
           break;
         case MS_PROJ: {

@@ -14,6 +14,8 @@ constexpr int kLdsMax = 160 * 1024;  // gfx950: 160 KiB of LDS per workgroup
 constexpr int kWtRows = 256;  // LayerNorm / attention launches of at most this many rows store write-through (common.hpp, FMT_WT)
 
 typedef void (*GemmKernel)(GemmArgs);
+// fmt_gemm_kernel: the members of GemmHead as scalar parameters, then the tail (fmt_gemm_launch passes them)
+typedef void (*GemmHeadKernel)(const u16*, const u16*, int, int, int, int, unsigned, unsigned, unsigned, unsigned, unsigned, unsigned, GemmTail);
 
 // dynamic LDS above the 64 KiB default, once per process and kernel
 template <class K>
@@ -113,7 +115,7 @@ constexpr int kMegaWgs = 256, kMegaSmem = 8 * 48 * 64 * 4;
 
 template <class T>
 void prime_kernels() {
-  auto raise = [](GemmKernel kern, int, int, int, int smem) {
+  auto raise = [](auto kern, int, int, int, int smem) {
     if (smem <= kLdsMax) raise_lds(kern, smem);
   };
   for_each_gemm<T, EPI_F32>(raise);
@@ -228,9 +230,9 @@ template <class T, int EPI>
 int launch_gemm(GemmArgs g, int mtw, int nt, int nw, hipStream_t s) {
   FH_REQUIRE(g.N % (nt * 16) == 0 && g.K % (32 * nw * ((EPI == EPI_PARTIAL && g.ksplit > 1) ? g.ksplit : 1)) == 0,
              "gemm shape N=%d K=%d not tileable by %d columns / %d waves", g.N, g.K, nt * 16, nw);
-  GemmKernel kern = nullptr;
+  GemmHeadKernel kern = nullptr;
   int smem = 0;
-  for_each_gemm<T, EPI>([&](GemmKernel k, int m, int n, int w, int bytes) {
+  for_each_gemm<T, EPI>([&](GemmHeadKernel k, int m, int n, int w, int bytes) {
     if (m == mtw && n == nt && w == nw) kern = k, smem = bytes;
   });
   FH_REQUIRE(kern, "no GEMM tiling (%d x %d tiles, %d waves) for epilogue %d", mtw, nt, nw, EPI);
@@ -239,7 +241,9 @@ int launch_gemm(GemmArgs g, int mtw, int nt, int nw, hipStream_t s) {
   g.mblk = (mt_total + mtw - 1) / mtw;
   if (EPI != EPI_PARTIAL || g.ksplit < 1) g.ksplit = 1;
   dim3 grid((g.N / (nt * 16)) * g.mblk * g.ksplit);
-  fh_launch_prof(0, kern, grid, dim3(nw * 64), smem, s, g);
+  FH_REQUIRE(grid.x < kFmtDivMax, "GEMM grid of %u workgroups is beyond the block decode's range", grid.x);
+  fmt_gemm_head(g, nt * 16, EPI == EPI_PARTIAL);
+  fmt_gemm_launch(0, kern, grid, dim3(nw * 64), smem, s, g);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }
@@ -493,7 +497,9 @@ int launch_lnmod(const FmtLaunch& cx, int M, const float* shift, const float* sc
     });
   });
   FH_REQUIRE(kern, "dim_h %d unsupported (must be 256*{1,2,4,8})", cx.D);
-  hipLaunchKernelGGL(kern, grid, block, 0, cx.s, cx.xres, M, shift, scale, cx.Ntot, out ? out : cx.h16, red, pf, cx.ntok, perm, cx.sat);
+  FH_REQUIRE(red.slab_stride <= 0xffffffffull, "split-K slab of %zu elements is beyond the LayerNorm kernel's 32-bit stride", red.slab_stride);
+  hipLaunchKernelGGL(kern, grid, block, 0, cx.s, cx.xres, shift, scale, red.slab, red.gate, M, cx.Ntot, rpw, (unsigned)red.slab_stride,
+                     out ? out : cx.h16, red.bias, pf, cx.ntok, perm, cx.sat);
   if (pend) pend->ks = 0;
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
@@ -516,7 +522,9 @@ void launch_attn(const FmtLaunch& cx, int M, const Lin* pull) {
       });
     });
   });
-  hipLaunchKernelGGL(kern, grid, block, 0, cx.s, cx.qkv16, 3 * cx.D, cx.att16, cx.ntok, M, cx.D, cx.attn_window, pf, cx.sat);
+  const FmtDiv nd = fmt_make_div((unsigned)cx.ntok);
+  hipLaunchKernelGGL(kern, grid, block, 0, cx.s, cx.qkv16, cx.att16, 3 * cx.D, cx.ntok, M, cx.D, cx.attn_window, (int)block.x, nd.mul, nd.sh,
+                     (int)grid.x, (int)grid.y, cx.sat, pf);
 }
 
 // Banded attention + attn.proj as one launch (fmt_attnproj_kernel): slab[head] = attention_head(qkv16) @ W_proj[:, head]^T for

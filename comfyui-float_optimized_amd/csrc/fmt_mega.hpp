@@ -84,6 +84,7 @@ int build_mega(float_fmt* h, int bc) {
     g.sat = h->sat;
     g.mblk = ((g.M + 15) / 16 + mtw - 1) / mtw;
     if (g.ksplit < 1) g.ksplit = 1;
+    fmt_gemm_head(g, nt * 16, kind == MS_FC2);  // fc2 is the chain's EPI_PARTIAL stage
     m.g = g;
     m.nblk = (unsigned)((g.N / (nt * 16)) * g.mblk * g.ksplit);
     return m;
@@ -193,7 +194,7 @@ int build_mega(float_fmt* h, int bc) {
   FH_CHECK_HIP(hipMemcpy(P.dev, st.data(), st.size() * sizeof(MegaStage), hipMemcpyHostToDevice));
   P.nstage = (int)st.size();
   P.bc = bc;
-  P.ctx = MegaCtx{h->xres, h->qkv16, h->slab, (size_t)h->Mpad * D, M, D, ntok, h->Ntot, c.attn_window, c.heads, h->sat};
+  P.ctx = MegaCtx{h->xres, h->qkv16, h->slab, (size_t)h->Mpad * D, M, D, ntok, h->Ntot, c.attn_window, c.heads, h->sat, fmt_make_div((unsigned)ntok)};
   return FLOAT_OK;
 }
 

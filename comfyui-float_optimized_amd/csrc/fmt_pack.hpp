@@ -2,6 +2,7 @@
 // operators that feed it packed activations (aud_kernels.hpp).
 #pragma once
 #include "common.hpp"
+#include "fmt_decode.hpp"
 
 enum {
   EPI_F32 = 0,       // out_f32 = acc + bias                                   (row-major fp32)
@@ -73,12 +74,24 @@ __device__ __forceinline__ void fmt_touch_retire(const unsigned (&v)[N]) {
   asm volatile("" ::"v"(o));
 }
 
-struct GemmArgs {
+// The argument block of a GEMM launch in two parts.  GemmHead is what the address of the first operand load and the block
+// decode need, 14 dwords: fmt_gemm_kernel takes them as leading scalar kernel parameters, which the command processor preloads
+// into SGPRs at dispatch (-mllvm -amdgpu-kernarg-preload-count, see the Makefile), so its operand loads are issued without a
+// scalar-memory round trip in front of them.  GemmTail is the rest (epilogue, CFG, touch, z-batch), passed as one struct behind
+// the head and first read after the operand loads are in flight.  Host code and the other GEMM kernels see one GemmArgs.
+struct GemmHead {
   const u16* A;   // packed [row tiles][KB][64][8]; pad rows/columns are zero
   const u16* W;   // packed [N/16][KB][64][8]
-  const float* bias;
-  int K, M, N;    // K padded to a multiple of 128
+  int K;          // padded to a multiple of 128
+  int kbs;        // fmt_gemm_kernel: k-blocks (of 32) per K slice = K / 32 / ksplit (fmt_gemm_head)
+  // EPI_PARTIAL: K is cut into ksplit slices, one per workgroup; slice ks writes out_f32 + ks * slab_stride
+  int ksplit;
   int mblk;       // number of row blocks (grid = N/BN * mblk workgroups)
+  GemmDecode dec; // fmt_gemm_kernel: workgroup id -> (column block, row block, K slice) (fmt_gemm_head)
+};
+struct GemmTail {
+  const float* bias;
+  int M, N;
   float* out_f32;
   int ldo;
   u16* out16;
@@ -94,9 +107,7 @@ struct GemmArgs {
   float* xcur;   // (ntok - n_prev, N) Euler state or nullptr
   u16* xin16;    // next evaluation's x_embedder input, packed with KB = ldx
   int ldx;
-  // EPI_PARTIAL: K is cut into ksplit slices, one per workgroup; slice ks writes out_f32 + ks * slab_stride
-  int ksplit;
-  size_t slab_stride;
+  size_t slab_stride;  // EPI_PARTIAL, see ksplit
   TouchSpec touch;  // weights of a later GEMM to pull into L2 (W == nullptr: none)
   // fmt_gemm_wide_kernel only: `zcount` independent row batches (the Euler steps of a window) against the same weights in one
   // launch; batch z reads A + z * a_zstride (elements) and writes out_f32 + z * o_zstride (elements).  0 / 1 = a single batch.
@@ -107,4 +118,12 @@ struct GemmArgs {
   int tokblk;
   unsigned long long* sat;  // range counter of the launch's 16-bit stores (fh_range_flush) or nullptr
 };
+struct GemmArgs : GemmHead, GemmTail {};
+static_assert(sizeof(GemmHead) == 14 * 4, "the head is what the dispatch can preload: 14 dwords");
 
+// Completes the head of a fmt_gemm_kernel launch (or fmt_gemm_body stage) once M, N, K, mblk and ksplit stand: `bn` columns per
+// workgroup, `partial` = the EPI_PARTIAL epilogue (K slices are workgroups).
+inline void fmt_gemm_head(GemmArgs& g, int bn, bool partial) {
+  g.kbs = (g.K >> 5) / (partial ? g.ksplit : 1);
+  g.dec = fmt_make_decode(g.N / bn, g.mblk, g.ksplit, partial);
+}

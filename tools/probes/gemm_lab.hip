@@ -102,7 +102,8 @@ void launch_old(GemmArgs g) {
   }
   g.mblk = ((g.M + 15) / 16 + MTW - 1) / MTW;
   if (EPI != EPI_PARTIAL) g.ksplit = 1;
-  hipLaunchKernelGGL(kern, dim3((g.N / (NT * 16)) * g.mblk * g.ksplit), dim3(NW * 64), smem, nullptr, g);
+  fmt_gemm_head(g, NT * 16, EPI == EPI_PARTIAL);
+  fmt_gemm_launch(-1, kern, dim3((g.N / (NT * 16)) * g.mblk * g.ksplit), dim3(NW * 64), smem, nullptr, g);
 }
 
 template <int EPI>
