@@ -750,6 +750,40 @@ static int debug_impl(float_fmt* h, int what, const float* in, float* out, hipSt
     FH_CHECK_HIP(hipMemcpy(out, us.data(), n * 4, hipMemcpyHostToDevice));
     return FLOAT_OK;
   }
+  if (what == 3 || what == 4) {
+    // the K-split exchange of fmt_gemm_kernel on ONE workgroup's tile: 48 rows x 64 (what = 3) or 16 (what = 4) columns, K = 1024
+    // over 8 waves (4 in the fp32 mode), zero bias: with 8 waves the straight-line form of the body (the 16-column tile through
+    // attn.proj's epilogue, which carries it).  in = [A (48, 1024) | W (N, 1024)] fp32 rows.
+    FH_REQUIRE(in != nullptr, "float_fmt_debug: request %d needs an input", what);
+    constexpr int Mt = 48, Kt = 1024;
+    const int Nt = what == 3 ? 64 : 16;
+    std::vector<float> host((size_t)(Mt + Nt) * Kt);
+    FH_CHECK_HIP(hipStreamSynchronize(s));
+    FH_CHECK_HIP(hipMemcpy(host.data(), in, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    struct Scratch : DevicePool {
+      ~Scratch() { release(); }
+    } pool;
+    Lin a, w;  // A packs like a weight: the operand layout is the same for both
+    int rc;
+    if ((rc = fmt_pack_linear_raw(h->tune, &pool, h->cfg.dtype, host.data(), nullptr, Mt, Kt, &a))) return rc;
+    if ((rc = fmt_pack_linear_raw(h->tune, &pool, h->cfg.dtype, host.data() + (size_t)Mt * Kt, nullptr, Nt, Kt, &w))) return rc;
+    GemmArgs g = base_args(a.W, w, Mt);
+    g.out_f32 = out, g.ldo = Nt;
+    if (what == 3) {
+      if ((rc = launch_gemm<T, EPI_F32>(g, 3, 4, T::is32 ? 4 : 8, s))) return rc;
+    } else {
+      // the 16-column tile as the chain runs it (attn.proj): out = 0 + 1 * (sum + 0), the sum itself
+      float* ones = nullptr;
+      if ((rc = pool.alloc(&ones, (size_t)Mt * Nt, false))) return rc;
+      const std::vector<float> one((size_t)Mt * Nt, 1.f);
+      FH_CHECK_HIP(hipMemcpy(ones, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice));
+      FH_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)Mt * Nt * sizeof(float), s));
+      g.gate = ones, g.ldg = Nt;
+      if ((rc = launch_gemm<T, EPI_GATE_RES>(g, 3, 1, T::is32 ? 4 : 8, s))) return rc;
+    }
+    FH_CHECK_HIP(hipStreamSynchronize(s));
+    return FLOAT_OK;
+  }
   FH_REQUIRE(what == 1 && in != nullptr, "float_fmt_debug: unknown request %d (or null input)", what);
   const int n = ntok * 3 * D;
   hipLaunchKernelGGL((fmt_dbg_to16_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, h->qkv16, in, n);

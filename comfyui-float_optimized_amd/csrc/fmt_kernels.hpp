@@ -15,10 +15,34 @@
 #include "common.hpp"
 #include "fmt_pack.hpp"
 
+// k-steps of operands in flight per wave.  With 4 k-blocks per wave (K = 1024 over 8 waves) PF = 4 puts the whole
+// K slice in flight at once: one memory round trip instead of two for the 48x64 tilings (7 fragments per k-step,
+// 112 operand registers + 48 accumulators still fit two waves per SIMD)
+template <class T, int MTW, int NT>
+constexpr int fmt_gemm_pf() {
+  return T::is32 ? 1 : ((MTW + NT <= 7) ? 4 : ((MTW + NT <= 8) ? 3 : 2));
+}
+// The instantiations that carry the straight-line form of the body (FLAT below) beside the general one: the tilings of the
+// one-clip step chain - qkv / fc1 / fc2 (48 x 64, 8 waves), proj and the head (48 x 16, 8 waves), x-embed (64 x 16, 4 waves).
+// Every other tiling keeps the general form alone: the straight-line form's registers would cost the small ones a wave per SIMD.
+template <class T, int MTW, int NT, int NW, int EPI>
+constexpr bool fmt_gemm_has_flat() {
+  if (T::is32) return false;
+  if (EPI == EPI_XEMBED) return MTW == 4 && NT == 1 && NW == 4;
+  return NW == 8 && MTW == 3 && (NT == 4 || EPI == EPI_GATE_RES || EPI == EPI_CFG);
+}
+
 // The kernel's body as a device function: `bid` of `nblk` workgroups (blockIdx.x of gridDim.x for the stand-alone launch, the
 // stage's virtual block for fmt_mega_kernel).  COH: the activations (A operand, residual stream) were produced earlier in the
 // same kernel -> coherent loads (fh_load16<true>), and every activation store writes through.
-template <class T, int MTW, int NT, int NW, int EPI, bool COH>
+// FLAT: the wave's K slice is exactly the PF k-steps in flight (every GEMM of the one-clip chain: K = 1024 over 8 waves, fc2 with
+// its K slices).  The body is then straight-line code from the first operand load to the last MFMA - every load of the prologue
+// is issued by every lane, none is issued in the K loop - and the compiler's s_waitcnt vmcnt in front of k-step p counts exactly
+// the loads behind that step's operands: the later steps, the epilogue operands and the touched lines stay in flight under the
+// MFMAs.  With the run-time trip counts of the general form it must assume the youngest load is the one it waits for, which
+// makes every wave wait for its whole K slice AND the touched HBM lines in front of its first MFMA.  The straight-line form
+// retires the touch behind its last store; everything else - the exchange through LDS, the epilogues - is the general form's.
+template <class T, int MTW, int NT, int NW, int EPI, bool COH, bool FLAT = false>
 __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned bid, const unsigned nblk) {
   constexpr int BN = NT * 16;
   constexpr int ROWS = MTW * 16;
@@ -29,10 +53,7 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
   // (415 vs 320 us per evaluation).  The residual stream and the split-K slabs (read once, by one workgroup) stay coherent.
   auto ldA = [](const typename T::elem* p) -> typename T::pack8 { return T::load8(p); };
   constexpr int NTHR = NW * 64;
-  // k-steps of operands in flight per wave.  With 4 k-blocks per wave (K = 1024 over 8 waves) PF = 4 puts the whole
-  // K slice in flight at once: one memory round trip instead of two for the 48x64 tilings (7 fragments per k-step,
-  // 112 operand registers + 48 accumulators still fit two waves per SIMD)
-  constexpr int PF = T::is32 ? 1 : ((MTW + NT <= 7) ? 4 : ((MTW + NT <= 8) ? 3 : 2));
+  constexpr int PF = fmt_gemm_pf<T, MTW, NT>();
   typedef typename T::elem E;
   typedef typename T::pack8 P8;
   extern __shared__ __attribute__((aligned(16))) float red[];  // [NW][ROWS][BN]
@@ -55,7 +76,7 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
 
   const int KB = g.K >> 5;
   const int KBs = (EPI == EPI_PARTIAL) ? g.kbs : KB;  // k-blocks of this workgroup's K slice
-  const int KBw = (int)((unsigned)KBs / NW);          // k-blocks per wave
+  const int KBw = FLAT ? PF : (int)((unsigned)KBs / NW);  // k-blocks per wave
   const E* Ap = reinterpret_cast<const E*>(g.A) + ((size_t)mt0 * KB + ks * KBs + w * KBw) * 512 + lane * 8;
   const E* Wp = reinterpret_cast<const E*>(g.W) + ((size_t)nb0 * KB + ks * KBs + w * KBw) * 512 + lane * 8;
   const size_t tstride = (size_t)KB * 512;
@@ -63,7 +84,7 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
   P8 a[PF][MTW], b[PF][NT];
 #pragma unroll
   for (int p = 0; p < PF; ++p) {
-    if (p < KBw) {
+    if (FLAT || p < KBw) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) b[p][j] = T::load8_nt(Wp + j * tstride + (size_t)p * 512);
 #pragma unroll
@@ -76,8 +97,10 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
   float4 res_pf[2], gate_pf[2];
   if constexpr (kEarlyRes) {
     const int r = threadIdx.x / (NT * 2), cg = threadIdx.x % (NT * 2);
-    const int row = m0 + r, nb = n0 + cg * 8;
-    if (r < ROWS && row < g.M) {
+    int row = m0 + r;
+    const int nb = n0 + cg * 8;
+    if constexpr (FLAT) row = min(m0 + min(r, ROWS - 1), g.M - 1);  // a thread without an item fetches a row that exists: no branch
+    if (FLAT || (r < ROWS && row < g.M)) {
       const float* o = g.out_f32 + (size_t)row * g.ldo + nb;
       const float* gt = g.gate + (size_t)row * g.ldg + nb;
       res_pf[0] = fh_load_f4<COH>(o);
@@ -89,9 +112,24 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
   // only the epilogue kinds whose launches are given a TouchSpec carry the code (2 registers, a branch)
   constexpr bool kTouch = (EPI == EPI_GELU_P16 || EPI == EPI_T16 || EPI == EPI_GATE_RES || EPI == EPI_PARTIAL);
   unsigned touched[2] = {0u, 0u};
-  if constexpr (kTouch) {
+  if constexpr (kTouch && FLAT) {
+    __builtin_amdgcn_sched_barrier(0);  // behind the operand loads
+    fmt_touch_always(g.touch, Wp, bid & 7, (bid >> 3) * NTHR + threadIdx.x, (nblk >> 3) * NTHR, touched);
+  } else if constexpr (kTouch) {
     if (g.touch.W) fmt_touch(g.touch, bid & 7, (bid >> 3) * NTHR + threadIdx.x, (nblk >> 3) * NTHR, touched);
   }
+  if constexpr (FLAT) {
+    // (the scheduler may not move a load down into the MFMAs to save registers, nor a k-step up across a wait)
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < MTW; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = T::mfma(a[p][i], b[p][j], acc[i][j]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  } else
   for (int kb0 = 0; kb0 < KBw; kb0 += PF) {
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
@@ -112,7 +150,9 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
     }
   }
 
-  if constexpr (kTouch) {
+  // (the general form has waited for the touched lines in its K loop already; holding their registers to the end would cost
+  // the 16-wave tilings spills and the smallest ones a wave)
+  if constexpr (kTouch && !FLAT) {
     if (g.touch.W) fmt_touch_retire(touched);
   }
   // C/D map of mfma_f32_16x16x32: col = lane & 15, row = (lane >> 4) * 4 + reg
@@ -251,6 +291,9 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
     }
   }
   if constexpr (EPI == EPI_CFG || EPI == EPI_T16 || EPI == EPI_SILU_P16 || EPI == EPI_GELU_P16 || EPI == EPI_GELUERF_P16) fh_range_flush<T>(g.sat, rm);
+  // straight-line form: behind the last store - the touched lines come from HBM and are the wave's youngest loads, and nothing
+  // reads their registers
+  if constexpr (kTouch && FLAT) fmt_touch_retire_last(touched);
 }
 
 template <class T, int MTW, int NT, int NW, int EPI>
@@ -261,6 +304,14 @@ __global__ __launch_bounds__(NW * 64) void fmt_gemm_kernel(const u16* A, const u
   GemmArgs g;
   static_cast<GemmHead&>(g) = GemmHead{A, W, K, kbs, ksplit, mblk, GemmDecode{mblk_mul, nbx, nbx_mul, nbn, nbn_mul, bits}};
   static_cast<GemmTail&>(g) = t;
+  // the straight-line form where the tiling carries it and the K slice is its PF k-steps per wave: a uniform branch on two
+  // preloaded scalars
+  if constexpr (fmt_gemm_has_flat<T, MTW, NT, NW, EPI>()) {
+    if ((EPI == EPI_PARTIAL ? kbs : (K >> 5)) == NW * fmt_gemm_pf<T, MTW, NT>()) {
+      fmt_gemm_body<T, MTW, NT, NW, EPI, false, true>(g, blockIdx.x, gridDim.x);
+      return;
+    }
+  }
   fmt_gemm_body<T, MTW, NT, NW, EPI, false>(g, blockIdx.x, gridDim.x);
 }
 // the host's side of that parameter list: launches fmt_gemm_kernel<...> `kern` with the head's members and the tail of `g`

@@ -65,13 +65,41 @@ __device__ __forceinline__ void fmt_touch(const TouchSpec& t, unsigned xcd, unsi
 #pragma unroll
   for (int i = 0; i < N; ++i) v[i] = fmt_touch_line(t, xcd, first + (unsigned)i * stride);
 }
-// keeps the touched dwords' registers reserved until the loads have landed, at no other cost
+// The same without a branch: a lane with no line to touch (none given, or past the XCD's share) re-reads `idle`, an address it
+// has requested already.  Every lane then issues exactly N loads, so the waits the compiler counts for OLDER loads of straight-
+// line code leave these outstanding; behind a branch it has to assume that they were skipped and waits for everything.
+template <int N>
+__device__ __forceinline__ void fmt_touch_always(const TouchSpec& t, const void* idle, unsigned xcd, unsigned first, unsigned stride,
+                                                 unsigned (&v)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    unsigned l = first + (unsigned)i * stride;
+    const bool on = t.W != nullptr && l < t.total;
+    l = on ? l : 0u;
+    const unsigned r = l >> t.run_shift, off = l & ((1u << t.run_shift) - 1u);
+    const unsigned cb = r >> t.nt_shift, jn = r & ((1u << t.nt_shift) - 1u);
+    const unsigned ks = xcd >> t.p_shift, bx = (cb << t.p_shift) + (xcd & ((1u << t.p_shift) - 1u));
+    const char* p = t.W + (size_t)((bx << t.nt_shift) + jn) * t.tile_bytes + ((size_t)((ks << t.run_shift) + off) << 7);
+    v[i] = *reinterpret_cast<const unsigned*>(on ? p : reinterpret_cast<const char*>(idle));
+  }
+}
+// Keeps the touched dwords' registers reserved until the loads have landed, at no other cost: the wave waits here for the
+// touched lines (HBM), so it stands where nothing else is left to do - behind a kernel's last store.
 template <int N>
 __device__ __forceinline__ void fmt_touch_retire(const unsigned (&v)[N]) {
   unsigned o = 0u;
 #pragma unroll
   for (int i = 0; i < N; ++i) o |= v[i];
   asm volatile("" ::"v"(o));
+}
+// The same at the end of a kernel: the compiler may not lift it (and the wait for the touched lines with it) over the stores
+// in front of it, as the listing of fmt_attn_kernel shows it doing with the form above.
+template <int N>
+__device__ __forceinline__ void fmt_touch_retire_last(const unsigned (&v)[N]) {
+  unsigned o = 0u;
+#pragma unroll
+  for (int i = 0; i < N; ++i) o |= v[i];
+  asm volatile("" ::"v"(o) : "memory");
 }
 
 // The argument block of a GEMM launch in two parts.  GemmHead is what the address of the first operand load and the block

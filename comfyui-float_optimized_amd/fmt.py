@@ -66,6 +66,20 @@ class FlowMatchingTransformerHIP:
                                                       native.stream_ptr(self.device)))
         return out
 
+    @torch.no_grad()
+    def gemm_tile_probe(self, a, w):
+        """a (48, 1024), w (64 | 16, 1024) -> (48, N) = a w^T in fp32: one workgroup of the chain's GEMM, K split over its waves
+        (8, or 4 for an fp32 handle; wave i multiplies columns i * 1024 / waves .. of a and w) and summed through LDS."""
+        a, w = self._f(a), self._f(w)
+        if a.shape != (48, 1024) or w.shape not in ((64, 1024), (16, 1024)):
+            raise ValueError("a must be (48,1024) and w (64,1024) or (16,1024)")
+        buf = torch.cat([a, w]).contiguous()
+        out = torch.empty(48, w.shape[0], device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().float_fmt_debug(self._h, 3 if w.shape[0] == 64 else 4, native.dev_ptr(buf), native.dev_ptr(out),
+                                                      native.stream_ptr(self.device)))
+        return out
+
     def saturation(self, reset=False):
         """Threads with a clamped (+-65504) or non-finite 16-bit activation store since create / the last reset
         (float_fmt_saturation): 0 unless the checkpoint leaves fp16's range - then the result is not the reference's within the

@@ -204,6 +204,10 @@ int float_fmt_sample_begin_range(float_fmt_t* h, const float* wr, const float* w
  *   what = 1: the attention kernel of the chain on caller data: in (n_prev + n_cur, 3 * dim_h) = [q | k | v] rows of one
  *             CFG row, out (n_prev + n_cur, dim_h) = softmax(q k^T / sqrt(128) + band mask) v per head; with q = k = 0 and
  *             one-hot v rows the output shows which keys each query may see (enc_dec_mask, FMT.py:15-19).
+ *   what = 3 / 4: one workgroup of the chain's GEMM on caller data, 48 rows x 64 (3) or 16 (4) columns with K = 1024 split over
+ *             its 8 waves (4 in the fp32 mode; the 64-column tile exists for fp16 / bf16 only): in = [A (48, 1024) | W (N, 1024)],
+ *             out (48, N) = A W^T in fp32 with no bias.  Wave w multiplies columns w * 1024 / waves .. of A and W, so operands
+ *             that are zero outside one wave's columns show that wave's partial sum alone.  Synchronises the stream.
  * in / out are fp32 device pointers. */
 int float_fmt_debug(float_fmt_t* h, int32_t what, const float* in, float* out, void* stream);
 
