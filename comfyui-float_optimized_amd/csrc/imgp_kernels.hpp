@@ -21,6 +21,26 @@
 // bounds.  Positions: d P, (d + 1) P, (sx + 1) Q and n Q are at most 16384 * 1024 = 2^24.  The tie test doubles a remainder < D.
 // The feather numerator is 255 (d + 1) <= 255 * 2^14 < 2^22, the blend a face + (255 - a) src + 127 <= 255^2 + 127.  Everything
 // fits 32 bits: the only 64-bit values in the kernel are the frame bases and the products of imgp_div below.
+//
+// Kernel of float_img_paste_i420: the same pasted frames leaving as planar YUV 4:2:0, bitwise host_models.paste_i420.  One launch,
+// no LDS, no scratch, no atomics.
+//   imgp_paste_i420_kernel  An output frame is 3 H W / 2 bytes at out + f * that (formed in 64 bits): the Y plane H x W, then U and V
+//                      at H/2 x W/2.  A lane owns a cell of 2 rows x 4 columns: it forms the eight pasted RGB pixels with imgp_setup /
+//                      imgp_face / imgp_blend - the very bytes float_img_paste stores - and from them eight Y samples and the two
+//                      2 x 2 chroma blocks of the cell, so a block that straddles the box edge or the feather mixes pasted and
+//                      source PIXELS, as the definition does; chroma is never blended.  A workgroup owns 256 consecutive cells in
+//                      row-major cell order (block order: frame-major and XCD-affine, as above), so a wave stores 256 contiguous Y
+//                      bytes per row.
+//                      FAST (W % 4 == 0 and out 4-byte aligned, chosen on the host per launch): every frame, the Y plane and its
+//                      rows are dword-aligned and the chroma planes and rows 2-byte aligned (H W / 4 may be odd in dwords, never in
+//                      16-bit words), so a lane stores one dword of Y per row, 16 bits of U and 16 bits of V, and reads the source
+//                      as three unaligned dwords per row (12 bytes that end inside the row).
+//                      Otherwise (W % 4 == 2: rows 2-byte aligned, the last cell of a row has two columns, H W / 4 can be odd and V
+//                      then starts at an odd address; or a misaligned out) every load of the source and every store is a byte.
+// Accumulator width: the RGB in front of the conversion is the kernel's above, 0 ... 255.  Y = 66 R + 129 G + 25 B + 128 <= 56228
+// < 2^16; a chroma mean is (c00 + c01 + c10 + c11 + 2) >> 2 with a sum <= 1022; the U / V numerators lie in [-28432, 28688].  They
+// are signed 32-bit ints and >> is the arithmetic shift (floor), as in host_models.rgb8_to_i420.  Cell and pixel indices are below
+// H W <= 2^28 and a source offset 3 (y W + x) below 3 * 2^28, in unsigned 32 bits; the frame bases are 64-bit.
 #pragma once
 #include "common.hpp"
 
@@ -227,5 +247,106 @@ __global__ __launch_bounds__(kImgpThreads) void imgp_paste_kernel(const unsigned
     if (k >= nd) break;
     const unsigned i0 = head + 4u * k;  // i0 + 3 < N
     *reinterpret_cast<unsigned*>(o + i0) = imgp_bytes(fr, p, i0, 4, imgp_load_u32(src + i0));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// float_img_paste_i420: the pasted frames as planar YUV 4:2:0
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int kImgpCellW = 4;  // a lane's cell: 2 rows x 4 columns = one dword of Y per row, two chroma samples per plane
+
+// what the I420 kernel needs besides the plan (ImgpPlan is the RGB kernel's and stays as it is)
+struct ImgpYuv {
+  ImgpDiv dcx;       // / cells_x
+  unsigned cells_x;  // cells per pair of rows: ceil(W / 4); the last one has two columns when W % 4 == 2
+  unsigned cells;    // cells per frame: (H / 2) cells_x <= 2^25
+  unsigned spans;    // workgroups per frame, a multiple of 8
+  unsigned y_bytes;  // H W
+  unsigned c_bytes;  // (H / 2) (W / 2): a frame is y_bytes + 2 c_bytes
+};
+
+inline ImgpYuv imgp_make_yuv(int src_h, int src_w) {  // both even
+  ImgpYuv q{};
+  q.cells_x = ((unsigned)src_w + kImgpCellW - 1) / kImgpCellW;
+  q.dcx = imgp_make_div(q.cells_x);
+  q.cells = (unsigned)(src_h / 2) * q.cells_x;
+  const unsigned spans = (q.cells + kImgpThreads - 1) / kImgpThreads;
+  q.spans = std::max(8u, (spans + 7u) & ~7u);
+  q.y_bytes = (unsigned)src_h * (unsigned)src_w;
+  q.c_bytes = (unsigned)(src_h / 2) * (unsigned)(src_w / 2);
+  return q;
+}
+
+// 8-bit BT.601 limited range in int32, >> the arithmetic shift: host_models.rgb8_to_i420
+__device__ __forceinline__ unsigned imgp_i420_y(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
+__device__ __forceinline__ unsigned imgp_i420_u(int mr, int mg, int mb) { return (unsigned)(((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128); }
+__device__ __forceinline__ unsigned imgp_i420_v(int mr, int mg, int mb) { return (unsigned)(((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128); }
+
+template <bool FAST>
+__global__ __launch_bounds__(kImgpThreads) void imgp_paste_i420_kernel(const unsigned char* __restrict__ src, const unsigned char* __restrict__ frames,
+                                                                       unsigned char* __restrict__ out, const ImgpPlan p, const ImgpYuv q) {
+  // block -> (frame, span): all frames of a span back to back on ids congruent mod 8
+  const unsigned slot = blockIdx.x >> 3;
+  const unsigned f = slot % (unsigned)p.n_frames;
+  const unsigned span = (slot / (unsigned)p.n_frames) * 8u + (blockIdx.x & 7u);
+  const unsigned k = span * (unsigned)kImgpThreads + threadIdx.x;
+  if (k >= q.cells) return;
+  const unsigned cy = imgp_div(k, q.dcx), cx = k - cy * q.cells_x;
+  const unsigned W = (unsigned)p.src_w, x0 = cx * kImgpCellW, y0 = 2u * cy;
+  const int ncol = FAST ? kImgpCellW : min(kImgpCellW, (int)(W - x0));  // 4, or 2 in the last cell of a row with W % 4 == 2
+  const unsigned char* fr = frames + (size_t)f * p.in_bytes;
+  unsigned char* o = out + (size_t)f * ((size_t)q.y_bytes + 2u * (size_t)q.c_bytes);
+  unsigned m[3] = {0u, 0u, 0u};  // per channel: the sum of the cell's left 2 x 2 block in bits 0 ... 15, of its right one in 16 ... 31 (<= 1020 each)
+  for (int r = 0; r < 2; ++r) {
+    const unsigned row = (y0 + (unsigned)r) * W + x0;  // pixel index of the row's first sample, < 2^28
+    const unsigned char* s = src + 3u * row;
+    unsigned a, b, c;  // the row's 3 ncol source bytes, little-endian
+    if (FAST) {
+      a = imgp_load_u32(s), b = imgp_load_u32(s + 4), c = imgp_load_u32(s + 8);
+    } else {
+      unsigned w[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int i = 0; i < 3 * kImgpCellW; ++i)
+        if (i < 3 * ncol) w[i >> 2] |= (unsigned)s[i] << (8 * (i & 3));
+      a = w[0], b = w[1], c = w[2];
+    }
+    unsigned yw = 0;
+    for (int col = 0; col < ncol; ++col) {
+      unsigned rgb[3] = {a & 255u, (a >> 8) & 255u, (a >> 16) & 255u};
+      a = (a >> 24) | (b << 8), b = (b >> 24) | (c << 8), c >>= 24;  // the next pixel's bytes move down
+      ImgpPixel px;
+      imgp_setup(p, (int)x0 + col, (int)y0 + r, &px);
+      if (px.inside && px.alpha != 0) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rgb[ch] = imgp_blend(imgp_face(fr, p, px, ch), rgb[ch], px.alpha);
+      }
+      yw |= imgp_i420_y((int)rgb[0], (int)rgb[1], (int)rgb[2]) << (8 * col);
+      const int sh = 16 * (col >> 1);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) m[ch] += rgb[ch] << sh;
+    }
+    unsigned char* yo = o + row;
+    if (FAST) {
+      *reinterpret_cast<unsigned*>(yo) = yw;  // out, y_bytes + 2 c_bytes and W are multiples of 4
+    } else {
+      for (int col = 0; col < ncol; ++col) yo[col] = (unsigned char)(yw >> (8 * col));
+    }
+  }
+  unsigned uv[2];  // U | V << 8 of the left and the right block
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    const int mr = (int)(((m[0] >> (16 * blk)) & 0xffffu) + 2u) >> 2, mg = (int)(((m[1] >> (16 * blk)) & 0xffffu) + 2u) >> 2,
+              mb = (int)(((m[2] >> (16 * blk)) & 0xffffu) + 2u) >> 2;
+    uv[blk] = imgp_i420_u(mr, mg, mb) | (imgp_i420_v(mr, mg, mb) << 8);
+  }
+  const unsigned at = cy * (W >> 1) + (x0 >> 1);  // < c_bytes
+  unsigned char* uo = o + q.y_bytes + at;
+  unsigned char* vo = uo + q.c_bytes;
+  if (FAST) {  // W / 2 and x0 / 2 are even, c_bytes is even: 2-byte aligned
+    *reinterpret_cast<unsigned short*>(uo) = (unsigned short)((uv[0] & 255u) | ((uv[1] & 255u) << 8));
+    *reinterpret_cast<unsigned short*>(vo) = (unsigned short)((uv[0] >> 8) | (uv[1] & 0xff00u));
+  } else {
+    uo[0] = (unsigned char)uv[0], vo[0] = (unsigned char)(uv[0] >> 8);
+    if (ncol == kImgpCellW) uo[1] = (unsigned char)uv[1], vo[1] = (unsigned char)(uv[1] >> 8);
   }
 }

@@ -453,6 +453,16 @@ def rgb8_to_i420(frames_u8):
     return out[0] if single else out
 
 
+def paste_i420(src8, frames8, rect, feather):
+    """The pasted frames as planar YUV 4:2:0: rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather)) -> (T, 3H/2, W) uint8 at the
+    portrait's size, H and W even (ValueError otherwise - nothing is padded or cropped).  Chroma is the 2 x 2 mean of the PASTED
+    8-bit RGB samples, so a block that straddles the box edge or the feather mixes pasted and source pixels; it is never a blend
+    of chroma.  The definition `float_img_paste_i420` (image.paste_frames_device(out_format="i420")) is held to bit for bit."""
+    if src8.dim() == 3 and (src8.shape[0] % 2 or src8.shape[1] % 2):
+        raise ValueError("paste_i420: a %d x %d portrait has an odd side; 4:2:0 chroma needs even sides" % (src8.shape[0], src8.shape[1]))
+    return rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather))
+
+
 def y4m_rate(fps):
     """The frame rate of a Y4M header as a fraction.
     Rule 1 (NTSC family): a non-integer float fps with |fps * 1.001 - n| < 1e-4 for an integer n >= 1 is n * 1000 / 1001:

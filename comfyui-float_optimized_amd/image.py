@@ -130,15 +130,40 @@ def _u8_device(t, what, dims, device):
     return t.detach().to(device, non_blocking=True).contiguous()
 
 
+def paste_format(what, out_format):
+    """The frame format of a pasted producer: None | "rgb" -> "rgb" ((T, H, W, 3) uint8), "i420" -> "i420" ((T, 3H/2, W) uint8)."""
+    if out_format in (None, "rgb"):
+        return "rgb"
+    if out_format != "i420":
+        raise ValueError("%s: out_format must be None, 'rgb' or 'i420' (got %r)" % (what, out_format))
+    return "i420"
+
+
+def require_even_sides(what, H, W):
+    """4:2:0 chroma halves both sides; a pasted clip has the portrait's size.  Nothing is padded or cropped."""
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError("%s: a %d x %d portrait cannot leave as I420 - 4:2:0 chroma needs even sides (crop or resize the portrait, "
+                         "or take the RGB frames)" % (what, H, W))
+
+
+def pasted_frame_shape(H, W, fmt):
+    """The shape of one pasted frame: (H, W, 3), or (3H/2, W) as I420."""
+    return (3 * H // 2, W) if fmt == "i420" else (H, W, 3)
+
+
 @torch.no_grad()
-def paste_frames_device(src8, frames8, rect, feather=None, out=None):
+def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None):
     """float_img_paste: frames8 (T, h, w, 3) uint8 - what the decoder's decode_u8 leaves in HBM - back in the portrait src8 (H, W,
     3) uint8 at the box rect = (x0, y0, w, h) in source coordinates (what InferenceAgent.host_inputs_placed returns; it may reach
     outside the image) -> (T, H, W, 3) uint8 on the device, bitwise host_models.paste_rgb8(src8, frames8, rect, feather).
     feather: the width in source pixels over which the box's open sides fade into the portrait; None = rect_w // 16
     (host_models.default_feather: a visual choice, not a measurement).  Host tensors are uploaded; the device is that of frames8,
     else of src8, else cuda:0.  out: a contiguous (T, H, W, 3) uint8 tensor on that device to write into.  One launch on the
-    current stream; nothing is allocated besides `out`, nothing synchronises."""
+    current stream; nothing is allocated besides `out`, nothing synchronises.
+    out_format: None | "rgb" as above; "i420" is float_img_paste_i420, paste and colour conversion in one kernel -> (T, 3H/2, W)
+    uint8 planar YUV 4:2:0 (BT.601 limited range), bitwise host_models.paste_i420(src8, frames8, rect, feather), half the bytes;
+    H and W must be even (ValueError) and `out` is checked against that shape."""
+    fmt = paste_format("paste_frames_device", out_format)
     device = frames8.device if frames8.is_cuda else (src8.device if src8.is_cuda else torch.device("cuda:0"))
     s = _u8_device(src8, "src8", 3, device)
     f = _u8_device(frames8, "frames8", 4, device)
@@ -151,14 +176,23 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None):
     if not 0 <= feather <= 1 << 30:
         raise ValueError("paste_frames_device: feather (%d) must be 0 ... 16384" % feather)
     T, H, W = int(f.shape[0]), int(s.shape[0]), int(s.shape[1])
+    if fmt == "i420":
+        require_even_sides("paste_frames_device", H, W)
+    shape = (T,) + pasted_frame_shape(H, W, fmt)
     with torch.cuda.device(device):
         if out is None:
-            out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (T, H, W, 3) or out.device != device or not out.is_contiguous()):
-            raise ValueError("paste_frames_device: out must be a contiguous (%d, %d, %d, 3) uint8 tensor on %s, got %s %s on %s"
-                             % (T, H, W, device, out.dtype, tuple(out.shape), out.device))
-        native.check(native.lib().float_img_paste(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
-                                                  x0, y0, w, h, feather, C.c_void_p(out.data_ptr()), native.stream_ptr(device)))
+            out = torch.empty(shape, dtype=torch.uint8, device=device)
+        elif (out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != device or not out.is_contiguous()):
+            raise ValueError("paste_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
+                             % (shape, device, out.dtype, tuple(out.shape), out.device))
+        L = native.lib()
+        if fmt == "i420":
+            native.check(L.float_img_paste_i420(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
+                                                x0, y0, w, h, feather, native.IMG_MATRIX_BT601_LIMITED, C.c_void_p(out.data_ptr()),
+                                                native.stream_ptr(device)))
+        else:
+            native.check(L.float_img_paste(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
+                                           x0, y0, w, h, feather, C.c_void_p(out.data_ptr()), native.stream_ptr(device)))
     return out
 
 

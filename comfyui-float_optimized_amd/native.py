@@ -13,6 +13,7 @@ AUD_FRONT_NORMALIZE = 1  # FLOAT_AUD_FRONT_NORMALIZE: the `flags` bit of float_a
 IMG_RGBA_MODES = {"discard_alpha": 0, "blend_with_color": 1, "replace_with_color": 2}  # FLOAT_IMG_RGBA_*: float_img_front's `rgba_mode`
 IMG_OUT_NCHW_PM1, IMG_OUT_HWC_U8 = 0, 1  # FLOAT_IMG_OUT_*: float_img_front's `out_mode`
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
+IMG_MATRIX_BT601_LIMITED = 0  # FLOAT_IMG_MATRIX_BT601_LIMITED: the `matrix` argument of float_img_paste_i420
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "heun2": 3, "heun3": 4}
 DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP16, "float16": FLOAT_DT_FP16,
           "fp32": FLOAT_DT_FP32, "float32": FLOAT_DT_FP32}  # fp32: the verification mode of the FMT and decoder operators
@@ -140,6 +141,7 @@ _SIGNATURES = {
     "float_img_front_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_img_front": (C.c_int, [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_img_paste": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]),
+    "float_img_paste_i420": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]),
     "float_jpg_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_jpg_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }

@@ -238,25 +238,41 @@ class _FrameSink:
 
 
 class _PasteSink:
-    """What FloatHotPath._ring does per slot for stream_to_host_pasted: a slot is a pinned (L, H, W, 3) uint8 buffer of pasted
-    frames; the device buffers of L 8-bit crops and of L pasted frames are shared by all of them (safe in stream order)."""
+    """What FloatHotPath._ring does per slot for stream_to_host_pasted: a slot is a pinned (L,) + frame_shape uint8 buffer of pasted
+    frames - (H, W, 3), or (3H/2, W) with out_format="i420" - and the device buffers of L 8-bit crops and of L pasted frames are
+    shared by all of them (safe in stream order).  generate_pasted runs its groups through the same three steps (`paste`).  The
+    format and, for I420, the portrait's even sides are checked when the sink is made: at the call."""
     name = "stream_to_host_pasted"
 
-    def __init__(self, hot, place, feather):
+    def __init__(self, hot, place, feather, out_format=None, name=None):
         self.hot, self.place, self.feather = hot, place, feather
+        self.name = name or self.name
+        self.fmt = image.paste_format(self.name, out_format)
+        if self.fmt == "i420":
+            image.require_even_sides(self.name, *place.size)
+        self.frame_shape = image.pasted_frame_shape(*place.size, self.fmt)
+
+    def device_buffers(self, n):
+        """the shared device buffers of n 8-bit crops and of n pasted frames"""
+        dev, R = self.hot.device, self.hot.size
+        self.crops = torch.empty(n, R, R, 3, dtype=torch.uint8, device=dev)
+        self.pasted = torch.empty((n,) + self.frame_shape, dtype=torch.uint8, device=dev)
 
     def open(self, slots):
-        dev, L, R, (H, W) = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size, self.place.size
-        ring = [torch.empty(L, H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
-        self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev)
-        self.pasted = torch.empty(L, H, W, 3, dtype=torch.uint8, device=dev)
+        L = self.hot.cfg.num_frames_for_clip
+        ring = [torch.empty((L,) + self.frame_shape, dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+        self.device_buffers(L)
         return ring
 
-    def enqueue(self, slot, s_r_d, rows):
+    def paste(self, host, s_r_d, rows):
+        """decode_u8, the paste (and, for I420, the colour conversion in the same kernel), one non-blocking copy into `host`"""
         n = rows.shape[0]
         self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
-        image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n])
-        slot[:n].copy_(self.pasted[:n], non_blocking=True)
+        image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n], out_format=self.fmt)
+        host.copy_(self.pasted[:n], non_blocking=True)
+
+    def enqueue(self, slot, s_r_d, rows):
+        self.paste(slot[:rows.shape[0]], s_r_d, rows)
 
     def block(self, slot, f0, f1, ev, st):
         return FrameBlock(f0, f1, slot[:f1 - f0])
@@ -548,46 +564,52 @@ class FloatHotPath:
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     def stream_to_host_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                              noise=None, place=None, feather=None, slots=3):
+                              noise=None, place=None, feather=None, slots=3, out_format=None):
         """stream_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: a generator of
         FrameBlock(first, last, frames), `frames` a (last - first, H, W, 3) uint8 view of a pinned ring slot, bitwise
         host_models.paste_rgb8(place.src8, the window's 8-bit crops, place.rect, feather).  place: a Placement (the portrait on
         this device and the box); feather: source pixels, None = rect_w // 16 (host_models.default_feather).  Per window:
         the chain, decode_u8 into a shared device buffer of 50 crops, float_img_paste into a shared device buffer of 50 pasted
         frames, one non-blocking copy into the slot.  The ring rules, lifetime and early exit are stream_to_host's; pinned memory
-        is slots x 50 x H x W x 3 bytes (940 MB at 1920 x 1088 and 3 slots)."""
+        is slots x 50 x H x W x 3 bytes (940 MB at 1920 x 1088 and 3 slots).
+        out_format="i420" (default None = "rgb": the above): `frames` is a (last - first, 3H/2, W) uint8 view, bitwise
+        host_models.paste_i420 of the same operands; float_img_paste_i420 pastes and converts in one kernel, and the device buffer
+        of pasted frames, the pinned slots and the copy are 3HW/2 bytes per frame - half of the above.  H and W must be even:
+        a ValueError here, at the call."""
         place = _check_place("stream_to_host_pasted", place, self.device)
-        sink = _PasteSink(self, place, feather)
+        sink = _PasteSink(self, place, feather, out_format)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     @torch.no_grad()
     def generate_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                        place=None, feather=None, out=None, return_rd=False):
+                        place=None, feather=None, out=None, return_rd=False, out_format=None):
         """generate_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: the chain of the
         whole clip, then per group of num_frames_for_clip frames decode_u8, float_img_paste and one non-blocking copy into the
         pinned (T, H, W, 3) uint8 result - device memory stays at 50 crops and 50 pasted frames whatever T is.  The result is
-        complete once the current stream has been synchronised (the callers that hand it to the user do that)."""
+        complete once the current stream has been synchronised (the callers that hand it to the user do that).
+        out_format="i420" (default None = "rgb": the above): the result is (T, 3H/2, W) uint8 planar YUV 4:2:0, bitwise
+        host_models.paste_i420; float_img_paste_i420 pastes and converts in one kernel, and the device buffer of pasted frames, the
+        result and the copies are 3HW/2 bytes per frame.  H and W must be even - a ValueError before anything is enqueued - and
+        an `out` of another shape than the format's is a ValueError."""
         place = _check_place("generate_pasted", place, self.device)
+        sink = _PasteSink(self, place, feather, out_format, name="generate_pasted")
         self.require_no_stream("generate_pasted")
         if feats is not None:
             self.dec.set_feats(feats)
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
         rd = _rows(r_d)
-        T, L, R, (H, W) = rd.shape[0], self.cfg.num_frames_for_clip, self.size, place.size
+        T, L = rd.shape[0], self.cfg.num_frames_for_clip
+        shape = (T,) + sink.frame_shape
         if out is None:
-            out = torch.empty(T, H, W, 3, dtype=torch.uint8, pin_memory=True)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (T, H, W, 3) or out.is_cuda or not out.is_contiguous():
-            raise ValueError("generate_pasted: out must be a contiguous CPU uint8 tensor of shape %s" % ((T, H, W, 3),))
+            out = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.is_cuda or not out.is_contiguous():
+            raise ValueError("generate_pasted: out must be a contiguous CPU uint8 tensor of shape %s" % (shape,))
         s_r_d = s_r.to(self.device, torch.float32).reshape(-1).contiguous()
         with torch.cuda.device(self.device):
-            crops = torch.empty(min(T, L), R, R, 3, dtype=torch.uint8, device=self.device)
-            pasted = torch.empty(min(T, L), H, W, 3, dtype=torch.uint8, device=self.device)
+            sink.device_buffers(min(T, L))
             for f0 in range(0, T, L):
-                n = min(L, T - f0)
-                self.dec.decode_u8(s_r_d, rd[f0:f0 + n], out=crops[:n])
-                image.paste_frames_device(place.src8, crops[:n], place.rect, feather, out=pasted[:n])
-                out[f0:f0 + n].copy_(pasted[:n], non_blocking=True)
+                sink.paste(out[f0:f0 + min(L, T - f0)], s_r_d, rd[f0:f0 + L])
         return (out, r_d) if return_rd else out
 
     def _check_stream_call(self, what, slots, wa):

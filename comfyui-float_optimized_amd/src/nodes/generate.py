@@ -10,7 +10,8 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
-from ...image import detector_view_device, front_takes, image_to_device, preprocess_image_device, require_jpeg_sides, source_rgb8_device
+from ...image import (detector_view_device, front_takes, image_to_device, paste_format, preprocess_image_device, require_even_sides,
+                      require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
 
@@ -507,15 +508,18 @@ class InferenceAgent:
             return w.frames
 
     # ------------------------------------------------------------------ paste back: the frames in the user's portrait
-    def _paste_call(self, what, ref_img, jpeg_out=False):
-        """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take."""
+    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None):
+        """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take; with
+        out_format="i420", a portrait with an odd side; an out_format that is none of None, "rgb", "i420"."""
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         if jpeg_out:
             require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]))
+        if paste_format(what, out_format) == "i420":
+            require_even_sides(what, int(img.shape[0]), int(img.shape[1]))
 
     @torch.no_grad()
     def infer_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                     feather=None, out=None):
+                     feather=None, out=None, out_format=None):
         """run_inference whose frames are the user's portrait with the generated face pasted back: (T, H, W, 3) uint8 in pinned host
         memory at the portrait's own size, bitwise host_models.paste_rgb8(place.src8, infer_device(s, a, out_dtype=torch.uint8),
         place.rect, feather) with (s, a, place) = host_inputs_placed(ref_img, ref_audio, no_crop).  The 8-bit crops never leave
@@ -523,30 +527,71 @@ class InferenceAgent:
         source pixels over which the box fades into the portrait where its edge lies inside the image; None = rect_w // 16, a
         visual choice, not a measurement.  With no_crop the box is the whole image: the frames resized to the portrait's size.
         FLOAT_AMD_RANGE applies as in infer_device (auto rebuilds and runs the clip again); FLOAT_AMD_VERIFY is NOT applied and
-        FLOAT_AMD_OVERLAP is ignored."""
+        FLOAT_AMD_OVERLAP is ignored.
+        out_format="i420" (default None = "rgb": the above): (T, 3H/2, W) uint8 planar YUV 4:2:0 in pinned host memory (BT.601
+        limited range), bitwise host_models.rgb8_to_i420 of the RGB result = host_models.paste_i420(...): paste and conversion are
+        one kernel and half the bytes cross PCIe.  Any even size is taken (1920 x 1080); a portrait with an odd side is a
+        ValueError at this call, before anything runs - nothing is padded or cropped.  FLOAT_AMD_RANGE applies as above."""
+        self._paste_call("infer_pasted", ref_img, out_format=out_format)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             host = self.G.generate_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                          noise=noise, place=place, feather=feather, out=out)
+                                          noise=noise, place=place, feather=feather, out=out, out_format=out_format)
             torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
             if self.check_range("InferenceAgent.infer_pasted", allow_rebuild=True) != "rebuilt":
                 return host  # otherwise once more, in the wider types
 
     def stream_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                      feather=None, slots=3):
+                      feather=None, slots=3, out_format=None):
         """The streaming sibling of infer_pasted: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
         frame order - concatenated, the frames infer_pasted returns for the same inputs and seed.  The ring rules are
         stream_device's: `frames` is a (last - first, H, W, 3) uint8 view of one of `slots` pinned buffers, complete when yielded,
         OVERWRITTEN once the generator has been advanced again; slots < 2 raises ValueError at the call; while the stream is open
         every other producer on this agent raises RuntimeError.  FLOAT_AMD_RANGE is applied once after the last block (auto acts
-        as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored.
+        out_format="i420": `frames` is a (last - first, 3H/2, W) uint8 view, the frames of infer_pasted(out_format="i420"); the
+        pinned slots are half the size.  A portrait with an odd side raises ValueError here, at the call."""
         self._check_stream_call("stream_pasted", slots)
+        self._paste_call("stream_pasted", ref_img, out_format=out_format)
 
         def _stream_pasted(c, noise, place):
             return self.G.stream_to_host_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
-                                                e_cfg_scale, noise=noise, place=place, feather=feather, slots=int(slots))
+                                                e_cfg_scale, noise=noise, place=place, feather=feather, slots=int(slots),
+                                                out_format=out_format)
         return self._stream_placed("InferenceAgent.stream_pasted", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted)
+
+    def write_y4m(self, path_or_file, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False,
+                  seed=25, fps=None, paste_back=False, feather=None, slots=3):
+        """A clip for an encoder: host_inputs, a stream of I420 blocks, and host_models.Y4MWriter on `path_or_file` - a path, or an
+        object with write(), which may be a non-seekable pipe to ffmpeg's or x264's stdin (the header goes out first and nothing
+        is patched afterwards).  The frames are yuv420p, BT.601 limited range: the consumer converts no colours.  Y4M carries
+        NO AUDIO: the clip's sound has to be given to the encoder separately (write_video writes a file with an audio track).
+        fps defaults to opt.fps.  Returns the number of frames written.
+        paste_back=False: stream_device(out_format="i420") at the model's size.
+        paste_back=True: stream_pasted(out_format="i420", feather=feather) - the user's portrait with the generated face pasted
+        back, at the portrait's size, which must have even sides (ValueError otherwise, before anything runs or a file is opened).
+        Pinned memory is `slots` x 50 frames of 1.5 bytes per pixel whatever the clip's length."""
+        o = self.opt
+        fps = o.fps if fps is None else fps
+        if paste_back:
+            img = ref_img[0] if ref_img.dim() == 4 else ref_img
+            height, width = int(img.shape[0]), int(img.shape[1])
+            blocks = self.stream_pasted(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, slots,
+                                        out_format="i420")
+        else:
+            height = width = o.input_size
+            self._check_stream_call("write_y4m", slots)
+            with torch.no_grad():
+                s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+            blocks = self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format="i420", slots=slots)
+        try:
+            with host_models.Y4MWriter(path_or_file, width, height, fps) as w:
+                for blk in blocks:
+                    w.write(blk.frames)
+                return w.frames
+        finally:
+            blocks.close()  # a writer that failed leaves no stream open on the agent
 
     def _stream_placed(self, where, ref_img, ref_audio, no_crop, emo, seed, start):
         with torch.no_grad():

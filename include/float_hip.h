@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_paste (the generated frames back in the source portrait on the device),
+/* Stays 6: float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
+ * float_img_paste (the generated frames back in the source portrait on the device),
  * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
  * float_img_front / float_img_front_work_bytes (the image front end on the device),
  * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
@@ -588,6 +589,28 @@ int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t chan
 int float_img_paste(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* frames8, int32_t n_frames, int32_t fr_h,
                     int32_t fr_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t feather, uint8_t* out,
                     void* stream);
+
+/* The same pasted frames leaving as planar YUV 4:2:0, pasted and converted in one kernel: out is (n_frames, 3 src_h / 2, src_w)
+ * uint8 I420 - per frame the Y plane src_h x src_w, then U and V at src_h / 2 x src_w / 2, row-major, contiguous (ffmpeg's
+ * yuv420p) - at 1.5 bytes per pixel instead of 3.  Bitwise host_models.paste_i420 = rgb8_to_i420(paste_rgb8(...)): the pasted
+ * 8-bit RGB samples are those of float_img_paste above, and from them
+ *   Y  = ((66 R + 129 G + 25 B + 128) >> 8) + 16                 per pixel
+ *   Mc = (c00 + c01 + c10 + c11 + 2) >> 2                        per 2 x 2 block and channel c of the PASTED samples
+ *   U  = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128,  V = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128
+ * in int32 with >> the arithmetic shift.  Chroma is not blended: a block that straddles the box edge or the feather averages
+ * pasted and source pixels.  `matrix` selects the conversion; FLOAT_IMG_MATRIX_BT601_LIMITED (0, the matrix of
+ * float_dec_frames_i420) is the only one, anything else is FLOAT_E_INVALID.
+ * Limits: those of float_img_paste, and src_h, src_w even and >= 2; any even size is taken (1920 x 1080).  The pointers are DEVICE
+ * pointers of any alignment; out must not overlap the inputs.  With src_w % 4 == 0 and out 4-byte aligned the kernel stores dwords
+ * of Y and 16-bit pairs of U and V, otherwise bytes; the bytes stored are the same.  A frame is 3 src_h src_w / 2 bytes; frame
+ * bases are formed in 64 bits.
+ * Enqueues one kernel on `stream` (one per 2^30 workgroups of 512 pixels); no scratch, no atomics, allocates nothing, synchronises
+ * nothing, two calls give equal bytes.  An argument outside these rules returns FLOAT_E_INVALID, with a message naming the
+ * function and the argument, before any HIP call. */
+enum { FLOAT_IMG_MATRIX_BT601_LIMITED = 0 };
+int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* frames8, int32_t n_frames, int32_t fr_h,
+                         int32_t fr_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t feather, int32_t matrix,
+                         uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------- JPEG encoder -- */
 /* n_frames 8-bit RGB frames in HBM - the (n, h, w, 3) buffer float_dec_frames_u8 writes - -> n complete baseline JPEG files

@@ -1,16 +1,18 @@
 """What pasting the generated frames back into the portrait costs, on the 512-px synthetic model (bench.py config 1: a 10-s clip,
 51 grid points, decode batches of 32, seeded weights of the checkpoint's shapes) with a 1024 x 1024 and a 1920 x 1088 portrait,
-face_align on and a stub detector whose box gives a crop of about 0.6 of the portrait's height.  Per portrait three forms take
+face_align on and a stub detector whose box gives a crop of about 0.6 of the portrait's height.  Per portrait four forms take
 turns in one process:
   u8      host_inputs + InferenceAgent.infer_device(out_dtype=torch.uint8): the crop clip, the yardstick of the same process;
   pasted  InferenceAgent.infer_pasted;
+  i420    InferenceAgent.infer_pasted(out_format="i420"): paste and colour conversion in one kernel, 1.5 bytes per pixel;
   jpeg    InferenceAgent.infer_pasted_jpeg(quality=QUALITY).
 Each call is timed on the host clock between device synchronisations, REPS (default 10) repetitions per form after WARMUP
 (default 2), taking turns.  The paste launch alone (image.paste_frames_device on 50 crops in HBM, the product's group) is timed by
-device events, LAUNCH_REPS (default 30) times after 3, and held to the bytes it moves - 50 H W 3 written, 50 H W 3 of the source
-and 50 x 512 x 512 x 3 of the frames read - over the copy bandwidth float_probe_peaks measures in this process (bytes read +
-bytes written per second).  Prints one JSON line: median, min, max and spread (max - min) per form, ms; the launch's median, its
-GB/s and its fraction of the copy peak.  Run from the repository root.  Environment: REPS, WARMUP, LAUNCH_REPS, QUALITY."""
+device events, LAUNCH_REPS (default 30) times after 3, the RGB and the I420 launch taking turns, and held to the bytes it moves -
+50 H W 3 (I420: 50 H W 3 / 2) written, 50 H W 3 of the source and 50 x 512 x 512 x 3 of the frames read - over the copy bandwidth
+float_probe_peaks measures in this process (bytes read + bytes written per second).  Prints one JSON line: median, min, max and
+spread (max - min) per form, ms; per launch its median, its GB/s and its fraction of the copy peak.  Run from the repository root.
+Environment: REPS, WARMUP, LAUNCH_REPS, QUALITY."""
 import importlib
 import json
 import os
@@ -55,7 +57,7 @@ parts = dict(enc=pkg.weights.synth_encoder_state(SIZE, seed=1), dec=pkg.weights.
              fmt=pkg.weights.synth_fmt_state(cfg, seed=1), audio_encoder=(pkg.weights.synth_audio_state(acfg, seed=1), acfg))
 agent = gen.InferenceAgent(opt, parts, dev, max_frames=MAX_FRAMES, use_graph=2)
 audio = {"waveform": pkg.weights.synth_waveform(SECONDS, seed=1).reshape(1, 1, -1).cpu(), "sample_rate": 16000}
-FORMS = ("u8", "pasted", "jpeg")
+FORMS = ("u8", "pasted", "i420", "jpeg")
 KW = dict(emo="neutral", seed=15)
 last = {}
 
@@ -66,6 +68,8 @@ def run(form, img):
         last[form] = agent.infer_device(s, a, 2.0, 1.0, 1.0, out_dtype=torch.uint8, **KW)
     elif form == "pasted":
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, **KW)
+    elif form == "i420":
+        last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", **KW)
     else:
         last[form] = agent.infer_pasted_jpeg(img, audio, 2.0, 1.0, 1.0, no_crop=False, quality=QUALITY, **KW)
 
@@ -85,24 +89,31 @@ def stats(v):
 
 
 def launch_alone(place, peaks):
+    """{"rgb": ..., "i420": ...}: float_img_paste and float_img_paste_i420 on the same 50 crops, taking turns"""
     n, (H, W) = 50, place.size
     crops = torch.randint(0, 256, (n, SIZE, SIZE, 3), dtype=torch.uint8, device=dev)
-    out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
     feather = hm.default_feather(place.rect)
-    ms = []
+    outs = {"rgb": torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev), "i420": torch.empty(n, 3 * H // 2, W, dtype=torch.uint8, device=dev)}
+    ms = {fmt: [] for fmt in outs}
     for i in range(3 + LAUNCH_REPS):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out)
-        e1.record()
-        e1.synchronize()
-        if i >= 3:
-            ms.append(e0.elapsed_time(e1))
-    moved = 2 * n * H * W * 3 + n * SIZE * SIZE * 3
-    res = stats(ms)
-    res.update(frames=n, bytes_moved=moved, GBps=round(moved / 1e9 / (res["median"] * 1e-3), 1),
-               fraction_of_copy_peak=round(moved / 1e9 / (res["median"] * 1e-3) / peaks["hbm_copy_GBps"], 3),
-               equals_definition=bool(torch.equal(out[:1].cpu(), hm.paste_rgb8(place.src8.cpu(), crops[:1].cpu(), place.rect, feather))))
+        for fmt, out in outs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out, out_format=fmt)
+            e1.record()
+            e1.synchronize()
+            if i >= 3:
+                ms[fmt].append(e0.elapsed_time(e1))
+    want = hm.paste_rgb8(place.src8.cpu(), crops[:1].cpu(), place.rect, feather)
+    res = {}
+    for fmt, out in outs.items():
+        moved = n * out[0].numel() + n * H * W * 3 + n * SIZE * SIZE * 3
+        r = stats(ms[fmt])
+        r.update(frames=n, bytes_moved=moved, GBps=round(moved / 1e9 / (r["median"] * 1e-3), 1),
+                 fraction_of_copy_peak=round(moved / 1e9 / (r["median"] * 1e-3) / peaks["hbm_copy_GBps"], 3),
+                 equals_definition=bool(torch.equal(out[:1].cpu(), want if fmt == "rgb" else hm.rgb8_to_i420(want))))
+        res[fmt] = r
+    res["i420_minus_rgb_ms"] = round(res["i420"]["median"] - res["rgb"]["median"], 3)
     return res
 
 
@@ -119,10 +130,12 @@ for H, W in ((1024, 1024), (1088, 1920)):
             ms[form].append(wall_ms(form, img))
     out = {form: stats(v) for form, v in ms.items()}
     out["pasted"]["minus_u8_ms"] = round(out["pasted"]["median"] - out["u8"]["median"], 3)
+    out["i420"]["minus_u8_ms"] = round(out["i420"]["median"] - out["u8"]["median"], 3)
+    out["i420"]["minus_pasted_ms"] = round(out["i420"]["median"] - out["pasted"]["median"], 3)
     out["jpeg"]["minus_u8_ms"] = round(out["jpeg"]["median"] - out["u8"]["median"], 3)
     _, _, place = agent.host_inputs_placed(img, audio, no_crop=False)
     out["rect"] = list(place.rect)
-    out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), jpeg=last["jpeg"].nbytes)
+    out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), i420=last["i420"].numel(), jpeg=last["jpeg"].nbytes)
     out["paste_launch_50_frames"] = launch_alone(place, peaks)
     res["%dx%d" % (W, H)] = out
 print(json.dumps(res))
