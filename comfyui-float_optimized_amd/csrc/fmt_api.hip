@@ -1,6 +1,5 @@
 // C-ABI entry points of the FMT operator (include/float_hip.h): the handle, the evaluation chain and its hipGraph cache, the
-// incremental sampler and the GEMM service.  Packing, launchers and the persistent kernel's host side: fmt_weights.hpp,
-// fmt_launch.hpp, fmt_mega.hpp.
+// incremental sampler and the GEMM service.  Packing and launchers: fmt_weights.hpp, fmt_launch.hpp.
 #include <math.h>
 #include <stdlib.h>
 
@@ -34,21 +33,12 @@ struct float_fmt {
   u16 *cond16, *sc16, *h16, *hfin16, *qkv16, *att16, *hid16, *xin16, *tsin16, *th16;
   float *ccond, *xres, *xcur, *temb, *vout;
   unsigned long long* sat = nullptr;  // range counter of every 16-bit activation store of the handle's launches (float_fmt_saturation)
-  float* slab = nullptr;  // [8][Mpad][D] split-K partial sums (EPI_PARTIAL; the fused attention + proj launch writes one slab per head)
+  float* slab = nullptr;  // [8][Mpad][D] split-K partial sums (EPI_PARTIAL)
   float *wa_c, *we_c, *prev_x, *prev_wa, *prev_we, *x0_c;
   float* wr_c = nullptr;   // [clip][dim_w]: wr of a ragged job in slot order
   int method = 0;          // FLOAT_ODE_*
   FmtTune tune;            // the environment's switches as float_fmt_create found them (tuning.hpp)
-  // the step chain of one evaluation as ONE persistent kernel (fmt_mega_kernel, tune.mega): stage table per CFG shape, barrier words
-  int n_cu = 0;
-  struct MegaPlan {
-    MegaStage* dev = nullptr;
-    int nstage = 0, bc = 0, tried = 0;
-    MegaCtx ctx{};
-  } mega[5];               // by CFG rows (1, 3, 4)
-  unsigned* mega_sync = nullptr;  // [8 x 32 | 32 | 8 x 32 | seq | err] words
-  unsigned* mega_err_host = nullptr;  // host-mapped twin of the err word (hipHostMalloc): read by mega_poll without a copy
-  u16* mega_ws = nullptr;         // write-once A operands of the persistent kernel: per block h16 x 2, att16, hid16; + the head's
+  int n_cu = 0;            // compute units of the device (big_shape_ok, launch_big4)
   float* kbuf = nullptr;   // [4][kMaxTok][dim_w] stage velocities of the Runge-Kutta solvers
   // Modulations of up to kScSteps evaluations of a window, [step][Mmod][Ntot] fp32: c = t_emb + c_embedder(wr, wa, we) does not
   // depend on x (FMT.py:333-335, 163-166), so every adaLN projection of those evaluations is ONE GEMM per window.
@@ -91,8 +81,6 @@ struct float_fmt {
     int rg_win[kFmtMaxClips];  // windows per slot, non-increasing
   } job;
 };
-
-#include "fmt_mega.hpp"
 
 namespace {
 
@@ -175,31 +163,26 @@ int run_mod_all(float_fmt* h, int M, int e0, int n, hipStream_t s) {
 
 bool split_ok(int ks, const Lin& L) { return (ks == 1 || ks == 2 || ks == 4) && L.K % (128 * ks) == 0; }
 
-// Attention and attn.proj of block B on the M rows of qkv16, by the first that applies: the row-blocked tile (stacked clips),
-// the fused attention + proj launch, a split-K proj, the proj GEMM with gate * residual in its epilogue.  *pend: the reduction
-// left to LN2 by the first three (`gate` = gate_msa).
+// Attention, then attn.proj of block B on the M rows of qkv16, by the first that applies: the row-blocked tile (stacked clips),
+// a split-K proj, the proj GEMM with gate * residual in its epilogue.  *pend: the reduction left to LN2 by the first two
+// (`gate` = gate_msa).
 template <class T>
 int run_proj(const FmtLaunch& cx, const Blk& B, int M, const float* gate, const RbPlan& rb, PendingRed* pend) {
   const FmtTune& tn = cx.tn;
-  const int hpw = attnproj_hpw(tn, cx.D, cx.heads);
-  const int ks = rb.shape >= 0 ? rb.ksplit : (hpw ? cx.heads / hpw : (split_ok(tn.proj_split, B.proj) ? tn.proj_split : 0));
+  const int ks = rb.shape >= 0 ? rb.ksplit : (split_ok(tn.proj_split, B.proj) ? tn.proj_split : 0);
   int rc;
-  if (rb.shape < 0 && hpw) {
-    rc = launch_attnproj<T>(cx, M, B.proj);
+  launch_attn<T>(cx, M, (!ks && (tn.touch & 2)) ? &B.proj : nullptr);
+  GemmArgs g = base_args(cx.att16, B.proj, M);
+  if (rb.shape >= 0) {
+    to_slab(g, cx.slab, cx.Mpad, ks);
+    rc = launch_rbs<T, EPI_PARTIAL>(g, rb.shape, cx.s);
+  } else if (ks) {
+    rc = run_gemm_partial<T>(cx, g, ks);
   } else {
-    launch_attn<T>(cx, M, (!ks && (tn.touch & 2)) ? &B.proj : nullptr);
-    GemmArgs g = base_args(cx.att16, B.proj, M);
-    if (rb.shape >= 0) {
-      to_slab(g, cx.slab, cx.Mpad, ks);
-      rc = launch_rbs<T, EPI_PARTIAL>(g, rb.shape, cx.s);
-    } else if (ks) {
-      rc = run_gemm_partial<T>(cx, g, ks);
-    } else {
-      g.sat = cx.sat, g.out_f32 = cx.xres, g.ldo = cx.D;
-      g.gate = gate, g.ldg = cx.Ntot;
-      if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
-      rc = run_gemm<T, EPI_GATE_RES>(tn, g, cx.s, false, &tn.plan_layer[RB_PROJ]);
-    }
+    g.sat = cx.sat, g.out_f32 = cx.xres, g.ldo = cx.D;
+    g.gate = gate, g.ldg = cx.Ntot;
+    if (tn.touch & 16) g.touch = make_touch(tn, B.fc1, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
+    rc = run_gemm<T, EPI_GATE_RES>(tn, g, cx.s, false, &tn.plan_layer[RB_PROJ]);
   }
   if (!rc && ks) *pend = pending_red(cx.slab, cx.Mpad, cx.D, B.proj.b, gate, ks);
   return rc;
@@ -240,11 +223,6 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
   const FmtLaunch cx = launch_ctx(h, s);
   const int D = h->D, ntok = h->ntok, M = nclip * bc * ntok;
   int rc;
-  if constexpr (!T::is32) {
-    if (bc <= 4 && mega_shape_ok<T>(h, nclip, bc)) {
-      if (h->mega[bc].dev) return run_mega<T>(h, bc, modbuf, euler, dt, a, r, e, s, vout_to);  // table built at create
-    }
-  }
   // x_embedder + pos_embed; the CFG rows share x, so 60 rows are computed and broadcast
   {
     GemmArgs g = base_args(h->xin16, h->x_embed, nclip * ntok);
@@ -259,7 +237,6 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
   if constexpr (!T::is32) {
     rb_qkv = pick_rb(tn, RB_QKV, M), rb_proj = pick_rb(tn, RB_PROJ, M), rb_fc1 = pick_rb(tn, RB_FC1, M), rb_fc2 = pick_rb(tn, RB_FC2, M);
   }
-  const int hpw = attnproj_hpw(tn, D, c.heads);
   for (int b = 0; b < c.depth; ++b) {
     const float* mod = modbuf + (size_t)b * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
     const Blk& B = h->blk[b];
@@ -268,8 +245,7 @@ int run_blocks(float_fmt* h, int nclip, int bc, const float* modbuf, bool euler,
     {
       GemmArgs g = base_args(h->h16, B.qkv, M);
       g.sat = h->sat, g.out16 = h->qkv16, g.ldo16 = 3 * D;
-      if ((tn.touch & 8) && hpw) g.touch = make_touch(tn, B.proj, M, c.heads / hpw, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2, 8 / hpw);  // k-slices <-> XCDs as the fused launch decodes them
-      else if ((tn.touch & 8) && !split_ok(tn.proj_split, B.proj)) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
+      if ((tn.touch & 8) && !split_ok(tn.proj_split, B.proj)) g.touch = make_touch(tn, B.proj, M, 0, gemm_lanes_per_xcd(tn, M, g.N, g.K), 2);
       if (rb_qkv.shape >= 0) rc = launch_rbs<T, EPI_T16>(g, rb_qkv.shape, s);
       else rc = run_gemm<T, EPI_T16>(tn, g, s, false, &tn.plan_layer[RB_QKV]);
       if (rc) return rc;
@@ -739,17 +715,6 @@ static int debug_impl(float_fmt* h, int what, const float* in, float* out, hipSt
   if (what == 0) {
     return dev_copy(out, h->pos, (size_t)ntok * D, s);
   }
-  if (what == 2) {  // diagnostic builds (-DMEGA_STAMPS): per stage [start, body end, stores drained] of the persistent kernel's last launch, in us
-    FH_REQUIRE(h->mega_sync && h->mega[3].nstage > 0 && h->mega[3].nstage <= 64, "no persistent-kernel plan");
-    FH_CHECK_HIP(hipStreamSynchronize(s));
-    const int n = h->mega[3].nstage * 3;
-    std::vector<unsigned long long> st(n);
-    FH_CHECK_HIP(hipMemcpy(st.data(), h->mega_sync + 20 * 32, n * 8, hipMemcpyDeviceToHost));
-    std::vector<float> us(n);
-    for (int i = 0; i < n; ++i) us[i] = st[i] ? (float)((double)(st[i] - st[0]) * 0.01) : -1.f;  // 100 MHz
-    FH_CHECK_HIP(hipMemcpy(out, us.data(), n * 4, hipMemcpyHostToDevice));
-    return FLOAT_OK;
-  }
   if (what == 3 || what == 4) {
     // the K-split exchange of fmt_gemm_kernel on ONE workgroup's tile: 48 rows x 64 (what = 3) or 16 (what = 4) columns, K = 1024
     // over 8 waves (4 in the fp32 mode), zero bias: with 8 waves the straight-line form of the body (the 16-column tile through
@@ -891,8 +856,6 @@ int float_fmt_create(const float_fmt_cfg_t* cfg, const float_tensor_t* tensors, 
       rc = FLOAT_E_HIP;
     }
   }
-  // stage table of the persistent evaluation kernel for the 3-way CFG shape, built now (prepare_mega)
-  if (!rc) rc = fmt_by_dtype(cfg->dtype, [&](auto t) { return prepare_mega<decltype(t)>(h, 3); });
   if (rc) {
     float_fmt_destroy(h);
     return rc;
@@ -905,7 +868,6 @@ void float_fmt_destroy(float_fmt_t* h) {
   if (!h) return;
   for (auto& g : h->graphs) destroy_graphs(g);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-  if (h->mega_err_host) (void)hipHostFree(h->mega_err_host);
   h->pool.release();
   delete h;
 }
@@ -915,7 +877,6 @@ int float_fmt_eval(float_fmt_t* h, float t, const float* x, const float* wa, con
                    float r_cfg, float e_cfg, int32_t include_r_cfg, float* out, void* stream) {
   int rc = check_common(h, we, we_len, prev_we);
   if (rc) return rc;
-  if ((rc = mega_poll(h))) return rc;
   FH_REQUIRE(x && wa && wr && we && prev_x && prev_wa && out, "null tensor argument to float_fmt_eval");
   hipStream_t s = (hipStream_t)stream;
   return fmt_by_dtype(h->cfg.dtype, [&](auto tag) {
@@ -928,7 +889,6 @@ int float_fmt_sample_chunk(float_fmt_t* h, const float* x0, const float* wa, con
                            float a_cfg, float r_cfg, float e_cfg, int32_t include_r_cfg, float* out, void* stream) {
   int rc = check_common(h, we, we_len, prev_we);
   if (rc) return rc;
-  if ((rc = mega_poll(h))) return rc;
   FH_REQUIRE(x0 && wa && wr && we && prev_x && prev_wa && out, "null tensor argument to float_fmt_sample_chunk");
   FH_REQUIRE(nfe >= 1 && n_evals(h->method, nfe) < kMaxSteps, "nfe=%d: too many evaluations (max %d)", nfe, kMaxSteps);
   hipStream_t s = (hipStream_t)stream;
@@ -973,7 +933,6 @@ int float_fmt_saturation(float_fmt_t* h, uint64_t* total, int32_t reset, void* s
     FH_CHECK_HIP(hipMemsetAsync(h->sat, 0, sizeof(v), (hipStream_t)stream));
     FH_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   }
-  if (int rc = mega_poll(h)) return rc;  // the persistent kernel's barrier watchdog (also polled by every other call)
   return FLOAT_OK;
 }
 
@@ -1042,7 +1001,6 @@ int float_fmt_sample_begin_range(float_fmt_t* h, const float* wr, const float* w
 
 int float_fmt_sample_next(float_fmt_t* h, void* stream, int32_t* window_done, int32_t* windows_left) {
   FH_REQUIRE(h != nullptr && h->job.active, "float_fmt_sample_next without float_fmt_sample_begin");
-  if (int prc = mega_poll(h)) return prc;
   auto& J = h->job;
   hipStream_t s = (hipStream_t)stream;
   const int k = J.next;

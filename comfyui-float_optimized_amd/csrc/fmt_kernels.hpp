@@ -32,9 +32,7 @@ constexpr bool fmt_gemm_has_flat() {
   return NW == 8 && MTW == 3 && (NT == 4 || EPI == EPI_GATE_RES || EPI == EPI_CFG);
 }
 
-// The kernel's body as a device function: `bid` of `nblk` workgroups (blockIdx.x of gridDim.x for the stand-alone launch, the
-// stage's virtual block for fmt_mega_kernel).  COH: the activations (A operand, residual stream) were produced earlier in the
-// same kernel -> coherent loads (fh_load16<true>), and every activation store writes through.
+// The kernel's body as a device function (fmt_gemm_kernel picks its FLAT or its general form).
 // FLAT: the wave's K slice is exactly the PF k-steps in flight (every GEMM of the one-clip chain: K = 1024 over 8 waves, fc2 with
 // its K slices).  The body is then straight-line code from the first operand load to the last MFMA - every load of the prologue
 // is issued by every lane, none is issued in the K loop - and the compiler's s_waitcnt vmcnt in front of k-step p counts exactly
@@ -42,16 +40,12 @@ constexpr bool fmt_gemm_has_flat() {
 // MFMAs.  With the run-time trip counts of the general form it must assume the youngest load is the one it waits for, which
 // makes every wave wait for its whole K slice AND the touched HBM lines in front of its first MFMA.  The straight-line form
 // retires the touch behind its last store; everything else - the exchange through LDS, the epilogues - is the general form's.
-template <class T, int MTW, int NT, int NW, int EPI, bool COH, bool FLAT = false>
-__device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned bid, const unsigned nblk) {
+template <class T, int MTW, int NT, int NW, int EPI, bool FLAT = false>
+__device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g) {
+  const unsigned bid = blockIdx.x, nblk = gridDim.x;
   constexpr int BN = NT * 16;
   constexpr int ROWS = MTW * 16;
-  constexpr bool WT = NW >= 8 || COH;  // the single-clip tilings (stacked clips split K over 4 waves): see common.hpp, FMT_WT
-  // A operand: plain (L2-cached) loads also inside the persistent kernel.  There the operand lives in a buffer that is written
-  // exactly ONCE per launch (write-through) before its first read - no cache of any level can hold an older copy of it - and
-  // it is re-read by every column block of the XCD: as agent-scope (sc1) loads those re-reads all crossed the fabric
-  // (415 vs 320 us per evaluation).  The residual stream and the split-K slabs (read once, by one workgroup) stay coherent.
-  auto ldA = [](const typename T::elem* p) -> typename T::pack8 { return T::load8(p); };
+  constexpr bool WT = NW >= 8;  // the single-clip tilings (stacked clips split K over 4 waves): see common.hpp, FMT_WT
   constexpr int NTHR = NW * 64;
   constexpr int PF = fmt_gemm_pf<T, MTW, NT>();
   typedef typename T::elem E;
@@ -88,7 +82,7 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
 #pragma unroll
       for (int j = 0; j < NT; ++j) b[p][j] = T::load8_nt(Wp + j * tstride + (size_t)p * 512);
 #pragma unroll
-      for (int i = 0; i < MTW; ++i) a[p][i] = ldA(Ap + i * tstride + (size_t)p * 512);
+      for (int i = 0; i < MTW; ++i) a[p][i] = T::load8(Ap + i * tstride + (size_t)p * 512);
     }
   }
   // EPI_GATE_RES with one epilogue item per thread: fetch residual and gate now, not after the K loop (behind the operand
@@ -103,8 +97,8 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
     if (FLAT || (r < ROWS && row < g.M)) {
       const float* o = g.out_f32 + (size_t)row * g.ldo + nb;
       const float* gt = g.gate + (size_t)row * g.ldg + nb;
-      res_pf[0] = fh_load_f4<COH>(o);
-      res_pf[1] = fh_load_f4<COH>(o + 4);
+      res_pf[0] = fh_load_f4(o);
+      res_pf[1] = fh_load_f4(o + 4);
       gate_pf[0] = fh_load_f4_stream(gt);
       gate_pf[1] = fh_load_f4_stream(gt + 4);
     }
@@ -144,7 +138,7 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
           for (int j = 0; j < NT; ++j)
             b[p][j] = T::load8_nt(Wp + j * tstride + (size_t)(kb + PF) * 512);
 #pragma unroll
-          for (int i = 0; i < MTW; ++i) a[p][i] = ldA(Ap + i * tstride + (size_t)(kb + PF) * 512);
+          for (int i = 0; i < MTW; ++i) a[p][i] = T::load8(Ap + i * tstride + (size_t)(kb + PF) * 512);
         }
       }
     }
@@ -241,8 +235,8 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
       }
       if constexpr (EPI == EPI_F32 || EPI == EPI_PARTIAL) {
         float* o = g.out_f32 + (size_t)ks * g.slab_stride + (size_t)row * g.ldo + nb;
-        fh_store_f4_wt<fh_site<COH>(4), WT>(o, float4{v[0], v[1], v[2], v[3]});
-        fh_store_f4_wt<fh_site<COH>(4), WT>(o + 4, float4{v[4], v[5], v[6], v[7]});
+        fh_store_f4_wt<4, WT>(o, float4{v[0], v[1], v[2], v[3]});
+        fh_store_f4_wt<4, WT>(o + 4, float4{v[4], v[5], v[6], v[7]});
       } else if constexpr (EPI == EPI_T16 || EPI == EPI_SILU_P16 || EPI == EPI_GELU_P16 || EPI == EPI_GELUERF_P16) {
         P8 u;
 #pragma unroll
@@ -255,8 +249,8 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
         }
         fh_track_pack<T>(rm, u);
         E* const o16 = reinterpret_cast<E*>(g.out16);
-        if constexpr (EPI == EPI_T16) T::template store8_wt<fh_site<COH>(8), WT>(o16 + (size_t)row * g.ldo16 + nb, u);
-        else T::template store8_wt<fh_site<COH>(8), WT>(o16 + fmt_pack_off(row, nb, g.ldo16), u);
+        if constexpr (EPI == EPI_T16) T::template store8_wt<8, WT>(o16 + (size_t)row * g.ldo16 + nb, u);
+        else T::template store8_wt<8, WT>(o16 + fmt_pack_off(row, nb, g.ldo16), u);
       } else if constexpr (EPI == EPI_GATE_RES) {
         float* o = g.out_f32 + (size_t)row * g.ldo + nb;
         const float* gt = g.gate + (size_t)row * g.ldg + nb;
@@ -267,14 +261,14 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
             x = res_pf[e / 4];
             gg = gate_pf[e / 4];
           } else {
-            x = fh_load_f4<COH>(o + e);
+            x = fh_load_f4(o + e);
             gg = fh_load_f4_stream(gt + e);
           }
           x.x += gg.x * v[e + 0];
           x.y += gg.y * v[e + 1];
           x.z += gg.z * v[e + 2];
           x.w += gg.w * v[e + 3];
-          fh_store_f4_wt<fh_site<COH>(16), WT>(o + e, x);
+          fh_store_f4_wt<16, WT>(o + e, x);
         }
       } else if constexpr (EPI == EPI_XEMBED) {
         // input row = clip * ntok + token (the CFG rows of a clip share x); output rows (clip * bc + b2) * ntok + token
@@ -284,8 +278,8 @@ __device__ __forceinline__ void fmt_gemm_body(const GemmArgs& g, const unsigned 
         for (int i = 0; i < 8; ++i) v[i] += ps[i];
         for (int b2 = 0; b2 < g.bc; ++b2) {
           float* o = g.out_f32 + (size_t)((q * g.bc + b2) * g.ntok + tok) * g.ldo + nb;
-          fh_store_f4_wt<fh_site<COH>(32), WT>(o, float4{v[0], v[1], v[2], v[3]});
-          fh_store_f4_wt<fh_site<COH>(32), WT>(o + 4, float4{v[4], v[5], v[6], v[7]});
+          fh_store_f4_wt<32, WT>(o, float4{v[0], v[1], v[2], v[3]});
+          fh_store_f4_wt<32, WT>(o + 4, float4{v[4], v[5], v[6], v[7]});
         }
       }
     }
@@ -308,11 +302,11 @@ __global__ __launch_bounds__(NW * 64) void fmt_gemm_kernel(const u16* A, const u
   // preloaded scalars
   if constexpr (fmt_gemm_has_flat<T, MTW, NT, NW, EPI>()) {
     if ((EPI == EPI_PARTIAL ? kbs : (K >> 5)) == NW * fmt_gemm_pf<T, MTW, NT>()) {
-      fmt_gemm_body<T, MTW, NT, NW, EPI, false, true>(g, blockIdx.x, gridDim.x);
+      fmt_gemm_body<T, MTW, NT, NW, EPI, true>(g);
       return;
     }
   }
-  fmt_gemm_body<T, MTW, NT, NW, EPI, false>(g, blockIdx.x, gridDim.x);
+  fmt_gemm_body<T, MTW, NT, NW, EPI>(g);
 }
 // the host's side of that parameter list: launches fmt_gemm_kernel<...> `kern` with the head's members and the tail of `g`
 // (whose head fmt_gemm_head has completed); `prof` as fh_launch_prof
@@ -736,15 +730,13 @@ struct LnRed {
 
 constexpr int kLnTouch = 6;  // lines per lane: 192 single-wave workgroups cover 8 XCDs x 1 MB (fc1) with 6
 
-// Body: workgroup `bid` of `nblk`, `wpb` waves per workgroup AS THE ROW MAPPING SEES IT (1 = one row per workgroup, the
-// XCD-grouped mapping; fmt_mega_kernel calls it with the first wave of its 8-wave workgroups).  COH as in fmt_gemm_body.
-template <class T, int NV, int KS, bool TOUCH, bool WT_, bool COH>
+// Body: `wpb` waves per workgroup (1 = one row per workgroup, the XCD-grouped mapping).
+template <class T, int NV, int KS, bool TOUCH, bool WT>
 __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, const float* __restrict__ shift,
                                                const float* __restrict__ scale, int ldm, u16* __restrict__ out, const LnRed& red,
-                                               const TouchSpec& pf, int ntok, int perm, unsigned long long* sat, const unsigned bid,
-                                               const unsigned nblk, const int wpb) {
+                                               const TouchSpec& pf, int ntok, int perm, unsigned long long* sat, const int wpb) {
   constexpr int D = NV * 256;
-  constexpr bool WT = WT_ || COH;
+  const unsigned bid = blockIdx.x, nblk = gridDim.x;
   const int lane = threadIdx.x & 63;
   int row = bid * wpb + (threadIdx.x >> 6);
   unsigned touched[kLnTouch] = {};
@@ -778,7 +770,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;
-    v[i] = fh_load_f4<COH>(xr + c);
+    v[i] = fh_load_f4(xr + c);
     a[i] = fh_load_f4_stream(sh + c);
     b[i] = fh_load_f4_stream(sc + c);
   }
@@ -791,8 +783,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
         const float* ps = red.slab + k * red.slab_stride + (size_t)row * D + c;
-        if constexpr (COH) p[k][i] = fh_load_f4<true>(ps);
-        else p[k][i] = fh_load_f4_stream(ps);  // the slab's only read
+        p[k][i] = fh_load_f4_stream(ps);  // the slab's only read
       }
       gt[i] = fh_load_f4_stream(red.gate + mrow * ldm + c);
     }
@@ -813,7 +804,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
       v[i].y += gt[i].y * (t.y + bi[i].y);
       v[i].z += gt[i].z * (t.z + bi[i].z);
       v[i].w += gt[i].w * (t.w + bi[i].w);
-      fh_store_f4_wt<fh_site<COH>(1), WT>(xr + i * 256 + lane * 4, v[i]);
+      fh_store_f4_wt<1, WT>(xr + i * 256 + lane * 4, v[i]);
     }
   }
 #pragma unroll
@@ -837,7 +828,7 @@ __device__ __forceinline__ void fmt_lnmod_body(float* __restrict__ x, int M, con
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;
-    fh_store4_wt<T, fh_site<COH>(1), WT>(reinterpret_cast<typename T::elem*>(out) + fmt_pack_off(orow, c, D / 32),
+    fh_store4_wt<T, 1, WT>(reinterpret_cast<typename T::elem*>(out) + fmt_pack_off(orow, c, D / 32),
               (v[i].x - mu) * rstd * (1.f + b[i].x) + a[i].x, (v[i].y - mu) * rstd * (1.f + b[i].y) + a[i].y,
               (v[i].z - mu) * rstd * (1.f + b[i].z) + a[i].z, (v[i].w - mu) * rstd * (1.f + b[i].w) + a[i].w, rm);
   }
@@ -855,7 +846,7 @@ __global__ __launch_bounds__(256) void fmt_lnmod_kernel(float* __restrict__ x, c
   // rows per workgroup included (blockDim would be a load from the kernarg segment) - are preloaded into SGPRs at dispatch; the
   // output, the fold's bias, the touch and the permutation come behind and are first read once those loads are in flight.
   const LnRed red{slab, (size_t)slab_stride, red_bias, gate};
-  fmt_lnmod_body<T, NV, KS, TOUCH, WT, false>(x, M, shift, scale, ldm, out, red, pf, ntok, perm, sat, blockIdx.x, gridDim.x, wpb);
+  fmt_lnmod_body<T, NV, KS, TOUCH, WT>(x, M, shift, scale, ldm, out, red, pf, ntok, perm, sat, wpb);
 }
 
 // Banded attention (FMT.py:71-88 with the mask of FMT.py:15-19): query i sees keys |i-j| <= window.
@@ -866,16 +857,11 @@ __global__ __launch_bounds__(256) void fmt_lnmod_kernel(float* __restrict__ x, c
 // L2.  For window <= 2 every load of the query's band is issued before the first use (one memory round trip); wider
 // windows loop.  Output is written in the packed A-operand order of the proj GEMM (K = D).
 // Body: head `h`, run `run` of `qpw` queries (nthr = qpw * LPQ threads take part), `lin` of `nwg` workgroups for the touch.
-template <class T, int LPQ, bool TOUCH, bool WT_, bool COH>
+template <class T, int LPQ, bool TOUCH, bool WT>
 __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int ld, u16* __restrict__ out, int ntok, int M, int D,
                                               int window, const FmtDiv ntok_div, const TouchSpec& pf, unsigned long long* sat,
                                               const int h, const int run, const int nthr, const unsigned lin, const unsigned nwg) {
   constexpr int HD = 128, PD = HD / LPQ, NU = PD / 8;
-  constexpr bool WT = WT_ || COH;
-  auto ld8 = [](const typename T::elem* p) -> typename T::pack8 {
-    if constexpr (COH && !T::is32) return fh_load16<true>(p);
-    else return T::load8(p);
-  };
   // blockIdx.x = head, blockIdx.y = run of blockDim.x / LPQ consecutive ROWS of the (cfg rows x tokens) batch: with 8 rows per
   // workgroup the run is one 8-row group of the packed output, whose 128-byte lines then come whole from a single wave
   const int row_ = run * (nthr / LPQ) + threadIdx.x / LPQ, part = threadIdx.x % LPQ;
@@ -901,7 +887,7 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
   float qf[PD], o[PD];
   P8 qq[NU];
 #pragma unroll
-  for (int u = 0; u < NU; ++u) qq[u] = ld8(base + (size_t)qi * ld + u * 8);
+  for (int u = 0; u < NU; ++u) qq[u] = T::load8(base + (size_t)qi * ld + u * 8);
   // converted behind the first k / v loads of either branch below: in front of the branch the conversion made the wave wait for
   // q (a whole memory round trip) before it asked for k and v
   auto scale_q = [&]() {
@@ -942,8 +928,8 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
       const E* kp = base + (size_t)kj * ld + D;
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
-        kk[t][u] = ld8(kp + u * 8);
-        vv[t][u] = ld8(kp + D + u * 8);
+        kk[t][u] = T::load8(kp + u * 8);
+        vv[t][u] = T::load8(kp + D + u * 8);
       }
     }
     touch();
@@ -963,8 +949,8 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
       P8 k[NU], v[NU];
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
-        k[u] = ld8(kp + u * 8);
-        v[u] = ld8(kp + D + u * 8);
+        k[u] = T::load8(kp + u * 8);
+        v[u] = T::load8(kp + D + u * 8);
       }
       fold(k, v, kj >= 0 && kj < ntok);
     }
@@ -978,7 +964,7 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
 #pragma unroll
     for (int j = 0; j < 8; ++j) T::set(uo, j, o[u * 8 + j] * inv);
     fh_track_pack<T>(rm, uo);
-    T::template store8_wt<fh_site<COH>(2), WT>(reinterpret_cast<E*>(out) + fmt_pack_off(row, d0 + u * 8, D / 32), uo);
+    T::template store8_wt<2, WT>(reinterpret_cast<E*>(out) + fmt_pack_off(row, d0 + u * 8, D / 32), uo);
   }
   fh_range_flush<T>(sat, rm);
   if constexpr (TOUCH) fmt_touch_retire(touched);
@@ -990,396 +976,8 @@ __global__ __launch_bounds__(512) void fmt_attn_kernel(const u16* __restrict__ q
                                                        int nrun, unsigned long long* sat, TouchSpec pf) {
   // 14 preloaded dwords in front of the TouchSpec: the launch's block and grid sizes are among them (blockDim / gridDim would
   // be loads from the kernarg segment), so the q / k / v loads are issued without a scalar-memory round trip in front of them
-  fmt_attn_body<T, LPQ, TOUCH, WT, false>(qkv, ld, out, ntok, M, D, window, FmtDiv{ntok_mul, ntok_sh}, pf, sat, blockIdx.x, blockIdx.y,
-                                          nthr, blockIdx.x + (unsigned)heads * blockIdx.y, (unsigned)(heads * nrun));
-}
-
-// Banded attention AND attn.proj in one launch (FMT.py:71-89): attention is per head, the projection sums over heads, so a
-// workgroup = (row block of MTW*16 rows, 128-column block of proj, head h) computes the head's attention output for its rows
-// (the same register scheme as fmt_attn_kernel: LPQ = 8 lanes per query, every load of the band issued before the first use),
-// leaves it in LDS in A-fragment order and multiplies it by rows h*128.. of W_proj: split-K over the heads with NO exchange
-// between workgroups.  Slab h of the EPI_PARTIAL buffer receives the partial sums; the LayerNorm launch that follows folds
-// bias + gate * sum_h slab[h] into the residual stream in a fixed order (fmt_lnmod_kernel<.., KS = heads>).  The attention
-// of a row block is recomputed by each of its N/128 column blocks (0.03 MFLOP); the proj weights are requested first, so
-// their round trip overlaps the q/k/v round trip.  Heads <-> XCDs (ids congruent mod 8 share an L2): XCD h fetches only head
-// h's columns of q|k|v and the k-slice h of W_proj.  Operands swapped (D = W_tile * O_tile^T): a lane holds 4 consecutive
-// columns of one row, stored as one float4.  HPW = 2: two heads per workgroup (wave = (column tile, head), 64-column blocks),
-// the pair summed through LDS: half the slab bytes, two attention passes.
-// MEASURED (round 4, ms per 250 evaluations, same box): two launches 80.2-80.8; this kernel 81.4 (HPW = 1), 81.7-82.0 (HPW = 2),
-// 80.8 with non-temporal slab stores - a tie, so the two-launch chain stays the default (FLOAT_FMT_ATTNPROJ=1|2 selects this
-// one).  Diagnostic builds: without the slab stores 76.5, with the LayerNorm reading one hot slab 79.9, attention arithmetic
-// free (0.2): the launch it removes (4.7 us) is paid back by heads x M x N x 4 B of partial sums leaving each XCD's L2 at the
-// kernel boundary (5.9 MB, ~2.7 us) and coming back into the LayerNorm (+0.9 us).
-// sum over the LPQ = 8 lanes of a query by DPP (quad_perm xor 1, xor 2, then row_half_mirror: lane i <-> 7 - i of an 8-lane
-// group, whose quads hold their own sums by then): 3 VALU instructions instead of 3 ds_bpermute round trips
-__device__ __forceinline__ float fh_sum8_dpp(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-  return v;
-}
-
-template <class T, int MTW, int HPW /* heads per workgroup: K slices = heads / HPW */>
-__global__ __launch_bounds__(512) void fmt_attnproj_kernel(const u16* __restrict__ qkv, int ld, GemmArgs g, int ntok, int D, int window) {
-  constexpr int HD = 128, LPQ = 8, NU = HD / (LPQ * 8), KBH = HD / 32, NWV = 8, ROWS = MTW * 16;
-  constexpr int NCT = NWV / HPW;                       // 16-column tiles per workgroup: wave = (column tile, head of the group)
-  constexpr int NPAIR = ROWS * HPW, NPASS = (NPAIR * LPQ + NWV * 64 - 1) / (NWV * 64);
-  typedef typename T::elem E;
-  typedef typename T::pack8 P8;
-  __shared__ __attribute__((aligned(16))) E sO[HPW * MTW * KBH * 512];  // [head][row tile][k-block][lane][8]
-  __shared__ __attribute__((aligned(16))) float sR[(HPW > 1 ? (HPW - 1) : 1) * NCT * MTW * 256];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r16 = lane & 15, q4 = lane >> 4;
-  const int ct = w % NCT, hh = w / NCT;
-  int ks, bx, by;
-  {
-    // (column block, K slice) pairs <-> XCDs as in fmt_gemm_kernel: slice ks on the 8 / ksplit XCDs that own it
-    const int id = blockIdx.x, nbn = g.N / (NCT * 16), nbx = nbn * g.ksplit;
-    if ((nbx & 7) == 0 && (8 % g.ksplit) == 0) {
-      const int slot = id >> 3, P = 8 / g.ksplit, x = id & 7;
-      by = slot % g.mblk;
-      ks = x / P;
-      bx = (slot / g.mblk) * P + (x % P);
-    } else {
-      const int bxl = id % nbx;
-      by = id / nbx;
-      ks = bxl / nbn;
-      bx = bxl - ks * nbn;
-    }
-  }
-  const int KB = g.K >> 5;
-  const int h0 = ks * HPW;      // first head of this workgroup
-  const int nt = bx * NCT + ct; // this wave's 16-column tile of proj
-  const E* Wp = reinterpret_cast<const E*>(g.W) + ((size_t)nt * KB + (h0 + hh) * KBH) * 512 + lane * 8;
-  P8 b[KBH];
-#pragma unroll
-  for (int kk = 0; kk < KBH; ++kk) b[kk] = T::load8_nt(Wp + (size_t)kk * 512);
-
-  const float scale = rsqrtf((float)HD);
-  unsigned rm = 0u;
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    const int pair = pass * (NWV * 64 / LPQ) + threadIdx.x / LPQ, part = threadIdx.x % LPQ;
-    if (pair < NPAIR) {
-      const int ah = pair / ROWS, qslot = pair - ah * ROWS;  // head of the group, row of the block
-      const int row_ = by * ROWS + qslot;
-      P8 uo[NU];
-#pragma unroll
-      for (int u = 0; u < NU; ++u) uo[u] = T::zero8();
-      if (row_ < g.M) {  // whole LPQ-lane groups take the branch together
-        const int bq = row_ / ntok, qi = row_ - bq * ntok;
-        // lane `part` owns head dims u*64 + part*8 .. +7: one load instruction reads 128 contiguous bytes per query
-        const E* base = reinterpret_cast<const E*>(qkv) + (size_t)(bq * ntok) * ld + (h0 + ah) * HD + part * 8;
-        float qf[NU * 8], o[NU * 8];
-        P8 qq[NU];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) qq[u] = T::load8(base + (size_t)qi * ld + u * 64);
-#pragma unroll
-        for (int i = 0; i < NU * 8; ++i) o[i] = 0.f;
-        float l = 0.f;
-        auto dotk = [&](const P8* k) {
-          float dot = 0.f;
-#pragma unroll
-          for (int u = 0; u < NU; ++u) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) dot += qf[u * 8 + j] * T::get(k[u], j);
-          }
-          return fh_sum8_dpp(dot);
-        };
-        if (window <= 2) {
-          // the band's five keys: every load issued before the first use, the five dot products reduced side by side, then
-          // a plain (not running) softmax over them
-          P8 kk[5][NU], vv[5][NU];
-#pragma unroll
-          for (int t = 0; t < 5; ++t) {
-            const int kj = min(max(qi + t - 2, 0), ntok - 1);
-            const E* kp = base + (size_t)kj * ld + D;
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-              kk[t][u] = T::load8(kp + u * 64);
-              vv[t][u] = T::load8(kp + D + u * 64);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < NU; ++u) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[u * 8 + j] = T::get(qq[u], j) * scale;
-          }
-          float dot[5], m = -INFINITY;
-#pragma unroll
-          for (int t = 0; t < 5; ++t) {
-            const int kj = qi + t - 2;
-            const bool valid = kj >= 0 && kj < ntok && (t - 2 >= -window) && (t - 2 <= window);
-            dot[t] = valid ? dotk(kk[t]) : -INFINITY;
-            m = fmaxf(m, dot[t]);
-          }
-#pragma unroll
-          for (int t = 0; t < 5; ++t) {
-            const float p = __expf(dot[t] - m);  // exp(-inf) = 0 for the keys outside the band / the sequence
-            l += p;
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) o[u * 8 + j] += p * T::get(vv[t][u], j);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < NU; ++u) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[u * 8 + j] = T::get(qq[u], j) * scale;
-          }
-          float m = -INFINITY;
-          for (int kj = max(qi - window, 0); kj <= min(qi + window, ntok - 1); ++kj) {
-            const E* kp = base + (size_t)kj * ld + D;
-            P8 k[NU], v[NU];
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-              k[u] = T::load8(kp + u * 64);
-              v[u] = T::load8(kp + D + u * 64);
-            }
-            const float dot = dotk(k);
-            const float mn = fmaxf(m, dot);
-            const float alpha = __expf(m - mn), p = __expf(dot - mn);
-            l = l * alpha + p;
-            m = mn;
-#pragma unroll
-            for (int u = 0; u < NU; ++u) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) o[u * 8 + j] = o[u * 8 + j] * alpha + p * T::get(v[u], j);
-            }
-          }
-        }
-        const float inv = 1.f / l;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) T::set(uo[u], j, o[u * 8 + j] * inv);
-          fh_track_pack<T>(rm, uo[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < NU; ++u) T::store8(sO + ah * (MTW * KBH * 512) + fmt_pack_off(qslot, u * 64 + part * 8, KBH), uo[u]);
-    }
-  }
-  fh_range_flush<T>(g.sat, rm);
-  __syncthreads();
-
-  f32x4 acc[MTW];
-#pragma unroll
-  for (int i = 0; i < MTW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const E* const sOh = sO + hh * (MTW * KBH * 512);
-#pragma unroll
-  for (int kk = 0; kk < KBH; ++kk) {
-#pragma unroll
-    for (int i = 0; i < MTW; ++i) acc[i] = T::mfma(b[kk], T::load8(sOh + (i * KBH + kk) * 512 + lane * 8), acc[i]);
-  }
-  if constexpr (HPW > 1) {
-    // the group's heads meet in LDS, summed in head order by the wave of head 0
-    if (hh > 0) {
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) *reinterpret_cast<f32x4*>(sR + (((hh - 1) * NCT + ct) * MTW + i) * 256 + lane * 4) = acc[i];
-    }
-    __syncthreads();
-    if (hh > 0) return;
-#pragma unroll
-    for (int o = 1; o < HPW; ++o) {
-#pragma unroll
-      for (int i = 0; i < MTW; ++i) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(sR + (((o - 1) * NCT + ct) * MTW + i) * 256 + lane * 4);
-        acc[i] += t;
-      }
-    }
-  }
-  // D[n = q4*4 + reg][m = r16]
-  float* const outp = g.out_f32 + (size_t)ks * g.slab_stride + nt * 16 + q4 * 4;
-#pragma unroll
-  for (int i = 0; i < MTW; ++i) {
-    const int row = (by * MTW + i) * 16 + r16;
-    // non-temporal: the slabs are read once, by the LayerNorm launch, from other XCDs (80.8 vs 81.4 ms per 250 evaluations with plain stores)
-    if (row < g.M) __builtin_nontemporal_store(acc[i], reinterpret_cast<f32x4*>(outp + (size_t)row * g.ldo));
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// ONE evaluation of the step chain as ONE persistent kernel (fmt_mega_kernel): x-embed, 8 x [LN, qkv, attention, proj, LN,
-// fc1, fc2], LN, head = 59 stages that were 59 dependent launches.  The stages are the SAME bodies (fmt_gemm_body /
-// fmt_lnmod_body / fmt_attn_body: same tilings, same arithmetic, bit for bit the launch chain's results); what changes is how
-// they meet: 256 workgroups (one per CU, all resident) pass a grid barrier between stages instead of a kernel boundary.
-// MEASURED (round 4, MI355X, one box): 375 us per evaluation against 322 for the launch chain - it LOSES, so it is opt-in
-// (FLOAT_FMT_MEGA=1) and the launch chain stays the default.  In-kernel stamps (-DMEGA_STAMPS, tools/probes/mega_stamps.py), us
-// per stage: bodies LN 2.7 / qkv 3.9 / attention 2.6 / proj 2.8 / fc1 5.5 / fc2 4.6 (the launch chain's kernels minus ~2.5 us
-// of boundary: 2.2 / 2.9 / 2.2 / 2.4 / 4.9 / 4.4), + 0.4-1.7 draining the write-through stores, + 1.6-2.5 in the barrier:
-// the software hand-off costs what the hardware's launch boundary costs, the bodies pay for coherent loads and sc1 stores,
-// and a 256 x 512-thread launch adds ~29 us per evaluation (workgroup dispatch skew ~6 us at the first stage).
-// Probes (tools/probes/grid_barrier.hip): hierarchical in-kernel barrier 2.1 us, 2.8 us with a stage's data exchanged through
-// sc1 stores / loads; agent-scope release / acquire FENCES (buffer_wbl2 / buffer_inv) 31 us, buffer_inv sc1 alone 4-9 us -
-// so the kernel never fences: every activation store of a stage writes through (sc1), a
-// workgroup drains its stores (s_waitcnt vmcnt(0)) before it arrives, and every activation load of the next stage is an
-// agent-scope load (COH = true).  Weights, biases and modulations are read-only for the whole kernel: plain loads.
-// Barrier: 8 group counters (workgroups congruent mod 8 = one XCD, 32 arrivals each on their own 128-byte line), the last
-// arriver of a group bumps a top counter, the last of those writes the generation into 8 per-group release words that the
-// waiters poll - three dependent memory round trips instead of 256 serialized atomics on one line.  Counters only ever count
-// up: generation = launches so far (a device word read at kernel start, bumped by workgroup 0 at the end) x barriers per
-// launch + stage, so a hipGraph can replay the same launch.  A waiter that does not see its release within ~0.3 s (a CU was
-// not available, so not all workgroups are resident) sets the error word (and its host-mapped twin) and leaves; the host
-// reports it at the next FMT call on the handle, whatever its dtype (mega_poll in fmt_api.hip: that call fails, the barrier
-// words are cleared and the handle falls back to the launch chain) instead of hanging the GPU.
-enum { MS_XEMBED = 0, MS_LN, MS_QKV, MS_ATTN, MS_PROJ, MS_FC1, MS_FC2, MS_HEAD };
-struct MegaStage {
-  int kind;
-  unsigned nblk;                 // workgroups with work in this stage (the rest only pass the barrier)
-  GemmArgs g;                    // GEMM stages; gate / head fields are patched per launch
-  long long gate_off;            // MS_PROJ: gate = mod + gate_off
-  long long shift_off, scale_off, red_gate_off;  // MS_LN: modulation rows / gate of the folded split-K GEMM, from `mod`
-  int ks;                        // MS_LN: slabs folded first (0 / 4)
-  const float* red_bias;
-  u16* ln_out;
-  int perm;
-  TouchSpec pf;                  // MS_LN / MS_ATTN: weights of the next GEMM to pull into L2
-  u16* att_out;                  // MS_ATTN: this block's attention output (A operand of its proj: a write-once buffer)
-};
-struct MegaCtx {                 // per handle and CFG shape
-  float* xres;
-  const u16* qkv16;
-  const float* slab;
-  size_t slab_stride;
-  int M, D, ntok, ldm, window, heads;
-  unsigned long long* sat;
-  FmtDiv ntok_div;  // row / ntok (fmt_attn_body)
-};
-struct MegaDyn {                 // per launch
-  const float* mod;
-  float dt, a, r, e;
-  int euler;
-  float* vout;
-};
-struct MegaSync {
-  unsigned* grp;   // [8] x 32 words
-  unsigned* top;   // [1]
-  unsigned* rel;   // [8] x 32 words
-  unsigned* seq;   // launches so far
-  unsigned* err;   // != 0: a barrier timed out
-  unsigned* err_host;  // the same flag in host-mapped memory: the host reads it at its next call without a device copy
-  unsigned long long* stamps;  // diagnostic builds (-DMEGA_STAMPS): [stage][3] s_memrealtime of workgroup `stamp_wg`
-  unsigned stamp_wg;
-};
-
-// (A flat form - every workgroup adds 1 to its group's counter and polls all 8 counters, two dependent round trips instead of
-// four - measured WORSE: 2.4-4.0 us per barrier against 1.6-2.5, 256 pollers x 8 lines.)  Called by thread 0.
-__device__ __forceinline__ bool fmt_grid_barrier(const MegaSync& sy, unsigned gen, unsigned nwg) {
-  typedef __attribute__((address_space(1))) unsigned int gu32;
-  const unsigned g = blockIdx.x & 7u, per = nwg >> 3;
-  const unsigned old = __hip_atomic_fetch_add((gu32*)(sy.grp + g * 32), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (old + 1u == gen * per) {
-    const unsigned t = __hip_atomic_fetch_add((gu32*)sy.top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t + 1u == gen * 8u) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) __hip_atomic_store((gu32*)(sy.rel + i * 32), gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  unsigned spins = 0;
-  while ((int)(__hip_atomic_load((gu32*)(sy.rel + g * 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - gen) < 0) {
-    if (++spins > (1u << 18) || ((spins & 63u) == 0u && __hip_atomic_load((gu32*)sy.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-      __hip_atomic_store((gu32*)sy.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (sy.err_host) __hip_atomic_store((gu32*)sy.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return false;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return true;
-}
-
-template <class T>
-__global__ __launch_bounds__(512) void fmt_mega_kernel(const MegaStage* __restrict__ tab, int nstage, MegaDyn d, MegaCtx c,
-                                                       MegaSync sy) {
-  typedef __attribute__((address_space(1))) unsigned int gu32;
-  __shared__ unsigned s_flag[2];
-  const unsigned bid = blockIdx.x, nwg = gridDim.x;
-  if (threadIdx.x == 0) {
-    s_flag[0] = __hip_atomic_load((gu32*)sy.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_flag[1] = 1u;
-  }
-  __syncthreads();
-  const unsigned seq0 = s_flag[0];
-  const unsigned gen0 = seq0 * (unsigned)(nstage - 1);
-#ifdef MEGA_STAMPS
-#define MEGA_STAMP(k) do { if (sy.stamps && bid == sy.stamp_wg && threadIdx.x == 0) sy.stamps[s * 3 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define MEGA_STAMP(k) do { } while (0)
-#endif
-  for (int s = 0; s < nstage; ++s) {
-    const MegaStage& st = tab[s];
-    MEGA_STAMP(0);
-    if (bid < st.nblk) {
-      switch (st.kind) {
-        case MS_XEMBED:
-          fmt_gemm_body<T, 4, 1, 8, EPI_XEMBED, true>(st.g, bid, st.nblk);
-          break;
-        case MS_LN:
-          if (threadIdx.x < 64) {
-            const LnRed red{c.slab, c.slab_stride, st.red_bias, d.mod + st.red_gate_off};
-            if (st.ks == 0)
-              fmt_lnmod_body<T, 4, 0, true, true, true>(c.xres, c.M, d.mod + st.shift_off, d.mod + st.scale_off, c.ldm, st.ln_out, red,
-                                                        st.pf, c.ntok, st.perm, c.sat, bid, st.nblk, 1);
-            else
-              fmt_lnmod_body<T, 4, 4, true, true, true>(c.xres, c.M, d.mod + st.shift_off, d.mod + st.scale_off, c.ldm, st.ln_out, red,
-                                                        st.pf, c.ntok, st.perm, c.sat, bid, st.nblk, 1);
-          }
-          break;
-        case MS_QKV:
-          fmt_gemm_body<T, 3, 4, 8, EPI_T16, true>(st.g, bid, st.nblk);
-          break;
-        case MS_ATTN:
-          if (threadIdx.x < 128)
-            fmt_attn_body<T, 16, true, true, true>(c.qkv16, 3 * c.D, st.att_out, c.ntok, c.M, c.D, c.window, c.ntok_div, st.pf, c.sat,
-                                                   (int)(bid % (unsigned)c.heads), (int)(bid / (unsigned)c.heads), 128, bid, st.nblk);
-          break;
-        case MS_PROJ: {
-          GemmArgs g = st.g;
-          g.gate = d.mod + st.gate_off;
-          fmt_gemm_body<T, 3, 1, 8, EPI_GATE_RES, true>(g, bid, st.nblk);
-          break;
-        }
-        case MS_FC1:
-          fmt_gemm_body<T, 3, 4, 8, EPI_GELU_P16, true>(st.g, bid, st.nblk);
-          break;
-        case MS_FC2:
-          fmt_gemm_body<T, 3, 4, 8, EPI_PARTIAL, true>(st.g, bid, st.nblk);
-          break;
-        default: {  // MS_HEAD
-          GemmArgs g = st.g;
-          g.a_cfg = d.a;
-          g.r_cfg = d.r;
-          g.e_cfg = d.e;
-          g.dt = d.dt;
-          if (!d.euler) {
-            g.xcur = nullptr;
-            g.xin16 = nullptr;
-            g.vout = d.vout;
-          }
-          fmt_gemm_body<T, 3, 1, 8, EPI_CFG, true>(g, bid, st.nblk);
-          break;
-        }
-      }
-    }
-    MEGA_STAMP(1);
-    if (s + 1 < nstage) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this workgroup's write-through stores have left
-      __syncthreads();
-      MEGA_STAMP(2);
-      if (threadIdx.x == 0) {
-        // the next stage's descriptor (5 lines of the table) into the scalar cache while the barrier is awaited (-0.3 us per stage)
-        int pre = 0;
-#pragma unroll
-        for (int i = 0; i < (int)(sizeof(MegaStage) + 63) / 64; ++i) pre ^= reinterpret_cast<const int*>(&tab[s + 1])[i * 16];
-        asm volatile("" ::"s"(pre));
-        if (!fmt_grid_barrier(sy, gen0 + (unsigned)s + 1u, nwg)) s_flag[1] = 0u;
-      }
-      __syncthreads();
-      if (s_flag[1] == 0u) return;
-    }
-  }
-  if (bid == 0 && threadIdx.x == 0) __hip_atomic_store((gu32*)sy.seq, seq0 + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  fmt_attn_body<T, LPQ, TOUCH, WT>(qkv, ld, out, ntok, M, D, window, FmtDiv{ntok_mul, ntok_sh}, pf, sat, blockIdx.x, blockIdx.y,
+                                   nthr, blockIdx.x + (unsigned)heads * blockIdx.y, (unsigned)(heads * nrun));
 }
 
 // Condition rows for c_embedder: [wr | wa | we | 0-pad] per (cfg row b, token i) with the CFG nulling

@@ -1,6 +1,6 @@
 // From a GemmArgs to a launch: the FMT's kernel instantiation lists, the raising of their dynamic-LDS limits, the tiling
 // choices, and the launchers of the GEMM families (generic, wide, LDS-DMA, persistent projection, row-blocked), LayerNorm,
-// attention and fused attention + proj.  Knows nothing of struct float_fmt: launchers that read a handle's workspace get it
+// and attention.  Knows nothing of struct float_fmt: launchers that read a handle's workspace get it
 // through FmtLaunch.  Included by fmt_api.hip only, after the kernel headers (the one translation unit that holds the FMT
 // kernels' instantiations).
 #pragma once
@@ -109,9 +109,8 @@ void for_each_rbs(F&& f) {
   rbs_tile<T, EPI, 6, 4, 2, 3>(f, 2);
 }
 
-// the two persistent kernels: one workgroup per CU (fmt_gemm_big4_kernel), 256 workgroups of 512 threads (fmt_mega_kernel)
+// the persistent projection kernel: one workgroup per CU (fmt_gemm_big4_kernel)
 constexpr int kBigSmem = 4 * 28 * 1024 + 4 * 4096;
-constexpr int kMegaWgs = 256, kMegaSmem = 8 * 48 * 64 * 4;
 
 template <class T>
 void prime_kernels() {
@@ -135,7 +134,6 @@ void prime_kernels() {
     for_each_rbs<T, EPI_T16>(raise_rb);
     for_each_rbs<T, EPI_GELU_P16>(raise_rb);
     for_each_rbs<T, EPI_PARTIAL>(raise_rb);
-    raise_lds(fmt_mega_kernel<T>, kMegaSmem);
   }
 }
 
@@ -525,30 +523,6 @@ void launch_attn(const FmtLaunch& cx, int M, const Lin* pull) {
   const FmtDiv nd = fmt_make_div((unsigned)cx.ntok);
   hipLaunchKernelGGL(kern, grid, block, 0, cx.s, cx.qkv16, cx.att16, 3 * cx.D, cx.ntok, M, cx.D, cx.attn_window, (int)block.x, nd.mul, nd.sh,
                      (int)grid.x, (int)grid.y, cx.sat, pf);
-}
-
-// Banded attention + attn.proj as one launch (fmt_attnproj_kernel): slab[head] = attention_head(qkv16) @ W_proj[:, head]^T for
-// the M rows; the caller hands the fold (bias, gate, residual) to the next LayerNorm launch through PendingRed with ks = heads.
-// FLOAT_FMT_ATTNPROJ=1|2 (heads per workgroup; read at float_fmt_create) selects it; the default is the two-launch form
-// (fmt_attn_kernel, then the proj GEMM), which measured the same or faster - see the kernel's header.
-int attnproj_hpw(const FmtTune& tn, int D, int heads) {
-  const int hpw = tn.attnproj;
-  if (hpw <= 0 || D != heads * 128 || heads % hpw) return 0;
-  const int ks = heads / hpw;
-  return (ks == 1 || ks == 2 || ks == 4 || ks == 8) && (hpw == 1 || hpw == 2) ? hpw : 0;
-}
-template <class T>
-int launch_attnproj(const FmtLaunch& cx, int M, const Lin& proj) {
-  const int hpw = attnproj_hpw(cx.tn, cx.D, cx.heads);
-  GemmArgs g = base_args(nullptr, proj, M);
-  g.sat = cx.sat;
-  to_slab(g, cx.slab, cx.Mpad, cx.heads / hpw);
-  g.mblk = ((M + 15) / 16 + 2) / 3;
-  const dim3 grid((unsigned)(g.ksplit * (g.N / (128 / hpw)) * g.mblk));
-  fh_launch_prof(0, hpw == 2 ? fmt_attnproj_kernel<T, 3, 2> : fmt_attnproj_kernel<T, 3, 1>, grid, dim3(512), 0, cx.s, cx.qkv16, 3 * cx.D, g,
-                 cx.ntok, cx.D, cx.attn_window);
-  FH_CHECK_HIP(hipGetLastError());
-  return FLOAT_OK;
 }
 
 }  // namespace

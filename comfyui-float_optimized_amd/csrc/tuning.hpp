@@ -79,9 +79,6 @@ struct FmtTune {
   int ln_rows = 1;       // FLOAT_FMT_LN_ROWS: rows (waves) per LayerNorm workgroup, 1..4 (4 rows per workgroup: +0.4 %)
   int attn_qpw = 8, attn_lpq = 16;  // FLOAT_FMT_ATTN="qpw,lpq": queries per workgroup / lanes per query, 16 or 8 (r01: 16 lanes 81.5-81.9 ms per 250 evaluations, 8 lanes 82.3-82.9)
   bool no_tokblk = false;  // FLOAT_FMT_NO_TOKBLK (set at all): the all-rows-per-workgroup head GEMM for one clip, at most 15 row tiles (a debugging aid)
-  int attnproj = 0;      // FLOAT_FMT_ATTNPROJ=1|2: heads per workgroup of the fused attention + proj launch, 0 = two launches
-  int mega = 0;          // FLOAT_FMT_MEGA=1: the step chain of an evaluation as ONE persistent kernel; 0 = the 59-launch chain (faster).  The handle clears it when the kernel cannot be resident or its watchdog fired.
-  int mega_stamp_wg = 0;   // FLOAT_FMT_MEGA_STAMP_WG: the workgroup that writes the persistent kernel's stage stamps (-DMEGA_STAMPS builds)
   bool pack_host = false;  // FLOAT_PACK_HOST=1 packs the weights in the host loop instead of on the device (the A/B switch; equal bit for bit)
 
   static FmtTune from_env() {
@@ -113,9 +110,6 @@ struct FmtTune {
     t.attn_lpq = attn[1] == 16 ? 16 : 8;
     t.attn_qpw = std::max(1, std::min(512 / t.attn_lpq, attn[0]));
     t.no_tokblk = env_set("FLOAT_FMT_NO_TOKBLK");
-    t.attnproj = env_atoi("FLOAT_FMT_ATTNPROJ", 0);
-    t.mega = env_atoi("FLOAT_FMT_MEGA", 0);
-    t.mega_stamp_wg = env_atoi("FLOAT_FMT_MEGA_STAMP_WG", 0);
     t.pack_host = env_atoi("FLOAT_PACK_HOST", 0) != 0;
     return t;
   }

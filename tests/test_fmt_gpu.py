@@ -150,34 +150,6 @@ def test_graph_cache_is_bounded():
     assert torch.equal(fmt.sample(r_s, wa, we, noise, 4, 1.5, 1.0, 1.0).cpu(), first)
 
 
-@pytest.mark.parametrize("hpw", [1, 2])
-@pytest.mark.parametrize("dtype", ["fp16", "fp32"])
-def test_fused_attention_proj_launch(hpw, dtype, monkeypatch):
-    """FLOAT_FMT_ATTNPROJ=1|2: banded attention and attn.proj in ONE launch (split-K over the heads, folded by the next
-    LayerNorm launch; FMT.py:71-89) against the same reference goldens as the default two-launch chain, and bitwise
-    reproducible from run to run."""
-    monkeypatch.setenv("FLOAT_FMT_ATTNPROJ", str(hpw))
-    g = golden("fmt_eval_full")
-    cfg = C.FmtConfig()
-    sd, fmt = _fmt(cfg, g["seed"], dtype)
-    tol = 2e-5 if dtype == "fp32" else TOL[dtype]
-    for case in ("cfg3", "cfg4"):
-        a, r, e, rc = [float(v) for v in g[case + "_scales"]]
-        call = lambda: fmt.forward_with_cfv(g["t"], g[case + "_x"], g[case + "_wa"], g[case + "_wr"], g[case + "_we"],  # noqa: E731
-                                            g[case + "_prev_x"], g[case + "_prev_wa"], g.get(case + "_prev_we"),
-                                            a_cfg_scale=a, r_cfg_scale=r, e_cfg_scale=e, include_r_cfg=bool(rc)).cpu()
-        out = call()
-        err = rel_l2(out, g[case + "_out"])
-        print("fused hpw=%d" % hpw, dtype, case, "rel-L2 %.3e" % err)
-        assert err < tol, (case, err)
-        assert torch.equal(out, call())
-    assert fmt.saturation() == 0
-    gs = golden("fmt_sample_full_static")
-    sd, fmt = _fmt(cfg, gs["seed"], dtype)
-    r_d = fmt.sample(gs["r_s"], gs["wa"], gs["we"], gs["noise"], gs["nfe"], gs["a"], 1.0, gs["e"]).cpu()
-    assert rel_l2(r_d, gs["r_d"]) < tol
-
-
 def test_fmt_saturation_counter_fires():
     """float_fmt_saturation: x_embedder input rows beyond fp16's range (|x| = 1e6 > 65504) are clamped AND counted in the fp16
     handle; the bf16 handle (fp32's exponent range) reports 0.  Without this, `saturation() == 0` elsewhere would prove nothing."""
@@ -192,21 +164,3 @@ def test_fmt_saturation_counter_fires():
         n = fmt.saturation(reset=True)
         print(dtype, "clamped-store threads with |x| = 1e6:", n)
         assert (n > 0) == expect and fmt.saturation() == 0
-
-
-def test_persistent_evaluation_kernel(monkeypatch):
-    """FLOAT_FMT_MEGA=1: the 59 stages of an evaluation as ONE persistent kernel with in-kernel grid barriers (write-through
-    stores, coherent loads, no fences) instead of 59 dependent launches.  Same stage bodies, so it agrees with the launch chain
-    to rounding (x-embed splits K over 8 waves instead of 4), holds the goldens, is bitwise reproducible, and its barrier
-    watchdog stays silent (float_fmt_saturation returns an error if a barrier timed out)."""
-    g = golden("fmt_sample_full_static")
-    cfg = C.FmtConfig()
-    sd, chain = _fmt(cfg, g["seed"], "fp16")
-    ref = chain.sample(g["r_s"], g["wa"], g["we"], g["noise"], g["nfe"], g["a"], 1.0, g["e"]).cpu()
-    monkeypatch.setenv("FLOAT_FMT_MEGA", "1")
-    sd, mega = _fmt(cfg, g["seed"], "fp16")
-    a = mega.sample(g["r_s"], g["wa"], g["we"], g["noise"], g["nfe"], g["a"], 1.0, g["e"]).cpu()
-    b = mega.sample(g["r_s"], g["wa"], g["we"], g["noise"], g["nfe"], g["a"], 1.0, g["e"]).cpu()
-    print("persistent kernel vs launch chain rel-L2 %.3e, vs reference %.3e" % (rel_l2(a, ref), rel_l2(a, g["r_d"])))
-    assert torch.equal(a, b) and rel_l2(a, ref) < 5e-4 and rel_l2(a, g["r_d"]) < TOL["fp16"]
-    assert mega.saturation() == 0  # also raises if the barrier watchdog fired

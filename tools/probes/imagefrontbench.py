@@ -96,7 +96,7 @@ res = dict(probe="imagefrontbench", size=SIZE, seconds=SECONDS, nfe=NFE, max_fra
 for name in PORTRAITS:
     img = portrait(name)
     assert not img.is_pinned()
-    r = {"shape": list(img.shape[1:]), "megabytes": round(img.numel() * 4 / 1e6, 1)}
+    r = {"shape": list(img.shape[1:]), "mbytes": round(img.numel() * 4 / 1e6, 1)}
     r["host_inputs"] = case(lambda: agent.host_inputs(img, audio))
     r["run_inference"] = case(lambda: agent.run_inference(None, img, audio, 2.0, 1.0, 1.0, emo="neutral", no_crop=True, seed=15))
     if CHECK:
