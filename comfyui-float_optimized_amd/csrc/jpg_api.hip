@@ -37,11 +37,12 @@ const HuffSpec kHuff[4] = {{0x00, {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 
                            {0x01, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, kDcVals},
                            {0x11, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, 162, kAcChromaVals}};
 
-// frame geometry of a call; false for sizes the operator does not take
-bool jpg_plan(int32_t n_frames, int32_t h, int32_t w, int32_t restart, JpgPlan* p) {
-  if (n_frames < 1 || h < 16 || w < 16 || h > kJpgMaxSide || w > kJpgMaxSide || h % 16 || w % 16 || restart < 0 || restart > 65535) return false;
-  p->h = h, p->w = w, p->mcw = w / 16;
-  p->nmcu = (h / 16) * (w / 16);
+// frame geometry of a call; false for sizes the operator does not take.  padded: any sides from 1 on, the MCU grid rounded up.
+bool jpg_plan(int32_t n_frames, int32_t h, int32_t w, int32_t restart, bool padded, JpgPlan* p) {
+  if (n_frames < 1 || h < 1 || w < 1 || h > kJpgMaxSide || w > kJpgMaxSide || restart < 0 || restart > 65535) return false;
+  if (!padded && (h % 16 || w % 16)) return false;
+  p->h = h, p->w = w, p->mcw = (w + 15) / 16;
+  p->nmcu = ((h + 15) / 16) * p->mcw;
   p->span = restart > 0 ? std::min(restart, p->nmcu) : p->nmcu;
   p->n_int = (p->nmcu + p->span - 1) / p->span;
   // the worst case of an interval: every block at its bound, every byte stuffed
@@ -93,34 +94,37 @@ void jpg_header(const JpgPlan& p, const JpgTables& tb, int restart, JpgHeader* h
   put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
   hd->len = (int)(o - hd->bytes);
 }
-}  // namespace
-
-extern "C" {
-
-size_t float_jpg_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t restart) {
+size_t jpg_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t restart, bool padded) {
   JpgPlan p{};
-  if (!jpg_plan(n_frames, h, w, restart, &p)) return 0;
+  if (!jpg_plan(n_frames, h, w, restart, padded, &p)) return 0;
   const size_t items = (size_t)std::min(n_frames, kJpgGroup) * p.n_int;
   return jpg_slots_off(items) + items * (size_t)p.slot_bytes;
 }
 
-int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out, size_t out_cap,
-                     int64_t* offsets, void* work, size_t work_bytes, void* stream) {
-  FH_REQUIRE(rgb8 && out && offsets && work, "float_jpg_encode: null argument (rgb8, out, offsets or work)");
-  FH_REQUIRE(n_frames >= 1, "float_jpg_encode: n_frames (%d) must be positive", n_frames);
-  FH_REQUIRE(h >= 16 && w >= 16 && h <= kJpgMaxSide && w <= kJpgMaxSide && h % 16 == 0 && w % 16 == 0,
-             "float_jpg_encode: sides (%d x %d) must be multiples of 16 in 16 ... %d (4:2:0 MCUs)", h, w, kJpgMaxSide);
-  FH_REQUIRE(quality >= 1 && quality <= 100, "float_jpg_encode: quality (%d) must be 1 ... 100", quality);
-  FH_REQUIRE(restart >= 0 && restart <= 65535, "float_jpg_encode: restart (%d) must be 0 ... 65535 MCUs", restart);
-  FH_REQUIRE(((uintptr_t)rgb8 & 1u) == 0, "float_jpg_encode: rgb8 must be 2-byte aligned");
-  FH_REQUIRE(((uintptr_t)offsets & 7u) == 0, "float_jpg_encode: offsets must be 8-byte aligned");
-  FH_REQUIRE(((uintptr_t)work & 15u) == 0, "float_jpg_encode: work must be 16-byte aligned");
+// float_jpg_encode (padded = false) and float_jpg_encode_padded: one set of checks, one launch sequence.  The coding kernel is
+// jpg_code_kernel<false> whenever the frames allow its 2-byte loads - whole MCUs and an even address - and <true> otherwise, so
+// the padded entry runs float_jpg_encode's own kernel on the sizes float_jpg_encode takes.
+int jpg_encode(const char* fn, bool padded, const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart,
+               uint8_t* out, size_t out_cap, int64_t* offsets, void* work, size_t work_bytes, void* stream) {
+  FH_REQUIRE(rgb8 && out && offsets && work, "%s: null argument (rgb8, out, offsets or work)", fn);
+  FH_REQUIRE(n_frames >= 1, "%s: n_frames (%d) must be positive", fn, n_frames);
+  if (padded) {
+    FH_REQUIRE(h >= 1 && w >= 1 && h <= kJpgMaxSide && w <= kJpgMaxSide, "%s: sides (%d x %d) must be in 1 ... %d", fn, h, w, kJpgMaxSide);
+  } else {
+    FH_REQUIRE(h >= 16 && w >= 16 && h <= kJpgMaxSide && w <= kJpgMaxSide && h % 16 == 0 && w % 16 == 0,
+               "%s: sides (%d x %d) must be multiples of 16 in 16 ... %d (4:2:0 MCUs)", fn, h, w, kJpgMaxSide);
+  }
+  FH_REQUIRE(quality >= 1 && quality <= 100, "%s: quality (%d) must be 1 ... 100", fn, quality);
+  FH_REQUIRE(restart >= 0 && restart <= 65535, "%s: restart (%d) must be 0 ... 65535 MCUs", fn, restart);
+  FH_REQUIRE(padded || ((uintptr_t)rgb8 & 1u) == 0, "%s: rgb8 must be 2-byte aligned", fn);
+  FH_REQUIRE(((uintptr_t)offsets & 7u) == 0, "%s: offsets must be 8-byte aligned", fn);
+  FH_REQUIRE(((uintptr_t)work & 15u) == 0, "%s: work must be 16-byte aligned", fn);
   JpgPlan p{};
-  FH_REQUIRE(jpg_plan(n_frames, h, w, restart, &p), "float_jpg_encode: an interval of %d MCUs needs a slot beyond 2 GiB (use a restart interval)",
-             restart > 0 ? restart : (h / 16) * (w / 16));
-  const size_t need = float_jpg_work_bytes(n_frames, h, w, restart);
-  FH_REQUIRE(work_bytes >= need, "float_jpg_encode: work_bytes %zu < float_jpg_work_bytes(%d, %d, %d, %d) = %zu", work_bytes, n_frames, h, w,
-             restart, need);
+  FH_REQUIRE(jpg_plan(n_frames, h, w, restart, padded, &p), "%s: an interval of %d MCUs needs a slot beyond 2 GiB (use a restart interval)", fn,
+             restart > 0 ? restart : ((h + 15) / 16) * ((w + 15) / 16));
+  const size_t need = jpg_work_bytes(n_frames, h, w, restart, padded);
+  FH_REQUIRE(work_bytes >= need, "%s: work_bytes %zu < float_jpg_work_bytes%s(%d, %d, %d, %d) = %zu", fn, work_bytes, padded ? "_padded" : "",
+             n_frames, h, w, restart, need);
 
   JpgTables tb;
   JpgHeader hd{};
@@ -129,6 +133,7 @@ int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w
   p.hdr_len = hd.len;
 
   hipStream_t s = (hipStream_t)stream;
+  const bool whole = h % 16 == 0 && w % 16 == 0 && ((uintptr_t)rgb8 & 1u) == 0;
   const size_t items = (size_t)std::min(n_frames, kJpgGroup) * p.n_int;
   long long* dst = (long long*)work;
   int* lens = (int*)((char*)work + jpg_lens_off(items));
@@ -136,13 +141,33 @@ int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w
   for (int f0 = 0; f0 < n_frames; f0 += kJpgGroup) {  // groups share `work` in stream order
     p.frame0 = f0, p.frames = std::min(kJpgGroup, n_frames - f0);
     const dim3 grid((unsigned)p.n_int, (unsigned)p.frames);
-    hipLaunchKernelGGL(jpg_code_kernel, grid, dim3(kJpgThreads), 0, s, rgb8, p, tb, lens, slots);
+    if (whole) hipLaunchKernelGGL(jpg_code_kernel<false>, grid, dim3(kJpgThreads), 0, s, rgb8, p, tb, lens, slots);
+    else hipLaunchKernelGGL(jpg_code_kernel<true>, grid, dim3(kJpgThreads), 0, s, rgb8, p, tb, lens, slots);
     hipLaunchKernelGGL(jpg_offsets_kernel, dim3(1), dim3(kJpgThreads), 0, s, p, (const int*)lens, dst, (long long*)offsets);
     hipLaunchKernelGGL(jpg_pack_kernel, grid, dim3(kJpgThreads), 0, s, p, hd, (const int*)lens, (const long long*)dst, (const uint8_t*)slots, out,
                        (unsigned long long)out_cap);
   }
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t float_jpg_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t restart) { return jpg_work_bytes(n_frames, h, w, restart, false); }
+
+size_t float_jpg_work_bytes_padded(int32_t n_frames, int32_t h, int32_t w, int32_t restart) {
+  return jpg_work_bytes(n_frames, h, w, restart, true);
+}
+
+int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out, size_t out_cap,
+                     int64_t* offsets, void* work, size_t work_bytes, void* stream) {
+  return jpg_encode("float_jpg_encode", false, rgb8, n_frames, h, w, quality, restart, out, out_cap, offsets, work, work_bytes, stream);
+}
+
+int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out,
+                            size_t out_cap, int64_t* offsets, void* work, size_t work_bytes, void* stream) {
+  return jpg_encode("float_jpg_encode_padded", true, rgb8, n_frames, h, w, quality, restart, out, out_cap, offsets, work, work_bytes, stream);
 }
 
 }  // extern "C"

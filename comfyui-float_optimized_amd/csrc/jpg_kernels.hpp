@@ -18,6 +18,11 @@
 //                       files' offsets (continuing from the previous group's last one) and every interval's place in `out`.
 //   jpg_pack_kernel     grid as jpg_code_kernel: header (first interval) or RSTk, the interval's bytes, EOI (last interval) into
 //                       `out`; a byte at or beyond out_cap is not written.
+// jpg_code_kernel<PAD>: <false> is the kernel of frames made of whole MCUs at an even address, stage (1) as stated.  <true>
+// (float_jpg_encode_padded, any sides from 1 x 1 on, any address) differs in stage (1) ONLY: the MCU grid is ceil(h / 16) x
+// ceil(w / 16) and a lane's four pixels sit at rows min(py + dy, h - 1) and columns min(px + dx, w - 1) - the last row and column
+// replicated into the partial MCUs, on RGB, in front of the conversion - read with single-byte loads, since 3 w and 3 h w may be
+// odd.  No read leaves a frame's h w 3 bytes.  Stages (2) - (6) and the two other kernels see whole MCUs either way.
 // The Huffman code tables, the quantiser tables and the header bytes are built on the host inside the call and reach the kernels
 // as KERNEL ARGUMENTS (JpgTables, 2432 bytes; JpgHeader, 644 bytes): no device table, no copy.  wave64 throughout.
 #pragma once
@@ -134,6 +139,9 @@ __device__ __forceinline__ int jpg_block(const int16_t* c, int prev_dc, const ui
   return len;
 }
 
+// PAD = false: both sides are multiples of 16 and rgb is 2-byte aligned.  PAD = true: any sides and any address; p.mcw and p.nmcu
+// count the partial MCUs too.
+template <bool PAD>
 __global__ __launch_bounds__(kJpgThreads) void jpg_code_kernel(const uint8_t* __restrict__ rgb, JpgPlan p, JpgTables tb, int* __restrict__ lens,
                                                                uint8_t* __restrict__ slots) {
   __shared__ int16_t s_smp[kJpgChunkBlocks * kJpgBlkStride];   // samples, then pass 1's result, per block row-major
@@ -172,9 +180,16 @@ __global__ __launch_bounds__(kJpgThreads) void jpg_code_kernel(const uint8_t* __
       int16_t* yb = s_smp + (m * 6 + (qy >> 2) * 2 + (qx >> 2)) * kJpgBlkStride + ((2 * qy) & 7) * 8 + ((2 * qx) & 7);
 #pragma unroll
       for (int dy = 0; dy < 2; ++dy) {
-        const unsigned short* s = reinterpret_cast<const unsigned short*>(img + ((size_t)(py + dy) * p.w + px) * 3);
-        const unsigned a = s[0], b = s[1], c = s[2];
-        const int r0 = a & 255, g0 = a >> 8, b0 = b & 255, r1 = b >> 8, g1 = c & 255, b1 = c >> 8;
+        int r0, g0, b0, r1, g1, b1;
+        if constexpr (!PAD) {
+          const unsigned short* s = reinterpret_cast<const unsigned short*>(img + ((size_t)(py + dy) * p.w + px) * 3);
+          const unsigned a = s[0], b = s[1], c = s[2];
+          r0 = a & 255, g0 = a >> 8, b0 = b & 255, r1 = b >> 8, g1 = c & 255, b1 = c >> 8;
+        } else {  // the last row and column fill the partial MCUs; 3 w and 3 h w may be odd: byte loads
+          const uint8_t* row = img + (size_t)min(py + dy, p.h - 1) * p.w * 3;
+          const uint8_t *s0 = row + (size_t)min(px, p.w - 1) * 3, *s1 = row + (size_t)min(px + 1, p.w - 1) * 3;
+          r0 = s0[0], g0 = s0[1], b0 = s0[2], r1 = s1[0], g1 = s1[1], b1 = s1[2];
+        }
         yb[dy * 8] = (int16_t)(((19595 * r0 + 38470 * g0 + 7471 * b0 + 32768) >> 16) - 128);
         yb[dy * 8 + 1] = (int16_t)(((19595 * r1 + 38470 * g1 + 7471 * b1 + 32768) >> 16) - 128);
         cb += ((-11059 * r0 - 21709 * g0 + 32768 * b0 + (128 << 16) + 32767) >> 16) + ((-11059 * r1 - 21709 * g1 + 32768 * b1 + (128 << 16) + 32767) >> 16);

@@ -587,22 +587,31 @@ def jpeg_huffman_codes(bits, vals):
     return codes
 
 
-def _jpeg_geometry(h, w, restart):
+JPEG_PAD_MAX_SIDE = 16384  # the largest side pad="edge" takes: float_jpg_encode_padded's
+
+
+def _jpeg_geometry(h, w, restart, pad=None):
     h, w = int(h), int(w)
-    if h < 16 or w < 16 or h % 16 or w % 16 or h > 65520 or w > 65520:
-        raise ValueError("JPEG 4:2:0 frames have sides that are multiples of 16 (got %d x %d)" % (h, w))
-    restart = w // 16 if restart is None else int(restart)
+    if pad is None:
+        if h < 16 or w < 16 or h % 16 or w % 16 or h > 65520 or w > 65520:
+            raise ValueError("JPEG 4:2:0 frames have sides that are multiples of 16 (got %d x %d)" % (h, w))
+    elif pad != "edge":
+        raise ValueError("JPEG pad must be None or \"edge\" (got %r)" % (pad,))
+    elif not (1 <= h <= JPEG_PAD_MAX_SIDE and 1 <= w <= JPEG_PAD_MAX_SIDE):
+        raise ValueError("JPEG frames under pad=\"edge\" have sides in 1 ... %d (got %d x %d)" % (JPEG_PAD_MAX_SIDE, h, w))
+    restart = -(-w // 16) if restart is None else int(restart)
     if not 0 <= restart <= 65535:
         raise ValueError("JPEG restart interval must be 0 ... 65535 MCUs (got %r)" % (restart,))
     return h, w, restart
 
 
-def jpeg_header(h, w, quality, restart):
+def jpeg_header(h, w, quality, restart, pad=None):
     """Everything of the file in front of the scan data: SOI, APP0 (JFIF 1.1, density 1:1), DQT 0 and 1 (8-bit, zigzag order),
     SOF0 (8 bits, h x w, Y 2x2 with table 0, Cb and Cr 1x1 with table 1), DHT DC0, AC0, DC1, AC1 (Annex K.3), DRI when
-    restart > 0, SOS (one interleaved scan, Ss 0, Se 63).  restart: MCUs per interval, 0 none, None one MCU row."""
+    restart > 0, SOS (one interleaved scan, Ss 0, Se 63).  restart: MCUs per interval, 0 none, None one MCU row (ceil(w / 16)).
+    pad: as in jpeg_encode_rgb8 - SOF0 carries the true h and w."""
     import struct
-    h, w, restart = _jpeg_geometry(h, w, restart)
+    h, w, restart = _jpeg_geometry(h, w, restart, pad)
     out = [b"\xff\xd8", b"\xff\xe0", struct.pack(">H5sBBBHHBB", 16, b"JFIF\0", 1, 1, 0, 1, 1, 0, 0)]
     for i, t in enumerate(jpeg_tables(quality)):
         out += [b"\xff\xdb", struct.pack(">HB", 67, i), bytes(int(t[z]) for z in JPEG_ZIGZAG)]
@@ -652,10 +661,16 @@ def jpeg_quantised_blocks(frames_u8, quality):
     return c.reshape(T, my * mx, 6, 64)[..., list(JPEG_ZIGZAG)].astype(np.int32)
 
 
-def jpeg_encode_rgb8(frames_u8, quality=90, restart=None, stats=False):
+def jpeg_encode_rgb8(frames_u8, quality=90, restart=None, stats=False, pad=None):
     """(T, H, W, 3) or (H, W, 3) uint8 RGB (a torch tensor on any device, or a numpy array) -> a list of `bytes`, one complete
-    baseline JFIF file per frame (4:2:0, one interleaved scan, the standard Huffman tables).  H and W are multiples of 16.  This
-    is the definition of what float_jpg_encode writes: all of it is integer arithmetic, `>>` an arithmetic shift.
+    baseline JFIF file per frame (4:2:0, one interleaved scan, the standard Huffman tables).  H and W are multiples of 16 (any
+    size with pad="edge").  This is the definition of what float_jpg_encode and float_jpg_encode_padded write: all of it is
+    integer arithmetic, `>>` an arithmetic shift.
+      pad      None: sides that are no multiples of 16 are refused.  "edge": any H and W in 1 ... 16384; the coded area is
+               ceil(H / 16) x ceil(W / 16) MCUs and its sample (y, x) is the source pixel (min(y, H - 1), min(x, W - 1)) - the last
+               row and column replicated, on RGB, in front of everything below, which is unchanged; SOF0 carries the true H and W
+               and the decoder crops.  (Plain replication, not libjpeg's DC-only dummy blocks.)  Sides that are multiples of 16
+               give the bytes of pad=None.
       colour   full-range BT.601 per pixel: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
                Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16;
                chroma subsampled 2 x 2 by (c00 + c01 + c10 + c11 + 2) >> 2 on the converted planes; level shift -128
@@ -679,8 +694,10 @@ def jpeg_encode_rgb8(frames_u8, quality=90, restart=None, stats=False):
     if x.ndim == 3:
         x = x[None]
     T, H, W, _ = x.shape
-    H, W, ri = _jpeg_geometry(H, W, restart)
-    header = jpeg_header(H, W, quality, ri)
+    H, W, ri = _jpeg_geometry(H, W, restart, pad)
+    header = jpeg_header(H, W, quality, ri, pad)
+    if H % 16 or W % 16:  # pad="edge": the last row and column fill the partial MCUs
+        x = x[:, np.minimum(np.arange(-(-H // 16) * 16), H - 1)][:, :, np.minimum(np.arange(-(-W // 16) * 16), W - 1)]
     zz = jpeg_quantised_blocks(x, quality).astype(np.int64)
     nmcu = zz.shape[1]
     nblk = nmcu * 6

@@ -196,8 +196,11 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
     return out
 
 
-def require_jpeg_sides(what, H, W):
-    """float_jpg_encode takes frames whose sides are multiples of 16; a pasted clip has the portrait's size.  Nothing is padded."""
-    if H % JPEG_SIDE_MULTIPLE or W % JPEG_SIDE_MULTIPLE:
+def require_jpeg_sides(what, H, W, pad=None):
+    """float_jpg_encode takes frames whose sides are multiples of 16; a pasted clip has the portrait's size.  Nothing is padded
+    unless the caller opts in: pad="edge" (float_jpg_encode_padded) passes any size."""
+    if pad is not None and pad != "edge":
+        raise ValueError("%s: pad must be None or \"edge\" (got %r)" % (what, pad))
+    if pad is None and (H % JPEG_SIDE_MULTIPLE or W % JPEG_SIDE_MULTIPLE):
         raise ValueError("%s: a %d x %d portrait cannot leave as JPEG - float_jpg_encode needs sides that are multiples of 16 "
                          "(crop or resize the portrait, or take the frames with infer_pasted)" % (what, H, W))

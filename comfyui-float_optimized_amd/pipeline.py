@@ -284,8 +284,8 @@ class _JpegSink:
     are the pasted H x W ones, and the window's 8-bit crops go through one shared device buffer."""
     name = "stream_to_jpeg"
 
-    def __init__(self, hot, quality, restart, place=None, feather=None):
-        self.hot, self.quality, self.restart, self.place, self.feather = hot, quality, restart, place, feather
+    def __init__(self, hot, quality, restart, place=None, feather=None, pad=None):
+        self.hot, self.quality, self.restart, self.place, self.feather, self.pad = hot, quality, restart, place, feather, pad
 
     def open(self, slots):
         dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
@@ -299,7 +299,8 @@ class _JpegSink:
         return ring
 
     def _encode(self, slot, n):
-        self.work = jpeg.enqueue_encode(slot["u8"][:n], self.quality, self.restart, slot["data"], slot["off"][:n + 1], self.work)
+        self.work = jpeg.enqueue_encode(slot["u8"][:n], self.quality, self.restart, slot["data"], slot["off"][:n + 1], self.work,
+                                         self.pad)
 
     def enqueue(self, slot, s_r_d, rows):
         n = rows.shape[0]
@@ -694,7 +695,7 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                         quality=90, restart=None, return_rd=False, place=None, feather=None):
+                         quality=90, restart=None, return_rd=False, place=None, feather=None, pad=None):
         """generate_to_host for one clip (B = 1) with the frames leaving as baseline JPEG files (jpeg.JpegFrames in pinned host
         memory): the chain, decode_u8 of the whole clip, float_jpg_encode on the 8-bit frames in HBM, ONE host read of the
         offsets, then offsets[T] bytes across PCIe - the files, not the frames.  File i is bitwise
@@ -703,10 +704,13 @@ class FloatHotPath:
         place (a Placement; default None: nothing above changes): the 8-bit crops are pasted back into the portrait on the device
         (float_img_paste, `feather` as in generate_pasted) and the encoder codes the H x W frames - file i is jpeg_encode_rgb8 of
         frame i of generate_pasted, and T * H * W * 3 more bytes of HBM are held while it runs.  float_jpg_encode takes sides that
-        are multiples of 16: another portrait size is a ValueError here, before anything runs; nothing is padded."""
+        are multiples of 16: another portrait size is a ValueError here, before anything runs; nothing is padded - unless
+        pad="edge" (default None) opts in: float_jpg_encode_padded then takes any portrait size, replicating the last row and column
+        into the partial MCUs, and file i is jpeg_encode_rgb8(..., pad="edge") of the same frame (restart=None: ceil(W / 16))."""
+        jpeg.check_pad(pad)
         if place is not None:
             place = _check_place("generate_to_jpeg", place, self.device)
-            image.require_jpeg_sides("generate_to_jpeg", *place.size)
+            image.require_jpeg_sides("generate_to_jpeg", *place.size, pad=pad)
         self.require_no_stream("generate_to_jpeg")
         if feats is not None:
             self.dec.set_feats(feats)
@@ -715,11 +719,11 @@ class FloatHotPath:
             u8 = self.dec.decode_u8(s_r, _rows(r_d))
             if place is not None:
                 u8 = image.paste_frames_device(place.src8, u8, place.rect, feather)
-            frames = jpeg.encode_jpeg_host(u8, quality, restart)
+            frames = jpeg.encode_jpeg_host(u8, quality, restart, pad=pad)
         return (frames, r_d) if return_rd else frames
 
     def stream_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                       quality=90, restart=None, slots=3, place=None, feather=None):
+                       quality=90, restart=None, slots=3, place=None, feather=None, pad=None):
         """generate_to_jpeg as a generator: one JpegBlock(first, last, frames) per FMT window, in frame order, the same files as the
         whole-clip call.  The contract is stream_to_host's: `frames` (a jpeg.JpegFrames) lives in one of `slots` pinned ring
         buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (AviMjpegWriter.write
@@ -733,16 +737,18 @@ class FloatHotPath:
         memory and copies that many bytes on a second stream.  Files beyond the slot's room (noise at quality 100) are encoded
         once more into a larger buffer.
         place, feather: as in generate_to_jpeg - the files are those of the pasted H x W frames, a slot's device buffer holds 50 of
-        them and one more buffer of 50 crops is shared; a portrait whose sides are no multiples of 16 is a ValueError at the call."""
+        them and one more buffer of 50 crops is shared; a portrait whose sides are no multiples of 16 is a ValueError at the call,
+        unless pad="edge" (as in generate_to_jpeg; the overflow re-encode pads the same way)."""
+        jpeg.check_pad(pad)
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError("stream_to_jpeg: quality (%d) must be 1 ... 100" % quality)
         width = self.size
         if place is not None:
             place = _check_place("stream_to_jpeg", place, self.device)
-            image.require_jpeg_sides("stream_to_jpeg", *place.size)
+            image.require_jpeg_sides("stream_to_jpeg", *place.size, pad=pad)
             width = place.size[1]
-        sink = _JpegSink(self, quality, jpeg.default_restart(width) if restart is None else int(restart), place, feather)
+        sink = _JpegSink(self, quality, jpeg.pad_restart(width, pad) if restart is None else int(restart), place, feather, pad)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 

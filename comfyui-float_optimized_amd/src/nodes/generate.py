@@ -475,20 +475,22 @@ class InferenceAgent:
         return self._stream_clip("InferenceAgent.stream_device_jpeg", s, a, emo, seed, _stream_device_jpeg)
 
     def write_video(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                    quality=90, fps=None, paste_back=False, feather=None):
+                    quality=90, fps=None, paste_back=False, feather=None, pad=None):
         """A playable file: host_inputs, stream_device_jpeg, and host_models.AviMjpegWriter on `path` (a path or a seekable binary
         file object) - Motion JPEG in an AVI container with the clip's audio as a 16-bit PCM track: the AUDIO item's own samples
         at its own rate, channels mixed to mono (not the normalised 16 kHz waveform the model hears), one `01wb` chunk behind the
         frames of every window.  fps defaults to opt.fps.  Returns the number of frames written.
         paste_back=True: the frames are the user's portrait with the generated face pasted back (stream_pasted_jpeg, `feather` as
         in infer_pasted) and the file is written at the portrait's size, whose sides must be multiples of 16 (ValueError
-        otherwise, before the file is opened)."""
+        otherwise, before the file is opened) unless pad="edge" (as in infer_pasted_jpeg) opts in to any size: a 1920 x 1080
+        portrait then gives a 1920 x 1080 file.  pad has no say without paste_back: the crops are model-size frames."""
         o = self.opt
         fps = o.fps if fps is None else fps
         if paste_back:
             img = ref_img[0] if ref_img.dim() == 4 else ref_img
             height, width = int(img.shape[0]), int(img.shape[1])
-            blocks = self.stream_pasted_jpeg(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, quality)
+            blocks = self.stream_pasted_jpeg(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, quality,
+                                             pad=pad)
         else:
             height = width = o.input_size
             with torch.no_grad():
@@ -508,12 +510,13 @@ class InferenceAgent:
             return w.frames
 
     # ------------------------------------------------------------------ paste back: the frames in the user's portrait
-    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None):
-        """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take; with
+    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None, pad=None):
+        """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take
+        (pad="edge": none) or a pad that is neither None nor "edge"; with
         out_format="i420", a portrait with an odd side; an out_format that is none of None, "rgb", "i420"."""
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         if jpeg_out:
-            require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]))
+            require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]), pad)
         if paste_format(what, out_format) == "i420":
             require_even_sides(what, int(img.shape[0]), int(img.shape[1]))
 
@@ -600,35 +603,39 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                          feather=None, quality=90, restart=None):
+                          feather=None, quality=90, restart=None, pad=None):
         """infer_pasted with the frames leaving as baseline JPEG files: a jpeg.JpegFrames in pinned host memory, file i bitwise
         host_models.jpeg_encode_rgb8(infer_pasted(...)[i], quality, restart).  Paste and encoder run on the device and only the
         files cross PCIe.  float_jpg_encode takes sides that are multiples of 16: a portrait of another size is a ValueError at
-        this call, before anything runs - nothing is padded.  FLOAT_AMD_RANGE applies as in infer_device_jpeg; FLOAT_AMD_VERIFY is
-        NOT applied and FLOAT_AMD_OVERLAP is ignored."""
-        self._paste_call("infer_pasted_jpeg", ref_img, jpeg_out=True)
+        this call, before anything runs - nothing is padded.  pad="edge" (default None) opts in to any portrait size:
+        float_jpg_encode_padded replicates the last row and column into the partial 16 x 16 MCUs, the files carry the true size, file
+        i is bitwise jpeg_encode_rgb8(infer_pasted(...)[i], quality, restart, pad="edge"), and restart=None is ceil(W / 16) MCUs.
+        FLOAT_AMD_RANGE applies as in infer_device_jpeg; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        self._paste_call("infer_pasted_jpeg", ref_img, jpeg_out=True, pad=pad)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             frames = self.G.generate_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                             noise=noise, quality=quality, restart=restart, place=place, feather=feather)
+                                             noise=noise, quality=quality, restart=restart, place=place, feather=feather, pad=pad)
             if self.check_range("InferenceAgent.infer_pasted_jpeg", allow_rebuild=True) != "rebuilt":
                 return frames  # otherwise once more, in the wider types
 
     def stream_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                           feather=None, quality=90, restart=None, slots=3):
+                           feather=None, quality=90, restart=None, slots=3, pad=None):
         """The streaming sibling of infer_pasted_jpeg: a generator of JpegBlock(first, last, frames) under the ring rules of
         stream_device_jpeg - concatenated, the files infer_pasted_jpeg returns.  slots < 2, a quality outside 1 ... 100 or a portrait
-        whose sides are no multiples of 16 raise ValueError here, at the call.  FLOAT_AMD_RANGE is applied once after the last block
-        (auto acts as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        whose sides are no multiples of 16 (without pad="edge", which is infer_pasted_jpeg's) raise ValueError here, at the call.
+        FLOAT_AMD_RANGE is applied once after the last block (auto acts as warn); FLOAT_AMD_VERIFY is NOT applied and
+        FLOAT_AMD_OVERLAP is ignored."""
         self._check_stream_call("stream_pasted_jpeg", slots)
         if not 1 <= int(quality) <= 100:
             raise ValueError("stream_pasted_jpeg: quality (%r) must be 1 ... 100" % (quality,))
-        self._paste_call("stream_pasted_jpeg", ref_img, jpeg_out=True)
+        self._paste_call("stream_pasted_jpeg", ref_img, jpeg_out=True, pad=pad)
 
         def _stream_pasted_jpeg(c, noise, place):
             return self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                         noise=noise, quality=int(quality), restart=restart, slots=int(slots), place=place, feather=feather)
+                                         noise=noise, quality=int(quality), restart=restart, slots=int(slots), place=place, feather=feather,
+                                         pad=pad)
         return self._stream_placed("InferenceAgent.stream_pasted_jpeg", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_jpeg)
 
     def range_counts(self, reset=True):

@@ -39,7 +39,8 @@ extern "C" {
 
 /* Stays 6: float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
  * float_img_paste (the generated frames back in the source portrait on the device),
- * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device),
+ * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device) and
+ * float_jpg_encode_padded / float_jpg_work_bytes_padded (the same for sides that are no multiples of 16),
  * float_img_front / float_img_front_work_bytes (the image front end on the device),
  * float_aud_front / float_aud_front_len / float_aud_front_work_bytes (the audio front end on the device),
  * float_cmp_segments / float_cmp_work_bytes (the precision guard's on-device comparison), float_dec_frames_u8 /
@@ -638,6 +639,20 @@ int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, cons
 size_t float_jpg_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t restart);
 int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out, size_t out_cap,
                      int64_t* offsets, void* work, size_t work_bytes, void* stream);
+
+/* float_jpg_encode for frames of ANY size, opt-in: h and w in 1 ... 16384, rgb8 of any alignment; everything else - arguments,
+ * checks, messages, the capacity rule of `out` and `offsets` - as above.  The scan codes ceil(h / 16) x ceil(w / 16) whole MCUs
+ * and sample (y, x) of that area is the source pixel (min(y, h - 1), min(x, w - 1)): the last row and the last column are
+ * replicated into the partial MCUs, on RGB, in front of the colour conversion (so a chroma sample is the (sum + 2) >> 2 of the
+ * four clamped pixels); SOF0 carries the true h and w and a decoder crops.  Plain replication, not libjpeg's DC-only dummy
+ * blocks.  Bitwise host_models.jpeg_encode_rgb8(..., pad="edge"); one MCU row is restart = ceil(w / 16).  `work` holds
+ * float_jpg_work_bytes_padded(n_frames, h, w, restart) bytes: the formula above with the rounded-up MCU grid.
+ * With both sides multiples of 16 and rgb8 2-byte aligned the call runs the kernels of float_jpg_encode and writes its bytes;
+ * otherwise the first stage reads single bytes at clamped coordinates, never outside a frame's h w 3 bytes.
+ * float_jpg_encode and float_jpg_work_bytes themselves refuse such sizes as before. */
+size_t float_jpg_work_bytes_padded(int32_t n_frames, int32_t h, int32_t w, int32_t restart);
+int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out,
+                            size_t out_cap, int64_t* offsets, void* work, size_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,10 @@ turns in one process:
   pasted  InferenceAgent.infer_pasted;
   i420    InferenceAgent.infer_pasted(out_format="i420"): paste and colour conversion in one kernel, 1.5 bytes per pixel;
   jpeg    InferenceAgent.infer_pasted_jpeg(quality=QUALITY).
+Then the pasted JPEG clip at 1920 x 1080 under pad="edge" (1080 lines are 67.5 MCUs: float_jpg_encode_padded, the first 1080 lines
+of the 1920 x 1088 portrait) takes turns with the one at 1920 x 1088 (float_jpg_encode), REPS times after WARMUP: key
+"jpeg_1080_edge_vs_1088"; the 1088 clip of that loop is the yardstick, the first file of the 1080 clip is compared with the
+definition's.
 Each call is timed on the host clock between device synchronisations, REPS (default 10) repetitions per form after WARMUP
 (default 2), taking turns.  The paste launch alone (image.paste_frames_device on 50 crops in HBM, the product's group) is timed by
 device events, LAUNCH_REPS (default 30) times after 3, the RGB and the I420 launch taking turns, and held to the bytes it moves -
@@ -62,7 +66,7 @@ KW = dict(emo="neutral", seed=15)
 last = {}
 
 
-def run(form, img):
+def run(form, img, pad=None):
     if form == "u8":
         s, a = agent.host_inputs(img, audio, no_crop=False)
         last[form] = agent.infer_device(s, a, 2.0, 1.0, 1.0, out_dtype=torch.uint8, **KW)
@@ -71,13 +75,13 @@ def run(form, img):
     elif form == "i420":
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", **KW)
     else:
-        last[form] = agent.infer_pasted_jpeg(img, audio, 2.0, 1.0, 1.0, no_crop=False, quality=QUALITY, **KW)
+        last[form] = agent.infer_pasted_jpeg(img, audio, 2.0, 1.0, 1.0, no_crop=False, quality=QUALITY, pad=pad, **KW)
 
 
-def wall_ms(form, img):
+def wall_ms(form, img, pad=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(form, img)
+    run(form, img, pad)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3
     agent.G.release_host_inflight()
@@ -138,4 +142,22 @@ for H, W in ((1024, 1024), (1088, 1920)):
     out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), i420=last["i420"].numel(), jpeg=last["jpeg"].nbytes)
     out["paste_launch_50_frames"] = launch_alone(place, peaks)
     res["%dx%d" % (W, H)] = out
+img1088 = torch.from_numpy(np.random.RandomState(1088).rand(1, 1088, 1920, 3).astype("float32"))
+turns = (("1920x1088", img1088, None), ("1920x1080_edge", img1088[:, :1080].contiguous(), "edge"))
+ms = {name: [] for name, _, _ in turns}
+for i in range(WARMUP + REPS):
+    for name, img, pad in turns:
+        t = wall_ms("jpeg", img, pad)
+        if i >= WARMUP:
+            ms[name].append(t)
+    if i == 0:  # `last` holds the 1080 clip: its first file against the definition of the first pasted frame
+        edge_file, edge_bytes = bytes(last["jpeg"][0]), last["jpeg"].nbytes
+        first = agent.infer_pasted(turns[1][1], audio, 2.0, 1.0, 1.0, no_crop=False, **KW)[:1].clone()
+        agent.G.release_host_inflight()
+        edge_ok = edge_file == hm.jpeg_encode_rgb8(first, QUALITY, None, pad="edge")[0]
+out = {name: stats(v) for name, v in ms.items()}
+out["edge_minus_1088_ms"] = round(out["1920x1080_edge"]["median"] - out["1920x1088"]["median"], 3)
+out["bytes_to_host_1080_edge"] = edge_bytes
+out["first_file_equals_definition"] = bool(edge_ok)
+res["jpeg_1080_edge_vs_1088"] = out
 print(json.dumps(res))
