@@ -288,10 +288,10 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
   int rc;
   // Ragged clips put their SHORT piece first at every level (style chunk, low group, high batch): the last batch of the call is
   // then a full one.  A short last batch carried the previous full batch's copy in launches too short for it (its launches took
-  // as long as a full batch's) and the short first batch carries nothing.  FLOAT_DEC_SHORT_FIRST=0: remainder last.
-  auto piece = [&tn](int done, int total, int cap) {
+  // as long as a full batch's) and the short first batch carries nothing.
+  auto piece = [](int done, int total, int cap) {
     const int r = total % cap;
-    return (tn.short_first && done == 0 && r) ? r : std::min(cap, total - done);
+    return (done == 0 && r) ? r : std::min(cap, total - done);
   };
   for (int s0 = 0, ns = 0; s0 < n_frames; s0 += ns) {
     ns = piece(s0, n_frames, kStyleCap);
@@ -305,12 +305,6 @@ int frames_impl(float_dec* h, const float* s_r, const float* r_d, int n_frames, 
       if ((rc = run_low<T>(h, na, st_a, dm_a, &skip_idx, st))) return rc;
       for (int b0 = 0, nb = 0; b0 < na; b0 += nb) {
         nb = piece(b0, na, FH);
-        // ride-along hand-over: the very last batch of the call has no successor to carry its copy.  Cutting it in two so that
-        // only FLOAT_DEC_RIDE_TAIL frames' copy stays exposed was measured and is off: 30.1 ms per 250 frames without, 31.0-31.8
-        // with a tail of 4..16 frames (the smaller launches lose more than the shorter copy gains)
-        const int tail = tn.ride_tail;
-        const bool last_of_call = (s0 + a0 + b0 + nb == n_frames);
-        if (host && ride && last_of_call && tail > 0 && nb > tail) nb -= tail;
         const size_t off = (size_t)(s0 + a0 + b0) * fbytes;
         if (host && ride) h->ride.open_batch(tn, h->levels, h->lo_levels);  // this batch's launches carry the previous one's frames
         rc = run_high<T>(h, nb, b0, st_a + (size_t)b0 * h->Stot, dm_a + (size_t)b0 * h->Dtot, skip_idx, out + off, final_mode, st);

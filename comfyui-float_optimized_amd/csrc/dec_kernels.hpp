@@ -498,8 +498,6 @@ __device__ __forceinline__ void dec_flow_pixels(const FlowArgs& g, const FlowFra
     float o[PIX][3];
 #pragma unroll
     for (int k = 0; k < PIX; ++k) o[k][0] = o[k][1] = o[k][2] = 0.f;
-#ifndef DEC_DIAG_NOFLOWDOT  // timing-only build (WRONG frames): no ToFlow channel loop, no reduction - the ceiling of moving ToFlow into
-    // conv2's epilogue at the levels that keep this kernel
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const float4 w0 = *reinterpret_cast<const float4*>(sw + j * C + c0);
@@ -513,7 +511,6 @@ __device__ __forceinline__ void dec_flow_pixels(const FlowArgs& g, const FlowFra
         o[k][j] = a;
       }
     }
-#endif
 #pragma unroll
     for (int k = 0; k < PIX; ++k) {
       // bias + up-sampled previous flow enter the sum once, in the lane that owns the pixel
@@ -522,7 +519,6 @@ __device__ __forceinline__ void dec_flow_pixels(const FlowArgs& g, const FlowFra
       o[k][1] += mine ? upf[1] + bf1 : 0.f;
       o[k][2] += mine ? upf[2] + bf2 : 0.f;
     }
-#ifndef DEC_DIAG_NOFLOWDOT
     for (int d = 1; d < lpp; d <<= 1) {
 #pragma unroll
       for (int k = 0; k < PIX; ++k) {
@@ -531,7 +527,6 @@ __device__ __forceinline__ void dec_flow_pixels(const FlowArgs& g, const FlowFra
         o[k][2] += __shfl_xor(o[k][2], d, 64);
       }
     }
-#endif
     // Sample position, tap addresses and blend weights of a pixel are the same in all its lanes: lane `sub` forms them for
     // pixel sub & (PIX - 1) ONLY and the group reads them by lane index (ds_bpermute: LDS pipe) - 9 values per pixel instead of
     // ~100 vector instructions per pixel in every lane (r03 listing: a third of the kernel's 1 200 instructions per iteration,
@@ -866,18 +861,14 @@ __global__ __launch_bounds__(256, T::is32 ? 1 : 2) void dec_conv_kernel(ConvArgs
 //     depends on the halo column only, so fragment rows differ by a constant), one offset for the stores - tiles are decoded
 //     by carrying (f, ty, tx) along instead of dividing, interior tiles load without any bounds logic, border tiles take one
 //     4-bit mask per chunk (top / bottom / left / right halo membership, formed once) against the tile's border bits.
-// DB = 1 (round 4, review item 2a): the halo tile, the weight slab and the epilogue operands are DOUBLE-BUFFERED in LDS: item
-// i + 1 is written into the other buffer while item i is multiplied (the writes are spread between the three tap-column
-// groups of MFMAs), and the K loop has ONE barrier per item instead of two.  115 KB of LDS at 64 output channels: one
-// workgroup per CU instead of two.  Bitwise the same results.  MEASURED: see DESIGN.md section 7 (FLOAT_DEC_CONV_DB selects it).
 // FLOWM = 1 (round 6; the last level's conv2, whose output V feeds ToFlow and nothing else): V is never stored.  The epilogue's
 // values - rounded to the operand type exactly as the stored V was - are the B operand of one more MFMA per m-tile against
 // ToFlow's per-frame folded weights (A fragments from dec_flowfrag_kernel: row r holds output r & 3, so every lane group gets
 // the three sums of its pixel; 16-bit operands: weights as hi + lo * 2^-11, two MFMAs, exact products, i.e. fp32 weights as
 // before), and the lane that owns pixel (row w*4 + q, column r16) stores 16 bytes.  At 512 px that is 4 MB per frame written
 // and read back instead of 16.8 + 16.8, and the channel loop + cross-lane reduction of the flow kernel are gone.
-template <class T, int NT, int TY, int TX, int DB = 0, int FLOWM = 0>
-__global__ __launch_bounds__(256, (T::is32 || DB) ? 1 : 2) void dec_conv16_kernel(ConvArgs g) {
+template <class T, int NT, int TY, int TX, int FLOWM = 0>
+__global__ __launch_bounds__(256, T::is32 ? 1 : 2) void dec_conv16_kernel(ConvArgs g) {
   DEC_COPY_PROLOGUE(g, bid)
   DEC_PH_BEGIN
   typedef typename T::elem E;
@@ -891,7 +882,6 @@ __global__ __launch_bounds__(256, (T::is32 || DB) ? 1 : 2) void dec_conv16_kerne
   unsigned char* const sA = smem;              // [NPIX][RB], chunk ^ ((halo column >> 1) & 3)
   unsigned char* const sB = smem + NPIX * RB;  // [NTAPS][BN][RB], chunk ^ ((row >> 1) & 3)
   float* const sE = reinterpret_cast<float*>(sB + NBROWS * RB);  // [3][BN]: demod, bias, next style of the tile's (frame, channels)
-  constexpr int BUF = NPIX * RB + NBROWS * RB + 3 * BN * (int)sizeof(float);  // DB: the second buffer set follows the first
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // the wave index is uniform: scalar arithmetic
   const int r16 = lane & 15, q = lane >> 4;
   const int Wi = g.Wi, Cin = g.Cin;
@@ -957,17 +947,13 @@ __global__ __launch_bounds__(256, (T::is32 || DB) ? 1 : 2) void dec_conv16_kerne
   float4 re = float4{0.f, 0.f, 0.f, 0.f};
   bool first = true;
   constexpr int NPK = NT / 2, NHL = T::is32 ? 1 : 2;  // FLOWM: weight fragments per frame (packs of 32 channels x (hi, lo))
-  static_assert(!FLOWM || (!DB && (NT == 2 || NT == 4)), "ToFlow epilogue: single-buffered kernel, 32 or 64 output channels");
+  static_assert(!FLOWM || NT == 2 || NT == 4, "ToFlow epilogue: 32 or 64 output channels");
   P8 wa[FLOWM ? NPK : 1][NHL];
   auto issue = [&]() {
     const unsigned edge = (sty == 0 ? 1u : 0u) | (sty == g.tiles_y - 1 ? 2u : 0u) | (stx == 0 ? 4u : 0u) | (stx == g.tiles_x - 1 ? 8u : 0u);
     s_edge = edge;
     const long long org = ((long long)(sf * g.Hi + sty * 16 + g.dymin) * Wi + stx * 16 + g.dxmin) * Cin + (schunk << 5);
     const unsigned char* const Xo = reinterpret_cast<const unsigned char*>(g.X) + org * EB;
-#ifdef DEC_DIAG_NOLOAD  // timing-only build (WRONG frames): halo loads for the workgroup's first item only (the registers keep what they had)
-    if (!first) {
-    } else
-#endif
     if (edge == 0u) {
 #pragma unroll
       for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const P8*>(Xo + a_off[i]);
@@ -976,12 +962,7 @@ __global__ __launch_bounds__(256, (T::is32 || DB) ? 1 : 2) void dec_conv16_kerne
 #pragma unroll
       for (int i = 0; i < NA; ++i) ra[i] = *reinterpret_cast<const P8*>(Xo + (((s_hit >> (4 * i)) & 15u) ? a_safe : a_off[i]));
     }
-#ifdef DEC_DIAG_WSTAGE1  // timing-only build (WRONG frames): the weight slab is fetched and staged for the workgroup's first item only -
-    // the ceiling of any weight-stationary form of this kernel
-    if (first) {
-#else
     if (nchunks > 1 || schunk == 0) {
-#endif
       const unsigned char* const Wc = Wn + (size_t)(schunk << 5) * EB;
 #pragma unroll
       for (int i = 0; i < NB - 1; ++i) rb[i] = *reinterpret_cast<const P8*>(Wc + i * b_round + b_off);
@@ -1013,304 +994,144 @@ __global__ __launch_bounds__(256, (T::is32 || DB) ? 1 : 2) void dec_conv16_kerne
   int chunk = 0;
   issue();
   DEC_PH(8);
-  if constexpr (DB) {
-    // write the staged registers (item `it`) into buffer set `bs`, in three parts: part 0 = halo tile, 1 = weights, 2 = epilogue operands
-    const bool wdb = nchunks > 1;  // one chunk per tile: the weight slab is staged once and shared by both buffer sets
-    auto commit = [&](int bs, int part, bool wfirst, bool lastchunk) {
-      unsigned char* const dA = sA + bs * BUF;
-      unsigned char* const dB = sB + (wdb ? bs * BUF : 0);
-      if (part == 0) {
-        if (s_edge == 0u) {
+  for (int item = 0; item < nitems; ++item) {
+    __syncthreads();  // every wave is done reading the previous item's tiles
+    if (s_edge == 0u) {
 #pragma unroll
-          for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(dA + a_lds[i]) = ra[i];
-        } else {
+      for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(sA + a_lds[i]) = ra[i];
+    } else {
 #pragma unroll
-          for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(dA + a_lds[i]) = ((s_hit >> (4 * i)) & 15u) ? T::zero8() : ra[i];
-        }
-      } else if (part == 1) {
-        if (wdb || wfirst) {
-#pragma unroll
-          for (int i = 0; i < NB - 1; ++i) *reinterpret_cast<P8*>(dB + b_lds + i * 64 * RB) = rb[i];
-          *reinterpret_cast<P8*>(dB + b_lds_l) = rb[NB - 1];
-        }
-      } else {
-        if (lastchunk && tid < 3 * BN / 4) *reinterpret_cast<float4*>(reinterpret_cast<unsigned char*>(sE) + bs * BUF + tid * 16) = re;
-      }
-    };
-    // chunk index of the item being STAGED (issue() advanced schunk already): the item whose registers are pending
-    int pchunk = 0;  // chunk of the pending (loaded, not yet committed) item
-    commit(0, 0, true, nchunks == 1);
-    commit(0, 1, true, nchunks == 1);
-    commit(0, 2, true, nchunks == 1);
-    if (nitems > 1) {
-      pchunk = nchunks > 1 ? 1 : 0;
-      issue();
+      for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(sA + a_lds[i]) = ((s_hit >> (4 * i)) & 15u) ? T::zero8() : ra[i];
     }
+    if (nchunks > 1 || first) {
+#pragma unroll
+      for (int i = 0; i < NB - 1; ++i) *reinterpret_cast<P8*>(sB + b_lds + i * 64 * RB) = rb[i];
+      *reinterpret_cast<P8*>(sB + b_lds_l) = rb[NB - 1];
+      first = false;
+    }
+    if (chunk == nchunks - 1 && tid < 3 * BN / 4) *reinterpret_cast<float4*>(sE + tid * 4) = re;
     __syncthreads();
-    for (int item = 0; item < nitems; ++item) {
-      const int cur = item & 1;
-      const bool more = item + 1 < nitems;
-      const bool plast = pchunk == nchunks - 1;
-      const unsigned char* const cA = sA + cur * BUF;
-      const unsigned char* const cB = sB + (wdb ? cur * BUF : 0);
-      if (chunk == 0) {
+    DEC_PH(9);
+    if (item + 1 < nitems) issue();  // in flight while this item computes
+    if constexpr (FLOWM) {
+      if (chunk == nchunks - 1) {  // ToFlow's weight fragments of the tile's frame: in registers when the epilogue starts
+        const P8* const wf = reinterpret_cast<const P8*>(g.wfrag) + (size_t)cf * (NPK * NHL * 64) + lane;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int pk = 0; pk < NPK; ++pk)
 #pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int hl = 0; hl < NHL; ++hl) wa[pk][hl] = wf[(pk * NHL + hl) * 64];
       }
+    }
+    if (chunk == 0) {
 #pragma unroll
-      for (int tx = 0; tx < TX; ++tx) {
-        P8 b[TY][NT];
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int ty = 0; ty < TY; ++ty)
+        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
-          for (int j = 0; j < NT; ++j) b[ty][j] = *reinterpret_cast<const P8*>(cB + fb + ((ty * TX + tx) * BN + j * 16) * RB);
-        P8 a[3 + TY];
+    for (int tx = 0; tx < TX; ++tx) {
+      P8 b[TY][NT];
 #pragma unroll
-        for (int hr = 0; hr < 3 + TY; ++hr) a[hr] = *reinterpret_cast<const P8*>(cA + fa[tx] + hr * HW * RB);
-        // the next item's LDS image, one part behind each tap column's fragment reads: it is written while the MFMAs below run
-        if (more && tx < 3) commit(cur ^ 1, tx, false, plast);
+      for (int ty = 0; ty < TY; ++ty)
 #pragma unroll
-        for (int hr = 0; hr < 3 + TY; ++hr) {
+        for (int j = 0; j < NT; ++j) b[ty][j] = *reinterpret_cast<const P8*>(sB + fb + ((ty * TX + tx) * BN + j * 16) * RB);
 #pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const int ty = hr - mt;
-            if (ty >= 0 && ty < TY) {
-#pragma unroll
-              for (int j = 0; j < NT; ++j) acc[mt][j] = T::mfma(b[ty][j], a[hr], acc[mt][j]);
-            }
-          }
-        }
-      }
-      if (more) {
-        if (TX < 3) {
-#pragma unroll
-          for (int part = TX; part < 3; ++part) commit(cur ^ 1, part, false, plast);
-        }
-        if (item + 2 < nitems) {
-          pchunk = (pchunk + 1 == nchunks) ? 0 : pchunk + 1;
-          issue();  // the registers are free again: item + 2 is in flight during the next item
-        }
-      }
-      if (++chunk == nchunks) {
-        chunk = 0;
-        const float* const cE = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(sE) + cur * BUF);
-        // v = lrelu(acc * d + b) * (sqrt2 * s): leaky_relu(0.2) as max(v, 0.2 v) = med3(v, slope v, +inf) (one instruction; fmaxf
-        // costs a canonicalising v_max first), slope = 1 when the layer has no activation; the sqrt(2) rides in the style
-        v2f ed[NT][2], eb[NT][2], es[NT][2];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const float4 d = *reinterpret_cast<const float4*>(cE + j * 16 + q * 4);
-          const float4 bb = *reinterpret_cast<const float4*>(cE + BN + j * 16 + q * 4);
-          float4 sn = *reinterpret_cast<const float4*>(cE + 2 * BN + j * 16 + q * 4);
-          if (g.act) {
-            sn.x *= 1.4142135623730951f;
-            sn.y *= 1.4142135623730951f;
-            sn.z *= 1.4142135623730951f;
-            sn.w *= 1.4142135623730951f;
-          }
-          ed[j][0] = v2f{d.x, d.y};
-          ed[j][1] = v2f{d.z, d.w};
-          eb[j][0] = v2f{bb.x, bb.y};
-          eb[j][1] = v2f{bb.z, bb.w};
-          es[j][0] = v2f{sn.x, sn.y};
-          es[j][1] = v2f{sn.z, sn.w};
-        }
-        const float slope = g.act ? 0.2f : 1.0f;
-        unsigned char* yt = reinterpret_cast<unsigned char*>(g.Y) +
-                            ((((size_t)cf * g.OH + (size_t)cty * 16 * g.sy + g.py) * g.OW + (size_t)ctx * 16 * g.sx + g.px) * g.Cout + n0) * EB;
-        unsigned sm = 0u;
+      for (int hr = 0; hr < 3 + TY; ++hr) {
+        const P8 a = *reinterpret_cast<const P8*>(sA + fa[tx] + hr * HW * RB);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
+          const int ty = hr - mt;
+          if (ty >= 0 && ty < TY) {
 #pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            v2f v0 = v2f{acc[mt][j][0], acc[mt][j][1]} * ed[j][0] + eb[j][0];
-            v2f v1 = v2f{acc[mt][j][2], acc[mt][j][3]} * ed[j][1] + eb[j][1];
-            const v2f l0 = slope * v0, l1 = slope * v1;
-            v0 = v2f{__builtin_amdgcn_fmed3f(v0.x, l0.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v0.y, l0.y, __builtin_inff())} * es[j][0];
-            v1 = v2f{__builtin_amdgcn_fmed3f(v1.x, l1.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v1.y, l1.y, __builtin_inff())} * es[j][1];
+            for (int j = 0; j < NT; ++j) acc[mt][j] = T::mfma(b[ty][j], a, acc[mt][j]);  // D[channel][pixel], see dec_conv_kernel
+          }
+        }
+      }
+    }
+    DEC_PH(10);
+    if (++chunk == nchunks) {
+      chunk = 0;
+      DEC_PH_COUNT(15);
+      // v = lrelu(acc * d + b) * (sqrt2 * s): leaky_relu(0.2) as max(v, 0.2 v) = med3(v, slope v, +inf) (one instruction; fmaxf
+      // costs a canonicalising v_max first), slope = 1 when the layer has no activation; the sqrt(2) rides in the style
+      v2f ed[NT][2], eb[NT][2], es[NT][2];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const float4 d = *reinterpret_cast<const float4*>(sE + j * 16 + q * 4);
+        const float4 bb = *reinterpret_cast<const float4*>(sE + BN + j * 16 + q * 4);
+        float4 sn = *reinterpret_cast<const float4*>(sE + 2 * BN + j * 16 + q * 4);
+        if (g.act) {
+          sn.x *= 1.4142135623730951f;
+          sn.y *= 1.4142135623730951f;
+          sn.z *= 1.4142135623730951f;
+          sn.w *= 1.4142135623730951f;
+        }
+        ed[j][0] = v2f{d.x, d.y};
+        ed[j][1] = v2f{d.z, d.w};
+        eb[j][0] = v2f{bb.x, bb.y};
+        eb[j][1] = v2f{bb.z, bb.w};
+        es[j][0] = v2f{sn.x, sn.y};
+        es[j][1] = v2f{sn.z, sn.w};
+      }
+      const float slope = g.act ? 0.2f : 1.0f;
+      unsigned char* yt = reinterpret_cast<unsigned char*>(g.Y) +
+                          ((((size_t)cf * g.OH + (size_t)cty * 16 * g.sy + g.py) * g.OW + (size_t)ctx * 16 * g.sx + g.px) * g.Cout + n0) * EB;
+      unsigned sm = 0u;
+      f32x4 dh[FLOWM ? 4 : 1], dl[FLOWM ? 4 : 1];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        float vv[NT * 4];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          v2f v0 = v2f{acc[mt][j][0], acc[mt][j][1]} * ed[j][0] + eb[j][0];
+          v2f v1 = v2f{acc[mt][j][2], acc[mt][j][3]} * ed[j][1] + eb[j][1];
+          const v2f l0 = slope * v0, l1 = slope * v1;
+          v0 = v2f{__builtin_amdgcn_fmed3f(v0.x, l0.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v0.y, l0.y, __builtin_inff())} * es[j][0];
+          v1 = v2f{__builtin_amdgcn_fmed3f(v1.x, l1.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v1.y, l1.y, __builtin_inff())} * es[j][1];
+          if constexpr (FLOWM) {
+            vv[j * 4] = v0.x;
+            vv[j * 4 + 1] = v0.y;
+            vv[j * 4 + 2] = v1.x;
+            vv[j * 4 + 3] = v1.y;
+          } else {
             dec_store4<T>(reinterpret_cast<E*>(yt + mt * y_row + y_off + j * 16 * EB), v0.x, v0.y, v1.x, v1.y, sm);
           }
         }
-        dec_sat_flush<T>(g.sat, sm);
-        // the next tile to compute
-        if (++ctx == g.tiles_x) {
-          ctx = 0;
-          if (++cty == g.tiles_y) {
-            cty = 0;
-            ++cf;
-          }
-        }
-      }
-      __syncthreads();  // the one barrier of the item: buffer `cur` is free, buffer `cur ^ 1` is complete
-    }
-  } else {
-    for (int item = 0; item < nitems; ++item) {
-      __syncthreads();  // every wave is done reading the previous item's tiles
-      if (s_edge == 0u) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(sA + a_lds[i]) = ra[i];
-      } else {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) *reinterpret_cast<P8*>(sA + a_lds[i]) = ((s_hit >> (4 * i)) & 15u) ? T::zero8() : ra[i];
-      }
-#ifdef DEC_DIAG_WSTAGE1
-      if (first) {
-#else
-      if (nchunks > 1 || first) {
-#endif
-#pragma unroll
-        for (int i = 0; i < NB - 1; ++i) *reinterpret_cast<P8*>(sB + b_lds + i * 64 * RB) = rb[i];
-        *reinterpret_cast<P8*>(sB + b_lds_l) = rb[NB - 1];
-        first = false;
-      }
-      if (chunk == nchunks - 1 && tid < 3 * BN / 4) *reinterpret_cast<float4*>(sE + tid * 4) = re;
-      __syncthreads();
-      DEC_PH(9);
-      if (item + 1 < nitems) issue();  // in flight while this item computes
-      if constexpr (FLOWM) {
-        if (chunk == nchunks - 1) {  // ToFlow's weight fragments of the tile's frame: in registers when the epilogue starts
-          const P8* const wf = reinterpret_cast<const P8*>(g.wfrag) + (size_t)cf * (NPK * NHL * 64) + lane;
-#pragma unroll
-          for (int pk = 0; pk < NPK; ++pk)
-#pragma unroll
-            for (int hl = 0; hl < NHL; ++hl) wa[pk][hl] = wf[(pk * NHL + hl) * 64];
-        }
-      }
-      if (chunk == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int tx = 0; tx < TX; ++tx) {
-        P8 b[TY][NT];
-#pragma unroll
-        for (int ty = 0; ty < TY; ++ty)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-#ifdef DEC_DIAG_READS36  // timing-only build (WRONG frames): two thirds of the fragment reads, every MFMA - the bound on a 32-pixel-wide M tile
-            if (ty == TY - 1 && TY == 3) {
-              b[ty][j] = b[0][j];
-              continue;
-            }
-#endif
-            b[ty][j] = *reinterpret_cast<const P8*>(sB + fb + ((ty * TX + tx) * BN + j * 16) * RB);
-          }
-#ifdef DEC_DIAG_READS36
-        P8 a_seen[3 + TY];
-#endif
-#pragma unroll
-        for (int hr = 0; hr < 3 + TY; ++hr) {
-#ifdef DEC_DIAG_READS36
-          const P8 a = (hr >= 4 && TY == 3) ? a_seen[hr - 4] : *reinterpret_cast<const P8*>(sA + fa[tx] + hr * HW * RB);
-          a_seen[hr] = a;
-#else
-          const P8 a = *reinterpret_cast<const P8*>(sA + fa[tx] + hr * HW * RB);
-#endif
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const int ty = hr - mt;
-            if (ty >= 0 && ty < TY) {
-#pragma unroll
-              for (int j = 0; j < NT; ++j) {
-#ifdef DEC_DIAG_NOMFMA  // timing-only build (WRONG frames): one VALU operation that consumes both fragments instead of the MFMA
-                if constexpr (!T::is32) acc[mt][j][0] += __builtin_bit_cast(float, b[ty][j][0] ^ a[mt & 3]);
-#else
-                acc[mt][j] = T::mfma(b[ty][j], a, acc[mt][j]);  // D[channel][pixel], see dec_conv_kernel
-#endif
-              }
-            }
-          }
-        }
-      }
-      DEC_PH(10);
-      if (++chunk == nchunks) {
-        chunk = 0;
-        DEC_PH_COUNT(15);
-        // v = lrelu(acc * d + b) * (sqrt2 * s): leaky_relu(0.2) as max(v, 0.2 v) = med3(v, slope v, +inf) (one instruction; fmaxf
-        // costs a canonicalising v_max first), slope = 1 when the layer has no activation; the sqrt(2) rides in the style
-        v2f ed[NT][2], eb[NT][2], es[NT][2];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const float4 d = *reinterpret_cast<const float4*>(sE + j * 16 + q * 4);
-          const float4 bb = *reinterpret_cast<const float4*>(sE + BN + j * 16 + q * 4);
-          float4 sn = *reinterpret_cast<const float4*>(sE + 2 * BN + j * 16 + q * 4);
-          if (g.act) {
-            sn.x *= 1.4142135623730951f;
-            sn.y *= 1.4142135623730951f;
-            sn.z *= 1.4142135623730951f;
-            sn.w *= 1.4142135623730951f;
-          }
-          ed[j][0] = v2f{d.x, d.y};
-          ed[j][1] = v2f{d.z, d.w};
-          eb[j][0] = v2f{bb.x, bb.y};
-          eb[j][1] = v2f{bb.z, bb.w};
-          es[j][0] = v2f{sn.x, sn.y};
-          es[j][1] = v2f{sn.z, sn.w};
-        }
-        const float slope = g.act ? 0.2f : 1.0f;
-        unsigned char* yt = reinterpret_cast<unsigned char*>(g.Y) +
-                            ((((size_t)cf * g.OH + (size_t)cty * 16 * g.sy + g.py) * g.OW + (size_t)ctx * 16 * g.sx + g.px) * g.Cout + n0) * EB;
-        unsigned sm = 0u;
-        f32x4 dh[FLOWM ? 4 : 1], dl[FLOWM ? 4 : 1];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-          float vv[NT * 4];
-#pragma unroll
-          for (int j = 0; j < NT; ++j) {
-            v2f v0 = v2f{acc[mt][j][0], acc[mt][j][1]} * ed[j][0] + eb[j][0];
-            v2f v1 = v2f{acc[mt][j][2], acc[mt][j][3]} * ed[j][1] + eb[j][1];
-            const v2f l0 = slope * v0, l1 = slope * v1;
-            v0 = v2f{__builtin_amdgcn_fmed3f(v0.x, l0.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v0.y, l0.y, __builtin_inff())} * es[j][0];
-            v1 = v2f{__builtin_amdgcn_fmed3f(v1.x, l1.x, __builtin_inff()), __builtin_amdgcn_fmed3f(v1.y, l1.y, __builtin_inff())} * es[j][1];
-            if constexpr (FLOWM) {
-              vv[j * 4] = v0.x;
-              vv[j * 4 + 1] = v0.y;
-              vv[j * 4 + 2] = v1.x;
-              vv[j * 4 + 3] = v1.y;
-            } else {
-              dec_store4<T>(reinterpret_cast<E*>(yt + mt * y_row + y_off + j * 16 * EB), v0.x, v0.y, v1.x, v1.y, sm);
-            }
-          }
-          if constexpr (FLOWM) {
-            // K slot s of pack pk in lane group q <-> channel (2 pk + (s >> 2)) * 16 + q * 4 + (s & 3): the order dec_flowfrag_kernel packs
-            dh[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dl[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pk = 0; pk < NPK; ++pk) {
-              const float v8[8] = {vv[pk * 8], vv[pk * 8 + 1], vv[pk * 8 + 2], vv[pk * 8 + 3], vv[pk * 8 + 4], vv[pk * 8 + 5], vv[pk * 8 + 6], vv[pk * 8 + 7]};
-              const P8 bp = dec_pack8<T>(v8, sm);  // the rounding (and range check) the stored V had
-              dh[mt] = T::mfma(wa[pk][0], bp, dh[mt]);
-              if constexpr (NHL == 2) dl[mt] = T::mfma(wa[pk][1], bp, dl[mt]);
-            }
-          }
-        }
         if constexpr (FLOWM) {
-          // D[row 4 q' + i][pixel r16] = output i of m-tile mt's pixel, the same in every lane group q': lane (r16, q) keeps m-tile q
-          f32x4 oh = dh[0], ol = dl[0];
+          // K slot s of pack pk in lane group q <-> channel (2 pk + (s >> 2)) * 16 + q * 4 + (s & 3): the order dec_flowfrag_kernel packs
+          dh[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          dl[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int mt = 1; mt < 4; ++mt)
-            if (q == mt) {
-              oh = dh[mt];
-              ol = dl[mt];
-            }
-          float4 o4;
-          if constexpr (NHL == 2) o4 = float4{oh[0] + ol[0] * (1.f / 2048.f), oh[1] + ol[1] * (1.f / 2048.f), oh[2] + ol[2] * (1.f / 2048.f), 0.f};
-          else o4 = float4{oh[0], oh[1], oh[2], 0.f};
-          *reinterpret_cast<float4*>(g.oflow + ((((size_t)cf * g.OH + cty * 16 + w * 4 + q) * g.OW + ctx * 16 + r16) << 2)) = o4;
-        }
-        dec_sat_flush<T>(g.sat, sm);
-        DEC_PH(11);
-        // the next tile to compute
-        if (++ctx == g.tiles_x) {
-          ctx = 0;
-          if (++cty == g.tiles_y) {
-            cty = 0;
-            ++cf;
+          for (int pk = 0; pk < NPK; ++pk) {
+            const float v8[8] = {vv[pk * 8], vv[pk * 8 + 1], vv[pk * 8 + 2], vv[pk * 8 + 3], vv[pk * 8 + 4], vv[pk * 8 + 5], vv[pk * 8 + 6], vv[pk * 8 + 7]};
+            const P8 bp = dec_pack8<T>(v8, sm);  // the rounding (and range check) the stored V had
+            dh[mt] = T::mfma(wa[pk][0], bp, dh[mt]);
+            if constexpr (NHL == 2) dl[mt] = T::mfma(wa[pk][1], bp, dl[mt]);
           }
+        }
+      }
+      if constexpr (FLOWM) {
+        // D[row 4 q' + i][pixel r16] = output i of m-tile mt's pixel, the same in every lane group q': lane (r16, q) keeps m-tile q
+        f32x4 oh = dh[0], ol = dl[0];
+#pragma unroll
+        for (int mt = 1; mt < 4; ++mt)
+          if (q == mt) {
+            oh = dh[mt];
+            ol = dl[mt];
+          }
+        float4 o4;
+        if constexpr (NHL == 2) o4 = float4{oh[0] + ol[0] * (1.f / 2048.f), oh[1] + ol[1] * (1.f / 2048.f), oh[2] + ol[2] * (1.f / 2048.f), 0.f};
+        else o4 = float4{oh[0], oh[1], oh[2], 0.f};
+        *reinterpret_cast<float4*>(g.oflow + ((((size_t)cf * g.OH + cty * 16 + w * 4 + q) * g.OW + ctx * 16 + r16) << 2)) = o4;
+      }
+      dec_sat_flush<T>(g.sat, sm);
+      DEC_PH(11);
+      // the next tile to compute
+      if (++ctx == g.tiles_x) {
+        ctx = 0;
+        if (++cty == g.tiles_y) {
+          cty = 0;
+          ++cf;
         }
       }
     }

@@ -31,7 +31,6 @@ struct RideCopy {
   // Weight of a carrying launch at resolution R: the share of the pending copy it takes is proportional to it, so that every
   // share ends inside its launch (per 32-frame batch, ~us; other resolutions: equal shares).
   static double weight(const DecTune& tn, int R, int kind) {
-    if (tn.ride_equal) return 1.0;
     const int li = R == 64 ? 0 : R == 128 ? 1 : R == 256 ? 2 : R == 512 ? 3 : -1;
     return li < 0 ? 250.0 : tn.ride_w[li][kind];
   }
@@ -57,10 +56,6 @@ struct RideCopy {
     ct.dst = reinterpret_cast<u32x4*>(dst);
     ct.n16 = n;
     ct.nwg = tn.ride_wgs, ct.pace = tn.ride_pace;
-#ifdef DEC_STAMPS  // diagnostic build only: probes that give wrong frames
-    if (tn.ride_test == 1) ct.dst = const_cast<u32x4*>(ct.src);  // device -> device instead of device -> host
-    if (tn.ride_test == 2) ct.n16 = 1;                            // copy workgroups with nothing to do
-#endif
     src += n * 16, dst += n * 16, dst_host += n * 16;
     left16 -= n;
     return ct;
@@ -95,15 +90,11 @@ struct Rows { const float* p = nullptr; int ld = 0; };  // a float table with on
 // Every instantiation of the two level kernels with more than one choice to make: f(kernel, <what selects it>).
 // raise_lds_limits and the launchers both walk these lists, so an instantiation is added by one line here.
 template <class T, class F>
-void for_each_conv16(F&& f) {  // f(kernel, output channels per workgroup, double-buffered LDS, ToFlow in the epilogue)
-  f(dec_conv16_kernel<T, 4, 3, 3>, 64, false, false);
-  f(dec_conv16_kernel<T, 2, 3, 3>, 32, false, false);
-  f(dec_conv16_kernel<T, 4, 3, 3, 0, 1>, 64, false, true);
-  f(dec_conv16_kernel<T, 2, 3, 3, 0, 1>, 32, false, true);
-  if constexpr (!T::is32) {  // FLOAT_DEC_CONV_DB: two buffer sets, up to 115 KB
-    f(dec_conv16_kernel<T, 4, 3, 3, 1>, 64, true, false);
-    f(dec_conv16_kernel<T, 2, 3, 3, 1>, 32, true, false);
-  }
+void for_each_conv16(F&& f) {  // f(kernel, output channels per workgroup, ToFlow in the epilogue)
+  f(dec_conv16_kernel<T, 4, 3, 3>, 64, false);
+  f(dec_conv16_kernel<T, 2, 3, 3>, 32, false);
+  f(dec_conv16_kernel<T, 4, 3, 3, 1>, 64, true);
+  f(dec_conv16_kernel<T, 2, 3, 3, 1>, 32, true);
 }
 template <class T, class F>
 void for_each_flowlast(F&& f) {  // f(kernel, the final_mode it is for: kOutNone = every mode but the listed ones); raise_lds_limits walks it
@@ -129,7 +120,7 @@ int raise_lds_limits(const DecTune& tn) {
   auto raise = [](auto kern, int bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   };
-  for_each_conv16<T>([&](auto kern, int, bool db, bool) { raise(kern, db ? 128 * 1024 : lim); });
+  for_each_conv16<T>([&](auto kern, int, bool) { raise(kern, lim); });
   for_each_flowlast<T>([&](auto kern, DecOut) { raise(kern, lim); });
   raise(dec_conv_kernel<T, 4>, lim);
   raise(dec_conv_kernel<T, 2>, lim);
@@ -252,12 +243,11 @@ int launch_conv(const DecLaunch& cx, const ConvGeom& c, const Styled& s, const v
       g.ncb = (unsigned)(s.cout / bn);
       grid = dim3(g.ngroups * g.ncb + g.ct.nwg, 1);
     }
-    const bool db = !oflow && !T::is32 && ((bn == 64 && (tn.conv_db & 1)) || (bn == 32 && (tn.conv_db & 2)));
     FH_REQUIRE(!oflow || s.cout == bn, "ToFlow epilogue needs the layer's %d output channels in one block of %d", s.cout, bn);
-    for_each_conv16<T>([&](auto k, int kbn, bool kdb, bool kflow) {
-      if (kbn == bn && kdb == db && kflow == (oflow != nullptr)) kern = k;
+    for_each_conv16<T>([&](auto k, int kbn, bool kflow) {
+      if (kbn == bn && kflow == (oflow != nullptr)) kern = k;
     });
-    smem = db ? 2 * smem : cx.smem(smem);
+    smem = cx.smem(smem);
   } else {
     FH_REQUIRE(!oflow, "ToFlow epilogue: only on the 16x16-tile 3x3 kernel (%d x %d)", c.Ho, c.Wo);
     smem = (size_t)npix * RB + (size_t)c.ntaps * bn * RB;

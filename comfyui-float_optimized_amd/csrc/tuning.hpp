@@ -130,7 +130,6 @@ struct DecTune {
   unsigned ride_wgs = 16;
   int ride_min_res = 64;
   unsigned ride_pace = 3;
-  bool ride_equal = false;  // FLOAT_DEC_RIDE_EQUAL (set at all): every carrying launch takes an equal share
   // FLOAT_DEC_RIDE_W="12 numbers" in (0, 1e6): weight of a carrying launch, rows 64 / 128 / 256 / 512 px x (up-conv, conv2, flow) -
   // launch durations (tools/probes/trace_sequence.py on the round-3 kernels: {203,155,61},{178,175,118},{242,226,215},{318,256,336})
   // shifted toward the flow launches, which absorb a share without getting longer while the 512-px convs are stretched by theirs
@@ -139,13 +138,6 @@ struct DecTune {
   // was): decode + hand-over per 250 frames 25.1-25.3 ms with the row below against 26.4-26.9 with round 5's {..,{290,225,370}},
   // 25.4 / 25.7 / 25.3 / 25.6 for four neighbours, 26.8 with equal shares (tools/probes/dec_host2.py)
   double ride_w[4][3] = {{170, 140, 50}, {170, 155, 100}, {220, 200, 180}, {300, 250, 120}};
-  // FLOAT_DEC_RIDE_TAIL=<frames>: cut the last batch of a call in two so that only that many frames' copy stays exposed.  Measured
-  // and off: 30.1 ms per 250 frames without, 31.0-31.8 with a tail of 4..16 frames (the smaller launches lose more than the shorter
-  // copy gains)
-  int ride_tail = 0;
-#ifdef DEC_STAMPS
-  int ride_test = 0;  // FLOAT_DEC_RIDE_TEST, diagnostic build only, probes that give wrong frames: 1 = device -> device instead of device -> host, 2 = copy workgroups with nothing to do
-#endif
   bool cb_order = true;    // FLOAT_DEC_CB_ORDER=0: output-channel blocks as grid.y (the round-1 order; A/B switch of dec_group_cb)
   // Output channels per workgroup of the 3x3 conv: FLOAT_DEC_CONV_BN = 32 | 64 in the 16x16-tile kernel (64 where the layer has them:
   // each A fragment feeds twice the MFMAs - 22.75 vs 23.10 ms per 250 frames since the kernel's address arithmetic went; before that
@@ -153,7 +145,6 @@ struct DecTune {
   // kernel (the A/B switches)
   int conv_bn = 64, conv_bn_lo = 32;
   int tpw = 0;             // FLOAT_DEC_TPW, 1..4096: tiles per workgroup of the 16x16-tile conv (0 = by tile count: 4 / 2 / 1), tuning aid
-  int conv_db = 0;         // FLOAT_DEC_CONV_DB bit mask: 1 = double-buffered LDS for the 64-channel tiles, 2 = for the 32-channel tiles (A/B switch)
   bool no_zfuse = false;   // FLOAT_DEC_NO_ZFUSE (set at all): the transposed conv class by class through the generic kernel instead of dec_zconv4_kernel
   int zblur_min = 64;      // FLOAT_DEC_ZBLUR_MIN, 16..4096: transposed conv + blur in one launch from this resolution up
   int flow_pix = 0;        // FLOAT_DEC_FLOW_PIX = 1 | 2 | 4: pixels per lane group and iteration of dec_flow_kernel (0 = by channel count), tuning aid
@@ -162,7 +153,6 @@ struct DecTune {
   bool yuv_fused = true;   // FLOAT_DEC_YUV_FUSED=0: I420 frames through u8 RGB + dec_rgb8_to_i420_kernel on the product path too (A/B switch, tests)
   bool write_pyr = false;  // FLOAT_DEC_WRITE_PYR (set at all): the last level stores its flow / rgb pyramids too
   bool copy_memcpy = false;  // FLOAT_DEC_COPY=memcpy: same-stream hand-over by hipMemcpyAsync instead of ride-along copy workgroups
-  bool short_first = true;   // FLOAT_DEC_SHORT_FIRST=0: the short piece of a ragged clip last instead of first
   bool style_norm = true;    // FLOAT_DEC_STYLE_NORM=0: styles are not divided by their max |s| before the demodulation
 
   static DecTune from_env() {
@@ -171,20 +161,14 @@ struct DecTune {
     t.ride_wgs = (unsigned)env_int("FLOAT_DEC_RIDE_WGS", 16, 0, 64) / 8 * 8;
     t.ride_min_res = env_int("FLOAT_DEC_RIDE_MIN_RES", 64, 64, 512);
     t.ride_pace = (unsigned)env_int("FLOAT_DEC_RIDE_PACE", 3, 0, 64);
-    t.ride_equal = env_set("FLOAT_DEC_RIDE_EQUAL");
     double w[12];
     if (env_list("FLOAT_DEC_RIDE_W", w, 12, ' ') == 12)
       for (int i = 0; i < 12; ++i)
         if (w[i] > 0.0 && w[i] < 1e6) t.ride_w[i / 3][i % 3] = w[i];
-    t.ride_tail = env_atoi("FLOAT_DEC_RIDE_TAIL", 0);
-#ifdef DEC_STAMPS
-    t.ride_test = env_int("FLOAT_DEC_RIDE_TEST", 0, 0, 2);
-#endif
     t.cb_order = env_atoi("FLOAT_DEC_CB_ORDER", 1) != 0;
     t.conv_bn = env_int("FLOAT_DEC_CONV_BN", 64, 32, 64);
     t.conv_bn_lo = env_int("FLOAT_DEC_CONV_BN_LO", 32, 32, 64);
     t.tpw = env_int("FLOAT_DEC_TPW", 0, 0, 4096);
-    t.conv_db = env_int("FLOAT_DEC_CONV_DB", 0, 0, 3);
     t.no_zfuse = env_set("FLOAT_DEC_NO_ZFUSE");
     t.zblur_min = env_int("FLOAT_DEC_ZBLUR_MIN", 64, 16, 4096);
     t.flow_pix = env_int("FLOAT_DEC_FLOW_PIX", 0, 0, 4);
@@ -194,7 +178,6 @@ struct DecTune {
     t.write_pyr = env_set("FLOAT_DEC_WRITE_PYR");
     const char* copy = getenv("FLOAT_DEC_COPY");
     t.copy_memcpy = copy && !strcmp(copy, "memcpy");
-    t.short_first = env_int("FLOAT_DEC_SHORT_FIRST", 1, 0, 1) != 0;
     t.style_norm = env_int("FLOAT_DEC_STYLE_NORM", 1, 0, 1) != 0;
     return t;
   }

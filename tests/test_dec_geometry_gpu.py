@@ -7,7 +7,7 @@ A. 128 / 256 px against the fp64 oracle (oracle/float_oracle.py, itself held to 
    frames max-abs <= 1e-4, raw <= 2e-4 (tests/test_dec_fp32_gpu.py); fp16 PSNR >= 52 dB, mean abs <= 0.5/255
    (LIMITS of tests/test_dec_gpu.py).  That the fp32 limits mean something on these inputs is pinned without a GPU by
    tests/test_oracle_golden.py::test_dec_geometry_inputs_are_well_conditioned (fp32 oracle within a quarter of them).
-B. The 64-channel last level of a 256-px decoder: ToFlow in conv2's epilogue (dec_conv16_kernel<T, 4, 3, 3, 0, 1> +
+B. The 64-channel last level of a 256-px decoder: ToFlow in conv2's epilogue (dec_conv16_kernel<T, 4, 3, 3, 1> +
    dec_flowfrag_kernel + dec_flowlast_kernel) is taken by both element types (float_dec_create: `flow_epi &&
    conv_takes_flow_epi(..)`), so part A at 256 px holds it to the oracle; the other side of the switch (FLOAT_DEC_FLOW_EPI=0,
    dec_flow_kernel<.., Last = true> on the stored V, read once per process: child processes) is held here, and so is the

@@ -129,6 +129,23 @@ def test_decode_into_host_equals_decode(side_stream):
         dec.decode_into_host(s_r, r_d, torch.empty(10, 64, 64, 3))
 
 
+def test_decode_into_host_ragged_equals_single_batches():
+    """A clip that is no multiple of max_frames runs its short piece first (6 frames at max_frames = 4: pieces 2 + 4, the
+    full batch carries the short one's copy).  The frames in pinned host memory are bitwise those of calls that decode one
+    batch each."""
+    sd = W.synth_decoder_state(64, seed=4)
+    feats = W.synth_feats(64, seed=4)
+    gen = torch.Generator().manual_seed(2)
+    s_r, r_d = torch.randn(1, 512, generator=gen), torch.randn(1, 6, 512, generator=gen) * 0.5
+    dec = pkg.decoder.SynthesisHIP(sd, 64, 512, "cuda:0", dtype="fp16", max_frames=4)
+    want = torch.cat([dec.decode_latent_into_processed_images(s_r, r_d[:, i:i + 4].contiguous(), feats).cpu() for i in (0, 4)])
+    assert want.shape == (6, 64, 64, 3)
+    host = torch.full((6, 64, 64, 3), -1.0).pin_memory()
+    dec.decode_into_host(s_r, r_d, host)
+    torch.cuda.current_stream().synchronize()
+    assert torch.equal(host, want)
+
+
 def test_decode_into_pageable_host():
     """a destination that is NOT pinned must not be written by the copy workgroups (a kernel storing to an
     unmapped host address is a GPU fault).  float_dec_frames_host asks hipPointerGetAttributes and sends pageable memory through

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix per basic block of one kernel in a `hipcc -S --cuda-device-only` listing.
-    python tools/isa_mix.py /tmp/dec.s _Z17dec_conv16_kernelI4FP16Li2ELi3ELi3EEv8ConvArgs [min instructions per block]"""
+    python tools/isa_mix.py /tmp/dec.s _Z17dec_conv16_kernelI4FP16Li2ELi3ELi3ELi0EEv8ConvArgs [min instructions per block]"""
 import collections
 import re
 import sys
