@@ -239,13 +239,16 @@ __global__ __launch_bounds__(256) void aud_interp_ln_kernel(const typename T::el
     for (int e = 0; e < 4; ++e) v[i][e] = l0 * T::to_float(a[e]) + l1 * T::to_float(b[e]);
     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
   }
-  const float mu = wave_sum(s) * (1.f / C);
+  // The __shfl_xor butterfly on purpose (here, in aud_ln_kernel and in aud_rowln_gelu_kernel): around wave_sum's DPP form hipcc
+  // no longer pairs the row's subtractions into packed operations and contracts `v - sum * (1 / C)` into one fma, which rounds
+  // once where this rounds twice - with C = 768 (1 / C is no power of two) that moves bits of every frame.
+  const float mu = wave_sum_shfl(s) * (1.f / C);
   float s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) s2 += (v[i][e] - mu) * (v[i][e] - mu);
-  const float rstd = rsqrtf(wave_sum(s2) * (1.f / C) + eps);
+  const float rstd = rsqrtf(wave_sum_shfl(s2) * (1.f / C) + eps);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;
@@ -300,14 +303,14 @@ __global__ __launch_bounds__(256) void aud_ln_kernel(AudLnArgs g) {
     }
     s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
-  const float mu = wave_sum(s) * (1.f / D);
+  const float mu = wave_sum_shfl(s) * (1.f / D);
   float s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const float d0 = v[i].x - mu, d1 = v[i].y - mu, d2 = v[i].z - mu, d3 = v[i].w - mu;
     s2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
   }
-  const float rstd = rsqrtf(wave_sum(s2) * (1.f / D) + g.eps);
+  const float rstd = rsqrtf(wave_sum_shfl(s2) * (1.f / D) + g.eps);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;
@@ -638,13 +641,13 @@ __global__ __launch_bounds__(256) void aud_rowln_gelu_kernel(typename T::elem* _
     for (int e = 0; e < 4; ++e) v[i][e] = T::to_float(a[e]);
     s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
   }
-  const float mu = wave_sum(s) * (1.f / C);
+  const float mu = wave_sum_shfl(s) * (1.f / C);
   float s2 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) s2 += (v[i][e] - mu) * (v[i][e] - mu);
-  const float rstd = rsqrtf(wave_sum(s2) * (1.f / C) + eps);
+  const float rstd = rsqrtf(wave_sum_shfl(s2) * (1.f / C) + eps);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 256 + lane * 4;

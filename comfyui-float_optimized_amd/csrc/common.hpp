@@ -314,9 +314,79 @@ __device__ __forceinline__ float fh_lrelu_s2(float x) {  // leaky_relu(x, 0.2) *
   return (x > 0.f ? x : 0.2f * x) * 1.4142135623730951f;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---------------------------------------------------------------- cross-lane reductions without LDS
+// __shfl_xor compiles to ds_bpermute_b32: an LDS-pipe round trip and an s_waitcnt lgkmcnt(0) per butterfly step.  The forms
+// below deliver the same operands to the same additions through the VALU's own lane crossbars (DPP, v_permlane*_swap), so
+// every lane ends with the bits of the __shfl_xor butterfly (fp32 add / max commute).  They assume what the butterfly's users
+// guarantee anyway: all lanes of the wave (of the group, for group_sum) are active.  The *_shfl forms are kept for the probe
+// that compares the two (float_fmt_debug request 5).
+constexpr int kDppQuadXor1 = 0xb1, kDppQuadXor2 = 0x4e;  // quad_perm:[1,0,3,2], quad_perm:[2,3,0,1]
+constexpr int kDppRowRor = 0x120;                         // + n: row_ror:n, lane i of a 16-lane row reads lane (i - n) & 15
+constexpr int kDppRowHalfMirror = 0x141;                  // lane i reads lane 7 - i of its 8-lane half row
+template <int CTRL>
+__device__ __forceinline__ float dpp_read(float v) {  // the compiler folds the move into the add / max that uses it
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// v of lanes 0..31 (row pairs 0 | 2 for the 16-lane form) in .x and of the partner lanes in .y, in every lane of the pair
+__device__ __forceinline__ float2 swap32(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return make_float2(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+__device__ __forceinline__ float2 swap16(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return make_float2(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+}
+
+struct XlAdd {
+  static __device__ __forceinline__ float op(float a, float b) { return a + b; }
+};
+struct XlMax {
+  static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
+};
+// Descending butterfly 32, 16, 8, 4, 2, 1 over the wave.  32 and 16 need the true partner lane: one swap each, whose two
+// results are own and partner value in either order.  From step 8 on the value in lane i depends on i mod 2n only, and a
+// rotation of the 16-lane row by n lands in the class of i ^ n: one DPP add per step.
+template <class OP>
+__device__ __forceinline__ float wave_reduce(float v) {
+  float2 p = swap32(v);
+  v = OP::op(p.x, p.y);
+  p = swap16(v);
+  v = OP::op(p.x, p.y);
+  v = OP::op(v, dpp_read<kDppRowRor + 8>(v));
+  v = OP::op(v, dpp_read<kDppRowRor + 4>(v));
+  v = OP::op(v, dpp_read<kDppRowRor + 2>(v));
+  v = OP::op(v, dpp_read<kDppRowRor + 1>(v));
+  return v;
+}
+template <class OP>
+__device__ __forceinline__ float wave_reduce_shfl(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v = OP::op(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return wave_reduce<XlAdd>(v); }
+__device__ __forceinline__ float wave_max(float v) { return wave_reduce<XlMax>(v); }
+__device__ __forceinline__ float wave_sum_shfl(float v) { return wave_reduce_shfl<XlAdd>(v); }
+__device__ __forceinline__ float wave_max_shfl(float v) { return wave_reduce_shfl<XlMax>(v); }
+
+// Ascending butterfly 1, 2, 4, (8) over aligned groups of G = 4 | 8 | 16 lanes, all inside one 16-lane DPP row.  Steps 1 and 2
+// are exact partners within the quad; after them a quad holds one value, so step 4 may read any lane of the partner quad
+// (7 - i of the half row) and step 8 any lane of the other half row.  No step reads outside the lane's own group.
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+  static_assert(G == 1 || G == 2 || G == 4 || G == 8 || G == 16, "group_sum: a group is at most one DPP row");
+  if constexpr (G > 1) v += dpp_read<kDppQuadXor1>(v);
+  if constexpr (G > 2) v += dpp_read<kDppQuadXor2>(v);
+  if constexpr (G > 4) v += dpp_read<kDppRowHalfMirror>(v);
+  if constexpr (G > 8) v += dpp_read<kDppRowRor + 8>(v);
+  return v;
+}
+template <int G>
+__device__ __forceinline__ float group_sum_shfl(float v) {
+#pragma unroll
+  for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d, 64);
   return v;
 }
 

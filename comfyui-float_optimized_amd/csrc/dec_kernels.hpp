@@ -183,8 +183,7 @@ static __global__ __launch_bounds__(256) void dec_style_norm_kernel(DemodArgs g)
   __shared__ float red[4];
   float m = 0.f;
   for (int i = threadIdx.x; i < L.cin; i += 256) m = fmaxf(m, fabsf(s[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));

@@ -749,6 +749,12 @@ static int debug_impl(float_fmt* h, int what, const float* in, float* out, hipSt
     FH_CHECK_HIP(hipStreamSynchronize(s));
     return FLOAT_OK;
   }
+  if (what == 5) {  // in (64, 64) -> out (64, 5, 2, 64): fmt_xlane_probe_kernel
+    FH_REQUIRE(in != nullptr, "float_fmt_debug: request %d needs an input", what);
+    hipLaunchKernelGGL(fmt_xlane_probe_kernel, dim3(kXlaneProbeVecs), dim3(64), 0, s, in, out);
+    FH_CHECK_HIP(hipGetLastError());
+    return FLOAT_OK;
+  }
   FH_REQUIRE(what == 1 && in != nullptr, "float_fmt_debug: unknown request %d (or null input)", what);
   const int n = ntok * 3 * D;
   hipLaunchKernelGGL((fmt_dbg_to16_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, h->qkv16, in, n);

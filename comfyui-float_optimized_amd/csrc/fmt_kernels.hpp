@@ -900,16 +900,16 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
 #pragma unroll
   for (int i = 0; i < PD; ++i) o[i] = 0.f;
   float m = -INFINITY, l = 0.f;
-  auto fold = [&](const P8* k, const P8* v, bool valid) {
+  auto score = [&](const P8* k) {  // depends on q and k only
     float dot = 0.f;
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) dot += qf[u * 8 + j] * T::get(k[u], j);
     }
-#pragma unroll
-    for (int d = 1; d < LPQ; d <<= 1) dot += __shfl_xor(dot, d, 64);
-    if (!valid) return;
+    return group_sum<LPQ>(dot);  // the query's LPQ lanes are one aligned group of a DPP row and leave together (above)
+  };
+  auto fold = [&](float dot, const P8* v) {
     const float mn = fmaxf(m, dot);
     const float alpha = __expf(m - mn), p = __expf(dot - mn);
     l = l * alpha + p;
@@ -934,11 +934,12 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
     }
     touch();
     scale_q();
+    // (the five scores formed in front of the first fold, so that their reductions overlap: measured, not faster - DESIGN.md §7)
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
       const int kj = qi + t - 2;
-      const bool valid = kj >= 0 && kj < ntok && (t - 2 >= -window) && (t - 2 <= window);
-      fold(kk[t], vv[t], valid);
+      const float dot = score(kk[t]);
+      if (kj >= 0 && kj < ntok && (t - 2 >= -window) && (t - 2 <= window)) fold(dot, vv[t]);
     }
   } else {
     touch();
@@ -952,7 +953,8 @@ __device__ __forceinline__ void fmt_attn_body(const u16* __restrict__ qkv, int l
         k[u] = T::load8(kp + u * 8);
         v[u] = T::load8(kp + D + u * 8);
       }
-      fold(k, v, kj >= 0 && kj < ntok);
+      const float dot = score(k);
+      if (kj >= 0 && kj < ntok) fold(dot, v);
     }
   }
   const float inv = 1.f / l;
@@ -978,6 +980,20 @@ __global__ __launch_bounds__(512) void fmt_attn_kernel(const u16* __restrict__ q
   // be loads from the kernarg segment), so the q / k / v loads are issued without a scalar-memory round trip in front of them
   fmt_attn_body<T, LPQ, TOUCH, WT>(qkv, ld, out, ntok, M, D, window, FmtDiv{ntok_mul, ntok_sh}, pf, sat, blockIdx.x, blockIdx.y,
                                    nthr, blockIdx.x + (unsigned)heads * blockIdx.y, (unsigned)(heads * nrun));
+}
+
+// Test hook (float_fmt_debug request 5): the cross-lane reductions of common.hpp on caller data, one wave per 64-lane vector.
+// out[vec][k][form][lane], k = wave sum, wave max, 16-, 8-, 4-lane group sum; form 0 = DPP / lane swap, 1 = __shfl_xor.
+constexpr int kXlaneProbeVecs = 64, kXlaneProbeSums = 5;
+__global__ __launch_bounds__(64) void fmt_xlane_probe_kernel(const float* __restrict__ in, float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const float v = in[blockIdx.x * 64 + lane];
+  float* o = out + (size_t)blockIdx.x * kXlaneProbeSums * 2 * 64 + lane;
+  o[0 * 64] = wave_sum(v), o[1 * 64] = wave_sum_shfl(v);
+  o[2 * 64] = wave_max(v), o[3 * 64] = wave_max_shfl(v);
+  o[4 * 64] = group_sum<16>(v), o[5 * 64] = group_sum_shfl<16>(v);
+  o[6 * 64] = group_sum<8>(v), o[7 * 64] = group_sum_shfl<8>(v);
+  o[8 * 64] = group_sum<4>(v), o[9 * 64] = group_sum_shfl<4>(v);
 }
 
 // Condition rows for c_embedder: [wr | wa | we | 0-pad] per (cfg row b, token i) with the CFG nulling

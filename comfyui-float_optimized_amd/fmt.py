@@ -80,6 +80,23 @@ class FlowMatchingTransformerHIP:
                                                       native.stream_ptr(self.device)))
         return out
 
+    @torch.no_grad()
+    def xlane_probe(self, v):
+        """v (n, 64), one value per lane of a wave -> (n, 5, 2, 64): per lane the 64-lane sum, the 64-lane max and the 16-,
+        8- and 4-lane group sums, [:, :, 0] as the kernels form them (DPP / lane swaps), [:, :, 1] as the __shfl_xor butterfly."""
+        v = self._f(v)
+        if v.dim() != 2 or v.shape[1] != 64:
+            raise ValueError("v must be (n,64)")
+        n, per = v.shape[0], native.XLANE_PROBE_VECS
+        buf = torch.zeros(-(-n // per) * per, 64, device=self.device, dtype=torch.float32)
+        buf[:n] = v
+        out = torch.empty(buf.shape[0], 5, 2, 64, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            for i in range(0, buf.shape[0], per):
+                native.check(native.lib().float_fmt_debug(self._h, 5, native.dev_ptr(buf[i:i + per]), native.dev_ptr(out[i:i + per]),
+                                                          native.stream_ptr(self.device)))
+        return out[:n]
+
     def saturation(self, reset=False):
         """Threads with a clamped (+-65504) or non-finite 16-bit activation store since create / the last reset
         (float_fmt_saturation): 0 unless the checkpoint leaves fp16's range - then the result is not the reference's within the

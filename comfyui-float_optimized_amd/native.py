@@ -19,6 +19,7 @@ DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP1
           "fp32": FLOAT_DT_FP32, "float32": FLOAT_DT_FP32}  # fp32: the verification mode of the FMT and decoder operators
 DTYPE_NAMES = {FLOAT_DT_BF16: "bf16", FLOAT_DT_FP16: "fp16", FLOAT_DT_FP32: "fp32"}
 DEC_SAT_SITES = 40
+XLANE_PROBE_VECS = 64  # kXlaneProbeVecs: 64-lane vectors per float_fmt_debug request 5
 ABI_VERSION = 6
 
 

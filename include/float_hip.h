@@ -210,6 +210,10 @@ int float_fmt_sample_begin_range(float_fmt_t* h, const float* wr, const float* w
  *             its 8 waves (4 in the fp32 mode; the 64-column tile exists for fp16 / bf16 only): in = [A (48, 1024) | W (N, 1024)],
  *             out (48, N) = A W^T in fp32 with no bias.  Wave w multiplies columns w * 1024 / waves .. of A and W, so operands
  *             that are zero outside one wave's columns show that wave's partial sum alone.  Synchronises the stream.
+ *   what = 5: the kernels' cross-lane reductions on caller data: in (64, 64) = 64 vectors of one value per lane of a wave,
+ *             out (64, 5, 2, 64) = per vector and lane the 64-lane sum, the 64-lane max and the sums over the lane's aligned
+ *             group of 16, 8 and 4 lanes, each in the form the kernels use (DPP / lane swaps, index 0) and as the
+ *             __shfl_xor butterfly it replaces (index 1): the two must agree bit for bit.
  * in / out are fp32 device pointers. */
 int float_fmt_debug(float_fmt_t* h, int32_t what, const float* in, float* out, void* stream);
 
