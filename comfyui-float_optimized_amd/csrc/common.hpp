@@ -314,6 +314,70 @@ __device__ __forceinline__ float fh_lrelu_s2(float x) {  // leaky_relu(x, 0.2) *
   return (x > 0.f ? x : 0.2f * x) * 1.4142135623730951f;
 }
 
+// ---------------------------------------------------------------- 8-bit RGB -> 8-bit YUV (the I420 outputs)
+// plane = ((cr r + cg g + cb b + rnd) >> 8) + off in int32, >> the arithmetic shift (floor), for a sample (Y) or the rounded
+// mean of a 2 x 2 block (U, V): host_models.YUV_MATRICES, include/float_hip.h.  The id is a flag word: bit 1 = BT.709, bit 2 =
+// full range.  Rows Y, U, V of {cr, cg, cb, rnd, off}:
+constexpr int kFhYuvRows[4][3][5] = {
+    {{66, 129, 25, 128, 16}, {-38, -74, 112, 128, 128}, {112, -94, -18, 128, 128}},   // 0: BT.601 limited
+    {{47, 157, 16, 128, 16}, {-26, -86, 112, 128, 128}, {112, -102, -10, 128, 128}},  // 2: BT.709 limited
+    {{77, 150, 29, 128, 0}, {-43, -85, 128, 127, 128}, {128, -107, -21, 127, 128}},   // 4: BT.601 full
+    {{54, 183, 19, 128, 0}, {-29, -99, 128, 127, 128}, {128, -116, -12, 127, 128}},   // 6: BT.709 full
+};
+// What a kernel gets, by value among its arguments (uniform: the fields are unpacked on the scalar unit): per plane one word of
+// the three coefficients at 10 signed bits each (cr in bits 0..9, cg 10..19, cb 20..29) and one of rnd + 256 off - off is a
+// whole number of 256ths, so adding it under the shift gives the same floor.  Six dwords; per sample three multiply-adds and
+// a shift.
+struct FhYuv {
+  int32_t coef[3];  // Y, U, V
+  int32_t bias[3];
+};
+constexpr int fh_yuv_field(int32_t w, int i) { return (int)((int32_t)((uint32_t)w << (22 - 10 * i)) >> 22); }
+constexpr FhYuv fh_yuv_pack(const int (&m)[3][5]) {
+  FhYuv t{};
+  for (int p = 0; p < 3; ++p) {
+    t.coef[p] = (int32_t)(((uint32_t)m[p][0] & 1023u) | (((uint32_t)m[p][1] & 1023u) << 10) | (((uint32_t)m[p][2] & 1023u) << 20));
+    t.bias[p] = m[p][3] + 256 * m[p][4];
+  }
+  return t;
+}
+// The table is checked where it is compiled: the packed words give the rows back; Y rows sum to 220 (limited) or 256 (full),
+// chroma rows to 0 (grey is exactly U = V = 128); and the extremes over r, g, b in 0 ... 255 are [16, 235] / [16, 240] (limited)
+// and [0, 255] (full) - a byte without a clamp.
+constexpr bool fh_yuv_table_ok() {
+  for (int k = 0; k < 4; ++k) {
+    const FhYuv t = fh_yuv_pack(kFhYuvRows[k]);
+    const bool full = k >= 2;
+    for (int p = 0; p < 3; ++p) {
+      const int* r = kFhYuvRows[k][p];
+      int sum = 0, lo = r[3], hi = r[3];
+      for (int i = 0; i < 3; ++i) {
+        if (fh_yuv_field(t.coef[p], i) != r[i]) return false;
+        sum += r[i];
+        (r[i] < 0 ? lo : hi) += 255 * r[i];
+      }
+      if ((t.bias[p] & 255) != r[3] || (t.bias[p] >> 8) != r[4]) return false;
+      if (sum != (p ? 0 : full ? 256 : 220)) return false;
+      lo = (lo >> 8) + r[4], hi = (hi >> 8) + r[4];
+      if (lo != (full ? 0 : 16) || hi != (full ? 255 : p ? 240 : 235)) return false;
+    }
+  }
+  return true;
+}
+static_assert(fh_yuv_table_ok(), "kFhYuvRows: packing, row sums or output ranges");
+// id -> table; false for anything but 0 / 2 / 4 / 6
+inline bool fh_yuv_of(int32_t matrix, FhYuv* t) {
+  if (matrix & ~6) return false;
+  *t = fh_yuv_pack(kFhYuvRows[matrix >> 1]);
+  return true;
+}
+#define FH_YUV_IDS "0 = BT.601 limited, 2 = BT.709 limited, 4 = BT.601 full, 6 = BT.709 full range"
+// plane p (0 Y, 1 U, 2 V) of the sample or block mean (r, g, b), each in 0 ... 255
+__device__ __forceinline__ unsigned fh_yuv_plane(const FhYuv& t, int p, int r, int g, int b) {
+  const int w = t.coef[p];
+  return (unsigned)((((w << 22) >> 22) * r + ((w << 12) >> 22) * g + ((w << 2) >> 22) * b + t.bias[p]) >> 8);
+}
+
 // ---------------------------------------------------------------- cross-lane reductions without LDS
 // __shfl_xor compiles to ds_bpermute_b32: an LDS-pipe round trip and an s_waitcnt lgkmcnt(0) per butterfly step.  The forms
 // below deliver the same operands to the same additions through the VALU's own lane crossbars (DPP, v_permlane*_swap), so

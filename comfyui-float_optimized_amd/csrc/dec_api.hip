@@ -38,6 +38,7 @@ struct float_dec {
   // 8-bit RGB, which dec_rgb8_to_i420_kernel turns into the caller's planes behind the level
   bool i420_fused = false;
   unsigned char* rgb8 = nullptr;
+  FhYuv yuv = fh_yuv_pack(kFhYuvRows[0]);  // the colour matrix of the I420 call that is running (float_dec_frames[_host]_i420 set it)
   unsigned long long* sat = nullptr;  // [kDecSatSites] saturation counters (dec_kernels.hpp), device
   DecTune tune;  // the environment's switches as float_dec_create found them (tuning.hpp)
   float *loFlow[2] = {nullptr, nullptr}, *loRgb[2] = {nullptr, nullptr};
@@ -195,6 +196,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
   FH_REQUIRE(!via_rgb8 || h->rgb8, "I420 frames: the handle has no 8-bit RGB scratch");
   g.final_out = last ? (via_rgb8 ? h->rgb8 : final_out) : nullptr;
   g.final_mode = last ? (via_rgb8 ? kOutU8 : final_mode) : kOutNone;
+  g.yuv = h->yuv;
   g.write_pyr = (!last || h->tune.write_pyr) ? 1 : 0;
   g.sat = h->sat + 16 + li;
   g.oflow = epi ? h->oflow : nullptr;
@@ -205,7 +207,7 @@ int run_level(float_dec* h, int li, int n, const void* x_in, void* Zb, void* U, 
   }
 #endif
   if ((rc = launch_flow<T>(cx, g))) return rc;
-  return via_rgb8 ? launch_rgb8_to_i420(cx, h->rgb8, final_out, n, R) : FLOAT_OK;
+  return via_rgb8 ? launch_rgb8_to_i420(cx, h->rgb8, final_out, n, R, h->yuv) : FLOAT_OK;
 }
 
 // Low phase for `n` frames (n <= lo_frames): constant input, conv1, levels 8..32.  Leaves the
@@ -623,21 +625,30 @@ int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d,
   return dec_run_host(h, s_r, r_d, n_frames, out_hwc, host_hwc, kOutU8, stream, copy_stream);
 }
 
-// The colour matrix of the I420 calls: 0 = BT.601 limited range, the only one there is (refused before anything else is looked at)
-#define DEC_REQUIRE_MATRIX(fn, matrix) \
-  FH_REQUIRE((matrix) == FLOAT_DEC_MATRIX_BT601_LIMITED, fn ": matrix %d unknown (0 = BT.601 limited range is the only one)", (int)(matrix))
+// The colour matrix of the I420 calls (common.hpp: kFhYuvRows; 0 / 2 / 4 / 6 = BT.601 / BT.709, limited / full range): an unknown
+// id is refused before anything else is looked at.  The table rides in the kernels' arguments (FlowArgs::yuv, and the converter's
+// last argument), six dwords that the scalar unit unpacks - not a template parameter: dec_flowlast_kernel's I420 instantiation
+// stays one per operand type at 56 VGPRs (64 -> 70 SGPRs), dec_rgb8_to_i420_kernel at 50 (51).  MI355X, yuvbench.py --matrix 6
+// (20 interleaved repetitions): decode + hand-over of 250 frames 20.13 (id 0) / 20.07 ms (id 6) fused and 20.28 / 20.27 ms through
+// the converter, against 20.08 and 20.25 ms for the constants in the instructions (the commit before; spreads 0.07 ... 0.26 ms).
+#define DEC_REQUIRE_MATRIX(fn, matrix, t) \
+  FH_REQUIRE(fh_yuv_of((matrix), &(t)), fn ": matrix %d unknown (" FH_YUV_IDS ")", (int)(matrix))
 
 int float_dec_frames_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix, uint8_t* out,
                           void* stream) {
+  FhYuv t;
   FH_REQUIRE(h && s_r && r_d && out, "null argument to float_dec_frames_i420");
-  DEC_REQUIRE_MATRIX("float_dec_frames_i420", matrix);
+  DEC_REQUIRE_MATRIX("float_dec_frames_i420", matrix, t);
+  h->yuv = t;
   return dec_run(h, s_r, r_d, n_frames, out, kOutI420, stream);
 }
 
 int float_dec_frames_host_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix, uint8_t* out,
                                uint8_t* host, void* stream, void* copy_stream) {
+  FhYuv t;
   FH_REQUIRE(h && s_r && r_d && out && host, "null argument to float_dec_frames_host_i420");
-  DEC_REQUIRE_MATRIX("float_dec_frames_host_i420", matrix);
+  DEC_REQUIRE_MATRIX("float_dec_frames_host_i420", matrix, t);
+  h->yuv = t;
   return dec_run_host(h, s_r, r_d, n_frames, out, host, kOutI420, stream, copy_stream);
 }
 

@@ -359,6 +359,7 @@ struct FlowArgs {
   void* final_out;     // last level: frames (float, modes 3 and 4: uint8_t)
   int final_mode;      // 0: none, 1: HWC clamp(-1,1)*0.5+0.5 (FLOAT.py:149-152), 2: raw CHW, 3: HWC uint8 = dec_quant8(mode 1's value),
                        // 4: planar I420 of mode 3's samples (dec_flowlast_kernel's I420 instantiation only)
+  FhYuv yuv;           // final_mode 4: the call's colour matrix
   int write_pyr;       // store flow_out / rgb_out (0 on the last level: nobody reads them)
   int F, R, C, ld_s;
   int nbands, band_pix;  // the image is cut into nbands runs of band_pix consecutive pixels (multiple of gpb*PIX)
@@ -424,11 +425,8 @@ __device__ __forceinline__ unsigned dec_quant8(float v) {
   return (unsigned)rintf(y * 255.0f);
 }
 
-// I420 (final_mode 4, float_dec_frames_i420): 8-bit BT.601 limited range from the 8-bit RGB samples, int32 throughout (>> of a
-// negative sum is an arithmetic shift = floor).  Chroma takes the rounded mean of the 2 x 2 block, sited at its centre.
-__device__ __forceinline__ unsigned dec_i420_y(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
-__device__ __forceinline__ unsigned dec_i420_u(int mr, int mg, int mb) { return (unsigned)(((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128); }
-__device__ __forceinline__ unsigned dec_i420_v(int mr, int mg, int mb) { return (unsigned)(((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128); }
+// I420 (final_mode 4, float_dec_frames_i420): 8-bit YUV from the 8-bit RGB samples by fh_yuv_plane (common.hpp) and the call's
+// matrix.  Chroma takes the rounded mean of the 2 x 2 block, sited at its centre.
 
 // One run of PIX consecutive pixels of a row (first pixel p0 = Y * R + X0 of frame f) for one lane group: ToFlow (1x1
 // modulated conv + up-sampled previous flow -> tanh / sigmoid), grid_sample of the skip features, blend, ToRGB, the pyramids,
@@ -1824,7 +1822,7 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
   } else if constexpr (I420) {
     const unsigned q0 = dec_quant8(v0), q1 = dec_quant8(v1), q2 = dec_quant8(v2), lane = threadIdx.x & 63u;
     // Y: bytes of lanes (0, 1) and (2, 3) pair up (quad_perm [1, 0, 3, 2]), then the pairs (quad_perm [2, 3, 0, 1]); lane 0 stores
-    const unsigned y = dec_i420_y((int)q0, (int)q1, (int)q2);
+    const unsigned y = fh_yuv_plane(g.yuv, 0, (int)q0, (int)q1, (int)q2);
     const unsigned y2 = y | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)y, 0xB1, 0xF, 0xF, false) << 8);
     const unsigned y4 = y2 | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)y2, 0x4E, 0xF, 0xF, false) << 16);
     if ((lane & 3u) == 0u) *reinterpret_cast<unsigned*>(ff.final_y + po) = y4;
@@ -1837,7 +1835,7 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
     const int mr = (int)((s & 1023u) + 2u) >> 2, mg = (int)((s >> 10 & 1023u) + 2u) >> 2, mb = (int)((s >> 20) + 2u) >> 2;
     // U in bits 0..7, V in bits 16..23; the quad's two blocks side by side (quad_perm [2, 3, 0, 1]), then the next quad's
     // pair from four lanes up (row_shl:4, within the row of 16 lanes): lanes with (lane & 7) == 0 hold four U and four V bytes
-    const unsigned c = dec_i420_u(mr, mg, mb) | (dec_i420_v(mr, mg, mb) << 16);
+    const unsigned c = fh_yuv_plane(g.yuv, 1, mr, mg, mb) | (fh_yuv_plane(g.yuv, 2, mr, mg, mb) << 16);
     const unsigned c2 = c | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)c, 0x4E, 0xF, 0xF, false) << 8);
     const unsigned cn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)c2, 0x104, 0xF, 0xF, false);
     if ((lane & 7u) == 0u) {
@@ -1864,7 +1862,7 @@ __global__ __launch_bounds__(256) void dec_flowlast_kernel(FlowArgs g) {
 // 2 x 8 Y bytes as two dwords per row, its four U bytes and its four V bytes as one dword each.  R % 8 == 0, rgb and out 4-byte
 // aligned.
 static __global__ __launch_bounds__(256) void dec_rgb8_to_i420_kernel(const unsigned char* __restrict__ rgb, unsigned char* __restrict__ out,
-                                                                      int F, int R) {
+                                                                      int F, int R, const FhYuv yuv) {
   const unsigned cols = (unsigned)R >> 3, per = cols * ((unsigned)R >> 1);
   const unsigned idx = blockIdx.x * 256u + threadIdx.x;
   if (idx >= per * (unsigned)F) return;
@@ -1883,14 +1881,14 @@ static __global__ __launch_bounds__(256) void dec_rgb8_to_i420_kernel(const unsi
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int x = 0; x < 8; ++x)
-      yw[a][x >> 2] |= dec_i420_y(byte(a, 3 * x), byte(a, 3 * x + 1), byte(a, 3 * x + 2)) << (8 * (x & 3));
+      yw[a][x >> 2] |= fh_yuv_plane(yuv, 0, byte(a, 3 * x), byte(a, 3 * x + 1), byte(a, 3 * x + 2)) << (8 * (x & 3));
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     int m[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) m[c] = (byte(0, 6 * b + c) + byte(0, 6 * b + 3 + c) + byte(1, 6 * b + c) + byte(1, 6 * b + 3 + c) + 2) >> 2;
-    uw |= dec_i420_u(m[0], m[1], m[2]) << (8 * b);
-    vw |= dec_i420_v(m[0], m[1], m[2]) << (8 * b);
+    uw |= fh_yuv_plane(yuv, 1, m[0], m[1], m[2]) << (8 * b);
+    vw |= fh_yuv_plane(yuv, 2, m[0], m[1], m[2]) << (8 * b);
   }
 #pragma unroll
   for (int a = 0; a < 2; ++a) {

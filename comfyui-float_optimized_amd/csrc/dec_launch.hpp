@@ -332,11 +332,11 @@ inline FlowArgs flow_args_of(const Level& L, const float* styles, int ld_s, int 
 inline bool flowlast_takes_i420(int R) { return R >= 128 && R % 128 == 0; }
 
 // I420 frames from `n` finished 8-bit RGB frames of R x R (dec_rgb8_to_i420_kernel), behind the level that rendered them.
-inline int launch_rgb8_to_i420(const DecLaunch& cx, const unsigned char* rgb, void* out, int n, int R) {
+inline int launch_rgb8_to_i420(const DecLaunch& cx, const unsigned char* rgb, void* out, int n, int R, const FhYuv& yuv) {
   FH_REQUIRE(R % 8 == 0, "I420 frames: %d px is not a multiple of 8", R);
   const size_t lanes = (size_t)n * (R / 2) * (R / 8);
   hipLaunchKernelGGL(dec_rgb8_to_i420_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, cx.st, rgb,
-                     static_cast<unsigned char*>(out), n, R);
+                     static_cast<unsigned char*>(out), n, R, yuv);
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;
 }

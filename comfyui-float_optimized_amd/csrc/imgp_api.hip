@@ -53,13 +53,22 @@ int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, cons
   FH_REQUIRE(rect_x >= -kImgpMaxOff && rect_x <= kImgpMaxOff && rect_y >= -kImgpMaxOff && rect_y <= kImgpMaxOff,
              "float_img_paste_i420: box origin rect_x, rect_y (%d, %d) must be within +-%d", rect_x, rect_y, kImgpMaxOff);
   FH_REQUIRE(feather >= 0 && feather <= kImgpMaxSrc, "float_img_paste_i420: feather (%d) must be 0 ... %d", feather, kImgpMaxSrc);
-  FH_REQUIRE(matrix == FLOAT_IMG_MATRIX_BT601_LIMITED, "float_img_paste_i420: matrix (%d) must be FLOAT_IMG_MATRIX_BT601_LIMITED (0)", matrix);
+  FhYuv t;
+  FH_REQUIRE(fh_yuv_of(matrix, &t), "float_img_paste_i420: matrix (%d) must be one of " FH_YUV_IDS, matrix);
 
   ImgpPlan p = imgp_make_plan(src_h, src_w, fr_h, fr_w, rect_x, rect_y, rect_w, rect_h, feather);
   const ImgpYuv q = imgp_make_yuv(src_h, src_w);
   const size_t out_bytes = (size_t)q.y_bytes + 2u * (size_t)q.c_bytes;  // 3 H W / 2
   // dword and 16-bit stores where every frame, plane and row is aligned for them; else bytes (imgp_kernels.hpp)
   const bool fast = src_w % 4 == 0 && ((uintptr_t)out & 3u) == 0;
+
+  void (*kern)(const unsigned char*, const unsigned char*, unsigned char*, ImgpPlan, ImgpYuv);
+  switch (matrix) {
+    case 2: kern = fast ? imgp_paste_i420_kernel<true, 2> : imgp_paste_i420_kernel<false, 2>; break;
+    case 4: kern = fast ? imgp_paste_i420_kernel<true, 4> : imgp_paste_i420_kernel<false, 4>; break;
+    case 6: kern = fast ? imgp_paste_i420_kernel<true, 6> : imgp_paste_i420_kernel<false, 6>; break;
+    default: kern = fast ? imgp_paste_i420_kernel<true, 0> : imgp_paste_i420_kernel<false, 0>;
+  }
 
   // one launch; a clip of more frames than a grid holds goes in groups of whole frames
   hipStream_t s = (hipStream_t)stream;
@@ -69,10 +78,7 @@ int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, cons
     const dim3 grid(q.spans * (unsigned)p.n_frames);
     const uint8_t* fr = frames8 + (size_t)f0 * p.in_bytes;
     uint8_t* o = out + (size_t)f0 * out_bytes;
-    if (fast)
-      hipLaunchKernelGGL(imgp_paste_i420_kernel<true>, grid, dim3(kImgpThreads), 0, s, src8, fr, o, p, q);
-    else
-      hipLaunchKernelGGL(imgp_paste_i420_kernel<false>, grid, dim3(kImgpThreads), 0, s, src8, fr, o, p, q);
+    hipLaunchKernelGGL(kern, grid, dim3(kImgpThreads), 0, s, src8, fr, o, p, q);
   }
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;

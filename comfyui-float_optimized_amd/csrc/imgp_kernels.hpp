@@ -277,14 +277,14 @@ inline ImgpYuv imgp_make_yuv(int src_h, int src_w) {  // both even
   return q;
 }
 
-// 8-bit BT.601 limited range in int32, >> the arithmetic shift: host_models.rgb8_to_i420
-__device__ __forceinline__ unsigned imgp_i420_y(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
-__device__ __forceinline__ unsigned imgp_i420_u(int mr, int mg, int mb) { return (unsigned)(((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128); }
-__device__ __forceinline__ unsigned imgp_i420_v(int mr, int mg, int mb) { return (unsigned)(((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128); }
-
-template <bool FAST>
+// The conversion is fh_yuv_plane (common.hpp) on the rows of matrix M (0 / 2 / 4 / 6): host_models.rgb8_to_i420.  M is a template
+// parameter here, not a kernel argument as in the decoder's kernels: the FAST instantiation sits at 80 VGPRs, six waves per SIMD,
+// and the table in SGPRs cost it the 81st (the compiler keeps coefficients in VGPRs across the cell's loops) and with it a wave;
+// folded into the instructions, M = 0 compiles to the registers it had.
+template <bool FAST, int M>
 __global__ __launch_bounds__(kImgpThreads) void imgp_paste_i420_kernel(const unsigned char* __restrict__ src, const unsigned char* __restrict__ frames,
                                                                        unsigned char* __restrict__ out, const ImgpPlan p, const ImgpYuv q) {
+  constexpr FhYuv t = fh_yuv_pack(kFhYuvRows[M >> 1]);
   // block -> (frame, span): all frames of a span back to back on ids congruent mod 8
   const unsigned slot = blockIdx.x >> 3;
   const unsigned f = slot % (unsigned)p.n_frames;
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(kImgpThreads) void imgp_paste_i420_kernel(const uns
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) rgb[ch] = imgp_blend(imgp_face(fr, p, px, ch), rgb[ch], px.alpha);
       }
-      yw |= imgp_i420_y((int)rgb[0], (int)rgb[1], (int)rgb[2]) << (8 * col);
+      yw |= fh_yuv_plane(t, 0, (int)rgb[0], (int)rgb[1], (int)rgb[2]) << (8 * col);
       const int sh = 16 * (col >> 1);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) m[ch] += rgb[ch] << sh;
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(kImgpThreads) void imgp_paste_i420_kernel(const uns
   for (int blk = 0; blk < 2; ++blk) {
     const int mr = (int)(((m[0] >> (16 * blk)) & 0xffffu) + 2u) >> 2, mg = (int)(((m[1] >> (16 * blk)) & 0xffffu) + 2u) >> 2,
               mb = (int)(((m[2] >> (16 * blk)) & 0xffffu) + 2u) >> 2;
-    uv[blk] = imgp_i420_u(mr, mg, mb) | (imgp_i420_v(mr, mg, mb) << 8);
+    uv[blk] = fh_yuv_plane(t, 1, mr, mg, mb) | (fh_yuv_plane(t, 2, mr, mg, mb) << 8);
   }
   const unsigned at = cy * (W >> 1) + (x0 >> 1);  // < c_bytes
   unsigned char* uo = o + q.y_bytes + at;

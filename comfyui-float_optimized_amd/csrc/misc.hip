@@ -221,6 +221,19 @@ int float_hip_abi_version(void) { return FLOAT_HIP_ABI_VERSION; }
 
 const char* float_last_error(void) { return g_err; }
 
+// The rows as the kernels get them: unpacked from the words of FhYuv, not copied from kFhYuvRows
+int float_yuv_matrix(int32_t matrix, int32_t table[15]) {
+  FhYuv t;
+  FH_REQUIRE(table, "float_yuv_matrix: null argument (table)");
+  FH_REQUIRE(fh_yuv_of(matrix, &t), "float_yuv_matrix: matrix %d unknown (" FH_YUV_IDS ")", (int)matrix);
+  for (int p = 0; p < 3; ++p) {
+    for (int i = 0; i < 3; ++i) table[5 * p + i] = fh_yuv_field(t.coef[p], i);
+    table[5 * p + 3] = t.bias[p] & 255;
+    table[5 * p + 4] = t.bias[p] >> 8;
+  }
+  return FLOAT_OK;
+}
+
 int float_set_profiling(int32_t on) {
   g_fh_profiling = on ? 1 : 0;
   if (on) {

@@ -4,7 +4,7 @@ import ctypes as C
 
 import torch
 
-from . import native
+from . import host_models, native
 
 
 def blur_taps(blur_kernel):
@@ -132,14 +132,17 @@ class SynthesisHIP:
         return self._run(native.lib().float_dec_frames_u8, s_r, r_d, (self.size, self.size, 3), torch.uint8, out)
 
     @torch.no_grad()
-    def decode_i420(self, s_r, r_d, s_r_feats=None, out=None):
+    def decode_i420(self, s_r, r_d, s_r_feats=None, out=None, matrix=None):
         """decode_latent_into_processed_images as planar YUV 4:2:0 frames (float_dec_frames_i420): (T, 3 * size / 2, size) uint8 on
         the GPU - per frame the Y plane, then U and V at half the size, what ffmpeg calls yuv420p and OpenCV's *_I420 conversions
-        use.  BT.601 limited range from the 8-bit samples, in integers: bitwise host_models.rgb8_to_i420(decode_u8(...))."""
+        use.  From the 8-bit samples, in integers: bitwise host_models.rgb8_to_i420(decode_u8(...), matrix).  matrix: as
+        host_models.yuv_matrix_id reads it - None = BT.601 limited range, "bt709", "bt601-full", "bt709-full", their ids, or
+        "auto" (by the model's size)."""
+        m = host_models.yuv_matrix_id(matrix, self.size, self.size)
         if s_r_feats is not None:
             self.set_feats(s_r_feats)
         L = native.lib()
-        return self._run(lambda h, s, r, T, out, st: L.float_dec_frames_i420(h, s, r, T, native.MATRIX_BT601_LIMITED, out, st),
+        return self._run(lambda h, s, r, T, out, st: L.float_dec_frames_i420(h, s, r, T, m, out, st),
                          s_r, r_d, (3 * self.size // 2, self.size), torch.uint8, out)
 
     @torch.no_grad()
@@ -167,13 +170,14 @@ class SynthesisHIP:
         return (tot.value, list(sites)) if per_site else tot.value
 
     @torch.no_grad()
-    def decode_into_host(self, s_r, r_d, host, staging=None, copy_stream=None, out_format=None):
+    def decode_into_host(self, s_r, r_d, host, staging=None, copy_stream=None, out_format=None, matrix=None):
         """decode_latent_into_processed_images with the reference's destination (a pre-allocated CPU tensor, FLOAT.py:139):
         `host` (T, size, size, 3) fp32, or uint8 for 8-bit frames (float_dec_frames_host_u8; the staging tensor has the same
         dtype, one of another dtype is replaced).  out_format "i420": `host` (T, 3 * size / 2, size) uint8, planar YUV 4:2:0 as
         decode_i420 gives it (float_dec_frames_host_i420); "rgb": the (T, size, size, 3) forms; None: by the number of dimensions
         of a uint8 `host`.  A `host` of the wrong shape for the stated format is a ValueError; a staging tensor of another format
-        is replaced, never reinterpreted.  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
+        is replaced, never reinterpreted.  matrix: the colour matrix of I420 frames, as in decode_i420; with RGB frames anything
+        but None is a ValueError.  Pinned (`pin_memory()`): the frames of batch i are stored into it by copy
         workgroups inside the launches of batch i+1 (or, with `copy_stream`, copied on that stream while the next batch
         renders - see include/float_hip.h for why that form does not pay on MI355X).  Pageable: accepted, one staged
         hipMemcpyAsync behind each batch (the operator asks the runtime what `host` is, nothing is assumed).  Returns the
@@ -182,6 +186,7 @@ class SynthesisHIP:
         r_d = r_d.to(self.device, torch.float32).reshape(-1, self.style_dim).contiguous()
         T = r_d.shape[0]
         out_format = infer_out_format(host, out_format)
+        m = host_models.yuv_matrix_for("decode_into_host", matrix, out_format, self.size, self.size)
         if host.dtype not in (torch.float32, torch.uint8):
             raise ValueError("host must be float32 or uint8 (got %s)" % (host.dtype,))
         shape = (T,) + self.frame_shape(out_format)
@@ -197,8 +202,7 @@ class SynthesisHIP:
                 C.c_void_p(copy_stream.cuda_stream) if copy_stream is not None else None)
         with torch.cuda.device(self.device):
             if out_format == "i420":
-                native.check(L.float_dec_frames_host_i420(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T,
-                                                          native.MATRIX_BT601_LIMITED, *tail))
+                native.check(L.float_dec_frames_host_i420(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, m, *tail))
             else:
                 native.check(fn(self._h, native.dev_ptr(s_r), native.dev_ptr(r_d), T, *tail))
         return staging

@@ -425,42 +425,108 @@ def emotion_one_hot(name, device="cpu"):
     return F.one_hot(torch.tensor(idx, device=device), num_classes=len(EMOTION_LABELS)).float()[None, None]
 
 
-def rgb8_to_i420(frames_u8):
+# The colour matrices of the I420 outputs, by id: rows Y, U, V of (cr, cg, cb, rnd, off) for
+#     plane = ((cr * r + cg * g + cb * b + rnd) >> 8) + off        in int32, >> the arithmetic shift (floor)
+# The id is a flag word: bit 1 = BT.709, bit 2 = full range.  Every Y row sums to 220 (limited) or 256 (full) and every chroma
+# row to 0, so a grey sample gives exactly U = V = 128 (the plainly rounded BT.709 U row -26, -87, 112 sums to -1 and tints bright
+# greys: hence -86).  No clamp: limited range gives Y in [16, 235] and U, V in [16, 240], full range exactly [0, 255] - the
+# chroma rounding term of 127 keeps pure blue and pure red at 255, as libjpeg's does.  Over all 2^24 RGB triples every plane is
+# within 1.17 levels of the float64 formulas (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722; scales 219/255 and 224/255, or 1).
+# csrc/common.hpp holds the same table for the kernels (float_yuv_matrix returns it).
+YUV_MATRICES = {
+    0: ((66, 129, 25, 128, 16), (-38, -74, 112, 128, 128), (112, -94, -18, 128, 128)),    # BT.601 limited
+    2: ((47, 157, 16, 128, 16), (-26, -86, 112, 128, 128), (112, -102, -10, 128, 128)),   # BT.709 limited
+    4: ((77, 150, 29, 128, 0), (-43, -85, 128, 127, 128), (128, -107, -21, 127, 128)),    # BT.601 full
+    6: ((54, 183, 19, 128, 0), (-29, -99, 128, 127, 128), (128, -116, -12, 127, 128)),    # BT.709 full
+}
+YUV_MATRIX_NAMES = {"bt601": 0, "bt709": 2, "bt601-full": 4, "bt709-full": 6}
+
+
+def yuv_matrix_id(m, width=None, height=None):
+    """The id (0 | 2 | 4 | 6, a key of YUV_MATRICES) of a `matrix` argument: None -> 0 (BT.601 limited range, the default
+    everywhere); an id; "bt601" | "bt709" | "bt601-full" | "bt709-full"; or "auto", which needs the size of the frames that
+    leave: BT.709 limited when width >= 1280 or height > 576, else BT.601 limited.  That rule mirrors what players and encoders
+    guess for untagged video (mpv's; ffmpeg-based players do likewise for HD) - a convention, not a measurement.  Anything else
+    is a ValueError."""
+    if m is None:
+        return 0
+    if isinstance(m, str):
+        if m == "auto":
+            if width is None or height is None:
+                raise ValueError("matrix='auto' needs the size of the frames that leave (width, height)")
+            return 2 if (int(width) >= 1280 or int(height) > 576) else 0
+        if m in YUV_MATRIX_NAMES:
+            return YUV_MATRIX_NAMES[m]
+    elif isinstance(m, int) and not isinstance(m, bool) and m in YUV_MATRICES:
+        return int(m)
+    raise ValueError("matrix must be None, 0 | 2 | 4 | 6, 'auto' or one of %s (got %r)" % (sorted(YUV_MATRIX_NAMES), m))
+
+
+def yuv_matrix_for(what, matrix, fmt, width=None, height=None):
+    """The id of the `matrix` keyword of a call `what` whose frames leave in format `fmt` at width x height: yuv_matrix_id for
+    "i420"; any other format (fp32 or uint8 RGB, JPEG) has no matrix to choose, and a `matrix` other than None there is a
+    ValueError - raised at the call, before anything is enqueued or opened."""
+    if fmt != "i420":
+        if matrix is not None:
+            raise ValueError("%s: matrix=%r applies to out_format='i420' only (these frames leave as %s)" % (what, matrix, fmt))
+        return 0
+    return yuv_matrix_id(matrix, width, height)
+
+
+def yuv_full_range(matrix):
+    """True where the matrix gives full-range samples (ids 4 and 6)."""
+    return bool(yuv_matrix_id(matrix) & 4)
+
+
+def yuv_ffmpeg_args(matrix):
+    """The arguments that tell ffmpeg what raw or Y4M I420 frames of `matrix` (None | id | name, not "auto") hold - Y4M carries
+    the range (XCOLORRANGE) but not the matrix, so a caller states it: ["-colorspace", .., "-color_primaries", .., "-color_trc",
+    .., "-color_range", ..] with bt709 x 3 for BT.709 and smpte170m x 3 for BT.601, and tv (limited) or pc (full)."""
+    i = yuv_matrix_id(matrix)
+    name = "bt709" if i & 2 else "smpte170m"
+    return ["-colorspace", name, "-color_primaries", name, "-color_trc", name, "-color_range", "pc" if i & 4 else "tv"]
+
+
+def rgb8_to_i420(frames_u8, matrix=None):
     """(T, R, R, 3) or (R, R, 3) uint8 RGB -> (T, 3R/2, R) or (3R/2, R) uint8 planar YUV 4:2:0 (I420: the Y plane R x R, then U and
-    V at R/2 x R/2 each, row-major, contiguous - OpenCV's *_I420 layout, ffmpeg's yuv420p).  8-bit BT.601 limited range, all in
-    int32 with >> an arithmetic shift (floor):
+    V at R/2 x R/2 each, row-major, contiguous - OpenCV's *_I420 layout, ffmpeg's yuv420p).  matrix: as yuv_matrix_id reads it
+    (not "auto"); None = 0 = 8-bit BT.601 limited range, all in int32 with >> an arithmetic shift (floor):
         Y  = ((66 R + 129 G + 25 B + 128) >> 8) + 16                        per pixel, in [16, 235]
         Mc = (c00 + c01 + c10 + c11 + 2) >> 2                               per 2 x 2 block and channel c
         U  = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128                   in [16, 240]
         V  = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128                    in [16, 240]
+    The other ids take their rows of YUV_MATRICES in the same arithmetic.
     Chroma is sited at the block centre (Y4M's C420jpeg).  This is the definition of what SynthesisHIP.decode_i420 and
-    float_dec_frames[_host]_i420 produce: bitwise rgb8_to_i420(decode_u8(...)).  Works on any device."""
+    float_dec_frames[_host]_i420 produce: bitwise rgb8_to_i420(decode_u8(...), matrix).  Works on any device."""
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (3, 4) or frames_u8.shape[-1] != 3:
         raise ValueError("rgb8_to_i420 takes (T, H, W, 3) or (H, W, 3) uint8 frames, got %s %s" % (frames_u8.dtype, tuple(frames_u8.shape)))
+    ky, ku, kv = YUV_MATRICES[yuv_matrix_id(matrix)]
     single = frames_u8.dim() == 3
     x = (frames_u8[None] if single else frames_u8).to(torch.int32)
     T, H, W, _ = x.shape
     if H % 2 or W % 2:
         raise ValueError("rgb8_to_i420 needs even sizes for 4:2:0 chroma (got %d x %d)" % (H, W))
-    r, g, b = x[..., 0], x[..., 1], x[..., 2]
-    y = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
+
+    def plane(k, r, g, b):
+        return ((k[0] * r + k[1] * g + k[2] * b + k[3]) >> 8) + k[4]
+
+    y = plane(ky, x[..., 0], x[..., 1], x[..., 2])
     m = (x.reshape(T, H // 2, 2, W // 2, 2, 3).sum(dim=(2, 4)) + 2) >> 2
-    mr, mg, mb = m[..., 0], m[..., 1], m[..., 2]
-    u = ((-38 * mr - 74 * mg + 112 * mb + 128) >> 8) + 128
-    v = ((112 * mr - 94 * mg - 18 * mb + 128) >> 8) + 128
+    u = plane(ku, m[..., 0], m[..., 1], m[..., 2])
+    v = plane(kv, m[..., 0], m[..., 1], m[..., 2])
     out = torch.cat([y.reshape(T, -1), u.reshape(T, -1), v.reshape(T, -1)], dim=1).to(torch.uint8)
     out = out.reshape(T, H * 3 // 2, W)
     return out[0] if single else out
 
 
-def paste_i420(src8, frames8, rect, feather):
-    """The pasted frames as planar YUV 4:2:0: rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather)) -> (T, 3H/2, W) uint8 at the
-    portrait's size, H and W even (ValueError otherwise - nothing is padded or cropped).  Chroma is the 2 x 2 mean of the PASTED
+def paste_i420(src8, frames8, rect, feather, matrix=None):
+    """The pasted frames as planar YUV 4:2:0: rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather), matrix) -> (T, 3H/2, W) uint8
+    at the portrait's size, H and W even (ValueError otherwise - nothing is padded or cropped).  Chroma is the 2 x 2 mean of the PASTED
     8-bit RGB samples, so a block that straddles the box edge or the feather mixes pasted and source pixels; it is never a blend
     of chroma.  The definition `float_img_paste_i420` (image.paste_frames_device(out_format="i420")) is held to bit for bit."""
     if src8.dim() == 3 and (src8.shape[0] % 2 or src8.shape[1] % 2):
         raise ValueError("paste_i420: a %d x %d portrait has an odd side; 4:2:0 chroma needs even sides" % (src8.shape[0], src8.shape[1]))
-    return rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather))
+    return rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather), matrix)
 
 
 def y4m_rate(fps):
@@ -482,15 +548,18 @@ class Y4MWriter:
     writer is made, and every write(frames) appends `FRAME` + the frame's bytes per frame.  path_or_file: a path (opened here
     and closed by close() / on leaving the `with` block), or an object with write() (a pipe to an encoder's stdin), which is
     left open.  fps: as y4m_rate reads it.  write() has handed the bytes on when it returns, so a view of a ring slot may be
-    given back right after it."""
+    given back right after it.  matrix: as yuv_matrix_id reads it; the full-range ids (4, 6) write XCOLORRANGE=FULL.  Y4M has no
+    tag for the matrix itself: yuv_ffmpeg_args states it to the consumer."""
 
-    def __init__(self, path_or_file, width, height, fps):
+    def __init__(self, path_or_file, width, height, fps, matrix=None):
         width, height = int(width), int(height)
         if width < 2 or height < 2 or width % 2 or height % 2:
             raise ValueError("Y4MWriter: 4:2:0 frames have even sides (got %d x %d)" % (width, height))
         self.width, self.height = width, height
+        self.matrix = yuv_matrix_id(matrix, width, height)
         rate = y4m_rate(fps)
-        header = "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (width, height, rate.numerator, rate.denominator)
+        header = "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=%s\n" % (width, height, rate.numerator, rate.denominator,
+                                                                              "FULL" if self.matrix & 4 else "LIMITED")
         self.frames = 0
         self._own = not hasattr(path_or_file, "write")
         self._f = open(path_or_file, "wb") if self._own else path_or_file
@@ -528,16 +597,16 @@ class Y4MWriter:
         return False
 
 
-def write_y4m(path_or_file, frames_i420, fps):
+def write_y4m(path_or_file, frames_i420, fps, matrix=None):
     """Write (T, 3R/2, R) uint8 I420 frames (rgb8_to_i420 / SynthesisHIP.decode_i420 / out_format="i420") as a YUV4MPEG2
     stream, which ffmpeg, x264 and mpv read as it is: the header `YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420jpeg
     XCOLORRANGE=LIMITED`, then `FRAME` + the frame's bytes per frame.  fps: as y4m_rate reads it (25 -> 25:1, 29.97 ->
     30000:1001).  path_or_file: a path, or an object with write() (a pipe to an encoder's stdin).  Y4MWriter is the
-    block-by-block form."""
+    block-by-block form.  matrix: the matrix the frames were made with (XCOLORRANGE=FULL for ids 4 and 6)."""
     if frames_i420.dtype != torch.uint8 or frames_i420.dim() != 3 or frames_i420.shape[1] * 2 != frames_i420.shape[2] * 3:
         raise ValueError("write_y4m takes (T, 3R/2, R) uint8 I420 frames, got %s %s" % (frames_i420.dtype, tuple(frames_i420.shape)))
     T, H32, W = frames_i420.shape
-    with Y4MWriter(path_or_file, W, H32 * 2 // 3, fps) as w:
+    with Y4MWriter(path_or_file, W, H32 * 2 // 3, fps, matrix) as w:
         w.write(frames_i420)
 
 

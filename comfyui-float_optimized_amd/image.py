@@ -152,7 +152,7 @@ def pasted_frame_shape(H, W, fmt):
 
 
 @torch.no_grad()
-def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None):
+def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None, matrix=None):
     """float_img_paste: frames8 (T, h, w, 3) uint8 - what the decoder's decode_u8 leaves in HBM - back in the portrait src8 (H, W,
     3) uint8 at the box rect = (x0, y0, w, h) in source coordinates (what InferenceAgent.host_inputs_placed returns; it may reach
     outside the image) -> (T, H, W, 3) uint8 on the device, bitwise host_models.paste_rgb8(src8, frames8, rect, feather).
@@ -161,12 +161,16 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
     else of src8, else cuda:0.  out: a contiguous (T, H, W, 3) uint8 tensor on that device to write into.  One launch on the
     current stream; nothing is allocated besides `out`, nothing synchronises.
     out_format: None | "rgb" as above; "i420" is float_img_paste_i420, paste and colour conversion in one kernel -> (T, 3H/2, W)
-    uint8 planar YUV 4:2:0 (BT.601 limited range), bitwise host_models.paste_i420(src8, frames8, rect, feather), half the bytes;
-    H and W must be even (ValueError) and `out` is checked against that shape."""
+    uint8 planar YUV 4:2:0, bitwise host_models.paste_i420(src8, frames8, rect, feather, matrix), half the bytes;
+    H and W must be even (ValueError) and `out` is checked against that shape.  matrix: as host_models.yuv_matrix_id reads it
+    (None = BT.601 limited range; "auto" goes by the portrait's size); with RGB frames anything but None is a ValueError."""
     fmt = paste_format("paste_frames_device", out_format)
+    if fmt != "i420":
+        host_models.yuv_matrix_for("paste_frames_device", matrix, fmt)  # refused before anything is uploaded
     device = frames8.device if frames8.is_cuda else (src8.device if src8.is_cuda else torch.device("cuda:0"))
     s = _u8_device(src8, "src8", 3, device)
     f = _u8_device(frames8, "frames8", 4, device)
+    m = host_models.yuv_matrix_for("paste_frames_device", matrix, fmt, int(s.shape[1]), int(s.shape[0]))
     if len(rect) != 4:
         raise ValueError("paste_frames_device: rect must be (x0, y0, w, h), got %r" % (rect,))
     x0, y0, w, h = (int(v) for v in rect)
@@ -188,7 +192,7 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
         L = native.lib()
         if fmt == "i420":
             native.check(L.float_img_paste_i420(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
-                                                x0, y0, w, h, feather, native.IMG_MATRIX_BT601_LIMITED, C.c_void_p(out.data_ptr()),
+                                                x0, y0, w, h, feather, m, C.c_void_p(out.data_ptr()),
                                                 native.stream_ptr(device)))
         else:
             native.check(L.float_img_paste(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),

@@ -14,6 +14,8 @@ IMG_RGBA_MODES = {"discard_alpha": 0, "blend_with_color": 1, "replace_with_color
 IMG_OUT_NCHW_PM1, IMG_OUT_HWC_U8 = 0, 1  # FLOAT_IMG_OUT_*: float_img_front's `out_mode`
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
 IMG_MATRIX_BT601_LIMITED = 0  # FLOAT_IMG_MATRIX_BT601_LIMITED: the `matrix` argument of float_img_paste_i420
+# FLOAT_DEC_MATRIX_* and their FLOAT_IMG_MATRIX_* twins: bit 1 = BT.709, bit 2 = full range (host_models.YUV_MATRICES)
+MATRIX_BT709_LIMITED, MATRIX_BT601_FULL, MATRIX_BT709_FULL = 2, 4, 6
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "heun2": 3, "heun3": 4}
 DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP16, "float16": FLOAT_DT_FP16,
           "fp32": FLOAT_DT_FP32, "float32": FLOAT_DT_FP32}  # fp32: the verification mode of the FMT and decoder operators
@@ -69,6 +71,7 @@ _F = C.POINTER(C.c_float)
 _SIGNATURES = {
     "float_hip_abi_version": (C.c_int, []),
     "float_last_error": (C.c_char_p, []),
+    "float_yuv_matrix": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
     "float_set_profiling": (C.c_int, [C.c_int32]),
     "float_probe_peaks": (C.c_int, [C.POINTER(C.c_float)] * 4 + [C.POINTER(C.c_int32)]),
     "float_profile_ms": (C.c_double, [C.c_int32, C.POINTER(C.c_int64)]),

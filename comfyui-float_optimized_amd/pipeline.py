@@ -9,7 +9,7 @@ import warnings
 
 import torch
 
-from . import image, jpeg, native
+from . import host_models, image, jpeg, native
 from .config import FmtConfig
 from .decoder import SynthesisHIP, infer_out_format
 from .fmt import FlowMatchingTransformerHIP, WindowSampler, draw_noise
@@ -166,17 +166,19 @@ def _resolve_out_dtype(out, out_dtype):
     return _frame_dtype(torch.float32 if out_dtype is None else out_dtype)
 
 
-def resolve_out_format(out, out_dtype, out_format):
+def resolve_out_format(out, out_dtype, out_format, matrix=None):
     """(dtype, format) of a hand-over call.  out_format: None | "rgb" ((T, R, R, 3) frames, fp32 or uint8 as _resolve_out_dtype
     decides) | "i420" ((T, 3R/2, R) uint8 planar YUV 4:2:0, host_models.rgb8_to_i420).  "i420" implies uint8: with
     out_dtype=torch.float32 or an fp32 `out` it is a ValueError.  A caller-supplied `out` fixes the format by its dimensions (a
-    3-d uint8 tensor is I420), and a stated format that contradicts it is a ValueError."""
+    3-d uint8 tensor is I420), and a stated format that contradicts it is a ValueError.  matrix: the colour matrix of I420 frames
+    (host_models.yuv_matrix_id); with RGB frames, fp32 or uint8, anything but None is a ValueError, as is an unknown name."""
     if out_format == "i420" and out is None and out_dtype is None:
         out_dtype = torch.uint8
     dtype = _resolve_out_dtype(out, out_dtype)
     fmt = infer_out_format(out, out_format, dtype)
     if out is not None and out.dim() != (3 if fmt == "i420" else 4):
         raise ValueError("out has %d dimensions, out_format %r takes %s" % (out.dim(), fmt, "(T, 3R/2, R)" if fmt == "i420" else "(T, R, R, 3)"))
+    host_models.yuv_matrix_for("out_format", matrix, fmt if fmt == "i420" else "%s RGB" % (dtype,), 0, 0)
     return dtype, fmt
 
 
@@ -220,8 +222,9 @@ class _FrameSink:
     staging buffer is shared by all of them (safe in stream order)."""
     name = "stream_to_host"
 
-    def __init__(self, hot, out_dtype, out_format):
+    def __init__(self, hot, out_dtype, out_format, matrix=None):
         self.hot, self.dtype, self.fmt = hot, out_dtype, out_format
+        self.matrix = hot.yuv_matrix(self.name, matrix, out_format)  # None for RGB frames
 
     def open(self, slots):
         shape = (self.hot.cfg.num_frames_for_clip,) + self.hot.dec.frame_shape(self.fmt)
@@ -231,7 +234,7 @@ class _FrameSink:
 
     def enqueue(self, slot, s_r_d, rows):
         n = rows.shape[0]
-        self.hot.dec.decode_into_host(s_r_d, rows, slot[:n], self.staging[:n], out_format=self.fmt)
+        self.hot.dec.decode_into_host(s_r_d, rows, slot[:n], self.staging[:n], out_format=self.fmt, matrix=self.matrix)
 
     def block(self, slot, f0, f1, ev, st):
         return FrameBlock(f0, f1, slot[:f1 - f0])
@@ -244,10 +247,12 @@ class _PasteSink:
     format and, for I420, the portrait's even sides are checked when the sink is made: at the call."""
     name = "stream_to_host_pasted"
 
-    def __init__(self, hot, place, feather, out_format=None, name=None):
+    def __init__(self, hot, place, feather, out_format=None, name=None, matrix=None):
         self.hot, self.place, self.feather = hot, place, feather
         self.name = name or self.name
         self.fmt = image.paste_format(self.name, out_format)
+        H, W = place.size  # "auto" goes by the size of the frames that leave: the portrait's
+        self.matrix = host_models.yuv_matrix_for(self.name, matrix, self.fmt, W, H) if matrix is not None else None
         if self.fmt == "i420":
             image.require_even_sides(self.name, *place.size)
         self.frame_shape = image.pasted_frame_shape(*place.size, self.fmt)
@@ -268,7 +273,8 @@ class _PasteSink:
         """decode_u8, the paste (and, for I420, the colour conversion in the same kernel), one non-blocking copy into `host`"""
         n = rows.shape[0]
         self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
-        image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n], out_format=self.fmt)
+        image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n], out_format=self.fmt,
+                                  matrix=self.matrix)
         host.copy_(self.pasted[:n], non_blocking=True)
 
     def enqueue(self, slot, s_r_d, rows):
@@ -461,6 +467,11 @@ class FloatHotPath:
             self.dec.set_feats(feats)
         return self.dec.decode_latent_into_processed_images(s_r, _rows(r_d, frame_range))
 
+    def yuv_matrix(self, what, matrix, out_format):
+        """The id of a `matrix` keyword for frames of the model's size (host_models.yuv_matrix_for: "auto" goes by that size; a
+        matrix with RGB frames is a ValueError); None stays None, which every layer below reads as BT.601 limited range."""
+        return None if matrix is None else host_models.yuv_matrix_for(what, matrix, out_format, self.size, self.size)
+
     def staging(self, n_frames, dtype=torch.float32, out_format="rgb"):
         """Device-side frame buffer of float_dec_frames_host[_u8|_i420], cached per clip length, dtype and format (786 MB for 250
         fp32 frames at 512 px, 197 MB as uint8, 98 MB as I420; sized for 288 GB).  The host side is NOT cached: callers get a fresh pinned tensor (torch's caching host allocator
@@ -474,14 +485,16 @@ class FloatHotPath:
         return cache[(shape, dtype, out_format)]
 
     @torch.no_grad()
-    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None, out_dtype=None, out_format=None):
+    def decode_to_host(self, s_r, r_d, feats=None, frame_range=None, out=None, out_dtype=None, out_format=None, matrix=None):
         """Frames of one clip (r_d (T,512)) into pinned host memory through float_dec_frames_host: the frames of batch i cross
         PCIe inside the launches of batch i+1.  Returns the host tensor (T,H,W,3); it is complete once the current stream has
         been synchronised (the callers that hand it to the user do that).  out_dtype: torch.float32 (default) or torch.uint8
         (8-bit frames quantised on the device, a quarter of the bytes); a caller-supplied `out` fixes the dtype, and an
         out_dtype that contradicts it is a ValueError.  out_format="i420": (T, 3H/2, W) uint8 planar YUV 4:2:0, converted on the
-        device (half the bytes of uint8 RGB; resolve_out_format has the rules)."""
-        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        device (half the bytes of uint8 RGB; resolve_out_format has the rules).  matrix: the colour matrix of I420 frames, as
+        host_models.yuv_matrix_id reads it (None = BT.601 limited range; "auto" by the model's size); a ValueError with RGB frames."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format, matrix)
+        matrix = self.yuv_matrix("decode_to_host", matrix, out_format)
         self.require_no_stream("decode_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
@@ -492,7 +505,7 @@ class FloatHotPath:
             out = torch.empty((n,) + self.dec.frame_shape(out_format), dtype=out_dtype, pin_memory=True)
         # (the frames by hipMemcpyAsync on a second stream instead of copy workgroups inside the next batch's launches: 121.4-122.1 vs
         # 105.7-106.8 ms per clip on the round-6 kernels, as in round 3 - decoder.decode_into_host(copy_stream=) keeps the form)
-        self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype, out_format), out_format=out_format)
+        self.dec.decode_into_host(s_r, rd, out, self.staging(n, out_dtype, out_format), out_format=out_format, matrix=matrix)
         self._hold_inflight(out, torch.cuda.current_stream(self.device))
         return out
 
@@ -517,20 +530,20 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                         noise=None, frame_range=None, out=None, return_rd=False, out_dtype=None, out_format=None):
+                         noise=None, frame_range=None, out=None, return_rd=False, out_dtype=None, out_format=None, matrix=None):
         """The product's hot path for one clip (B = 1): conditioning tensors in HBM -> frames in pinned host memory, the
         reference's destination (FLOAT.py:139,157-167).  This is what InferenceAgent.run_inference, FloatProcess and bench.py run.
-        out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
-        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        out_dtype, out_format, matrix: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format, matrix)
         self.require_no_stream("generate_to_host")
         if feats is not None:
             self.dec.set_feats(feats)
         r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)  # noise=None: drawn there from `seed`
-        host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype, out_format)
+        host = self.decode_to_host(s_r, r_d, None, frame_range, out, out_dtype, out_format, matrix)
         return (host, r_d) if return_rd else host
 
     def stream_to_host(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                       noise=None, out_dtype=None, out_format=None, slots=3):
+                       noise=None, out_dtype=None, out_format=None, slots=3, matrix=None):
         """generate_to_host for one clip (B = 1) as a generator: one FrameBlock(first, last, frames) per FMT window, in frame
         order, the same bytes as the whole-clip call (same kernels on the same operands; decode batching does not change a
         frame).  `frames` is a view of one of `slots` pinned ring buffers and is complete when it is yielded: the generator has
@@ -552,6 +565,7 @@ class FloatHotPath:
         size (the first stream of a process, or of a format) the pinned allocation - 472 MB for fp32 at 512 px and 3 slots - is
         part of the time to the first block; later streams get the cached blocks back.
 
+        matrix: the colour matrix of I420 frames, as in decode_to_host.
         slots >= 2, B = 1 and the resolve_out_format rules are checked here, at the call (ValueError); nothing is enqueued before the
         first next().  While the generator is open (first next() until exhaustion, close(), garbage collection or an exception
         thrown into it) sample, decode*, generate* and a second stream on this object raise RuntimeError.  Leaving early waits
@@ -560,12 +574,12 @@ class FloatHotPath:
         time table and the history rows of the workspace, and the only call that reads an unfinished job is
         float_fmt_sample_next, which is reachable only through the WindowSampler this generator drops - so the next sample /
         sample_begin starts clean."""
-        sink = _FrameSink(self, *resolve_out_format(None, out_dtype, out_format))
+        sink = _FrameSink(self, *resolve_out_format(None, out_dtype, out_format, matrix), matrix=matrix)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     def stream_to_host_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                              noise=None, place=None, feather=None, slots=3, out_format=None):
+                              noise=None, place=None, feather=None, slots=3, out_format=None, matrix=None):
         """stream_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: a generator of
         FrameBlock(first, last, frames), `frames` a (last - first, H, W, 3) uint8 view of a pinned ring slot, bitwise
         host_models.paste_rgb8(place.src8, the window's 8-bit crops, place.rect, feather).  place: a Placement (the portrait on
@@ -576,15 +590,16 @@ class FloatHotPath:
         out_format="i420" (default None = "rgb": the above): `frames` is a (last - first, 3H/2, W) uint8 view, bitwise
         host_models.paste_i420 of the same operands; float_img_paste_i420 pastes and converts in one kernel, and the device buffer
         of pasted frames, the pinned slots and the copy are 3HW/2 bytes per frame - half of the above.  H and W must be even:
-        a ValueError here, at the call."""
+        a ValueError here, at the call.  matrix: the colour matrix of I420 frames (host_models.yuv_matrix_id; "auto" goes by the
+        portrait's size); with RGB frames anything but None is a ValueError, also at the call."""
         place = _check_place("stream_to_host_pasted", place, self.device)
-        sink = _PasteSink(self, place, feather, out_format)
+        sink = _PasteSink(self, place, feather, out_format, matrix=matrix)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     @torch.no_grad()
     def generate_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                        place=None, feather=None, out=None, return_rd=False, out_format=None):
+                        place=None, feather=None, out=None, return_rd=False, out_format=None, matrix=None):
         """generate_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: the chain of the
         whole clip, then per group of num_frames_for_clip frames decode_u8, float_img_paste and one non-blocking copy into the
         pinned (T, H, W, 3) uint8 result - device memory stays at 50 crops and 50 pasted frames whatever T is.  The result is
@@ -592,9 +607,9 @@ class FloatHotPath:
         out_format="i420" (default None = "rgb": the above): the result is (T, 3H/2, W) uint8 planar YUV 4:2:0, bitwise
         host_models.paste_i420; float_img_paste_i420 pastes and converts in one kernel, and the device buffer of pasted frames, the
         result and the copies are 3HW/2 bytes per frame.  H and W must be even - a ValueError before anything is enqueued - and
-        an `out` of another shape than the format's is a ValueError."""
+        an `out` of another shape than the format's is a ValueError.  matrix: as in stream_to_host_pasted."""
         place = _check_place("generate_pasted", place, self.device)
-        sink = _PasteSink(self, place, feather, out_format, name="generate_pasted")
+        sink = _PasteSink(self, place, feather, out_format, name="generate_pasted", matrix=matrix)
         self.require_no_stream("generate_pasted")
         if feats is not None:
             self.dec.set_feats(feats)
@@ -793,14 +808,15 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_host_overlap(self, r_s, wa, we, s_r, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, noise=None,
-                                 out=None, mode="prio", return_rd=False, out_dtype=None, out_format=None, seed=15):
+                                 out=None, mode="prio", return_rd=False, out_dtype=None, out_format=None, seed=15, matrix=None):
         """generate_to_host with the two stages pipelined (FLOAT.py runs 209-253 then 113-169; here window k is decoded and
         handed to the host on a second stream while the chain samples window k + 1).  Same kernels on the same operands as
         the sequential order, per-window decode batches (50 frames = 32 + 18 instead of 250 = 7 x 32 + 26): frames bitwise
         equal to generate_to_host (decode batching does not change a frame, tests/test_dec_gpu.py).  FLOAT_AMD_OVERLAP
         selects it in InferenceAgent.infer_device; what it measures against the sequential order: DESIGN.md section 7.
-        out_dtype, out_format: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
-        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format)
+        out_dtype, out_format, matrix: as in decode_to_host (torch.uint8 = 8-bit frames, "i420" = planar YUV 4:2:0)."""
+        out_dtype, out_format = resolve_out_format(out, out_dtype, out_format, matrix)
+        matrix = self.yuv_matrix("generate_to_host_overlap", matrix, out_format)
         self.require_no_stream("generate_to_host_overlap")
         T = wa.shape[1]
         if noise is None:
@@ -811,7 +827,7 @@ class FloatHotPath:
         staging = self.staging(T, out_dtype, out_format)
         r_d = self._overlapped(mode, (r_s, wa, we, noise, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r,
                                lambda s_r_d, rows, f0, f1: self.dec.decode_into_host(s_r_d, rows, out[f0:f1], staging[f0:f1],
-                                                                                     out_format=out_format))
+                                                                                     out_format=out_format, matrix=matrix))
         self._hold_inflight(out, torch.cuda.current_stream(self.device))
         return (out, r_d) if return_rd else out
 

@@ -343,7 +343,7 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out=None,
-                     out_dtype=None, out_format=None):
+                     out_dtype=None, out_format=None, matrix=None):
         """Portrait and waveform in HBM -> (T,H,W,3) fp32 frames in [0,1] in pinned host memory: every operator of the path and
         the hand-over (frames of decode batch i leave inside the launches of batch i+1, float_dec_frames_host).  bench.py
         times exactly this call.  Like the reference, the grid size comes from opt.nfe (FLOAT.py:188).
@@ -352,25 +352,28 @@ class InferenceAgent:
         fixes the dtype; contradicting it is a ValueError.
         out_format="i420": (T, 3H/2, W) uint8 planar YUV 4:2:0 (BT.601 limited range, host_models.rgb8_to_i420 of the 8-bit
         frames, converted by the decoder's last kernel) - what a video encoder reads, half the bytes of uint8 RGB
-        (host_models.write_y4m pipes it).  It implies uint8; with out_dtype=torch.float32 or an fp32 `out` it is a ValueError."""
-        resolve_out_format(out, out_dtype, out_format)  # a contradiction is refused before anything runs
+        (host_models.write_y4m pipes it).  It implies uint8; with out_dtype=torch.float32 or an fp32 `out` it is a ValueError.
+        matrix: the colour matrix of I420 frames, as host_models.yuv_matrix_id reads it - None = BT.601 limited range, "bt709",
+        "bt601-full", "bt709-full", their ids 2 / 4 / 6, or "auto" (by the crop's size: BT.709 from 1280 x 720 up).  The bytes
+        are host_models.rgb8_to_i420(the 8-bit frames, matrix).  With fp32 or uint8 RGB frames anything but None is a ValueError."""
+        matrix = self._crop_matrix("infer_device", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
         c, noise = self._clip_inputs(s, a, emo, seed)
         ov = os.environ.get("FLOAT_AMD_OVERLAP", "")  # "prio" | "cu:N": decode window k beside the chain of window k + 1 (pipeline.py)
         verify = precision_policy(self._precision_checked) == "check"  # FLOAT_AMD_VERIFY, default off: nothing below changes
         if ov and ov != "0":
             host = self.G.generate_to_host_overlap(c["r_s"], c["wa"], c["we"], c["s_r"], self.opt.nfe, a_cfg_scale, r_cfg_scale,
                                                    e_cfg_scale, noise=noise, out=out, mode=ov, return_rd=verify,
-                                                   out_dtype=out_dtype, out_format=out_format)
+                                                   out_dtype=out_dtype, out_format=out_format, matrix=matrix)
         else:
             host = self.G.generate_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
                                            e_cfg_scale, noise=noise, out=out, return_rd=verify, out_dtype=out_dtype,
-                                           out_format=out_format)
+                                           out_format=out_format, matrix=matrix)
         host, r_d = host if verify else (host, None)
         torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
         self.G.release_host_inflight()
         bad = self.check_range("InferenceAgent.infer_device", allow_rebuild=True)
         if bad == "rebuilt":
-            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format)  # once more, in the wider types
+            return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format, matrix)  # once more, in the wider types
         if verify and not bad:  # a range failure has been reported already: the frames are wrong for a reason that is known
             # 8-bit output (RGB or I420): the staging buffer holds quantised frames, so the first k frames are decoded once more in the fp32
             # form by the same handle (a frame does not depend on its batch: bitwise what the fp32 staging buffer would hold)
@@ -380,14 +383,14 @@ class InferenceAgent:
                 frames_dev = self.G.dec.decode_latent_into_processed_images(c["s_r"], r_d[0, :k])
             if self.check_precision("InferenceAgent.infer_device", s, c, noise, r_d, a_cfg_scale, r_cfg_scale, e_cfg_scale,
                                     allow_rebuild=True, frames_dev=frames_dev) == "rebuilt":
-                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format)  # once more, in fp32
+                return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format, matrix)  # once more, in fp32
         return host
 
     def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,
-                      out_format=None, slots=3):
+                      out_format=None, slots=3, matrix=None):
         """The streaming sibling of infer_device: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
         frame order - concatenated, bit for bit the frames infer_device returns for the same inputs and seed, in both
-        FLOAT_AMD_NOISE modes and all three formats (out_dtype / out_format as there).  `frames` is a view of one of `slots`
+        FLOAT_AMD_NOISE modes and all three formats (out_dtype / out_format / matrix as there).  `frames` is a view of one of `slots`
         pinned buffers (FloatHotPath.stream_to_host has the contract): complete when yielded, OVERWRITTEN once the generator has
         been advanced again - copy what is to be kept.  Pinned memory is slots x 50 frames whatever the clip's length, and the
         first block arrives after one window instead of after the clip.  slots < 2 or contradicting formats raise ValueError here,
@@ -398,20 +401,28 @@ class InferenceAgent:
         early (close(), dropped, an exception in the consumer) is not reported, and its range counters are read and reset so
         that they are not held against the next clip.  FLOAT_AMD_VERIFY is NOT applied in a stream, and FLOAT_AMD_OVERLAP is ignored (the stream is
         windowed already, on one queue)."""
-        self._check_stream_call("stream_device", slots, out_dtype, out_format)
+        matrix = self._check_stream_call("stream_device", slots, out_dtype, out_format, matrix)
 
         def _stream_device(c, noise):
             return self.G.stream_to_host(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                         noise=noise, out_dtype=out_dtype, out_format=out_format, slots=int(slots))
+                                         noise=noise, out_dtype=out_dtype, out_format=out_format, slots=int(slots), matrix=matrix)
         return self._stream_clip("InferenceAgent.stream_device", s, a, emo, seed, _stream_device)
 
-    def _check_stream_call(self, what, slots, out_dtype=None, out_format=None):
-        """What a stream refuses at the call, before its generator exists (a generator's body runs at the first next())."""
+    def _crop_matrix(self, what, out, out_dtype, out_format, matrix):
+        """resolve_out_format's refusals, and the id of `matrix` for frames of the crop's size (None stays None: BT.601 limited range)"""
+        _, fmt = resolve_out_format(out, out_dtype, out_format, matrix)
+        size = self.opt.input_size
+        return None if matrix is None else host_models.yuv_matrix_for(what, matrix, fmt, size, size)
+
+    def _check_stream_call(self, what, slots, out_dtype=None, out_format=None, matrix=None):
+        """What a stream refuses at the call, before its generator exists (a generator's body runs at the first next()).  Returns
+        the id of `matrix` (None for None)."""
         if int(slots) < 2:
             raise ValueError("%s needs slots >= 2 (one block with the consumer, one in flight), got %r" % (what, slots))
-        resolve_out_format(None, out_dtype, out_format)
+        matrix = self._crop_matrix(what, None, out_dtype, out_format, matrix)
         if self.G is not None:
             self.G.require_no_stream(what)
+        return matrix
 
     def _stream_clip(self, where, s, a, emo, seed, start):
         """The generator behind every stream of the agent: the clip's inputs, the blocks of start(conditions, noise) - a
@@ -430,18 +441,18 @@ class InferenceAgent:
         self.check_range(where)
 
     def stream_inference(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False,
-                         seed=25, out_dtype=None, out_format=None, slots=3):
+                         seed=25, out_dtype=None, out_format=None, slots=3, matrix=None):
         """The streaming sibling of run_inference: host inputs as there, blocks as stream_device yields them.  There is no
         `nfe` argument: the grid size comes from opt.nfe (run_inference keeps the reference's argument and ignores it)."""
-        self._check_stream_call("stream_inference", slots, out_dtype, out_format)
+        matrix = self._check_stream_call("stream_inference", slots, out_dtype, out_format, matrix)
         return self._stream_inference(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, out_dtype,
-                                      out_format, int(slots))
+                                      out_format, int(slots), matrix)
 
     def _stream_inference(self, ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, out_dtype,
-                          out_format, slots):
+                          out_format, slots, matrix=None):
         with torch.no_grad():
             s, a = self.host_inputs(ref_img, ref_audio, no_crop)
-        yield from self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots)
+        yield from self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_dtype, out_format, slots, matrix)
 
     @torch.no_grad()
     def infer_device_jpeg(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, quality=90, restart=None):
@@ -510,19 +521,22 @@ class InferenceAgent:
             return w.frames
 
     # ------------------------------------------------------------------ paste back: the frames in the user's portrait
-    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None, pad=None):
+    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None, pad=None, matrix=None):
         """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take
         (pad="edge": none) or a pad that is neither None nor "edge"; with
-        out_format="i420", a portrait with an odd side; an out_format that is none of None, "rgb", "i420"."""
+        out_format="i420", a portrait with an odd side; an out_format that is none of None, "rgb", "i420"; a `matrix` with RGB
+        frames or one host_models.yuv_matrix_id does not know.  Returns the id of `matrix` ("auto": by the portrait's size), None for None."""
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         if jpeg_out:
             require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]), pad)
-        if paste_format(what, out_format) == "i420":
+        fmt = paste_format(what, out_format)
+        if fmt == "i420":
             require_even_sides(what, int(img.shape[0]), int(img.shape[1]))
+        return None if matrix is None else host_models.yuv_matrix_for(what, matrix, fmt, int(img.shape[1]), int(img.shape[0]))
 
     @torch.no_grad()
     def infer_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                     feather=None, out=None, out_format=None):
+                     feather=None, out=None, out_format=None, matrix=None):
         """run_inference whose frames are the user's portrait with the generated face pasted back: (T, H, W, 3) uint8 in pinned host
         memory at the portrait's own size, bitwise host_models.paste_rgb8(place.src8, infer_device(s, a, out_dtype=torch.uint8),
         place.rect, feather) with (s, a, place) = host_inputs_placed(ref_img, ref_audio, no_crop).  The 8-bit crops never leave
@@ -534,19 +548,22 @@ class InferenceAgent:
         out_format="i420" (default None = "rgb": the above): (T, 3H/2, W) uint8 planar YUV 4:2:0 in pinned host memory (BT.601
         limited range), bitwise host_models.rgb8_to_i420 of the RGB result = host_models.paste_i420(...): paste and conversion are
         one kernel and half the bytes cross PCIe.  Any even size is taken (1920 x 1080); a portrait with an odd side is a
-        ValueError at this call, before anything runs - nothing is padded or cropped.  FLOAT_AMD_RANGE applies as above."""
-        self._paste_call("infer_pasted", ref_img, out_format=out_format)
+        ValueError at this call, before anything runs - nothing is padded or cropped.  FLOAT_AMD_RANGE applies as above.
+        matrix: the colour matrix of I420 frames, as in infer_device; "auto" goes by the portrait's size (BT.709 limited range
+        when W >= 1280 or H > 576 - what players assume for untagged video of that size).  A ValueError with RGB frames."""
+        matrix = self._paste_call("infer_pasted", ref_img, out_format=out_format, matrix=matrix)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             host = self.G.generate_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                          noise=noise, place=place, feather=feather, out=out, out_format=out_format)
+                                          noise=noise, place=place, feather=feather, out=out, out_format=out_format,
+                                          matrix=matrix)
             torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
             if self.check_range("InferenceAgent.infer_pasted", allow_rebuild=True) != "rebuilt":
                 return host  # otherwise once more, in the wider types
 
     def stream_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                      feather=None, slots=3, out_format=None):
+                      feather=None, slots=3, out_format=None, matrix=None):
         """The streaming sibling of infer_pasted: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
         frame order - concatenated, the frames infer_pasted returns for the same inputs and seed.  The ring rules are
         stream_device's: `frames` is a (last - first, H, W, 3) uint8 view of one of `slots` pinned buffers, complete when yielded,
@@ -554,42 +571,58 @@ class InferenceAgent:
         every other producer on this agent raises RuntimeError.  FLOAT_AMD_RANGE is applied once after the last block (auto acts
         as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored.
         out_format="i420": `frames` is a (last - first, 3H/2, W) uint8 view, the frames of infer_pasted(out_format="i420"); the
-        pinned slots are half the size.  A portrait with an odd side raises ValueError here, at the call."""
+        pinned slots are half the size.  A portrait with an odd side raises ValueError here, at the call.  matrix: as in
+        infer_pasted."""
         self._check_stream_call("stream_pasted", slots)
-        self._paste_call("stream_pasted", ref_img, out_format=out_format)
+        matrix = self._paste_call("stream_pasted", ref_img, out_format=out_format, matrix=matrix)
 
         def _stream_pasted(c, noise, place):
             return self.G.stream_to_host_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
                                                 e_cfg_scale, noise=noise, place=place, feather=feather, slots=int(slots),
-                                                out_format=out_format)
+                                                out_format=out_format, matrix=matrix)
         return self._stream_placed("InferenceAgent.stream_pasted", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted)
 
     def write_y4m(self, path_or_file, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False,
                   seed=25, fps=None, paste_back=False, feather=None, slots=3):
         """A clip for an encoder: host_inputs, a stream of I420 blocks, and host_models.Y4MWriter on `path_or_file` - a path, or an
         object with write(), which may be a non-seekable pipe to ffmpeg's or x264's stdin (the header goes out first and nothing
-        is patched afterwards).  The frames are yuv420p, BT.601 limited range: the consumer converts no colours.  Y4M carries
+        is patched afterwards).  The frames are yuv420p, BT.601 limited range (write_y4m_matrix is this call with a colour matrix
+        to choose): the consumer converts no colours.  Y4M carries
         NO AUDIO: the clip's sound has to be given to the encoder separately (write_video writes a file with an audio track).
         fps defaults to opt.fps.  Returns the number of frames written.
         paste_back=False: stream_device(out_format="i420") at the model's size.
         paste_back=True: stream_pasted(out_format="i420", feather=feather) - the user's portrait with the generated face pasted
         back, at the portrait's size, which must have even sides (ValueError otherwise, before anything runs or a file is opened).
         Pinned memory is `slots` x 50 frames of 1.5 bytes per pixel whatever the clip's length."""
+        return self.write_y4m_matrix(path_or_file, ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, fps,
+                                     paste_back, feather, slots)
+
+    def write_y4m_matrix(self, path_or_file, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E",
+                         no_crop=False, seed=25, fps=None, paste_back=False, feather=None, slots=3, matrix=None):
+        """write_y4m with the colour matrix of the frames to choose.  matrix: as in infer_device / infer_pasted - None = BT.601
+        limited range (then this is write_y4m, byte for byte), "bt709", "bt601-full", "bt709-full", their ids, or "auto": by the
+        size of the frames that leave, the model's with paste_back=False and the portrait's with paste_back=True (BT.709 limited
+        range when W >= 1280 or H > 576, what players assume for untagged video).  It is resolved once, before anything runs or a
+        file is opened, and the one id goes to the producer and to the writer, so the tag cannot disagree with the samples: full
+        range is written as XCOLORRANGE=FULL.  Y4M has no tag for the matrix itself: host_models.yuv_ffmpeg_args(matrix) are the
+        arguments that state it to ffmpeg.  (A method of its own because write_y4m's parameter list is held as it is.)"""
         o = self.opt
         fps = o.fps if fps is None else fps
         if paste_back:
             img = ref_img[0] if ref_img.dim() == 4 else ref_img
             height, width = int(img.shape[0]), int(img.shape[1])
+            matrix = self._paste_call("write_y4m", ref_img, out_format="i420", matrix=matrix)
             blocks = self.stream_pasted(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, slots,
-                                        out_format="i420")
+                                        out_format="i420", matrix=matrix)
         else:
             height = width = o.input_size
-            self._check_stream_call("write_y4m", slots)
+            matrix = self._check_stream_call("write_y4m", slots, out_format="i420", matrix=matrix)
             with torch.no_grad():
                 s, a = self.host_inputs(ref_img, ref_audio, no_crop)
-            blocks = self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format="i420", slots=slots)
+            blocks = self.stream_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format="i420", slots=slots,
+                                        matrix=matrix)
         try:
-            with host_models.Y4MWriter(path_or_file, width, height, fps) as w:
+            with host_models.Y4MWriter(path_or_file, width, height, fps, matrix) as w:
                 for blk in blocks:
                     w.write(blk.frames)
                 return w.frames
@@ -731,15 +764,15 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_device_batch(self, items, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seeds=None,
-                           out_dtype=None, out_format=None):
+                           out_dtype=None, out_format=None, matrix=None):
         """B clips through one stacked FMT chain (every weight is read once per evaluation for all of them), then decoded one
         after the other.  Clips of equal length run float_fmt_sample_batch; clips of different lengths run its ragged sibling
         (FlowMatchingTransformerHIP.sample_ragged: a clip leaves the stack after its last window).  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
         item (FloatProcess uses seed + i, nodes.py:189-209) - each item keeps its own noise stream, so item i is what
         infer_device gives for it alone (bit for bit where the GEMM tilings coincide, within the fp16 tolerance otherwise).
         Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device; out_format="i420":
-        (T,3H/2,W) uint8 planar YUV 4:2:0 as there."""
-        resolve_out_format(None, out_dtype, out_format)  # a contradiction is refused before anything runs
+        (T,3H/2,W) uint8 planar YUV 4:2:0 as there, with `matrix` as there."""
+        matrix = self._crop_matrix("infer_device_batch", None, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
         self.to_target()
         B = len(items)
         seeds = list(seeds) if seeds is not None else [self.opt.seed] * B
@@ -770,7 +803,7 @@ class InferenceAgent:
         for i in range(B):
             # decodes queue back to back: the last frames of item i cross PCIe inside the launches of item i + 1
             self.G.dec.set_feats16(feats[i], self.enc.dtype)
-            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i], out_dtype=out_dtype, out_format=out_format))
+            out.append(self.G.decode_to_host(conds[i]["s_r"], r_d[i], out_dtype=out_dtype, out_format=out_format, matrix=matrix))
         torch.cuda.current_stream(self.rank).synchronize()
         self.G.release_host_inflight()
         self.check_range("InferenceAgent.infer_device_batch")
@@ -778,9 +811,10 @@ class InferenceAgent:
 
     @torch.no_grad()
     def run_inference(self, res_video_path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0,
-                      emo="S2E", nfe=10, no_crop=False, seed=25, out_format=None):
+                      emo="S2E", nfe=10, no_crop=False, seed=25, out_format=None, matrix=None):
         """Reference signature (generate.py:154-173).  Returns (T,H,W,3) fp32 in [0,1] on the CPU (pinned); out_format="i420":
-        (T,3H/2,W) uint8 planar YUV 4:2:0 as in infer_device.
+        (T,3H/2,W) uint8 planar YUV 4:2:0 as in infer_device, `matrix` its colour matrix as there.
         Like the reference, the grid size comes from opt.nfe, not from the `nfe` argument (FLOAT.py:188)."""
+        self._crop_matrix("run_inference", None, None, out_format, matrix)  # refused before the inputs are prepared
         s, a = self.host_inputs(ref_img, ref_audio, no_crop)
-        return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format=out_format)
+        return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out_format=out_format, matrix=matrix)

@@ -280,17 +280,30 @@ int float_dec_frames_host_u8(float_dec_t* h, const float* s_r, const float* r_d,
 
 /* Planar YUV 4:2:0 frames (I420), converted on the device from the 8-bit samples R8, G8, B8 that float_dec_frames_u8 stores.
  * One frame is 3 * size * size / 2 bytes: the Y plane size x size, then U and V at size/2 x size/2 each, row-major, contiguous.
- * `matrix` selects the conversion; FLOAT_DEC_MATRIX_BT601_LIMITED (0) is the only one, anything else is FLOAT_E_INVALID.  For it,
- * in int32 with >> an arithmetic shift (floor):
- *   Y = ((66 R8 + 129 G8 + 25 B8 + 128) >> 8) + 16                                    per pixel, in [16, 235]
+ * `matrix` selects the conversion.  All four have one form, in int32 with >> an arithmetic shift (floor):
+ *   Y  = ((cr R8 + cg G8 + cb B8 + rnd) >> 8) + off                                   per pixel
  *   Mc = (c00 + c01 + c10 + c11 + 2) >> 2                                             per 2 x 2 block and channel c
- *   U = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128,  V = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128      in [16, 240]
+ *   U, V = ((cr MR + cg MG + cb MB + rnd) >> 8) + off                                 per block
+ * with the rows (cr, cg, cb, rnd, off) of
+ *   id  name                                Y                     U                          V
+ *   0   FLOAT_DEC_MATRIX_BT601_LIMITED      66, 129, 25, 128, 16  -38, -74, 112, 128, 128    112,  -94, -18, 128, 128
+ *   2   FLOAT_DEC_MATRIX_BT709_LIMITED      47, 157, 16, 128, 16  -26, -86, 112, 128, 128    112, -102, -10, 128, 128
+ *   4   FLOAT_DEC_MATRIX_BT601_FULL         77, 150, 29, 128, 0   -43, -85, 128, 127, 128    128, -107, -21, 127, 128
+ *   6   FLOAT_DEC_MATRIX_BT709_FULL         54, 183, 19, 128, 0   -29, -99, 128, 127, 128    128, -116, -12, 127, 128
+ * The id is a flag word: bit 1 = BT.709, bit 2 = full range; bit 0 and every higher bit must be 0, so 1, 3, 5, 7, 8, -1 are
+ * FLOAT_E_INVALID, refused before anything else is looked at.  Every Y row sums to 220 (limited) or 256 (full) and every chroma
+ * row to 0: a grey sample gives exactly U = V = 128.  No clamp is needed: limited range gives Y in [16, 235] and U, V in
+ * [16, 240], full range exactly [0, 255] on every plane (the chroma rounding term of 127 keeps pure blue and red at 255).  Each
+ * plane is within 1.17 levels of the float64 formulas of BT.601 / BT.709 (Kr, Kb = 0.299, 0.114 / 0.2126, 0.0722).  Id 0 is
+ *   Y = ((66 R8 + 129 G8 + 25 B8 + 128) >> 8) + 16,  U = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128,
+ *   V = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128
  * (chroma sited at the block centre, Y4M's C420jpeg).  The definition starts from the 8-bit samples, so the bytes are those a
  * caller gets by converting float_dec_frames_u8's frames this way, whichever kernel forms them.  `out` must be 4-byte aligned;
  * `host`, `copy_stream` and what synchronising `stream` means follow float_dec_frames_host_u8's contract word for word (pinned and
  * 16-byte aligned: copy workgroups; anything else: one hipMemcpyAsync behind each batch).  Calls of all three formats may
  * alternate on one handle. */
 enum { FLOAT_DEC_MATRIX_BT601_LIMITED = 0 };
+enum { FLOAT_DEC_MATRIX_BT709_LIMITED = 2, FLOAT_DEC_MATRIX_BT601_FULL = 4, FLOAT_DEC_MATRIX_BT709_FULL = 6 };
 int float_dec_frames_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix,
                           uint8_t* out, void* stream);
 int float_dec_frames_host_i420(float_dec_t* h, const float* s_r, const float* r_d, int32_t n_frames, int32_t matrix,
@@ -463,6 +476,9 @@ int float_aud_debug(float_aud_t* h, int32_t what, const float* in, int32_t Tn, f
 /* ---------------------------------------------------------------- misc ------------ */
 int float_hip_abi_version(void);
 const char* float_last_error(void);
+/* The colour matrix `matrix` of the I420 calls as the kernels use it: table = Y, U, V rows of (cr, cg, cb, rnd, off), 15 values
+ * (float_dec_frames_i420 above states them).  FLOAT_E_INVALID for an id that is not 0, 2, 4 or 6.  Host only: no HIP call. */
+int float_yuv_matrix(int32_t matrix, int32_t table[15]);
 /* A HIP stream restricted to CUs [cu_begin, cu_end) (hipExtStreamCreateWithCUMask).  Used to run the FMT
  * chain and the decoder concurrently on disjoint CU sets (pipeline.generate(overlap="cu")). */
 int float_stream_create_cu_range(int32_t cu_begin, int32_t cu_end, void** stream_out);
@@ -603,8 +619,9 @@ int float_img_paste(const uint8_t* src8, int32_t src_h, int32_t src_w, const uin
  *   Mc = (c00 + c01 + c10 + c11 + 2) >> 2                        per 2 x 2 block and channel c of the PASTED samples
  *   U  = ((-38 MR - 74 MG + 112 MB + 128) >> 8) + 128,  V = ((112 MR - 94 MG - 18 MB + 128) >> 8) + 128
  * in int32 with >> the arithmetic shift.  Chroma is not blended: a block that straddles the box edge or the feather averages
- * pasted and source pixels.  `matrix` selects the conversion; FLOAT_IMG_MATRIX_BT601_LIMITED (0, the matrix of
- * float_dec_frames_i420) is the only one, anything else is FLOAT_E_INVALID.
+ * pasted and source pixels.  `matrix` selects the conversion: the formulas above are FLOAT_IMG_MATRIX_BT601_LIMITED (0); 2, 4 and
+ * 6 take the rows of float_dec_frames_i420's table (BT.709 limited, BT.601 full, BT.709 full range) in the same arithmetic, and
+ * any other value is FLOAT_E_INVALID.
  * Limits: those of float_img_paste, and src_h, src_w even and >= 2; any even size is taken (1920 x 1080).  The pointers are DEVICE
  * pointers of any alignment; out must not overlap the inputs.  With src_w % 4 == 0 and out 4-byte aligned the kernel stores dwords
  * of Y and 16-bit pairs of U and V, otherwise bytes; the bytes stored are the same.  A frame is 3 src_h src_w / 2 bytes; frame
@@ -613,6 +630,7 @@ int float_img_paste(const uint8_t* src8, int32_t src_h, int32_t src_w, const uin
  * nothing, two calls give equal bytes.  An argument outside these rules returns FLOAT_E_INVALID, with a message naming the
  * function and the argument, before any HIP call. */
 enum { FLOAT_IMG_MATRIX_BT601_LIMITED = 0 };
+enum { FLOAT_IMG_MATRIX_BT709_LIMITED = 2, FLOAT_IMG_MATRIX_BT601_FULL = 4, FLOAT_IMG_MATRIX_BT709_FULL = 6 };
 int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* frames8, int32_t n_frames, int32_t fr_h,
                          int32_t fr_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t feather, int32_t matrix,
                          uint8_t* out, void* stream);

@@ -16,7 +16,11 @@ device events, LAUNCH_REPS (default 30) times after 3, the RGB and the I420 laun
 50 H W 3 (I420: 50 H W 3 / 2) written, 50 H W 3 of the source and 50 x 512 x 512 x 3 of the frames read - over the copy bandwidth
 float_probe_peaks measures in this process (bytes read + bytes written per second).  Prints one JSON line: median, min, max and
 spread (max - min) per form, ms; per launch its median, its GB/s and its fraction of the copy peak.  Run from the repository root.
+--matrix M (2 | 4 | 6 or a name host_models.yuv_matrix_id knows): one more form, i420_m = infer_pasted(out_format="i420", matrix=M),
+takes turns with the others, and one more launch, i420_m, with the paste launches; each reports `minus_id0_ms` against i420 and
+`ok_vs_id0` = its median does not exceed i420's by more than i420's own spread.
 Environment: REPS, WARMUP, LAUNCH_REPS, QUALITY."""
+import argparse
 import importlib
 import json
 import os
@@ -32,6 +36,10 @@ from tests.util import load_pkg  # noqa: E402
 
 pkg = load_pkg()
 hm = pkg.host_models
+ap = argparse.ArgumentParser()
+ap.add_argument("--matrix", default=None, help="a second colour matrix to interleave with id 0 (2, 4, 6 or a name)")
+MATRIX = ap.parse_args().matrix
+MATRIX = None if MATRIX is None else hm.yuv_matrix_id(int(MATRIX) if MATRIX.lstrip("-").isdigit() else MATRIX)
 REPS, WARMUP, QUALITY = int(os.environ.get("REPS", "10")), int(os.environ.get("WARMUP", "2")), int(os.environ.get("QUALITY", "90"))
 LAUNCH_REPS = int(os.environ.get("LAUNCH_REPS", "30"))
 SIZE, SECONDS, NFE, MAX_FRAMES = 512, 10.0, 51, 32
@@ -61,7 +69,7 @@ parts = dict(enc=pkg.weights.synth_encoder_state(SIZE, seed=1), dec=pkg.weights.
              fmt=pkg.weights.synth_fmt_state(cfg, seed=1), audio_encoder=(pkg.weights.synth_audio_state(acfg, seed=1), acfg))
 agent = gen.InferenceAgent(opt, parts, dev, max_frames=MAX_FRAMES, use_graph=2)
 audio = {"waveform": pkg.weights.synth_waveform(SECONDS, seed=1).reshape(1, 1, -1).cpu(), "sample_rate": 16000}
-FORMS = ("u8", "pasted", "i420", "jpeg")
+FORMS = ("u8", "pasted", "i420", "jpeg") + (("i420_m",) if MATRIX is not None else ())
 KW = dict(emo="neutral", seed=15)
 last = {}
 
@@ -74,6 +82,8 @@ def run(form, img, pad=None):
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, **KW)
     elif form == "i420":
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", **KW)
+    elif form == "i420_m":
+        last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", matrix=MATRIX, **KW)
     else:
         last[form] = agent.infer_pasted_jpeg(img, audio, 2.0, 1.0, 1.0, no_crop=False, quality=QUALITY, pad=pad, **KW)
 
@@ -92,18 +102,26 @@ def stats(v):
     return dict(median=round(statistics.median(v), 3), min=round(min(v), 3), max=round(max(v), 3), spread=round(max(v) - min(v), 3))
 
 
+def vs_id0(out):
+    out["i420_m"]["minus_id0_ms"] = round(out["i420_m"]["median"] - out["i420"]["median"], 3)
+    out["i420_m"]["ok_vs_id0"] = out["i420_m"]["median"] <= out["i420"]["median"] + out["i420"]["spread"]
+
+
 def launch_alone(place, peaks):
     """{"rgb": ..., "i420": ...}: float_img_paste and float_img_paste_i420 on the same 50 crops, taking turns"""
     n, (H, W) = 50, place.size
     crops = torch.randint(0, 256, (n, SIZE, SIZE, 3), dtype=torch.uint8, device=dev)
     feather = hm.default_feather(place.rect)
     outs = {"rgb": torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev), "i420": torch.empty(n, 3 * H // 2, W, dtype=torch.uint8, device=dev)}
+    if MATRIX is not None:
+        outs["i420_m"] = torch.empty(n, 3 * H // 2, W, dtype=torch.uint8, device=dev)
     ms = {fmt: [] for fmt in outs}
     for i in range(3 + LAUNCH_REPS):
         for fmt, out in outs.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out, out_format=fmt)
+            kw = dict(out_format="i420", matrix=MATRIX) if fmt == "i420_m" else dict(out_format=fmt)
+            pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out, **kw)
             e1.record()
             e1.synchronize()
             if i >= 3:
@@ -115,14 +133,17 @@ def launch_alone(place, peaks):
         r = stats(ms[fmt])
         r.update(frames=n, bytes_moved=moved, GBps=round(moved / 1e9 / (r["median"] * 1e-3), 1),
                  fraction_of_copy_peak=round(moved / 1e9 / (r["median"] * 1e-3) / peaks["hbm_copy_GBps"], 3),
-                 equals_definition=bool(torch.equal(out[:1].cpu(), want if fmt == "rgb" else hm.rgb8_to_i420(want))))
+                 equals_definition=bool(torch.equal(out[:1].cpu(), want if fmt == "rgb" else
+                                                    hm.rgb8_to_i420(want, MATRIX if fmt == "i420_m" else None))))
         res[fmt] = r
     res["i420_minus_rgb_ms"] = round(res["i420"]["median"] - res["rgb"]["median"], 3)
+    if MATRIX is not None:
+        vs_id0(res)
     return res
 
 
 peaks = pkg.native.probe_peaks(dev)
-res = dict(probe="pastebench", size=SIZE, frames=250, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP, quality=QUALITY, peaks=peaks)
+res = dict(probe="pastebench", matrix=MATRIX, size=SIZE, frames=250, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP, quality=QUALITY, peaks=peaks)
 for H, W in ((1024, 1024), (1088, 1920)):
     img = torch.from_numpy(np.random.RandomState(H).rand(1, H, W, 3).astype("float32"))
     for _ in range(WARMUP):
@@ -137,6 +158,8 @@ for H, W in ((1024, 1024), (1088, 1920)):
     out["i420"]["minus_u8_ms"] = round(out["i420"]["median"] - out["u8"]["median"], 3)
     out["i420"]["minus_pasted_ms"] = round(out["i420"]["median"] - out["pasted"]["median"], 3)
     out["jpeg"]["minus_u8_ms"] = round(out["jpeg"]["median"] - out["u8"]["median"], 3)
+    if MATRIX is not None:
+        vs_id0(out)
     _, _, place = agent.host_inputs_placed(img, audio, no_crop=False)
     out["rect"] = list(place.rect)
     out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), i420=last["i420"].numel(), jpeg=last["jpeg"].nbytes)

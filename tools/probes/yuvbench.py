@@ -11,7 +11,12 @@ Every destination of the decode and clip cases is allocated (pinned) before the 
 product's own tensors.  Each call is timed with device events around it, REPS (default 20) repetitions per form after WARMUP
 (default 3).  Prints one JSON line: median, min, max and spread (max - min) per form and case, ms.  `ok` = an I420 median does
 not exceed the u8 median by more than the u8 repetitions' own spread.  Run from the repository root.
+--matrix M (2 | 4 | 6 or a name host_models.yuv_matrix_id knows): two more forms, i420_fused_m and i420_conv_m, the same calls with
+matrix=M, take turns with the others; each reports `minus_id0_ms` against its id-0 sibling and `ok_vs_id0` = its median does not
+exceed the sibling's by more than the sibling's own spread, and the clip of the last repetition is compared with
+rgb8_to_i420(u8, M).
 Environment: REPS, WARMUP, B (default 16; 0 skips the batch case)."""
+import argparse
 import importlib
 import json
 import os
@@ -25,6 +30,10 @@ sys.path.insert(0, ".")
 from tests.util import load_pkg  # noqa: E402
 
 pkg = load_pkg()
+ap = argparse.ArgumentParser()
+ap.add_argument("--matrix", default=None, help="a second colour matrix to interleave with id 0 (2, 4, 6 or a name)")
+MATRIX = ap.parse_args().matrix
+MATRIX = None if MATRIX is None else pkg.host_models.yuv_matrix_id(int(MATRIX) if MATRIX.lstrip("-").isdigit() else MATRIX)
 REPS, WARMUP, B = int(os.environ.get("REPS", "20")), int(os.environ.get("WARMUP", "3")), int(os.environ.get("B", "16"))
 SIZE, SECONDS, NFE, MAX_FRAMES = 512, 10.0, 51, 32
 dev = "cuda:0"
@@ -51,8 +60,11 @@ def build(fused):
 
 
 agents = dict(fused=build(True), conv=build(False))
-# form -> (agent, out_dtype, out_format)
-FORMS = dict(u8=(agents["fused"], torch.uint8, None), i420_fused=(agents["fused"], None, "i420"), i420_conv=(agents["conv"], None, "i420"))
+# form -> (agent, out_dtype, out_format, matrix)
+FORMS = dict(u8=(agents["fused"], torch.uint8, None, None), i420_fused=(agents["fused"], None, "i420", None),
+             i420_conv=(agents["conv"], None, "i420", None))
+if MATRIX is not None:
+    FORMS.update(i420_fused_m=(agents["fused"], None, "i420", MATRIX), i420_conv_m=(agents["conv"], None, "i420", MATRIX))
 
 
 def portrait(seed):
@@ -67,25 +79,29 @@ s_r, r_d = torch.randn(1, 512, generator=g).to(dev), (torch.randn(T, 512, genera
 for a in agents.values():
     a.enc.encode_image_into_latent(img, want_feats=False)
     a.enc.hand_feats_to(a.G.dec)
-SHAPES = dict(u8=(T, SIZE, SIZE, 3), i420_fused=(T, 3 * SIZE // 2, SIZE), i420_conv=(T, 3 * SIZE // 2, SIZE))
+SHAPES = {f: (T, SIZE, SIZE, 3) if f == "u8" else (T, 3 * SIZE // 2, SIZE) for f in FORMS}
 dst = {(c, f): torch.empty(SHAPES[f], dtype=torch.uint8).pin_memory() for c in ("decode", "clip") for f in FORMS}
 keep = {}
 
 
+def mkw(m):
+    return {} if m is None else dict(matrix=m)
+
+
 def decode(form):
-    agent, dt, fmt = FORMS[form]
-    agent.G.decode_to_host(s_r, r_d, out=dst["decode", form], out_dtype=dt, out_format=fmt)
+    agent, dt, fmt, m = FORMS[form]
+    agent.G.decode_to_host(s_r, r_d, out=dst["decode", form], out_dtype=dt, out_format=fmt, **mkw(m))
 
 
 def clip(form):
-    agent, dt, fmt = FORMS[form]
-    agent.infer_device(img, wav, 2.0, 1.0, 1.0, emo="neutral", seed=15, out=dst["clip", form], out_dtype=dt, out_format=fmt)
+    agent, dt, fmt, m = FORMS[form]
+    agent.infer_device(img, wav, 2.0, 1.0, 1.0, emo="neutral", seed=15, out=dst["clip", form], out_dtype=dt, out_format=fmt, **mkw(m))
 
 
 def batch(form):
-    agent, dt, fmt = FORMS[form]
+    agent, dt, fmt, m = FORMS[form]
     keep["b"] = None  # the previous result is released first, as a caller that consumed it would have
-    keep["b"] = agent.infer_device_batch(items, 2.0, 1.0, 1.0, "neutral", [15 + i for i in range(B)], out_dtype=dt, out_format=fmt)
+    keep["b"] = agent.infer_device_batch(items, 2.0, 1.0, 1.0, "neutral", [15 + i for i in range(B)], out_dtype=dt, out_format=fmt, **mkw(m))
 
 
 def ev_ms(f, form):
@@ -111,10 +127,14 @@ def case(f, per=1):
     for form in ("i420_fused", "i420_conv"):
         out[form]["minus_u8_ms"] = round(out[form]["median"] - out["u8"]["median"], 3)
         out[form]["ok"] = out[form]["median"] <= out["u8"]["median"] + out["u8"]["spread"]
+        if MATRIX is not None:
+            a, b = out[form + "_m"], out[form]
+            a["minus_id0_ms"] = round(a["median"] - b["median"], 3)
+            a["ok_vs_id0"] = a["median"] <= b["median"] + b["spread"]
     return out
 
 
-res = dict(probe="yuvbench", size=SIZE, frames=T, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP,
+res = dict(probe="yuvbench", matrix=MATRIX, size=SIZE, frames=T, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP,
            staging_mb=dict(u8=round(T * SIZE * SIZE * 3 / 1e6, 1), i420=round(T * SIZE * SIZE * 3 / 2 / 1e6, 1)))
 res["decode_250"] = case(decode)
 res["clip"] = case(clip)
@@ -125,5 +145,9 @@ if B > 0:
 want = pkg.host_models.rgb8_to_i420(dst["clip", "u8"])
 res["i420_equals_converted_u8"] = dict(fused=bool(torch.equal(dst["clip", "i420_fused"], want)),
                                        conv=bool(torch.equal(dst["clip", "i420_conv"], want)))
+if MATRIX is not None:
+    want_m = pkg.host_models.rgb8_to_i420(dst["clip", "u8"], MATRIX)
+    res["i420_m_equals_converted_u8"] = dict(fused=bool(torch.equal(dst["clip", "i420_fused_m"], want_m)),
+                                             conv=bool(torch.equal(dst["clip", "i420_conv_m"], want_m)))
 res["pinned_bytes_per_250_frames"] = dict(u8=dst["clip", "u8"].numel(), i420=dst["clip", "i420_fused"].numel())
 print(json.dumps(res))
