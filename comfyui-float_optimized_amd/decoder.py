@@ -153,6 +153,14 @@ class SynthesisHIP:
         from .jpeg import encode_jpeg_device
         return encode_jpeg_device(self.decode_u8(s_r, r_d, s_r_feats), quality, restart, out)
 
+    @torch.no_grad()
+    def decode_png(self, s_r, r_d, band=None, s_r_feats=None, out=None):
+        """decode_u8, then float_png_encode on the 8-bit frames: (data, offsets, crcs) on the GPU as png.encode_png_device returns
+        them - frame i is data[offsets[i]:offsets[i + 1]], a complete PNG file that decodes to decode_u8(...)[i] bit for bit,
+        bitwise host_models.png_encode_rgb8(decode_u8(...), band)[i].  Reads offsets[-1] on the host (one synchronisation)."""
+        from .png import encode_png_device
+        return encode_png_device(self.decode_u8(s_r, r_d, s_r_feats), band, out)
+
     def frame_shape(self, out_format="rgb"):
         """Shape of one frame as the hand-over calls store it: (size, size, 3), or (3 * size / 2, size) for "i420"."""
         return (3 * self.size // 2, self.size) if out_format == "i420" else (self.size, self.size, 3)

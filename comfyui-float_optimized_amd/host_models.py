@@ -15,6 +15,8 @@ this package).  What is left is tensor plumbing:
     writer for handing such frames to an encoder
   * baseline JPEG in integer arithmetic (jpeg_tables, jpeg_header, jpeg_encode_rgb8: the definition the kernels of
     `float_jpg_encode` are held to bit for bit; numpy, no imaging library) and a Motion-JPEG AVI writer (AviMjpegWriter)
+  * lossless PNG in integer arithmetic (png_filter_rows, png_code_lengths, png_encode_rgb8, crc32_combine: the definition the
+    kernels of `float_png_encode` are held to bit for bit) and an animated-PNG writer (ApngWriter)
 """
 import fractions
 import logging
@@ -985,5 +987,318 @@ class AviMjpegWriter:
         return self
 
     def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# ---------------------------------------------------------------- lossless PNG in integers (the definition of float_png_encode)
+# Eight code-length tables over the 256 byte values and end-of-block, one hex digit per symbol (csrc/png_kernels.hpp states the
+# same digits).  Tables 0 ... 6: Huffman lengths of 0.97 Laplace(min(v, 256 - v) / s) + 0.03 uniform for s = 0.35, 0.7, 1.5, 3, 6,
+# 12, 24 - residuals of growing spread; table 7 is flat: 8 bits, byte value 128 and end-of-block 9 - no band costs more than
+# 9 bits per byte.
+_PNG_LENGTHS = (
+    "137abbbbbbbbbbbbbccccccccccccccccccccccccccccccccccccccccccccccccccccccccccccbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbb"
+    "bbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbbba72b",
+    "13579acccccdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+    "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddccccca8652d",
+    "233556789aabcccccccdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+    "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddcccccccbaa98765433d",
+    "3344555667788999aabbbcccccccddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+    "ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddccccccbbbbaa999887766554443d",
+    "44445555666667777888889999aaaabbbbbbcccccccccdddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddd"
+    "dddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddcccccccccbbbbbaaaaa9999888887777666665555444d",
+    "555555556666666677777777888888888999999999aaaaaaaaaabbbbbbbbbbbccccccccccccccccccdddddddddddddddddddddddddddddddddddddddddddddddd"
+    "dddddddddddddddddddddddddddddddddddddddddddddddccccccccccccccccccbbbbbbbbbbbaaaaaaaaaa99999999988888888877777777666666665555555d",
+    "6666666666666667777777777777777788888888888888888999999999999999999aaaaaaaaaaaaaaaaaaabbbbbbbbbbbbbbbbbbbbbcccccccccccccccccccccd"
+    "ccccccccccccccccccccbbbbbbbbbbbbbbbbbbbbbbaaaaaaaaaaaaaaaaaaa999999999999999998888888888888888887777777777777777666666666666666d",
+    "888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888889"
+    "88888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888888889",
+)
+PNG_MAX_SIDE = 16384
+PNG_BAND_BYTES = 65536   # the most filter-plus-row bytes of one band
+PNG_HEADER_BITS = 1106   # BFINAL, BTYPE, HLIT, HDIST, HCLEN, 19 x 3 bits, 258 x 4 bits
+_PNG_CLEN_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_CRC_POLY = 0xEDB88320   # CRC-32, reflected: bit 31 is x^0
+
+
+def png_code_lengths():
+    """The 8 code-length tables of the PNG encoder: a tuple of 8 tuples of 257 lengths (byte values 0 ... 255, end-of-block).
+    Every table is complete (the Kraft sum is exactly 1) and no length passes 15."""
+    return tuple(tuple(int(c, 16) for c in t) for t in _PNG_LENGTHS)
+
+
+def png_default_band(h, w):
+    """Rows per band when none is given: 8, fewer for short frames, and never more bytes than PNG_BAND_BYTES."""
+    return max(1, min(8, int(h), PNG_BAND_BYTES // (1 + 3 * int(w))))
+
+
+def png_check_band(h, w, band=None):
+    """The band of an (h, w) frame: None or 0 -> png_default_band; otherwise 1 ... h rows with band (1 + 3 w) <= 65536."""
+    h, w = int(h), int(w)
+    if not (1 <= h <= PNG_MAX_SIDE and 1 <= w <= PNG_MAX_SIDE):
+        raise ValueError("PNG sides (%d x %d) must be in 1 ... %d" % (h, w, PNG_MAX_SIDE))
+    band = png_default_band(h, w) if band is None or int(band) == 0 else int(band)
+    if not 1 <= band <= h or band * (1 + 3 * w) > PNG_BAND_BYTES:
+        raise ValueError("PNG band (%d) must be 1 ... h (%d) rows of at most %d bytes in all (a row is %d)" % (band, h, PNG_BAND_BYTES, 1 + 3 * w))
+    return band
+
+
+def png_slot_bytes(rows, w):
+    """The worst case of one band of `rows` rows in bytes, float_png_encode's slot: the 1106-bit header, 9 bits per byte (the
+    flat table bounds the chosen one), an end-of-block of at most 15 bits (9 in the flat table), the 3-bit header of the
+    stored block, up to 7 bits to the byte boundary and 00 00 FF FF; rounded up to 16 bytes."""
+    n = int(rows) * (1 + 3 * int(w))
+    return ((PNG_HEADER_BITS + 9 * n + 15 + 3 + 7) // 8 + 4 + 15) & ~15
+
+
+def png_filter_rows(frame_u8):
+    """(h, w, 3) uint8 -> the h (1 + 3 w) bytes PNG compresses: per row the filter type, then the filtered bytes.  The five
+    filters are the PNG specification's with bpp = 3 (the row above row 0 is zero); a row takes the filter whose
+    sum of min(v, 256 - v) over its 3 w filtered bytes is smallest, ties to the smallest type."""
+    import numpy as np
+    x = frame_u8.detach().cpu().numpy() if isinstance(frame_u8, torch.Tensor) else np.asarray(frame_u8)
+    if x.dtype != np.uint8 or x.ndim != 3 or x.shape[-1] != 3:
+        raise ValueError("png_filter_rows takes (h, w, 3) uint8, got %s %s" % (x.dtype, tuple(x.shape)))
+    h, w, _ = x.shape
+    cur = x.reshape(h, 3 * w).astype(np.int32)
+    a = np.zeros_like(cur)
+    a[:, 3:] = cur[:, :-3]
+    b = np.zeros_like(cur)
+    b[1:] = cur[:-1]
+    c = np.zeros_like(cur)
+    c[1:, 3:] = cur[:-1, :-3]
+    p = a + b - c
+    pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    cand = np.stack([cur, cur - a, cur - b, cur - ((a + b) >> 1), cur - paeth]) & 255  # (5, h, 3w)
+    cost = np.minimum(cand, 256 - cand).sum(axis=2)  # (5, h)
+    f = np.argmin(cost, axis=0)  # the first of equal minima
+    out = np.empty((h, 1 + 3 * w), np.uint8)
+    out[:, 0] = f
+    out[:, 1:] = cand[f, np.arange(h)]
+    return out.tobytes()
+
+
+def _crc_mul(a, b):
+    """a(x) b(x) mod the CRC-32 polynomial, both reflected (bit 31 is x^0)"""
+    p = 0
+    for i in range(32):
+        if a & (0x80000000 >> i):
+            p ^= b
+        b = (b >> 1) ^ _CRC_POLY if b & 1 else b >> 1
+    return p
+
+
+def _crc_xpow8(n):
+    """x^(8 n) mod the CRC-32 polynomial, by square-and-multiply"""
+    p, sq = 0x80000000, 0x00800000  # x^0, x^8
+    while n:
+        if n & 1:
+            p = _crc_mul(sq, p)
+        sq = _crc_mul(sq, sq)
+        n >>= 1
+    return p
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(A + B) from crc_a = zlib.crc32(A), crc_b = zlib.crc32(B) and len_b = len(B): crc_a times x^(8 len_b) modulo the
+    CRC polynomial (a carry-less multiplication, the power by square-and-multiply), xor crc_b.  What the kernels of
+    float_png_encode and ApngWriter form chunk CRCs with instead of a pass over the data."""
+    return (_crc_mul(_crc_xpow8(int(len_b)), int(crc_a) & 0xFFFFFFFF) ^ int(crc_b)) & 0xFFFFFFFF
+
+
+_png_codes_cache = []
+
+
+def _png_codes():
+    """per table (lengths, codes bit-reversed for an LSB-first stream, the 1106 header bits as a 0 / 1 array)"""
+    import numpy as np
+    if not _png_codes_cache:
+        for lens in png_code_lengths():
+            lens = np.array(lens, np.int64)
+            code, rev = 0, np.zeros(257, np.int64)
+            for n in range(1, 16):  # canonical: the codes of one length count up in symbol order, and double to the next length
+                for s in np.nonzero(lens == n)[0]:
+                    rev[s] = int(format(code, "0%db" % n)[::-1], 2)
+                    code += 1
+                code <<= 1
+            bits = [0, 0, 1] + [0] * 5 + [0] * 5 + [1, 1, 1, 1]  # BFINAL 0, BTYPE 2, HLIT 0, HDIST 0, HCLEN 15: LSB first
+            for s in _PNG_CLEN_ORDER:
+                v = 4 if s < 16 else 0
+                bits += [v & 1, (v >> 1) & 1, (v >> 2) & 1]
+            for n in list(lens) + [0]:  # the code-length code is 4 bits for 0 ... 15: symbol n has code n, sent MSB first
+                bits += [(n >> 3) & 1, (n >> 2) & 1, (n >> 1) & 1, n & 1]
+            assert len(bits) == PNG_HEADER_BITS
+            _png_codes_cache.append((lens, rev, np.array(bits, np.uint8)))
+    return _png_codes_cache
+
+
+def png_band_bytes(data, stats=None):
+    """One band's filter-plus-row bytes -> its deflate bytes: a dynamic-Huffman block of literals in the cheapest of the 8
+    tables (bits(k) = sum of hist[v] T_k[v]; ties to the smallest k), then an empty stored block (sync flush)."""
+    import numpy as np
+    d = np.frombuffer(bytes(data), np.uint8).astype(np.int64)
+    tabs = _png_codes()
+    hist = np.bincount(d, minlength=256)
+    cost = [int((hist * t[0][:256]).sum()) for t in tabs]
+    k = cost.index(min(cost))
+    if stats is not None:
+        stats.append(k)
+    lens, rev, head = tabs[k]
+    sym = np.concatenate([d, [256]])
+    n = lens[sym]
+    start = PNG_HEADER_BITS + np.cumsum(n) - n
+    total = int(start[-1] + n[-1]) + 3
+    total = (total + 7) & ~7
+    bits = np.zeros(total + 32, np.uint8)
+    bits[:PNG_HEADER_BITS] = head
+    code = rev[sym]
+    for b in range(int(n.max())):
+        m = n > b
+        bits[start[m] + b] = (code[m] >> b) & 1
+    bits[total + 16:] = 1  # 00 00 FF FF
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def png_encode_rgb8(frames_u8, band=None, stats=False):
+    """(T, H, W, 3) or (H, W, 3) uint8 RGB (a torch tensor on any device, or a numpy array) -> a list of `bytes`, one complete
+    PNG file per frame (8 bits, colour type 2, no interlace, one IDAT).  This is the definition of what float_png_encode
+    writes; all of it is integer arithmetic.
+      filter   png_filter_rows
+      bands    band b is rows [b band, min(H, (b + 1) band)); band: None or 0 = png_default_band(H, W), else png_check_band's rule
+      band     png_band_bytes: literals only (no LZ77 matches) in one of 8 fixed tables, then a sync flush, so that the bands
+               are independent, byte-aligned pieces
+      zlib     78 01, the bands, 01 00 00 FF FF (the final, empty stored block), the Adler-32 of the filtered bytes
+      file     signature, IHDR, IDAT, IEND
+    stats=True: also returns the list of the tables chosen, band by band."""
+    import struct
+    import zlib
+
+    import numpy as np
+    x = frames_u8
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x)
+    if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
+        raise ValueError("png_encode_rgb8 takes (T, H, W, 3) or (H, W, 3) uint8 frames, got %s %s" % (x.dtype, tuple(x.shape)))
+    if x.ndim == 3:
+        x = x[None]
+    T, H, W, _ = x.shape
+    band = png_check_band(H, W, band)
+    stride = 1 + 3 * W
+    chunk = lambda cc, body: struct.pack(">I", len(body)) + cc + body + struct.pack(">I", zlib.crc32(cc + body))  # noqa: E731
+    ihdr = chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+    files, chosen = [], []
+    for t in range(T):
+        rows = png_filter_rows(x[t])
+        z = [b"\x78\x01"] + [png_band_bytes(rows[r * stride:min(H, r + band) * stride], chosen) for r in range(0, H, band)]
+        z += [b"\x01\x00\x00\xff\xff", struct.pack(">I", zlib.adler32(rows))]
+        files.append(b"\x89PNG\r\n\x1a\n" + ihdr + chunk(b"IDAT", b"".join(z)) + chunk(b"IEND", b""))
+    return (files, chosen) if stats else files
+
+
+def png_idat(data):
+    """(offset, length) of the IDAT data of a PNG file as png_encode_rgb8 and float_png_encode write it: 41 bytes of signature,
+    IHDR and the IDAT chunk's head in front, 16 bytes (its CRC and IEND) behind."""
+    return 41, len(data) - 57
+
+
+class ApngWriter:
+    """An animated PNG written block by block from the files of png_encode_rgb8 / float_png_encode (png.PngFrames): signature,
+    IHDR, `acTL`, then per frame an `fcTL` (the whole canvas, delay 1 / fps as the fraction y4m_rate(fps) gives, no blending)
+    and the frame's zlib stream - frame 0 as `IDAT`, the later ones as `fdAT` - and `IEND`.  The zlib streams are copied as they
+    are, and a chunk's CRC is formed from `crcs[i]`, the CRC-32 of frame i's zlib stream, by crc32_combine - never by a pass
+    over the data.  path_or_file: a path (opened here, closed by close()), or a SEEKABLE binary file object, left open: close()
+    goes back and writes the frame count into `acTL` (ValueError at open for a sink that cannot seek; ValueError at close()
+    when no frame was written: an APNG has at least one).  APNG carries NO AUDIO.  Players that do not know APNG show frame 0."""
+
+    def __init__(self, path_or_file, width, height, fps):
+        import struct
+        self.width, self.height = int(width), int(height)
+        if not (1 <= self.width <= PNG_MAX_SIDE and 1 <= self.height <= PNG_MAX_SIDE):
+            raise ValueError("ApngWriter: sides (%d x %d) must be in 1 ... %d" % (self.width, self.height, PNG_MAX_SIDE))
+        rate = y4m_rate(fps)
+        self.delay = (rate.denominator, rate.numerator)  # seconds per frame as a fraction
+        if not (1 <= self.delay[0] <= 65535 and 1 <= self.delay[1] <= 65535):
+            raise ValueError("ApngWriter: the frame delay %d / %d does not fit fcTL's 16-bit fields" % self.delay)
+        self.frames = self._seq = 0
+        self._own = not hasattr(path_or_file, "write")
+        if not self._own and not (hasattr(path_or_file, "seekable") and path_or_file.seekable()):
+            raise ValueError("ApngWriter needs a seekable sink: close() writes the frame count into acTL")
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        try:
+            ihdr = struct.pack(">IIBBBBB", self.width, self.height, 8, 2, 0, 0, 0)
+            self._f.write(b"\x89PNG\r\n\x1a\n" + self._chunk(b"IHDR", ihdr))
+            self._actl = self._f.tell()
+            self._f.write(self._chunk(b"acTL", struct.pack(">II", 0, 0)))
+        except BaseException:
+            f, self._f = self._f, None
+            if self._own:
+                f.close()
+            raise
+
+    @staticmethod
+    def _chunk(cc, body):
+        import struct
+        import zlib
+        return struct.pack(">I", len(body)) + cc + body + struct.pack(">I", zlib.crc32(cc + body))
+
+    def write(self, frames, crcs=None):
+        """Append frames: a png.PngFrames (its .crcs are taken), or an iterable of bytes-likes with `crcs`, one CRC-32 of the
+        zlib stream per frame - one complete PNG file each, of this writer's size, as png_encode_rgb8 lays it out.  Returns the
+        number of frames written so far."""
+        import struct
+        import zlib
+        if self._f is None:
+            raise ValueError("ApngWriter.write after close()")
+        crcs = getattr(frames, "crcs", None) if crcs is None else crcs
+        if crcs is None:
+            raise ValueError("ApngWriter.write: crcs (the CRC-32 of every frame's zlib stream) are needed")
+        crcs = crcs.tolist() if hasattr(crcs, "tolist") else list(crcs)
+        for i, fr in enumerate(frames):
+            fr = memoryview(fr)
+            at, n = png_idat(fr)
+            if n < 11 or bytes(fr[16:24]) != struct.pack(">II", self.width, self.height) or bytes(fr[37:41]) != b"IDAT":
+                raise ValueError("ApngWriter.write: frame %d is not a %d x %d file of png_encode_rgb8's layout" % (self.frames, self.width, self.height))
+            fctl = struct.pack(">IIIIIHHBB", self._seq, self.width, self.height, 0, 0, self.delay[0], self.delay[1], 0, 0)
+            self._f.write(self._chunk(b"fcTL", fctl))
+            self._seq += 1
+            if self.frames == 0:
+                head, size = b"IDAT", n
+            else:
+                head, size = b"fdAT" + struct.pack(">I", self._seq), n + 4
+                self._seq += 1
+            self._f.write(struct.pack(">I", size) + head)
+            self._f.write(fr[at:at + n])
+            self._f.write(struct.pack(">I", crc32_combine(zlib.crc32(head), int(crcs[i]) & 0xFFFFFFFF, n)))
+            self.frames += 1
+        return self.frames
+
+    def close(self):
+        import struct
+        f, self._f = self._f, None
+        if f is None:
+            return
+        try:
+            if self.frames == 0:
+                raise ValueError("ApngWriter: no frame was written (an APNG holds at least one)")
+            f.write(self._chunk(b"IEND", b""))
+            end = f.tell()
+            f.seek(self._actl)
+            f.write(self._chunk(b"acTL", struct.pack(">II", self.frames, 0)))  # 0 plays: loop for ever
+            f.seek(end)
+        finally:
+            if self._own:
+                f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if exc[0] is not None and self.frames == 0:  # the block failed before a frame: its error is the one to report
+            f, self._f = self._f, None
+            if f is not None and self._own:
+                f.close()
+            return False
         self.close()
         return False

@@ -150,6 +150,10 @@ _SIGNATURES = {
     "float_jpg_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_jpg_work_bytes_padded": (C.c_size_t, [C.c_int32] * 4),
     "float_jpg_encode_padded": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "float_png_work_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "float_png_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "float_png_tables": (C.c_int, [C.POINTER(C.c_int32)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

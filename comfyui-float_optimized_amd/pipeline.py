@@ -9,7 +9,7 @@ import warnings
 
 import torch
 
-from . import host_models, image, jpeg, native
+from . import host_models, image, jpeg, native, png
 from .config import FmtConfig
 from .decoder import SynthesisHIP, infer_out_format
 from .fmt import FlowMatchingTransformerHIP, WindowSampler, draw_noise
@@ -196,6 +196,13 @@ class JpegBlock(collections.namedtuple("JpegBlock", "first last frames")):
     __slots__ = ()
 
 
+class PngBlock(collections.namedtuple("PngBlock", "first last frames")):
+    """One FMT window of a clip streamed as PNG files (FloatHotPath.stream_to_png): frames [first, last) of the clip, `frames` a
+    png.PngFrames over a pinned ring slot - complete when the block is yielded and OVERWRITTEN after the generator has been
+    advanced again: write it out or copy it (`bytes(blk.frames[i])`) to keep it."""
+    __slots__ = ()
+
+
 class Placement(collections.namedtuple("Placement", "src8 rect")):
     """Where the generated frames belong in the user's portrait (InferenceAgent.host_inputs_placed): `src8` the (H, W, 3) uint8
     portrait on the device (image.source_rgb8_device), `rect` = (x0, y0, w, h) the box of the crop in its coordinates - it may
@@ -330,6 +337,44 @@ class _JpegSink:
             st.synchronize()
         self.s_copy.wait_event(ev)
         return JpegBlock(f0, f1, jpeg.to_host(slot["data"], edges.clone(), slot["host"], self.s_copy))
+
+
+class _PngSink(_JpegSink):
+    """What FloatHotPath._ring does per slot for stream_to_png: _JpegSink's slots with room for the frames' raw size, and the
+    files' CRCs beside the offsets on both sides."""
+    name = "stream_to_png"
+
+    def __init__(self, hot, band, place=None, feather=None):
+        self.hot, self.band, self.place, self.feather = hot, band, place, feather
+
+    def open(self, slots):
+        dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
+        H, W = self.place.size if self.place is not None else (R, R)
+        cap = png.default_capacity(L, H, W)
+        ring = [dict(u8=torch.empty(L, H, W, 3, dtype=torch.uint8, device=dev), data=torch.empty(cap, dtype=torch.uint8, device=dev),
+                     off=torch.empty(L + 1, dtype=torch.int64, device=dev), host=torch.empty(cap, dtype=torch.uint8, pin_memory=True),
+                     off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True), crc=torch.empty(L, dtype=torch.int32, device=dev),
+                     crc_host=torch.empty(L, dtype=torch.int32, pin_memory=True)) for _ in range(slots)]
+        self.s_copy, self.work = torch.cuda.Stream(dev), None
+        self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev) if self.place is not None else None
+        return ring
+
+    def _encode(self, slot, n):
+        self.work = png.enqueue_encode(slot["u8"][:n], self.band, slot["data"], slot["off"][:n + 1], slot["crc"][:n], self.work)
+        slot["crc_host"][:n].copy_(slot["crc"][:n], non_blocking=True)
+
+    def block(self, slot, f0, f1, ev, st):
+        n = f1 - f0
+        edges = slot["off_host"][:n + 1]
+        total = int(edges[-1])
+        if total > slot["data"].numel():  # the files did not fit: once more, with room (behind the windows already enqueued)
+            with torch.cuda.stream(st):
+                slot["data"] = torch.empty(total, dtype=torch.uint8, device=self.hot.device)
+                slot["host"] = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+                self._encode(slot, n)
+            st.synchronize()
+        self.s_copy.wait_event(ev)
+        return PngBlock(f0, f1, png.to_host(slot["data"], edges.clone(), slot["crc_host"][:n].clone(), slot["host"], self.s_copy))
 
 
 class FloatHotPath:
@@ -764,6 +809,50 @@ class FloatHotPath:
             image.require_jpeg_sides("stream_to_jpeg", *place.size, pad=pad)
             width = place.size[1]
         sink = _JpegSink(self, quality, jpeg.pad_restart(width, pad) if restart is None else int(restart), place, feather, pad)
+        self._check_stream_call(sink.name, slots, wa)
+        return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
+
+    @torch.no_grad()
+    def generate_to_png(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
+                        band=None, return_rd=False, place=None, feather=None):
+        """generate_to_host for one clip (B = 1) with the frames leaving as LOSSLESS PNG files (png.PngFrames in pinned host memory):
+        the chain, decode_u8 of the whole clip, float_png_encode on the 8-bit frames in HBM, ONE host read of the offsets, then
+        offsets[T] bytes across PCIe - the files, not the frames.  File i decodes to frame i of
+        generate_to_host(out_dtype=torch.uint8) bit for bit and is bitwise host_models.png_encode_rgb8 of it (band: rows per
+        band, None = png.default_band).  Complete on return (the stream has been synchronised).  The 8-bit frames stay on the
+        device: T * size * size * 3 bytes of HBM while it runs, and as much again for the files.
+        place (a Placement; default None: nothing above changes): the 8-bit crops are pasted back into the portrait on the device
+        (float_img_paste, `feather` as in generate_pasted) and the encoder codes the H x W frames, of any size up to 16384 - file i
+        is png_encode_rgb8 of frame i of generate_pasted."""
+        if place is not None:
+            place = _check_place("generate_to_png", place, self.device)
+        H, W = place.size if place is not None else (self.size, self.size)
+        band = host_models.png_check_band(H, W, band)
+        self.require_no_stream("generate_to_png")
+        if feats is not None:
+            self.dec.set_feats(feats)
+        r_d = self.sample(r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale, seed, noise)
+        with torch.cuda.device(self.device):
+            u8 = self.dec.decode_u8(s_r, _rows(r_d))
+            if place is not None:
+                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather)
+            frames = png.encode_png_host(u8, band)
+        return (frames, r_d) if return_rd else frames
+
+    def stream_to_png(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
+                      band=None, slots=3, place=None, feather=None):
+        """generate_to_png as a generator: one PngBlock(first, last, frames) per FMT window, in frame order, the same files as the
+        whole-clip call.  The contract is stream_to_jpeg's: `frames` (a png.PngFrames) lives in one of `slots` pinned ring
+        buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (ApngWriter.write has
+        handed the bytes on when it returns); slots >= 2, B = 1 and the band are checked at the call (ValueError), nothing is
+        enqueued before the first next(); while the generator is open every other producer on this object raises RuntimeError.
+        Per slot: a device buffer of 50 8-bit frames, a device and a pinned buffer of their raw size for the files, and the offsets
+        and CRCs on both sides.  Files beyond the slot's room (noise: 9 / 8 of the raw size) are encoded once more into a larger
+        buffer.  place, feather: as in generate_to_png."""
+        if place is not None:
+            place = _check_place("stream_to_png", place, self.device)
+        H, W = place.size if place is not None else (self.size, self.size)
+        sink = _PngSink(self, host_models.png_check_band(H, W, band), place, feather)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 

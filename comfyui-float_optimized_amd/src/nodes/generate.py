@@ -671,6 +671,107 @@ class InferenceAgent:
                                          pad=pad)
         return self._stream_placed("InferenceAgent.stream_pasted_jpeg", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_jpeg)
 
+    # ------------------------------------------------------------------ lossless frames: PNG files and APNG clips
+    def _png_call(self, what, band, ref_img=None):
+        """What a PNG producer refuses at the call: a band host_models.png_check_band does not take for the frames that leave -
+        the model's size, or with ref_img the portrait's (any size up to 16384 is taken).  Returns the band in rows."""
+        if ref_img is None:
+            return host_models.png_check_band(self.opt.input_size, self.opt.input_size, band)
+        img = ref_img[0] if ref_img.dim() == 4 else ref_img
+        try:
+            return host_models.png_check_band(int(img.shape[0]), int(img.shape[1]), band)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e)) from None
+
+    @torch.no_grad()
+    def infer_device_png(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, band=None):
+        """infer_device with the frames leaving as LOSSLESS PNG files: a png.PngFrames in pinned host memory; file i decodes to
+        infer_device(out_dtype=torch.uint8)[i] bit for bit and is bitwise host_models.png_encode_rgb8 of it
+        (FloatHotPath.generate_to_png: the encoder runs on the 8-bit frames in HBM and only the files cross PCIe).  band: rows
+        per band, None = png.default_band.  FLOAT_AMD_RANGE applies as in infer_device (auto rebuilds and runs the clip again);
+        FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        band = self._png_call("infer_device_png", band)
+        c, noise = self._clip_inputs(s, a, emo, seed)
+        frames = self.G.generate_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                        noise=noise, band=band)
+        if self.check_range("InferenceAgent.infer_device_png", allow_rebuild=True) == "rebuilt":
+            return self.infer_device_png(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, band)  # once more, in the wider types
+        return frames
+
+    def stream_device_png(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, band=None, slots=3):
+        """The streaming sibling of infer_device_png: a generator of PngBlock(first, last, frames), one per 50-frame FMT window, in
+        frame order - concatenated, the files infer_device_png returns for the same inputs and seed.  The ring rules are
+        stream_device_jpeg's: `frames` lives in one of `slots` pinned buffers, complete when yielded, OVERWRITTEN once the generator
+        has been advanced again; slots < 2 or a band outside its rule raise ValueError here, at the call; while the stream is open
+        every other producer on this agent raises RuntimeError.  FLOAT_AMD_RANGE is applied once after the last block (auto acts
+        as warn); FLOAT_AMD_VERIFY is NOT applied."""
+        self._check_stream_call("stream_device_png", slots)
+        band = self._png_call("stream_device_png", band)
+
+        def _stream_device_png(c, noise):
+            return self.G.stream_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                        noise=noise, band=band, slots=int(slots))
+        return self._stream_clip("InferenceAgent.stream_device_png", s, a, emo, seed, _stream_device_png)
+
+    @torch.no_grad()
+    def infer_pasted_png(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                         feather=None, band=None):
+        """infer_pasted with the frames leaving as LOSSLESS PNG files: a png.PngFrames in pinned host memory; file i decodes to
+        infer_pasted(...)[i] bit for bit and is bitwise host_models.png_encode_rgb8 of it.  Paste and encoder run on the device and
+        only the files cross PCIe.  A portrait of any size up to 16384 x 16384 is taken.  FLOAT_AMD_RANGE applies as in
+        infer_device_png; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        band = self._png_call("infer_pasted_png", band, ref_img)
+        s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
+        while True:
+            c, noise = self._clip_inputs(s, a, emo, seed)
+            frames = self.G.generate_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                            noise=noise, band=band, place=place, feather=feather)
+            if self.check_range("InferenceAgent.infer_pasted_png", allow_rebuild=True) != "rebuilt":
+                return frames  # otherwise once more, in the wider types
+
+    def stream_pasted_png(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                          feather=None, band=None, slots=3):
+        """The streaming sibling of infer_pasted_png: a generator of PngBlock(first, last, frames) under the ring rules of
+        stream_device_png - concatenated, the files infer_pasted_png returns.  slots < 2 or a band outside its rule raise
+        ValueError here, at the call.  FLOAT_AMD_RANGE is applied once after the last block (auto acts as warn); FLOAT_AMD_VERIFY
+        is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        self._check_stream_call("stream_pasted_png", slots)
+        band = self._png_call("stream_pasted_png", band, ref_img)
+
+        def _stream_pasted_png(c, noise, place):
+            return self.G.stream_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
+                                        noise=noise, band=band, slots=int(slots), place=place, feather=feather)
+        return self._stream_placed("InferenceAgent.stream_pasted_png", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_png)
+
+    def write_apng(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
+                   fps=None, paste_back=False, feather=None, band=None):
+        """A lossless clip in one file: host_inputs, stream_device_png, and host_models.ApngWriter on `path` (a path or a seekable
+        binary file object) - an animated PNG that browsers and ffmpeg open, every frame bit for bit the 8-bit frame.  The
+        zlib streams are copied as the device wrote them and every chunk CRC comes from the device's per-frame CRCs.  APNG carries
+        NO AUDIO: the clip's sound has to be kept separately (write_video writes a file with an audio track).  fps defaults to
+        opt.fps.  Returns the number of frames written.
+        paste_back=True: the frames are the user's portrait with the generated face pasted back (stream_pasted_png, `feather` as
+        in infer_pasted) and the file is written at the portrait's size, any size up to 16384."""
+        o = self.opt
+        fps = o.fps if fps is None else fps
+        if paste_back:
+            img = ref_img[0] if ref_img.dim() == 4 else ref_img
+            height, width = int(img.shape[0]), int(img.shape[1])
+            blocks = self.stream_pasted_png(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, band)
+        else:
+            height = width = o.input_size
+            band = self._png_call("write_apng", band)
+            with torch.no_grad():
+                s, a = self.host_inputs(ref_img, ref_audio, no_crop)
+            blocks = self.stream_device_png(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, band)
+        try:
+            with host_models.ApngWriter(path, width, height, fps) as w:
+                for blk in blocks:
+                    w.write(blk.frames)
+                return w.frames
+        finally:
+            blocks.close()  # a writer that failed leaves no stream open on the agent
+
     def range_counts(self, reset=True):
         """{operator: clamped / non-finite 16-bit stores since the last call} over every fp16 handle of the agent."""
         if self.G is None:

@@ -676,6 +676,46 @@ size_t float_jpg_work_bytes_padded(int32_t n_frames, int32_t h, int32_t w, int32
 int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out,
                             size_t out_cap, int64_t* offsets, void* work, size_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------- PNG encoder -- */
+/* n_frames 8-bit RGB frames in HBM -> n complete PNG files (8 bits, colour type 2, no interlace, one IDAT), LOSSLESS, back to
+ * back in `out`: file i is out[offsets[i] : offsets[i + 1]].  Every step is integer arithmetic, so the bytes are bitwise the
+ * definition in the host mirror, host_models.png_encode_rgb8:
+ *   filter    per row the cheapest of the specification's five (bpp = 3, the row above row 0 is zero) by the sum of
+ *             min(v, 256 - v) over the row's filtered bytes; ties go to the smallest type.
+ *   bands     the filtered rows (1 + 3 w bytes each) are cut into bands of `band` rows, the last one may be short.  A band is ONE
+ *             deflate block with a dynamic-Huffman header, coding literals only - no LZ77 matches - followed by an empty stored
+ *             block (zlib's sync flush), so every band is an independent, byte-aligned piece, coded by one workgroup.
+ *   tables    the block's code is one of 8 FIXED code-length tables over the 256 byte values and end-of-block, the one with the
+ *             fewest bits for the band's histogram (ties: the smallest index).  Tables 0 ... 6 suit residuals of growing spread;
+ *             table 7 is flat (8 bits; byte value 128 and end-of-block 9).  float_png_tables copies the 8 x 257 lengths out.
+ *   stream    78 01, the bands, 01 00 00 FF FF, the Adler-32 of the filtered bytes.
+ *   h, w      1 ... 16384.  rgb8 has any alignment.
+ *   band      1 ... h rows with band (1 + 3 w) <= 65536; 0 = the default max(1, min(8, h, 65536 / (1 + 3 w))).
+ *   out       DEVICE, out_cap bytes.  offsets: DEVICE, n_frames + 1 int64, 8-byte aligned; ALWAYS complete and exact, also when
+ *             offsets[n_frames] > out_cap: then nothing at or beyond out + out_cap is written (what lies below is valid), and the
+ *             caller reads offsets[n_frames] and calls again with room.
+ *   crcs      DEVICE, n_frames uint32, or NULL: per frame the CRC-32 of the zlib stream alone (the IDAT chunk's data), from
+ *             which a container writer forms the CRC of any chunk that carries the stream (host_models.crc32_combine) without
+ *             reading the data again.
+ *   work      DEVICE scratch of at least float_png_work_bytes(n_frames, h, w, band) bytes, 16-byte aligned, no zeroing needed.
+ *             Frames are coded in groups of 16 that share it in stream order: with g = min(n_frames, 16) frames and b bands per
+ *             frame it is g b (24 + slot) + 256 bytes rounded up.  A slot is the provable worst case of a band of n = band (1 + 3 w)
+ *             bytes: the 1106-bit block header, 9 bits per byte (the flat table bounds the chosen one), an end-of-block of at
+ *             most 15 bits (9 in the flat table), the stored block's 3 bits, up to 7 bits to the byte boundary and 00 00 FF FF -
+ *             (1106 + 9 n + 25) / 8 + 4 bytes, rounded up to 16 (14.3 MB for 16 frames of 512 x 512 at the default band).
+ * Not built: LZ77 matching, a code fitted to the frame, a stored-block fallback (the flat table bounds a band at 9 / 8 of its
+ * size), 16-bit or RGBA frames.
+ * The canonical codes and the CRC tables are compile-time constants of the library.  The CRC-32s of the pieces are combined on
+ * the device by multiplication with x^(8 n) modulo the CRC polynomial, as crc32_combine does.  Enqueues three kernels per group on
+ * `stream`; allocates nothing, synchronises nothing, kernel launches only; the only atomics are integer adds, ORs and XORs in LDS,
+ * so two calls give equal bytes.  An argument outside these rules (a null pointer, a side outside 1 ... 16384, a band above h or
+ * of more than 65536 bytes, a short or misaligned work) returns FLOAT_E_INVALID, with a message naming the function and the
+ * argument, before any HIP call; float_png_work_bytes returns 0 for such sizes. */
+size_t float_png_work_bytes(int32_t n_frames, int32_t h, int32_t w, int32_t band);
+int float_png_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t band, uint8_t* out, size_t out_cap, int64_t* offsets,
+                     uint32_t* crcs, void* work, size_t work_bytes, void* stream);
+int float_png_tables(int32_t lengths[8 * 257]);
+
 #ifdef __cplusplus
 }
 #endif
