@@ -4,7 +4,9 @@
 
 namespace {
 constexpr int32_t kImgpMaxSrc = 16384;    // source and box sides, feather
-constexpr int32_t kImgpMaxFrame = 1024;   // sides of a generated frame: what keeps every sum in 32 bits (imgp_kernels.hpp)
+constexpr int32_t kImgpMaxFrame = 1024;   // sides of a generated frame: what keeps every sum in 32 bits (imgp_kernels.hpp).  A side that
+                                          // equals the box's (frames already resampled: float_img_resample) reduces to P = Q = 1 on that
+                                          // axis, so it may be as long as the box; a frame is then still below 3 * 2^28 bytes
 constexpr int32_t kImgpMaxOff = 1 << 30;  // |rect_x|, |rect_y|: origin + side stays in 32 bits
 constexpr unsigned kImgpMaxGrid = 1u << 30;
 }  // namespace
@@ -17,8 +19,8 @@ int float_img_paste(const uint8_t* src8, int32_t src_h, int32_t src_w, const uin
   FH_REQUIRE(src_h >= 1 && src_h <= kImgpMaxSrc && src_w >= 1 && src_w <= kImgpMaxSrc,
              "float_img_paste: source sides src_h, src_w (%d x %d) must be 1 ... %d", src_h, src_w, kImgpMaxSrc);
   FH_REQUIRE(n_frames >= 1, "float_img_paste: n_frames (%d) must be at least 1", n_frames);
-  FH_REQUIRE(fr_h >= 1 && fr_h <= kImgpMaxFrame && fr_w >= 1 && fr_w <= kImgpMaxFrame,
-             "float_img_paste: frame sides fr_h, fr_w (%d x %d) must be 1 ... %d", fr_h, fr_w, kImgpMaxFrame);
+  FH_REQUIRE(fr_h >= 1 && (fr_h <= kImgpMaxFrame || fr_h == rect_h) && fr_w >= 1 && (fr_w <= kImgpMaxFrame || fr_w == rect_w),
+             "float_img_paste: frame sides fr_h, fr_w (%d x %d) must be 1 ... %d, or the box's own", fr_h, fr_w, kImgpMaxFrame);
   FH_REQUIRE(rect_w >= 1 && rect_w <= kImgpMaxSrc && rect_h >= 1 && rect_h <= kImgpMaxSrc,
              "float_img_paste: box sides rect_h, rect_w (%d x %d) must be 1 ... %d", rect_h, rect_w, kImgpMaxSrc);
   FH_REQUIRE(rect_x >= -kImgpMaxOff && rect_x <= kImgpMaxOff && rect_y >= -kImgpMaxOff && rect_y <= kImgpMaxOff,
@@ -46,8 +48,8 @@ int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, cons
   FH_REQUIRE(src_h >= 2 && src_h <= kImgpMaxSrc && src_w >= 2 && src_w <= kImgpMaxSrc && src_h % 2 == 0 && src_w % 2 == 0,
              "float_img_paste_i420: source sides src_h, src_w (%d x %d) must be even and 2 ... %d (4:2:0 chroma)", src_h, src_w, kImgpMaxSrc);
   FH_REQUIRE(n_frames >= 1, "float_img_paste_i420: n_frames (%d) must be at least 1", n_frames);
-  FH_REQUIRE(fr_h >= 1 && fr_h <= kImgpMaxFrame && fr_w >= 1 && fr_w <= kImgpMaxFrame,
-             "float_img_paste_i420: frame sides fr_h, fr_w (%d x %d) must be 1 ... %d", fr_h, fr_w, kImgpMaxFrame);
+  FH_REQUIRE(fr_h >= 1 && (fr_h <= kImgpMaxFrame || fr_h == rect_h) && fr_w >= 1 && (fr_w <= kImgpMaxFrame || fr_w == rect_w),
+             "float_img_paste_i420: frame sides fr_h, fr_w (%d x %d) must be 1 ... %d, or the box's own", fr_h, fr_w, kImgpMaxFrame);
   FH_REQUIRE(rect_w >= 1 && rect_w <= kImgpMaxSrc && rect_h >= 1 && rect_h <= kImgpMaxSrc,
              "float_img_paste_i420: box sides rect_h, rect_w (%d x %d) must be 1 ... %d", rect_h, rect_w, kImgpMaxSrc);
   FH_REQUIRE(rect_x >= -kImgpMaxOff && rect_x <= kImgpMaxOff && rect_y >= -kImgpMaxOff && rect_y <= kImgpMaxOff,

@@ -11,6 +11,8 @@ this package).  What is left is tensor plumbing:
     `float_img_front` (image.py in this package) are held to bit for bit
   * the paste of the generated frames back into the source portrait (paste_alpha, paste_rgb8): the definition the kernel of
     `float_img_paste` is held to bit for bit
+  * bicubic and Lanczos resampling of 8-bit frames in Pillow's fixed-point arithmetic (resample_coeffs, resample_rgb8): the
+    definition the kernels of `float_img_resample` are held to bit for bit, and what `resample=` selects on the paste routes
   * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
     writer for handing such frames to an encoder
   * baseline JPEG in integer arithmetic (jpeg_tables, jpeg_header, jpeg_encode_rgb8: the definition the kernels of
@@ -182,6 +184,163 @@ def rgb8_to_model_input(q):
     return (q.float() / 127.5 - 1.0).permute(2, 0, 1)[None].contiguous()
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# bicubic and Lanczos resampling: Pillow's Image.resize for 8-bit images, restated.  What `resample=` puts in the place of
+# resize_rgb8 on the paste routes; the front end keeps its own rule.
+# ---------------------------------------------------------------------------------------------------------------------------
+RESAMPLE_FILTERS = {"bicubic": 0, "lanczos": 1}  # name -> FLOAT_IMG_FILTER_*
+RESAMPLE_PRECISION_BITS = 22                     # coefficients are integers in units of 2^-22
+RESAMPLE_MAX_KSIZE = 255                         # the most taps of one output sample (shrinking by about 42 x with Lanczos)
+_RESAMPLE_SUPPORT = (2.0, 3.0)
+
+
+def resample_filter_id(what, filter):
+    """"bicubic" | "lanczos" -> 0 | 1; anything else is a ValueError that names the caller."""
+    if not isinstance(filter, str) or filter not in RESAMPLE_FILTERS:
+        raise ValueError("%s: resample filter must be one of %s (got %r)" % (what, ", ".join(sorted(RESAMPLE_FILTERS)), filter))
+    return RESAMPLE_FILTERS[filter]
+
+
+def _bicubic_filter(x):
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos_filter(x):
+    if -3.0 <= x < 3.0:
+        return _sinc(x) * _sinc(x / 3)
+    return 0.0
+
+
+def resample_ksize(n_in, n_out, filter):
+    """The slots a table row holds for its coefficients: int(ceil(support)) * 2 + 1, support = S * max(n_in / n_out, 1)."""
+    fid = resample_filter_id("resample_ksize", filter)
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("resample_ksize: sizes %d -> %d must be at least 1" % (n_in, n_out))
+    ksize = int(math.ceil(_RESAMPLE_SUPPORT[fid] * max(n_in / n_out, 1.0))) * 2 + 1
+    if ksize > RESAMPLE_MAX_KSIZE:
+        raise ValueError("resample: %d -> %d with the %s filter needs %d taps per sample, more than %d" % (n_in, n_out, filter, ksize,
+                                                                                                          RESAMPLE_MAX_KSIZE))
+    return ksize
+
+
+def resample_coeffs(n_in, n_out, filter, first=0, count=None):
+    """One axis of Pillow's Image.resize (src/libImaging/Resample.c: precompute_coeffs, normalize_coeffs_8bpc) for output indices
+    first ... first + count - 1 of n_out (default: all) -> (xmin, n, k): int64 tensors of shape (count,), (count,), (count, ksize).
+        scale = n_in / n_out;  fs = max(scale, 1.0);  support = S * fs  (S = 2 bicubic, 3 lanczos);  ss = 1.0 / fs
+        ksize = int(ceil(support)) * 2 + 1
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5));  xmax = min(n_in, int(center + support + 0.5));  n = xmax - xmin
+        w[x] = f((x + xmin - center + 0.5) * ss), x = 0 ... n - 1;  ww = their sum in that order;  w[x] /= ww if ww != 0
+        k[x] = int(-0.5 + w[x] * 2^22) if w[x] < 0 else int(0.5 + w[x] * 2^22)   (int truncates toward zero);  k[x] = 0 for x >= n
+        bicubic (a = -0.5): |x| < 1: ((a + 2) x - (a + 3)) x x + 1;  |x| < 2: (((x - 5) x + 8) x - 4) a;  else 0
+        lanczos: -3 <= x < 3: sinc(x) sinc(x / 3) with sinc(0) = 1, sinc(x) = sin(pi x) / (pi x);  else 0
+    in Python floats (IEEE double) with math.sin and math.pi: the libm Pillow and float_img_resample_plan call.  An output
+    sample of the axis is clamp((2^21 + sum_x k[x] in[xmin + x]) >> 22, 0, 255); 255 sum|k| + 2^21 < 2^31 is asserted for every
+    row, so 32-bit accumulators hold it.  ValueError: an unknown filter, a size below 1, a range outside 0 ... n_out, or more than
+    255 taps (shrinking by more than about 42 x)."""
+    fid = resample_filter_id("resample_coeffs", filter)
+    resample_ksize(n_in, n_out, filter)  # the refusals
+    n_out, first = int(n_out), int(first)
+    count = n_out - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > n_out:
+        raise ValueError("resample_coeffs: indices %d ... %d lie outside 0 ... %d" % (first, first + count, n_out))
+    return _resample_table(int(n_in), n_out, fid, first, count)
+
+
+def _resample_table(n_in, n_out, fid, first, count):
+    """the rule of resample_coeffs itself, at any number of taps"""
+    f = (_bicubic_filter, _lanczos_filter)[fid]
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = _RESAMPLE_SUPPORT[fid] * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    one = float(1 << RESAMPLE_PRECISION_BITS)
+    xmins, ns, ks = [], [], []
+    for xx in range(first, first + count):
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        n = min(n_in, int(center + support + 0.5)) - xmin
+        w = [f((x + xmin - center + 0.5) * ss) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        k = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+        assert 255 * sum(abs(v) for v in k) + (1 << (RESAMPLE_PRECISION_BITS - 1)) < 1 << 31, (n_in, n_out, fid, xx)
+        xmins.append(xmin), ns.append(n), ks.append(k + [0] * (ksize - n))
+    return (torch.tensor(xmins, dtype=torch.int64), torch.tensor(ns, dtype=torch.int64),
+            torch.tensor(ks, dtype=torch.int64).reshape(count, ksize))
+
+
+def _resample_axis(x, axis, coeffs):
+    """one pass over `axis` of an int64 tensor of 8-bit samples -> the same, the axis as long as the table"""
+    xmin, n, k = coeffs
+    x = x.movedim(axis, 0)
+    idx = (xmin[:, None] + torch.arange(k.shape[1], dtype=torch.int64)[None, :]).clamp(max=x.shape[0] - 1)  # k is 0 beyond n
+    acc = torch.full((k.shape[0],) + tuple(x.shape[1:]), 1 << (RESAMPLE_PRECISION_BITS - 1), dtype=torch.int64)
+    for j in range(k.shape[1]):
+        acc += x[idx[:, j]] * k[:, j].reshape((-1,) + (1,) * (x.dim() - 1))
+    return (acc >> RESAMPLE_PRECISION_BITS).clamp(0, 255).movedim(0, axis)  # >> on a negative int64 is the arithmetic shift
+
+
+def resample_window(what, h, w, window):
+    """window = (xa, ya, wc, hc) of an h x w result, checked; None is the whole."""
+    if window is None:
+        return 0, 0, int(w), int(h)
+    if len(window) != 4:
+        raise ValueError("%s: window must be (xa, ya, wc, hc), got %r" % (what, window))
+    xa, ya, wc, hc = (int(v) for v in window)
+    if xa < 0 or ya < 0 or wc < 1 or hc < 1 or xa + wc > w or ya + hc > h:
+        raise ValueError("%s: window %r lies outside the %d x %d result" % (what, tuple(window), h, w))
+    return xa, ya, wc, hc
+
+
+def resample_rgb8(frames8, h, w, filter, window=None):
+    """(T, h_f, w_f, 3) uint8 -> (T, h, w, 3) uint8: Pillow's Image.resize((w, h), BICUBIC | LANCZOS) of every frame, bit for bit
+    (tests/test_img_resample.py holds it to Pillow itself).  filter: "bicubic" | "lanczos".  The horizontal pass comes first and
+    gives an 8-bit intermediate, the vertical pass follows; a pass whose two sizes are equal is skipped.  window = (xa, ya, wc,
+    hc): only that part of the (h, w) result, (T, hc, wc, 3) - every output sample is independent, so it is the slice of the
+    whole, and the whole is never formed (a box may be far larger than the image it is pasted into).  The definition
+    `float_img_resample` (image.resample_frames_device) is held to bit for bit."""
+    resample_filter_id("resample_rgb8", filter)
+    if frames8.dtype != torch.uint8 or frames8.dim() != 4 or frames8.shape[-1] != 3 or 0 in frames8.shape:
+        raise ValueError("resample_rgb8 takes (T, h, w, 3) uint8 frames, got %s %s" % (frames8.dtype, tuple(frames8.shape)))
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("resample_rgb8: the result %d x %d must be at least 1 x 1" % (h, w))
+    xa, ya, wc, hc = resample_window("resample_rgb8", h, w, window)
+    h_f, w_f = int(frames8.shape[1]), int(frames8.shape[2])
+    cx = resample_coeffs(w_f, w, filter, xa, wc) if w != w_f else None
+    cy = resample_coeffs(h_f, h, filter, ya, hc) if h != h_f else None
+    x = frames8.cpu().to(torch.int64)
+    if cy is not None:  # only the rows the window's rows reference go through the horizontal pass
+        r0, r1 = int(cy[0].min()), int((cy[0] + cy[1]).max())
+        x, cy = x[:, r0:r1], (cy[0] - r0, cy[1], cy[2])
+    else:
+        x = x[:, ya:ya + hc]
+    x = _resample_axis(x, 2, cx) if cx is not None else x[:, :, xa:xa + wc]
+    if cy is not None:
+        x = _resample_axis(x, 1, cy)
+    return x.to(torch.uint8).contiguous()
+
+
 def default_feather(rect):
     """The feather a caller gets who passes None: rect_w // 16 source pixels.  A visual choice, not a measurement - there is no
     checkpoint here to judge a seam on."""
@@ -206,7 +365,7 @@ def paste_alpha(H, W, rect, feather):
     return torch.clamp((255 * (d + 1)) // (f + 1), max=255)
 
 
-def paste_rgb8(src8, frames8, rect, feather):
+def paste_rgb8(src8, frames8, rect, feather, resample=None):
     """The generated frames back in the source portrait: src8 (H, W, 3) uint8, frames8 (T, h_f, w_f, 3) uint8, rect = (x0, y0, w,
     h) in source coordinates (it may reach outside the image or miss it), feather >= 0 in source pixels -> (T, H, W, 3) uint8.
       outside rect & image   out[t] = src8
@@ -214,6 +373,8 @@ def paste_rgb8(src8, frames8, rect, feather):
                              rounded to 8 bits - and out = (a face + (255 - a) src + 127) // 255 with a = paste_alpha (255 is odd:
                              no ties, this is round-to-nearest).
     The parts of the generated frame that map outside the image are discarded: they are the zero border the model was shown.
+    resample: None as above; "bicubic" | "lanczos": face = resample_rgb8(frames8[t], h, w, resample) - Pillow's filter, sharper
+    where the box is larger than the frame - in the place of the resize_rgb8 call; alpha, blend and the discard are unchanged.
     Integer arithmetic in torch on the CPU; the definition `float_img_paste` (image.paste_frames_device) is held to bit for
     bit, as resize_rgb8 is for the front end."""
     if src8.dtype != torch.uint8 or src8.dim() != 3 or src8.shape[-1] != 3:
@@ -222,6 +383,8 @@ def paste_rgb8(src8, frames8, rect, feather):
         raise ValueError("paste_rgb8 takes (T, h, w, 3) uint8 frames, got %s %s" % (frames8.dtype, tuple(frames8.shape)))
     if len(rect) != 4:
         raise ValueError("paste_rgb8: rect must be (x0, y0, w, h), got %r" % (rect,))
+    if resample is not None:
+        resample_filter_id("paste_rgb8", resample)
     x0, y0, w, h = (int(v) for v in rect)
     f = int(feather)
     if w < 1 or h < 1 or f < 0 or src8.shape[0] < 1 or src8.shape[1] < 1:
@@ -235,8 +398,13 @@ def paste_rgb8(src8, frames8, rect, feather):
         return out
     a = paste_alpha(H, W, (x0, y0, w, h), f)[ya - y0:yb - y0, xa - x0:xb - x0, None]
     s = src8[ya:yb, xa:xb].to(torch.int64)
+    if resample is not None:  # the window of the box that lies in the image, never the whole box
+        faces = resample_rgb8(frames8, h, w, resample, (xa - x0, ya - y0, xb - xa, yb - ya)).to(torch.int64)
     for t in range(frames8.shape[0]):
-        face = resize_rgb8(frames8[t], None, h, w)[ya - y0:yb - y0, xa - x0:xb - x0].to(torch.int64)
+        if resample is not None:
+            face = faces[t]
+        else:
+            face = resize_rgb8(frames8[t], None, h, w)[ya - y0:yb - y0, xa - x0:xb - x0].to(torch.int64)
         out[t, ya:yb, xa:xb] = ((a * face + (255 - a) * s + 127) // 255).to(torch.uint8)
     return out
 
@@ -521,14 +689,14 @@ def rgb8_to_i420(frames_u8, matrix=None):
     return out[0] if single else out
 
 
-def paste_i420(src8, frames8, rect, feather, matrix=None):
+def paste_i420(src8, frames8, rect, feather, matrix=None, resample=None):
     """The pasted frames as planar YUV 4:2:0: rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather), matrix) -> (T, 3H/2, W) uint8
     at the portrait's size, H and W even (ValueError otherwise - nothing is padded or cropped).  Chroma is the 2 x 2 mean of the PASTED
     8-bit RGB samples, so a block that straddles the box edge or the feather mixes pasted and source pixels; it is never a blend
-    of chroma.  The definition `float_img_paste_i420` (image.paste_frames_device(out_format="i420")) is held to bit for bit."""
+    of chroma.  resample: as in paste_rgb8.  The definition `float_img_paste_i420` (image.paste_frames_device(out_format="i420")) is held to bit for bit."""
     if src8.dim() == 3 and (src8.shape[0] % 2 or src8.shape[1] % 2):
         raise ValueError("paste_i420: a %d x %d portrait has an odd side; 4:2:0 chroma needs even sides" % (src8.shape[0], src8.shape[1]))
-    return rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather), matrix)
+    return rgb8_to_i420(paste_rgb8(src8, frames8, rect, feather, resample), matrix)
 
 
 def y4m_rate(fps):

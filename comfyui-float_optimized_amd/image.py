@@ -2,6 +2,7 @@
 img_tensor_2_np_array, process_img's zero-bordered crop, cv2.resize(INTER_AREA), / 127.5 - 1 (utils/image.py, generate.py:29-39) -
 as HIP kernels on the raw ComfyUI IMAGE tensor.  The definition is host_models.image_to_rgb8 + host_models.resize_rgb8; the
 kernels work in integers from the quantiser on and give its bytes."""
+import collections
 import ctypes as C
 import fractions
 import logging
@@ -151,8 +152,124 @@ def pasted_frame_shape(H, W, fmt):
     return (3 * H // 2, W) if fmt == "i420" else (H, W, 3)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# bicubic / Lanczos resampling of 8-bit frames (`float_img_resample`, include/float_hip.h): what `resample=` selects on the paste
+# ---------------------------------------------------------------------------------------------------------------------------
+RESAMPLE_TABLES_KEPT = 8  # (sizes, window, filter, device) entries of the table cache: a clip uses one
+_resample_tables = collections.OrderedDict()
+
+
+def resample_table(n_in, n_out, filter, first=0, count=None):
+    """float_img_resample_plan: one axis's table for output indices first ... first + count - 1 -> (count, 2 + ksize) int32 on the
+    host, rows xmin, n, k[0 ... ksize - 1]: integer for integer host_models.resample_coeffs.  Host arithmetic in the library; no
+    GPU is touched.  The library's refusals (an unknown filter, sizes below 1, more than 255 taps) are ValueErrors."""
+    fid = host_models.resample_filter_id("resample_table", filter)
+    n_in, n_out, first = int(n_in), int(n_out), int(first)
+    count = n_out - first if count is None else int(count)
+    L = native.lib()
+    ints = int(L.float_img_resample_plan_ints(n_in, n_out, fid, count))
+    table = torch.empty(max(ints, 1), dtype=torch.int32)
+    native.check(L.float_img_resample_plan(n_in, n_out, fid, first, count, C.cast(table.data_ptr(), C.POINTER(C.c_int32)), ints))
+    return table[:ints].reshape(count, ints // count)
+
+
+def _resample_tables_device(device, fr_h, fr_w, h, w, filter, window):
+    """(tab_x, tab_y) on the device for a call of float_img_resample, None for an axis that keeps its size; made and uploaded
+    once per (sizes, window, filter, device) - once per clip on the paste routes - and kept for the next call."""
+    key = (str(device), fr_h, fr_w, h, w, filter, window)
+    tabs = _resample_tables.get(key)
+    if tabs is None:
+        xa, ya, wc, hc = window
+        tabs = (resample_table(fr_w, w, filter, xa, wc).to(device) if fr_w != w else None,
+                resample_table(fr_h, h, filter, ya, hc).to(device) if fr_h != h else None)  # blocking copies: complete on return
+        _resample_tables[key] = tabs
+        while len(_resample_tables) > RESAMPLE_TABLES_KEPT:
+            _resample_tables.popitem(last=False)
+    else:
+        _resample_tables.move_to_end(key)
+    return tabs
+
+
+class ResampleScratch:
+    """The device memory one resampled paste needs besides its output: `face`, the box-sized window of n frames, and `work`, the
+    intermediate of float_img_resample.  Made once by paste_scratch for the largest group of frames and handed to every
+    paste_frames_device(..., resample=, scratch=) of a clip."""
+
+    def __init__(self, face, work):
+        self.face, self.work = face, work
+
+
+def paste_window(H, W, rect):
+    """(xa, ya, xb, yb): the box rect = (x0, y0, w, h) clipped to an H x W image, as host_models.paste_rgb8 clips it; None when
+    the box misses the image."""
+    x0, y0, w, h = (int(v) for v in rect)
+    ya, yb, xa, xb = max(0, y0), min(H, y0 + h), max(0, x0), min(W, x0 + w)
+    return None if yb <= ya or xb <= xa else (xa, ya, xb, yb)
+
+
+def _resample_work_bytes(n, fr_h, fr_w, h, w, fid, window):
+    need = int(native.lib().float_img_resample_work_bytes(n, fr_h, fr_w, h, w, fid, *window))
+    if not need:
+        raise ValueError("resample: %d frames of %d x %d to %d x %d, window %r, are outside float_img_resample's limits (sides 1 ... 16384, "
+                         "at most 255 taps per sample)" % (n, fr_h, fr_w, h, w, tuple(window)))
+    return need
+
+
+def paste_scratch(src_hw, frame_hw, rect, n, resample, device):
+    """The ResampleScratch of pasting up to n frames of frame_hw at `rect` into a portrait of src_hw with resample=`resample`;
+    None when there is nothing to resample (resample None, or a box that misses the image)."""
+    if resample is None:
+        return None
+    fid = host_models.resample_filter_id("paste_scratch", resample)
+    win = paste_window(int(src_hw[0]), int(src_hw[1]), rect)
+    if win is None:
+        return None
+    xa, ya, xb, yb = win
+    x0, y0, w, h = (int(v) for v in rect)
+    need = _resample_work_bytes(int(n), int(frame_hw[0]), int(frame_hw[1]), h, w, fid, (xa - x0, ya - y0, xb - xa, yb - ya))
+    return ResampleScratch(torch.empty(int(n), yb - ya, xb - xa, 3, dtype=torch.uint8, device=device),
+                           torch.empty((need + 3) // 4, dtype=torch.int32, device=device))
+
+
 @torch.no_grad()
-def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None, matrix=None):
+def resample_frames_device(frames8, h, w, filter, window=None, out=None, work=None):
+    """float_img_resample: frames8 (T, h_f, w_f, 3) uint8 resampled to h x w by Pillow's rule with filter "bicubic" | "lanczos" ->
+    (T, h, w, 3) uint8 on the device, or with window = (xa, ya, wc, hc) only that part of it, (T, hc, wc, 3): bitwise
+    host_models.resample_rgb8(frames8, h, w, filter, window).  Host tensors are uploaded (device: that of frames8, else cuda:0).
+    out: a contiguous uint8 tensor of the result's shape on that device to write into; work: an int32 device tensor of at least
+    float_img_resample_work_bytes (default: torch's allocator).  The two tables come from float_img_resample_plan and are kept
+    on the device per (sizes, window, filter).  At most two launches on the current stream; nothing synchronises."""
+    fid = host_models.resample_filter_id("resample_frames_device", filter)
+    device = frames8.device if frames8.is_cuda else torch.device("cuda:0")
+    f = _u8_device(frames8, "frames8", 4, device)
+    T, fr_h, fr_w = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("resample_frames_device: the result %d x %d must be at least 1 x 1" % (h, w))
+    window = host_models.resample_window("resample_frames_device", h, w, window)
+    xa, ya, wc, hc = window
+    need = _resample_work_bytes(T, fr_h, fr_w, h, w, fid, window)
+    shape = (T, hc, wc, 3)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != device or not out.is_contiguous():
+            raise ValueError("resample_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
+                             % (shape, device, out.dtype, tuple(out.shape), out.device))
+        if work is None:
+            work = torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+        elif work.dtype != torch.int32 or work.device != device or not work.is_contiguous() or work.numel() * 4 < need:
+            raise ValueError("resample_frames_device: work must be a contiguous int32 tensor of at least %d bytes on %s" % (need, device))
+        tab_x, tab_y = _resample_tables_device(device, fr_h, fr_w, h, w, filter, window)
+        native.check(native.lib().float_img_resample(
+            C.c_void_p(f.data_ptr()), T, fr_h, fr_w, h, w, fid, xa, ya, wc, hc, C.c_void_p(tab_x.data_ptr()) if tab_x is not None else None,
+            C.c_void_p(tab_y.data_ptr()) if tab_y is not None else None, C.c_void_p(work.data_ptr()), work.numel() * 4,
+            C.c_void_p(out.data_ptr()), native.stream_ptr(device)))
+    return out
+
+
+@torch.no_grad()
+def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None, matrix=None, resample=None, scratch=None):
     """float_img_paste: frames8 (T, h, w, 3) uint8 - what the decoder's decode_u8 leaves in HBM - back in the portrait src8 (H, W,
     3) uint8 at the box rect = (x0, y0, w, h) in source coordinates (what InferenceAgent.host_inputs_placed returns; it may reach
     outside the image) -> (T, H, W, 3) uint8 on the device, bitwise host_models.paste_rgb8(src8, frames8, rect, feather).
@@ -163,8 +280,16 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
     out_format: None | "rgb" as above; "i420" is float_img_paste_i420, paste and colour conversion in one kernel -> (T, 3H/2, W)
     uint8 planar YUV 4:2:0, bitwise host_models.paste_i420(src8, frames8, rect, feather, matrix), half the bytes;
     H and W must be even (ValueError) and `out` is checked against that shape.  matrix: as host_models.yuv_matrix_id reads it
-    (None = BT.601 limited range; "auto" goes by the portrait's size); with RGB frames anything but None is a ValueError."""
+    (None = BT.601 limited range; "auto" goes by the portrait's size); with RGB frames anything but None is a ValueError.
+    resample: None as above; "bicubic" | "lanczos": the face is Pillow's resize of the frame with that filter instead of the front
+    end's rule - bitwise host_models.paste_rgb8 / paste_i420(..., resample=resample).  float_img_resample forms the window of the
+    box that lies in the image (two more launches, tables uploaded once per sizes), and the paste kernel above gets that window
+    as its frames, the clipped box as its rect and the feather of the unclipped one: its resize at equal sizes is the identity
+    and clipping moves no open side, so the bytes are the definition's.  A box that misses the image launches nothing new.
+    scratch: a ResampleScratch of paste_scratch for at least T frames (default: torch's allocator, per call)."""
     fmt = paste_format("paste_frames_device", out_format)
+    if resample is not None:
+        host_models.resample_filter_id("paste_frames_device", resample)  # refused before anything is uploaded
     if fmt != "i420":
         host_models.yuv_matrix_for("paste_frames_device", matrix, fmt)  # refused before anything is uploaded
     device = frames8.device if frames8.is_cuda else (src8.device if src8.is_cuda else torch.device("cuda:0"))
@@ -190,6 +315,16 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
             raise ValueError("paste_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
                              % (shape, device, out.dtype, tuple(out.shape), out.device))
         L = native.lib()
+        win = paste_window(H, W, (x0, y0, w, h)) if resample is not None else None
+        if win is not None:
+            xa, ya, xb, yb = win
+            if scratch is None:
+                scratch = paste_scratch((H, W), f.shape[1:3], (x0, y0, w, h), T, resample, device)
+            elif scratch.face.shape[0] < T or tuple(scratch.face.shape[1:]) != (yb - ya, xb - xa, 3) or scratch.face.device != device:
+                raise ValueError("paste_frames_device: scratch was made for another paste (%s for %d frames of the window %r)"
+                                 % (tuple(scratch.face.shape), T, win))
+            f = resample_frames_device(f, h, w, resample, (xa - x0, ya - y0, xb - xa, yb - ya), out=scratch.face[:T], work=scratch.work)
+            x0, y0, w, h = xa, ya, xb - xa, yb - ya  # `feather` stays the unclipped box's
         if fmt == "i420":
             native.check(L.float_img_paste_i420(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),
                                                 x0, y0, w, h, feather, m, C.c_void_p(out.data_ptr()),

@@ -16,6 +16,7 @@ MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argumen
 IMG_MATRIX_BT601_LIMITED = 0  # FLOAT_IMG_MATRIX_BT601_LIMITED: the `matrix` argument of float_img_paste_i420
 # FLOAT_DEC_MATRIX_* and their FLOAT_IMG_MATRIX_* twins: bit 1 = BT.709, bit 2 = full range (host_models.YUV_MATRICES)
 MATRIX_BT709_LIMITED, MATRIX_BT601_FULL, MATRIX_BT709_FULL = 2, 4, 6
+IMG_FILTER_BICUBIC, IMG_FILTER_LANCZOS = 0, 1  # FLOAT_IMG_FILTER_*: the `filter` argument of float_img_resample[_plan] (host_models.RESAMPLE_FILTERS)
 ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "heun2": 3, "heun3": 4}
 DTYPES = {"bf16": FLOAT_DT_BF16, "bfloat16": FLOAT_DT_BF16, "fp16": FLOAT_DT_FP16, "float16": FLOAT_DT_FP16,
           "fp32": FLOAT_DT_FP32, "float32": FLOAT_DT_FP32}  # fp32: the verification mode of the FMT and decoder operators
@@ -146,6 +147,10 @@ _SIGNATURES = {
     "float_img_front": (C.c_int, [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_img_paste": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]),
     "float_img_paste_i420": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]),
+    "float_img_resample_plan_ints": (C.c_size_t, [C.c_int32] * 4),
+    "float_img_resample_plan": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_size_t]),
+    "float_img_resample_work_bytes": (C.c_size_t, [C.c_int32] * 10),
+    "float_img_resample": (C.c_int, [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "float_jpg_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_jpg_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_jpg_work_bytes_padded": (C.c_size_t, [C.c_int32] * 4),

@@ -224,6 +224,20 @@ def _check_place(what, place, device):
     return place
 
 
+def _check_resample(what, resample, place):
+    """`resample` of a pasted producer: None or a filter of host_models.RESAMPLE_FILTERS, and only where something is pasted"""
+    if resample is not None:
+        host_models.resample_filter_id(what, resample)
+        if place is None:
+            raise ValueError("%s: resample=%r needs a place (the crops are not resized unless they are pasted back)" % (what, resample))
+    return resample
+
+
+def _paste_scratch(hot, place, n, resample):
+    """the scratch of pasting up to n crops with `resample`, owned by the caller beside its crops (None: nothing to resample)"""
+    return image.paste_scratch(place.size, (hot.size, hot.size), place.rect, n, resample, hot.device) if place is not None else None
+
+
 class _FrameSink:
     """What FloatHotPath._ring does per slot for stream_to_host: a slot is a pinned (L,) + frame_shape buffer, and the one device
     staging buffer is shared by all of them (safe in stream order)."""
@@ -254,9 +268,10 @@ class _PasteSink:
     format and, for I420, the portrait's even sides are checked when the sink is made: at the call."""
     name = "stream_to_host_pasted"
 
-    def __init__(self, hot, place, feather, out_format=None, name=None, matrix=None):
+    def __init__(self, hot, place, feather, out_format=None, name=None, matrix=None, resample=None):
         self.hot, self.place, self.feather = hot, place, feather
         self.name = name or self.name
+        self.resample = _check_resample(self.name, resample, place)
         self.fmt = image.paste_format(self.name, out_format)
         H, W = place.size  # "auto" goes by the size of the frames that leave: the portrait's
         self.matrix = host_models.yuv_matrix_for(self.name, matrix, self.fmt, W, H) if matrix is not None else None
@@ -269,6 +284,7 @@ class _PasteSink:
         dev, R = self.hot.device, self.hot.size
         self.crops = torch.empty(n, R, R, 3, dtype=torch.uint8, device=dev)
         self.pasted = torch.empty((n,) + self.frame_shape, dtype=torch.uint8, device=dev)
+        self.scratch = _paste_scratch(self.hot, self.place, n, self.resample)
 
     def open(self, slots):
         L = self.hot.cfg.num_frames_for_clip
@@ -281,7 +297,7 @@ class _PasteSink:
         n = rows.shape[0]
         self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
         image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=self.pasted[:n], out_format=self.fmt,
-                                  matrix=self.matrix)
+                                  matrix=self.matrix, resample=self.resample, scratch=self.scratch)
         host.copy_(self.pasted[:n], non_blocking=True)
 
     def enqueue(self, slot, s_r_d, rows):
@@ -297,8 +313,9 @@ class _JpegSink:
     are the pasted H x W ones, and the window's 8-bit crops go through one shared device buffer."""
     name = "stream_to_jpeg"
 
-    def __init__(self, hot, quality, restart, place=None, feather=None, pad=None):
+    def __init__(self, hot, quality, restart, place=None, feather=None, pad=None, resample=None):
         self.hot, self.quality, self.restart, self.place, self.feather, self.pad = hot, quality, restart, place, feather, pad
+        self.resample = _check_resample(self.name, resample, place)
 
     def open(self, slots):
         dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
@@ -309,6 +326,7 @@ class _JpegSink:
                      off_host=torch.empty(L + 1, dtype=torch.int64, pin_memory=True)) for _ in range(slots)]
         self.s_copy, self.work = torch.cuda.Stream(dev), None
         self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev) if self.place is not None else None
+        self.scratch = _paste_scratch(self.hot, self.place, L, self.resample)
         return ring
 
     def _encode(self, slot, n):
@@ -321,7 +339,8 @@ class _JpegSink:
             self.hot.dec.decode_u8(s_r_d, rows, out=slot["u8"][:n])
         else:
             self.hot.dec.decode_u8(s_r_d, rows, out=self.crops[:n])
-            image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=slot["u8"][:n])
+            image.paste_frames_device(self.place.src8, self.crops[:n], self.place.rect, self.feather, out=slot["u8"][:n],
+                                      resample=self.resample, scratch=self.scratch)
         self._encode(slot, n)
         slot["off_host"][:n + 1].copy_(slot["off"][:n + 1], non_blocking=True)
 
@@ -344,8 +363,9 @@ class _PngSink(_JpegSink):
     files' CRCs beside the offsets on both sides."""
     name = "stream_to_png"
 
-    def __init__(self, hot, band, place=None, feather=None):
+    def __init__(self, hot, band, place=None, feather=None, resample=None):
         self.hot, self.band, self.place, self.feather = hot, band, place, feather
+        self.resample = _check_resample(self.name, resample, place)
 
     def open(self, slots):
         dev, L, R = self.hot.device, self.hot.cfg.num_frames_for_clip, self.hot.size
@@ -357,6 +377,7 @@ class _PngSink(_JpegSink):
                      crc_host=torch.empty(L, dtype=torch.int32, pin_memory=True)) for _ in range(slots)]
         self.s_copy, self.work = torch.cuda.Stream(dev), None
         self.crops = torch.empty(L, R, R, 3, dtype=torch.uint8, device=dev) if self.place is not None else None
+        self.scratch = _paste_scratch(self.hot, self.place, L, self.resample)
         return ring
 
     def _encode(self, slot, n):
@@ -624,7 +645,7 @@ class FloatHotPath:
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     def stream_to_host_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15,
-                              noise=None, place=None, feather=None, slots=3, out_format=None, matrix=None):
+                              noise=None, place=None, feather=None, slots=3, out_format=None, matrix=None, resample=None):
         """stream_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: a generator of
         FrameBlock(first, last, frames), `frames` a (last - first, H, W, 3) uint8 view of a pinned ring slot, bitwise
         host_models.paste_rgb8(place.src8, the window's 8-bit crops, place.rect, feather).  place: a Placement (the portrait on
@@ -636,15 +657,18 @@ class FloatHotPath:
         host_models.paste_i420 of the same operands; float_img_paste_i420 pastes and converts in one kernel, and the device buffer
         of pasted frames, the pinned slots and the copy are 3HW/2 bytes per frame - half of the above.  H and W must be even:
         a ValueError here, at the call.  matrix: the colour matrix of I420 frames (host_models.yuv_matrix_id; "auto" goes by the
-        portrait's size); with RGB frames anything but None is a ValueError, also at the call."""
+        portrait's size); with RGB frames anything but None is a ValueError, also at the call.
+        resample (default None: the above): "bicubic" | "lanczos" - the face is Pillow's resize of the crop with that filter
+        (float_img_resample in front of the paste: image.paste_frames_device), bitwise host_models.paste_rgb8 / paste_i420(...,
+        resample=resample); its tables are uploaded once and its scratch sits beside the two shared buffers."""
         place = _check_place("stream_to_host_pasted", place, self.device)
-        sink = _PasteSink(self, place, feather, out_format, matrix=matrix)
+        sink = _PasteSink(self, place, feather, out_format, matrix=matrix, resample=resample)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     @torch.no_grad()
     def generate_pasted(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                        place=None, feather=None, out=None, return_rd=False, out_format=None, matrix=None):
+                        place=None, feather=None, out=None, return_rd=False, out_format=None, matrix=None, resample=None):
         """generate_to_host(out_dtype=torch.uint8) with every frame pasted back into the portrait on the device: the chain of the
         whole clip, then per group of num_frames_for_clip frames decode_u8, float_img_paste and one non-blocking copy into the
         pinned (T, H, W, 3) uint8 result - device memory stays at 50 crops and 50 pasted frames whatever T is.  The result is
@@ -652,9 +676,9 @@ class FloatHotPath:
         out_format="i420" (default None = "rgb": the above): the result is (T, 3H/2, W) uint8 planar YUV 4:2:0, bitwise
         host_models.paste_i420; float_img_paste_i420 pastes and converts in one kernel, and the device buffer of pasted frames, the
         result and the copies are 3HW/2 bytes per frame.  H and W must be even - a ValueError before anything is enqueued - and
-        an `out` of another shape than the format's is a ValueError.  matrix: as in stream_to_host_pasted."""
+        an `out` of another shape than the format's is a ValueError.  matrix, resample: as in stream_to_host_pasted."""
         place = _check_place("generate_pasted", place, self.device)
-        sink = _PasteSink(self, place, feather, out_format, name="generate_pasted", matrix=matrix)
+        sink = _PasteSink(self, place, feather, out_format, name="generate_pasted", matrix=matrix, resample=resample)
         self.require_no_stream("generate_pasted")
         if feats is not None:
             self.dec.set_feats(feats)
@@ -755,7 +779,7 @@ class FloatHotPath:
 
     @torch.no_grad()
     def generate_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                         quality=90, restart=None, return_rd=False, place=None, feather=None, pad=None):
+                         quality=90, restart=None, return_rd=False, place=None, feather=None, pad=None, resample=None):
         """generate_to_host for one clip (B = 1) with the frames leaving as baseline JPEG files (jpeg.JpegFrames in pinned host
         memory): the chain, decode_u8 of the whole clip, float_jpg_encode on the 8-bit frames in HBM, ONE host read of the
         offsets, then offsets[T] bytes across PCIe - the files, not the frames.  File i is bitwise
@@ -766,8 +790,10 @@ class FloatHotPath:
         frame i of generate_pasted, and T * H * W * 3 more bytes of HBM are held while it runs.  float_jpg_encode takes sides that
         are multiples of 16: another portrait size is a ValueError here, before anything runs; nothing is padded - unless
         pad="edge" (default None) opts in: float_jpg_encode_padded then takes any portrait size, replicating the last row and column
-        into the partial MCUs, and file i is jpeg_encode_rgb8(..., pad="edge") of the same frame (restart=None: ceil(W / 16))."""
+        into the partial MCUs, and file i is jpeg_encode_rgb8(..., pad="edge") of the same frame (restart=None: ceil(W / 16)).
+        resample: as in generate_pasted (with place only)."""
         jpeg.check_pad(pad)
+        _check_resample("generate_to_jpeg", resample, place)
         if place is not None:
             place = _check_place("generate_to_jpeg", place, self.device)
             image.require_jpeg_sides("generate_to_jpeg", *place.size, pad=pad)
@@ -778,12 +804,13 @@ class FloatHotPath:
         with torch.cuda.device(self.device):
             u8 = self.dec.decode_u8(s_r, _rows(r_d))
             if place is not None:
-                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather)
+                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather, resample=resample,
+                                               scratch=_paste_scratch(self, place, u8.shape[0], resample))
             frames = jpeg.encode_jpeg_host(u8, quality, restart, pad=pad)
         return (frames, r_d) if return_rd else frames
 
     def stream_to_jpeg(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                       quality=90, restart=None, slots=3, place=None, feather=None, pad=None):
+                       quality=90, restart=None, slots=3, place=None, feather=None, pad=None, resample=None):
         """generate_to_jpeg as a generator: one JpegBlock(first, last, frames) per FMT window, in frame order, the same files as the
         whole-clip call.  The contract is stream_to_host's: `frames` (a jpeg.JpegFrames) lives in one of `slots` pinned ring
         buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (AviMjpegWriter.write
@@ -798,8 +825,9 @@ class FloatHotPath:
         once more into a larger buffer.
         place, feather: as in generate_to_jpeg - the files are those of the pasted H x W frames, a slot's device buffer holds 50 of
         them and one more buffer of 50 crops is shared; a portrait whose sides are no multiples of 16 is a ValueError at the call,
-        unless pad="edge" (as in generate_to_jpeg; the overflow re-encode pads the same way)."""
+        unless pad="edge" (as in generate_to_jpeg; the overflow re-encode pads the same way).  resample: as in generate_pasted."""
         jpeg.check_pad(pad)
+        _check_resample("stream_to_jpeg", resample, place)
         quality = int(quality)
         if not 1 <= quality <= 100:
             raise ValueError("stream_to_jpeg: quality (%d) must be 1 ... 100" % quality)
@@ -808,13 +836,13 @@ class FloatHotPath:
             place = _check_place("stream_to_jpeg", place, self.device)
             image.require_jpeg_sides("stream_to_jpeg", *place.size, pad=pad)
             width = place.size[1]
-        sink = _JpegSink(self, quality, jpeg.pad_restart(width, pad) if restart is None else int(restart), place, feather, pad)
+        sink = _JpegSink(self, quality, jpeg.pad_restart(width, pad) if restart is None else int(restart), place, feather, pad, resample)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 
     @torch.no_grad()
     def generate_to_png(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                        band=None, return_rd=False, place=None, feather=None):
+                        band=None, return_rd=False, place=None, feather=None, resample=None):
         """generate_to_host for one clip (B = 1) with the frames leaving as LOSSLESS PNG files (png.PngFrames in pinned host memory):
         the chain, decode_u8 of the whole clip, float_png_encode on the 8-bit frames in HBM, ONE host read of the offsets, then
         offsets[T] bytes across PCIe - the files, not the frames.  File i decodes to frame i of
@@ -823,7 +851,8 @@ class FloatHotPath:
         device: T * size * size * 3 bytes of HBM while it runs, and as much again for the files.
         place (a Placement; default None: nothing above changes): the 8-bit crops are pasted back into the portrait on the device
         (float_img_paste, `feather` as in generate_pasted) and the encoder codes the H x W frames, of any size up to 16384 - file i
-        is png_encode_rgb8 of frame i of generate_pasted."""
+        is png_encode_rgb8 of frame i of generate_pasted.  resample: as in generate_pasted (with place only)."""
+        _check_resample("generate_to_png", resample, place)
         if place is not None:
             place = _check_place("generate_to_png", place, self.device)
         H, W = place.size if place is not None else (self.size, self.size)
@@ -835,12 +864,13 @@ class FloatHotPath:
         with torch.cuda.device(self.device):
             u8 = self.dec.decode_u8(s_r, _rows(r_d))
             if place is not None:
-                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather)
+                u8 = image.paste_frames_device(place.src8, u8, place.rect, feather, resample=resample,
+                                               scratch=_paste_scratch(self, place, u8.shape[0], resample))
             frames = png.encode_png_host(u8, band)
         return (frames, r_d) if return_rd else frames
 
     def stream_to_png(self, r_s, wa, we, s_r, feats, nfe, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, seed=15, noise=None,
-                      band=None, slots=3, place=None, feather=None):
+                      band=None, slots=3, place=None, feather=None, resample=None):
         """generate_to_png as a generator: one PngBlock(first, last, frames) per FMT window, in frame order, the same files as the
         whole-clip call.  The contract is stream_to_jpeg's: `frames` (a png.PngFrames) lives in one of `slots` pinned ring
         buffers, is complete when it is yielded and OVERWRITTEN after the generator has been advanced again (ApngWriter.write has
@@ -848,11 +878,12 @@ class FloatHotPath:
         enqueued before the first next(); while the generator is open every other producer on this object raises RuntimeError.
         Per slot: a device buffer of 50 8-bit frames, a device and a pinned buffer of their raw size for the files, and the offsets
         and CRCs on both sides.  Files beyond the slot's room (noise: 9 / 8 of the raw size) are encoded once more into a larger
-        buffer.  place, feather: as in generate_to_png."""
+        buffer.  place, feather, resample: as in generate_to_png."""
+        _check_resample("stream_to_png", resample, place)
         if place is not None:
             place = _check_place("stream_to_png", place, self.device)
         H, W = place.size if place is not None else (self.size, self.size)
-        sink = _PngSink(self, host_models.png_check_band(H, W, band), place, feather)
+        sink = _PngSink(self, host_models.png_check_band(H, W, band), place, feather, resample)
         self._check_stream_call(sink.name, slots, wa)
         return self._ring(sink, (r_s, wa, we, nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale), s_r, feats, seed, noise, int(slots))
 

@@ -486,7 +486,7 @@ class InferenceAgent:
         return self._stream_clip("InferenceAgent.stream_device_jpeg", s, a, emo, seed, _stream_device_jpeg)
 
     def write_video(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                    quality=90, fps=None, paste_back=False, feather=None, pad=None):
+                    quality=90, fps=None, paste_back=False, feather=None, pad=None, resample=None):
         """A playable file: host_inputs, stream_device_jpeg, and host_models.AviMjpegWriter on `path` (a path or a seekable binary
         file object) - Motion JPEG in an AVI container with the clip's audio as a 16-bit PCM track: the AUDIO item's own samples
         at its own rate, channels mixed to mono (not the normalised 16 kHz waveform the model hears), one `01wb` chunk behind the
@@ -494,14 +494,16 @@ class InferenceAgent:
         paste_back=True: the frames are the user's portrait with the generated face pasted back (stream_pasted_jpeg, `feather` as
         in infer_pasted) and the file is written at the portrait's size, whose sides must be multiples of 16 (ValueError
         otherwise, before the file is opened) unless pad="edge" (as in infer_pasted_jpeg) opts in to any size: a 1920 x 1080
-        portrait then gives a 1920 x 1080 file.  pad has no say without paste_back: the crops are model-size frames."""
+        portrait then gives a 1920 x 1080 file.  pad has no say without paste_back: the crops are model-size frames.
+        resample: as in infer_pasted; with paste_back=False anything but None is a ValueError, before the file is opened."""
         o = self.opt
         fps = o.fps if fps is None else fps
+        self._paste_call("write_video", ref_img, resample=resample, paste_back=paste_back)
         if paste_back:
             img = ref_img[0] if ref_img.dim() == 4 else ref_img
             height, width = int(img.shape[0]), int(img.shape[1])
             blocks = self.stream_pasted_jpeg(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, quality,
-                                             pad=pad)
+                                             pad=pad, resample=resample)
         else:
             height = width = o.input_size
             with torch.no_grad():
@@ -521,11 +523,18 @@ class InferenceAgent:
             return w.frames
 
     # ------------------------------------------------------------------ paste back: the frames in the user's portrait
-    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None, pad=None, matrix=None):
+    def _paste_call(self, what, ref_img, jpeg_out=False, out_format=None, pad=None, matrix=None, resample=None, paste_back=True):
         """What a pasted producer refuses at the call: with JPEG output, a portrait whose sides float_jpg_encode does not take
         (pad="edge": none) or a pad that is neither None nor "edge"; with
         out_format="i420", a portrait with an odd side; an out_format that is none of None, "rgb", "i420"; a `matrix` with RGB
-        frames or one host_models.yuv_matrix_id does not know.  Returns the id of `matrix` ("auto": by the portrait's size), None for None."""
+        frames or one host_models.yuv_matrix_id does not know; a `resample` that is no filter of host_models.RESAMPLE_FILTERS, or any
+        without paste_back (only a pasted crop is resized).  Returns the id of `matrix` ("auto": by the portrait's size), None for None."""
+        if resample is not None:
+            host_models.resample_filter_id(what, resample)
+            if not paste_back:
+                raise ValueError("%s: resample=%r needs paste_back=True (the crops leave at the model's size, nothing is resized)" % (what, resample))
+        if not paste_back:
+            return None
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         if jpeg_out:
             require_jpeg_sides(what, int(img.shape[0]), int(img.shape[1]), pad)
@@ -536,7 +545,7 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                     feather=None, out=None, out_format=None, matrix=None):
+                     feather=None, out=None, out_format=None, matrix=None, resample=None):
         """run_inference whose frames are the user's portrait with the generated face pasted back: (T, H, W, 3) uint8 in pinned host
         memory at the portrait's own size, bitwise host_models.paste_rgb8(place.src8, infer_device(s, a, out_dtype=torch.uint8),
         place.rect, feather) with (s, a, place) = host_inputs_placed(ref_img, ref_audio, no_crop).  The 8-bit crops never leave
@@ -550,20 +559,25 @@ class InferenceAgent:
         one kernel and half the bytes cross PCIe.  Any even size is taken (1920 x 1080); a portrait with an odd side is a
         ValueError at this call, before anything runs - nothing is padded or cropped.  FLOAT_AMD_RANGE applies as above.
         matrix: the colour matrix of I420 frames, as in infer_device; "auto" goes by the portrait's size (BT.709 limited range
-        when W >= 1280 or H > 576 - what players assume for untagged video of that size).  A ValueError with RGB frames."""
-        matrix = self._paste_call("infer_pasted", ref_img, out_format=out_format, matrix=matrix)
+        when W >= 1280 or H > 576 - what players assume for untagged video of that size).  A ValueError with RGB frames.
+        resample (default None: the above, byte for byte): "bicubic" | "lanczos" - the crop is brought to the box's size by Pillow's
+        Image.resize rule with that filter (float_img_resample, two more launches per 50 frames) instead of the front end's rule,
+        which enlarges linearly: bitwise host_models.paste_rgb8 / paste_i420(..., resample=resample).  For a box larger than the
+        model's frame - a face in an HD portrait, no_crop - the pasted face is as sharp as an image tool would make it.  Another
+        name is a ValueError at this call."""
+        matrix = self._paste_call("infer_pasted", ref_img, out_format=out_format, matrix=matrix, resample=resample)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             host = self.G.generate_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
                                           noise=noise, place=place, feather=feather, out=out, out_format=out_format,
-                                          matrix=matrix)
+                                          matrix=matrix, resample=resample)
             torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
             if self.check_range("InferenceAgent.infer_pasted", allow_rebuild=True) != "rebuilt":
                 return host  # otherwise once more, in the wider types
 
     def stream_pasted(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                      feather=None, slots=3, out_format=None, matrix=None):
+                      feather=None, slots=3, out_format=None, matrix=None, resample=None):
         """The streaming sibling of infer_pasted: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in
         frame order - concatenated, the frames infer_pasted returns for the same inputs and seed.  The ring rules are
         stream_device's: `frames` is a (last - first, H, W, 3) uint8 view of one of `slots` pinned buffers, complete when yielded,
@@ -571,15 +585,15 @@ class InferenceAgent:
         every other producer on this agent raises RuntimeError.  FLOAT_AMD_RANGE is applied once after the last block (auto acts
         as warn); FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored.
         out_format="i420": `frames` is a (last - first, 3H/2, W) uint8 view, the frames of infer_pasted(out_format="i420"); the
-        pinned slots are half the size.  A portrait with an odd side raises ValueError here, at the call.  matrix: as in
+        pinned slots are half the size.  A portrait with an odd side raises ValueError here, at the call.  matrix, resample: as in
         infer_pasted."""
         self._check_stream_call("stream_pasted", slots)
-        matrix = self._paste_call("stream_pasted", ref_img, out_format=out_format, matrix=matrix)
+        matrix = self._paste_call("stream_pasted", ref_img, out_format=out_format, matrix=matrix, resample=resample)
 
         def _stream_pasted(c, noise, place):
             return self.G.stream_to_host_pasted(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale,
                                                 e_cfg_scale, noise=noise, place=place, feather=feather, slots=int(slots),
-                                                out_format=out_format, matrix=matrix)
+                                                out_format=out_format, matrix=matrix, resample=resample)
         return self._stream_placed("InferenceAgent.stream_pasted", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted)
 
     def write_y4m(self, path_or_file, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False,
@@ -598,22 +612,25 @@ class InferenceAgent:
                                      paste_back, feather, slots)
 
     def write_y4m_matrix(self, path_or_file, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E",
-                         no_crop=False, seed=25, fps=None, paste_back=False, feather=None, slots=3, matrix=None):
+                         no_crop=False, seed=25, fps=None, paste_back=False, feather=None, slots=3, matrix=None, resample=None):
         """write_y4m with the colour matrix of the frames to choose.  matrix: as in infer_device / infer_pasted - None = BT.601
         limited range (then this is write_y4m, byte for byte), "bt709", "bt601-full", "bt709-full", their ids, or "auto": by the
         size of the frames that leave, the model's with paste_back=False and the portrait's with paste_back=True (BT.709 limited
         range when W >= 1280 or H > 576, what players assume for untagged video).  It is resolved once, before anything runs or a
         file is opened, and the one id goes to the producer and to the writer, so the tag cannot disagree with the samples: full
         range is written as XCOLORRANGE=FULL.  Y4M has no tag for the matrix itself: host_models.yuv_ffmpeg_args(matrix) are the
-        arguments that state it to ffmpeg.  (A method of its own because write_y4m's parameter list is held as it is.)"""
+        arguments that state it to ffmpeg.  (A method of its own because write_y4m's parameter list is held as it is.)
+        resample: as in infer_pasted (write_y4m's held parameter list has no room for it: this is the Y4M call that takes it); with
+        paste_back=False anything but None is a ValueError, before anything runs or a file is opened."""
         o = self.opt
         fps = o.fps if fps is None else fps
+        self._paste_call("write_y4m", ref_img, resample=resample, paste_back=paste_back)
         if paste_back:
             img = ref_img[0] if ref_img.dim() == 4 else ref_img
             height, width = int(img.shape[0]), int(img.shape[1])
-            matrix = self._paste_call("write_y4m", ref_img, out_format="i420", matrix=matrix)
+            matrix = self._paste_call("write_y4m", ref_img, out_format="i420", matrix=matrix, resample=resample)
             blocks = self.stream_pasted(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, slots,
-                                        out_format="i420", matrix=matrix)
+                                        out_format="i420", matrix=matrix, resample=resample)
         else:
             height = width = o.input_size
             matrix = self._check_stream_call("write_y4m", slots, out_format="i420", matrix=matrix)
@@ -636,39 +653,41 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                          feather=None, quality=90, restart=None, pad=None):
+                          feather=None, quality=90, restart=None, pad=None, resample=None):
         """infer_pasted with the frames leaving as baseline JPEG files: a jpeg.JpegFrames in pinned host memory, file i bitwise
         host_models.jpeg_encode_rgb8(infer_pasted(...)[i], quality, restart).  Paste and encoder run on the device and only the
         files cross PCIe.  float_jpg_encode takes sides that are multiples of 16: a portrait of another size is a ValueError at
         this call, before anything runs - nothing is padded.  pad="edge" (default None) opts in to any portrait size:
         float_jpg_encode_padded replicates the last row and column into the partial 16 x 16 MCUs, the files carry the true size, file
         i is bitwise jpeg_encode_rgb8(infer_pasted(...)[i], quality, restart, pad="edge"), and restart=None is ceil(W / 16) MCUs.
-        FLOAT_AMD_RANGE applies as in infer_device_jpeg; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
-        self._paste_call("infer_pasted_jpeg", ref_img, jpeg_out=True, pad=pad)
+        FLOAT_AMD_RANGE applies as in infer_device_jpeg; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored.
+        resample: as in infer_pasted - the files are those of infer_pasted(..., resample=resample)."""
+        self._paste_call("infer_pasted_jpeg", ref_img, jpeg_out=True, pad=pad, resample=resample)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             frames = self.G.generate_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                             noise=noise, quality=quality, restart=restart, place=place, feather=feather, pad=pad)
+                                             noise=noise, quality=quality, restart=restart, place=place, feather=feather, pad=pad,
+                                             resample=resample)
             if self.check_range("InferenceAgent.infer_pasted_jpeg", allow_rebuild=True) != "rebuilt":
                 return frames  # otherwise once more, in the wider types
 
     def stream_pasted_jpeg(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                           feather=None, quality=90, restart=None, slots=3, pad=None):
+                           feather=None, quality=90, restart=None, slots=3, pad=None, resample=None):
         """The streaming sibling of infer_pasted_jpeg: a generator of JpegBlock(first, last, frames) under the ring rules of
         stream_device_jpeg - concatenated, the files infer_pasted_jpeg returns.  slots < 2, a quality outside 1 ... 100 or a portrait
         whose sides are no multiples of 16 (without pad="edge", which is infer_pasted_jpeg's) raise ValueError here, at the call.
         FLOAT_AMD_RANGE is applied once after the last block (auto acts as warn); FLOAT_AMD_VERIFY is NOT applied and
-        FLOAT_AMD_OVERLAP is ignored."""
+        FLOAT_AMD_OVERLAP is ignored.  resample: as in infer_pasted, refused at the call too."""
         self._check_stream_call("stream_pasted_jpeg", slots)
         if not 1 <= int(quality) <= 100:
             raise ValueError("stream_pasted_jpeg: quality (%r) must be 1 ... 100" % (quality,))
-        self._paste_call("stream_pasted_jpeg", ref_img, jpeg_out=True, pad=pad)
+        self._paste_call("stream_pasted_jpeg", ref_img, jpeg_out=True, pad=pad, resample=resample)
 
         def _stream_pasted_jpeg(c, noise, place):
             return self.G.stream_to_jpeg(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
                                          noise=noise, quality=int(quality), restart=restart, slots=int(slots), place=place, feather=feather,
-                                         pad=pad)
+                                         pad=pad, resample=resample)
         return self._stream_placed("InferenceAgent.stream_pasted_jpeg", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_jpeg)
 
     # ------------------------------------------------------------------ lossless frames: PNG files and APNG clips
@@ -715,49 +734,56 @@ class InferenceAgent:
 
     @torch.no_grad()
     def infer_pasted_png(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                         feather=None, band=None):
+                         feather=None, band=None, resample=None):
         """infer_pasted with the frames leaving as LOSSLESS PNG files: a png.PngFrames in pinned host memory; file i decodes to
         infer_pasted(...)[i] bit for bit and is bitwise host_models.png_encode_rgb8 of it.  Paste and encoder run on the device and
         only the files cross PCIe.  A portrait of any size up to 16384 x 16384 is taken.  FLOAT_AMD_RANGE applies as in
-        infer_device_png; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        infer_device_png; FLOAT_AMD_VERIFY is NOT applied and FLOAT_AMD_OVERLAP is ignored.  resample: as in infer_pasted - the
+        files decode to infer_pasted(..., resample=resample)."""
+        self._paste_call("infer_pasted_png", ref_img, resample=resample)
         band = self._png_call("infer_pasted_png", band, ref_img)
         s, a, place = self.host_inputs_placed(ref_img, ref_audio, no_crop)
         while True:
             c, noise = self._clip_inputs(s, a, emo, seed)
             frames = self.G.generate_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                            noise=noise, band=band, place=place, feather=feather)
+                                            noise=noise, band=band, place=place, feather=feather, resample=resample)
             if self.check_range("InferenceAgent.infer_pasted_png", allow_rebuild=True) != "rebuilt":
                 return frames  # otherwise once more, in the wider types
 
     def stream_pasted_png(self, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                          feather=None, band=None, slots=3):
+                          feather=None, band=None, slots=3, resample=None):
         """The streaming sibling of infer_pasted_png: a generator of PngBlock(first, last, frames) under the ring rules of
         stream_device_png - concatenated, the files infer_pasted_png returns.  slots < 2 or a band outside its rule raise
         ValueError here, at the call.  FLOAT_AMD_RANGE is applied once after the last block (auto acts as warn); FLOAT_AMD_VERIFY
-        is NOT applied and FLOAT_AMD_OVERLAP is ignored."""
+        is NOT applied and FLOAT_AMD_OVERLAP is ignored.  resample: as in infer_pasted, refused at the call too."""
         self._check_stream_call("stream_pasted_png", slots)
+        self._paste_call("stream_pasted_png", ref_img, resample=resample)
         band = self._png_call("stream_pasted_png", band, ref_img)
 
         def _stream_pasted_png(c, noise, place):
             return self.G.stream_to_png(c["r_s"], c["wa"], c["we"], c["s_r"], None, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale,
-                                        noise=noise, band=band, slots=int(slots), place=place, feather=feather)
+                                        noise=noise, band=band, slots=int(slots), place=place, feather=feather,
+                                        resample=resample)
         return self._stream_placed("InferenceAgent.stream_pasted_png", ref_img, ref_audio, no_crop, emo, seed, _stream_pasted_png)
 
     def write_apng(self, path, ref_img, ref_audio, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", no_crop=False, seed=25,
-                   fps=None, paste_back=False, feather=None, band=None):
+                   fps=None, paste_back=False, feather=None, band=None, resample=None):
         """A lossless clip in one file: host_inputs, stream_device_png, and host_models.ApngWriter on `path` (a path or a seekable
         binary file object) - an animated PNG that browsers and ffmpeg open, every frame bit for bit the 8-bit frame.  The
         zlib streams are copied as the device wrote them and every chunk CRC comes from the device's per-frame CRCs.  APNG carries
         NO AUDIO: the clip's sound has to be kept separately (write_video writes a file with an audio track).  fps defaults to
         opt.fps.  Returns the number of frames written.
         paste_back=True: the frames are the user's portrait with the generated face pasted back (stream_pasted_png, `feather` as
-        in infer_pasted) and the file is written at the portrait's size, any size up to 16384."""
+        in infer_pasted) and the file is written at the portrait's size, any size up to 16384.  resample: as in infer_pasted; with
+        paste_back=False anything but None is a ValueError, before the file is opened."""
         o = self.opt
         fps = o.fps if fps is None else fps
+        self._paste_call("write_apng", ref_img, resample=resample, paste_back=paste_back)
         if paste_back:
             img = ref_img[0] if ref_img.dim() == 4 else ref_img
             height, width = int(img.shape[0]), int(img.shape[1])
-            blocks = self.stream_pasted_png(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, band)
+            blocks = self.stream_pasted_png(ref_img, ref_audio, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, no_crop, seed, feather, band,
+                                            resample=resample)
         else:
             height = width = o.input_size
             band = self._png_call("write_apng", band)

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
+/* Stays 6: float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
+ * Lanczos resampling of 8-bit frames on the device), float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
  * float_img_paste (the generated frames back in the source portrait on the device),
  * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device) and
  * float_jpg_encode_padded / float_jpg_work_bytes_padded (the same for sides that are no multiples of 16),
@@ -601,7 +602,8 @@ int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t chan
  *           rect_h < src_h).  a = min(255, 255 (d + 1) / (feather + 1)) (integer division); no open side or feather == 0: a = 255.
  *   blend   out = (a face + (255 - a) src + 127) / 255 (integer division: round to nearest, 255 is odd).
  * Limits: source and box sides 1 ... 16384, frame sides 1 ... 1024 (with them every sum of the resize fits 32 bits: S <= 255 *
- * 2^20, positions <= 2^24), feather 0 ... 16384, n_frames >= 1, |rect_x|, |rect_y| <= 2^30.  All three pointers are DEVICE
+ * 2^20, positions <= 2^24) or, per axis, the box's own side (the scale of that axis is 1: frames that float_img_resample below
+ * already brought to the box's size pass at any size the box may have), feather 0 ... 16384, n_frames >= 1, |rect_x|, |rect_y| <= 2^30.  All three pointers are DEVICE
  * pointers to contiguous HWC bytes of any alignment; out must not overlap the inputs.  An output frame is 3 src_h src_w < 2^31
  * bytes; frame bases are formed in 64 bits, so out may exceed 4 GiB.
  * Enqueues one kernel on `stream` (one per 2^30 workgroups: thousands of frames); no scratch, no atomics, allocates nothing,
@@ -634,6 +636,54 @@ enum { FLOAT_IMG_MATRIX_BT709_LIMITED = 2, FLOAT_IMG_MATRIX_BT601_FULL = 4, FLOA
 int float_img_paste_i420(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* frames8, int32_t n_frames, int32_t fr_h,
                          int32_t fr_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t feather, int32_t matrix,
                          uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------- bicubic / Lanczos resampling -- */
+/* n_frames 8-bit RGB frames (n_frames, fr_h, fr_w, 3) in HBM resampled to box_h x box_w by Pillow's Image.resize rule for 8-bit
+ * images (src/libImaging/Resample.c) with the BICUBIC or the LANCZOS filter - of which only the window win_x, win_y, win_w, win_h
+ * is formed: out is (n_frames, win_h, win_w, 3) uint8.  Bitwise host_models.resample_rgb8 in the host mirror, and through it
+ * Pillow 12.2.0.  It is what gives the paste-back routes a filter with negative lobes: the face of float_img_paste above is
+ * enlarged by the linear rule, and a caller who wants it sharper resamples the window of the box that lies in the image here and
+ * hands float_img_paste the box-sized result (its resize at equal sizes is the identity).
+ *
+ * One axis n_in -> n_out, output index xx (float_img_resample_plan; C double and libm's sin, no HIP call, usable without a GPU):
+ *     scale = n_in / n_out;  fs = max(scale, 1.0);  support = S * fs  (S = 2 bicubic, 3 lanczos);  ss = 1.0 / fs
+ *     ksize = (int)ceil(support) * 2 + 1
+ *     center = (xx + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5));  xmax = min(n_in, (int)(center + support + 0.5));  n = xmax - xmin
+ *     w[x] = f((x + xmin - center + 0.5) * ss), x = 0 ... n - 1;  ww = their sum in that order;  w[x] /= ww if ww != 0
+ *     k[x] = (int)(-0.5 + w[x] * 2^22) if w[x] < 0 else (int)(0.5 + w[x] * 2^22);  k[x] = 0 for n <= x < ksize
+ *     bicubic (a = -0.5): |x| < 1: ((a + 2) x - (a + 3)) x x + 1;  |x| < 2: (((x - 5) x + 8) x - 4) a;  else 0
+ *     lanczos: -3 <= x < 3: sinc(x) sinc(x / 3), sinc(0) = 1, sinc(x) = sin(pi x) / (pi x);  else 0
+ * `table` receives, for each of the `count` indices from `first` on, the 2 + ksize int32 values xmin, n, k[0 ... ksize - 1];
+ * float_img_resample_plan_ints is count * (2 + ksize), the least table_ints (0 for arguments the planner refuses).  Refused
+ * (FLOAT_E_INVALID): a filter other than the two, a size outside 1 ... 2^30, indices outside 0 ... n_out, ksize > 255 (shrinking by
+ * more than about 42 x with Lanczos, 63 x with bicubic), a short table.  Every row satisfies 255 sum|k| + 2^21 < 2^31.
+ *
+ * On the device (float_img_resample), in int32 and with >> the arithmetic shift, no float anywhere:
+ *     one axis   out = clamp((2^21 + sum_{x < n} k[x] in[xmin + x]) >> 22, 0, 255)
+ *     two axes   the horizontal pass first, over only the input rows the window's rows reference, rounded to 8 bits into `work`;
+ *                then the vertical pass.  A pass whose two sizes are equal (fr_w == box_w, fr_h == box_h) is skipped, as in Pillow;
+ *                with both equal the window is copied.
+ *   tab_x     DEVICE copy of the table of float_img_resample_plan(fr_w, box_w, filter, win_x, win_w, ...); ignored (may be NULL)
+ *             when fr_w == box_w.  tab_y: the same of (fr_h, box_h, filter, win_y, win_h).  The kernels trust xmin and n: a table
+ *             that was made for other sizes reads outside the frames.
+ *   work      DEVICE scratch of at least float_img_resample_work_bytes(...) bytes (0 for arguments the call refuses), 16-byte
+ *             aligned, no zeroing needed.
+ * Limits: frame and window sides 1 ... 16384, box sides 1 ... 2^30, the window inside the box, n_frames >= 1.  frames8 and out are
+ * DEVICE pointers to contiguous HWC bytes of any alignment and must not overlap.  A lane forms four neighbouring pixels; with
+ * win_w % 4 == 0 and out 4-byte aligned it stores them as three dwords, otherwise as bytes; the bytes stored are the same.
+ * Enqueues at most two kernels on `stream` (per 65535 frames); no atomics, allocates nothing, synchronises nothing, two calls
+ * give equal bytes.  An argument outside these rules returns FLOAT_E_INVALID, with a message naming the function and the
+ * argument, before any HIP call. */
+enum { FLOAT_IMG_FILTER_BICUBIC = 0, FLOAT_IMG_FILTER_LANCZOS = 1 };
+size_t float_img_resample_plan_ints(int32_t n_in, int32_t n_out, int32_t filter, int32_t count);
+int float_img_resample_plan(int32_t n_in, int32_t n_out, int32_t filter, int32_t first, int32_t count, int32_t* table,
+                            size_t table_ints);
+size_t float_img_resample_work_bytes(int32_t n_frames, int32_t fr_h, int32_t fr_w, int32_t box_h, int32_t box_w, int32_t filter,
+                                     int32_t win_x, int32_t win_y, int32_t win_w, int32_t win_h);
+int float_img_resample(const uint8_t* frames8, int32_t n_frames, int32_t fr_h, int32_t fr_w, int32_t box_h, int32_t box_w,
+                       int32_t filter, int32_t win_x, int32_t win_y, int32_t win_w, int32_t win_h, const int32_t* tab_x,
+                       const int32_t* tab_y, void* work, size_t work_bytes, uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------- JPEG encoder -- */
 /* n_frames 8-bit RGB frames in HBM - the (n, h, w, 3) buffer float_dec_frames_u8 writes - -> n complete baseline JPEG files
