@@ -8,7 +8,7 @@ import importlib
 
 __version__ = "0.1.0"
 
-_SUBMODULES = ("config", "weights", "native", "fmt", "decoder", "encoder", "audio", "image", "jpeg", "png", "pipeline", "distributed", "host_models")
+_SUBMODULES = ("config", "weights", "native", "fmt", "decoder", "encoder", "audio", "image", "jpeg", "png", "pipeline", "distributed", "host_models", "face")
 
 
 def __getattr__(name):

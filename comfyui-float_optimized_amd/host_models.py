@@ -19,10 +19,14 @@ this package).  What is left is tensor plumbing:
     `float_jpg_encode` are held to bit for bit; numpy, no imaging library) and a Motion-JPEG AVI writer (AviMjpegWriter)
   * lossless PNG in integer arithmetic (png_filter_rows, png_code_lengths, png_encode_rgb8, crc32_combine: the definition the
     kernels of `float_png_encode` are held to bit for bit) and an animated-PNG writer (ApngWriter)
+  * the S3FD face detector written from the published network (sfd_forward, sfd_decode_dense, sfd_nms, sfd_detect): the
+    definition the kernels of `float_sfd_*` (face.py in this package) are held to, and the FLOAT_AMD_FACE_DETECTOR switch of
+    process_img
 """
 import fractions
 import logging
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -501,7 +505,7 @@ def preprocess_audio(waveform, sample_rate, target_rate=16000, device=None):
     return ((w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7))[None]
 
 
-def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=None):
+def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=None, detector=None):
     """The reference's face-aligned crop (utils/image.py:135-180) on an (H,W,3) float image in [0,1]: detect faces on a
     360-px-high copy, take box `index`, crop a square of `margin` x the larger half side around its centre from the
     zero-bordered image, resize to input_size.  The detector (`face_alignment`, SFD) is an optional dependency: without it
@@ -512,26 +516,41 @@ def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=Non
     only thing that reaches the host, nothing is cropped or resized here (only the shape of img_hwc is read), and the function
     returns (rect, bbox): rect = (x0, y0, w, h), the crop window in source coordinates, which may reach outside the image -
     what image.preprocess_image_device takes.  Images of 360 px height or less (the reference's INTER_CUBIC route) ignore
-    `front` and take the host route above."""
+    `front` and take the host route above.
+    detector: a callable view -> [[x1, y1, x2, y2, score], ...] on the (view_h, view_w, 3) uint8 view (a device tensor on the
+    `front` route, a host tensor otherwise) - the device detector (face.FaceDetectorHIP.detect); a caller passes it only where
+    its weight file exists (face.find_sfd_weights).  FLOAT_AMD_FACE_DETECTOR (face_detector_mode, read per call) chooses:
+    auto = the `face_alignment` package if it can be built, else `detector` if given, else the centre square with a warning;
+    device = `detector` (ValueError without one); package = the package alone; off = the centre square.  detector=None with
+    the switch unset is the code path as it was before the switch."""
     H, Wd = int(img_hwc.shape[0]), int(img_hwc.shape[1])
     mult = 360.0 / H
     use_front = front is not None and mult < 1.0
     bboxes = None
     fa = None
-    try:  # ANY failure to obtain a detector (package absent, a stub or broken install, model files unreachable) takes the
-        fa = _face_detector()  # reference's no-face branch below instead of failing the node at its default face_align=True
-    except Exception as e:  # noqa: BLE001
-        if logger is not None:
-            logger.warning("face_align=True, but no face detector is available (%s: %s): no face detection, the centre square "
-                           "of the image is used (install face_alignment for the reference's crop)" % (type(e).__name__, e))
-    if fa is not None:
+    mode = face_detector_mode()
+    if mode == "device" and detector is None:
+        raise ValueError("FLOAT_AMD_FACE_DETECTOR=device, but this call has no device detector (process_img(detector=...))")
+    if mode in ("auto", "package"):
+        try:  # ANY failure to obtain a detector (package absent, a stub or broken install, model files unreachable) takes the
+            fa = _face_detector()  # reference's no-face branch below instead of failing the node at its default face_align=True
+        except Exception as e:  # noqa: BLE001
+            if (mode == "package" or detector is None) and logger is not None:
+                logger.warning("face_align=True, but no face detector is available (%s: %s): no face detection, the centre square "
+                               "of the image is used (install face_alignment for the reference's crop).  %s"
+                               % (type(e).__name__, e, SFD_WEIGHTS_HINT))
+    use_device = fa is None and detector is not None and mode in ("auto", "device")
+    if fa is not None or use_device:
         import numpy as np
         if use_front:
-            small = front(360).cpu().numpy()
+            small = front(360)
         else:
             small = F.interpolate(img_hwc.permute(2, 0, 1)[None], scale_factor=mult, mode="area" if mult < 1.0 else "bicubic")
-            small = (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()
-        det = fa.face_detector.detect_from_image(np.ascontiguousarray(small))
+            small = (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8)
+        if use_device:
+            det = detector(small)
+        else:
+            det = fa.face_detector.detect_from_image(np.ascontiguousarray(small.cpu().numpy()))
         bboxes = [(int(x1 / mult), int(y1 / mult), int(x2 / mult), int(y2 / mult), sc) for (x1, y1, x2, y2, sc) in (det or []) if sc > 0.95]
     if not bboxes:
         if bboxes is not None and logger is not None:
@@ -575,6 +594,181 @@ def _face_detector():
         import face_alignment
         _FA = face_alignment.FaceAlignment(face_alignment.LandmarksType.TWO_D, flip_input=False)
     return _FA
+
+
+# ---------------------------------------------------------------------------------------------- the S3FD face detector
+# Written from the published network (Zhang et al., "S3FD: Single Shot Scale-invariant Face Detector", ICCV 2017; VGG-16 trunk,
+# six detection heads) with the state-dict key names and shapes of the `face_alignment` package's s3fd module, so that its weight
+# file loads with a strict check.  The package is not a dependency and parity with it is not pinned.
+FACE_DETECTOR_MODES = ("auto", "device", "package", "off")
+SFD_WEIGHTS_HINT = ("Without the package, the built-in detector takes over once its weight file is at FLOAT_AMD_SFD_WEIGHTS or "
+                    "<models>/face_alignment/s3fd.safetensors (also s3fd.pth, s3fd-619a316812.pth, or torch hub's checkpoint cache).")
+SFD_MEAN_BGR = (104.0, 117.0, 123.0)
+# (name, cin, cout, k, stride, pad); every trunk conv is followed by ReLU, `pool` = max_pool2d(2, 2) in floor mode behind it
+SFD_TRUNK = [("conv1_1", 3, 64, 3, 1, 1), ("conv1_2", 64, 64, 3, 1, 1), "pool",
+             ("conv2_1", 64, 128, 3, 1, 1), ("conv2_2", 128, 128, 3, 1, 1), "pool",
+             ("conv3_1", 128, 256, 3, 1, 1), ("conv3_2", 256, 256, 3, 1, 1), ("conv3_3", 256, 256, 3, 1, 1), "pool",
+             ("conv4_1", 256, 512, 3, 1, 1), ("conv4_2", 512, 512, 3, 1, 1), ("conv4_3", 512, 512, 3, 1, 1), "pool",
+             ("conv5_1", 512, 512, 3, 1, 1), ("conv5_2", 512, 512, 3, 1, 1), ("conv5_3", 512, 512, 3, 1, 1), "pool",
+             ("fc6", 512, 1024, 3, 1, 3), ("fc7", 1024, 1024, 1, 1, 0),
+             ("conv6_1", 1024, 256, 1, 1, 0), ("conv6_2", 256, 512, 3, 2, 1),
+             ("conv7_1", 512, 128, 1, 1, 0), ("conv7_2", 128, 256, 3, 2, 1)]
+# (feature map, channels, L2Norm or not, conf channels) per level; stride of level i = 2^(i + 2)
+SFD_LEVELS = [("conv3_3", 256, True, 4), ("conv4_3", 512, True, 2), ("conv5_3", 512, True, 2),
+              ("fc7", 1024, False, 2), ("conv6_2", 512, False, 2), ("conv7_2", 256, False, 2)]
+SFD_MIN_SIDE, SFD_MAX_SIDE = 16, 4096
+
+
+def face_detector_mode():
+    """FLOAT_AMD_FACE_DETECTOR, read per call: auto (default) | device | package | off."""
+    mode = os.environ.get("FLOAT_AMD_FACE_DETECTOR", "auto").strip().lower() or "auto"
+    if mode not in FACE_DETECTOR_MODES:
+        raise ValueError("FLOAT_AMD_FACE_DETECTOR=%r: one of %s" % (mode, ", ".join(FACE_DETECTOR_MODES)))
+    return mode
+
+
+def sfd_state_shapes():
+    """{key: shape} of the s3fd module's state dict: what a weight file must hold, no more and no less."""
+    shapes = {}
+    for layer in SFD_TRUNK:
+        if layer != "pool":
+            name, cin, cout, k = layer[:4]
+            shapes[name + ".weight"], shapes[name + ".bias"] = (cout, cin, k, k), (cout,)
+    for name, c, norm, nconf in SFD_LEVELS:
+        head = name + ("_norm" if norm else "")
+        if norm:
+            shapes[head + ".weight"] = (c,)
+        for what, co in (("conf", nconf), ("loc", 4)):
+            shapes["%s_mbox_%s.weight" % (head, what)], shapes["%s_mbox_%s.bias" % (head, what)] = (co, c, 3, 3), (co,)
+    return shapes
+
+
+def sfd_check_state(state, where="state dict"):
+    """The strict check: a missing or extra key, or a wrong shape, is a ValueError that names it."""
+    want = sfd_state_shapes()
+    missing, extra = sorted(set(want) - set(state)), sorted(set(state) - set(want))
+    if missing or extra:
+        raise ValueError("%s is not an s3fd state dict: missing %s, unexpected %s" % (where, missing or "none", extra or "none"))
+    for k, shp in want.items():
+        if tuple(state[k].shape) != shp:
+            raise ValueError("%s: '%s' has shape %s, s3fd has %s" % (where, k, tuple(state[k].shape), shp))
+    return state
+
+
+def sfd_map_sizes(H, W):
+    """[(h, w)] of the six feature maps of an H x W view: floor pooling, fc6's growth by 4, the two stride-2 convs."""
+    sizes, at = [], {}
+    h, w = int(H), int(W)
+    for layer in SFD_TRUNK:
+        if layer == "pool":
+            h, w = h // 2, w // 2
+        else:
+            name, _, _, k, s, p = layer
+            h, w = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+            at[name] = (h, w)
+    for name, _, _, _ in SFD_LEVELS:
+        sizes.append(at[name])
+    return sizes
+
+
+def _sfd_pool(x):
+    if x.shape[-2] < 2 or x.shape[-1] < 2:  # floor mode down to an empty map (torch refuses it): fc6 then sees its padding alone
+        return x[:, :, :x.shape[-2] // 2, :x.shape[-1] // 2]
+    return F.max_pool2d(x, 2, 2)
+
+
+def sfd_forward(state, rgb8):
+    """The 12 maps of the (H, W, 3) uint8 RGB view: [conf_0 (1,2,h0,w0), loc_0 (1,4,h0,w0), conf_1, ...], after level 0's
+    max-out and before the softmax.  Runs in the dtype and on the device of `state`'s tensors (fp32 on the CPU is the
+    definition)."""
+    w0 = state["conv1_1.weight"]
+    H, W = int(rgb8.shape[0]), int(rgb8.shape[1])
+    if min(H, W) < SFD_MIN_SIDE or max(H, W) > SFD_MAX_SIDE or rgb8.shape[-1] != 3:
+        raise ValueError("the detector's view must be (H, W, 3) with sides in %d ... %d, got %s" % (SFD_MIN_SIDE, SFD_MAX_SIDE, tuple(rgb8.shape)))
+    x = torch.as_tensor(rgb8).to(w0.device).float().flip(-1) - torch.tensor(SFD_MEAN_BGR, device=w0.device)
+    x = x.permute(2, 0, 1)[None].to(w0.dtype)
+    feats = {}
+    for layer in SFD_TRUNK:
+        if layer == "pool":
+            x = _sfd_pool(x)
+            continue
+        name, _, _, _, s, p = layer
+        if p > 1:  # fc6: pad by hand, so that a 0 x 0 map (a side below 32) still gives the 4 x 4 of its padding
+            x, p = F.pad(x, (p, p, p, p)), 0
+        x = F.relu(F.conv2d(x, state[name + ".weight"], state[name + ".bias"], stride=s, padding=p))
+        feats[name] = x
+    maps = []
+    for i, (name, _, norm, nconf) in enumerate(SFD_LEVELS):
+        f, head = feats[name], name + ("_norm" if norm else "")
+        if norm:
+            f = f / (f.float().pow(2).sum(dim=1, keepdim=True).sqrt() + 1e-10).to(f.dtype) * state[head + ".weight"].view(1, -1, 1, 1)
+        conf = F.conv2d(f, state[head + "_mbox_conf.weight"], state[head + "_mbox_conf.bias"], padding=1)
+        loc = F.conv2d(f, state[head + "_mbox_loc.weight"], state[head + "_mbox_loc.bias"], padding=1)
+        if nconf == 4:
+            conf = torch.cat([conf[:, :3].max(dim=1, keepdim=True).values, conf[:, 3:4]], dim=1)
+        maps += [conf, loc]
+    return maps
+
+
+def sfd_decode_dense(maps):
+    """Every position of the 12 maps decoded, in position order (level, y, x): a (P, 5) float64 array of
+    [x1, y1, x2, y2, score].  Level i has stride s = 2^(i + 2) - level 3 too, although fc6 enlarged its map, and its
+    positions beyond the image are kept; prior centre (s / 2 + x s, s / 2 + y s), prior size 4 s, variances (0.1, 0.2);
+    score = softmax(conf)[1] = 1 / (1 + exp(c0 - c1))."""
+    import numpy as np
+    rows = []
+    for i in range(len(maps) // 2):
+        conf = maps[2 * i].detach().float().cpu().numpy().astype(np.float64)[0]
+        loc = maps[2 * i + 1].detach().float().cpu().numpy().astype(np.float64)[0]
+        s = float(2 ** (i + 2))
+        h, w = conf.shape[-2:]
+        ys, xs = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+        with np.errstate(over="ignore"):
+            score = 1.0 / (1.0 + np.exp(conf[0] - conf[1]))
+            bw, bh = 4 * s * np.exp(0.2 * loc[2]), 4 * s * np.exp(0.2 * loc[3])
+        cx, cy = s / 2 + xs * s + loc[0] * 0.1 * 4 * s, s / 2 + ys * s + loc[1] * 0.1 * 4 * s
+        rows.append(np.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2, score], axis=-1).reshape(-1, 5))
+    return np.concatenate(rows, axis=0) if rows else np.zeros((0, 5))
+
+
+def sfd_decode(maps, score_thr):
+    """The candidates: rows of sfd_decode_dense with score > score_thr, in position order."""
+    dense = sfd_decode_dense(maps)
+    return dense[dense[:, 4] > score_thr]
+
+
+def sfd_nms(boxes, iou_thr):
+    """Greedy NMS of (N, 5) rows given in position order: indices in keep order.  Descending score, ties by position ascending
+    (a stable sort: what numpy's argsort leaves open); areas and overlaps with the `+1` convention; a box is dropped when its
+    IoU with a kept box EXCEEDS iou_thr."""
+    import numpy as np
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 5)
+    x1, y1, x2, y2, sc = b[:, 0], b[:, 1], b[:, 2], b[:, 3], b[:, 4]
+    areas = (x2 - x1 + 1) * (y2 - y1 + 1)
+    order = np.argsort(-sc, kind="stable")
+    keep = []
+    while order.size > 0:
+        i, rest = order[0], order[1:]
+        keep.append(int(i))
+        w = np.maximum(0.0, np.minimum(x2[i], x2[rest]) - np.maximum(x1[i], x1[rest]) + 1)
+        h = np.maximum(0.0, np.minimum(y2[i], y2[rest]) - np.maximum(y1[i], y1[rest]) + 1)
+        ovr = w * h / (areas[i] + areas[rest] - w * h)
+        order = rest[ovr <= iou_thr]
+    return keep
+
+
+def sfd_select(dense, score_thr=0.5, iou_thr=0.3):
+    """Dense rows -> the detections.  The package's detect_from_image takes candidates above 0.05, runs the NMS and then keeps
+    score > 0.5; a box's fate in greedy NMS depends on boxes of HIGHER score only, so filtering by a score threshold commutes
+    with it: the filter runs first here and the 0.05 pass is dropped (tests/test_face_detect.py states it on random boxes)."""
+    cand = dense[dense[:, 4] > score_thr]
+    return [[float(v) for v in cand[i]] for i in sfd_nms(cand, iou_thr)]
+
+
+def sfd_detect(state, rgb8, score_thr=0.5, iou_thr=0.3):
+    """[[x1, y1, x2, y2, score], ...] in keep order: what the package's detect_from_image returns for the view."""
+    with torch.no_grad():
+        return sfd_select(sfd_decode_dense(sfd_forward(state, rgb8)), score_thr, iou_thr)
 
 
 EMOTION_LABELS = ["angry", "disgust", "fear", "happy", "neutral", "sad", "surprise"]  # FLOAT.py:390

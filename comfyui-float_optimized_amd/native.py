@@ -61,6 +61,10 @@ class EncCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("size", "dim", "dim_motion", "dtype")]
 
 
+class SfdCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "max_h", "max_w", "max_candidates", "max_boxes")]
+
+
 class AudCfg(C.Structure):
     _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
                [(n, C.c_int32) for n in ("hidden", "layers", "heads", "intermediate", "pos_k", "pos_groups", "dim_w", "only_last",
@@ -159,6 +163,13 @@ _SIGNATURES = {
     "float_png_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
     "float_png_tables": (C.c_int, [C.POINTER(C.c_int32)]),
+    "float_sfd_create": (C.c_int, [C.POINTER(SfdCfg), C.POINTER(FloatTensor), C.c_int32, C.POINTER(C.c_void_p)]),
+    "float_sfd_destroy": (None, [C.c_void_p]),
+    "float_sfd_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "float_sfd_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "float_sfd_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "float_sfd_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "float_sfd_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -10,6 +10,7 @@ from ... import host_models, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
+from ...face import FaceDetectorHIP, find_sfd_weights, load_sfd_state
 from ...image import (detector_view_device, front_takes, image_to_device, paste_format, preprocess_image_device, require_even_sides,
                       require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
@@ -93,7 +94,7 @@ class InferenceAgent:
         if self.G is None:
             return
         torch.cuda.current_stream(self.rank).synchronize()
-        for op in [self.G.fmt, self.G.dec, self.enc, self.audio_encoder, self.emotion_encoder] + list(self.G._fmt_batched.values()):
+        for op in [self.G.fmt, self.G.dec, self.enc, self.audio_encoder, self.emotion_encoder, self.face] + list(self.G._fmt_batched.values()):
             if op is not None:
                 op.close()
         if self.emotion_encoder is not None:
@@ -109,6 +110,8 @@ class InferenceAgent:
         self._noise_pin = self._noise_pin_b = self._noise_pin_r = None  # pinned noise of one clip / a batch / a ragged batch (_draw_noise)
         self._feat_slots = []      # per batch item, the encoder's skip maps copied aside (infer_device_batch)
         self._side_stream = None   # the speech-emotion model's stream (_cond_stream)
+        self.face = None           # the face detector (float_sfd_*), built on first use (_face_detector)
+        self._face_key = None      # (weight file, dtype) it was built from
 
     @property
     def resident(self):
@@ -272,6 +275,39 @@ class InferenceAgent:
             return source_rgb8_device(img, getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000"), self.rank)
         return host_models.image_to_rgb8(img, "discard_alpha").to(self.rank, non_blocking=True).contiguous()
 
+    def _face_detector(self):
+        """The `detector=` of host_models.process_img for this call: the device detector where FLOAT_AMD_FACE_DETECTOR allows it
+        and its weight file is found (face.find_sfd_weights; never downloaded), else None.  device: a missing file is an error.
+        The handle is built when the callable is first used - in auto mode an installed `face_alignment` package goes first and
+        nothing is built - and is freed with the other operators in offload()."""
+        mode = host_models.face_detector_mode()
+        if mode in ("package", "off"):
+            return None
+        path = find_sfd_weights()
+        if path is None:
+            if mode == "device":
+                raise FileNotFoundError("FLOAT_AMD_FACE_DETECTOR=device, but no s3fd weight file was found.  " + host_models.SFD_WEIGHTS_HINT)
+            return None
+        return lambda view: self._detect_faces(path, view)
+
+    def _detect_faces(self, path, view):
+        """S3FD on the (h, w, 3) uint8 view - on the device already (image.detector_view_device) or host-made (the H <= 360
+        route: uploaded) - with the handle built on first use.  Only the box rows and the two counts come back.
+        FLOAT_AMD_SFD_DTYPE = fp16 (default) | bf16 | fp32: fp32 is the remedy where check_range reports the detector."""
+        from ... import native as _native
+        key = (path, _native.canon_dtype(os.environ.get("FLOAT_AMD_SFD_DTYPE", "fp16")))
+        if self.face is None or self._face_key != key:
+            if self.face is not None:
+                self.face.close()
+            self.face = FaceDetectorHIP(load_sfd_state(path), self.rank, dtype=key[1])
+            self._face_key = key
+        h, w = int(view.shape[0]), int(view.shape[1])
+        if min(h, w) < host_models.SFD_MIN_SIDE or h > self.face.max_hw[0] or w > self.face.max_hw[1]:
+            main_logger.warning("face_align=True: a %d x %d detector view is outside the device detector's sizes (%d ... %d x %d): "
+                                "no face detection", h, w, host_models.SFD_MIN_SIDE, self.face.max_hw[0], self.face.max_hw[1])
+            return []
+        return self.face.detect(view)
+
     def _host_inputs(self, ref_img, ref_audio, no_crop, placed):
         """The one body of host_inputs and host_inputs_placed: (s, a, place), place None unless `placed`."""
         o = self.opt
@@ -293,7 +329,8 @@ class InferenceAgent:
             rect = None
             if not no_crop:  # generate.py:77-78
                 rect, _ = host_models.process_img(dimg, o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger,
-                                                  front=lambda view_h: detector_view_device(dimg, view_h, rgba, bkg))
+                                                  front=lambda view_h: detector_view_device(dimg, view_h, rgba, bkg),
+                                                  detector=self._face_detector())
             if ch == 3 and (H, Wd) == (o.input_size, o.input_size) and rect is not None and tuple(rect) == (0, 0, Wd, H):
                 # the crop turned out to be the whole image (a square portrait without a detected face): nothing to convert,
                 # crop or resize after all, so this is the case of the lines below, bitwise
@@ -307,7 +344,8 @@ class InferenceAgent:
             img = host_models.image_to_rgb8(img, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0
         bbox = (0, 0, Wd, H)
         if not no_crop:  # generate.py:77-78
-            img, bbox = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger)
+            img, bbox = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger,
+                                                detector=self._face_detector())
         # The raw tensors cross PCIe first (3 MB + 0.6 MB for a 10-s clip) and the elementwise / reduction plumbing runs on the
         # device: on the host the same ops cost 1-29 ms per clip (torch's 128-thread intra-op pool on sub-megabyte tensors),
         # as much as a quarter of the whole clip.  The reference moves its slices to the device first too (nodes.py:193-201).
@@ -803,7 +841,8 @@ class InferenceAgent:
         if self.G is None:
             return {}
         counts = self.G.range_counts(reset)
-        for name, op in (("encoder", self.enc), ("audio", self.audio_encoder), ("speech_emotion", self.emotion_encoder)):
+        for name, op in (("encoder", self.enc), ("audio", self.audio_encoder), ("speech_emotion", self.emotion_encoder),
+                         ("face_detector", self.face)):
             if op is not None and op.dtype == "fp16":
                 counts[name] = op.saturation(reset)
         return counts

@@ -224,6 +224,24 @@ def synth_encoder_state(size=512, dim=512, dim_motion=20, seed=0):
     return sd
 
 
+def synth_sfd_state(seed=0):
+    """S3FD face-detector weights with the key names and shapes of the `face_alignment` package's s3fd module
+    (host_models.sfd_state_shapes): He-initialised convs (std sqrt(2 / fan_in): activations keep their scale through the
+    ReLU trunk), small biases, L2Norm weights 10 / 8 / 5 as the published network initialises them.  conv1_1 carries 1 / 64 on
+    top: its input is the mean-subtracted image in 0 ... 255 units, and without it every later activation is O(100), the logits
+    of the three heads without an L2Norm are +-400 and their scores are all exactly 0 or 1 - nothing a selection can be tested on."""
+    from .host_models import sfd_state_shapes
+    sd = {}
+    for k, shp in sfd_state_shapes().items():
+        if len(shp) == 4:
+            sd[k] = _randn(seed, k, shp, math.sqrt(2.0 / (shp[1] * shp[2] * shp[3])) / (64.0 if k == "conv1_1.weight" else 1.0))
+        elif k.endswith(".bias"):
+            sd[k] = _randn(seed, k, shp, 0.02)
+        else:
+            sd[k] = torch.full(shp, {"conv3_3_norm": 10.0, "conv4_3_norm": 8.0, "conv5_3_norm": 5.0}[k[:-len(".weight")]])
+    return sd
+
+
 def fir_buffer_states(size=64, seed=0):
     """(encoder state, decoder state) of synth_*_state(size, seed) whose FIR BUFFERS outside the up-sampling StyledConvs are not
     make_kernel([1,3,3,1]) - what a checkpoint may hold and the reference's strict load takes over (tests/golden/fir_buffers.npz):

@@ -766,6 +766,49 @@ int float_png_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w
                      uint32_t* crcs, void* work, size_t work_bytes, void* stream);
 int float_png_tables(int32_t lengths[8 * 257]);
 
+/* ---------------------------------------------------------------- face detector --- */
+/* S3FD (VGG-16 trunk, six detection heads) on the detector's view of the portrait, once per clip: what the reference's
+ * process_img (utils/image.py:135-180) asks the `face_alignment` package for.  The definition is host_models.sfd_forward /
+ * sfd_decode_dense / sfd_nms / sfd_detect, written from the published network with the package's state-dict keys
+ * (`conv1_1.weight` ... `conv7_2_mbox_loc.bias`); parity with the package itself is not pinned.
+ *   conv1_1 is a direct kernel on the uint8 view (BGR flip, mean (104, 117, 123), bias, ReLU); every other conv is an implicit
+ *   GEMM on MFMA (operands of `dtype`, fp32 accumulation, NHWC); the two heads of a level run as one conv of 8 or 6 channels,
+ *   zero-padded to 16; 2 x 2 max-pool (floor mode) and L2Norm (fp32 sums) are kernels of their own.  16-bit stores are
+ *   range-tracked (float_sfd_saturation, see float_fmt_saturation).
+ *   Post-processing: every position is decoded into dense rows [x1, y1, x2, y2, score] in position order (level, y, x); ONE
+ *   workgroup compacts the rows with score > score_thr in that order (prefix scan, no atomic cursor), ranks them by (score
+ *   descending, position ascending) and runs the greedy NMS (`+1` areas; dropped when IoU > iou_thr).
+ * Views: (H, W, 3) uint8 RGB on the device, 16 <= H <= max_h, 16 <= W <= max_w, both at most 4096.  The workspace lives in the
+ * handle and is sized from max_h x max_w at create time; detect / maps / post allocate nothing, synchronise nothing and only
+ * launch kernels on `stream`, and two calls on the same view give equal bytes.  A null handle or pointer, or a size outside
+ * these rules, returns FLOAT_E_INVALID before any HIP call. */
+typedef struct {
+  int32_t dtype;           /* FLOAT_DT_* of activations / conv weights (FLOAT_DT_FP32 = verification mode) */
+  int32_t max_h, max_w;    /* largest view, each 16 ... 4096 */
+  int32_t max_candidates;  /* capacity of the selection kernel, 1 ... 2048 (a face yields tens of candidates) */
+  int32_t max_boxes;       /* rows of `boxes`, 1 ... max_candidates */
+} float_sfd_cfg_t;
+
+typedef struct float_sfd float_sfd_t;
+
+int float_sfd_create(const float_sfd_cfg_t* cfg, const float_tensor_t* tensors, int32_t n_tensors, float_sfd_t** out);
+void float_sfd_destroy(float_sfd_t* h);
+/* boxes: (max_boxes, 5) fp32, rows [x1, y1, x2, y2, score] in keep order; counts: 2 x int32 = {kept, candidates}, both device
+ * memory.  Both counts are the true numbers: with kept > max_boxes only the first max_boxes rows are written, and with
+ * candidates > max_candidates nothing is selected (kept = 0) - the call still succeeds and the dense rows stay valid, so the
+ * caller selects from float_sfd_dense with the definition instead (face.FaceDetectorHIP does).  Nothing is truncated silently. */
+int float_sfd_detect(float_sfd_t* h, const void* rgb8, int32_t H, int32_t W, float score_thr, float iou_thr, float* boxes, int32_t* counts,
+                     void* stream);
+/* The verification hook: the 12 maps as sfd_forward returns them (after level 0's max-out, before the softmax), fp32 NCHW in
+ * one buffer of 6 P floats, P = the number of positions: per level conf (2, h, w) then loc (4, h, w), levels in order. */
+int float_sfd_maps(float_sfd_t* h, const void* rgb8, int32_t H, int32_t W, float* maps12, void* stream);
+/* The post-processing alone, on maps in the layout of float_sfd_maps that the caller supplies for an H x W view. */
+int float_sfd_post(float_sfd_t* h, const float* maps12, int32_t H, int32_t W, float score_thr, float iou_thr, float* boxes, int32_t* counts,
+                   void* stream);
+/* The dense rows (P, 5) of the last detect / post call on the handle, copied on `stream`. */
+int float_sfd_dense(float_sfd_t* h, float* scores_boxes, void* stream);
+int float_sfd_saturation(float_sfd_t* h, uint64_t* total, int32_t reset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
