@@ -176,3 +176,93 @@ class Audio2EmotionHIP(AudioEncoderHIP):
                 native.check(native.lib().float_aud_classify(self._h, native.dev_ptr(a[b]), a.shape[1], native.dev_ptr(out[b]),
                                                              native.stream_ptr(self.device)))
         return out
+
+    def segment_normalised(self, n_floats):
+        """Test hook (float_aud_debug, what = 2): the first n_floats of the normalised (n_seg, seg_len) copy that the last
+        float_aud_classify_segments(FLOAT_AUD_SEG_NORMALIZE) of this handle left in its workspace."""
+        out = torch.empty(int(n_floats), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().float_aud_debug(self._h, 2, None, int(n_floats), native.dev_ptr(out), native.stream_ptr(self.device)))
+        return out
+
+    @torch.no_grad()
+    def classify_segments(self, a, n_seg, seg_len, seg_stride=None, normalize=True, T=None):
+        """float_aud_classify_segments on a device waveform: segment s = a[s * seg_stride : s * seg_stride + seg_len] ->
+        (scores (n_seg, labels), frames (T, labels) or None).  Reserves first; `a` is not written."""
+        a = a.to(self.device, torch.float32).reshape(-1).contiguous()
+        n_seg, seg_len = int(n_seg), int(seg_len)
+        seg_stride = seg_len if seg_stride is None else int(seg_stride)
+        if n_seg >= 1 and seg_stride >= seg_len and a.numel() < (n_seg - 1) * seg_stride + seg_len:
+            raise ValueError("classify_segments: %d samples do not hold %d segments of %d at stride %d" % (a.numel(), n_seg, seg_len, seg_stride))
+        labels = self.cfg.num_labels
+        scores = torch.empty(max(n_seg, 0), labels, device=self.device, dtype=torch.float32)
+        frames = torch.empty(int(T), labels, device=self.device, dtype=torch.float32) if T is not None else None
+        L = native.lib()
+        with torch.cuda.device(self.device):
+            st = native.stream_ptr(self.device)
+            native.check(L.float_aud_reserve_segments(self._h, n_seg, seg_len, st))  # a no-op when it fits
+            native.check(L.float_aud_classify_segments(self._h, native.dev_ptr(a), n_seg, seg_len, seg_stride,
+                                                       native.AUD_SEG_NORMALIZE if normalize else 0, native.dev_ptr(scores),
+                                                       native.dev_ptr(frames) if frames is not None else None, int(T or 0),
+                                                       _nearest_scale(n_seg, T or 1), st))
+        return scores, frames
+
+    @torch.no_grad()
+    def predict_emotion_chunks(self, w, chunk, T=None, normalize=True):
+        """Dynamic emotion (reference FloatExtractEmotionWithCustomModelDyn, nodes_vadv.py:812-838) on the device: w, the (N,) or
+        (1, N) mono waveform at the model's rate on any device, in chunks of `chunk` samples, each normalised on its own
+        (`normalize`) and classified -> (seq (n_chunks, labels), frames (T, labels) or None), frames = host_models.nearest_rows(seq, T).
+        Both on the device; nothing synchronises and nothing comes back to the host.
+        The N // chunk equal chunks are ONE float_aud_classify_segments (one stacked launch sequence); a shorter last chunk is
+        normalised on its own by the audio front end's kernels (float_aud_front at equal rates), replicate-padded to 400 samples
+        when it is shorter than the feature extractor's receptive field (as the node does), and scored by float_aud_classify into
+        the last row of seq.  The expansion then runs ONCE over all rows: float_aud_expand_rows is its own entry of the ABI, so a
+        clip with a tail does not expand the stacked rows a second time; without a tail it is the `frames` argument of the
+        stacked call (the same kernel).
+        What the stacked call does not take goes chunk by chunk through the tail's route - normalised on the device, padded,
+        float_aud_classify into row i, then the one expansion; still nothing on the host: handles with the GroupNorm extractor
+        (feat_extract_norm = "group": its statistics run over time) and chunks below 400 samples (the reference's loop pads every
+        such chunk, not only the last)."""
+        w = w.detach()
+        if w.dim() == 2 and w.shape[0] == 1:
+            w = w[0]
+        if w.dim() != 1:
+            raise ValueError("predict_emotion_chunks: waveform must be (N,) or (1, N), got %s" % (tuple(w.shape),))
+        w = w.to(self.device, torch.float32, non_blocking=True).contiguous()
+        N, chunk = int(w.shape[0]), int(chunk)
+        if chunk < 1 or N < 1:
+            raise ValueError("predict_emotion_chunks: needs at least one sample and chunk >= 1 (N = %d, chunk = %d)" % (N, chunk))
+        n_chunks = -(-N // chunk)
+        stacked = N // chunk if (self.cfg.feat_extract_norm == "layer" and chunk >= 400) else 0  # rows of the stacked call
+        labels = self.cfg.num_labels
+        seq = torch.empty(n_chunks, labels, device=self.device, dtype=torch.float32)
+        frames = torch.empty(int(T), labels, device=self.device, dtype=torch.float32) if T is not None else None
+        L = native.lib()
+        with torch.cuda.device(self.device):
+            st = native.stream_ptr(self.device)
+            inline = frames is not None and stacked == n_chunks  # every row from the stacked call: it expands its own rows
+            if stacked:
+                native.check(L.float_aud_reserve_segments(self._h, stacked, chunk, st))  # a no-op when it fits
+                native.check(L.float_aud_classify_segments(self._h, native.dev_ptr(w), stacked, chunk, chunk,
+                                                           native.AUD_SEG_NORMALIZE if normalize else 0, native.dev_ptr(seq),
+                                                           native.dev_ptr(frames) if inline else None, int(T) if inline else 0,
+                                                           _nearest_scale(stacked, T) if inline else 0.0, st))
+            for i in range(stacked, n_chunks):
+                piece = w[i * chunk:(i + 1) * chunk]
+                n = int(piece.shape[0])
+                if normalize:
+                    piece = preprocess_audio_device(piece, self.sampling_rate, self.sampling_rate, self.device, True)[0]
+                if n < 400:
+                    piece = F.pad(piece[None, None], (0, 400 - n), mode="replicate")[0, 0].contiguous()
+                self.reserve(piece.shape[0], 0)
+                native.check(L.float_aud_classify(self._h, native.dev_ptr(piece), int(piece.shape[0]), native.dev_ptr(seq[i]), st))
+            if frames is not None and not inline:
+                native.check(L.float_aud_expand_rows(native.dev_ptr(seq), n_chunks, labels, native.dev_ptr(frames), int(T),
+                                                     _nearest_scale(n_chunks, T), st))
+        return seq, frames
+
+
+def _nearest_scale(n, T):
+    """(float)n / (float)T as fp32, the scale F.interpolate(mode="nearest") multiplies the output index by (host_models.nearest_rows)."""
+    import numpy as np
+    return float(np.float32(n) / np.float32(T))

@@ -26,6 +26,22 @@ struct TLayer {
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// float_aud_classify_segments: n_seg equal segments through one launch sequence.  The feature extractor keeps
+// aud_gemm_tile_kernel untouched by storing layer l with a per-segment row pitch P[l], P[l-1] = stride[l] * P[l]: output row
+// s * P[l] + t then reads the input window at row (s * P[l] + t) * stride[l] = s * P[l-1] + t * stride[l], i.e. the stacked
+// index stays affine and `lda` serves as it is.  N[l] is the number of rows of a segment that the last layer's L rows depend
+// on (N[l-1] = (N[l] - 1) * stride[l] + k[l] <= the layer's true length); P[last] is the smallest pitch >= L with
+// P[l] >= N[l] for every l (k > stride makes L itself too small: xlsr at 32 000 samples has L = 99, P[last] = 100).  Rows t of a
+// segment with N[l] <= t < P[l] mix in the first rows of the next segment (or, past the layer's true length, zero filler of
+// layer 0): finite, written, and read by nothing that reaches the transformer.  The last segment stops at N[l] rows, so no
+// launch reads a row that was not written in the same call.
+struct SegPlan {
+  int n_seg = 1, seg_len = 0, L = 0;
+  long long seg_stride = 0;
+  int P[8] = {0}, N[8] = {0};
+  long long rows(int l) const { return (long long)(n_seg - 1) * P[l] + N[l]; }  // rows layer l computes
+};
+
 }  // namespace
 
 struct float_aud {
@@ -51,6 +67,10 @@ struct float_aud {
   // workspace
   size_t cap_samples = 0;
   int cap_T = 0, Mp = 0;
+  // stacked segments (float_aud_reserve_segments): rows of fa / fb, floats of the normalised copy, segments of the head buffers
+  long long cap_rows0 = 0, cap_rows1 = 0, cap_segn = 0;
+  int cap_nseg = 0;
+  float *segn = nullptr, *seg_pooled = nullptr, *seg_h = nullptr, *seg_logits = nullptr;
   void *fa = nullptr, *fb = nullptr;  // T::elem (every activation buffer below: bytes = elements * element size of cfg.dtype)
   float *part = nullptr, *scsh = nullptr;
   void *x16 = nullptr, *hp16 = nullptr, *qkv16 = nullptr, *att16 = nullptr, *hid16 = nullptr, *stack16 = nullptr;
@@ -235,16 +255,25 @@ int create_impl(float_aud* h, const TensorTable& tt) {
 constexpr int kAudMaxFrames = 200000;
 
 // float_aud_reserve: the only place the operator allocates after create.  Run-time calls check the capacity and refuse.
-int ensure_workspace(float_aud* h, int n_samples, int Tn, hipStream_t st) {
-  if ((size_t)n_samples <= h->cap_samples && Tn <= h->cap_T) return FLOAT_OK;
+// `sp`: the stacked form's needs on top (float_aud_reserve_segments), or nullptr.
+int ensure_workspace(float_aud* h, int n_samples, int Tn, hipStream_t st, const SegPlan* sp = nullptr) {
+  const long long rows0 = sp ? (long long)sp->n_seg * sp->P[0] : 0, rows1 = sp ? (long long)sp->n_seg * sp->P[1] : 0;
+  const long long segn = sp ? (long long)sp->n_seg * sp->seg_len : 0;
+  const int nseg = sp ? sp->n_seg : 0;
+  if ((size_t)n_samples <= h->cap_samples && Tn <= h->cap_T && rows0 <= h->cap_rows0 && rows1 <= h->cap_rows1 && segn <= h->cap_segn &&
+      nseg <= h->cap_nseg)
+    return FLOAT_OK;
   const float_aud_cfg_t& c = h->cfg;
   FH_CHECK_HIP(hipStreamSynchronize(st));  // earlier calls may still use the old buffers
   h->ws.release();
   h->ws = DevicePool();
   const size_t ns = std::max((size_t)n_samples, h->cap_samples);
   const int Tc = std::max(Tn, h->cap_T);
-  const size_t L0 = (ns - c.conv_kernel[0]) / c.conv_stride[0] + 1;
-  const size_t L1 = c.n_conv > 1 ? (L0 - c.conv_kernel[1]) / c.conv_stride[1] + 1 : 1;
+  const size_t L0c = (ns - c.conv_kernel[0]) / c.conv_stride[0] + 1;  // one clip of ns samples
+  const size_t L1c = c.n_conv > 1 ? (L0c - c.conv_kernel[1]) / c.conv_stride[1] + 1 : 1;
+  const long long r0 = std::max(rows0, h->cap_rows0), r1 = std::max(rows1, h->cap_rows1), sn = std::max(segn, h->cap_segn);
+  const int nsg = std::max(nseg, h->cap_nseg);
+  const size_t L0 = std::max(L0c, (size_t)r0), L1 = std::max(L1c, (size_t)r1);
   const int Mp = round_up(Tc, 80) + 80;
   const int D = h->D, C = h->C;
   int rc = 0;
@@ -259,7 +288,7 @@ int ensure_workspace(float_aud* h, int n_samples, int Tn, hipStream_t st) {
   };
   AE(&h->fa, L0 * C + 64);
   AE(&h->fb, L1 * C + 64);
-  A(&h->part, ((L0 + 63) / 64) * C * 2);
+  A(&h->part, ((L0c + 63) / 64) * C * 2);  // GroupNorm partials: single clips only
   A(&h->scsh, (size_t)2 * C);
   AE(&h->x16, (size_t)Mp * C);
   AE(&h->hp16, (size_t)Mp * D);
@@ -273,10 +302,18 @@ int ensure_workspace(float_aud* h, int n_samples, int Tn, hipStream_t st) {
   A(&h->h1, (size_t)Mp * D);
   A(&h->y, (size_t)Mp * D);
   A(&h->yproj, (size_t)Mp * std::max(c.dim_w, 256));
+  A(&h->segn, (size_t)sn + 64);
+  A(&h->seg_pooled, (size_t)(nsg + 1) * D);
+  A(&h->seg_h, (size_t)(nsg + 1) * D);
+  A(&h->seg_logits, (size_t)(nsg + 1) * std::max(c.num_labels, 16));
   if (rc) return rc;
   h->cap_samples = ns;
   h->cap_T = Tc;
   h->Mp = Mp;
+  h->cap_rows0 = r0;
+  h->cap_rows1 = r1;
+  h->cap_segn = sn;
+  h->cap_nseg = nsg;
   return FLOAT_OK;
 }
 
@@ -307,25 +344,29 @@ int feature_len(const float_aud_cfg_t& c, int n_samples) {
 // The attention launch of one layer: h->qkv16 (Tn, 3*D) = [q | k | v] -> h->att16, the packed operand of out_proj.  16-bit
 // operands: the matrix-pipe kernel (64 queries per workgroup, K / V shared); fp32 mode and FLOAT_AUD_ATTN_MFMA=0: one wave per
 // query.  The one place that dispatch is written: inference_impl and the test hook (float_aud_debug) both launch through it.
+// n_seg > 1: Tn frames per segment, one grid plane per segment (a query sees the keys of its own segment only).
 template <class T>
-void launch_attn(float_aud* h, int Tn, hipStream_t st) {
+void launch_attn(float_aud* h, int Tn, hipStream_t st, int n_seg = 1) {
   typedef typename T::elem E;
   const int D = h->D, heads = h->cfg.heads;
   const bool mfma_on = h->tune.attn_mfma;
   if constexpr (!T::is32) {
     if (mfma_on)
-      hipLaunchKernelGGL((aud_attn_mfma_kernel<T>), dim3((Tn + 63) / 64, heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D,
+      hipLaunchKernelGGL((aud_attn_mfma_kernel<T>), dim3((Tn + 63) / 64, heads, n_seg), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D,
                          heads, reinterpret_cast<E*>(h->att16), h->sat);
   }
   if (T::is32 || !mfma_on)
-    hipLaunchKernelGGL((aud_attn_kernel<T>), dim3((Tn + 3) / 4, heads), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D, heads,
+    hipLaunchKernelGGL((aud_attn_kernel<T>), dim3((Tn + 3) / 4, heads, n_seg), dim3(256), 0, st, reinterpret_cast<const E*>(h->qkv16), Tn, D, heads,
                        reinterpret_cast<E*>(h->att16), h->sat);
 }
 
 // Tn: number of frames fed to the transformer: seq_len (interpolated, audio conditioning) or, Tn <= 0, the
 // extractor's own length (speech-emotion model, no interpolation).  wa: (Tn, dim_w) or scores: (num_labels).
+// sp != nullptr: the stacked form (float_aud_classify_segments, which has checked the reservation): `a` holds sp->n_seg
+// segments of n_samples samples sp->seg_stride apart, Tn is 0, out is (n_seg, num_labels).  Every launch below is the one the
+// single clip takes, with the segment count where rows of different segments would meet.
 template <class T>
-int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* out, hipStream_t st) {
+int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* out, hipStream_t st, const SegPlan* sp = nullptr) {
   typedef typename T::elem E;
   const float_aud_cfg_t& c = h->cfg;
   const int C = h->C, D = h->D;
@@ -333,16 +374,20 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
   const int Lfeat = feature_len(c, n_samples);
   FH_REQUIRE(Lfeat >= 1, "audio too short for the feature extractor (%d samples)", n_samples);
   if (Tn <= 0) Tn = Lfeat;
+  const int n_seg = sp ? sp->n_seg : 1, Ls = Tn;  // Ls: transformer rows per segment
+  if (sp) Tn = n_seg * Ls;                        // dense rows of the transformer
   FH_REQUIRE(Tn <= kAudMaxFrames, "%d frames: one call takes at most %d transformer frames (32-bit element indices)", Tn, kAudMaxFrames);
-  FH_REQUIRE((size_t)n_samples <= h->cap_samples && Tn <= h->cap_T,
-             "clip of %d samples / %d frames exceeds the reserved workspace (%zu samples / %d frames): call float_aud_reserve "
-             "first (run-time calls do not allocate)", n_samples, Tn, h->cap_samples, h->cap_T);
+  if (!sp)
+    FH_REQUIRE((size_t)n_samples <= h->cap_samples && Tn <= h->cap_T,
+               "clip of %d samples / %d frames exceeds the reserved workspace (%zu samples / %d frames): call float_aud_reserve "
+               "first (run-time calls do not allocate)", n_samples, Tn, h->cap_samples, h->cap_T);
   // ---- feature extractor
   int L = (n_samples - c.conv_kernel[0]) / c.conv_stride[0] + 1;
   FH_REQUIRE(c.conv_kernel[0] == 10, "first conv kernel must be 10 (got %d)", c.conv_kernel[0]);
   if (c.feat_norm_layer) {
-    hipLaunchKernelGGL((aud_conv0_ln_kernel<T, 10>), dim3((L + 3) / 4), dim3(256), 0, st, a, h->w0, h->b0, c.conv_stride[0], L, C, h->gn.g, h->gn.b,
-                       1e-5f, reinterpret_cast<E*>(h->fa), h->sat);
+    const int rows = sp ? sp->P[0] : L;
+    hipLaunchKernelGGL((aud_conv0_ln_kernel<T, 10>), dim3((rows + 3) / 4, n_seg), dim3(256), 0, st, a, h->w0, h->b0, c.conv_stride[0], L, C, h->gn.g,
+                       h->gn.b, 1e-5f, reinterpret_cast<E*>(h->fa), h->sat, sp ? sp->seg_stride : 0ll, rows);
   } else {
     const int tchunk = 64, nchunk = (L + tchunk - 1) / tchunk;
     hipLaunchKernelGGL((aud_conv0_stats_kernel<10>), dim3(nchunk, (C + 255) / 256), dim3(256), 0, st, a, n_samples, h->w0, c.conv_stride[0], L, C,
@@ -353,8 +398,10 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
                        h->scsh, reinterpret_cast<E*>(h->fa), h->sat);
   }
   E *cur = reinterpret_cast<E*>(h->fa), *nxt = reinterpret_cast<E*>(h->fb);
+  int li = 0;
   for (const ConvL& Lc : h->convs) {
-    const int Lo = (L - Lc.k) / Lc.stride + 1;
+    ++li;
+    const int Lo = sp ? (int)sp->rows(li) : (L - Lc.k) / Lc.stride + 1;  // stacked: pitched rows of all segments (SegPlan)
     AudGemmArgs g;
     memset(&g, 0, sizeof(g));
     g.sat = h->sat;
@@ -384,10 +431,13 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
   FH_CHECK_HIP(hipGetLastError());
   // ---- (interpolate to Tn frames +) feature-projection LayerNorm -> packed x16; projection -> hproj (fp32)
   {
-    dim3 grid((Tn + 3) / 4);
+    // stacked: segment s has Lfeat rows at pitch P[last]; the copy (scale 1) makes the transformer's rows dense
+    if (sp) L = Lfeat;
+    const int pitch = sp ? sp->P[c.n_conv - 1] : 0;
+    dim3 grid((Ls + 3) / 4, n_seg);
     switch (C / 256) {
-      case 1: hipLaunchKernelGGL((aud_interp_ln_kernel<T, 1>), grid, dim3(256), 0, st, cur, L, Tn, h->fp_ln.g, h->fp_ln.b, c.ln_eps, reinterpret_cast<E*>(h->x16), h->sat); break;
-      case 2: hipLaunchKernelGGL((aud_interp_ln_kernel<T, 2>), grid, dim3(256), 0, st, cur, L, Tn, h->fp_ln.g, h->fp_ln.b, c.ln_eps, reinterpret_cast<E*>(h->x16), h->sat); break;
+      case 1: hipLaunchKernelGGL((aud_interp_ln_kernel<T, 1>), grid, dim3(256), 0, st, cur, L, Ls, h->fp_ln.g, h->fp_ln.b, c.ln_eps, reinterpret_cast<E*>(h->x16), h->sat, pitch); break;
+      case 2: hipLaunchKernelGGL((aud_interp_ln_kernel<T, 2>), grid, dim3(256), 0, st, cur, L, Ls, h->fp_ln.g, h->fp_ln.b, c.ln_eps, reinterpret_cast<E*>(h->x16), h->sat, pitch); break;
       default: fh_set_error("conv_dim %d unsupported", C); return FLOAT_E_INVALID;
     }
     GemmArgs g = fmt_gemm_args(reinterpret_cast<const u16*>(h->x16), h->fp_proj, Tn);
@@ -421,7 +471,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
   {
     dim3 grid((Tn + 15) / 16, h->pos_pairs);
 #define POS_CASE(GP) \
-  case GP: hipLaunchKernelGGL((aud_posconv_kernel<T, GP>), grid, dim3(256), 0, st, h->hproj, Tn, D, reinterpret_cast<const E*>(h->pos_w), h->pos_b, c.pos_k, c.pos_k / 2, h->pos, h->sat); break;
+  case GP: hipLaunchKernelGGL((aud_posconv_kernel<T, GP>), grid, dim3(256), 0, st, h->hproj, Tn, D, reinterpret_cast<const E*>(h->pos_w), h->pos_b, c.pos_k, c.pos_k / 2, h->pos, h->sat, Ls); break;
     switch (h->pos_gp) {
       POS_CASE(32) POS_CASE(64) POS_CASE(96) POS_CASE(128)
       default: fh_set_error("merged positional group width %d unsupported", h->pos_gp); return FLOAT_E_INVALID;
@@ -440,7 +490,7 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
       g.ldo16 = 3 * D;
       if ((rc = fmt_gemm_run(h->gemm_tune, c.dtype, EPI_T16, g, st))) return rc;
     }
-    launch_attn<T>(h, Tn, st);
+    launch_attn<T>(h, Ls, st, n_seg);
     {
       GemmArgs g = fmt_gemm_args(reinterpret_cast<const u16*>(h->att16), Ly.out, Tn);
       g.sat = h->sat;
@@ -476,11 +526,13 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
   }
   if (c.num_labels > 0) {
     // ---- mean over time -> dense -> tanh -> out_proj -> softmax (wav2vec2_ser.py:58-75,94-96; FLOAT.py:396-401)
-    hipLaunchKernelGGL(aud_meanpool_kernel, dim3((D + 63) / 64), dim3(256), 0, st, h->h, Tn, D, h->pooled);
-    hipLaunchKernelGGL(aud_dense_kernel, dim3((D + 3) / 4), dim3(256), 0, st, h->pooled, h->cls_dense_w, h->cls_dense_b, h->cls_h, D, D, 1);
-    hipLaunchKernelGGL(aud_dense_kernel, dim3((c.num_labels + 3) / 4), dim3(256), 0, st, h->cls_h, h->cls_out_w, h->cls_out_b, h->cls_logits,
+    // per segment (stacked) in the same launches: one pooled row, one head evaluation, one softmax row each
+    float *pooled = sp ? h->seg_pooled : h->pooled, *cls_h = sp ? h->seg_h : h->cls_h, *logits = sp ? h->seg_logits : h->cls_logits;
+    hipLaunchKernelGGL(aud_meanpool_kernel, dim3((D + 63) / 64, n_seg), dim3(256), 0, st, h->h, Ls, D, pooled);
+    hipLaunchKernelGGL(aud_dense_kernel, dim3((D + 3) / 4, n_seg), dim3(256), 0, st, pooled, h->cls_dense_w, h->cls_dense_b, cls_h, D, D, 1);
+    hipLaunchKernelGGL(aud_dense_kernel, dim3((c.num_labels + 3) / 4, n_seg), dim3(256), 0, st, cls_h, h->cls_out_w, h->cls_out_b, logits,
                        c.num_labels, D, 0);
-    hipLaunchKernelGGL(aud_softmax_kernel, dim3(1), dim3(64), 0, st, h->cls_logits, out, c.num_labels);
+    hipLaunchKernelGGL(aud_softmax_kernel, dim3(n_seg), dim3(64), 0, st, logits, out, c.num_labels);
   } else {
     // ---- audio projection: Linear -> LayerNorm -> SiLU
     GemmArgs g = fmt_gemm_args(reinterpret_cast<const u16*>(h->stack16), h->aproj, Tn);
@@ -501,6 +553,45 @@ int inference_impl(float_aud* h, const float* a, int n_samples, int Tn, float* o
     if ((rc = launch_ln<T>(c.dim_w, n, st))) return rc;
   }
   FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
+// The pitches of the stacked extractor for segments of seg_len samples (SegPlan above).  0 rows: seg_len is below the receptive field.
+bool seg_plan(const float_aud_cfg_t& c, int n_seg, int seg_len, long long seg_stride, SegPlan* p) {
+  const int last = c.n_conv - 1;
+  p->n_seg = n_seg;
+  p->seg_len = seg_len;
+  p->seg_stride = seg_stride;
+  p->L = feature_len(c, seg_len);
+  if (p->L < 1) return false;
+  p->N[last] = p->L;
+  for (int l = last; l >= 1; --l) p->N[l - 1] = (p->N[l] - 1) * c.conv_stride[l] + c.conv_kernel[l];
+  for (int pl = p->L;; ++pl) {
+    long long q = pl;
+    bool ok = true;
+    for (int l = last; l >= 0 && ok; --l) {
+      ok = q >= p->N[l] && q < (1ll << 30);
+      p->P[l] = (int)q;
+      if (l) q *= c.conv_stride[l];
+    }
+    if (ok) return true;
+    if (q >= (1ll << 30)) return false;
+  }
+}
+
+// What both segment calls refuse, before any HIP call.
+int seg_validate(const char* fn, float_aud* h, int n_seg, int seg_len, long long seg_stride, SegPlan* p) {
+  FH_REQUIRE(n_seg >= 1, "%s: n_seg must be >= 1 (got %d)", fn, n_seg);
+  FH_REQUIRE(seg_stride >= seg_len, "%s: seg_stride (%lld) must be >= seg_len (%d)", fn, seg_stride, seg_len);
+  FH_REQUIRE(h != nullptr, "%s: null audio handle", fn);
+  FH_REQUIRE(h->cfg.num_labels > 0, "%s: this handle was created with the audio projection head (num_labels = 0)", fn);
+  FH_REQUIRE(h->cfg.feat_norm_layer, "%s: feat_extract_norm = \"group\" normalises over time; the stacked form takes the LayerNorm extractor only", fn);
+  FH_REQUIRE(seg_len >= 400 && seg_plan(h->cfg, n_seg, seg_len, seg_stride, p),
+             "%s: segment too short: %d samples (the feature extractor needs >= 400 and its receptive field)", fn, seg_len);
+  FH_REQUIRE((long long)n_seg * p->L <= kAudMaxFrames, "%s: %d segments x %d frames: one call takes at most %d transformer frames", fn, n_seg, p->L,
+             kAudMaxFrames);
+  FH_REQUIRE((long long)n_seg * p->P[0] < (1ll << 31) && (long long)n_seg * seg_len < (1ll << 31), "%s: %d segments of %d samples are too many rows for one call", fn,
+             n_seg, seg_len);
   return FLOAT_OK;
 }
 
@@ -611,7 +702,57 @@ int float_aud_inference(float_aud_t* h, const float* a, int32_t n_samples, int32
                                        : inference_impl<FP16>(h, a, n_samples, seq_len, wa, st);
 }
 
+int float_aud_reserve_segments(float_aud_t* h, int32_t n_seg, int32_t seg_len, void* stream) {
+  SegPlan p;
+  int rc = seg_validate("float_aud_reserve_segments", h, n_seg, seg_len, seg_len, &p);
+  if (rc) return rc;
+  return ensure_workspace(h, seg_len, n_seg * p.L, (hipStream_t)stream, &p);
+}
+
+int float_aud_classify_segments(float_aud_t* h, const float* a, int32_t n_seg, int32_t seg_len, int64_t seg_stride, int32_t flags, float* scores,
+                                float* frames, int32_t T, float scale, void* stream) {
+  const char* fn = "float_aud_classify_segments";
+  FH_REQUIRE(!frames || T >= 1, "%s: T must be >= 1 when frames is set (got %d)", fn, T);
+  FH_REQUIRE((flags & ~FLOAT_AUD_SEG_NORMALIZE) == 0, "%s: unknown flags 0x%x", fn, flags);
+  SegPlan p;
+  int rc = seg_validate(fn, h, n_seg, seg_len, seg_stride, &p);
+  if (rc) return rc;
+  FH_REQUIRE(a && scores, "null argument to %s", fn);
+  FH_REQUIRE(!frames || (long long)T * h->cfg.num_labels < (1ll << 31), "%s: T = %d is too many rows", fn, T);
+  FH_REQUIRE((long long)n_seg * p.P[0] <= h->cap_rows0 && (long long)n_seg * p.P[1] <= h->cap_rows1 && (long long)n_seg * seg_len <= h->cap_segn &&
+                 n_seg <= h->cap_nseg && n_seg * p.L <= h->cap_T && (size_t)seg_len <= h->cap_samples,
+             "%s: %d segments of %d samples exceed the reserved workspace: call float_aud_reserve_segments first (run-time calls do not allocate)",
+             fn, n_seg, seg_len);
+  hipStream_t st = (hipStream_t)stream;
+  if (flags & FLOAT_AUD_SEG_NORMALIZE) {
+    hipLaunchKernelGGL(aud_seg_norm_kernel, dim3(n_seg), dim3(256), 0, st, a, (long long)seg_stride, seg_len, h->segn);
+    a = h->segn;
+    p.seg_stride = seg_len;
+  }
+  rc = h->cfg.dtype == FLOAT_DT_FP32   ? inference_impl<FP32>(h, a, seg_len, 0, scores, st, &p)
+       : h->cfg.dtype == FLOAT_DT_BF16 ? inference_impl<BF16>(h, a, seg_len, 0, scores, st, &p)
+                                       : inference_impl<FP16>(h, a, seg_len, 0, scores, st, &p);
+  if (rc || !frames) return rc;
+  return float_aud_expand_rows(scores, n_seg, h->cfg.num_labels, frames, T, scale, stream);
+}
+
+int float_aud_expand_rows(const float* rows, int32_t n, int32_t c, float* frames, int32_t T, float scale, void* stream) {
+  FH_REQUIRE(n >= 1 && c >= 1 && T >= 1, "float_aud_expand_rows: n, c and T must be >= 1 (got %d, %d, %d)", n, c, T);
+  FH_REQUIRE((long long)T * c < (1ll << 31), "float_aud_expand_rows: T x c = %d x %d is too large", T, c);
+  FH_REQUIRE(rows && frames, "null argument to float_aud_expand_rows");
+  hipLaunchKernelGGL(aud_nearest_rows_kernel, dim3((T * c + 255) / 256), dim3(256), 0, (hipStream_t)stream, rows, n, c, frames, T, scale);
+  FH_CHECK_HIP(hipGetLastError());
+  return FLOAT_OK;
+}
+
 int float_aud_debug(float_aud_t* h, int32_t what, const float* in, int32_t Tn, float* out, void* stream) {
+  if (what == 2) {  // the normalised copy of the last float_aud_classify_segments(FLOAT_AUD_SEG_NORMALIZE): Tn floats
+    FH_REQUIRE(h && out, "null argument to float_aud_debug");
+    FH_REQUIRE(Tn >= 1 && Tn <= h->cap_segn, "float_aud_debug: %d floats exceed the reserved segments (%lld): call float_aud_reserve_segments first", Tn,
+               h->cap_segn);
+    FH_CHECK_HIP(hipMemcpyAsync(out, h->segn, (size_t)Tn * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return FLOAT_OK;
+  }
   FH_REQUIRE(h && in && out, "null argument to float_aud_debug");
   FH_REQUIRE(what == 1, "float_aud_debug: unknown request %d", what);
   FH_REQUIRE(Tn >= 1, "float_aud_debug: Tn must be >= 1 (got %d)", Tn);

@@ -215,15 +215,19 @@ __global__ __launch_bounds__(256) void aud_gemm_tile_kernel(AudGemmArgs g) {
 // linear_interpolation(features, seq_len) (wav2vec2.py:184-197: F.interpolate(mode='linear', align_corners=True)
 // along time) fused with the feature projection's LayerNorm (Wav2Vec2FeatureProjection.layer_norm, affine).
 // One wave per output frame; writes the packed 16-bit A operand of the projection GEMM (K = C).
+// Stacked segments (float_aud_classify_segments): blockIdx.y = segment; its L feature rows start at row blockIdx.y * seg_pitch
+// of f (the extractor's pitched layout, aud_api.hip) and its Tn output rows are dense at row blockIdx.y * Tn.  One clip: grid.y = 1.
 template <class T, int NV>
 __global__ __launch_bounds__(256) void aud_interp_ln_kernel(const typename T::elem* __restrict__ f, int L, int Tn,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                            typename T::elem* __restrict__ out, unsigned long long* sat) {
+                                                            typename T::elem* __restrict__ out, unsigned long long* sat, int seg_pitch) {
   constexpr int C = NV * 256;
   unsigned rm = 0u;  // range tracker (fh_range_flush)
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= Tn) return;
+  f += (size_t)blockIdx.y * seg_pitch * C;
+  const int orow = blockIdx.y * Tn + t;
   const float scale = (Tn > 1) ? (float)(L - 1) / (float)(Tn - 1) : 0.f;
   const float src = scale * (float)t;
   const int i0 = min((int)src, L - 1), i1 = min(i0 + 1, L - 1);
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(256) void aud_interp_ln_kernel(const typename T::el
     const int c = i * 256 + lane * 4;
     const float4 gm = *reinterpret_cast<const float4*>(gamma + c);
     const float4 bt = *reinterpret_cast<const float4*>(beta + c);
-    fh_store4<T>(out + fmt_pack_off(t, c, C / 32), (v[i][0] - mu) * rstd * gm.x + bt.x, (v[i][1] - mu) * rstd * gm.y + bt.y,
+    fh_store4<T>(out + fmt_pack_off(orow, c, C / 32), (v[i][0] - mu) * rstd * gm.x + bt.x, (v[i][1] - mu) * rstd * gm.y + bt.y,
                  (v[i][2] - mu) * rstd * gm.z + bt.z, (v[i][3] - mu) * rstd * gm.w + bt.w, rm);
   }
   fh_range_flush<T>(sat, rm);
@@ -345,7 +349,9 @@ __global__ __launch_bounds__(256) void aud_ln_kernel(AudLnArgs g) {
 template <class T, int GP /* channels per merged group */>
 __global__ __launch_bounds__(256) void aud_posconv_kernel(const float* __restrict__ x, int Tn, int D, const typename T::elem* __restrict__ W,
                                                           const float* __restrict__ bias, int ktaps, int pad, float* __restrict__ out,
-                                                          unsigned long long* sat) {
+                                                          unsigned long long* sat, int Ls) {
+  // Ls: rows per segment.  The Tn rows are Tn / Ls independent sequences (float_aud_classify_segments) and the zero padding
+  // applies at the edges of each: a tap whose frame lies in a neighbouring segment contributes zero.  One clip: Ls = Tn.
   typedef typename T::pack8 P8;
   constexpr int NT = GP / 16, KBN = GP / 32;
   unsigned rm = 0u;  // range tracker (fh_range_flush)
@@ -357,9 +363,10 @@ __global__ __launch_bounds__(256) void aud_posconv_kernel(const float* __restric
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int tpw = ktaps / 4;
+  const int lo = Ls >= Tn ? 0 : (t0 + r16) / Ls * Ls, hi = min(lo + Ls, Tn);  // this lane's output frame sees [lo, hi); one clip: [0, Tn), no division
   for (int kk = w * tpw; kk < (w + 1) * tpw; ++kk) {
     const int t = t0 + r16 + kk - pad;
-    const bool ok = t >= 0 && t < Tn;
+    const bool ok = t >= lo && t < hi;
     const float* xr = x + (size_t)(ok ? t : 0) * D + gp * GP + q * 8;
     const typename T::elem* wr = W + (((size_t)gp * ktaps + kk) * GP + r16) * GP + q * 8;
 #pragma unroll
@@ -412,6 +419,8 @@ __global__ __launch_bounds__(256) void aud_attn_kernel(const typename T::elem* _
   __shared__ float sm[4 * (HD + kAudKeyTile)];  // per wave: q[64] + p[tile]
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int qi = blockIdx.x * 4 + w, h = blockIdx.y;
+  const int row0 = blockIdx.z * Tn;  // stacked segments: blockIdx.z = segment, Tn = its length; a query sees its own segment
+  qkv += (size_t)row0 * (3 * D);
   float* sq = sm + (size_t)w * (HD + kAudKeyTile);
   float* sp = sq + HD;
   const bool live = qi < Tn;
@@ -464,7 +473,7 @@ __global__ __launch_bounds__(256) void aud_attn_kernel(const typename T::elem* _
     __threadfence_block();
   }
   unsigned rm = 0u;
-  out[fmt_pack_off(qi, h * HD + lane, D / 32)] = fh_cvt<T>(acc / l, rm);
+  out[fmt_pack_off(row0 + qi, h * HD + lane, D / 32)] = fh_cvt<T>(acc / l, rm);
   fh_range_flush<T>(sat, rm);
 }
 
@@ -492,6 +501,8 @@ __global__ __launch_bounds__(256) void aud_attn_mfma_kernel(const typename T::el
   __shared__ __attribute__((aligned(16))) E sV[HD * VSTR];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c16 = lane & 15, g = lane >> 4;
   const int h = blockIdx.y, ld = 3 * D;
+  const int row0 = blockIdx.z * Tn;  // stacked segments: blockIdx.z = segment, Tn = its length (aud_attn_kernel)
+  qkv += (size_t)row0 * ld;
   const int q_raw = blockIdx.x * 64 + w * 16 + c16, qi = min(q_raw, Tn - 1);
   const E* const qp = qkv + (size_t)qi * ld + h * HD + g * 8;
   const P8 qB0 = T::load8(qp), qB1 = T::load8(qp + 32);  // B operand: query c16, dims kb*32 + g*8 .. +7
@@ -572,7 +583,7 @@ __global__ __launch_bounds__(256) void aud_attn_mfma_kernel(const typename T::el
   unsigned rm = 0u;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
-    fh_store4<T>(out + fmt_pack_off(q_raw, h * HD + dt * 16 + g * 4, D / 32), oT[dt][0] * inv, oT[dt][1] * inv, oT[dt][2] * inv, oT[dt][3] * inv, rm);
+    fh_store4<T>(out + fmt_pack_off(row0 + q_raw, h * HD + dt * 16 + g * 4, D / 32), oT[dt][0] * inv, oT[dt][1] * inv, oT[dt][2] * inv, oT[dt][3] * inv, rm);
   fh_range_flush<T>(sat, rm);
 }
 
@@ -580,15 +591,24 @@ __global__ __launch_bounds__(256) void aud_attn_mfma_kernel(const typename T::el
 // feat_extract_norm = "layer" (wav2vec2-large / the speech-emotion model, Wav2Vec2LayerNormConvLayer): every conv is
 // followed by LayerNorm over the CHANNELS of each time step (affine) and GELU.
 // Layer 0: Conv1d(1 -> C, k = 10) + bias, LayerNorm, GELU; one wave per time step, 8 channels per lane (C = 512).
+// Stacked segments: blockIdx.y = segment, its samples start at x + blockIdx.y * seg_stride and its rows at row blockIdx.y * rows
+// of out (rows = the layer's per-segment pitch, aud_api.hip); rows L .. rows - 1 of a segment are zero filler.  One clip:
+// grid.y = 1 and rows = L.
 template <class T, int KW>
 __global__ __launch_bounds__(256) void aud_conv0_ln_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                            int stride, int L, int C, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, typename T::elem* __restrict__ out,
-                                                           unsigned long long* sat) {
+                                                           unsigned long long* sat, long long seg_stride, int rows) {
   const int lane = threadIdx.x & 63;
   unsigned rm = 0u;  // range tracker (fh_range_flush)
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= L) return;
+  if (t >= rows) return;
+  x += (size_t)blockIdx.y * seg_stride;
+  out += ((size_t)blockIdx.y * rows) * C;
+  if (t >= L) {  // wave-uniform
+    for (int c = lane; c < C; c += 64) out[(size_t)t * C + c] = fh_cvt<T>(0.f, rm);
+    return;
+  }
   float xv[KW];
 #pragma unroll
   for (int k = 0; k < KW; ++k) xv[k] = x[(size_t)t * stride + k];
@@ -667,6 +687,8 @@ __global__ __launch_bounds__(256) void aud_meanpool_kernel(const float* __restri
   // fixed order (one thread per channel walking all Tn frames took 116 us at 500 frames)
   __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
+  h += (size_t)blockIdx.y * Tn * D;  // stacked segments: blockIdx.y = segment, Tn = its length, one pooled row each
+  out += (size_t)blockIdx.y * D;
   float s = 0.f;
   if (c < D)
     for (int t = w; t < Tn; t += 4) s += h[(size_t)t * D + c];
@@ -675,11 +697,13 @@ __global__ __launch_bounds__(256) void aud_meanpool_kernel(const float* __restri
   if (w == 0 && c < D) out[c] = ((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane])) / (float)Tn;
 }
 
-// y = act(W x + b), one wave per output; act 1 = tanh
+// y = act(W x + b), one wave per output; act 1 = tanh.  blockIdx.y = vector (one per stacked segment): x (n, K), y (n, N)
 __global__ __launch_bounds__(256) void aud_dense_kernel(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b,
                                                         float* __restrict__ y, int N, int K, int act) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
+  x += (size_t)blockIdx.y * K;
+  y += (size_t)blockIdx.y * N;
   float s = 0.f;
   for (int k = lane; k < K; k += 64) s += x[k] * W[(size_t)n * K + k];
   s = wave_sum(s);
@@ -690,10 +714,58 @@ __global__ __launch_bounds__(256) void aud_dense_kernel(const float* __restrict_
 }
 
 __global__ void aud_softmax_kernel(const float* __restrict__ x, float* __restrict__ y, int n) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (threadIdx.x != 0) return;
+  x += (size_t)blockIdx.x * n;  // one workgroup per row (stacked segments)
+  y += (size_t)blockIdx.x * n;
   float m = -INFINITY;
   for (int i = 0; i < n; ++i) m = fmaxf(m, x[i]);
   float s = 0.f;
   for (int i = 0; i < n; ++i) s += expf(x[i] - m);
   for (int i = 0; i < n; ++i) y[i] = expf(x[i] - m) / s;
+}
+
+// ------------------------------------------------------------------------------------------
+// float_aud_classify_segments, FLOAT_AUD_SEG_NORMALIZE: every segment to zero mean / unit variance on its own,
+// out = (x - mean) / sqrt(var + 1e-7) with the biased variance: float_aud_front's rule (audf_fold_kernel / audf_norm_kernel) per
+// segment.  One workgroup per segment: fp64 partial sums per thread (stride 256), a shuffle butterfly per wave and the four wave
+// sums added in a fixed order, so the statistics do not depend on anything but the segment - bitwise repeatable, no atomics.
+// The caller's samples are only read; the normalised copy is dense (n_seg, seg_len).
+__global__ __launch_bounds__(256) void aud_seg_norm_kernel(const float* __restrict__ x, long long seg_stride, int seg_len, float* __restrict__ out) {
+  __shared__ double red[4][2];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* xs = x + (size_t)blockIdx.x * seg_stride;
+  float* os = out + (size_t)blockIdx.x * seg_len;
+  double s1 = 0.0, s2 = 0.0;
+  for (int i = tid; i < seg_len; i += 256) {
+    const double v = (double)xs[i];
+    s1 += v;
+    s2 += v * v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s1 += __shfl_xor(s1, o, 64);
+    s2 += __shfl_xor(s2, o, 64);
+  }
+  if (lane == 0) {
+    red[w][0] = s1;
+    red[w][1] = s2;
+  }
+  __syncthreads();
+  const double t1 = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]), t2 = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+  const double mean = t1 / (double)seg_len;
+  const double var = fmax(t2 / (double)seg_len - mean * mean, 0.0);  // biased; a constant segment: 0, not a negative rounding
+  const double inv = 1.0 / sqrt(var + 1e-7);
+  for (int i = tid; i < seg_len; i += 256) os[i] = (float)(((double)xs[i] - mean) * inv);
+}
+
+// Nearest-neighbour expansion of n rows to T rows, F.interpolate(mode="nearest") along time: frames[t] = rows[min((int)
+// floorf((float)t * scale), n - 1)] with scale = (float)n / (float)T computed by the HOST (torch's fp32 form: the exact integer
+// t * n / T picks another row for some (n, T), e.g. (2, 82)).  n == 1 repeats the row.
+__global__ __launch_bounds__(256) void aud_nearest_rows_kernel(const float* __restrict__ rows, int n, int C, float* __restrict__ frames, int T,
+                                                               float scale) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= T * C) return;
+  const int t = idx / C, c = idx - t * C;
+  const int src = n > 1 ? min((int)floorf((float)t * scale), n - 1) : 0;
+  frames[idx] = rows[(size_t)src * C + c];
 }

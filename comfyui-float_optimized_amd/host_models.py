@@ -781,6 +781,47 @@ def emotion_index(name):
     return EMOTION_LABELS.index(name) if name in EMOTION_LABELS else None
 
 
+def dynamic_emotion_chunk_sec(emo, default_sec=2.0):
+    """The chunk length of a dynamic-emotion request, or None: emo == "dynamic" (any case) -> default_sec, ("dynamic", sec) ->
+    float(sec), a TUPLE (a list of emo values means one per item wherever a call takes several clips: infer_device_batch).
+    Everything else (a label, None, 'none', 'S2E', ...) is not dynamic."""
+    if isinstance(emo, list):
+        return None
+    if isinstance(emo, tuple):
+        if len(emo) == 2 and str(emo[0]).lower() == "dynamic":
+            return float(emo[1])
+        return None
+    return float(default_sec) if str(emo).lower() == "dynamic" else None
+
+
+def dynamic_emotion_plan(n_samples, rate, chunk_sec, fps):
+    """(chunk, n_chunks, tail_len, T) of a dynamic-emotion clip, as the reference's FloatExtractEmotionWithCustomModelDyn
+    computes them (src/nodes/nodes_vadv.py): chunk = int(chunk_sec * rate) samples per chunk, n_chunks = ceil(n_samples / chunk)
+    (the last one tail_len = n_samples - (n_chunks - 1) * chunk samples long, == chunk when it is full) and
+    T = ceil(n_samples / rate * fps) video frames."""
+    chunk = int(chunk_sec * rate)
+    if chunk == 0:
+        raise ValueError("Chunk duration is too small for the sample rate.")
+    n_samples = int(n_samples)
+    n_chunks = math.ceil(n_samples / chunk)
+    tail_len = n_samples - (n_chunks - 1) * chunk if n_chunks else 0
+    return chunk, n_chunks, tail_len, math.ceil(n_samples / rate * fps)
+
+
+def nearest_rows(seq, T):
+    """F.interpolate(seq.transpose(1, 2), size=T, mode="nearest").transpose(1, 2) for (..., n, C) -> (..., T, C), bitwise: row t
+    is row min(int(floor(fp32(t) * fp32(n / T))), n - 1), the scale and the product rounded to fp32 as torch's kernel does (the
+    exact integer t * n // T differs for some pairs, e.g. (n, T) = (2, 82)).  The definition float_aud_expand_rows is held to."""
+    import numpy as np
+    n, T = int(seq.shape[-2]), int(T)
+    if n == 1:
+        idx = torch.zeros(T, dtype=torch.long)
+    else:
+        scale = np.float32(n) / np.float32(T)
+        idx = torch.from_numpy(np.minimum(np.floor(np.arange(T, dtype=np.float32) * scale).astype(np.int64), n - 1))
+    return seq.index_select(-2, idx.to(seq.device))
+
+
 def emotion_one_hot(name, device="cpu"):
     """One-hot `we` (1,1,7) for a named emotion (FLOAT.py:196-200; float like nodes_adv.py:533-536)."""
     idx = emotion_index(name)

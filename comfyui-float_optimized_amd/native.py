@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfloat_hip.so")
 
 FLOAT_DT_BF16, FLOAT_DT_FP16, FLOAT_DT_FP32 = 0, 1, 2
 AUD_FRONT_NORMALIZE = 1  # FLOAT_AUD_FRONT_NORMALIZE: the `flags` bit of float_aud_front
+AUD_SEG_NORMALIZE = 1  # FLOAT_AUD_SEG_NORMALIZE: the `flags` bit of float_aud_classify_segments
 IMG_RGBA_MODES = {"discard_alpha": 0, "blend_with_color": 1, "replace_with_color": 2}  # FLOAT_IMG_RGBA_*: float_img_front's `rgba_mode`
 IMG_OUT_NCHW_PM1, IMG_OUT_HWC_U8 = 0, 1  # FLOAT_IMG_OUT_*: float_img_front's `out_mode`
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
@@ -135,6 +136,10 @@ _SIGNATURES = {
     "float_aud_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "float_aud_inference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "float_aud_debug": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "float_aud_reserve_segments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "float_aud_classify_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_float, C.c_void_p]),
+    "float_aud_expand_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "float_enc_feats16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "float_enc_export_feats16": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
     "float_fmt_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),

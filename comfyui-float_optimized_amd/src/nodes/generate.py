@@ -215,11 +215,18 @@ class InferenceAgent:
     def conditions_device(self, s, a, emo=None):
         """Once-per-clip stage on HIP operators, inputs already in HBM: s (1,3,H,W) in [-1,1] -> (s_r, feats handed to the
         decoder, r_s); a (N,) the normalised 16 kHz waveform -> (wa, T); and for any `emo` that is not one of the seven labels
-        (None, 'none', 'S2E', ...) the speech-emotion scores (FLOAT.py:196-198)."""
+        (None, 'none', 'S2E', ...) the speech-emotion scores (FLOAT.py:196-198).
+        emo = "dynamic" or ("dynamic", chunk_sec): one emotion vector per frame, `we` (1, T, 7) - the scores of every chunk of
+        chunk_sec seconds (default opt.wav2vec_sec), each normalised on its own, nearest-expanded to the T frames
+        (Audio2EmotionHIP.predict_emotion_chunks: one stacked pass on the device, the reference's dynamic-emotion node).  `a`
+        is the clip-normalised waveform; a chunk's own normalisation is invariant under that positive affine map."""
         o = self.opt
         if self.G is not None:
             self.G.require_no_stream("conditions_device")  # it hands this clip's skip features to the decoder an open stream reads
-        if host_models.emotion_index(emo) is None and self.emotion_predictor is None:
+        dyn_sec = host_models.dynamic_emotion_chunk_sec(emo, getattr(o, "wav2vec_sec", 2.0))
+        if dyn_sec is not None:
+            emo = None  # scores from the audio
+        if host_models.emotion_index(emo) is None and (self.emotion_predictor is None or (dyn_sec is not None and self.emotion_encoder is None)):
             raise NotImplementedError(
                 "emotion='none' asks the speech-emotion model for scores (FLOAT.py:196-198) but the checkpoint has "
                 "no `emotion_encoder.wav2vec2_for_emotion.` weights - pick an emotion or attach agent.emotion_predictor")
@@ -237,7 +244,11 @@ class InferenceAgent:
             if side is not None:
                 side.wait_stream(cur)  # `a` was produced on the caller's stream
             with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                we = self.emotion_predictor(a).reshape(1, 1, -1).to(self.rank)
+                if dyn_sec is not None:
+                    chunk = host_models.dynamic_emotion_plan(a.shape[-1], o.sampling_rate, dyn_sec, o.fps)[0]
+                    we = self.emotion_encoder.predict_emotion_chunks(a.reshape(-1), chunk, T)[1][None]
+                else:
+                    we = self.emotion_predictor(a).reshape(1, 1, -1).to(self.rank)
         wa = self.audio_encoder.inference(a, seq_len=T)
         s_r, _, _, r_s = self.enc.encode_image_into_latent(s, want_feats=False)  # FLOAT.py:283-291
         self.enc.hand_feats_to(self.G.dec)
@@ -936,18 +947,27 @@ class InferenceAgent:
         (FlowMatchingTransformerHIP.sample_ragged: a clip leaves the stack after its last window).  items: [(s (1,3,H,W), a (N,))] in HBM; seeds: one per
         item (FloatProcess uses seed + i, nodes.py:189-209) - each item keeps its own noise stream, so item i is what
         infer_device gives for it alone (bit for bit where the GEMM tilings coincide, within the fp16 tolerance otherwise).
+        emo: one value for all items, or a list with one per item (a list ALWAYS means per item: the chunk length goes in a tuple); dynamic emotion ("dynamic", ("dynamic", sec)) for all or none.
         Returns a list of (T,H,W,3) pinned host tensors, fp32 or - out_dtype=torch.uint8 - 8-bit frames as in infer_device; out_format="i420":
         (T,3H/2,W) uint8 planar YUV 4:2:0 as there, with `matrix` as there."""
         matrix = self._crop_matrix("infer_device_batch", None, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
-        self.to_target()
         B = len(items)
+        emos = list(emo) if isinstance(emo, list) else [emo] * B  # a list: one `emo` per item
+        if len(emos) != B:
+            raise ValueError("infer_device_batch: %d emo entries for %d items" % (len(emos), B))
+        dyn = [host_models.dynamic_emotion_chunk_sec(e) is not None for e in emos]
+        if any(dyn) and not all(dyn):
+            raise ValueError("infer_device_batch: dynamic emotion for every item of a batch or for none (one stacked chain takes `we` "
+                             "per frame for all clips or one row per clip); got %s" % (emos,))
+        dyn = all(dyn)
+        self.to_target()
         seeds = list(seeds) if seeds is not None else [self.opt.seed] * B
         # once-per-clip producers of every item; the encoder's skip maps of item i are copied aside (33 MB, a D2D copy) so
         # that no item needs a second encoder pass when its turn to decode comes
         conds, feats = [], []
         slots = self._feat_slots
         for i, (s, a) in enumerate(items):
-            conds.append(self.conditions_device(s, a, emo))
+            conds.append(self.conditions_device(s, a, emos[i]))
             if i >= len(slots):
                 slots.append(None)
             slots[i] = self.enc.export_feats16(slots[i])
@@ -958,12 +978,12 @@ class InferenceAgent:
             # clips of different lengths: one chain whose stack shrinks as clips end (float_fmt_sample_batch_ragged)
             noise = self._noise_ragged_to_device([self.G.n_chunks(c["T"]) for c in conds], seeds)
             r_d = self.G.batched_fmt(B).sample_ragged(r_s, [c["wa"].reshape(c["T"], -1) for c in conds],
-                                                      [c["we"].reshape(1, -1) for c in conds], noise, self.opt.nfe,
+                                                      [c["we"].reshape(c["T"] if dyn else 1, -1) for c in conds], noise, self.opt.nfe,
                                                       a_cfg_scale, r_cfg_scale, e_cfg_scale)
         else:
             noise = self._noise_batch_to_device(self.G.n_chunks(T), seeds)
             wa = torch.cat([c["wa"].reshape(1, T, -1) for c in conds])
-            we = torch.cat([c["we"].reshape(1, 1, -1) for c in conds])
+            we = torch.cat([c["we"].reshape(1, T if dyn else 1, -1) for c in conds])
             r_d = self.G.batched_fmt(B).sample(r_s, wa, we, noise, self.opt.nfe, a_cfg_scale, r_cfg_scale, e_cfg_scale)
         out = []
         for i in range(B):

@@ -363,7 +363,7 @@ class FloatExtractEmotionWithCustomModelDyn:
     FUNCTION = "extract_dynamic_emotion"
 
     def extract_dynamic_emotion(self, audio, emotion_model_pipe, target_fps, chunk_duration_sec):
-        model, normalise, info = emotion_model_pipe
+        model, _, info = emotion_model_pipe  # the normaliser slot is not used: the chunks are normalised on the device
         want = info.get("sampling_rate", 16000)
         if not isinstance(audio, dict) or "waveform" not in audio or "sample_rate" not in audio:
             raise TypeError("Input 'audio' must be a ComfyUI AUDIO dictionary.")
@@ -378,19 +378,12 @@ class FloatExtractEmotionWithCustomModelDyn:
         chunk = int(chunk_duration_sec * sr)
         if chunk == 0:
             raise ValueError("Chunk duration is too small for the sample rate.")
-        n_chunks = math.ceil(total / chunk)
-        seq = []
+        _, n_chunks, _, T = host_models.dynamic_emotion_plan(total, sr, chunk_duration_sec, target_fps)
+        # nodes_vadv.py:812-838: every chunk is normalised on its own, classified, and the scores nearest-neighbour up-sampled
+        # to T frames - per batch item one stacked pass on the device (Audio2EmotionHIP.predict_emotion_chunks: the equal chunks
+        # in one launch sequence, normalisation and expansion as kernels); the results come back in one copy each.
         with model_to_target(model):
-            for b in range(B):  # nodes_vadv.py:812-826: every chunk is normalised on its own, then classified
-                for i in range(n_chunks):
-                    piece = normalise(w[b, :, i * chunk:(i + 1) * chunk], sr, want)
-                    if piece.shape[1] < 400:  # shorter than the feature extractor's receptive field: pad by replication
-                        piece = torch.nn.functional.pad(piece[:, None], (0, 400 - piece.shape[1]), mode="replicate")[:, 0]
-                    seq.append(model.predict_emotion(piece))
-            seq = torch.cat(seq, dim=0).view(B, n_chunks, info["num_labels"]).cpu()
-        T = math.ceil(total / sr * target_fps)
-        if n_chunks > 1:  # nearest-neighbour up-sampling (nodes_vadv.py:835-838)
-            we = torch.nn.functional.interpolate(seq.transpose(1, 2), size=T, mode="nearest").transpose(1, 2)
-        else:
-            we = seq.repeat(1, T, 1)
+            out = [model.predict_emotion_chunks(w[b, 0], chunk, T) for b in range(B)]
+            seq = torch.stack([o[0] for o in out]).cpu()
+            we = torch.stack([o[1] for o in out]).cpu()
         return (we, emotion_model_pipe, seq)

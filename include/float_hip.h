@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
+/* Stays 6: float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
+ * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
  * Lanczos resampling of 8-bit frames on the device), float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
  * float_img_paste (the generated frames back in the source portrait on the device),
  * float_aud_debug (test hook of the audio attention stage), float_jpg_encode / float_jpg_work_bytes (baseline JPEG files from 8-bit frames on the device) and
@@ -471,8 +472,41 @@ int float_aud_classify(float_aud_t* h, const float* a, int32_t n_samples, float*
  *   what = 1: the attention launch exactly as float_aud_inference / float_aud_classify dispatch it for this handle (by operand
  *             type and by FLOAT_AUD_ATTN_MFMA as read at create): in (Tn, 3 * hidden) = [q | k | v] rows, rounded to the
  *             operand type; out (Tn, hidden) = softmax(q k^T / 8) v per head of 64, no mask, as the handle stores it.
- * in / out are fp32 device pointers.  Allocation-free: Tn beyond the reserved frames is refused - call float_aud_reserve first. */
+ * in / out are fp32 device pointers.  Allocation-free: Tn beyond the reserved frames is refused - call float_aud_reserve first.
+ *   what = 2: the normalised copy that the last float_aud_classify_segments(FLOAT_AUD_SEG_NORMALIZE) left in the workspace: the
+ *             first Tn floats of its dense (n_seg, seg_len) layout -> out.  `in` is not read (NULL allowed). */
 int float_aud_debug(float_aud_t* h, int32_t what, const float* in, int32_t Tn, float* out, void* stream);
+
+/* Dynamic emotion: the equal chunks of a clip through the speech-emotion model as ONE launch sequence (the reference's
+ * FloatExtractEmotionWithCustomModelDyn.extract_dynamic_emotion, src/nodes/nodes_vadv.py, calls predict_emotion once per
+ * 2-s chunk).  The chunks are independent sequences of equal length, so the transformer runs on n_seg x L stacked rows:
+ * every GEMM, LayerNorm and GELU launch is row-wise and serves as it is; the positional conv pads at every segment's edges,
+ * attention takes one grid plane per segment, and the mean over time and the head run per segment in the same launches.
+ * Additive: the ABI version does not change.
+ *   a:       device waveform at the model's rate; segment s = the seg_len samples at a + s * seg_stride, seg_stride >= seg_len.
+ *            Never written.
+ *   flags & FLOAT_AUD_SEG_NORMALIZE: every segment is first brought to zero mean / unit variance on its own,
+ *            (x - mean) / sqrt(var + 1e-7) with the biased variance and fp64 statistics: float_aud_front's rule per segment.
+ *            The normalised copy lives in the workspace.  Without the flag the segments are used as given.
+ *   scores:  (n_seg, num_labels); row s is what float_aud_classify defines for segment s alone.
+ *   frames:  NULL, or (T, num_labels): float_aud_expand_rows(scores, n_seg, num_labels, frames, T, scale).
+ * Handles with the classification head and feat_norm_layer = 1 only (GroupNorm statistics run over time).  Allocation-free:
+ * more than float_aud_reserve_segments reserved is refused (FLOAT_E_INVALID).  Bad arguments (n_seg < 1, seg_stride < seg_len,
+ * T < 1 with frames set, a segment below the extractor's receptive field, n_seg x L above the frame limit of one call, a
+ * handle of the wrong kind) are refused before any HIP call.
+ * float_aud_reserve_segments sizes the workspace of float_aud_reserve(seg_len, n_seg x L) plus the stacked extractor buffers;
+ * like float_aud_reserve it is the only allocation, never shrinks, synchronises `stream` when it grows, and is not capturable.
+ * float_aud_expand_rows (no handle) is F.interpolate(mode="nearest") along time on the device, n rows -> T rows of c floats:
+ *   frames[t] = rows[min((int)floorf((float)t * scale), n - 1)],  scale = (float)n / (float)T computed by the caller on the HOST
+ * (torch's fp32 form; the exact integer t * n / T picks another row for some pairs, e.g. (n, T) = (2, 82)); n == 1 repeats
+ * the row.  It is its own entry so that a clip with a shorter last chunk (scored by float_aud_classify into row n_seg of the
+ * same matrix) is expanded by one launch over all its rows. */
+enum { FLOAT_AUD_SEG_NORMALIZE = 1 };
+int float_aud_reserve_segments(float_aud_t* h, int32_t n_seg, int32_t seg_len, void* stream);
+int float_aud_classify_segments(float_aud_t* h, const float* a, int32_t n_seg, int32_t seg_len, int64_t seg_stride, int32_t flags,
+                                float* scores /* (n_seg, num_labels) */, float* frames /* (T, num_labels) or NULL */, int32_t T,
+                                float scale, void* stream);
+int float_aud_expand_rows(const float* rows, int32_t n, int32_t c, float* frames, int32_t T, float scale, void* stream);
 
 /* ---------------------------------------------------------------- misc ------------ */
 int float_hip_abi_version(void);
