@@ -3,6 +3,10 @@
 // NHWC in the operand type T like the encoder's (16-bit in production, fp32 in the verification mode), accumulation is fp32.
 // The maps are large and shallow (360 x 640 x 64 at the top), the opposite corner from the encoder's shapes; the convs read
 // both operands straight from global memory, and whether LDS staging would pay here has not been measured.
+// Every kernel takes n stacked views of one size (float_sfd_*_batch): the maps are packed [n][H][W][C], and the pixel index of a
+// launch runs over n x pixels, so the small deep maps of several views share 64-pixel tiles.  An output element's arithmetic
+// (taps, then 32-channel steps) does not depend on where its pixel sits in a tile or in the stack: view i of a stacked call is
+// bit for bit the single-view call.
 #pragma once
 #include "common.hpp"
 
@@ -15,7 +19,7 @@ constexpr int kSfdHeadC = 16;  // conf + loc of a level stacked (8 or 6 channels
 // w: [ky][kx][c_bgr][64] fp32, bias [64].
 template <class T>
 __global__ __launch_bounds__(256) void sfd_first_kernel(const unsigned char* __restrict__ rgb, const float* __restrict__ w,
-                                                        const float* __restrict__ bias, typename T::elem* __restrict__ out, int H,
+                                                        const float* __restrict__ bias, typename T::elem* __restrict__ out, int n, int H,
                                                         int W, unsigned long long* sat) {
   __shared__ float sw[27 * 64];
   __shared__ float sb[64];
@@ -23,10 +27,12 @@ __global__ __launch_bounds__(256) void sfd_first_kernel(const unsigned char* __r
   if (threadIdx.x < 64) sb[threadIdx.x] = bias[threadIdx.x];
   __syncthreads();
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)H * W * 8) return;
+  if (idx >= (size_t)n * H * W * 8) return;
   const int cg = (int)(idx & 7);
-  const size_t p = idx >> 3;
-  const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+  const size_t p = idx >> 3;  // over the n stacked views
+  const size_t view = p / ((size_t)H * W), pl = p - view * ((size_t)H * W);
+  rgb += view * ((size_t)H * W * 3);
+  const int y = (int)(pl / W), x = (int)(pl - (size_t)y * W);
   const float mean[3] = {104.f, 117.f, 123.f};
   float in[27];
 #pragma unroll
@@ -59,18 +65,18 @@ __global__ __launch_bounds__(256) void sfd_first_kernel(const unsigned char* __r
 
 // ------------------------------------------------------------------------------------------
 // Conv2d as an implicit GEMM on MFMA, the encoder's scheme (enc_conv_kernel) with this network's epilogue: k x k taps
-// (3 x 3 or 1 x 1), stride 1 | 2, any zero padding (fc6 pads by 3).  M = output pixels (64 per workgroup, 16 per wave), N = NT * 16
+// (3 x 3 or 1 x 1), stride 1 | 2, any zero padding (fc6 pads by 3).  M = output pixels of the n stacked views (64 per workgroup, 16 per wave), N = NT * 16
 // output channels, K = taps x Cin in 32-channel steps; a lane's 16 bytes are 8 consecutive channels of one pixel (A) or of one
 // (tap, output channel) weight row (B), both straight from global memory.  Operands are swapped (D = W * X^T): a lane ends
 // with 4 consecutive channels of one pixel.  Epilogue: + bias, optional ReLU; NHWC store in T (range-tracked) or, for the heads,
 // an fp32 NHWC store.  Cin is a multiple of 32, Cout (padded) a multiple of NT * 16.
 struct SfdConvArgs {
-  const void* X;      // [Hi][Wi][Cin] T::elem
+  const void* X;      // [n][Hi][Wi][Cin] T::elem
   const void* W;      // [k*k][Cout][Cin] T::elem
-  void* Y;            // [Ho][Wo][Cout] T::elem or nullptr
-  float* Yf32;        // [Ho][Wo][Cout] fp32 or nullptr
+  void* Y;            // [n][Ho][Wo][Cout] T::elem or nullptr
+  float* Yf32;        // [n][Ho][Wo][Cout] fp32 or nullptr
   const float* bias;  // [Cout]
-  int Hi, Wi, Cin, Cout, Ho, Wo, k, stride, pad, relu;
+  int n, Hi, Wi, Cin, Cout, Ho, Wo, k, stride, pad, relu;
   unsigned long long* sat;  // range counter of the 16-bit stores (fh_range_flush)
 };
 
@@ -78,15 +84,17 @@ template <class T, int NT>
 __global__ __launch_bounds__(256) void sfd_conv_kernel(SfdConvArgs g) {
   typedef typename T::elem E;
   typedef typename T::pack8 P8;
-  const E* const gX = reinterpret_cast<const E*>(g.X);
+  const E* gX = reinterpret_cast<const E*>(g.X);
   const E* const gW = reinterpret_cast<const E*>(g.W);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r16 = lane & 15, q = lane >> 4;
   const int npix = g.Ho * g.Wo;
   const int m = blockIdx.x * 64 + w * 16 + r16;
   const int n0 = blockIdx.y * NT * 16;
-  const bool mvalid = m < npix;
-  const int oy = mvalid ? m / g.Wo : 0, ox = mvalid ? m - oy * g.Wo : 0;
+  const bool mvalid = m < g.n * npix;
+  const int view = mvalid ? m / npix : 0, ml = mvalid ? m - view * npix : 0;
+  gX += (size_t)view * g.Hi * g.Wi * g.Cin;
+  const int oy = ml / g.Wo, ox = ml - oy * g.Wo;
   f32x4 acc[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -132,18 +140,19 @@ __global__ __launch_bounds__(256) void sfd_conv_kernel(SfdConvArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------
-// max_pool2d(2, 2) in floor mode on NHWC: (Hi, Wi) -> (Hi / 2, Wi / 2), an odd last row / column is dropped.
+// max_pool2d(2, 2) in floor mode on NHWC, n stacked views: (Hi, Wi) -> (Hi / 2, Wi / 2), an odd last row / column is dropped.
 // One thread = one output pixel x 8 channels.
 template <class T>
 __global__ __launch_bounds__(256) void sfd_pool_kernel(const typename T::elem* __restrict__ in, typename T::elem* __restrict__ out,
-                                                       int Hi, int Wi, int C, unsigned long long* sat) {
+                                                       int n, int Hi, int Wi, int C, unsigned long long* sat) {
   const int Ho = Hi >> 1, Wo = Wi >> 1, c8 = C >> 3;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)Ho * Wo * c8) return;
+  if (idx >= (size_t)n * Ho * Wo * c8) return;
   const int cg = (int)(idx % c8);
-  const size_t p = idx / c8;
-  const int y = (int)(p / Wo), x = (int)(p - (size_t)y * Wo);
-  const typename T::elem* s = in + ((size_t)(2 * y) * Wi + 2 * x) * C + cg * 8;
+  const size_t p = idx / c8;  // over the n stacked views
+  const size_t view = p / ((size_t)Ho * Wo), pl = p - view * ((size_t)Ho * Wo);
+  const int y = (int)(pl / Wo), x = (int)(pl - (size_t)y * Wo);
+  const typename T::elem* s = in + ((view * Hi + (size_t)(2 * y)) * Wi + 2 * x) * C + cg * 8;
   const typename T::pack8 a = T::load8(s), b = T::load8(s + C), c = T::load8(s + (size_t)Wi * C), d = T::load8(s + (size_t)Wi * C + C);
   typename T::pack8 o;
 #pragma unroll
@@ -194,12 +203,15 @@ __global__ __launch_bounds__(256) void sfd_l2norm_kernel(const typename T::elem*
 // ------------------------------------------------------------------------------------------
 // A level's head output [npix][16] fp32 (conf rows first, then the 4 loc rows) -> the definition's two maps, fp32 NCHW:
 // conf [2][npix] (level 0's 4 conf channels maxed out: channel 0 = max of the first three, channel 1 = the fourth) and loc
-// [4][npix].
+// [4][npix].  raw holds n stacked views; view v's maps lie view_stride floats behind view v - 1's.
 __global__ __launch_bounds__(256) void sfd_maps_kernel(const float* __restrict__ raw, float* __restrict__ conf, float* __restrict__ loc,
-                                                       int npix, int nconf) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= npix) return;
-  const float* r = raw + (size_t)p * kSfdHeadC;
+                                                       int n, size_t view_stride, int npix, int nconf) {
+  const int pg = blockIdx.x * 256 + threadIdx.x;
+  if (pg >= n * npix) return;
+  const int view = pg / npix, p = pg - view * npix;
+  const float* r = raw + (size_t)pg * kSfdHeadC;
+  conf += view * view_stride;
+  loc += view * view_stride;
   conf[p] = nconf == 4 ? fmaxf(fmaxf(r[0], r[1]), r[2]) : r[0];
   conf[(size_t)npix + p] = r[nconf - 1];
 #pragma unroll
@@ -210,7 +222,7 @@ __global__ __launch_bounds__(256) void sfd_maps_kernel(const float* __restrict__
 // Decoding of every position (host_models.sfd_decode_dense): level i has stride s = 2^(i + 2) (level 3 too, beyond the image
 // included), prior centre (s / 2 + x s, s / 2 + y s), prior size 4 s, variances (0.1, 0.2); score = 1 / (1 + exp(c0 - c1)).
 // maps: per level conf [2][n] then loc [4][n] at float offset 6 * pos0[level]; dense: [P][5] = x1, y1, x2, y2, score in
-// position order (level, y, x).
+// position order (level, y, x).  blockIdx.y = the view: its maps at 6 P floats, its rows at 5 P floats per view.
 struct SfdGeom {
   int h[kSfdLevels], w[kSfdLevels];
   int pos0[kSfdLevels + 1];  // first position of a level; pos0[6] = P
@@ -219,6 +231,8 @@ struct SfdGeom {
 __global__ __launch_bounds__(256) void sfd_decode_kernel(const float* __restrict__ maps, SfdGeom g, float* __restrict__ dense) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= g.pos0[kSfdLevels]) return;
+  maps += (size_t)blockIdx.y * 6 * g.pos0[kSfdLevels];
+  dense += (size_t)blockIdx.y * 5 * g.pos0[kSfdLevels];
   int l = 0;
 #pragma unroll
   for (int i = 1; i < kSfdLevels; ++i) l += p >= g.pos0[i] ? 1 : 0;
@@ -245,12 +259,12 @@ __global__ __launch_bounds__(256) void sfd_decode_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// Selection in ONE workgroup (host_models.sfd_select): the positions with score > score_thr are compacted in position order by
+// Selection in ONE workgroup per view (blockIdx.x = the view; host_models.sfd_select): the positions with score > score_thr are compacted in position order by
 // a ballot prefix scan (no atomic cursor: the order never depends on timing), ranked by (score descending, position ascending)
 // in LDS, and run through the greedy NMS (`+1` areas, a box is dropped when its IoU with a kept one EXCEEDS iou_thr).
 // boxes: up to max_boxes rows of 5 floats in keep order; counts = {kept, candidates}, both the TRUE numbers: with
 // candidates > cap nothing is selected (kept = 0) and the caller runs the definition on `dense`, which stays valid.
-// Dynamic LDS: cap * 32 bytes.
+// Per view: P dense rows, max_boxes rows of boxes, 2 counts.  Dynamic LDS: cap * 32 bytes.
 __global__ __launch_bounds__(256) void sfd_select_kernel(const float* __restrict__ dense, int P, float score_thr, float iou_thr, int cap,
                                                          int max_boxes, float* __restrict__ boxes, int* __restrict__ counts) {
   extern __shared__ float s_dyn[];
@@ -262,6 +276,9 @@ __global__ __launch_bounds__(256) void sfd_select_kernel(const float* __restrict
   __shared__ int s_wtot[4];
   __shared__ int s_base;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  dense += (size_t)blockIdx.x * P * 5;
+  boxes += (size_t)blockIdx.x * max_boxes * 5;
+  counts += blockIdx.x * 2;
   if (tid == 0) s_base = 0;
   __syncthreads();
   for (int base = 0; base < P; base += 256) {

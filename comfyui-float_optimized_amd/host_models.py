@@ -505,6 +505,17 @@ def preprocess_audio(waveform, sample_rate, target_rate=16000, device=None):
     return ((w - w.mean()) / torch.sqrt(w.var(unbiased=False) + 1e-7))[None]
 
 
+def process_img_view(img_hwc, front=None):
+    """The 360-px-high uint8 copy of the image that process_img shows its detector (utils/image.py:142-146): `front(360)` for an
+    image more than 360 px high when `front` is given, else the host resize (area down, bicubic up).  A caller that aligns a
+    batch of portraits makes the views with this, runs the detector on all of them at once and hands process_img the rows."""
+    mult = 360.0 / int(img_hwc.shape[0])
+    if front is not None and mult < 1.0:
+        return front(360)
+    small = F.interpolate(img_hwc.permute(2, 0, 1)[None], scale_factor=mult, mode="area" if mult < 1.0 else "bicubic")
+    return (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8)
+
+
 def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=None, detector=None):
     """The reference's face-aligned crop (utils/image.py:135-180) on an (H,W,3) float image in [0,1]: detect faces on a
     360-px-high copy, take box `index`, crop a square of `margin` x the larger half side around its centre from the
@@ -542,11 +553,7 @@ def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=Non
     use_device = fa is None and detector is not None and mode in ("auto", "device")
     if fa is not None or use_device:
         import numpy as np
-        if use_front:
-            small = front(360)
-        else:
-            small = F.interpolate(img_hwc.permute(2, 0, 1)[None], scale_factor=mult, mode="area" if mult < 1.0 else "bicubic")
-            small = (small[0].permute(1, 2, 0).clamp(0, 1) * 255).round().to(torch.uint8)
+        small = process_img_view(img_hwc, front)
         if use_device:
             det = detector(small)
         else:

@@ -175,6 +175,13 @@ _SIGNATURES = {
     "float_sfd_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "float_sfd_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "float_sfd_saturation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p]),
+    "float_sfd_reserve_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "float_sfd_maps_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "float_sfd_post_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "float_sfd_detect_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "float_sfd_dense_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

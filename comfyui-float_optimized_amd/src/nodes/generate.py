@@ -3,6 +3,7 @@ conditioning encoders and the HIP hot path, and exposes run_inference with the r
 import contextlib
 import math
 import os
+import weakref
 
 import torch
 
@@ -11,7 +12,7 @@ from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
 from ...face import FaceDetectorHIP, find_sfd_weights, load_sfd_state
-from ...image import (detector_view_device, front_takes, image_to_device, paste_format, preprocess_image_device, require_even_sides,
+from ...image import (detector_view_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
                       require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
@@ -39,7 +40,10 @@ def split_unified(state):
 
 
 class InferenceAgent:
+    latest = None  # weakref to the agent built last in this process: the pipe of the one Ad node that has no pipe input (Face Align)
+
     def __init__(self, opt, parts=None, device=None, max_frames=32, use_graph=2, fmt_dtype=None, dec_dtype=None, aud_dtype=None):
+        InferenceAgent.latest = weakref.ref(self)
         self.opt = opt
         self.rank = torch.device(device if device is not None else getattr(opt, "rank", "cuda:0"))
         self.cfg = FmtConfig.from_options(opt)
@@ -211,6 +215,15 @@ class InferenceAgent:
                                  lambda buf, i, k: buf[first[i] + k:first[i] + k + 1])
         return list(noise.split(list(n_chunks)))
 
+    NO_EMOTION_MODEL = ("emotion='none' asks the speech-emotion model for scores (FLOAT.py:196-198) but the checkpoint has "
+                        "no `emotion_encoder.wav2vec2_for_emotion.` weights - pick an emotion or attach agent.emotion_predictor")
+
+    def require_emotion_predictor(self):
+        """The callable (1, N) normalised audio -> (1, 7) scores, or the error conditions_device raises without one."""
+        if self.emotion_predictor is None:
+            raise NotImplementedError(self.NO_EMOTION_MODEL)
+        return self.emotion_predictor
+
     @torch.no_grad()
     def conditions_device(self, s, a, emo=None):
         """Once-per-clip stage on HIP operators, inputs already in HBM: s (1,3,H,W) in [-1,1] -> (s_r, feats handed to the
@@ -227,9 +240,7 @@ class InferenceAgent:
         if dyn_sec is not None:
             emo = None  # scores from the audio
         if host_models.emotion_index(emo) is None and (self.emotion_predictor is None or (dyn_sec is not None and self.emotion_encoder is None)):
-            raise NotImplementedError(
-                "emotion='none' asks the speech-emotion model for scores (FLOAT.py:196-198) but the checkpoint has "
-                "no `emotion_encoder.wav2vec2_for_emotion.` weights - pick an emotion or attach agent.emotion_predictor")
+            raise NotImplementedError(self.NO_EMOTION_MODEL)
         T = math.ceil(a.shape[-1] * o.fps / o.sampling_rate)  # FLOAT.py:192
         need_ser = host_models.emotion_index(emo) is None
         # The speech-emotion model (emotion = "none", the reference's default widget) is independent of the other two producers
@@ -291,6 +302,11 @@ class InferenceAgent:
         and its weight file is found (face.find_sfd_weights; never downloaded), else None.  device: a missing file is an error.
         The handle is built when the callable is first used - in auto mode an installed `face_alignment` package goes first and
         nothing is built - and is freed with the other operators in offload()."""
+        path = self._sfd_path()
+        return None if path is None else (lambda view: self._detect_faces(path, view))
+
+    def _sfd_path(self):
+        """The weight file of _face_detector's callable, or None where there is no such callable."""
         mode = host_models.face_detector_mode()
         if mode in ("package", "off"):
             return None
@@ -299,12 +315,10 @@ class InferenceAgent:
             if mode == "device":
                 raise FileNotFoundError("FLOAT_AMD_FACE_DETECTOR=device, but no s3fd weight file was found.  " + host_models.SFD_WEIGHTS_HINT)
             return None
-        return lambda view: self._detect_faces(path, view)
+        return path
 
-    def _detect_faces(self, path, view):
-        """S3FD on the (h, w, 3) uint8 view - on the device already (image.detector_view_device) or host-made (the H <= 360
-        route: uploaded) - with the handle built on first use.  Only the box rows and the two counts come back.
-        FLOAT_AMD_SFD_DTYPE = fp16 (default) | bf16 | fp32: fp32 is the remedy where check_range reports the detector."""
+    def _face_handle(self, path):
+        """The detector built from `path`, on first use or when the file or FLOAT_AMD_SFD_DTYPE changed."""
         from ... import native as _native
         key = (path, _native.canon_dtype(os.environ.get("FLOAT_AMD_SFD_DTYPE", "fp16")))
         if self.face is None or self._face_key != key:
@@ -312,16 +326,122 @@ class InferenceAgent:
                 self.face.close()
             self.face = FaceDetectorHIP(load_sfd_state(path), self.rank, dtype=key[1])
             self._face_key = key
-        h, w = int(view.shape[0]), int(view.shape[1])
-        if min(h, w) < host_models.SFD_MIN_SIDE or h > self.face.max_hw[0] or w > self.face.max_hw[1]:
-            main_logger.warning("face_align=True: a %d x %d detector view is outside the device detector's sizes (%d ... %d x %d): "
-                                "no face detection", h, w, host_models.SFD_MIN_SIDE, self.face.max_hw[0], self.face.max_hw[1])
-            return []
-        return self.face.detect(view)
+        return self.face
 
-    def _host_inputs(self, ref_img, ref_audio, no_crop, placed):
-        """The one body of host_inputs and host_inputs_placed: (s, a, place), place None unless `placed`."""
+    def _view_fits(self, face, view):
+        h, w = int(view.shape[0]), int(view.shape[1])
+        if min(h, w) < host_models.SFD_MIN_SIDE or h > face.max_hw[0] or w > face.max_hw[1]:
+            main_logger.warning("face_align=True: a %d x %d detector view is outside the device detector's sizes (%d ... %d x %d): "
+                                "no face detection", h, w, host_models.SFD_MIN_SIDE, face.max_hw[0], face.max_hw[1])
+            return False
+        return True
+
+    def _detect_faces(self, path, view):
+        """S3FD on the (h, w, 3) uint8 view - on the device already (image.detector_view_device) or host-made (the H <= 360
+        route: uploaded) - with the handle built on first use.  Only the box rows and the two counts come back.
+        FLOAT_AMD_SFD_DTYPE = fp16 (default) | bf16 | fp32: fp32 is the remedy where check_range reports the detector."""
+        face = self._face_handle(path)
+        return face.detect(view) if self._view_fits(face, view) else []
+
+    # ------------------------------------------------------------------ a batch of portraits: one detector pass
+    def _align_source(self, img, size, rgba, bkg):
+        """How _host_inputs treats an image with face_align: (True, the image on the device) on the device-front route, (False,
+        the (H, W, 3) float host image process_img gets) on the host routes (H <= 360, beyond the front end's size limits,
+        FLOAT_AMD_IMAGE_FRONT=0)."""
+        front_on = os.environ.get("FLOAT_AMD_IMAGE_FRONT", "1") != "0"
+        H, Wd, ch = int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+        if front_on and H > 360 and front_takes(H, Wd, size, crop=True):
+            return True, image_to_device(img, self.rank)
+        if front_on and ch == 4:
+            img = host_models.image_to_rgb8(img, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0
+        return False, img[..., :3].float()
+
+    def _found_faces(self, sources, rgba, bkg):
+        """For each (on_device, image) of _align_source: (view, rows) - the detector's view of the image and the rows of the
+        device detector on it - or None where the device detector is not the one process_img would use (FLOAT_AMD_FACE_DETECTOR
+        = off | package, auto with the `face_alignment` package at hand or without a weight file): those images take the
+        per-image route.  The views are made one by one (the front end on the device, process_img_view on the host routes),
+        stacked, and go through ONE FaceDetectorHIP.detect_batch per view size: one S3FD pass and one synchronisation for the
+        batch instead of one each per portrait."""
+        path = self._sfd_path()
+        if path is not None and host_models.face_detector_mode() == "auto":
+            try:
+                host_models._face_detector()  # the package goes first in auto mode, per image as before
+                path = None
+            except Exception:  # noqa: BLE001
+                pass
+        if path is None:
+            return [None] * len(sources)
+        face = self._face_handle(path)
+        views = [host_models.process_img_view(x, (lambda vh, x=x: detector_view_device(x, vh, rgba, bkg)) if on_dev else None)
+                 for on_dev, x in sources]
+        rows = [[] for _ in views]
+        groups = {}
+        for i, v in enumerate(views):
+            if self._view_fits(face, v):
+                groups.setdefault(tuple(v.shape), []).append(i)
+        for idx in groups.values():
+            stacked = torch.stack([views[i].to(self.rank, non_blocking=True) for i in idx])
+            for i, r in zip(idx, face.detect_batch(stacked)):
+                rows[i] = r
+        return list(zip(views, rows))
+
+    @torch.no_grad()
+    def face_align_batch(self, images, size=None, margin=None, index=1, rgba_conversion=None, bkg_color_hex=None):
+        """The face-aligned crops of a batch of portraits (the Ad tier's Face Align node): images (B, H, W, 3|4) float in
+        [0, 1] -> (crops8 (B, size, size, 3) uint8 on the device, rects = B tuples (x, y, w, h) as process_img returns them).
+        Item i is what the single-image route gives: process_img(..., index=index, front=..., detector=...) and the image
+        front end in its 8-bit output mode (on the host routes: process_img's crop, rounded to 8 bits).  The B detector views
+        go through one detect_batch (_found_faces); the crop rule is process_img's own, on the rows that came back.  Defaults
+        come from opt."""
         o = self.opt
+        size = int(size if size is not None else o.input_size)
+        margin = float(margin if margin is not None else getattr(o, "face_margin", 1.6))
+        rgba = rgba_conversion if rgba_conversion is not None else getattr(o, "rgba_conversion", "blend_with_color")
+        bkg = bkg_color_hex if bkg_color_hex is not None else getattr(o, "bkg_color_hex", "#000000")
+        if images.dim() != 4 or images.shape[-1] not in (3, 4):
+            raise ValueError("face_align_batch: images must be (B, H, W, 3|4), got %s" % (tuple(images.shape),))
+        self.to_target()
+        sources = [self._align_source(images[i], size, rgba, bkg) for i in range(images.shape[0])]
+        found = self._found_faces(sources, rgba, bkg)
+        crops, rects = [], []
+        for (on_dev, x), f in zip(sources, found):
+            front = None
+            if on_dev:
+                front = (lambda vh, v=f[0]: v) if f is not None else (lambda vh, x=x: detector_view_device(x, vh, rgba, bkg))
+            detector = (lambda view, r=f[1]: r) if f is not None else self._face_detector()
+            crop, rect = host_models.process_img(x, size, margin, index=index, logger=main_logger, front=front, detector=detector)
+            if on_dev:
+                crop8 = image_front_device(x, size, size, rect, None, rgba, bkg, True)
+            else:
+                crop8 = (crop.clamp(0, 1) * 255).round().to(torch.uint8).to(self.rank, non_blocking=True)
+            crops.append(crop8)
+            rects.append(tuple(int(v) for v in rect))
+        return torch.stack(crops), rects
+
+    def host_inputs_batch(self, ref_images, audios, no_crop=True):
+        """host_inputs for a batch: ref_images (B, H, W, C) or a list of B images, audios a list of B AUDIO items -> a list of
+        (s, a); item i is bitwise host_inputs(ref_images[i:i+1], audios[i], no_crop).  With face_align the B detector views
+        go through one detect_batch (_found_faces) instead of B detector passes and B synchronisations."""
+        o = self.opt
+        imgs = [x[0] if x.dim() == 4 else x for x in (ref_images if isinstance(ref_images, (list, tuple)) else
+                                                       [ref_images[i] for i in range(ref_images.shape[0])])]
+        if len(imgs) != len(audios):
+            raise ValueError("host_inputs_batch: %d images, %d audio items" % (len(imgs), len(audios)))
+        found = [None] * len(imgs)
+        if not no_crop:
+            rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+            sources = [self._align_source(x, o.input_size, rgba, bkg) for x in imgs]
+            found = self._found_faces(sources, rgba, bkg)
+            imgs = [src if on_dev else x for x, (on_dev, src) in zip(imgs, sources)]  # on the device already: not uploaded twice
+        return [self._host_inputs(x, a, no_crop, False, f)[:2] for x, a, f in zip(imgs, audios, found)]
+
+    def _host_inputs(self, ref_img, ref_audio, no_crop, placed, found=None):
+        """The one body of host_inputs and host_inputs_placed: (s, a, place), place None unless `placed`.  found: (view, rows)
+        of _found_faces for this image - the detector's view and what the device detector found on it - where a batch has them
+        already."""
+        o = self.opt
+        detector = (lambda view: found[1]) if found is not None else None
         img = ref_img[0] if ref_img.dim() == 4 else ref_img
         # The image front end on the device (float_img_front): the raw IMAGE tensor crosses PCIe once, and RGBA conversion
         # (opt.rgba_conversion, opt.bkg_color_hex), the zero-bordered crop, the exact area resize, the 8-bit rounding and the
@@ -340,8 +460,9 @@ class InferenceAgent:
             rect = None
             if not no_crop:  # generate.py:77-78
                 rect, _ = host_models.process_img(dimg, o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger,
-                                                  front=lambda view_h: detector_view_device(dimg, view_h, rgba, bkg),
-                                                  detector=self._face_detector())
+                                                  front=(lambda view_h: found[0]) if found is not None else
+                                                  (lambda view_h: detector_view_device(dimg, view_h, rgba, bkg)),
+                                                  detector=detector or self._face_detector())
             if ch == 3 and (H, Wd) == (o.input_size, o.input_size) and rect is not None and tuple(rect) == (0, 0, Wd, H):
                 # the crop turned out to be the whole image (a square portrait without a detected face): nothing to convert,
                 # crop or resize after all, so this is the case of the lines below, bitwise
@@ -356,7 +477,7 @@ class InferenceAgent:
         bbox = (0, 0, Wd, H)
         if not no_crop:  # generate.py:77-78
             img, bbox = host_models.process_img(img[..., :3].float(), o.input_size, getattr(o, "face_margin", 1.6), logger=main_logger,
-                                                detector=self._face_detector())
+                                                detector=detector or self._face_detector())
         # The raw tensors cross PCIe first (3 MB + 0.6 MB for a 10-s clip) and the elementwise / reduction plumbing runs on the
         # device: on the host the same ops cost 1-29 ms per clip (torch's 128-thread intra-op pool on sub-megabyte tensors),
         # as much as a quarter of the whole clip.  The reference moves its slices to the device first too (nodes.py:193-201).

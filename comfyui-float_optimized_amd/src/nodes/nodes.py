@@ -114,12 +114,18 @@ class FloatProcess:
         if target_batch_size > 1 and hasattr(float_pipe, "infer_device_batch") and os.environ.get("FLOAT_AMD_BATCH_CLIPS", "1") != "0":
             # the items of one call have equal length (one audio tensor): their FMT chains run stacked
             # (InferenceAgent.infer_device_batch -> float_fmt_sample_batch), each with its own noise stream of seed + i
-            items = []
+            items, imgs, auds = [], [], []
             for i in range(target_batch_size):
                 ii, ai = min(i, image_batch_size - 1), min(i, audio_batch_size - 1)
                 wf = audio_waveform[ai:ai + 1]
-                items.append(float_pipe.host_inputs(ref_image[ii:ii + 1], {'waveform': wf, 'sample_rate': audio_sample_rate}, not face_align))
+                imgs.append(ref_image[ii:ii + 1])
+                auds.append({'waveform': wf, 'sample_rate': audio_sample_rate})
                 used_audio.append(wf.cpu())
+            if face_align and hasattr(float_pipe, "host_inputs_batch"):
+                # the portraits' detector views in one S3FD pass with one synchronisation (InferenceAgent.host_inputs_batch)
+                items = float_pipe.host_inputs_batch(imgs, auds, False)
+            else:
+                items = [float_pipe.host_inputs(img, aud, not face_align) for img, aud in zip(imgs, auds)]
             all_images = float_pipe.infer_device_batch(items, a_cfg_scale, float_pipe.opt.r_cfg_scale, e_cfg_scale,
                                                        None if emotion == "none" else emotion,
                                                        [seed + i for i in range(target_batch_size)])

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
+/* Stays 6: float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
+ * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
  * Lanczos resampling of 8-bit frames on the device), float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
  * float_img_paste (the generated frames back in the source portrait on the device),
@@ -842,6 +843,31 @@ int float_sfd_post(float_sfd_t* h, const float* maps12, int32_t H, int32_t W, fl
 /* The dense rows (P, 5) of the last detect / post call on the handle, copied on `stream`. */
 int float_sfd_dense(float_sfd_t* h, float* scores_boxes, void* stream);
 int float_sfd_saturation(float_sfd_t* h, uint64_t* total, int32_t reset, void* stream);
+
+/* n stacked views of ONE size in one pass (a batch of portraits behind face_align): rgb8 (n, H, W, 3), maps12 (n, 6 P),
+ * boxes (n, max_boxes, 5), counts (n, 2) = {kept, candidates} per view, dense rows (n, P, 5).  The kernels run over n x pixels
+ * (the small maps of conv5_* ... conv7_2, 22 x 40 pixels and less at 360 x 640, of several views share 64-pixel tiles), decode runs one grid row per view
+ * and the selection one workgroup per view, all in one launch each.  View i of every call is BIT FOR BIT what the single-view
+ * call returns for that view alone, in fp16, bf16 and fp32: an output element's accumulation order (taps, then 32-channel
+ * steps) does not depend on its place in a tile or in the stack, and nothing is split over K.  Views are independent: one with
+ * candidates > max_candidates reports {0, candidates} and its neighbours are selected normally; one with no candidate reports
+ * {0, 0}.  The range counter stays one per handle.
+ *   float_sfd_reserve_batch grows the handle's workspace to n views of H x W (1 <= n <= 64, H x W within max_h x max_w) and
+ * never shrinks it; the largest n, H and W reserved so far are what the other four calls accept.  Of the
+ * five calls it alone allocates, and where it has to grow it synchronises the device (the dense rows of an earlier call are then gone); a reservation that cannot be allocated (FLOAT_E_NOMEM) leaves the handle as it was.
+ * Per view the workspace is every term of the single view's: two ping-pong activation buffers of H x W x 64 elements (at
+ * 360 x 640 in a 16-bit type 29.5 MB each), the L2Norm map (H/4 x W/4 x 256 elements, 7.4 MB), the head output, maps and dense
+ * rows (under 2 MB together): about 68 MB per view, 1.1 GB for sixteen views.
+ *   The other four return FLOAT_E_INVALID before any HIP call, with a message naming the function and the argument, when n is
+ * outside 1 ... the reserved n, when the view exceeds the reserved size, or for a null pointer.  The single-view calls are
+ * unchanged; float_sfd_dense after a batched call returns view 0's rows. */
+int float_sfd_reserve_batch(float_sfd_t* h, int32_t n, int32_t H, int32_t W);
+int float_sfd_maps_batch(float_sfd_t* h, const void* rgb8, int32_t n, int32_t H, int32_t W, float* maps12, void* stream);
+int float_sfd_post_batch(float_sfd_t* h, const float* maps12, int32_t n, int32_t H, int32_t W, float score_thr, float iou_thr, float* boxes,
+                         int32_t* counts, void* stream);
+int float_sfd_detect_batch(float_sfd_t* h, const void* rgb8, int32_t n, int32_t H, int32_t W, float score_thr, float iou_thr, float* boxes,
+                           int32_t* counts, void* stream);
+int float_sfd_dense_batch(float_sfd_t* h, float* scores_boxes, void* stream);
 
 #ifdef __cplusplus
 }
