@@ -4,49 +4,8 @@
 #include <math.h>
 
 #include "dec_kernels.hpp"  // dec_conv16_kernel: the LDS-staged 3x3 conv of the decoder, used for the ResBlocks' conv1
+#include "enc_handle.hpp"  // struct float_enc
 #include "enc_kernels.hpp"
-#include "tuning.hpp"
-
-namespace {
-
-struct EConv {
-  void* W = nullptr;     // [k*k][Cout][Cin] T::elem, equalised-lr scale folded in
-  float* bias = nullptr; // [Cout] FusedLeakyReLU bias or nullptr
-  int cin = 0, cout = 0, k = 0;
-};
-
-struct ResBlk {
-  EConv conv1, conv2, skip;
-  int R = 0;  // input resolution
-  EncFir fir2, firs;  // the Blur in front of conv2 / of the skip conv, flipped (enc_blur_taps)
-};
-
-struct FcLayer {
-  float* W = nullptr;
-  float* b = nullptr;
-  int n = 0, k = 0;
-};
-
-}  // namespace
-
-struct float_enc {
-  float_enc_cfg_t cfg;
-  EncTune tune;
-  DevicePool pool;
-  int C0 = 0;
-  float *w0 = nullptr, *b0 = nullptr;  // convs.0: [C0][3] scaled, [C0]
-  std::vector<ResBlk> blocks;
-  EConv last;                          // EqualConv2d(C, dim, 4, padding 0, no bias)
-  std::vector<FcLayer> fc;
-  float* Q = nullptr;                  // [dim][dim_motion] of QR(direction.weight + 1e-8), or nullptr
-  // activations: res[i] (NHWC 16-bit) for i = 0..n_blocks (res[0] = convs.0 output), scratch for
-  // conv1 output, the two blurred images and the skip branch
-  std::vector<void*> res;  // T::elem
-  std::vector<int> resR, resC;
-  void *t1 = nullptr, *tb = nullptr, *tsk = nullptr;
-  float *s_r = nullptr, *fcA = nullptr, *fcB = nullptr;
-  unsigned long long* sat = nullptr;  // range counter of every 16-bit activation store (float_enc_saturation): conv1 of the ResBlocks runs the decoder's kernel (overflow -> inf, counted), the other layers clamp at 65504 and count
-};
 
 namespace {
 
@@ -415,6 +374,7 @@ int float_enc_create(const float_enc_cfg_t* cfg, const float_tensor_t* tensors, 
 
 void float_enc_destroy(float_enc_t* h) {
   if (!h) return;
+  h->motion.release();
   h->pool.release();
   delete h;
 }

@@ -4,6 +4,7 @@
 // the decoder without a round trip; accumulation is fp32.
 #pragma once
 #include "common.hpp"
+#include "enc_fir.hpp"
 
 // ------------------------------------------------------------------------------------------
 // convs.0 = ConvLayer(3, C, 1): EqualConv2d 1x1 (scale 1/sqrt(3), no bias) + FusedLeakyReLU
@@ -37,9 +38,7 @@ __global__ __launch_bounds__(256) void enc_first_kernel(const float* __restrict_
 // 4 x 4 FIR (upfirdn2d, encoder.py:28-29); output (R + 2p - 3)^2.  One thread = one pixel x 8 channels.
 // EncFir: k[a][b] = weight of in[Y + a - pad][X + b - pad] = the layer's `kernel` buffer flipped in both axes
 // (make_kernel([1,3,3,1]) = (1,3,3,1) (x) (1,3,3,1) / 64 for every released checkpoint; exact in fp32 either way).
-struct EncFir {
-  float k[16];
-};
+// (struct EncFir: enc_fir.hpp)
 template <class T>
 __global__ __launch_bounds__(256) void enc_blur_kernel(const typename T::elem* __restrict__ in, typename T::elem* __restrict__ out,
                                                        int R, int C, int pad, EncFir fir, unsigned long long* sat) {

@@ -71,12 +71,64 @@ class EncoderHIP:
                 native.stream_ptr(dev)))
         return s_r, lam, feats, r_s
 
+    @torch.no_grad()
+    def encode_motion(self, frames_u8, block=None):
+        """Motion coefficients of T driving frames (float_enc_motion): frames_u8 (T,S,S,3) uint8 NHWC on the device ->
+        lambda (T, dim_motion) fp32, `fc(net_app(q / 127.5 - 1))` per frame (encoder.py:262-277).  The frames go through in
+        blocks of `block` frames (None: the handle's current block, 8 on first use) over a scratch of their own: the source
+        portrait's state in the handle (s_r, the skip maps) stays what the last encode_image_into_latent left.  Row t does not
+        depend, by a bit, on T, on `block` or on the other frames."""
+        S = self.size
+        if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or tuple(frames_u8.shape[1:]) != (S, S, 3) or frames_u8.shape[0] < 1:
+            raise ValueError("driving frames must be (T,%d,%d,3) uint8 with T >= 1, got %s %s" % (S, S, tuple(frames_u8.shape), frames_u8.dtype))
+        frames_u8 = frames_u8.to(self.device).contiguous()
+        lam = torch.empty(frames_u8.shape[0], self.dim_motion, device=self.device)
+        L = native.lib()
+        with torch.cuda.device(self.device):
+            if block is not None:
+                native.check(L.float_enc_motion_reserve(self._h, int(block)))
+            native.check(L.float_enc_motion(self._h, C.c_void_p(frames_u8.data_ptr()), frames_u8.shape[0], native.dev_ptr(lam),
+                                            native.stream_ptr(self.device)))
+        return lam
+
+    DRIVE_MODES = {"absolute": 0, "relative": 1}
+
+    @torch.no_grad()
+    def drive_rows(self, lam, mode="relative", lam_source=None, lam_start=None):
+        """Driving rows r_d (T, dim) of the decoder from lambda rows (float_enc_drive_rows; host_models.drive_rows is the
+        definition).  "absolute": Direction(lam[t]); "relative": Direction(lam[t] - lam_start + lam_source), lam_source the
+        portrait's own lambda (encode_image_into_latent()[1]), lam_start the driving clip's reference row (None: lam[0])."""
+        if mode not in self.DRIVE_MODES:
+            raise ValueError("drive_rows: mode must be 'relative' or 'absolute', got %r" % (mode,))
+        if mode == "relative" and lam_source is None:
+            raise ValueError("drive_rows: the relative mode needs lam_source, the portrait's own lambda")
+        dev = self.device
+        row = lambda v: None if v is None else v.to(dev, torch.float32).reshape(self.dim_motion).contiguous()
+        lam = lam.to(dev, torch.float32).reshape(-1, self.dim_motion).contiguous()
+        src, start = row(lam_source), row(lam_start)
+        r_d = torch.empty(lam.shape[0], self.dim, device=dev)
+        with torch.cuda.device(dev):
+            native.check(native.lib().float_enc_drive_rows(self._h, native.dev_ptr(lam), lam.shape[0], self.DRIVE_MODES[mode], native.dev_ptr(src),
+                                                           native.dev_ptr(start), native.dev_ptr(r_d), native.stream_ptr(dev)))
+        return r_d
+
+    def quantise_frames(self, x):
+        """(T,3,S,S) in [-1,1] -> (T,S,S,3) uint8, q = round((x + 1) * 127.5) clamped to 0..255: the 8-bit grid the motion pass
+        reads (q / 127.5 - 1 gives back x for every x that came from 8-bit pixels)."""
+        x = x.to(self.device, torch.float32).reshape(-1, 3, self.size, self.size)
+        return ((x + 1.0) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
     def forward(self, input_source, input_target=None, h_start=None):
-        """Encoder.forward with input_target=None (encoder.py:277-281): (h_source, None, feats)."""
-        if input_target is not None:
-            raise NotImplementedError("the inference path only encodes the source image (FLOAT.py:283-286)")
-        s_r, _, feats, _ = self.encode_image_into_latent(input_source)
-        return s_r, None, feats
+        """Encoder.forward (encoder.py:262-281).  input_target=None: (h_source, None, feats).  With input_target (T,3,S,S) in
+        [-1,1]: (h_source, [h_motion_target], feats), or with h_start (a lambda row) (h_source, [h_motion_target,
+        h_motion_source, h_start], feats) - the lists Synthesis.forward takes as `alpha`.  The target frames are QUANTISED to
+        the 8-bit grid on the way in (quantise_frames): the motion pass reads 8-bit frames, which is what a video holds."""
+        if input_target is None:
+            s_r, _, feats, _ = self.encode_image_into_latent(input_source)
+            return s_r, None, feats
+        s_r, lam_s, feats, _ = self.encode_image_into_latent(input_source)
+        h_t = self.encode_motion(self.quantise_frames(input_target))
+        return s_r, ([h_t] if h_start is None else [h_t, lam_s, h_start]), feats
 
     __call__ = forward
 

@@ -778,6 +778,20 @@ def sfd_detect(state, rgb8, score_thr=0.5, iou_thr=0.3):
         return sfd_select(sfd_decode_dense(sfd_forward(state, rgb8)), score_thr, iou_thr)
 
 
+def drive_rows(lam, Q, mode="relative", lam_source=None, lam_start=None):
+    """Driving rows of a portrait driven by video (Synthesis.forward, styledecoder.py:497-508, without the `wa +`: the decoder
+    adds s_r itself).  lam (T, dim_motion): the driving frames' motion coefficients; Q (dim, dim_motion): Direction's
+    orthonormal basis, Direction(x) = x @ Q.T (linear, styledecoder.py:434-444).  "absolute" (one alpha): Direction(lam);
+    "relative" (three alphas): (Direction(lam) - Direction(lam_start)) + Direction(lam_source) = Direction(lam - lam_start +
+    lam_source), lam_start None = lam[0].  In the dtype of `lam`."""
+    if mode == "absolute":
+        return lam @ Q.to(lam.dtype).T
+    if mode != "relative":
+        raise ValueError("drive_rows: mode must be 'relative' or 'absolute', got %r" % (mode,))
+    start = lam[0:1] if lam_start is None else lam_start.to(lam.dtype).reshape(1, -1)
+    return ((lam - start) + lam_source.to(lam.dtype).reshape(1, -1)) @ Q.to(lam.dtype).T
+
+
 EMOTION_LABELS = ["angry", "disgust", "fear", "happy", "neutral", "sad", "surprise"]  # FLOAT.py:390
 
 

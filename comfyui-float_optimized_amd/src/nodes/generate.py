@@ -556,6 +556,28 @@ class InferenceAgent:
                 return self.infer_device(s, a, a_cfg_scale, r_cfg_scale, e_cfg_scale, emo, seed, out, out_dtype, out_format, matrix)  # once more, in fp32
         return host
 
+    @torch.no_grad()
+    def drive_device(self, s, frames_u8, mode="relative", out=None, out_dtype=None, out_format=None, matrix=None):
+        """The portrait driven by VIDEO instead of audio (the motion autoencoder's own route, encoder.py:262-277 +
+        styledecoder.py:497-508): s (1,3,H,W) in [-1,1] and frames_u8 (T,H,W,3) uint8 driving frames of the model's size, both
+        in HBM -> T frames in pinned host memory, one per driving frame.  The source is encoded once (s_r, skip features to the
+        decoder, its own lambda), the driving frames go through EncoderHIP.encode_motion and drive_rows(mode) - "relative":
+        motion relative to the first driving frame, applied to the portrait's pose; "absolute": the driving frame's motion as
+        it is - and the rows are decoded exactly as infer_device decodes the FMT's: out, out_dtype, out_format and matrix as
+        there.  FLOAT_AMD_RANGE is applied once after the frames have arrived: warn, raise and off as in infer_device; auto
+        acts as warn (nothing is rebuilt and run again here)."""
+        matrix = self._crop_matrix("drive_device", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
+        self.to_target()  # no-op while resident
+        self.G.require_no_stream("drive_device")  # it hands this portrait's skip features to the decoder an open stream reads
+        s_r, lam_s, _, _ = self.enc.encode_image_into_latent(s, want_feats=False)
+        self.enc.hand_feats_to(self.G.dec)
+        r_d = self.enc.drive_rows(self.enc.encode_motion(frames_u8), mode, lam_source=lam_s)
+        host = self.G.decode_to_host(s_r, r_d, None, None, out, out_dtype, out_format, matrix)
+        torch.cuda.current_stream(self.rank).synchronize()  # the frames are in host memory
+        self.G.release_host_inflight()
+        self.check_range("InferenceAgent.drive_device")
+        return host
+
     def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,
                       out_format=None, slots=3, matrix=None):
         """The streaming sibling of infer_device: a generator of FrameBlock(first, last, frames), one per 50-frame FMT window, in

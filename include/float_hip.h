@@ -414,6 +414,22 @@ int float_enc_feats16(float_enc_t* h, const void** feats16, int32_t* channels, i
  * is decoded, instead of encoding the item a second time. */
 int float_enc_export_feats16(float_enc_t* h, void* const* dst, int32_t n_feats, void* stream);
 
+/* The motion pass: one lambda row per DRIVING frame (encoder.py:262-277, `fc(net_app(input_target))`), for a portrait driven
+ * by video instead of audio.  frames: (T, size, size, 3) uint8 NHWC on the device (what float_dec_frames_u8 and the image
+ * front end's 8-bit mode produce); the first layer forms q / 127.5 - 1 itself.  lam: (T, dim_motion) fp32.  The frames go
+ * through in blocks of `block` frames (default 8, taken on first use) over a scratch of the pass's own - per frame and element
+ * size e: (2 size^2 C(size) + (size/2)^2 C(size/2)) e bytes, 42 MB at 512 px in 16 bits - so the handle's source-portrait state
+ * (s_r, the maps behind float_enc_feats16 / float_enc_export_feats16) is left exactly as float_enc_forward wrote it.  Row t does
+ * not depend, by a bit, on T, on `block` or on the other frames.  float_enc_motion_reserve with another `block` waits for the
+ * device and replaces the scratch.  16-bit stores are counted by float_enc_saturation. */
+int float_enc_motion_reserve(float_enc_t* h, int32_t block);
+int float_enc_motion(float_enc_t* h, const uint8_t* frames, int32_t T, float* lam, void* stream);
+/* Driving rows for the decoder from lambda rows (Synthesis.forward, styledecoder.py:497-508; needs direction.weight), fp32:
+ * mode 0, absolute: r_d[t] = lam[t] Q^T; mode 1, relative: r_d[t] = ((lam[t] - lam_start) + lam_source) Q^T, with lam_start
+ * (dim_motion) NULL = lam[0].  lam_source: the portrait's own lambda (float_enc_forward's `lam`); unused in mode 0.  r_d: (T, dim). */
+int float_enc_drive_rows(float_enc_t* h, const float* lam, int32_t T, int32_t mode, const float* lam_source,
+                         const float* lam_start, float* r_d, void* stream);
+
 /* ---------------------------------------------------------------- audio encoder --- */
 /* Audio conditioning, once per clip: AudioEncoder.inference (reference
  * src/nodes/models/float/FLOAT.py:370-375) = Wav2VecModel.forward(input_values, seq_len,
