@@ -81,10 +81,11 @@ def image_to_rgb8(img, rgba_conversion="blend_with_color", bkg_rgb8=(0, 0, 0)):
       blend_with_color    rgb * (a / 255.0) + bkg * (1.0 - a / 255.0) in fp32, every operation rounded on its own (no fused
                           multiply-add), clipped to 0 ... 255 and truncated
       anything else       a logged warning, then discard_alpha - as in the reference.
+    A uint8 image (a decoded video frame) is q already: the quantiser alone is left out, the conversion above is the same.
     Torch on the CPU; this is the definition `float_img_front` is held to, as rgb8_to_i420 is for the I420 kernels."""
-    if img.dim() != 3 or img.shape[-1] not in (3, 4) or not img.is_floating_point():
-        raise ValueError("image_to_rgb8 takes an (H, W, 3) or (H, W, 4) float image, got %s %s" % (img.dtype, tuple(img.shape)))
-    q = _quant8(img.detach().cpu())
+    if img.dim() != 3 or img.shape[-1] not in (3, 4) or not (img.is_floating_point() or img.dtype == torch.uint8):
+        raise ValueError("image_to_rgb8 takes an (H, W, 3) or (H, W, 4) float or uint8 image, got %s %s" % (img.dtype, tuple(img.shape)))
+    q = img.detach().cpu() if img.dtype == torch.uint8 else _quant8(img.detach().cpu())
     if q.shape[-1] == 3:
         return q
     rgb, a = q[..., :3], q[..., 3]
@@ -590,6 +591,107 @@ def process_img(img_hwc, input_size, margin=1.6, index=1, logger=None, front=Non
             c = F.interpolate(c, size=(input_size, input_size), mode="bicubic", align_corners=False).clamp(0, 1)  # INTER_CUBIC
         crop = c[0].permute(1, 2, 0)
     return crop, bbox_r
+
+
+# ---------------------------------------------------------------------------------------------- the crop of a driving video
+DRIVING_CROPS = ("fixed", "track", None)
+
+
+def driving_detect_frames(T, detect_every=5):
+    """The frames of a T-frame clip that the detector looks at: 0, detect_every, 2 detect_every, ... and T - 1."""
+    T, k = int(T), int(detect_every)
+    if T < 1 or k < 1:
+        raise ValueError("driving_detect_frames: T (%d) and detect_every (%d) must be at least 1" % (T, k))
+    return sorted(set(range(0, T, k)) | {T - 1})
+
+
+def _centre_half(b, margin):
+    """process_img's rule on a box (x1, y1, x2, y2): the centre and the half side of the crop.  The one departure: the half
+    side is at least 1 (process_img has no such clamp), so a degenerate box gives a 2-px window instead of an empty one that
+    float_img_front_frames would refuse."""
+    bsy, bsx = int((b[3] - b[1]) / 2), int((b[2] - b[0]) / 2)
+    return int((b[0] + b[2]) / 2), int((b[1] + b[3]) / 2), max(1, int(max(bsy, bsx) * margin))
+
+
+def _chosen_boxes(rows, H, index, logger):
+    """One box (x1, y1, x2, y2) in source pixels per detected frame, None everywhere when no frame has a face: box `index` on
+    the first frame with faces, then the box whose centre is nearest to the last chosen one (ties: the lower index); a frame
+    without a face takes the nearest earlier chosen box, else the nearest later one."""
+    mult = 360.0 / H
+    boxes = [[(int(x1 / mult), int(y1 / mult), int(x2 / mult), int(y2 / mult)) for (x1, y1, x2, y2, sc) in (det or []) if sc > 0.95]
+             for det in rows]
+    chosen, prev = [], None
+    for bb in boxes:
+        if not bb:
+            chosen.append(prev)
+            continue
+        if prev is None:
+            if index > len(bb):
+                if logger is not None:
+                    logger.warning("Only %d detected, using the first one" % len(bb))
+                index = 1
+            prev = bb[index - 1]
+        else:  # doubled centres: integers
+            cx, cy = prev[0] + prev[2], prev[1] + prev[3]
+            prev = min(bb, key=lambda b: (b[0] + b[2] - cx) ** 2 + (b[1] + b[3] - cy) ** 2)
+        chosen.append(prev)
+    first = next((b for b in chosen if b is not None), None)
+    return None if first is None else [first if b is None else b for b in chosen]
+
+
+def driving_rects(rows, frames, T, H, W, margin=1.6, index=1, crop="fixed", smooth=25, logger=None):
+    """The crop windows of a driving video: T rects (x, y, w, h) in source coordinates, every one a square, from the detector's
+    rows on a few of its frames.  Host code, integers from the rows on.
+      rows: per detected frame what FaceDetectorHIP.detect_batch returns for its 360-px view, [[x1, y1, x2, y2, score], ...];
+      frames: the ascending frame indices the rows belong to (driving_detect_frames).  T, H, W: the clip.
+      Boxes with score > 0.95 are scaled by H / 360 as process_img scales them, and one is chosen per frame (_chosen_boxes).
+      Centre and half side of a box go by process_img's rule, with the half side clamped to at least 1 (_centre_half).
+      crop="fixed": ONE rect for the clip - process_img's rule (centre, half side int(max(bsy, bsx) * margin)) on the union of the
+        chosen boxes: the head's own translation stays inside the crop, which is what relative driving needs.
+      crop="track": a rect per frame - centre and half side by process_img's rule per detected frame, interpolated linearly
+        between detected frames (floor division), then a centred moving average over `smooth` frames (odd; the window is
+        clipped at the clip's ends, the sums are floor-divided by the frames in it).
+      crop=None: process_img's no-face branch, the centre square, with no rows read.
+    No face on any frame: the centre square for every frame and one logged warning."""
+    T, H, W = int(T), int(H), int(W)
+    if crop not in DRIVING_CROPS:
+        raise ValueError("driving_rects: crop must be 'fixed', 'track' or None (got %r)" % (crop,))
+    my, mx = H // 2, W // 2
+    bs = min(mx, my)
+    centre = [(mx - bs, my - bs, 2 * bs, 2 * bs)] * T
+    if crop is None:
+        return centre
+    frames = [int(f) for f in frames]
+    if len(frames) != len(rows) or not frames or frames != sorted(set(frames)) or frames[0] < 0 or frames[-1] >= T:
+        raise ValueError("driving_rects: frames must be %d ascending indices below %d, got %r" % (len(rows), T, frames))
+    chosen = _chosen_boxes(rows, H, int(index), logger)
+    if chosen is None:
+        if logger is not None:
+            logger.warning("Failed to detect any face in the driving video, no face align performed")
+        return centre
+    if crop == "fixed":
+        union = (min(b[0] for b in chosen), min(b[1] for b in chosen), max(b[2] for b in chosen), max(b[3] for b in chosen))
+        cx, cy, half = _centre_half(union, margin)
+        return [(cx - half, cy - half, 2 * half, 2 * half)] * T
+    smooth = int(smooth)
+    if smooth < 1 or smooth % 2 == 0:
+        raise ValueError("driving_rects: smooth (%d) must be odd and positive" % smooth)
+    keys = [_centre_half(b, margin) for b in chosen]
+    track, k = [], 0
+    for t in range(T):
+        while k + 1 < len(frames) and frames[k + 1] <= t:
+            k += 1
+        if t <= frames[k] or k + 1 == len(frames):
+            track.append(keys[k])
+        else:
+            ta, tb = frames[k], frames[k + 1]
+            track.append(tuple(va + ((vb - va) * (t - ta)) // (tb - ta) for va, vb in zip(keys[k], keys[k + 1])))
+    out = []
+    for t in range(T):
+        lo, hi = max(0, t - smooth // 2), min(T - 1, t + smooth // 2)
+        cx, cy, half = (sum(v[c] for v in track[lo:hi + 1]) // (hi - lo + 1) for c in range(3))
+        out.append((cx - half, cy - half, 2 * half, 2 * half))
+    return out
 
 
 _FA = None

@@ -104,6 +104,64 @@ def detector_view_device(img, view_h=360, rgba_conversion="blend_with_color", bk
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# a stack of frames, one window per frame (`float_img_front_frames`, include/float_hip.h): the driving video's front end
+# ---------------------------------------------------------------------------------------------------------------------------
+def frames_to_device(frames, device=None):
+    """A video - (T, H, W, 3|4), uint8 or any float dtype, host or device - as the contiguous uint8 or fp32 device tensor
+    `float_img_front_frames` reads; a tensor already in that form is returned as it is."""
+    if frames.dim() != 4 or frames.shape[-1] not in (3, 4) or 0 in frames.shape or not (frames.dtype == torch.uint8 or frames.is_floating_point()):
+        raise ValueError("frames front end: expected (T, H, W, 3|4) uint8 or float frames, got %s %s" % (frames.dtype, tuple(frames.shape)))
+    device = torch.device(device if device is not None else (frames.device if frames.is_cuda else "cuda:0"))
+    x = frames.detach().to(device, non_blocking=True)
+    if x.dtype != torch.uint8 and x.dtype != torch.float32:
+        x = x.float()
+    return x.contiguous()
+
+
+@torch.no_grad()
+def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with_color", bkg_color_hex="#000000", out=None, scale=None,
+                        device=None):
+    """float_img_front_frames: frames (T, H, W, 3|4), fp32 in [0, 1] or uint8, and one window per frame - rects, T rows (x0, y0, w,
+    h) in source coordinates (a single row serves every frame; a window may reach outside the image, where it is black) ->
+    (T, dst_h, dst_w, 3) uint8 on the device.  Frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(frames[t],
+    ...), rects[t], dst_h, dst_w, scale).  One fused kernel per 16 frames on the current stream of the frames' device; no scratch;
+    nothing synchronises.  out: a contiguous (T, dst_h, dst_w, 3) uint8 tensor on that device to write into."""
+    x = frames_to_device(frames, device)
+    T, H, W, ch = (int(v) for v in x.shape)
+    r = torch.as_tensor(rects, dtype=torch.int32, device="cpu").reshape(-1, 4)
+    if r.shape[0] == 1 and T > 1:
+        r = r.expand(T, 4)
+    if r.shape[0] != T:
+        raise ValueError("front_frames_device: %d rects for %d frames" % (r.shape[0], T))
+    r = r.contiguous()
+    sn, sd = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+    bkg = host_models.hex_to_rgb8(bkg_color_hex)
+    mode = _rgba_mode(rgba_conversion)
+    dst_h, dst_w = int(dst_h), int(dst_w)
+    shape = (T, dst_h, dst_w, 3)
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+            raise ValueError("front_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
+                             % (shape, x.device, out.dtype, tuple(out.shape), out.device))
+        native.check(native.lib().float_img_front_frames(
+            C.c_void_p(x.data_ptr()), T, H, W, ch, native.IMG_SRC_U8 if x.dtype == torch.uint8 else native.IMG_SRC_F32,
+            C.cast(r.data_ptr(), C.POINTER(C.c_int32)), sn, sd, mode, bkg[0], bkg[1], bkg[2], C.c_void_p(out.data_ptr()), dst_h, dst_w,
+            native.stream_ptr(x.device)))
+    return out
+
+
+def detector_views_device(frames, view_h=360, rgba_conversion="blend_with_color", bkg_color_hex="#000000", out=None, device=None):
+    """The detector's view of every frame in one call: (T, view_h, round(W view_h / H), 3) uint8 on the device; view t is bitwise
+    detector_view_device(frames[t], view_h, ...) - the whole image as every rect, both axes at the one scale H / view_h."""
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    vh, vw = detector_view_size(H, W, view_h)
+    g = math.gcd(H, vh)
+    return front_frames_device(frames, (0, 0, W, H), vh, vw, rgba_conversion, bkg_color_hex, out, (H // g, vh // g), device)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # the step after the decoder: the generated frames back in the source portrait (`float_img_paste`, include/float_hip.h)
 # ---------------------------------------------------------------------------------------------------------------------------
 JPEG_SIDE_MULTIPLE = 16  # float_jpg_encode codes frames whose sides are multiples of 16

@@ -12,7 +12,7 @@ from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
 from ...face import FaceDetectorHIP, find_sfd_weights, load_sfd_state
-from ...image import (detector_view_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
+from ...image import (detector_view_device, detector_views_device, front_frames_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
                       require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
@@ -577,6 +577,99 @@ class InferenceAgent:
         self.G.release_host_inflight()
         self.check_range("InferenceAgent.drive_device")
         return host
+
+    # ------------------------------------------------------------------ a raw driving video: crop every frame to the face
+    def _driving_rows(self, video, idx, rgba, bkg):
+        """The detector's rows on frames `idx` of the video, or None where FLOAT_AMD_FACE_DETECTOR leaves no detector (off, no
+        package and no weight file): the same choice as _found_faces.  The device detector sees the views of up to 16 frames
+        per pass (detector_views_device + detect_batch: one read-back per group); where the `face_alignment` package is the one
+        in use, and for frames of 360 rows or less (process_img_view's host resize), the views are made per image."""
+        mode = host_models.face_detector_mode()
+        if mode == "off":
+            return None
+        path, fa = self._sfd_path(), None
+        if mode in ("auto", "package"):
+            try:
+                fa = host_models._face_detector()
+            except Exception as e:  # noqa: BLE001
+                if path is None:
+                    main_logger.warning("align_driving: no face detector is available (%s: %s): the centre square of every frame is used.  %s"
+                                        % (type(e).__name__, e, host_models.SFD_WEIGHTS_HINT))
+                    return None
+        face = self._face_handle(path) if fa is None else None
+        rows = []
+        for at in range(0, len(idx), 16):
+            group = video[torch.as_tensor(idx[at:at + 16], device=video.device)]
+            if int(video.shape[1]) > 360:
+                views = detector_views_device(group, 360, rgba, bkg, device=self.rank)
+            else:
+                views = torch.stack([host_models.process_img_view(
+                    x[..., :3].float().cpu() if x.is_floating_point() and x.shape[-1] == 3 else
+                    host_models.image_to_rgb8(x, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0) for x in group])
+            if fa is not None:
+                v = views.cpu().numpy()
+                rows += [fa.face_detector.detect_from_image(v[i].copy()) for i in range(v.shape[0])]
+            else:
+                rows += face.detect_batch(views) if self._view_fits(face, views[0]) else [[] for _ in range(views.shape[0])]
+        return rows
+
+    @torch.no_grad()
+    def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32):
+        """A raw driving video -> the frames drive_device takes: video (T, H, W, 3|4), fp32 in [0, 1] or uint8, on the host or on
+        the device -> (frames_u8 (T, size, size, 3) uint8 on the device, rects = T tuples (x, y, w, h) in source coordinates).
+        Frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(video[t], ...), rects[t], size, size)
+        (float_img_front_frames; opt.rgba_conversion and opt.bkg_color_hex honoured).
+        rects: given (one rect, or one per frame), they are used as they are and no detector runs.  Otherwise
+        host_models.driving_rects decides from the detector's rows on frames 0, detect_every, 2 detect_every, ... and T - 1
+        (crop="fixed": one square for the clip around the union of the tracked face's boxes; "track": a smoothed square per
+        frame; None: the centre square, no detector pass).  detect_every=5 is a choice, not a measurement of this call: 20.5 ms per
+        16 views (README) makes every frame of a 10-s clip about 320 ms beside a 95-ms motion pass, every fifth about 64 ms.
+        A host video goes through `chunk` frames at a time over one reused device buffer, so the source's HBM is bounded by the
+        chunk whatever the clip's length; it crosses PCIe once, and the sampled frames once more when the detector runs."""
+        o = self.opt
+        size = int(o.input_size)
+        rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+        if video.dim() != 4 or video.shape[-1] not in (3, 4) or 0 in video.shape or not (video.dtype == torch.uint8 or video.is_floating_point()):
+            raise ValueError("align_driving: video must be (T, H, W, 3|4) uint8 or float, got %s %s" % (video.dtype, tuple(video.shape)))
+        T, H, Wd, ch = (int(v) for v in video.shape)
+        chunk = max(1, int(chunk))
+        self.to_target()
+        if rects is not None:
+            r = torch.as_tensor(rects, dtype=torch.int64).reshape(-1, 4)
+            if r.shape[0] not in (1, T):
+                raise ValueError("align_driving: %d rects for %d frames" % (r.shape[0], T))
+            rects = [tuple(int(v) for v in row) for row in r.expand(T, 4).tolist()]
+        else:
+            idx = host_models.driving_detect_frames(T, detect_every) if crop is not None else []
+            rows = self._driving_rows(video, idx, rgba, bkg) if idx else None
+            rects = host_models.driving_rects(rows, idx, T, H, Wd, float(margin if margin is not None else getattr(o, "face_margin", 1.6)),
+                                              index, None if rows is None else crop, smooth, main_logger)
+            rects = [tuple(int(v) for v in row) for row in rects]
+        out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=self.rank)
+        buf = None
+        for at in range(0, T, chunk):
+            part = video[at:at + chunk]
+            if not part.is_cuda:  # one device buffer for the whole clip; copies and kernels are ordered by the stream
+                if part.dtype not in (torch.uint8, torch.float32):
+                    part = part.float()
+                if buf is None:
+                    buf = torch.empty((min(chunk, T), H, Wd, ch), dtype=part.dtype, device=self.rank)
+                part = buf[:part.shape[0]].copy_(part, non_blocking=True)
+            front_frames_device(part, rects[at:at + chunk], size, size, rgba, bkg, out=out[at:at + chunk])
+        return out, rects
+
+    @torch.no_grad()
+    def drive_video(self, ref_img, video, mode="relative", no_crop=True, crop="fixed", detect_every=5, smooth=25, margin=None, index=1,
+                    rects=None, chunk=32, out=None, out_dtype=None, out_format=None, matrix=None):
+        """drive_device from raw inputs: the portrait ref_img (a ComfyUI IMAGE item) goes through host_inputs' image half
+        (no_crop as there), the raw driving video through align_driving (crop ... chunk as there), and the two through
+        drive_device (mode, out, out_dtype, out_format, matrix as there).  With rects= given it is bit for bit drive_device on
+        the definition's crops of the video."""
+        self._crop_matrix("drive_video", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
+        silence = {"waveform": torch.zeros(1, 1, 16), "sample_rate": self.opt.sampling_rate}  # _host_inputs' audio half: unused
+        s = self._host_inputs(ref_img, silence, no_crop, False)[0]
+        frames_u8, _ = self.align_driving(video, crop, detect_every, smooth, margin, index, rects, chunk)
+        return self.drive_device(s, frames_u8, mode, out, out_dtype, out_format, matrix)
 
     def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,
                       out_format=None, slots=3, matrix=None):

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
+/* Stays 6: float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
  * Lanczos resampling of 8-bit frames on the device), float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
@@ -638,6 +638,27 @@ size_t float_img_front_work_bytes(int32_t src_h, int32_t src_w, int32_t dst_h, i
 int float_img_front(const float* img, int32_t src_h, int32_t src_w, int32_t channels, int32_t rect_x, int32_t rect_y, int32_t rect_w,
                     int32_t rect_h, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g, int32_t bkg_b,
                     int32_t out_mode, void* out, int32_t dst_h, int32_t dst_w, void* work, size_t work_bytes, void* stream);
+
+/* The same front end over a stack of frames, one window PER FRAME, in one pass: what turns a raw driving video into the
+ * (n_frames, dst_h, dst_w, 3) uint8 stack that float_enc_motion and float_sfd_*_batch read.
+ *   frames: (n_frames, src_h, src_w, channels) contiguous in HBM.  src_type FLOAT_IMG_SRC_F32: fp32, quantised as above;
+ *     FLOAT_IMG_SRC_U8: bytes that are q already (no quantiser; NOT defined through x / 255 * 255).  The RGBA conversion runs on
+ *     the quantised values, so it is one arithmetic for both types.
+ *   rects: a HOST array (n_frames, 4) int32, rows rect_x, rect_y, rect_w, rect_h in source coordinates, read before the call
+ *     returns.  A window may reach outside the image (zero border) or miss it (a black frame).
+ *   scale_num / scale_den: as above - 0, 0: frame t is resized at rect_w[t] / dst_w by rect_h[t] / dst_h.
+ *   out: (n_frames, dst_h, dst_w, 3) uint8; frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(frame t, ...),
+ *     rects[t], dst_h, dst_w, scale), and bitwise float_img_front in FLOAT_IMG_OUT_HWC_U8 mode on that frame.
+ *   Limits as above per frame, 1 <= n_frames <= 65535; fp32 frames 16-byte aligned for 4 channels and 4-byte for 3, 8-bit frames
+ *   4-byte aligned for 4 channels and unaligned for 3.  Every rect is checked on the host before any HIP call: FLOAT_E_INVALID,
+ *   with a message naming the frame, and nothing is launched.
+ * One fused kernel per block of 16 frames (their rects travel in the kernel arguments): no scratch of any kind, the row sums stay
+ * in registers; every source pixel of a window is read from HBM once per 64-column tile, pixels outside the image never.  No
+ * atomics, two calls give equal bytes; allocates nothing, synchronises nothing; kernel launches only (no test captures it). */
+enum { FLOAT_IMG_SRC_F32 = 0, FLOAT_IMG_SRC_U8 = 1 };
+int float_img_front_frames(const void* frames, int32_t n_frames, int32_t src_h, int32_t src_w, int32_t channels, int32_t src_type,
+                           const int32_t* rects, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g,
+                           int32_t bkg_b, uint8_t* out, int32_t dst_h, int32_t dst_w, void* stream);
 
 /* ---------------------------------------------------------------- paste back -- */
 /* The step after the decoder: n_frames generated 8-bit frames (n_frames, fr_h, fr_w, 3) - the buffer float_dec_frames_u8 writes -
