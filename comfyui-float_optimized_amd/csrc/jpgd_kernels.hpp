@@ -1,0 +1,198 @@
+// Kernels of float_jpg_decode: baseline JPEG files in HBM -> 8-bit RGB frames, bitwise host_models.jpeg_decode_rgb8.  Four
+// launches per group of frames, all reading the DEVICE plan (jpgd_rule.hpp has its layout and the arithmetic):
+//   jpgd_scan_kernel     one workgroup per frame walks the scan bytes, a byte pair per lane, and compacts the RSTn positions in
+//                        order (wave ballot + prefix count) into the frame's interval table; writes the frame's status word.
+//   jpgd_entropy_kernel  one restart interval per lane; the frame's table set sits in LDS once per workgroup, a lane gathers a
+//                        block in an LDS row of its own (33 dwords apart: lanes fall into different banks) and hands it to the
+//                        coefficient buffer as eight 16-byte stores.
+//   jpgd_idct_kernel     32 blocks per workgroup: coefficients into LDS by 16-byte loads, pass 1 down the columns (dequantising),
+//                        the block transposed through LDS, pass 2 along the rows, 8 samples per lane as one 8-byte store.
+//   jpgd_rgb_kernel      4 pixels per lane: fancy upsampling from the chroma planes, colour conversion, one 12-byte store.
+#pragma once
+#include "common.hpp"
+#include "jpgd_rule.hpp"
+
+constexpr int kJpgdScanThreads = 256, kJpgdLanes = 64, kJpgdIdctBlocks = 32, kJpgdRgbThreads = 64;
+constexpr int kJpgdRowDwords = 33;   // a lane's block in the entropy kernel: 32 dwords + 1, so that lane l starts in bank l
+constexpr int kJpgdCoefDwords = 36;  // a block's coefficients in the IDCT kernel: 32 dwords + 4 (16-byte aligned, 8 blocks of a wave in 8 bank groups)
+constexpr int kJpgdWsRow = 9, kJpgdWsBlock = 72;  // pass 1's result: rows 8 + 1 dwords apart, blocks 72
+
+struct JpgdLaunch {  // what the host read from its copy of the plan
+  int frame0, frames;  // the group
+  unsigned long long seg, coef, plane[3], frame;  // byte offsets inside a frame's share of `work`, and its size
+  int pw, cw;          // row strides of the luma and chroma planes
+  long long nblocks;
+};
+
+// LDS words that are written as one type and read as another (a block's int16 coefficients, moved as dwords)
+typedef int __attribute__((may_alias)) jpgd_word;
+typedef short __attribute__((may_alias)) jpgd_half;
+typedef unsigned short __attribute__((may_alias)) jpgd_uhalf;
+
+__device__ __forceinline__ const int* jpgd_frame(const int* plan, int f) { return plan + plan[JPGD_P_FRAMES] + f * JPGD_F_INTS; }
+
+__global__ __launch_bounds__(kJpgdScanThreads) void jpgd_scan_kernel(const uint8_t* __restrict__ files, const long long* __restrict__ offsets,
+                                                                    const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work,
+                                                                    int* __restrict__ status) {
+  __shared__ int wave_cnt[kJpgdScanThreads / 64];
+  const int f = L.frame0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* fr = jpgd_frame(plan, f);
+  const uint8_t* file = files + offsets[f];
+  const int s0 = fr[JPGD_F_SCAN0], s1 = fr[JPGD_F_SCAN1], n_int = fr[JPGD_F_NINT];
+  int* seg = (int*)(work + (size_t)blockIdx.x * L.frame + L.seg);
+  int total = 0;  // markers so far, the same in every lane
+  for (int base = s0; base < s1; base += kJpgdScanThreads) {
+    const int p = base + tid;
+    const bool mark = p + 1 < s1 && file[p] == 0xFF && (file[p + 1] & 0xF8) == 0xD0;
+    const unsigned long long vote = __ballot(mark);
+    if (lane == 0) wave_cnt[wave] = __popcll(vote);
+    __syncthreads();
+    int before = total, all = 0;
+#pragma unroll
+    for (int w = 0; w < kJpgdScanThreads / 64; ++w) {
+      const int c = wave_cnt[w];
+      before += w < wave ? c : 0;
+      all += c;
+    }
+    if (mark) {
+      const int k = before + __popcll(vote & ((1ull << lane) - 1ull));  // this marker's number: it ends interval k, interval k + 1 follows
+      if (k < n_int) seg[2 * k + 1] = p;
+      if (k + 1 < n_int) seg[2 * k + 2] = p + 2;
+    }
+    total += all;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    seg[0] = s0;
+    if (total < n_int) seg[2 * total + 1] = s1;
+    status[f] = total == n_int - 1 ? 0 : JPGD_ST_RESTARTS;
+  }
+  for (int k = total + 1 + tid; k < n_int; k += kJpgdScanThreads) seg[2 * k] = -1, seg[2 * k + 1] = -1;  // no segment: an all-zero interval
+}
+
+__global__ __launch_bounds__(kJpgdLanes) void jpgd_entropy_kernel(const uint8_t* __restrict__ files, const long long* __restrict__ offsets,
+                                                                 const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work,
+                                                                 int* __restrict__ status) {
+  __shared__ int set[kJpgdSetInts];
+  __shared__ jpgd_word rows[kJpgdLanes * kJpgdRowDwords];
+  const int f = L.frame0 + blockIdx.y, lane = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  for (int i = lane; i < kJpgdSetInts; i += kJpgdLanes) set[i] = gset[i];
+  __syncthreads();
+  const int iv = blockIdx.x * kJpgdLanes + lane, n_int = fr[JPGD_F_NINT];
+  if (iv >= n_int) return;
+  uint8_t* mine = work + (size_t)blockIdx.y * L.frame;
+  const int* seg = (const int*)(mine + L.seg);
+  int16_t* coef = (int16_t*)(mine + L.coef);
+  const int hv = plan[JPGD_P_HS] * plan[JPGD_P_VS], bpm = plan[JPGD_P_BPM], span = fr[JPGD_F_SPAN];
+  const int nmcu = plan[JPGD_P_MCUX] * plan[JPGD_P_MCUY], m1 = min((iv + 1) * span, nmcu);
+  const uint8_t* file = files + offsets[f];
+  const int b0 = seg[2 * iv], b1 = seg[2 * iv + 1];
+  jpgd_word* row = rows + lane * kJpgdRowDwords;
+  JpgdBits b;
+  jpgd_bits_open(b, file + max(b0, 0), file + max(b1, 0));
+  bool ok = b0 >= 0;
+  int st = 0;
+  int32_t pred[3] = {0, 0, 0};
+  for (int m = iv * span; m < m1; ++m)
+    for (int j = 0; j < bpm; ++j) {
+      const int c = j < hv ? 0 : j - hv + 1;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) row[i] = 0;
+      if (ok) {
+        int32_t& pr = c == 0 ? pred[0] : c == 1 ? pred[1] : pred[2];
+        ok = jpgd_block(b, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pr, (jpgd_half*)row);
+        if (!ok) {
+          st |= JPGD_ST_BAD_CODE;
+#pragma unroll
+          for (int i = 0; i < 32; ++i) row[i] = 0;
+        }
+      }
+      uint4* dst = (uint4*)(coef + ((size_t)m * bpm + j) * 64);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) dst[i] = uint4{(unsigned)row[4 * i], (unsigned)row[4 * i + 1], (unsigned)row[4 * i + 2], (unsigned)row[4 * i + 3]};
+    }
+  if (b0 >= 0 && jpgd_past_end(b)) st |= JPGD_ST_PAST_END;
+  if (st) atomicOr(status + f, st);
+}
+
+__global__ __launch_bounds__(kJpgdIdctBlocks * 8) void jpgd_idct_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {
+  __shared__ __attribute__((aligned(16))) jpgd_word cf[kJpgdIdctBlocks * kJpgdCoefDwords];
+  __shared__ int ws[kJpgdIdctBlocks * kJpgdWsBlock];
+  __shared__ jpgd_word qt[3 * 32];  // three tables of 64 uint16
+  const int f = L.frame0 + blockIdx.y, tid = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  if (tid < 96) qt[tid] = gset[tid];
+  uint8_t* mine = work + (size_t)blockIdx.y * L.frame;
+  const long long g0 = (long long)blockIdx.x * kJpgdIdctBlocks;
+  {  // 256 lanes x 16 bytes = the 32 blocks; a block past the end reads as zeros
+    const int blk = tid >> 3, part = tid & 7;
+    uint4 v = uint4{0u, 0u, 0u, 0u};
+    if (g0 + blk < L.nblocks) v = *(const uint4*)(mine + L.coef + (size_t)(g0 + blk) * 128 + part * 16);
+    jpgd_word* d = cf + blk * kJpgdCoefDwords + part * 4;
+    d[0] = (int)v.x, d[1] = (int)v.y, d[2] = (int)v.z, d[3] = (int)v.w;
+  }
+  __syncthreads();
+  const int blk = tid >> 3, k = tid & 7;
+  const long long g = g0 + blk;
+  const int hs = plan[JPGD_P_HS], hv = hs * plan[JPGD_P_VS], bpm = plan[JPGD_P_BPM], mcux = plan[JPGD_P_MCUX];
+  const int m = (int)(g / bpm), j = (int)(g - (long long)m * bpm);
+  const int c = j < hv ? 0 : j - hv + 1;
+  {  // pass 1: column k
+    const jpgd_half* src = (const jpgd_half*)(cf + blk * kJpgdCoefDwords);
+    const jpgd_uhalf* q = (const jpgd_uhalf*)qt + c * 64;
+    int32_t v[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = jpgd_mul(src[r * 8 + k], q[r * 8 + k]);
+    jpgd_idct8<11>(v);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) ws[blk * kJpgdWsBlock + r * kJpgdWsRow + k] = v[r];
+  }
+  __syncthreads();
+  if (g >= L.nblocks) return;
+  int32_t v[8];  // pass 2: row k
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = ws[blk * kJpgdWsBlock + k * kJpgdWsRow + i];
+  jpgd_idct8<18>(v);
+  const int my = m / mcux, mx = m - my * mcux;
+  const int by = c ? my : my * plan[JPGD_P_VS] + j / hs, bx = c ? mx : mx * hs + j % hs, stride = c ? L.cw : L.pw;
+  uint2 o;
+  o.x = jpgd_sample(v[0]) | (jpgd_sample(v[1]) << 8) | (jpgd_sample(v[2]) << 16) | ((unsigned)jpgd_sample(v[3]) << 24);
+  o.y = jpgd_sample(v[4]) | (jpgd_sample(v[5]) << 8) | (jpgd_sample(v[6]) << 16) | ((unsigned)jpgd_sample(v[7]) << 24);
+  *(uint2*)(mine + L.plane[c] + (size_t)(by * 8 + k) * stride + bx * 8) = o;
+}
+
+struct jpgd_u3 {  // 12 bytes at a 4-byte boundary
+  unsigned x, y, z;
+};
+__global__ __launch_bounds__(kJpgdRgbThreads) void jpgd_rgb_kernel(const int* __restrict__ plan, JpgdLaunch L, const uint8_t* __restrict__ work,
+                                                                  uint8_t* __restrict__ rgb) {
+  const int H = plan[JPGD_P_H], W = plan[JPGD_P_W], nc = plan[JPGD_P_NCOMP], hs = plan[JPGD_P_HS], vs = plan[JPGD_P_VS];
+  const int x0 = (blockIdx.x * kJpgdRgbThreads + threadIdx.x) * 4, y = blockIdx.y;
+  if (x0 >= W) return;
+  const uint8_t* mine = work + (size_t)blockIdx.z * L.frame;
+  const uint8_t* yp = mine + L.plane[0];
+  const uint8_t *cbp = mine + L.plane[1], *crp = mine + L.plane[2];
+  const int cw = (W + hs - 1) / hs, ch = (H + vs - 1) / vs;
+  const unsigned y4 = *(const unsigned*)(yp + (size_t)y * L.pw + x0);  // the plane's rows are whole blocks: x0 + 3 < pw
+  uint8_t px[12];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int Y = (y4 >> (8 * i)) & 255, x = min(x0 + i, W - 1);
+    if (nc == 1) px[3 * i] = px[3 * i + 1] = px[3 * i + 2] = (uint8_t)Y;
+    else jpgd_rgb(Y, jpgd_chroma(cbp, L.cw, cw, ch, hs, vs, x, y), jpgd_chroma(crp, L.cw, cw, ch, hs, vs, x, y), px + 3 * i);
+  }
+  uint8_t* o = rgb + (((size_t)(L.frame0 + blockIdx.z) * H + y) * W + x0) * 3;
+  if (x0 + 4 <= W && ((uintptr_t)o & 3u) == 0) {
+    jpgd_u3 v;
+    v.x = px[0] | (px[1] << 8) | (px[2] << 16) | ((unsigned)px[3] << 24);
+    v.y = px[4] | (px[5] << 8) | (px[6] << 16) | ((unsigned)px[7] << 24);
+    v.z = px[8] | (px[9] << 8) | (px[10] << 16) | ((unsigned)px[11] << 24);
+    *(jpgd_u3*)o = v;
+  } else {
+    const int n = min(4, W - x0) * 3;
+    for (int i = 0; i < n; ++i) o[i] = px[i];
+  }
+}

@@ -1,0 +1,187 @@
+// The JPEG decoder's rule as host-and-device inline code, shared by its kernels (jpgd_kernels.hpp) and by the host path
+// (jpgd_plan.hpp: float_jpg_decode_host and the stand-alone tools/probes/jpgd_host.cpp): the plan's layout, the bit reader, the
+// Huffman symbol decode, one block's coefficients, the two IDCT passes, chroma upsampling and the colour conversion.  The rule
+// itself is written out in host_models.jpeg_decode_rgb8.  Plain C++ plus stdint: a host compiler without HIP takes it as it is.
+// All arithmetic is int32 with wrap-around, spelled in uint32_t where a signed overflow or a shift of a negative could occur.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define JPGD_HD __host__ __device__ __forceinline__
+#else
+#define JPGD_HD inline
+#endif
+
+// ---------------------------------------------------------------- the plan: int32 words
+// header, then one frame record per frame, then the distinct table sets
+enum {
+  JPGD_P_MAGIC = 0,  // kJpgdMagic
+  JPGD_P_INTS,       // words in use
+  JPGD_P_N,          // frames
+  JPGD_P_H,
+  JPGD_P_W,
+  JPGD_P_NCOMP,  // 1 or 3
+  JPGD_P_HS,     // luma sampling: 1 | 2
+  JPGD_P_VS,
+  JPGD_P_MCUX,  // MCUs per row, rows of MCUs
+  JPGD_P_MCUY,
+  JPGD_P_BPM,      // blocks per MCU
+  JPGD_P_NSETS,    // distinct table sets
+  JPGD_P_MAXINT,   // the most intervals of a frame
+  JPGD_P_GROUP,    // frames that share `work`
+  JPGD_P_FRAMES,   // word index of frame record 0
+  JPGD_P_SETS,     // word index of table set 0
+  JPGD_P_HEADER = 16
+};
+enum { JPGD_F_SCAN0 = 0, JPGD_F_SCAN1, JPGD_F_SPAN, JPGD_F_NINT, JPGD_F_SET, JPGD_F_INTS = 8 };  // scan bytes [SCAN0, SCAN1) of the file; MCUs per interval
+constexpr int32_t kJpgdMagic = 0x4A504744;
+// a Huffman table: look[512] uint16 (length << 8 | symbol of every 9-bit prefix, 0: longer or none), maxcode[18], valoff[18], vals[256] uint8
+constexpr int kJpgdHuffLook = 0, kJpgdHuffMax = 256, kJpgdHuffOff = 274, kJpgdHuffVals = 292, kJpgdHuffInts = 356;
+// a table set: per component c the quantiser (64 uint16, natural order) at 32 c, then the tables DC c, AC c at kJpgdSetHuff + (2 c + class) kJpgdHuffInts
+constexpr int kJpgdSetHuff = 96, kJpgdSetInts = kJpgdSetHuff + 6 * kJpgdHuffInts;
+constexpr int JPGD_ST_BAD_CODE = 1, JPGD_ST_RESTARTS = 2, JPGD_ST_PAST_END = 4;  // the bits of a frame's status word
+
+struct JpgdHuff {
+  const uint16_t* look;
+  const int32_t* maxcode;
+  const int32_t* valoff;
+  const uint8_t* vals;
+};
+JPGD_HD JpgdHuff jpgd_huff(const int32_t* set, int comp, int cls) {
+  const int32_t* t = set + kJpgdSetHuff + (2 * comp + cls) * kJpgdHuffInts;
+  return JpgdHuff{(const uint16_t*)(t + kJpgdHuffLook), t + kJpgdHuffMax, t + kJpgdHuffOff, (const uint8_t*)(t + kJpgdHuffVals)};
+}
+
+JPGD_HD int jpgd_natural(int k) {  // zigzag position -> row-major index
+  constexpr uint8_t z[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+  return z[k];
+}
+
+// ---------------------------------------------------------------- bit reader over bytes [p, end): unstuffs 0xFF 0x00, zeros past the end
+struct JpgdBits {
+  const uint8_t* p;
+  const uint8_t* end;
+  uint64_t acc;   // the low n bits are unread
+  int n;
+  uint32_t over;  // zero bytes supplied past the end
+};
+JPGD_HD void jpgd_bits_open(JpgdBits& b, const uint8_t* p, const uint8_t* end) { b.p = p, b.end = end, b.acc = 0, b.n = 0, b.over = 0; }
+JPGD_HD void jpgd_fill(JpgdBits& b) {  // at least 57 unread bits afterwards
+  while (b.n <= 56) {
+    uint32_t v = 0;
+    if (b.p < b.end) {
+      v = *b.p++;
+      if (v == 0xFF && b.p < b.end && *b.p == 0) ++b.p;
+    } else {
+      ++b.over;
+    }
+    b.acc = (b.acc << 8) | v;
+    b.n += 8;
+  }
+}
+JPGD_HD uint32_t jpgd_peek(const JpgdBits& b, int k) { return (uint32_t)(b.acc >> (b.n - k)) & ((1u << k) - 1u); }  // 1 <= k <= 16 <= n
+JPGD_HD bool jpgd_past_end(const JpgdBits& b) { return (uint64_t)b.over * 8 > (uint64_t)b.n; }  // a supplied zero bit was consumed
+
+// one symbol (needs 16 unread bits); -1 for a code that matches none
+JPGD_HD int jpgd_symbol(JpgdBits& b, const JpgdHuff& t) {
+  const uint32_t e = t.look[jpgd_peek(b, 9)];
+  if (e) {
+    b.n -= (int)(e >> 8);
+    return (int)(e & 255);
+  }
+  int l = 10;
+  while (l <= 16 && (int32_t)jpgd_peek(b, l) > t.maxcode[l]) ++l;
+  if (l > 16) return -1;
+  const int sym = t.vals[((int32_t)jpgd_peek(b, l) + t.valoff[l]) & 255];
+  b.n -= l;
+  return sym;
+}
+// s more bits (s <= 15, after jpgd_symbol's 16 of one fill) as the signed value of category s
+JPGD_HD int32_t jpgd_extend(JpgdBits& b, int s) {
+  if (s == 0) return 0;
+  const int32_t r = (int32_t)jpgd_peek(b, s);
+  b.n -= s;
+  return r >= (1 << (s - 1)) ? r : r - (1 << s) + 1;
+}
+
+// One block: 64 coefficients in natural order into coef[0 ... 63] (zeroed by the caller), NOT dequantised - a 16-bit table entry
+// times a coefficient needs the int32 the IDCT multiplies in.  false: a bad code or an overflowing run.
+template <class P>
+JPGD_HD bool jpgd_block(JpgdBits& b, const JpgdHuff& dc, const JpgdHuff& ac, int32_t& pred, P coef) {
+  jpgd_fill(b);
+  int s = jpgd_symbol(b, dc);
+  if (s < 0) return false;
+  pred = (int32_t)((uint32_t)pred + (uint32_t)jpgd_extend(b, s & 15));
+  coef[0] = (int16_t)(uint16_t)((uint32_t)pred & 0xFFFFu);
+  for (int k = 1; k < 64;) {
+    jpgd_fill(b);
+    const int rs = jpgd_symbol(b, ac);
+    if (rs < 0) return false;
+    const int r = rs >> 4;
+    s = rs & 15;
+    if (s == 0) {
+      if (r != 15) break;
+      if (k + 16 > 64) return false;
+      k += 16;
+      continue;
+    }
+    k += r;
+    if (k > 63) return false;
+    coef[jpgd_natural(k)] = (int16_t)jpgd_extend(b, s);
+    ++k;
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------- jidctint.c ("islow"): one 8-point pass
+JPGD_HD int32_t jpgd_mul(int32_t a, int32_t c) { return (int32_t)((uint32_t)a * (uint32_t)c); }
+JPGD_HD int32_t jpgd_add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+JPGD_HD int32_t jpgd_sub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
+JPGD_HD int32_t jpgd_shl13(int32_t a) { return (int32_t)((uint32_t)a << 13); }
+// v[0 ... 7] in place; SHIFT 11 for pass 1 (down a column of dequantised coefficients), 18 for pass 2 (along a row of pass 1)
+template <int SHIFT>
+JPGD_HD void jpgd_idct8(int32_t* v) {
+  const int32_t i0 = v[0], i1 = v[1], i2 = v[2], i3 = v[3], i4 = v[4], i5 = v[5], i6 = v[6], i7 = v[7];
+  int32_t z1 = jpgd_mul(jpgd_add(i2, i6), 4433);
+  int32_t t2 = jpgd_add(z1, jpgd_mul(i6, -15137));
+  int32_t t3 = jpgd_add(z1, jpgd_mul(i2, 6270));
+  int32_t t0 = jpgd_shl13(jpgd_add(i0, i4));
+  int32_t t1 = jpgd_shl13(jpgd_sub(i0, i4));
+  const int32_t t10 = jpgd_add(t0, t3), t13 = jpgd_sub(t0, t3), t11 = jpgd_add(t1, t2), t12 = jpgd_sub(t1, t2);
+  z1 = jpgd_add(i7, i1);
+  int32_t z2 = jpgd_add(i5, i3), z3 = jpgd_add(i7, i3), z4 = jpgd_add(i5, i1);
+  const int32_t z5 = jpgd_mul(jpgd_add(z3, z4), 9633);
+  t0 = jpgd_mul(i7, 2446), t1 = jpgd_mul(i5, 16819), t2 = jpgd_mul(i3, 25172), t3 = jpgd_mul(i1, 12299);
+  z1 = jpgd_mul(z1, -7373), z2 = jpgd_mul(z2, -20995);
+  z3 = jpgd_add(jpgd_mul(z3, -16069), z5), z4 = jpgd_add(jpgd_mul(z4, -3196), z5);
+  t0 = jpgd_add(t0, jpgd_add(z1, z3)), t1 = jpgd_add(t1, jpgd_add(z2, z4));
+  t2 = jpgd_add(t2, jpgd_add(z2, z3)), t3 = jpgd_add(t3, jpgd_add(z1, z4));
+  constexpr int32_t rnd = 1 << (SHIFT - 1);
+  v[0] = jpgd_add(jpgd_add(t10, t3), rnd) >> SHIFT, v[7] = jpgd_add(jpgd_sub(t10, t3), rnd) >> SHIFT;
+  v[1] = jpgd_add(jpgd_add(t11, t2), rnd) >> SHIFT, v[6] = jpgd_add(jpgd_sub(t11, t2), rnd) >> SHIFT;
+  v[2] = jpgd_add(jpgd_add(t12, t1), rnd) >> SHIFT, v[5] = jpgd_add(jpgd_sub(t12, t1), rnd) >> SHIFT;
+  v[3] = jpgd_add(jpgd_add(t13, t0), rnd) >> SHIFT, v[4] = jpgd_add(jpgd_sub(t13, t0), rnd) >> SHIFT;
+}
+JPGD_HD int32_t jpgd_clamp8(int32_t v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+JPGD_HD uint8_t jpgd_sample(int32_t pass2) { return (uint8_t)jpgd_clamp8(jpgd_add(pass2, 128)); }  // range limit around +128
+
+// ---------------------------------------------------------------- chroma at full resolution and the colour conversion
+// The planes hold whole blocks; (cw, ch) is the chroma plane's true size, which neighbours are clamped to.  hs, vs: 1 | 2.
+JPGD_HD int32_t jpgd_chroma(const uint8_t* plane, int stride, int cw, int ch, int hs, int vs, int x, int y) {
+  const int cy = vs == 2 ? y >> 1 : y, cx = hs == 2 ? x >> 1 : x;
+  const uint8_t* row = plane + (size_t)cy * stride;
+  if (hs == 1 || cw <= 2) return row[cx];  // replication (vs == 2 comes with hs == 2 only)
+  const int nx = (x & 1) ? (cx + 1 < cw ? cx + 1 : cw - 1) : (cx > 0 ? cx - 1 : 0);
+  if (vs == 1) return (3 * row[cx] + row[nx] + ((x & 1) ? 2 : 1)) >> 2;
+  const int ny = (y & 1) ? (cy + 1 < ch ? cy + 1 : ch - 1) : (cy > 0 ? cy - 1 : 0);
+  const uint8_t* far = plane + (size_t)ny * stride;
+  const int32_t s_this = 3 * row[cx] + far[cx], s_next = 3 * row[nx] + far[nx];
+  return (3 * s_this + s_next + ((x & 1) ? 7 : 8)) >> 4;
+}
+JPGD_HD void jpgd_rgb(int32_t y, int32_t cb, int32_t cr, uint8_t* rgb) {
+  cb -= 128, cr -= 128;
+  rgb[0] = (uint8_t)jpgd_clamp8(y + ((91881 * cr + 32768) >> 16));
+  rgb[1] = (uint8_t)jpgd_clamp8(y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+  rgb[2] = (uint8_t)jpgd_clamp8(y + ((116130 * cb + 32768) >> 16));
+}

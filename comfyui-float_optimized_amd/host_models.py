@@ -1517,6 +1517,529 @@ class AviMjpegWriter:
         return False
 
 
+class AviMjpegReader:
+    """The reading half of AviMjpegWriter: a Motion-JPEG clip in an AVI container -> its JPEG files, for jpeg.decode_jpeg_device
+    and InferenceAgent.align_driving.  Reads what AviMjpegWriter writes and plain ffmpeg-style MJPEG AVIs (`-c:v mjpeg`): RIFF
+    `AVI `, `hdrl` with `avih` and one `strl` per stream, `movi` with `NNdc` / `NNdb` chunks of the video stream (also inside
+    `rec ` lists) and `NNwb` chunks of a 16-bit PCM stream; `idx1` is used where present (offsets from the `movi` fourcc or from the
+    start of the file, whichever points at the chunks), otherwise `movi` is walked.  OpenDML (`AVIX`) extensions are not followed.
+      width, height, fps (a Fraction: dwRate / dwScale), len(reader) frames;
+      audio_rate, audio_channels, audio_pcm ((samples, channels) int16 numpy array) - None without a PCM stream;
+      read(first=0, count=None) -> jpeg.JpegFrames of those frames (pinned host memory where a GPU is present);
+      chunks(n) yields read() in pieces of n frames; iterating yields one memoryview-able `bytes` per frame.
+    A frame without a DHT segment gets the Annex K.3 tables in front of its SOS, as the Motion-JPEG convention has it.
+    path_or_file: a path (opened here, closed by close()), or a seekable binary file object, left open."""
+
+    def __init__(self, path_or_file):
+        import struct
+        self._own = not hasattr(path_or_file, "read")
+        self._f = f = open(path_or_file, "rb") if self._own else path_or_file
+        try:
+            base = f.tell()
+            head = f.read(12)
+            if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+                raise ValueError("AviMjpegReader: not a RIFF AVI file")
+            end = base + 8 + struct.unpack("<I", head[4:8])[0]
+            self.width = self.height = 0
+            self.fps, self.audio_rate, self.audio_channels = None, None, None
+            self._video_id, self._audio_id, movi, index = None, None, None, None
+            pos = base + 12
+            while pos + 8 <= end:
+                f.seek(pos)
+                hd = f.read(8)
+                if len(hd) < 8:
+                    break
+                cc, n = hd[:4], struct.unpack("<I", hd[4:])[0]
+                if cc == b"LIST":
+                    kind = f.read(4)
+                    if kind == b"hdrl":
+                        self._headers(f.read(n - 4))
+                    elif kind == b"movi":
+                        movi = (pos + 8, pos + 8 + n)  # from the fourcc to the end of the list
+                elif cc == b"idx1":
+                    index = f.read(n)
+                pos += 8 + n + (n & 1)
+            if movi is None or self._video_id is None:
+                raise ValueError("AviMjpegReader: no `movi` list or no MJPG video stream")
+            self._chunks, self._audio = self._locate(movi, index)
+        except BaseException:
+            self.close()
+            raise
+
+    def _headers(self, hdrl):
+        import struct
+        from fractions import Fraction
+        pos, stream = 0, 0
+        while pos + 8 <= len(hdrl):
+            cc, n = hdrl[pos:pos + 4], struct.unpack("<I", hdrl[pos + 4:pos + 8])[0]
+            if cc == b"LIST" and hdrl[pos + 8:pos + 12] == b"strl":
+                body, at, kind = hdrl[pos + 12:pos + 8 + n], 0, None
+                while at + 8 <= len(body):
+                    c2, n2 = body[at:at + 4], struct.unpack("<I", body[at + 4:at + 8])[0]
+                    d = body[at + 8:at + 8 + n2]
+                    if c2 == b"strh" and n2 >= 28:
+                        kind, handler = d[:4], d[4:8]
+                        scale, rate = struct.unpack("<II", d[20:28])
+                        if kind == b"vids" and self._video_id is None:
+                            if handler.upper() not in (b"MJPG", b"\0\0\0\0"):
+                                raise ValueError("AviMjpegReader: the video stream is %r, not MJPG" % handler)
+                            self._video_id = b"%02d" % stream
+                            self.fps = Fraction(rate, max(1, scale))
+                    elif c2 == b"strf" and kind == b"vids" and n2 >= 20 and self._video_id == b"%02d" % stream:
+                        self.width, self.height = struct.unpack("<ii", d[4:12])
+                        self.height = abs(self.height)
+                        if d[16:20].upper() != b"MJPG":
+                            raise ValueError("AviMjpegReader: the video stream's compression is %r, not MJPG" % d[16:20])
+                    elif c2 == b"strf" and kind == b"auds" and n2 >= 16 and self._audio_id is None:
+                        tag, ch, rate, _, _, bits = struct.unpack("<HHIIHH", d[:16])
+                        if tag == 1 and bits == 16:
+                            self._audio_id, self.audio_rate, self.audio_channels = b"%02d" % stream, rate, ch
+                    at += 8 + n2 + (n2 & 1)
+                stream += 1
+            pos += 8 + n + (n & 1)
+
+    def _locate(self, movi, index):
+        """[(offset, size)] of the video chunks' and of the audio chunks' bodies, in file order."""
+        import struct
+        f, vid, aud = self._f, [], []
+        take = lambda cc, off, n: (vid if cc[:2] == self._video_id and cc[2:] in (b"dc", b"db") else
+                                   aud if self._audio_id and cc == self._audio_id + b"wb" else []).append((off, n))  # noqa: E731
+        if index:
+            entries = [struct.unpack("<4sIII", index[i:i + 16]) for i in range(0, len(index) - 15, 16)]
+            for origin in (movi[0], 0):  # offsets count from the `movi` fourcc, or from the start of the file
+                vid, aud = [], []
+                cc, _, off, n = entries[0] if entries else (b"", 0, 0, 0)
+                f.seek(origin + off)
+                if entries and f.read(8) == cc + struct.pack("<I", n):
+                    for cc, _, off, n in entries:
+                        take(cc, origin + off + 8, n)
+                    return vid, aud
+        pos, end = movi[0] + 4, movi[1]
+        while pos + 8 <= end:
+            f.seek(pos)
+            hd = f.read(8)
+            if len(hd) < 8:
+                break
+            cc, n = hd[:4], struct.unpack("<I", hd[4:])[0]
+            if cc == b"LIST":
+                pos += 12  # a `rec ` list: its chunks follow
+                continue
+            take(cc, pos + 8, n)
+            pos += 8 + n + (n & 1)
+        return vid, aud
+
+    def __len__(self):
+        return len(self._chunks)
+
+    def _frame(self, i):
+        off, n = self._chunks[i]
+        self._f.seek(off)
+        data = self._f.read(n)
+        if len(data) != n:
+            raise ValueError("AviMjpegReader: frame %d runs past the end of the file" % i)
+        pos = 2
+        while pos + 4 <= len(data) and data[pos] == 0xFF:  # walk to SOS; a DHT on the way means the frame has its tables
+            m, ln = data[pos + 1], (data[pos + 2] << 8) | data[pos + 3]
+            if m == 0xC4:
+                return data
+            if m == 0xDA:
+                return data[:pos] + jpeg_dht_segment() + data[pos:]
+            pos += 2 + ln
+        return data
+
+    def __iter__(self):
+        return (self._frame(i) for i in range(len(self)))
+
+    def read(self, first=0, count=None):
+        from . import jpeg
+        first = int(first)
+        last = len(self) if count is None else min(len(self), first + int(count))
+        if not 0 <= first <= last:
+            raise ValueError("AviMjpegReader.read: frames %d ... of %d" % (first, len(self)))
+        files = [self._frame(i) for i in range(first, last)]
+        edges = [0]
+        for fr in files:
+            edges.append(edges[-1] + len(fr))
+        data = torch.empty(max(1, edges[-1]), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        data[:edges[-1]] = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8) if edges[-1] else data[:0]
+        return jpeg.JpegFrames(data[:edges[-1]], torch.tensor(edges, dtype=torch.int64))
+
+    def chunks(self, n):
+        n = max(1, int(n))
+        return (self.read(at, n) for at in range(0, len(self), n))
+
+    @property
+    def audio_pcm(self):
+        import numpy as np
+        if self._audio_id is None:
+            return None
+        parts = []
+        for off, n in self._audio:
+            self._f.seek(off)
+            parts.append(self._f.read(n))
+        return np.frombuffer(b"".join(parts), dtype="<i2").reshape(-1, self.audio_channels)
+
+    def close(self):
+        f, self._f = getattr(self, "_f", None), None
+        if f is not None and self._own:
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# ---------------------------------------------------------------- baseline JPEG decoding in integers (the definition of float_jpg_decode)
+JPEG_DEC_BAD_CODE, JPEG_DEC_RESTARTS, JPEG_DEC_PAST_END = 1, 2, 4  # the bits of a frame's status word
+_JPEG_SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+                   0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic coding (SOF9)",
+                   0xCA: "arithmetic coding (SOF10)", 0xCB: "arithmetic coding (SOF11)", 0xCD: "arithmetic coding (SOF13)",
+                   0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
+
+
+def jpeg_dht_segment():
+    """The DHT segment of the four Annex K.3 tables, as jpeg_header writes it: what a Motion-JPEG frame without tables means."""
+    import struct
+    return b"".join(b"\xff\xc4" + struct.pack(">HB", 19 + len(vals), tc_th) + bytes(bits) + vals for tc_th, bits, vals in JPEG_HUFFMAN)
+
+
+def jpeg_parse_header(data):
+    """The header of one baseline JPEG file (bytes-like) -> a dict: h, w, ncomp, hs, vs (luma sampling; 1, 1 for grey), qt (per
+    component (64,) int32 in natural order), huff (per component ((bits, vals) DC, (bits, vals) AC)), restart (MCUs, 0 none),
+    scan_start, scan_end (the entropy-coded bytes are data[scan_start:scan_end]: scan_end is the first 0xFF that is followed by
+    anything but 0x00, 0xD0 ... 0xD7 or 0xFF, or the end of the file).  Everything jpeg_decode_rgb8 refuses is a ValueError here."""
+    d = bytes(data)
+    n = len(d)
+    bad = lambda why: ValueError("JPEG decode: " + why)
+    if n < 4 or d[:2] != b"\xff\xd8":
+        raise bad("no SOI marker at the start of the file")
+    qt, huff, sof, ri, pos = {}, {}, None, 0, 2
+    while True:
+        if pos + 2 > n:
+            raise bad("the header runs past the end of the file (truncated header)")
+        if d[pos] != 0xFF:
+            raise bad("no marker at byte %d of the header" % pos)
+        m = d[pos + 1]
+        if m == 0xFF:
+            pos += 1
+            continue
+        pos += 2
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            raise bad("EOI before any scan")
+        if pos + 2 > n or pos + ((d[pos] << 8) | d[pos + 1]) > n or ((d[pos] << 8) | d[pos + 1]) < 2:
+            raise bad("the header runs past the end of the file (truncated header)")
+        seg = d[pos + 2:pos + ((d[pos] << 8) | d[pos + 1])]
+        pos += 2 + len(seg)
+        if m in _JPEG_SOF_NAMES:
+            raise bad("%s is not baseline" % _JPEG_SOF_NAMES[m])
+        if m == 0xCC:
+            raise bad("arithmetic coding (DAC)")
+        if m == 0xDB:
+            at = 0
+            while at < len(seg):
+                pq, tq = seg[at] >> 4, seg[at] & 15
+                size = 64 * (2 if pq else 1)
+                if pq > 1 or tq > 3 or at + 1 + size > len(seg):
+                    raise bad("bad DQT segment")
+                raw = seg[at + 1:at + 1 + size]
+                vals = [(raw[2 * i] << 8) | raw[2 * i + 1] for i in range(64)] if pq else list(raw)
+                t = [0] * 64
+                for i, z in enumerate(JPEG_ZIGZAG):
+                    t[z] = vals[i]
+                qt[tq] = t
+                at += 1 + size
+        elif m == 0xC4:
+            at = 0
+            while at < len(seg):
+                if at + 17 > len(seg):
+                    raise bad("bad DHT segment")
+                tc, th = seg[at] >> 4, seg[at] & 15
+                bits = tuple(seg[at + 1:at + 17])
+                cnt = sum(bits)
+                if tc > 1 or th > 3 or cnt > 256 or at + 17 + cnt > len(seg):
+                    raise bad("bad DHT segment")
+                vals = bytes(seg[at + 17:at + 17 + cnt])
+                code = 0
+                for length in range(1, 17):
+                    code += bits[length - 1]
+                    if code > (1 << length):
+                        raise bad("bad DHT segment (over-subscribed code lengths)")
+                    code <<= 1
+                if tc == 0 and any(v > 15 for v in vals):
+                    raise bad("bad DHT segment (DC category above 15)")
+                huff[(tc, th)] = (bits, vals)
+                at += 17 + cnt
+        elif m == 0xC0:
+            if sof is not None or len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise bad("bad or repeated SOF0 segment")
+            if seg[0] != 8:
+                raise bad("%d-bit samples (8-bit only)" % seg[0])
+            h, w, nc = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if nc not in (1, 3):
+                raise bad("%d components (1 or 3 only)" % nc)
+            if not (1 <= h <= 16384 and 1 <= w <= 16384):
+                raise bad("sides %d x %d outside 1 ... 16384" % (h, w))
+            comps = [(seg[6 + 3 * i], seg[7 + 3 * i] >> 4, seg[7 + 3 * i] & 15, seg[8 + 3 * i]) for i in range(nc)]
+            if nc == 3 and (comps[0][1:3] not in ((1, 1), (2, 1), (2, 2)) or comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1)):
+                raise bad("sampling factors %s (4:4:4, 4:2:2 as 2x1 and 4:2:0 as 2x2 only)" % ", ".join("%dx%d" % c[1:3] for c in comps))
+            if any(c[3] > 3 for c in comps):
+                raise bad("bad SOF0 segment (quantiser table id)")
+            sof = (h, w, nc, comps)
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise bad("bad DRI segment")
+            ri = (seg[0] << 8) | seg[1]
+        elif m == 0xDA:
+            if sof is None:
+                raise bad("SOS before SOF0")
+            h, w, nc, comps = sof
+            if len(seg) < 1 or len(seg) != 4 + 2 * seg[0]:
+                raise bad("bad SOS segment")
+            if seg[0] != nc:
+                raise bad("a scan of %d of %d components (multiple scans)" % (seg[0], nc))
+            tabs = []
+            for i in range(nc):
+                if seg[1 + 2 * i] != comps[i][0]:
+                    raise bad("the scan's components are not in the frame's order")
+                td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+                if comps[i][3] not in qt:
+                    raise bad("missing quantisation table %d" % comps[i][3])
+                if (0, td) not in huff or (1, ta) not in huff:
+                    raise bad("missing Huffman table (DC %d / AC %d)" % (td, ta))
+                tabs.append((huff[(0, td)], huff[(1, ta)]))
+            if tuple(seg[1 + 2 * nc:]) != (0, 63, 0):
+                raise bad("spectral selection or successive approximation in SOS (not baseline)")
+            break
+    import re
+    end = re.compile(b"\xff[^\x00\xd0-\xd7\xff]", re.S).search(d, pos)
+    scan_end = end.start() if end else n
+    at = scan_end
+    while at + 4 <= n and d[at] == 0xFF and d[at + 1] != 0xD9:  # what follows the scan: another scan is refused
+        if d[at + 1] == 0xDA:
+            raise bad("a second SOS (multiple scans)")
+        at += 2 + ((d[at + 2] << 8) | d[at + 3])
+    hs, vs = (comps[0][1], comps[0][2]) if nc == 3 else (1, 1)
+    return dict(h=h, w=w, ncomp=nc, hs=hs, vs=vs, qt=[qt[c[3]] for c in comps], huff=tabs, restart=ri, scan_start=pos, scan_end=scan_end)
+
+
+def _jpeg_huff_decoder(bits, vals):
+    """(look, maxcode, valoff, vals) of a BITS / HUFFVAL pair: look[9-bit prefix] = length << 8 | symbol for codes of up to 9 bits
+    (0: none), maxcode[l] the largest code of length l (-1: none; maxcode[17] ends every search), valoff[l] = index of the first
+    value of length l - its code."""
+    look, maxcode, valoff = [0] * 512, [-1] * 18, [0] * 18
+    code = k = 0
+    for length in range(1, 17):
+        if bits[length - 1]:
+            valoff[length] = k - code
+            for _ in range(bits[length - 1]):
+                if length <= 9:
+                    for fill in range(1 << (9 - length)):
+                        look[(code << (9 - length)) | fill] = (length << 8) | vals[k]
+                code, k = code + 1, k + 1
+            maxcode[length] = code - 1
+        code <<= 1
+    maxcode[17] = 0xFFFFF
+    return look, maxcode, valoff, bytes(vals) + bytes(256 - len(vals))
+
+
+def jpeg_decode_coefficients(data, hdr=None):
+    """The entropy decoding of jpeg_decode_rgb8: -> (coef (MCUs, blocks per MCU, 64) int16 in natural order, NOT dequantised, status)."""
+    import numpy as np
+    import re
+    d = bytes(data)
+    p = hdr or jpeg_parse_header(d)
+    hs, vs, nc = p["hs"], p["vs"], p["ncomp"]
+    mcux, mcuy = -(-p["w"] // (8 * hs)), -(-p["h"] // (8 * vs))
+    nmcu, bpm = mcux * mcuy, hs * vs + nc - 1
+    span = p["restart"] if p["restart"] > 0 else nmcu
+    n_int = -(-nmcu // span)
+    scan = d[p["scan_start"]:p["scan_end"]]
+    marks = [m.start() for m in re.finditer(b"\xff[\xd0-\xd7]", scan, re.S)]
+    status = 0 if len(marks) == n_int - 1 else JPEG_DEC_RESTARTS
+    edges = [0] + [m + 2 for m in marks]
+    ends = marks + [len(scan)]
+    tabs = [(_jpeg_huff_decoder(*dc), _jpeg_huff_decoder(*ac)) for dc, ac in p["huff"]]
+    comp_of = [0] * (hs * vs) + list(range(1, nc))
+    coef = np.zeros((nmcu, bpm, 64), dtype=np.int16)
+    for k in range(min(n_int, len(edges))):  # an interval whose segment is missing keeps its zeros
+        seg = scan[edges[k]:ends[k]].replace(b"\xff\x00", b"\xff")
+        total = 8 * len(seg)
+        val = int.from_bytes(seg, "big")
+        pos = 0
+
+        def peek(nb):  # the next nb bits; zeros past the end of the segment
+            sh = total - pos - nb
+            return ((val >> sh) if sh >= 0 else (val << -sh)) & ((1 << nb) - 1)
+
+        def symbol(tab):
+            nonlocal pos
+            look, maxcode, valoff, vals = tab
+            e = look[peek(9)]
+            if e:
+                pos += e >> 8
+                return e & 255
+            length = 10
+            while length <= 16 and peek(length) > maxcode[length]:
+                length += 1
+            if length > 16:
+                return -1
+            sym = vals[(peek(length) + valoff[length]) & 255]
+            pos += length
+            return sym
+
+        def extend(s):
+            nonlocal pos
+            if s == 0:
+                return 0
+            r = peek(s)
+            pos += s
+            return r if r >= (1 << (s - 1)) else r - (1 << s) + 1
+
+        pred, ok = [0] * nc, True
+        for m in range(k * span, min((k + 1) * span, nmcu)):
+            for j in range(bpm):
+                c = comp_of[j]
+                blk = [0] * 64
+                s = symbol(tabs[c][0])
+                good = s >= 0
+                if good:
+                    pred[c] = (pred[c] + extend(s) + 2**31) % 2**32 - 2**31
+                    blk[0] = (pred[c] + 2**15) % 2**16 - 2**15
+                    i = 1
+                    while i < 64:
+                        rs = symbol(tabs[c][1])
+                        if rs < 0:
+                            good = False
+                            break
+                        r, s = rs >> 4, rs & 15
+                        if s == 0:
+                            if r != 15:
+                                break
+                            if i + 16 > 64:
+                                good = False
+                                break
+                            i += 16
+                            continue
+                        i += r
+                        if i > 63:
+                            good = False
+                            break
+                        blk[JPEG_ZIGZAG[i]] = extend(s)
+                        i += 1
+                if not good:
+                    ok = False
+                    break
+                coef[m, j] = blk
+            if not ok:
+                status |= JPEG_DEC_BAD_CODE
+                break
+        if pos > total:
+            status |= JPEG_DEC_PAST_END
+    return coef, status
+
+
+def _jpeg_idct_islow(x):
+    """libjpeg's jidctint.c on (..., 8, 8) int32 dequantised blocks -> the level-shifted, clamped samples, int32 wrap-around."""
+    import numpy as np
+
+    def pass_(v, shift):  # along the second-to-last axis: v[..., k, :] is input k
+        i0, i1, i2, i3, i4, i5, i6, i7 = (v[..., k, :] for k in range(8))
+        z1 = (i2 + i6) * 4433
+        t2 = z1 + i6 * -15137
+        t3 = z1 + i2 * 6270
+        t0 = (i0 + i4) << 13
+        t1 = (i0 - i4) << 13
+        t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+        z1, z2, z3, z4 = i7 + i1, i5 + i3, i7 + i3, i5 + i1
+        z5 = (z3 + z4) * 9633
+        t0, t1, t2, t3 = i7 * 2446, i5 * 16819, i3 * 25172, i1 * 12299
+        z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+        t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+        rnd = np.int32(1 << (shift - 1))
+        out = [t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3]
+        return np.stack([(o + rnd) >> shift for o in out], axis=-2)
+
+    with np.errstate(over="ignore"):
+        ws = pass_(x.astype(np.int32), 11)
+        px = pass_(ws.swapaxes(-1, -2), 18).swapaxes(-1, -2)
+    return np.clip(px + 128, 0, 255)
+
+
+def jpeg_decode_rgb8(file_bytes, status=False):
+    """One baseline JPEG file (bytes-like) -> (H, W, 3) uint8 RGB as a numpy array: the definition float_jpg_decode is held to bit
+    for bit.  Integer arithmetic only, int32 with wrap-around, `>>` arithmetic; written to libjpeg's published rules, so that on a
+    valid file it is numpy.asarray(PIL.Image.open(...).convert("RGB")) of a Pillow built on libjpeg-turbo.
+    Accepted: SOF0, 8-bit samples, Huffman coding, ONE interleaved scan; 1 component (grey, replicated to RGB) or 3 (YCbCr; chroma
+    1x1, luma 1x1, 2x1 or 2x2); the file's own DQT (8- or 16-bit) and DHT tables; any restart interval; sides 1 ... 16384 (partial
+    MCUs are cropped); APPn, COM and other segments with a length are skipped.  Everything else is a ValueError naming the reason
+    (jpeg_parse_header).
+      entropy  the scan is cut at every 0xFF 0xD0 ... 0xD7; interval k (restart MCUs, or the whole frame) decodes segment k with
+               the predictors at 0; 0xFF 0x00 is the byte 0xFF.  A symbol is looked up by its 9-bit prefix, then bit by bit against
+               maxcode (T.81 F.2.2.3).  DC: category s <= 15, s more bits, the difference added to the predictor in int32, its low
+               16 bits stored.  AC: run r / size s; s = 0 and r = 15 skips 16, s = 0 otherwise ends the block.
+      corrupt  bits past the end of a segment are zero (status |= 4).  A code that matches no symbol, a run past coefficient 63 or
+               a ZRL past 64 ends the interval: that block and the rest of the interval have all-zero coefficients (status |= 1).
+               A marker count other than intervals - 1: status |= 2, missing segments give all-zero intervals, extra ones are
+               ignored.  status 0 is a clean file.
+      IDCT     coefficient x table entry in int32, then jidctint.c ("islow"): scaled LL&M with 13-bit constants, pass 1 down the
+               columns keeping 2 extra bits ((x + 2^10) >> 11), pass 2 along the rows ((x + 2^17) >> 18), + 128, clamped to
+               0 ... 255 (libjpeg's table wraps beyond +-512 instead; no valid file gets there).
+      chroma   "fancy" upsampling where the chroma plane is more than 2 samples wide (cw = ceil(W / 2), ch = ceil(H / 2) for 2x2;
+               neighbours clamped to the plane's true size), else replication.  2x1: out[2i] = (3 c[i] + c[i - 1] + 1) >> 2,
+               out[2i + 1] = (3 c[i] + c[i + 1] + 2) >> 2.  2x2: s[i] = 3 c[near row][i] + c[far row][i], the far row above for an
+               even output row and below for an odd one; out[2i] = (3 s[i] + s[i - 1] + 8) >> 4, out[2i + 1] = (3 s[i] + s[i + 1] + 7) >> 4.
+      colour   R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16),
+               G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16), clamped to 0 ... 255.
+    status=True: returns (rgb, status word)."""
+    import numpy as np
+    d = bytes(file_bytes)
+    p = jpeg_parse_header(d)
+    coef, st = jpeg_decode_coefficients(d, p)
+    H, W, hs, vs, nc = p["h"], p["w"], p["hs"], p["vs"], p["ncomp"]
+    mcux, mcuy = -(-W // (8 * hs)), -(-H // (8 * vs))
+    c5 = coef.reshape(mcuy, mcux, hs * vs + nc - 1, 8, 8).astype(np.int32)
+    planes = []
+    with np.errstate(over="ignore"):
+        for c in range(nc):
+            q = np.array(p["qt"][c], dtype=np.int32).reshape(8, 8)
+            if c == 0:
+                blocks = c5[:, :, :hs * vs].reshape(mcuy, mcux, vs, hs, 8, 8) * q
+                planes.append(_jpeg_idct_islow(blocks).transpose(0, 2, 4, 1, 3, 5).reshape(mcuy * vs * 8, mcux * hs * 8))
+            else:
+                planes.append(_jpeg_idct_islow(c5[:, :, hs * vs + c - 1] * q).transpose(0, 2, 1, 3).reshape(mcuy * 8, mcux * 8))
+    y = planes[0][:H, :W]
+    if nc == 1:
+        out = np.repeat(y[:, :, None], 3, axis=2)
+        return (out.astype(np.uint8), st) if status else out.astype(np.uint8)
+    cw, ch = -(-W // hs), -(-H // vs)
+    full = []
+    for pl in planes[1:]:
+        c = pl[:ch, :cw]
+        if hs == 2 and cw > 2:
+            if vs == 2:
+                up, dn = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+                rows = np.stack([3 * c + up, 3 * c + dn], axis=1).reshape(2 * ch, cw)
+                b0, b1, sh = 8, 7, 4
+            else:
+                rows, b0, b1, sh = c, 1, 2, 2
+            left, right = np.concatenate([rows[:, :1], rows[:, :-1]], axis=1), np.concatenate([rows[:, 1:], rows[:, -1:]], axis=1)
+            c = np.stack([(3 * rows + left + b0) >> sh, (3 * rows + right + b1) >> sh], axis=2).reshape(rows.shape[0], 2 * cw)
+        else:
+            c = np.repeat(np.repeat(c, vs, axis=0), hs, axis=1)
+        full.append(c[:H, :W] - 128)
+    cb, cr = full
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    out = np.clip(np.stack([r, g, b], axis=2), 0, 255).astype(np.uint8)
+    return (out, st) if status else out
+
+
 # ---------------------------------------------------------------- lossless PNG in integers (the definition of float_png_encode)
 # Eight code-length tables over the 256 byte values and end-of-block, one hex digit per symbol (csrc/png_kernels.hpp states the
 # same digits).  Tables 0 ... 6: Huffman lengths of 0.97 Laplace(min(v, 256 - v) / s) + 0.03 uniform for s = 0.35, 0.7, 1.5, 3, 6,

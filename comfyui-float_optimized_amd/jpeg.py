@@ -1,6 +1,7 @@
 """Baseline JPEG files from 8-bit frames on the device (`float_jpg_encode`, include/float_hip.h).  The definition is
 host_models.jpeg_encode_rgb8: colour conversion, chroma subsampling, the two DCT passes, the quantiser and the entropy coding are
-integer arithmetic, and the kernels give its bytes.  What crosses PCIe afterwards is the files, not the frames."""
+integer arithmetic, and the kernels give its bytes.  What crosses PCIe afterwards is the files, not the frames.
+The way back is `float_jpg_decode`: baseline JPEG files -> 8-bit frames on the device, bitwise host_models.jpeg_decode_rgb8."""
 import ctypes as C
 
 import torch
@@ -116,6 +117,126 @@ class JpegFrames:
     @property
     def nbytes(self):
         return self._edges[-1] - self._edges[0]
+
+
+def host_files(files):
+    """JpegFrames, or a list of bytes-likes (one JPEG file each) -> (data, offsets): a 1-d uint8 host tensor holding the files
+    back to back and (n + 1,) int64 host offsets counted from data[0].  A JpegFrames whose offsets start at 0 is used as it is."""
+    if isinstance(files, JpegFrames):
+        base = files._edges[0]
+        return files.data[base:files._edges[-1]], files.offsets - base
+    parts = [bytes(f) for f in files]
+    if not parts:
+        raise ValueError("decode_jpeg_device: no files")
+    edges = [0]
+    for p in parts:
+        edges.append(edges[-1] + len(p))
+    data = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8) if edges[-1] else torch.zeros(0, dtype=torch.uint8)
+    return data, torch.tensor(edges, dtype=torch.int64)
+
+
+class JpegPlan:
+    """float_jpg_decode_plan of n files in host memory (data, offsets as host_files gives them): `.ints` the plan as an int32 host
+    tensor cut to the words in use, and n, h, w, components, sampling, group.  No GPU is needed; what float_jpg_decode_plan
+    refuses is a ValueError naming the frame."""
+
+    def __init__(self, data, offsets):
+        if data.is_cuda or offsets.is_cuda or data.dtype != torch.uint8 or offsets.dtype != torch.int64 or data.dim() != 1 or offsets.dim() != 1:
+            raise ValueError("JpegPlan takes a 1-d uint8 host tensor and 1-d int64 host offsets")
+        data, offsets = data.contiguous(), offsets.contiguous()
+        n = offsets.numel() - 1
+        if n < 1 or int(offsets[0]) < 0 or int(offsets[-1]) > data.numel():
+            raise ValueError("JpegPlan: %d offsets over %d bytes" % (offsets.numel(), data.numel()))
+        L = native.lib()
+        ints = torch.empty(int(L.float_jpg_decode_plan_ints(n)), dtype=torch.int32)
+        native.check(L.float_jpg_decode_plan(C.c_void_p(data.data_ptr()), C.c_void_p(offsets.data_ptr()), n, C.c_void_p(ints.data_ptr()),
+                                             ints.numel()))
+        self.ints = ints[:int(ints[1])].clone()
+        self.n, self.h, self.w, self.components = (int(v) for v in self.ints[2:6])
+        self.sampling, self.group = (int(self.ints[6]), int(self.ints[7])), int(self.ints[13])
+        self.work_bytes = int(L.float_jpg_decode_work_bytes(C.c_void_p(self.ints.data_ptr())))
+
+
+def decode_jpeg_host(files):
+    """float_jpg_decode_host: the kernels' rule run on the host, no GPU -> ((n, H, W, 3) uint8 host tensor, (n,) int32 status)."""
+    data, offsets = host_files(files)
+    plan = JpegPlan(data, offsets)
+    out = torch.empty(plan.n, plan.h, plan.w, 3, dtype=torch.uint8)
+    status = torch.empty(plan.n, dtype=torch.int32)
+    native.check(native.lib().float_jpg_decode_host(C.c_void_p(data.data_ptr()), C.c_void_p(offsets.data_ptr()), C.c_void_p(plan.ints.data_ptr()),
+                                                    plan.n, C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr())))
+    return out, status
+
+
+def enqueue_decode(data_dev, offsets_dev, plan, out, status, work=None):
+    """One float_jpg_decode call on the current stream, nothing read back: data_dev / offsets_dev the files and their offsets on
+    the GPU, plan the JpegPlan made of their host copies, out (n, H, W, 3) uint8 and status (n,) int32 on the same device; work:
+    scratch of plan.work_bytes or None (allocated here, from torch's allocator).  Returns (work, the plan's device copy).
+    Lifetime: tensors that came from torch's caching allocator on this device (data_dev, offsets_dev, work, the plan's copy) may
+    be dropped right after the call - the allocator hands a freed block only to work enqueued LATER on the same stream, and this
+    call runs on the current stream.  Memory from anywhere else (another allocator, another stream's pool) must stay alive
+    until the stream has run the call."""
+    dev = data_dev.device
+    with torch.cuda.device(dev):
+        if work is None or work.numel() < plan.work_bytes:
+            work = torch.empty(max(16, plan.work_bytes), dtype=torch.uint8, device=dev)
+        plan_dev = plan.ints.to(dev, non_blocking=True)
+        native.check(native.lib().float_jpg_decode(
+            C.c_void_p(data_dev.data_ptr()), C.c_void_p(offsets_dev.data_ptr()), C.c_void_p(plan_dev.data_ptr()), C.c_void_p(plan.ints.data_ptr()),
+            plan.n, C.c_void_p(out.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()), work.numel(), native.stream_ptr(dev)))
+    return work, plan_dev
+
+
+STATUS_BITS = {1: "a code that matches no symbol or a run past coefficient 63", 2: "a wrong number of restart markers",
+               4: "a scan that ends early"}
+
+
+@torch.no_grad()
+def decode_jpeg_device(files, offsets=None, strict=True, out=None, device=None, return_status=False):
+    """float_jpg_decode: baseline JPEG files -> (T, H, W, 3) uint8 frames on the device, frame i bitwise
+    host_models.jpeg_decode_rgb8(file i) (which states what is accepted and the arithmetic; a valid file decodes as libjpeg-turbo
+    decodes it).  files: a JpegFrames, a list of bytes-likes - planned on the host and uploaded as files, so only the files' bytes
+    (and a plan of a few KB) cross PCIe - or a 1-d uint8 DEVICE tensor with `offsets` ((T + 1,) int64, host or device), the layout
+    encode_jpeg_device returns: the headers are then read back for planning (one synchronising copy of the files to the host).
+    All files of a call share size, components and sampling; tables and restart intervals may differ.  A file without restart
+    markers is decoded by a single lane: supported, and slow - one interval per MCU row is what the encoder here writes.
+    strict: a frame whose status word is not 0 raises ValueError naming the first such frame (one read-back of T words, which
+    synchronises); strict=False returns the definition's pixels for damaged frames too and reads nothing back.
+    out: a (T, H, W, 3) uint8 device tensor to write into.  return_status=True: (frames, (T,) int32 device tensor)."""
+    if isinstance(files, torch.Tensor):
+        if offsets is None or not files.is_cuda or files.dtype != torch.uint8 or files.dim() != 1:
+            raise ValueError("decode_jpeg_device: a tensor of files must be 1-d uint8 on the GPU and come with offsets")
+        dev = files.device
+        edges = torch.as_tensor(offsets).to("cpu", torch.int64)
+        base, end = int(edges[0]), int(edges[-1])
+        data_dev = files[base:end].contiguous()
+        data, edges = data_dev.cpu(), edges - base
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        data, edges = host_files(files)
+        data_dev = None
+    plan = JpegPlan(data, edges)
+    shape = (plan.n, plan.h, plan.w, 3)
+    if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise ValueError("decode_jpeg_device: out must be a contiguous %s uint8 tensor on the GPU" % (shape,))
+    with torch.cuda.device(dev):
+        if data_dev is None:
+            data_dev = data.to(dev, non_blocking=True)
+        out = torch.empty(shape, dtype=torch.uint8, device=dev) if out is None else out
+        status = torch.empty(plan.n, dtype=torch.int32, device=dev)
+        enqueue_decode(data_dev, edges.to(dev, non_blocking=True), plan, out, status)
+        if strict:
+            check_status(status.cpu())
+    return (out, status) if return_status else out
+
+
+def check_status(status_host, first=0):
+    """ValueError naming the first frame of a decode whose status word is not 0."""
+    bad = torch.nonzero(status_host).flatten()
+    if bad.numel():
+        i, st = int(bad[0]), int(status_host[int(bad[0])])
+        raise ValueError("decode_jpeg_device: frame %d is damaged (status %d: %s)"
+                         % (first + i, st, "; ".join(v for k, v in STATUS_BITS.items() if st & k)))
 
 
 def to_host(data_dev, edges, host=None, stream=None):

@@ -7,7 +7,7 @@ import weakref
 
 import torch
 
-from ... import host_models, weights
+from ... import host_models, jpeg, weights
 from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
@@ -613,6 +613,72 @@ class InferenceAgent:
                 rows += face.detect_batch(views) if self._view_fits(face, views[0]) else [[] for _ in range(views.shape[0])]
         return rows
 
+    def _driving_clip_rects(self, T, H, Wd, rects, crop, detect_every, smooth, margin, index, sampled):
+        """align_driving's rects, one per frame: those given, or host_models.driving_rects on the detector's rows;
+        sampled(idx) -> (video, idx') hands over the frames the detector is to see."""
+        o = self.opt
+        rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+        if rects is not None:
+            r = torch.as_tensor(rects, dtype=torch.int64).reshape(-1, 4)
+            if r.shape[0] not in (1, T):
+                raise ValueError("align_driving: %d rects for %d frames" % (r.shape[0], T))
+            return [tuple(int(v) for v in row) for row in r.expand(T, 4).tolist()]
+        idx = host_models.driving_detect_frames(T, detect_every) if crop is not None else []
+        rows = self._driving_rows(*sampled(idx), rgba, bkg) if idx else None
+        rects = host_models.driving_rects(rows, idx, T, H, Wd, float(margin if margin is not None else getattr(o, "face_margin", 1.6)),
+                                          index, None if rows is None else crop, smooth, main_logger)
+        return [tuple(int(v) for v in row) for row in rects]
+
+    def _align_driving_jpeg(self, video, crop, detect_every, smooth, margin, index, rects, chunk):
+        """align_driving for a Motion-JPEG clip: a jpeg.JpegFrames, a host_models.AviMjpegReader, or the path of an .avi.  The
+        files cross PCIe as they are, `chunk` at a time; float_jpg_decode turns them into uint8 frames in one reused device
+        buffer, which float_img_front_frames reads as it reads an uploaded chunk.  Frames the detector is to see are decoded
+        once more, on their own.  A path or a reader is read from the file chunk by chunk too."""
+        o = self.opt
+        size = int(o.input_size)
+        rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+        opened = host_models.AviMjpegReader(video) if isinstance(video, (str, os.PathLike)) else None
+        try:
+            return self._align_driving_files(video if opened is None else opened, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg)
+        finally:
+            if opened is not None:
+                opened.close()
+
+    def _align_driving_files(self, video, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg):
+        """_align_driving_jpeg on a JpegFrames (in host memory as it is) or an open AviMjpegReader, which is read `chunk` frames at
+        a time: the host holds one chunk of files, the device one chunk of frames, whatever the clip's length."""
+        if isinstance(video, host_models.AviMjpegReader):
+            part = lambda lo, hi: video.read(lo, hi - lo)  # noqa: E731
+        elif isinstance(video, jpeg.JpegFrames):
+            part = lambda lo, hi: jpeg.JpegFrames(video.data, video.offsets[lo:hi + 1])  # noqa: E731
+        else:
+            raise ValueError("align_driving: video must be a (T, H, W, 3|4) tensor, a JpegFrames, an AviMjpegReader or the path of an .avi, got %s"
+                             % type(video).__name__)
+        T = len(video)
+        if T == 0:
+            raise ValueError("align_driving: the clip holds no frames")
+        first = jpeg.JpegPlan(*jpeg.host_files(part(0, 1)))
+        H, Wd = first.h, first.w
+        self.to_target()
+        rects = self._driving_clip_rects(T, H, Wd, rects, crop, detect_every, smooth, margin, index,
+                                         lambda idx: (jpeg.decode_jpeg_device([bytes(part(i, i + 1)[0]) for i in idx], device=self.rank), list(range(len(idx)))))
+        out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=self.rank)
+        dev = torch.device("cuda", self.rank) if isinstance(self.rank, int) else torch.device(self.rank)
+        status = torch.empty(T, dtype=torch.int32, device=dev)
+        buf = torch.empty((min(chunk, T), H, Wd, 3), dtype=torch.uint8, device=dev)
+        work = None
+        with torch.cuda.device(dev):
+            for at in range(0, T, chunk):
+                n = min(chunk, T - at)
+                data, edges = jpeg.host_files(part(at, at + n))
+                plan = jpeg.JpegPlan(data, edges)
+                if (plan.h, plan.w) != (H, Wd):
+                    raise ValueError("align_driving: frame %d is %d x %d, the clip's first frame %d x %d" % (at, plan.h, plan.w, H, Wd))
+                work, _ = jpeg.enqueue_decode(data.to(dev, non_blocking=True), edges.to(dev, non_blocking=True), plan, buf[:n], status[at:at + n], work)
+                front_frames_device(buf[:n], rects[at:at + n], size, size, rgba, bkg, out=out[at:at + n])
+        jpeg.check_status(status.cpu())
+        return out, rects
+
     @torch.no_grad()
     def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32):
         """A raw driving video -> the frames drive_device takes: video (T, H, W, 3|4), fp32 in [0, 1] or uint8, on the host or on
@@ -625,26 +691,22 @@ class InferenceAgent:
         frame; None: the centre square, no detector pass).  detect_every=5 is a choice, not a measurement of this call: 20.5 ms per
         16 views (README) makes every frame of a 10-s clip about 320 ms beside a 95-ms motion pass, every fifth about 64 ms.
         A host video goes through `chunk` frames at a time over one reused device buffer, so the source's HBM is bounded by the
-        chunk whatever the clip's length; it crosses PCIe once, and the sampled frames once more when the detector runs."""
+        chunk whatever the clip's length; it crosses PCIe once, and the sampled frames once more when the detector runs.
+        video may also be a Motion-JPEG clip - a jpeg.JpegFrames, a host_models.AviMjpegReader or the path of an .avi (what
+        write_video and AviMjpegWriter write, or an ffmpeg / webcam MJPEG capture): the files cross PCIe compressed, `chunk` at a
+        time, float_jpg_decode makes the uint8 frames in the reused device buffer, and the result is bit for bit align_driving on
+        host_models.jpeg_decode_rgb8 of every frame.  A damaged frame (a non-zero status word) is a ValueError naming it."""
         o = self.opt
         size = int(o.input_size)
         rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
+        if not isinstance(video, torch.Tensor):
+            return self._align_driving_jpeg(video, crop, detect_every, smooth, margin, index, rects, max(1, int(chunk)))
         if video.dim() != 4 or video.shape[-1] not in (3, 4) or 0 in video.shape or not (video.dtype == torch.uint8 or video.is_floating_point()):
             raise ValueError("align_driving: video must be (T, H, W, 3|4) uint8 or float, got %s %s" % (video.dtype, tuple(video.shape)))
         T, H, Wd, ch = (int(v) for v in video.shape)
         chunk = max(1, int(chunk))
         self.to_target()
-        if rects is not None:
-            r = torch.as_tensor(rects, dtype=torch.int64).reshape(-1, 4)
-            if r.shape[0] not in (1, T):
-                raise ValueError("align_driving: %d rects for %d frames" % (r.shape[0], T))
-            rects = [tuple(int(v) for v in row) for row in r.expand(T, 4).tolist()]
-        else:
-            idx = host_models.driving_detect_frames(T, detect_every) if crop is not None else []
-            rows = self._driving_rows(video, idx, rgba, bkg) if idx else None
-            rects = host_models.driving_rects(rows, idx, T, H, Wd, float(margin if margin is not None else getattr(o, "face_margin", 1.6)),
-                                              index, None if rows is None else crop, smooth, main_logger)
-            rects = [tuple(int(v) for v in row) for row in rects]
+        rects = self._driving_clip_rects(T, H, Wd, rects, crop, detect_every, smooth, margin, index, lambda idx: (video, idx))
         out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=self.rank)
         buf = None
         for at in range(0, T, chunk):
@@ -664,7 +726,8 @@ class InferenceAgent:
         """drive_device from raw inputs: the portrait ref_img (a ComfyUI IMAGE item) goes through host_inputs' image half
         (no_crop as there), the raw driving video through align_driving (crop ... chunk as there), and the two through
         drive_device (mode, out, out_dtype, out_format, matrix as there).  With rects= given it is bit for bit drive_device on
-        the definition's crops of the video."""
+        the definition's crops of the video.  video: a tensor of raw frames, or a Motion-JPEG clip (JpegFrames, AviMjpegReader,
+        the path of an .avi) that is decoded on the device - align_driving has the details."""
         self._crop_matrix("drive_video", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
         silence = {"waveform": torch.zeros(1, 1, 16), "sample_rate": self.opt.sampling_rate}  # _host_inputs' audio half: unused
         s = self._host_inputs(ref_img, silence, no_crop, False)[0]

@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
+/* Stays 6: float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
+ * decoded to 8-bit RGB frames on the device), float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
  * Lanczos resampling of 8-bit frames on the device), float_img_paste_i420 (the pasted frames as planar YUV 4:2:0),
@@ -797,6 +798,50 @@ int float_jpg_encode(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w
 size_t float_jpg_work_bytes_padded(int32_t n_frames, int32_t h, int32_t w, int32_t restart);
 int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, int32_t w, int32_t quality, int32_t restart, uint8_t* out,
                             size_t out_cap, int64_t* offsets, void* work, size_t work_bytes, void* stream);
+
+/* ---------------------------------------------------------------- JPEG decoder -- */
+/* n baseline JPEG files, back to back as float_jpg_encode writes them (file i is files[offsets[i] : offsets[i + 1]]), -> n 8-bit
+ * RGB frames (n, h, w, 3) in HBM, bitwise the definition in the host mirror, host_models.jpeg_decode_rgb8, which states the
+ * arithmetic: libjpeg's integer rules (the "islow" IDCT, "fancy" chroma upsampling, the 16-bit YCbCr tables), so that a valid
+ * file decodes to what libjpeg-turbo gives.  Accepted: SOF0, 8-bit samples, Huffman coding, one interleaved scan, 1 component
+ * (grey, replicated) or 3 (YCbCr; luma sampled 1x1, 2x1 or 2x2, chroma 1x1), the file's own DQT (8- or 16-bit) and DHT tables,
+ * any restart interval, sides 1 ... 16384 (partial MCUs are cropped), APPn / COM skipped.
+ *
+ * float_jpg_decode_plan parses the headers of n files in HOST memory into `plan` (plan_ints >= float_jpg_decode_plan_ints(n)
+ * int32 words; plan[1] is the number of words in use, the part to copy to the device).  Host only: no HIP call, usable without
+ * a GPU.  The plan holds, per frame, the scan's first and last byte, the MCUs per restart interval, the number of intervals and
+ * the index of its table set, and per DISTINCT table set the components' quantiser tables and Huffman tables in the decoder's
+ * form (9-bit look-ahead, maxcode, value offsets, values); csrc/jpgd_rule.hpp has the layout.  All frames of a call share h, w,
+ * components and sampling - plan[3], plan[4], plan[5] and plan[6] x plan[7] - while table sets may differ from frame to frame.
+ * Refused (FLOAT_E_INVALID, the message names the frame and the reason): progressive, extended, lossless or differential SOFs,
+ * arithmetic coding, 12-bit samples, 4 components or other sampling factors, more than one scan, a missing table, a header
+ * that runs past the end of its file, frames of different geometry.
+ *
+ * float_jpg_decode:
+ *   files, offsets   DEVICE copies of what the plan call read: the bytes, and n_frames + 1 int64, 8-byte aligned
+ *   plan, plan_host  the plan in DEVICE memory (the kernels read it) and the host's own copy (the call reads its header and the
+ *                    frame count from it to size the launches)
+ *   rgb8_out         DEVICE, (n_frames, h, w, 3) uint8.  status: DEVICE, n_frames int32, written by the call: 0 for a clean
+ *                    frame, else bits 1 (a code that matches no symbol, or a run past coefficient 63: the rest of that restart
+ *                    interval has all-zero coefficients), 2 (the scan does not hold intervals - 1 restart markers: missing
+ *                    intervals are all zero, extra bytes ignored), 4 (bits were read past the end of a segment: they are zero).
+ *                    A damaged frame still gets the definition's pixels; nothing is read outside a file's bytes or written
+ *                    outside a frame.
+ *   work             DEVICE scratch of float_jpg_decode_work_bytes(plan_host) bytes, 16-byte aligned, no zeroing needed: per
+ *                    frame of a group the interval table, the int16 coefficients and the component planes.  Frames go in
+ *                    groups of 16 (fewer where 16 frames' share would pass 1 GiB; plan[13]) that share it in stream order.
+ * Four kernels per group: the restart markers of a scan are found by all lanes of a workgroup and compacted in order; every
+ * restart interval is then decoded by a lane of its own (DC prediction restarts at a marker), so a file WITHOUT restart markers
+ * is one serial chain on one lane - supported, bitwise the definition, and slow; IDCT; upsampling and colour.  Enqueues kernels
+ * only: allocates nothing, synchronises nothing, and the only atomics are ORs into the status words, so two calls give equal
+ * bytes.  float_jpg_decode_host runs the same rule on the host (everything in host memory; the test and sanitizer path). */
+size_t float_jpg_decode_plan_ints(int32_t n_frames);
+int float_jpg_decode_plan(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints);
+size_t float_jpg_decode_work_bytes(const int32_t* plan_host);
+int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t* plan, const int32_t* plan_host, int32_t n_frames,
+                     uint8_t* rgb8_out, int32_t* status, void* work, size_t work_bytes, void* stream);
+int float_jpg_decode_host(const uint8_t* files, const int64_t* offsets, const int32_t* plan_host, int32_t n_frames, uint8_t* rgb8_out,
+                          int32_t* status);
 
 /* ---------------------------------------------------------------- PNG encoder -- */
 /* n_frames 8-bit RGB frames in HBM -> n complete PNG files (8 bits, colour type 2, no interlace, one IDAT), LOSSLESS, back to

@@ -1,0 +1,112 @@
+"""JPEG decode timing probe: a 10-s driving clip (250 frames of 1920 x 1080) as Motion-JPEG files (quality 90, 4:2:0, made by
+float_jpg_encode_padded from a smooth moving pattern with noise), with one restart interval per MCU row and without restart
+markers.  All routes interleaved in one process, medians of JPEGDEC_REPS (10) repetitions after warm-up, spread max - min:
+  (a) float_jpg_decode alone, files already in HBM: device-event ms per clip and GB/s of output pixels, both clips.
+  (b) InferenceAgent.drive_video (512-px synthetic model, rects given, wall clock) from: the MJPEG files with restart markers;
+      the files without; the raw pageable uint8 host video (the route before this decoder); a Pillow decode loop on the host
+      feeding that raw route (the Pillow loop is also reported alone).
+Bytes across PCIe: the files against T x 1080 x 1920 x 3.  JPEGDEC_FRAMES / JPEGDEC_REPS shrink the run for a rehearsal."""
+import importlib
+import io
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, ".")
+from tests.util import load_pkg  # noqa: E402
+
+pkg = load_pkg()
+J, Wt = pkg.jpeg, pkg.weights
+T, REPS, WARM = int(os.environ.get("JPEGDEC_FRAMES", 250)), int(os.environ.get("JPEGDEC_REPS", 10)), 2
+H, W = 1080, 1920
+RECT = (460, 40, 1000, 1000)
+
+g = torch.Generator(device="cuda").manual_seed(2)
+yy, xx = torch.meshgrid(torch.arange(H, device="cuda"), torch.arange(W, device="cuda"), indexing="ij")
+frames = torch.empty(T, H, W, 3, dtype=torch.uint8, device="cuda")
+for t in range(T):
+    base = torch.stack([128 + 100 * torch.sin((xx + 3 * t) / 70.0 + c) * torch.cos(yy / 50.0 - c) for c in range(3)], -1)
+    frames[t] = (base + 6 * torch.randn(H, W, 3, device="cuda", generator=g)).clamp_(0, 255).to(torch.uint8)
+clips = {}
+for name, restart in (("restart per MCU row", None), ("no restart markers", 0)):
+    data, offsets = J.encode_jpeg_device(frames, 90, restart, pad="edge")
+    clips[name] = J.to_host(data, offsets.cpu())
+del frames
+video8 = J.decode_jpeg_device(clips["restart per MCU row"]).cpu()  # pageable: what the raw route is handed
+print("%d frames of %d x %d: %.1f MB of files (%.1f MB without restart markers) against %.1f MB raw" % (
+    T, W, H, clips["restart per MCU row"].nbytes / 1e6, clips["no restart markers"].nbytes / 1e6, video8.numel() / 1e6))
+
+
+def event_ms(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+# (a) the decode launches alone
+resident = {}
+for name, jf in clips.items():
+    data, edges = J.host_files(jf)
+    plan = J.JpegPlan(data, edges)
+    resident[name] = (data.cuda(), edges.cuda(), plan, torch.empty(plan.n, H, W, 3, dtype=torch.uint8, device="cuda"),
+                      torch.empty(plan.n, dtype=torch.int32, device="cuda"), torch.empty(plan.work_bytes, dtype=torch.uint8, device="cuda"))
+ta = {k: [] for k in resident}
+for r in range(WARM + REPS):
+    for k, (d, e, plan, out, st, work) in resident.items():
+        ms = event_ms(lambda: J.enqueue_decode(d, e, plan, out, st, work))
+        if r >= WARM:
+            ta[k].append(ms)
+for k, v in ta.items():
+    m = statistics.median(v)
+    print("(a) decode, %-20s %9.2f ms per clip (spread %.2f) | %.1f GB/s of pixels | equal to the other clip's frames: %s" % (
+        k, m, max(v) - min(v), T * H * W * 3 / m / 1e6, torch.equal(resident[k][3], next(iter(resident.values()))[3])))
+del resident
+
+# (b) through the agent
+gen = importlib.import_module(pkg.__name__ + ".src.nodes.generate")
+opt = importlib.import_module(pkg.__name__ + ".src.nodes.options.base_options").BaseOptions()
+opt.input_size = 512
+acfg = pkg.config.small_audio_config()
+acfg.dim_w = opt.dim_w
+parts = dict(enc=Wt.synth_encoder_state(512, seed=31), dec=Wt.synth_decoder_state(512, seed=31),
+             fmt=Wt.synth_fmt_state(pkg.config.FmtConfig.from_options(opt), seed=31), audio_encoder=(Wt.synth_audio_state(acfg, seed=31), acfg))
+agent = gen.InferenceAgent(opt, parts, "cuda:0")
+portrait = torch.rand(1, 512, 512, 3, generator=torch.Generator().manual_seed(3))
+pil_files = [bytes(f) for f in clips["restart per MCU row"]]
+
+
+def pillow_loop():
+    return torch.from_numpy(np.stack([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in pil_files]))
+
+
+drive = lambda v: agent.drive_video(portrait, v, rects=RECT, out_dtype=torch.uint8)  # noqa: E731
+routes = {"mjpeg, restart per MCU row": lambda: drive(clips["restart per MCU row"]),
+          "mjpeg, no restart markers": lambda: drive(clips["no restart markers"]),
+          "raw pageable uint8 video": lambda: drive(video8),
+          "pillow loop + raw route": lambda: drive(pillow_loop()),
+          "pillow loop alone": pillow_loop}
+tb = {k: [] for k in routes}
+for r in range(1 + REPS):
+    for k, fn in routes.items():
+        ms = wall_ms(fn)
+        if r >= 1:
+            tb[k].append(ms)
+for k, v in tb.items():
+    print("(b) %-28s %9.1f ms per clip (spread %.1f)" % (k, statistics.median(v), max(v) - min(v)))
