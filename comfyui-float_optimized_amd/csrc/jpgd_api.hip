@@ -1,4 +1,4 @@
-// float_jpg_decode_plan[_ints] / float_jpg_decode_work_bytes / float_jpg_decode / float_jpg_decode_host: baseline JPEG files ->
+// float_jpg_decode_plan[_ints | _entropy] / float_jpg_decode_work_bytes / float_jpg_decode / float_jpg_decode_host: baseline JPEG files ->
 // 8-bit RGB frames on the device (include/float_hip.h).
 #include "jpgd_kernels.hpp"
 #include "jpgd_plan.hpp"
@@ -7,7 +7,7 @@ namespace {
 JpgdLaunch jpgd_launch(const int32_t* plan) {
   const JpgdWork k = jpgd_work(plan);
   JpgdLaunch L{};
-  L.seg = k.seg, L.coef = k.coef, L.frame = k.frame, L.pw = k.pw, L.cw = k.cw, L.nblocks = k.nblocks;
+  L.seg = k.seg, L.coef = k.coef, L.frame = k.frame, L.pw = k.pw, L.cw = k.cw, L.nblocks = k.nblocks, L.unst = k.unst, L.table = k.table;
   for (int c = 0; c < 3; ++c) L.plane[c] = k.plane[c];
   return L;
 }
@@ -22,6 +22,16 @@ int float_jpg_decode_plan(const uint8_t* files, const int64_t* offsets, int32_t 
   FH_REQUIRE(n_frames >= 1, "float_jpg_decode_plan: n_frames (%d) must be positive", n_frames);
   char why[400];
   FH_REQUIRE(jpgd_build_plan(files, offsets, n_frames, plan, plan_ints, why, sizeof(why)) == 0, "float_jpg_decode_plan: %s", why);
+  return FLOAT_OK;
+}
+
+int float_jpg_decode_plan_entropy(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints, int32_t entropy,
+                                  int32_t sync_bytes) {
+  FH_REQUIRE(files && offsets && plan, "float_jpg_decode_plan_entropy: null argument (files, offsets or plan)");
+  FH_REQUIRE(n_frames >= 1, "float_jpg_decode_plan_entropy: n_frames (%d) must be positive", n_frames);
+  char why[400];
+  FH_REQUIRE(jpgd_build_plan(files, offsets, n_frames, plan, plan_ints, why, sizeof(why), entropy, sync_bytes) == 0, "float_jpg_decode_plan_entropy: %s",
+             why);
   return FLOAT_OK;
 }
 
@@ -56,6 +66,7 @@ int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t
   const unsigned lanes = (unsigned)((plan_host[JPGD_P_MAXINT] + kJpgdLanes - 1) / kJpgdLanes);
   const unsigned idct = (unsigned)((L.nblocks + kJpgdIdctBlocks - 1) / kJpgdIdctBlocks);
   const unsigned cols = (unsigned)(((W + 3) / 4 + kJpgdRgbThreads - 1) / kJpgdRgbThreads);
+  const unsigned sync = (unsigned)((jpgd_work(plan_host).sync_lanes + kJpgdLanes - 1) / kJpgdLanes);  // 0: no frame on the sync route
   for (int f0 = 0; f0 < n_frames; f0 += group) {  // groups share `work` in stream order
     L.frame0 = f0, L.frames = std::min(group, n_frames - f0);
     const unsigned nf = (unsigned)L.frames;
@@ -63,6 +74,14 @@ int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t
                        (uint8_t*)work, (int*)status);
     hipLaunchKernelGGL(jpgd_entropy_kernel, dim3(lanes, nf), dim3(kJpgdLanes), 0, s, files, (const long long*)offsets, (const int*)plan, L,
                        (uint8_t*)work, (int*)status);
+    bool any = false;
+    for (int f = f0; f < f0 + L.frames; ++f) any = any || plan_host[plan_host[JPGD_P_FRAMES] + f * JPGD_F_INTS + JPGD_F_ROUTE];
+    if (any) {  // each returns at once for a frame on the interval route, as jpgd_entropy_kernel does for the others
+      hipLaunchKernelGGL(jpgd_unstuff_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, files, (const long long*)offsets, (const int*)plan, L,
+                         (uint8_t*)work);
+      hipLaunchKernelGGL(jpgd_relax_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, (const int*)plan, L, (uint8_t*)work);
+      hipLaunchKernelGGL(jpgd_sync_write_kernel, dim3(sync, nf), dim3(kJpgdLanes), 0, s, (const int*)plan, L, (uint8_t*)work, (int*)status);
+    }
     hipLaunchKernelGGL(jpgd_idct_kernel, dim3(idct, nf), dim3(kJpgdIdctBlocks * 8), 0, s, (const int*)plan, L, (uint8_t*)work);
     hipLaunchKernelGGL(jpgd_rgb_kernel, dim3(cols, (unsigned)H, nf), dim3(kJpgdRgbThreads), 0, s, (const int*)plan, L, (const uint8_t*)work,
                        rgb8_out);

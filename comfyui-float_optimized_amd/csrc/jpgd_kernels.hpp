@@ -5,6 +5,8 @@
 //   jpgd_entropy_kernel  one restart interval per lane; the frame's table set sits in LDS once per workgroup, a lane gathers a
 //                        block in an LDS row of its own (33 dwords apart: lanes fall into different banks) and hands it to the
 //                        coefficient buffer as eight 16-byte stores.
+//   (frames on the sync route - a scan without restart markers over up to 1024 lanes - are skipped by it and go through
+//   jpgd_unstuff_kernel, jpgd_relax_kernel and jpgd_sync_write_kernel instead: three more launches, described where they are)
 //   jpgd_idct_kernel     32 blocks per workgroup: coefficients into LDS by 16-byte loads, pass 1 down the columns (dequantising),
 //                        the block transposed through LDS, pass 2 along the rows, 8 samples per lane as one 8-byte store.
 //   jpgd_rgb_kernel      4 pixels per lane: fancy upsampling from the chroma planes, colour conversion, one 12-byte store.
@@ -22,6 +24,7 @@ struct JpgdLaunch {  // what the host read from its copy of the plan
   unsigned long long seg, coef, plane[3], frame;  // byte offsets inside a frame's share of `work`, and its size
   int pw, cw;          // row strides of the luma and chroma planes
   long long nblocks;
+  unsigned long long unst, table;  // the sync route's share: a scan without its stuffing, the lane table
 };
 
 // LDS words that are written as one type and read as another (a block's int16 coefficients, moved as dwords)
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(kJpgdLanes) void jpgd_entropy_kernel(const uint8_t*
   __shared__ jpgd_word rows[kJpgdLanes * kJpgdRowDwords];
   const int f = L.frame0 + blockIdx.y, lane = threadIdx.x;
   const int* fr = jpgd_frame(plan, f);
+  if (fr[JPGD_F_ROUTE]) return;  // the sync route's frame
   const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
   for (int i = lane; i < kJpgdSetInts; i += kJpgdLanes) set[i] = gset[i];
   __syncthreads();
@@ -115,6 +119,175 @@ __global__ __launch_bounds__(kJpgdLanes) void jpgd_entropy_kernel(const uint8_t*
     }
   if (b0 >= 0 && jpgd_past_end(b)) st |= JPGD_ST_PAST_END;
   if (st) atomicOr(status + f, st);
+}
+
+// ---------------------------------------------------------------- the sync route (jpgd_rule.hpp): frames whose ROUTE word is set
+// The frame's one segment [seg[0], seg[1]) - jpgd_scan_kernel cut it - without the 0x00 behind a 0xFF: a byte per lane, wave
+// ballot + prefix count as in the marker compaction.  Writes the table's header: the length, S and n_sub.
+__global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_unstuff_kernel(const uint8_t* __restrict__ files, const long long* __restrict__ offsets,
+                                                                     const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {
+  constexpr int kWaves = kJpgdSyncLanes / 64;
+  __shared__ int wave_cnt[2][kWaves];  // iteration k + 2 writes a row only behind iteration k + 1's barrier: all have read k's
+  const int f = L.frame0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* fr = jpgd_frame(plan, f);
+  if (!fr[JPGD_F_ROUTE]) return;
+  uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
+  const int* seg = (const int*)(mine + L.seg);
+  const uint8_t* file = files + offsets[f];
+  uint8_t* u = mine + L.unst;
+  const int b0 = seg[0], b1 = seg[1];
+  int total = 0;  // bytes kept so far, the same in every lane
+  for (int base = b0, it = 0; base < b1; base += kJpgdSyncLanes, it ^= 1) {
+    const int q = base + tid;
+    const uint8_t v = q < b1 ? file[q] : 0;
+    const bool keep = q < b1 && !(v == 0 && q > b0 && file[q - 1] == 0xFF);
+    const unsigned long long vote = __ballot(keep);
+    if (lane == 0) wave_cnt[it][wave] = __popcll(vote);
+    __syncthreads();
+    int before = total, all = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      const int c = wave_cnt[it][w];
+      before += w < wave ? c : 0;
+      all += c;
+    }
+    if (keep) u[before + __popcll(vote & ((1ull << lane) - 1ull))] = v;
+    total += all;
+  }
+  if (tid == 0) {
+    int* tab = (int*)(mine + L.table);
+    const uint32_t S = jpgd_sync_sub((uint32_t)total, (uint32_t)fr[JPGD_F_ROUTE]);
+    tab[JPGD_T_LEN] = total, tab[JPGD_T_S] = (int)S, tab[JPGD_T_NSUB] = (int)jpgd_sync_lanes((uint32_t)total, S);
+  }
+}
+
+// One workgroup per frame, lane = subsequence, the exits in LDS.  Round 0 decodes from the guesses (8 i S, 0) - lane 0 from the
+// true (0, 0) -, round r only where the predecessor's exit is not the entry last used; nothing is stored.  A dead exit is taken
+// over in round i and not before, when lane i - 1 is final: a guess that ran into a bad code (one lane in six does, on 1080p
+// frames) would otherwise kill every guess behind it, and the chain would be walked lane by lane.  The loop ends with the first
+// round in which no exit changes and no lane waits, after n_sub rounds at the latest.  Then an exclusive prefix over the lanes of the block
+// counts and DC sums gives every lane its first block and predictions: the lane table.
+__global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_relax_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {
+  __shared__ int set[kJpgdSetInts];
+  __shared__ uint32_t xp[kJpgdSyncLanes], xn[kJpgdSyncLanes];
+  __shared__ int xj[kJpgdSyncLanes], xd[3][kJpgdSyncLanes];
+  const int f = L.frame0 + blockIdx.x, i = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  if (!fr[JPGD_F_ROUTE]) return;
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  for (int k = i; k < kJpgdSetInts; k += kJpgdSyncLanes) set[k] = gset[k];
+  uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
+  const uint8_t* u = mine + L.unst;
+  int* tab = (int*)(mine + L.table);
+  const uint32_t len = (uint32_t)tab[JPGD_T_LEN], S = (uint32_t)tab[JPGD_T_S];
+  const int nsub = tab[JPGD_T_NSUB], hv = plan[JPGD_P_HS] * plan[JPGD_P_VS], bpm = plan[JPGD_P_BPM];
+  const bool active = i < nsub;
+  const uint32_t end = jpgd_sync_end((uint32_t)i, S, len);
+  uint32_t entry_p = 8u * (uint32_t)i * S;
+  int entry_j = 0, rounds = 0;
+  xp[i] = kJpgdDead, xj[i] = 0, xn[i] = 0, xd[0][i] = 0, xd[1][i] = 0, xd[2][i] = 0;
+  __syncthreads();
+  bool need = active, wait = false;
+  for (int r = 0; r < nsub; ++r) {
+    bool changed = wait;
+    if (need) {
+      JpgdRun x{entry_p, entry_j, 0u, {0, 0, 0}};
+      JpgdRaw b;
+      jpgd_sync_run(b, u, len, end, false, 0xFFFFFFFFu, hv, bpm, x, [&](JpgdRaw& bits, int c, int32_t& pred, uint32_t) {
+        return jpgd_block(bits, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pred, JpgdNoCoef());
+      });
+      changed = r == 0 || x.p != xp[i] || x.j != xj[i];
+      xp[i] = x.p, xj[i] = x.j, xn[i] = x.n, xd[0][i] = x.dc[0], xd[1][i] = x.dc[1], xd[2][i] = x.dc[2];
+    }
+    ++rounds;
+    if (!__syncthreads_or(changed)) break;
+    need = wait = false;
+    if (active && i > 0 && (xp[i - 1] != entry_p || xj[i - 1] != entry_j)) {
+      if (xp[i - 1] == kJpgdDead && r + 1 < i) wait = true;  // a guess ran into a bad code: not final before round i
+      else entry_p = xp[i - 1], entry_j = xj[i - 1], need = true;
+    }
+    __syncthreads();  // every exit is read before the round rewrites it
+  }
+  __syncthreads();
+  const uint32_t own_n = xn[i];
+  const int own_d[3] = {xd[0][i], xd[1][i], xd[2][i]};
+  const bool dead = xp[nsub - 1] == kJpgdDead;
+  for (int off = 1; off < kJpgdSyncLanes; off <<= 1) {  // inclusive prefix, in place
+    const bool has = i >= off;
+    const uint32_t an = has ? xn[i - off] : 0u;
+    const int a0 = has ? xd[0][i - off] : 0, a1 = has ? xd[1][i - off] : 0, a2 = has ? xd[2][i - off] : 0;
+    __syncthreads();
+    xn[i] += an, xd[0][i] = jpgd_add(xd[0][i], a0), xd[1][i] = jpgd_add(xd[1][i], a1), xd[2][i] = jpgd_add(xd[2][i], a2);
+    __syncthreads();
+  }
+  if (active) {
+    int* e = tab + JPGD_T_HEADER + i * JPGD_T_LANE;
+    e[0] = (int)entry_p, e[1] = entry_j, e[2] = (int)(xn[i] - own_n);
+    e[3] = jpgd_sub(xd[0][i], own_d[0]), e[4] = jpgd_sub(xd[1][i], own_d[1]), e[5] = jpgd_sub(xd[2][i], own_d[2]);
+  }
+  if (i == 0) {  // a chain that died inside the data: every block from the bad one on is zero
+    const long long good = xn[kJpgdSyncLanes - 1];
+    tab[JPGD_T_ZERO] = (int)(dead && good < L.nblocks ? good : L.nblocks), tab[JPGD_T_ROUNDS] = rounds;
+  }
+}
+
+// The write pass, jpgd_entropy_kernel's shape: a lane decodes its owned blocks once more, from its table entry, into an LDS row
+// and the coefficient buffer, and stops at block nblocks.  The last lane goes on past the data on zero bits.  A bad code on
+// the chain ends it; the blocks from there on are zeroed by all lanes of the launch when the relaxation saw the chain die, and
+// by the lane itself when it died on the zero bits behind the data, which no lane owns.
+__global__ __launch_bounds__(kJpgdLanes) void jpgd_sync_write_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work,
+                                                                    int* __restrict__ status) {
+  __shared__ int set[kJpgdSetInts];
+  __shared__ jpgd_word rows[kJpgdLanes * kJpgdRowDwords];
+  const int f = L.frame0 + blockIdx.y, lane = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  if (!fr[JPGD_F_ROUTE]) return;
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  for (int k = lane; k < kJpgdSetInts; k += kJpgdLanes) set[k] = gset[k];
+  __syncthreads();
+  uint8_t* mine = work + (size_t)blockIdx.y * L.frame;
+  const int* tab = (const int*)(mine + L.table);
+  int16_t* coef = (int16_t*)(mine + L.coef);
+  const uint32_t len = (uint32_t)tab[JPGD_T_LEN], S = (uint32_t)tab[JPGD_T_S];
+  const int nsub = tab[JPGD_T_NSUB], i = blockIdx.x * kJpgdLanes + lane;
+  const long long zero_from = tab[JPGD_T_ZERO];
+  const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
+  if (i < nsub) {
+    const int* e = tab + JPGD_T_HEADER + i * JPGD_T_LANE;
+    const long long first = (uint32_t)e[2];
+    if ((uint32_t)e[0] != kJpgdDead && first < L.nblocks) {
+      jpgd_word* row = rows + lane * kJpgdRowDwords;
+      JpgdRun x{(uint32_t)e[0], e[1], 0u, {e[3], e[4], e[5]}};
+      JpgdRaw b;
+      bool bad = false;
+      jpgd_sync_run(b, mine + L.unst, len, jpgd_sync_end((uint32_t)i, S, len), i == nsub - 1, (uint32_t)(L.nblocks - first), plan[JPGD_P_HS] * plan[JPGD_P_VS],
+                    plan[JPGD_P_BPM], x, [&](JpgdRaw& bits, int c, int32_t& pred, uint32_t k) {
+                      jpgd_word* r = row;  // the captured pointer, once
+#pragma unroll
+                      for (int w = 0; w < 32; ++w) r[w] = 0;
+                      if (!jpgd_block(bits, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pred, (jpgd_half*)r)) {
+                        bad = true;
+                        return false;
+                      }
+                      uint4* dst = (uint4*)(coef + (size_t)(first + k) * 64);
+#pragma unroll
+                      for (int w = 0; w < 8; ++w) dst[w] = uint4{(unsigned)r[4 * w], (unsigned)r[4 * w + 1], (unsigned)r[4 * w + 2], (unsigned)r[4 * w + 3]};
+                      return true;
+                    });
+      int st = jpgd_past_end(b) ? JPGD_ST_PAST_END : 0;
+      if (bad) {
+        st |= JPGD_ST_BAD_CODE;
+        if (zero_from == L.nblocks)  // died behind the data
+          for (long long g = first + x.n; g < L.nblocks; ++g)
+#pragma unroll
+            for (int w = 0; w < 8; ++w) ((uint4*)(coef + (size_t)g * 64))[w] = zero4;
+      }
+      if (st) atomicOr(status + f, st);
+    }
+  }
+  for (long long g = zero_from + i; g < L.nblocks; g += (long long)gridDim.x * kJpgdLanes)
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ((uint4*)(coef + (size_t)g * 64))[w] = zero4;
 }
 
 __global__ __launch_bounds__(kJpgdIdctBlocks * 8) void jpgd_idct_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {

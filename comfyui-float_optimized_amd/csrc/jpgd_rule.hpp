@@ -33,7 +33,9 @@ enum {
   JPGD_P_SETS,     // word index of table set 0
   JPGD_P_HEADER = 16
 };
-enum { JPGD_F_SCAN0 = 0, JPGD_F_SCAN1, JPGD_F_SPAN, JPGD_F_NINT, JPGD_F_SET, JPGD_F_INTS = 8 };  // scan bytes [SCAN0, SCAN1) of the file; MCUs per interval
+// scan bytes [SCAN0, SCAN1) of the file; MCUs per interval; ROUTE: 0 = one lane per restart interval, else the sync route (below) with
+// that many bytes as its shortest subsequence
+enum { JPGD_F_SCAN0 = 0, JPGD_F_SCAN1, JPGD_F_SPAN, JPGD_F_NINT, JPGD_F_SET, JPGD_F_ROUTE, JPGD_F_INTS = 8 };
 constexpr int32_t kJpgdMagic = 0x4A504744;
 // a Huffman table: look[512] uint16 (length << 8 | symbol of every 9-bit prefix, 0: longer or none), maxcode[18], valoff[18], vals[256] uint8
 constexpr int kJpgdHuffLook = 0, kJpgdHuffMax = 256, kJpgdHuffOff = 274, kJpgdHuffVals = 292, kJpgdHuffInts = 356;
@@ -80,11 +82,36 @@ JPGD_HD void jpgd_fill(JpgdBits& b) {  // at least 57 unread bits afterwards
     b.n += 8;
   }
 }
-JPGD_HD uint32_t jpgd_peek(const JpgdBits& b, int k) { return (uint32_t)(b.acc >> (b.n - k)) & ((1u << k) - 1u); }  // 1 <= k <= 16 <= n
+template <class B>
+JPGD_HD uint32_t jpgd_peek(const B& b, int k) { return (uint32_t)(b.acc >> (b.n - k)) & ((1u << k) - 1u); }  // 1 <= k <= 16 <= n
 JPGD_HD bool jpgd_past_end(const JpgdBits& b) { return (uint64_t)b.over * 8 > (uint64_t)b.n; }  // a supplied zero bit was consumed
 
+// The same reader over bytes that hold no stuffing any more (the sync route's copy of a scan): a position is one integer, a bit
+// offset.  u[at] is the next byte to load, zeros from u[len] on.
+struct JpgdRaw {
+  const uint8_t* u;
+  uint32_t at, len;
+  uint64_t acc;
+  int n;
+};
+JPGD_HD void jpgd_raw_open(JpgdRaw& b, const uint8_t* u, uint32_t len, uint32_t bit) {
+  b.u = u, b.len = len, b.at = bit >> 3, b.acc = 0, b.n = 0;
+  if (bit & 7u) b.acc = b.at < len ? u[b.at] : 0u, ++b.at, b.n = 8 - (int)(bit & 7u);  // the byte's read bits stay above the low n
+}
+JPGD_HD void jpgd_fill(JpgdRaw& b) {
+  while (b.n <= 56) {
+    const uint32_t v = b.at < b.len ? b.u[b.at] : 0u;
+    ++b.at;
+    b.acc = (b.acc << 8) | v;
+    b.n += 8;
+  }
+}
+JPGD_HD uint32_t jpgd_raw_pos(const JpgdRaw& b) { return 8u * b.at - (uint32_t)b.n; }  // the next unread bit
+JPGD_HD bool jpgd_past_end(const JpgdRaw& b) { return 8ull * b.at - (uint64_t)b.n > 8ull * b.len; }  // JpgdBits' rule: over = at - len
+
 // one symbol (needs 16 unread bits); -1 for a code that matches none
-JPGD_HD int jpgd_symbol(JpgdBits& b, const JpgdHuff& t) {
+template <class B>
+JPGD_HD int jpgd_symbol(B& b, const JpgdHuff& t) {
   const uint32_t e = t.look[jpgd_peek(b, 9)];
   if (e) {
     b.n -= (int)(e >> 8);
@@ -98,7 +125,8 @@ JPGD_HD int jpgd_symbol(JpgdBits& b, const JpgdHuff& t) {
   return sym;
 }
 // s more bits (s <= 15, after jpgd_symbol's 16 of one fill) as the signed value of category s
-JPGD_HD int32_t jpgd_extend(JpgdBits& b, int s) {
+template <class B>
+JPGD_HD int32_t jpgd_extend(B& b, int s) {
   if (s == 0) return 0;
   const int32_t r = (int32_t)jpgd_peek(b, s);
   b.n -= s;
@@ -107,8 +135,8 @@ JPGD_HD int32_t jpgd_extend(JpgdBits& b, int s) {
 
 // One block: 64 coefficients in natural order into coef[0 ... 63] (zeroed by the caller), NOT dequantised - a 16-bit table entry
 // times a coefficient needs the int32 the IDCT multiplies in.  false: a bad code or an overflowing run.
-template <class P>
-JPGD_HD bool jpgd_block(JpgdBits& b, const JpgdHuff& dc, const JpgdHuff& ac, int32_t& pred, P coef) {
+template <class B, class P>
+JPGD_HD bool jpgd_block(B& b, const JpgdHuff& dc, const JpgdHuff& ac, int32_t& pred, P coef) {
   jpgd_fill(b);
   int s = jpgd_symbol(b, dc);
   if (s < 0) return false;
@@ -132,6 +160,64 @@ JPGD_HD bool jpgd_block(JpgdBits& b, const JpgdHuff& dc, const JpgdHuff& ac, int
     ++k;
   }
   return true;
+}
+
+// ---------------------------------------------------------------- the sync route: one scan without restart markers, many lanes
+// The scan's one segment is copied without its stuffing and cut into n_sub subsequences of S bytes; lane i OWNS the blocks whose
+// first bit lies in subsequence i and decodes an owned block to its end.  Between blocks the decoder's state is (p, j): the
+// bit offset of the next block and that block's index inside the MCU; kJpgdDead for p says that a bad code was met.  Lanes
+// guess an entry state, decode, and decode again from their predecessor's exit until no exit changes: Huffman streams fall
+// into step, and lane i's entry is the serial chain's after round i at the latest.  A dead exit may be a wrong guess's: lane i
+// takes it over in round i, when it is final, and keeps its own entry until then.
+constexpr uint32_t kJpgdDead = 0xFFFFFFFFu;
+constexpr int kJpgdSyncLanes = 1024;        // subsequences of a scan, at most
+constexpr int kJpgdSyncBytes = 64;          // the default shortest subsequence
+constexpr int kJpgdSyncMaxBytes = 65536;    // the longest a caller may ask for
+constexpr int32_t kJpgdSyncScan = 1 << 28;  // scans from here on stay on the interval route: a bit offset is a uint32_t
+// the lane table in `work`: a header, then per lane (entry p, entry j, first block, pred[3])
+enum { JPGD_T_LEN = 0, JPGD_T_S, JPGD_T_NSUB, JPGD_T_ZERO, JPGD_T_ROUNDS, JPGD_T_HEADER = 8, JPGD_T_LANE = 6 };
+constexpr int kJpgdTableInts = JPGD_T_HEADER + kJpgdSyncLanes * JPGD_T_LANE;
+
+JPGD_HD uint32_t jpgd_sync_sub(uint32_t len, uint32_t sync_bytes) {  // S
+  const uint32_t s = (len + kJpgdSyncLanes - 1) / kJpgdSyncLanes;
+  return s > sync_bytes ? s : sync_bytes;
+}
+JPGD_HD uint32_t jpgd_sync_lanes(uint32_t len, uint32_t S) { return len ? (len + S - 1) / S : 1u; }  // n_sub <= kJpgdSyncLanes
+JPGD_HD uint32_t jpgd_sync_end(uint32_t i, uint32_t S, uint32_t len) { return 8u * ((i + 1) * S < len ? (i + 1) * S : len); }  // lane i's last bit + 1
+
+struct JpgdNoCoef {  // a block that is decoded and not kept
+  struct Sink {
+    JPGD_HD void operator=(int16_t) {}
+  };
+  JPGD_HD Sink operator[](int) const { return Sink(); }
+};
+struct JpgdRun {
+  uint32_t p;     // in: the entry's bit offset.  out: where the first block starts that is not this run's, or kJpgdDead
+  int32_t j;      // ... and that block's index inside the MCU
+  uint32_t n;     // out: blocks decoded well
+  int32_t dc[3];  // in: the predictions.  out: after the last block (from 0: the wrap-around sums of the DC differences)
+};
+// The blocks from state (x.p, x.j) that start before bit `end` - all of them for `tail`, which reads zero bits from the end
+// of the data on - and at most `room` blocks.  block(b, component, prediction, k) decodes the run's k-th block.
+template <class F>
+JPGD_HD void jpgd_sync_run(JpgdRaw& b, const uint8_t* u, uint32_t len, uint32_t end, bool tail, uint32_t room, int hv, int bpm, JpgdRun& x, F&& block) {
+  x.n = 0;
+  if (x.p == kJpgdDead) {
+    x.j = 0;
+    return;
+  }
+  jpgd_raw_open(b, u, len, x.p);
+  while ((x.p < end || tail) && x.n < room) {
+    const int c = x.j < hv ? 0 : x.j - hv + 1;
+    int32_t& pr = c == 0 ? x.dc[0] : c == 1 ? x.dc[1] : x.dc[2];
+    if (!block(b, c, pr, x.n)) {
+      x.p = kJpgdDead, x.j = 0;
+      return;
+    }
+    ++x.n;
+    x.j = x.j + 1 == bpm ? 0 : x.j + 1;
+    x.p = jpgd_raw_pos(b);
+  }
 }
 
 // ---------------------------------------------------------------- jidctint.c ("islow"): one 8-point pass

@@ -135,12 +135,29 @@ def host_files(files):
     return data, torch.tensor(edges, dtype=torch.int64)
 
 
+ENTROPY = {None: 0, "interval": 0, "sync": 1, "auto": 2}
+
+
+def entropy_id(entropy, sync_bytes=None):
+    """(entropy, sync_bytes) of the decode calls -> float_jpg_decode_plan_entropy's two integers.  entropy: None or "interval" (a
+    lane per restart interval), "sync" (every frame WITHOUT restart markers has its scan cut into up to 1024 subsequences that
+    as many lanes decode, bit for bit the serial result) or "auto" (sync for such frames from 64 KB of scan on).  sync_bytes:
+    the shortest subsequence, 1 ... 65536; None is the library's default."""
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be None, \"interval\", \"sync\" or \"auto\" (got %r)" % (entropy,))
+    if sync_bytes is not None and (isinstance(sync_bytes, bool) or not isinstance(sync_bytes, int) or not 1 <= sync_bytes <= 65536):
+        raise ValueError("sync_bytes must be None or an int in 1 ... 65536 (got %r)" % (sync_bytes,))
+    return ENTROPY[entropy], 0 if sync_bytes is None else sync_bytes
+
+
 class JpegPlan:
     """float_jpg_decode_plan of n files in host memory (data, offsets as host_files gives them): `.ints` the plan as an int32 host
     tensor cut to the words in use, and n, h, w, components, sampling, group.  No GPU is needed; what float_jpg_decode_plan
-    refuses is a ValueError naming the frame."""
+    refuses is a ValueError naming the frame.  entropy, sync_bytes: entropy_id's; anything but None / "interval" goes through
+    float_jpg_decode_plan_entropy, and a plan in which no frame takes the sync route is the plain plan word for word."""
 
-    def __init__(self, data, offsets):
+    def __init__(self, data, offsets, entropy=None, sync_bytes=None):
+        route, sync = entropy_id(entropy, sync_bytes)
         if data.is_cuda or offsets.is_cuda or data.dtype != torch.uint8 or offsets.dtype != torch.int64 or data.dim() != 1 or offsets.dim() != 1:
             raise ValueError("JpegPlan takes a 1-d uint8 host tensor and 1-d int64 host offsets")
         data, offsets = data.contiguous(), offsets.contiguous()
@@ -149,18 +166,19 @@ class JpegPlan:
             raise ValueError("JpegPlan: %d offsets over %d bytes" % (offsets.numel(), data.numel()))
         L = native.lib()
         ints = torch.empty(int(L.float_jpg_decode_plan_ints(n)), dtype=torch.int32)
-        native.check(L.float_jpg_decode_plan(C.c_void_p(data.data_ptr()), C.c_void_p(offsets.data_ptr()), n, C.c_void_p(ints.data_ptr()),
-                                             ints.numel()))
+        args = (C.c_void_p(data.data_ptr()), C.c_void_p(offsets.data_ptr()), n, C.c_void_p(ints.data_ptr()), ints.numel())
+        native.check(L.float_jpg_decode_plan_entropy(*args, route, sync) if route else L.float_jpg_decode_plan(*args))
         self.ints = ints[:int(ints[1])].clone()
         self.n, self.h, self.w, self.components = (int(v) for v in self.ints[2:6])
         self.sampling, self.group = (int(self.ints[6]), int(self.ints[7])), int(self.ints[13])
         self.work_bytes = int(L.float_jpg_decode_work_bytes(C.c_void_p(self.ints.data_ptr())))
 
 
-def decode_jpeg_host(files):
-    """float_jpg_decode_host: the kernels' rule run on the host, no GPU -> ((n, H, W, 3) uint8 host tensor, (n,) int32 status)."""
+def decode_jpeg_host(files, entropy=None, sync_bytes=None):
+    """float_jpg_decode_host: the kernels' rule run on the host, no GPU -> ((n, H, W, 3) uint8 host tensor, (n,) int32 status).
+    entropy, sync_bytes: as in decode_jpeg_device; the sync route's steps then run with its lanes as a loop."""
     data, offsets = host_files(files)
-    plan = JpegPlan(data, offsets)
+    plan = JpegPlan(data, offsets, entropy, sync_bytes)
     out = torch.empty(plan.n, plan.h, plan.w, 3, dtype=torch.uint8)
     status = torch.empty(plan.n, dtype=torch.int32)
     native.check(native.lib().float_jpg_decode_host(C.c_void_p(data.data_ptr()), C.c_void_p(offsets.data_ptr()), C.c_void_p(plan.ints.data_ptr()),
@@ -192,14 +210,18 @@ STATUS_BITS = {1: "a code that matches no symbol or a run past coefficient 63", 
 
 
 @torch.no_grad()
-def decode_jpeg_device(files, offsets=None, strict=True, out=None, device=None, return_status=False):
+def decode_jpeg_device(files, offsets=None, strict=True, out=None, device=None, return_status=False, entropy=None, sync_bytes=None):
     """float_jpg_decode: baseline JPEG files -> (T, H, W, 3) uint8 frames on the device, frame i bitwise
     host_models.jpeg_decode_rgb8(file i) (which states what is accepted and the arithmetic; a valid file decodes as libjpeg-turbo
     decodes it).  files: a JpegFrames, a list of bytes-likes - planned on the host and uploaded as files, so only the files' bytes
     (and a plan of a few KB) cross PCIe - or a 1-d uint8 DEVICE tensor with `offsets` ((T + 1,) int64, host or device), the layout
     encode_jpeg_device returns: the headers are then read back for planning (one synchronising copy of the files to the host).
-    All files of a call share size, components and sampling; tables and restart intervals may differ.  A file without restart
-    markers is decoded by a single lane: supported, and slow - one interval per MCU row is what the encoder here writes.
+    All files of a call share size, components and sampling; tables and restart intervals may differ.
+    entropy: None or "interval" gives every restart interval a lane, so a file without restart markers - what ffmpeg, Pillow
+    and most cameras write - is decoded by a single lane; "sync" cuts such a file's scan into up to 1024 subsequences, decoded
+    by as many lanes that fall into step with the serial decode (entropy_id; three more launches per group, the same bytes);
+    "auto" does so from 64 KB of scan on.  Files with restart markers take the interval route whatever entropy says.
+    sync_bytes: the shortest subsequence (None: the library's default).
     strict: a frame whose status word is not 0 raises ValueError naming the first such frame (one read-back of T words, which
     synchronises); strict=False returns the definition's pixels for damaged frames too and reads nothing back.
     out: a (T, H, W, 3) uint8 device tensor to write into.  return_status=True: (frames, (T,) int32 device tensor)."""
@@ -215,7 +237,7 @@ def decode_jpeg_device(files, offsets=None, strict=True, out=None, device=None, 
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         data, edges = host_files(files)
         data_dev = None
-    plan = JpegPlan(data, edges)
+    plan = JpegPlan(data, edges, entropy, sync_bytes)
     shape = (plan.n, plan.h, plan.w, 3)
     if out is not None and (not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()):
         raise ValueError("decode_jpeg_device: out must be a contiguous %s uint8 tensor on the GPU" % (shape,))

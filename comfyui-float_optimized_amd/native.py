@@ -172,6 +172,7 @@ _SIGNATURES = {
     "float_jpg_encode_padded": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_jpg_decode_plan_ints": (C.c_size_t, [C.c_int32]),
     "float_jpg_decode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
+    "float_jpg_decode_plan_entropy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32]),
     "float_jpg_decode_work_bytes": (C.c_size_t, [C.c_void_p]),
     "float_jpg_decode": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_jpg_decode_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),

@@ -629,7 +629,7 @@ class InferenceAgent:
                                           index, None if rows is None else crop, smooth, main_logger)
         return [tuple(int(v) for v in row) for row in rects]
 
-    def _align_driving_jpeg(self, video, crop, detect_every, smooth, margin, index, rects, chunk):
+    def _align_driving_jpeg(self, video, crop, detect_every, smooth, margin, index, rects, chunk, entropy=None):
         """align_driving for a Motion-JPEG clip: a jpeg.JpegFrames, a host_models.AviMjpegReader, or the path of an .avi.  The
         files cross PCIe as they are, `chunk` at a time; float_jpg_decode turns them into uint8 frames in one reused device
         buffer, which float_img_front_frames reads as it reads an uploaded chunk.  Frames the detector is to see are decoded
@@ -639,12 +639,13 @@ class InferenceAgent:
         rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
         opened = host_models.AviMjpegReader(video) if isinstance(video, (str, os.PathLike)) else None
         try:
-            return self._align_driving_files(video if opened is None else opened, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg)
+            return self._align_driving_files(video if opened is None else opened, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg,
+                                             entropy)
         finally:
             if opened is not None:
                 opened.close()
 
-    def _align_driving_files(self, video, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg):
+    def _align_driving_files(self, video, crop, detect_every, smooth, margin, index, rects, chunk, size, rgba, bkg, entropy=None):
         """_align_driving_jpeg on a JpegFrames (in host memory as it is) or an open AviMjpegReader, which is read `chunk` frames at
         a time: the host holds one chunk of files, the device one chunk of frames, whatever the clip's length."""
         if isinstance(video, host_models.AviMjpegReader):
@@ -661,7 +662,8 @@ class InferenceAgent:
         H, Wd = first.h, first.w
         self.to_target()
         rects = self._driving_clip_rects(T, H, Wd, rects, crop, detect_every, smooth, margin, index,
-                                         lambda idx: (jpeg.decode_jpeg_device([bytes(part(i, i + 1)[0]) for i in idx], device=self.rank), list(range(len(idx)))))
+                                         lambda idx: (jpeg.decode_jpeg_device([bytes(part(i, i + 1)[0]) for i in idx], device=self.rank, entropy=entropy),
+                                                      list(range(len(idx)))))
         out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=self.rank)
         dev = torch.device("cuda", self.rank) if isinstance(self.rank, int) else torch.device(self.rank)
         status = torch.empty(T, dtype=torch.int32, device=dev)
@@ -671,7 +673,7 @@ class InferenceAgent:
             for at in range(0, T, chunk):
                 n = min(chunk, T - at)
                 data, edges = jpeg.host_files(part(at, at + n))
-                plan = jpeg.JpegPlan(data, edges)
+                plan = jpeg.JpegPlan(data, edges, entropy)
                 if (plan.h, plan.w) != (H, Wd):
                     raise ValueError("align_driving: frame %d is %d x %d, the clip's first frame %d x %d" % (at, plan.h, plan.w, H, Wd))
                 work, _ = jpeg.enqueue_decode(data.to(dev, non_blocking=True), edges.to(dev, non_blocking=True), plan, buf[:n], status[at:at + n], work)
@@ -680,7 +682,7 @@ class InferenceAgent:
         return out, rects
 
     @torch.no_grad()
-    def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32):
+    def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32, entropy=None):
         """A raw driving video -> the frames drive_device takes: video (T, H, W, 3|4), fp32 in [0, 1] or uint8, on the host or on
         the device -> (frames_u8 (T, size, size, 3) uint8 on the device, rects = T tuples (x, y, w, h) in source coordinates).
         Frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(video[t], ...), rects[t], size, size)
@@ -695,12 +697,15 @@ class InferenceAgent:
         video may also be a Motion-JPEG clip - a jpeg.JpegFrames, a host_models.AviMjpegReader or the path of an .avi (what
         write_video and AviMjpegWriter write, or an ffmpeg / webcam MJPEG capture): the files cross PCIe compressed, `chunk` at a
         time, float_jpg_decode makes the uint8 frames in the reused device buffer, and the result is bit for bit align_driving on
-        host_models.jpeg_decode_rgb8 of every frame.  A damaged frame (a non-zero status word) is a ValueError naming it."""
+        host_models.jpeg_decode_rgb8 of every frame.  A damaged frame (a non-zero status word) is a ValueError naming it.
+        entropy: jpeg.decode_jpeg_device's, for such a clip - "sync" or "auto" spread a frame WITHOUT restart markers (ffmpeg's
+        and most cameras' files) over up to 1024 lanes, where None decodes it on one; the frames are the same bytes."""
+        jpeg.entropy_id(entropy)
         o = self.opt
         size = int(o.input_size)
         rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
         if not isinstance(video, torch.Tensor):
-            return self._align_driving_jpeg(video, crop, detect_every, smooth, margin, index, rects, max(1, int(chunk)))
+            return self._align_driving_jpeg(video, crop, detect_every, smooth, margin, index, rects, max(1, int(chunk)), entropy)
         if video.dim() != 4 or video.shape[-1] not in (3, 4) or 0 in video.shape or not (video.dtype == torch.uint8 or video.is_floating_point()):
             raise ValueError("align_driving: video must be (T, H, W, 3|4) uint8 or float, got %s %s" % (video.dtype, tuple(video.shape)))
         T, H, Wd, ch = (int(v) for v in video.shape)
@@ -722,16 +727,16 @@ class InferenceAgent:
 
     @torch.no_grad()
     def drive_video(self, ref_img, video, mode="relative", no_crop=True, crop="fixed", detect_every=5, smooth=25, margin=None, index=1,
-                    rects=None, chunk=32, out=None, out_dtype=None, out_format=None, matrix=None):
+                    rects=None, chunk=32, out=None, out_dtype=None, out_format=None, matrix=None, entropy=None):
         """drive_device from raw inputs: the portrait ref_img (a ComfyUI IMAGE item) goes through host_inputs' image half
         (no_crop as there), the raw driving video through align_driving (crop ... chunk as there), and the two through
         drive_device (mode, out, out_dtype, out_format, matrix as there).  With rects= given it is bit for bit drive_device on
         the definition's crops of the video.  video: a tensor of raw frames, or a Motion-JPEG clip (JpegFrames, AviMjpegReader,
-        the path of an .avi) that is decoded on the device - align_driving has the details."""
+        the path of an .avi) that is decoded on the device - align_driving has the details, and takes `entropy`."""
         self._crop_matrix("drive_video", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
         silence = {"waveform": torch.zeros(1, 1, 16), "sample_rate": self.opt.sampling_rate}  # _host_inputs' audio half: unused
         s = self._host_inputs(ref_img, silence, no_crop, False)[0]
-        frames_u8, _ = self.align_driving(video, crop, detect_every, smooth, margin, index, rects, chunk)
+        frames_u8, _ = self.align_driving(video, crop, detect_every, smooth, margin, index, rects, chunk, entropy)
         return self.drive_device(s, frames_u8, mode, out, out_dtype, out_format, matrix)
 
     def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
+/* Stays 6: float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
  * decoded to 8-bit RGB frames on the device), float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
@@ -834,9 +834,26 @@ int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, in
  * restart interval is then decoded by a lane of its own (DC prediction restarts at a marker), so a file WITHOUT restart markers
  * is one serial chain on one lane - supported, bitwise the definition, and slow; IDCT; upsampling and colour.  Enqueues kernels
  * only: allocates nothing, synchronises nothing, and the only atomics are ORs into the status words, so two calls give equal
- * bytes.  float_jpg_decode_host runs the same rule on the host (everything in host memory; the test and sanitizer path). */
+ * bytes.  float_jpg_decode_host runs the same rule on the host (everything in host memory; the test and sanitizer path).
+ *
+ * float_jpg_decode_plan_entropy is float_jpg_decode_plan with a choice of the entropy route for frames WITHOUT restart markers
+ * (one interval; what ffmpeg, Pillow and most cameras write).  entropy 0: the interval route for every frame, the plan of
+ * float_jpg_decode_plan word for word.  1: the sync route for every frame with one interval and a scan below 256 MiB.  2: for
+ * those whose scan has at least 1024 x 64 bytes.  Frames with more intervals stay on the interval route, and a plan in which no
+ * frame takes the sync route is entropy 0's: the same words, work size and launches.  sync_bytes: the shortest subsequence,
+ * 1 ... 65536, or 0 for the default (64).  The sync route (csrc/jpgd_rule.hpp): the scan's segment is copied without its stuffed
+ * zeros and cut into n_sub <= 1024 subsequences of S = max(sync_bytes, ceil(len / 1024)) bytes; lane i owns the blocks whose
+ * first bit lies in subsequence i.  One workgroup per frame decodes all subsequences from guessed states and then again from
+ * the predecessor's exit state until no exit changes - Huffman streams fall into step after a few symbols, and n_sub rounds
+ * bound the loop whatever the bytes are -, a prefix over the lanes gives each its first block and DC predictions, and a third
+ * launch decodes once more into the coefficient buffer.  Pixels and status words are the interval route's, bit for bit, for
+ * damaged scans too.  Three more kernels per group that holds such a frame; `work` grows by the longest such scan and a lane
+ * table of 24 KB per frame of a group (float_jpg_decode_work_bytes says so); float_jpg_decode_host follows the plan's route with
+ * the lanes as a loop.  An entropy or sync_bytes outside these values is FLOAT_E_INVALID. */
 size_t float_jpg_decode_plan_ints(int32_t n_frames);
 int float_jpg_decode_plan(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints);
+int float_jpg_decode_plan_entropy(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints, int32_t entropy,
+                                  int32_t sync_bytes);
 size_t float_jpg_decode_work_bytes(const int32_t* plan_host);
 int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t* plan, const int32_t* plan_host, int32_t n_frames,
                      uint8_t* rgb8_out, int32_t* status, void* work, size_t work_bytes, void* stream);

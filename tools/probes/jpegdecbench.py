@@ -5,7 +5,11 @@ markers.  All routes interleaved in one process, medians of JPEGDEC_REPS (10) re
   (b) InferenceAgent.drive_video (512-px synthetic model, rects given, wall clock) from: the MJPEG files with restart markers;
       the files without; the raw pageable uint8 host video (the route before this decoder); a Pillow decode loop on the host
       feeding that raw route (the Pillow loop is also reported alone).
-Bytes across PCIe: the files against T x 1080 x 1920 x 3.  JPEGDEC_FRAMES / JPEGDEC_REPS shrink the run for a rehearsal."""
+Bytes across PCIe: the files against T x 1080 x 1920 x 3.  JPEGDEC_FRAMES / JPEGDEC_REPS shrink the run for a rehearsal.
+--entropy sync|auto adds, interleaved with the others: to (a) the clip without restart markers through that entropy route, once per
+value of --sync-bytes (a comma list, default: the library's), with the relaxation's rounds over the last group's frames; to (b)
+drive_video from that clip with entropy= set."""
+import argparse
 import importlib
 import io
 import os
@@ -22,6 +26,11 @@ from tests.util import load_pkg  # noqa: E402
 
 pkg = load_pkg()
 J, Wt = pkg.jpeg, pkg.weights
+ap = argparse.ArgumentParser()
+ap.add_argument("--entropy", choices=("sync", "auto"), default=None)
+ap.add_argument("--sync-bytes", default="")
+args = ap.parse_args()
+SYNC = [int(v) for v in args.sync_bytes.split(",") if v] or [None]
 T, REPS, WARM = int(os.environ.get("JPEGDEC_FRAMES", 250)), int(os.environ.get("JPEGDEC_REPS", 10)), 2
 H, W = 1080, 1920
 RECT = (460, 40, 1000, 1000)
@@ -62,9 +71,12 @@ def wall_ms(fn):
 
 # (a) the decode launches alone
 resident = {}
-for name, jf in clips.items():
-    data, edges = J.host_files(jf)
-    plan = J.JpegPlan(data, edges)
+variants = [(name, name, None, None) for name in clips]
+if args.entropy:
+    variants += [("no restart markers, %s%s" % (args.entropy, "" if S is None else " S=%d" % S), "no restart markers", args.entropy, S) for S in SYNC]
+for name, clip, entropy, S in variants:
+    data, edges = J.host_files(clips[clip])
+    plan = J.JpegPlan(data, edges, entropy, S)
     resident[name] = (data.cuda(), edges.cuda(), plan, torch.empty(plan.n, H, W, 3, dtype=torch.uint8, device="cuda"),
                       torch.empty(plan.n, dtype=torch.int32, device="cuda"), torch.empty(plan.work_bytes, dtype=torch.uint8, device="cuda"))
 ta = {k: [] for k in resident}
@@ -77,6 +89,12 @@ for k, v in ta.items():
     m = statistics.median(v)
     print("(a) decode, %-20s %9.2f ms per clip (spread %.2f) | %.1f GB/s of pixels | equal to the other clip's frames: %s" % (
         k, m, max(v) - min(v), T * H * W * 3 / m / 1e6, torch.equal(resident[k][3], next(iter(resident.values()))[3])))
+    plan, work = resident[k][2], resident[k][5]
+    if int(plan.ints[16:16 + 8 * plan.n].view(-1, 8)[:, 5].max()):  # frames on the sync route: the lane table ends a frame's share of `work`
+        per = plan.work_bytes // min(plan.n, plan.group)
+        rounds = work[:plan.work_bytes].view(-1, per)[:(plan.n - 1) % plan.group + 1, per - 24608:][:, 8:20].contiguous().view(torch.int32).cpu()
+        print("    relaxation: %s lanes, rounds min %d median %d max %d (the last group's frames)" % (
+            sorted(set(rounds[:, 0].tolist())), rounds[:, 2].min(), rounds[:, 2].median(), rounds[:, 2].max()))
 del resident
 
 # (b) through the agent
@@ -100,6 +118,8 @@ drive = lambda v: agent.drive_video(portrait, v, rects=RECT, out_dtype=torch.uin
 routes = {"mjpeg, restart per MCU row": lambda: drive(clips["restart per MCU row"]),
           "mjpeg, no restart markers": lambda: drive(clips["no restart markers"]),
           "raw pageable uint8 video": lambda: drive(video8),
+          **({"mjpeg, no restart markers, " + args.entropy: lambda: agent.drive_video(portrait, clips["no restart markers"], rects=RECT, out_dtype=torch.uint8,
+                                                                                      entropy=args.entropy)} if args.entropy else {}),
           "pillow loop + raw route": lambda: drive(pillow_loop()),
           "pillow loop alone": pillow_loop}
 tb = {k: [] for k in routes}

@@ -16,6 +16,7 @@ out = sys.argv[1]
 os.makedirs(out, exist_ok=True)
 files = [f for sub in ("4:4:4", "4:2:2", "4:2:0", "grey") for size in SIZES for f in case_files(sub, size)]
 files += [f for restart in (0, None, 1) for f in hm.jpeg_encode_rgb8(np.stack([image(48, 64), image(16, 16).repeat(3, 0).repeat(4, 1)]), 90, restart)]
+files += [pil_file(96, 128, sub, 100, None) for sub in ("4:4:4", "4:2:2", "4:2:0", "grey")]  # long scans without markers: --sync 8 needs all 1024 lanes
 for restart in (None, "row"):
     f = pil_file(48, 64, "4:2:0", 90, restart)
     hdr = hm.jpeg_parse_header(f)
