@@ -378,6 +378,34 @@ __device__ __forceinline__ unsigned fh_yuv_plane(const FhYuv& t, int p, int r, i
   return (unsigned)((((w << 22) >> 22) * r + ((w << 12) >> 22) * g + ((w << 2) >> 22) * b + t.bias[p]) >> 8);
 }
 
+// ---------------------------------------------------------------- 8-bit YUV -> 8-bit RGB (the YUV 4:2:0 inputs)
+// host_models.YUV_INVERSE: one row {yoff, cy, crv, cgu, cgv, cbu} per id, each coefficient round(16384 c) of the float64
+// inverse of the matrix above (cy = 255/219 or 1; crv = 2 (1 - Kr) s, cbu = 2 (1 - Kb) s with s = 255/224 or 1; cgu = cbu Kb / Kg,
+// cgv = crv Kr / Kg).  With y = Y - yoff, u = U - 128, v = V - 128, in int32 (every product is below 2^24):
+//   R = clamp8((cy y + crv v + 8192) >> 14), G = clamp8((cy y - cgu u - cgv v + 8192) >> 14), B = clamp8((cy y + cbu u + 8192) >> 14)
+constexpr int kFhYuvInverse[4][6] = {
+    {16, 19077, 26149, 6419, 13320, 33050},  // 0: BT.601 limited
+    {16, 19077, 29372, 3494, 8731, 34610},   // 2: BT.709 limited
+    {0, 16384, 22970, 5638, 11700, 29032},   // 4: BT.601 full
+    {0, 16384, 25802, 3069, 7670, 30402},    // 6: BT.709 full
+};
+// What a kernel gets, by value among its arguments (uniform, like FhYuv).
+struct FhYuvInv {
+  int32_t yoff, cy, crv, cgu, cgv, cbu;
+};
+inline bool fh_yuv_inverse_of(int32_t matrix, FhYuvInv* t) {
+  if (matrix & ~6) return false;
+  const int* r = kFhYuvInverse[matrix >> 1];
+  *t = FhYuvInv{r[0], r[1], r[2], r[3], r[4], r[5]};
+  return true;
+}
+// one pixel: Y, U, V bytes -> the packed RGB dword (r | g << 8 | b << 16)
+__device__ __forceinline__ unsigned fh_yuv_to_rgb(const FhYuvInv& t, int Y, int U, int V) {
+  const int y = t.cy * (Y - t.yoff) + 8192, u = U - 128, v = V - 128;
+  const int r = (y + t.crv * v) >> 14, g = (y - t.cgu * u - t.cgv * v) >> 14, b = (y + t.cbu * u) >> 14;
+  return (unsigned)min(max(r, 0), 255) | ((unsigned)min(max(g, 0), 255) << 8) | ((unsigned)min(max(b, 0), 255) << 16);
+}
+
 // ---------------------------------------------------------------- cross-lane reductions without LDS
 // __shfl_xor compiles to ds_bpermute_b32: an LDS-pipe round trip and an s_waitcnt lgkmcnt(0) per butterfly step.  The forms
 // below deliver the same operands to the same additions through the VALU's own lane crossbars (DPP, v_permlane*_swap), so

@@ -76,9 +76,9 @@ int float_img_front_frames(const void* frames, int32_t n_frames, int32_t src_h, 
     const dim3 grid(tiles.x, tiles.y, (unsigned)nb);
     const size_t lds = (size_t)kImgvWaves * a.stage_px * sizeof(unsigned);  // <= 64 KiB
     if (u8)
-      hipLaunchKernelGGL(imgv_frames_kernel<true>, grid, dim3(kImgvCols * kImgvWaves), lds, s, a);
+      hipLaunchKernelGGL(imgv_frames_kernel<ImgvSrcU8>, grid, dim3(kImgvCols * kImgvWaves), lds, s, a);
     else
-      hipLaunchKernelGGL(imgv_frames_kernel<false>, grid, dim3(kImgvCols * kImgvWaves), lds, s, a);
+      hipLaunchKernelGGL(imgv_frames_kernel<ImgvSrcF32>, grid, dim3(kImgvCols * kImgvWaves), lds, s, a);
   }
   FH_CHECK_HIP(hipGetLastError());
   return FLOAT_OK;

@@ -26,6 +26,8 @@
 //   with packed fp32 instructions turned off (FLAGS_imgv_api, as the motion pass): the quantiser of a float4 is four independent
 //   multiplications that the compiler would otherwise pair into v_pk_mul_f32, and the result has to be the definition's bit for
 //   bit on every pixel; the scalar form costs nothing next to the loads.  imgf_api is left as it has been built and tested.
+// How a source row's span gets into the slice is a source policy (ImgvSrcF32, ImgvSrcU8 below; ImgySrc in imgy_kernels.hpp for
+//   YUV 4:2:0): a template parameter of the kernel, so that the area and linear loops exist once.
 #pragma once
 #include "imgf_rule.hpp"
 
@@ -85,24 +87,58 @@ struct ImgvTaps {
   int w_lo, w_hi;  // linear: their weights P - f and f
 };
 
+// A source policy says how one source row's span becomes packed RGB dwords in the wave's LDS slice; everything after that - the
+// taps, the sums, the totals - is the same code for every source.  A policy has: Args, the kernel's argument struct, and
+// common(args), the ImgvArgs in it; slice(args), the dwords of LDS a wave owns (its first stage_px are the RGB slice, the rest
+// the policy's own); first_col(c), the first source column that is staged for a span that begins at c (a policy may begin
+// earlier, inside the image); a constructor (args, frame of the block, plan, the wave's own LDS); and stage(px, lane, row, col0,
+// n), which writes pixels col0 ... col0 + n - 1 of source row `row` (all inside the image) to px[0 ... n - 1].  stage may keep
+// state between rows (imgy_kernels.hpp keeps chroma rows); the wave-level barrier after it is the caller's.
+struct ImgvSrcF32 {
+  using Args = ImgvArgs;
+  __device__ static const ImgvArgs& common(const Args& a) { return a; }
+  __device__ static int slice(const Args& a) { return a.stage_px; }
+  __device__ static int first_col(int c) { return c; }
+  const float* frame;
+  const ImgfPlan& p;
+  __device__ ImgvSrcF32(const Args& a, int fr, const ImgfPlan& plan, unsigned*)
+      : frame((const float*)a.frames + (size_t)fr * a.src_h * a.src_w * a.channels), p(plan) {}
+  __device__ __forceinline__ void stage(unsigned* px, int lane, int row, int col0, int n) {
+    const size_t at = (size_t)row * p.x.src + col0;
+    for (int k = lane; k < n; k += kImgvCols) px[k] = imgf_pixel(frame, at + k, p);
+  }
+};
+
+struct ImgvSrcU8 {
+  using Args = ImgvArgs;
+  __device__ static const ImgvArgs& common(const Args& a) { return a; }
+  __device__ static int slice(const Args& a) { return a.stage_px; }
+  __device__ static int first_col(int c) { return c; }
+  const unsigned char* frame;
+  const ImgfPlan& p;
+  uintptr_t safe_lo, safe_hi;  // the aligned part of the block's frames
+  __device__ ImgvSrcU8(const Args& a, int fr, const ImgfPlan& plan, unsigned*)
+      : frame((const unsigned char*)a.frames + (size_t)fr * a.src_h * a.src_w * a.channels),
+        p(plan),
+        safe_lo(((uintptr_t)a.frames + 3) & ~(uintptr_t)3),
+        safe_hi(((uintptr_t)a.frames + a.bytes) & ~(uintptr_t)3) {}
+  __device__ __forceinline__ void stage(unsigned* px, int lane, int row, int col0, int n) {
+    const size_t at = (size_t)row * p.x.src + col0;
+    for (int k = lane; k < n; k += kImgvCols) px[k] = imgv_pixel_u8(frame, at + k, p, safe_lo, safe_hi);
+  }
+};
+
 // Stages the tile's span of window row `i` (wave-uniform) chunk by chunk into `px` and returns lane d's three int32 sums in h.
 // s_lo, n_tot: the source columns of the span that lie in the image, [s_lo, s_lo + n_tot).
-template <bool U8>
-__device__ __forceinline__ void imgv_row_sums(const void* __restrict__ frame, unsigned* px, int lane, int i, const ImgfPlan& p,
-                                              const ImgvTaps& t, int s_lo, int n_tot, int stage_px, uintptr_t safe_lo, uintptr_t safe_hi,
-                                              int h[3]) {
+template <class Src>
+__device__ __forceinline__ void imgv_row_sums(Src& src, unsigned* px, int lane, int i, const ImgfPlan& p, const ImgvTaps& t, int s_lo,
+                                              int n_tot, int stage_px, int h[3]) {
   h[0] = h[1] = h[2] = 0;
   const int row = p.y.off + i;
   if ((unsigned)row >= (unsigned)p.y.src) return;  // a row of the zero border: nothing is loaded
-  const size_t row_px = (size_t)row * p.x.src + s_lo;
   for (int k0 = 0; k0 < n_tot; k0 += stage_px) {
     const int n_stage = min(stage_px, n_tot - k0);
-    for (int k = lane; k < n_stage; k += kImgvCols) {
-      if constexpr (U8)
-        px[k] = imgv_pixel_u8((const unsigned char*)frame, row_px + k0 + k, p, safe_lo, safe_hi);
-      else
-        px[k] = imgf_pixel((const float*)frame, row_px + k0 + k, p);
-    }
+    src.stage(px, lane, row, s_lo + k0, n_stage);
     __builtin_amdgcn_wave_barrier();
     __threadfence_block();
     // window sample s sits at px[s + sh]; anything outside [0, n_stage) is the zero border or another chunk
@@ -127,16 +163,17 @@ __device__ __forceinline__ void imgv_row_sums(const void* __restrict__ frame, un
   }
 }
 
-// dynamic LDS: kImgvWaves slices of a.stage_px dwords
-template <bool U8>
-__global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(const ImgvArgs a) {
+// dynamic LDS: kImgvWaves slices of Src::slice(args) dwords
+template <class Src>
+__global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(const typename Src::Args args) {
+  const ImgvArgs& a = Src::common(args);
   extern __shared__ __attribute__((aligned(16))) unsigned imgv_lds[];
   const int lane = threadIdx.x & (kImgvCols - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kImgvCols);
   const int fr = blockIdx.z;
   const int oy_lo = blockIdx.y * kImgvRows + wave * kImgvBand, oy_hi = min(oy_lo + kImgvBand, a.dst_h);
   if (oy_lo >= oy_hi) return;  // wave-uniform, and no barrier of the workgroup follows
-  unsigned* px = imgv_lds + (size_t)wave * a.stage_px;
+  unsigned* px = imgv_lds + (size_t)wave * Src::slice(args);
 
   // the frame's plan
   ImgfPlan p{};
@@ -153,7 +190,7 @@ __global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(cons
   int first, last, tmp;
   imgf_span(p.x, p.linear, d0, &first, &tmp);
   imgf_span(p.x, p.linear, d1, &tmp, &last);
-  const int s_lo = max(0, p.x.off + first);
+  const int s_lo = Src::first_col(max(0, p.x.off + first));
   const int n_tot = max(0, min(p.x.src, p.x.off + last + 1) - s_lo);  // 0: the tile reads the border only
   ImgvTaps t{};
   long long len_x = (long long)p.x.P;  // the divisor's x factor
@@ -171,10 +208,7 @@ __global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(cons
     t.lo = 0, t.hi = -1;  // no column: no taps (linear: both weights are 0)
   }
 
-  const size_t frame_elems = (size_t)a.src_h * a.src_w * a.channels;
-  const void* frame = U8 ? (const void*)((const unsigned char*)a.frames + (size_t)fr * frame_elems)
-                         : (const void*)((const float*)a.frames + (size_t)fr * frame_elems);
-  const uintptr_t safe_lo = ((uintptr_t)a.frames + 3) & ~(uintptr_t)3, safe_hi = ((uintptr_t)a.frames + a.bytes) & ~(uintptr_t)3;
+  Src src(args, fr, p, px + a.stage_px);
   unsigned char* out = a.out + ((size_t)fr * a.dst_h * a.dst_w + d) * 3;
   auto finish = [&](int oy, const long long S[3], long long D) {
     if (d > d1) return;
@@ -193,14 +227,14 @@ __global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(cons
         if (s0 == ib) {
           ha[0] = hb[0], ha[1] = hb[1], ha[2] = hb[2];
         } else {
-          imgv_row_sums<U8>(frame, px, lane, s0, p, t, s_lo, n_tot, a.stage_px, safe_lo, safe_hi, ha);
+          imgv_row_sums(src, px, lane, s0, p, t, s_lo, n_tot, a.stage_px, ha);
         }
         ia = s0;
       }
       if (s1 == ia) {
         hb[0] = ha[0], hb[1] = ha[1], hb[2] = ha[2];
       } else if (s1 != ib) {
-        imgv_row_sums<U8>(frame, px, lane, s1, p, t, s_lo, n_tot, a.stage_px, safe_lo, safe_hi, hb);
+        imgv_row_sums(src, px, lane, s1, p, t, s_lo, n_tot, a.stage_px, hb);
       }
       ib = s1;
       long long S[3];
@@ -216,7 +250,7 @@ __global__ __launch_bounds__(kImgvCols* kImgvWaves) void imgv_frames_kernel(cons
   int c0 = oy * p.y.P, c1 = min(c0 + p.y.P, p.y.n * p.y.Q);
   long long S[3] = {0, 0, 0};
   for (int i = c0 / p.y.Q; oy < oy_hi; ++i) {
-    imgv_row_sums<U8>(frame, px, lane, i, p, t, s_lo, n_tot, a.stage_px, safe_lo, safe_hi, h);
+    imgv_row_sums(src, px, lane, i, p, t, s_lo, n_tot, a.stage_px, h);
     const int pos = i * p.y.Q;
     while (oy < oy_hi) {
       const int wy = min(pos + p.y.Q, c1) - max(pos, c0);

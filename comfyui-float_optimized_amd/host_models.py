@@ -1138,6 +1138,168 @@ def write_y4m(path_or_file, frames_i420, fps, matrix=None):
         w.write(frames_i420)
 
 
+# The way back, for YUV 4:2:0 frames that arrive (a driving video): one row (yoff, cy, crv, cgu, cgv, cbu) per id of YUV_MATRICES,
+# each coefficient round(16384 c) with c in float64: cy = 255/219 (limited range) or 1 (full); crv = 2 (1 - Kr) s and
+# cbu = 2 (1 - Kb) s with s = 255/224 or 1; cgu = cbu Kb / Kg, cgv = crv Kr / Kg; (Kr, Kb) = (0.299, 0.114) or (0.2126, 0.0722),
+# Kg = 1 - Kr - Kb; yoff = 16 or 0.  With y = Y - yoff, u = U - 128, v = V - 128 in int32, >> the arithmetic shift:
+#     R = clamp8((cy y + crv v + 8192) >> 14)    G = clamp8((cy y - cgu u - cgv v + 8192) >> 14)    B = clamp8((cy y + cbu u + 8192) >> 14)
+# Every product stays below 2^24.  Before the clamp each channel is within 0.5 + 3 * 255 * 0.5 / 16384 = 0.524 of the float64
+# formula (the final rounding plus the coefficients' roundings).  csrc/common.hpp holds the same table (kFhYuvInverse).
+YUV_INVERSE = {
+    0: (16, 19077, 26149, 6419, 13320, 33050),   # BT.601 limited
+    2: (16, 19077, 29372, 3494, 8731, 34610),    # BT.709 limited
+    4: (0, 16384, 22970, 5638, 11700, 29032),    # BT.601 full
+    6: (0, 16384, 25802, 3069, 7670, 30402),     # BT.709 full
+}
+YUV_LAYOUTS = ("i420", "nv12")
+YUV_CHROMA = ("nearest", "centre")
+
+
+def yuv420_check(what, layout, chroma):
+    if layout not in YUV_LAYOUTS:
+        raise ValueError("%s: layout must be one of %s (got %r)" % (what, YUV_LAYOUTS, layout))
+    if chroma not in YUV_CHROMA:
+        raise ValueError("%s: chroma must be one of %s (got %r)" % (what, YUV_CHROMA, chroma))
+
+
+def yuv420_to_rgb8(frames_yuv, layout="i420", matrix=None, chroma="nearest"):
+    """(T, 3H/2, W) or (3H/2, W) uint8 YUV 4:2:0 -> (T, H, W, 3) or (H, W, 3) uint8 RGB, in int32 by the rule above YUV_INVERSE:
+    the definition of float_img_front_frames_yuv's colour conversion.  H and W must be even (ValueError).
+    layout  "i420": the Y plane, then U and V at H/2 x W/2 each - what rgb8_to_i420 writes; "nv12": the Y plane, then H/2 rows of
+            W bytes of interleaved U, V.
+    matrix  as yuv_matrix_id reads it: the matrix the frames were MADE with (None = BT.601 limited range; "auto" by W x H).
+    chroma  how a luma sample gets its U and V.  "nearest": the sample of its 2 x 2 block (OpenCV's I420 / NV12 conversions and
+            swscale's unscaled converter).  "centre": jpeg_upsample_plane, libjpeg's h2v2 triangle rule with replicated edges
+            (replication where W <= 4) - the rule of jpeg_decode_rgb8 for 4:2:0 files and the inverse siting of rgb8_to_i420's
+            block means (Y4M's C420jpeg).  Left-sited (MPEG-2) interpolation is not offered.
+    Works on any device; "centre" forms its planes on the host."""
+    yuv420_check("yuv420_to_rgb8", layout, chroma)
+    if frames_yuv.dtype != torch.uint8 or frames_yuv.dim() not in (2, 3):
+        raise ValueError("yuv420_to_rgb8 takes (T, 3H/2, W) or (3H/2, W) uint8 frames, got %s %s" % (frames_yuv.dtype, tuple(frames_yuv.shape)))
+    single = frames_yuv.dim() == 2
+    x = frames_yuv[None] if single else frames_yuv
+    T, H32, W = (int(v) for v in x.shape)
+    H = H32 * 2 // 3
+    if H < 2 or W < 2 or H % 2 or W % 2 or H * 3 // 2 != H32:
+        raise ValueError("yuv420_to_rgb8 needs even sizes for 4:2:0 chroma (got %d rows of %d bytes: H = %s, W = %d)"
+                         % (H32, W, H32 * 2 / 3, W))
+    yoff, cy, crv, cgu, cgv, cbu = YUV_INVERSE[yuv_matrix_id(matrix, W, H)]
+    ch, cw = H // 2, W // 2
+    y = x[:, :H].to(torch.int32)
+    if layout == "nv12":
+        uv = x[:, H:].reshape(T, ch, cw, 2).to(torch.int32)
+        u, v = uv[..., 0], uv[..., 1]
+    else:
+        uv = x[:, H:].reshape(T, 2, ch, cw).to(torch.int32)
+        u, v = uv[:, 0], uv[:, 1]
+    if chroma == "centre":
+        up = lambda c: torch.from_numpy(jpeg_upsample_plane(c.cpu().numpy(), 2, 2)).to(x.device)  # noqa: E731
+        u, v = (torch.stack([up(c[t]) for t in range(T)]) for c in (u, v))
+    else:
+        u, v = (c.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2) for c in (u, v))
+    y, u, v = cy * (y - yoff) + 8192, u - 128, v - 128
+    out = torch.stack([(y + crv * v) >> 14, (y - cgu * u - cgv * v) >> 14, (y + cbu * u) >> 14], dim=-1).clamp(0, 255).to(torch.uint8)
+    return out[0] if single else out
+
+
+class Y4MReader:
+    """The reading half of Y4MWriter / write_y4m: a YUV4MPEG2 stream of 8-bit 4:2:0 frames -> (n, 3H/2, W) uint8 I420 tensors, for
+    InferenceAgent.align_driving and image.YuvFrames.  The header's W, H and F give width, height and fps (a Fraction); C420,
+    C420jpeg, C420mpeg2 and C420paldv (and no C tag) are all read as I420 and the tag is kept in .chroma_tag - which siting the
+    conversion assumes is the caller's `chroma`; XCOLORRANGE=FULL sets .full_range and bit 2 of .matrix (Y4M has no tag for the
+    matrix itself: .matrix is 0 or 4, BT.601).  Any other C tag (4:2:2, 4:4:4, more than 8 bits, mono) or an interlaced stream
+    (I other than p or ?) is a ValueError.  len(reader) frames (the file's size decides; frame headers with parameters are
+    followed one by one); read(first=0, count=None, pin=True) -> the frames, in pinned host memory where a GPU is present
+    (pin=False: pageable, for a frame that is copied again anyway); chunks(n).
+    path_or_file: a path (opened here, closed by close()), or a seekable binary file object, left open."""
+
+    def __init__(self, path_or_file):
+        self._own = not hasattr(path_or_file, "read")
+        self._f = f = open(path_or_file, "rb") if self._own else path_or_file
+        try:
+            base = f.tell()
+            head = f.read(9)
+            if head == b"YUV4MPEG2":
+                head += f.readline(65536)  # up to the newline, however long the X tags are
+            end = head.find(b"\n")
+            if not head.startswith(b"YUV4MPEG2") or end < 0:
+                raise ValueError("Y4MReader: not a YUV4MPEG2 stream")
+            self.width = self.height = 0
+            self.fps, self.chroma_tag, self.full_range = None, "420", False
+            for tok in head[9:end].decode("ascii", "replace").split():
+                if tok[0] == "W":
+                    self.width = int(tok[1:])
+                elif tok[0] == "H":
+                    self.height = int(tok[1:])
+                elif tok[0] == "F":
+                    num, den = tok[1:].split(":")
+                    self.fps = fractions.Fraction(int(num), max(1, int(den)))
+                elif tok[0] == "I" and tok[1:] not in ("p", "?"):
+                    raise ValueError("Y4MReader: an interlaced stream (%s) is not read" % tok)
+                elif tok[0] == "C":
+                    if tok[1:] not in ("420", "420jpeg", "420mpeg2", "420paldv"):
+                        raise ValueError("Y4MReader: colour space %s is not read (8-bit 4:2:0 only)" % tok)
+                    self.chroma_tag = tok[1:]
+                elif tok == "XCOLORRANGE=FULL":
+                    self.full_range = True
+            if self.width < 2 or self.height < 2 or self.width % 2 or self.height % 2:
+                raise ValueError("Y4MReader: 4:2:0 frames have even sides (got %d x %d)" % (self.width, self.height))
+            self.matrix = 4 if self.full_range else 0
+            self._bytes = self.width * self.height * 3 // 2
+            self._at = []  # the offset of every frame's bytes
+            pos, size = base + end + 1, f.seek(0, 2)
+            while pos + 6 + self._bytes <= size:
+                f.seek(pos)
+                line = f.read(6)
+                if line[:5] != b"FRAME":
+                    raise ValueError("Y4MReader: frame %d does not begin with FRAME" % len(self._at))
+                while line[-1:] != b"\n":  # a frame header with parameters
+                    c = f.read(1)
+                    if not c:
+                        raise ValueError("Y4MReader: frame %d: the header runs past the end of the file" % len(self._at))
+                    line += c
+                pos += len(line)
+                if pos + self._bytes > size:
+                    break
+                self._at.append(pos)
+                pos += self._bytes
+        except BaseException:
+            self.close()
+            raise
+
+    def __len__(self):
+        return len(self._at)
+
+    def read(self, first=0, count=None, pin=True):
+        first = int(first)
+        last = len(self) if count is None else min(len(self), first + int(count))
+        if not 0 <= first <= last:
+            raise ValueError("Y4MReader.read: frames %d ... of %d" % (first, len(self)))
+        out = torch.empty((last - first, 3 * self.height // 2, self.width), dtype=torch.uint8, pin_memory=bool(pin) and torch.cuda.is_available())
+        flat = out.numpy().reshape(last - first, -1)
+        for i in range(first, last):
+            self._f.seek(self._at[i])
+            if self._f.readinto(memoryview(flat[i - first])) != self._bytes:
+                raise ValueError("Y4MReader: frame %d runs past the end of the file" % i)
+        return out
+
+    def chunks(self, n):
+        n = max(1, int(n))
+        return (self.read(at, n) for at in range(0, len(self), n))
+
+    def close(self):
+        f, self._f = getattr(self, "_f", None), None
+        if f is not None and self._own:
+            f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 # ---------------------------------------------------------------- baseline JPEG in integers (the definition of float_jpg_encode)
 # ITU-T T.81 Annex K.1 / K.2 (quantiser tables, row-major) and K.3 (the four Huffman tables as BITS + HUFFVAL)
 _JPEG_Q_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -1970,6 +2132,24 @@ def _jpeg_idct_islow(x):
     return np.clip(px + 128, 0, 255)
 
 
+def jpeg_upsample_plane(c, hs, vs):
+    """A (ch, cw) int32 numpy chroma plane at hs x vs subsampling -> (vs ch, hs cw): the `chroma` rule of jpeg_decode_rgb8, which
+    yuv420_to_rgb8(chroma="centre") shares - libjpeg's "fancy" triangle filters where hs = 2 and the plane is more than 2
+    samples wide, with the neighbours of the first and last row and column replicated; replication otherwise."""
+    import numpy as np
+    ch, cw = c.shape
+    if hs == 2 and cw > 2:
+        if vs == 2:
+            up, dn = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+            rows = np.stack([3 * c + up, 3 * c + dn], axis=1).reshape(2 * ch, cw)
+            b0, b1, sh = 8, 7, 4
+        else:
+            rows, b0, b1, sh = c, 1, 2, 2
+        left, right = np.concatenate([rows[:, :1], rows[:, :-1]], axis=1), np.concatenate([rows[:, 1:], rows[:, -1:]], axis=1)
+        return np.stack([(3 * rows + left + b0) >> sh, (3 * rows + right + b1) >> sh], axis=2).reshape(rows.shape[0], 2 * cw)
+    return np.repeat(np.repeat(c, vs, axis=0), hs, axis=1)
+
+
 def jpeg_decode_rgb8(file_bytes, status=False):
     """One baseline JPEG file (bytes-like) -> (H, W, 3) uint8 RGB as a numpy array: the definition float_jpg_decode is held to bit
     for bit.  Integer arithmetic only, int32 with wrap-around, `>>` arithmetic; written to libjpeg's published rules, so that on a
@@ -2017,22 +2197,7 @@ def jpeg_decode_rgb8(file_bytes, status=False):
         out = np.repeat(y[:, :, None], 3, axis=2)
         return (out.astype(np.uint8), st) if status else out.astype(np.uint8)
     cw, ch = -(-W // hs), -(-H // vs)
-    full = []
-    for pl in planes[1:]:
-        c = pl[:ch, :cw]
-        if hs == 2 and cw > 2:
-            if vs == 2:
-                up, dn = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
-                rows = np.stack([3 * c + up, 3 * c + dn], axis=1).reshape(2 * ch, cw)
-                b0, b1, sh = 8, 7, 4
-            else:
-                rows, b0, b1, sh = c, 1, 2, 2
-            left, right = np.concatenate([rows[:, :1], rows[:, :-1]], axis=1), np.concatenate([rows[:, 1:], rows[:, -1:]], axis=1)
-            c = np.stack([(3 * rows + left + b0) >> sh, (3 * rows + right + b1) >> sh], axis=2).reshape(rows.shape[0], 2 * cw)
-        else:
-            c = np.repeat(np.repeat(c, vs, axis=0), hs, axis=1)
-        full.append(c[:H, :W] - 128)
-    cb, cr = full
+    cb, cr = (jpeg_upsample_plane(pl[:ch, :cw], hs, vs)[:H, :W] - 128 for pl in planes[1:])
     r = y + ((91881 * cr + 32768) >> 16)
     g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
     b = y + ((116130 * cb + 32768) >> 16)

@@ -118,6 +118,62 @@ def frames_to_device(frames, device=None):
     return x.contiguous()
 
 
+class YuvFrames:
+    """A stack of 8-bit YUV 4:2:0 frames as front_frames_device and InferenceAgent.align_driving take them: data (T, 3h/2, w) - or
+    (3h/2, w), one frame - uint8 on the host or the device, in `layout` "i420" (Y, then U and V at h/2 x w/2: ffmpeg's yuv420p,
+    what the I420 outputs and host_models.Y4MReader give) or "nv12" (Y, then h/2 rows of interleaved U, V: most hardware
+    decoders).  matrix: the matrix the frames were made with, as host_models.yuv_matrix_id reads it (None = BT.601 limited range;
+    "auto" by w x h); chroma: "nearest" | "centre" (host_models.yuv420_to_rgb8).  h and w must be even; everything is checked
+    here (ValueError).  len() is T and a slice frames[a:b] (step 1) is a YuvFrames over a view of those frames."""
+
+    def __init__(self, data, h, w, layout="i420", matrix=None, chroma="nearest"):
+        host_models.yuv420_check("YuvFrames", layout, chroma)
+        h, w = int(h), int(w)
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError("YuvFrames: 4:2:0 frames have even sides (got %d x %d)" % (h, w))
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() not in (2, 3) or tuple(data.shape[-2:]) != (3 * h // 2, w):
+            raise ValueError("YuvFrames: data must be (T, %d, %d) uint8 for %d x %d frames, got %s %s"
+                             % (3 * h // 2, w, h, w, getattr(data, "dtype", type(data).__name__), tuple(getattr(data, "shape", ()))))
+        self.data = data[None] if data.dim() == 2 else data
+        self.h, self.w, self.layout, self.chroma = h, w, layout, chroma
+        self.matrix = host_models.yuv_matrix_id(matrix, w, h)
+
+    def __len__(self):
+        return int(self.data.shape[0])
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice) or key.step not in (None, 1):
+            raise TypeError("YuvFrames: frames are taken by range, frames[a:b]")
+        return YuvFrames(self.data[key], self.h, self.w, self.layout, self.matrix, self.chroma)
+
+    def take(self, idx):
+        """The frames `idx` (a list of indices) as a YuvFrames of their own."""
+        return YuvFrames(self.data[torch.as_tensor(idx, dtype=torch.int64, device=self.data.device)], self.h, self.w, self.layout, self.matrix,
+                         self.chroma)
+
+    def to_rgb8(self):
+        """The definition's frames: host_models.yuv420_to_rgb8 -> (T, h, w, 3) uint8 on the data's device."""
+        return host_models.yuv420_to_rgb8(self.data, self.layout, self.matrix, self.chroma)
+
+
+def _front_frames_yuv(frames, r, dst_h, dst_w, out, sn, sd, device):
+    """front_frames_device for a YuvFrames: float_img_front_frames_yuv"""
+    device = torch.device(device if device is not None else (frames.data.device if frames.data.is_cuda else "cuda:0"))
+    x = frames.data.detach().to(device, non_blocking=True).contiguous()
+    T = len(frames)
+    shape = (T, dst_h, dst_w, 3)
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+            raise ValueError("front_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
+                             % (shape, x.device, out.dtype, tuple(out.shape), out.device))
+        native.check(native.lib().float_img_front_frames_yuv(
+            C.c_void_p(x.data_ptr()), T, frames.h, frames.w, native.YUV_LAYOUTS[frames.layout], frames.matrix, native.YUV_CHROMA[frames.chroma],
+            C.cast(r.data_ptr(), C.POINTER(C.c_int32)), sn, sd, C.c_void_p(out.data_ptr()), dst_h, dst_w, native.stream_ptr(x.device)))
+    return out
+
+
 @torch.no_grad()
 def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with_color", bkg_color_hex="#000000", out=None, scale=None,
                         device=None):
@@ -125,9 +181,13 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
     h) in source coordinates (a single row serves every frame; a window may reach outside the image, where it is black) ->
     (T, dst_h, dst_w, 3) uint8 on the device.  Frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(frames[t],
     ...), rects[t], dst_h, dst_w, scale).  One fused kernel per 16 frames on the current stream of the frames' device; no scratch;
-    nothing synchronises.  out: a contiguous (T, dst_h, dst_w, 3) uint8 tensor on that device to write into."""
-    x = frames_to_device(frames, device)
-    T, H, W, ch = (int(v) for v in x.shape)
+    nothing synchronises.  out: a contiguous (T, dst_h, dst_w, 3) uint8 tensor on that device to write into.
+    frames may also be a YuvFrames (8-bit YUV 4:2:0, I420 or NV12): float_img_front_frames_yuv converts, crops and resizes in the
+    same single pass, frame t bitwise host_models.resize_rgb8(host_models.yuv420_to_rgb8(frame t, layout, matrix, chroma),
+    rects[t], dst_h, dst_w, scale); YUV has no alpha, so rgba_conversion and bkg_color_hex are not read."""
+    yuv = isinstance(frames, YuvFrames)
+    x = None if yuv else frames_to_device(frames, device)
+    T, H, W, ch = (len(frames), frames.h, frames.w, 3) if yuv else (int(v) for v in x.shape)
     r = torch.as_tensor(rects, dtype=torch.int32, device="cpu").reshape(-1, 4)
     if r.shape[0] == 1 and T > 1:
         r = r.expand(T, 4)
@@ -135,6 +195,8 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
         raise ValueError("front_frames_device: %d rects for %d frames" % (r.shape[0], T))
     r = r.contiguous()
     sn, sd = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
+    if yuv:
+        return _front_frames_yuv(frames, r, int(dst_h), int(dst_w), out, sn, sd, device)
     bkg = host_models.hex_to_rgb8(bkg_color_hex)
     mode = _rgba_mode(rgba_conversion)
     dst_h, dst_w = int(dst_h), int(dst_w)
@@ -154,8 +216,9 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
 
 def detector_views_device(frames, view_h=360, rgba_conversion="blend_with_color", bkg_color_hex="#000000", out=None, device=None):
     """The detector's view of every frame in one call: (T, view_h, round(W view_h / H), 3) uint8 on the device; view t is bitwise
-    detector_view_device(frames[t], view_h, ...) - the whole image as every rect, both axes at the one scale H / view_h."""
-    H, W = int(frames.shape[1]), int(frames.shape[2])
+    detector_view_device(frames[t], view_h, ...) - the whole image as every rect, both axes at the one scale H / view_h.  For a
+    YuvFrames view t is bitwise resize_rgb8(yuv420_to_rgb8(frame t, ...), None, view_h, columns, scale=(H, view_h))."""
+    H, W = (frames.h, frames.w) if isinstance(frames, YuvFrames) else (int(frames.shape[1]), int(frames.shape[2]))
     vh, vw = detector_view_size(H, W, view_h)
     g = math.gcd(H, vh)
     return front_frames_device(frames, (0, 0, W, H), vh, vw, rgba_conversion, bkg_color_hex, out, (H // g, vh // g), device)

@@ -14,6 +14,8 @@ AUD_SEG_NORMALIZE = 1  # FLOAT_AUD_SEG_NORMALIZE: the `flags` bit of float_aud_c
 IMG_RGBA_MODES = {"discard_alpha": 0, "blend_with_color": 1, "replace_with_color": 2}  # FLOAT_IMG_RGBA_*: float_img_front's `rgba_mode`
 IMG_OUT_NCHW_PM1, IMG_OUT_HWC_U8 = 0, 1  # FLOAT_IMG_OUT_*: float_img_front's `out_mode`
 IMG_SRC_F32, IMG_SRC_U8 = 0, 1  # FLOAT_IMG_SRC_*: float_img_front_frames' `src_type`
+YUV_LAYOUTS = {"i420": 0, "nv12": 1}  # FLOAT_IMG_YUV_*: float_img_front_frames_yuv's `layout`
+YUV_CHROMA = {"nearest": 0, "centre": 1}  # FLOAT_IMG_CHROMA_*: its `chroma`
 MATRIX_BT601_LIMITED = 0  # FLOAT_DEC_MATRIX_BT601_LIMITED: the `matrix` argument of float_dec_frames[_host]_i420
 IMG_MATRIX_BT601_LIMITED = 0  # FLOAT_IMG_MATRIX_BT601_LIMITED: the `matrix` argument of float_img_paste_i420
 # FLOAT_DEC_MATRIX_* and their FLOAT_IMG_MATRIX_* twins: bit 1 = BT.709, bit 2 = full range (host_models.YUV_MATRICES)
@@ -160,6 +162,8 @@ _SIGNATURES = {
     "float_img_front": (C.c_int, [C.c_void_p] + [C.c_int32] * 14 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_img_front_frames": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_int32)] + [C.c_int32] * 6 +
                                [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "float_img_front_frames_yuv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_int32)] + [C.c_int32] * 2 +
+                                   [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "float_img_paste": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]),
     "float_img_paste_i420": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]),
     "float_img_resample_plan_ints": (C.c_size_t, [C.c_int32] * 4),

@@ -12,7 +12,7 @@ from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
 from ...face import FaceDetectorHIP, find_sfd_weights, load_sfd_state
-from ...image import (detector_view_device, detector_views_device, front_frames_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
+from ...image import (YuvFrames, detector_view_device, detector_views_device, front_frames_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
                       require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
@@ -599,10 +599,17 @@ class InferenceAgent:
         face = self._face_handle(path) if fa is None else None
         rows = []
         for at in range(0, len(idx), 16):
-            group = video[torch.as_tensor(idx[at:at + 16], device=video.device)]
-            if int(video.shape[1]) > 360:
+            if isinstance(video, YuvFrames):  # the same kernel on the planes; 360 rows or less: the definition's frames on the host
+                group = video.take(idx[at:at + 16])
+                if video.h > 360:
+                    views = detector_views_device(group, 360, device=self.rank)
+                else:
+                    views = torch.stack([host_models.process_img_view(x.float().cpu() / 255.0) for x in group.to_rgb8()])
+            elif int(video.shape[1]) > 360:
+                group = video[torch.as_tensor(idx[at:at + 16], device=video.device)]
                 views = detector_views_device(group, 360, rgba, bkg, device=self.rank)
             else:
+                group = video[torch.as_tensor(idx[at:at + 16], device=video.device)]
                 views = torch.stack([host_models.process_img_view(
                     x[..., :3].float().cpu() if x.is_floating_point() and x.shape[-1] == 3 else
                     host_models.image_to_rgb8(x, rgba, host_models.hex_to_rgb8(bkg)).float() / 255.0) for x in group])
@@ -653,8 +660,8 @@ class InferenceAgent:
         elif isinstance(video, jpeg.JpegFrames):
             part = lambda lo, hi: jpeg.JpegFrames(video.data, video.offsets[lo:hi + 1])  # noqa: E731
         else:
-            raise ValueError("align_driving: video must be a (T, H, W, 3|4) tensor, a JpegFrames, an AviMjpegReader or the path of an .avi, got %s"
-                             % type(video).__name__)
+            raise ValueError("align_driving: video must be a (T, H, W, 3|4) tensor, a JpegFrames, an AviMjpegReader or the path of an .avi, "
+                             "a YuvFrames, a Y4MReader or the path of a .y4m, got %s" % type(video).__name__)
         T = len(video)
         if T == 0:
             raise ValueError("align_driving: the clip holds no frames")
@@ -681,8 +688,56 @@ class InferenceAgent:
         jpeg.check_status(status.cpu())
         return out, rects
 
+    @staticmethod
+    def _is_yuv_video(video):
+        return isinstance(video, (YuvFrames, host_models.Y4MReader)) or (
+            isinstance(video, (str, os.PathLike)) and os.fspath(video).lower().endswith(".y4m"))
+
+    def _align_driving_yuv(self, video, crop, detect_every, smooth, margin, index, rects, chunk, src_matrix, src_chroma):
+        """align_driving for 8-bit YUV 4:2:0: an image.YuvFrames, a host_models.Y4MReader or the path of a .y4m file - the sibling
+        of _align_driving_files.  `chunk` frames of planes cross PCIe into one reused device buffer (1.5 bytes per pixel; a reader
+        or a path is read from the file chunk by chunk), float_img_front_frames_yuv writes the crops, and the frames the detector
+        is to see go through detector_views_device on the same kernel.  src_matrix / src_chroma override what the YuvFrames
+        carries; a Y4M file is BT.601 in the range its header states and "nearest" unless they say otherwise."""
+        opened = host_models.Y4MReader(video) if isinstance(video, (str, os.PathLike)) else None
+        try:
+            src = video if opened is None else opened
+            if isinstance(src, YuvFrames):
+                H, Wd, layout = src.h, src.w, src.layout
+                matrix, chroma = src.matrix if src_matrix is None else src_matrix, src.chroma if src_chroma is None else src_chroma
+                part = one = lambda lo, hi: src.data[lo:hi]  # noqa: E731
+            else:
+                H, Wd, layout = src.height, src.width, "i420"
+                matrix, chroma = src.matrix if src_matrix is None else src_matrix, "nearest" if src_chroma is None else src_chroma
+                part = lambda lo, hi: src.read(lo, hi - lo)  # noqa: E731
+                one = lambda lo, hi: src.read(lo, hi - lo, pin=False)  # noqa: E731  (a sampled frame is copied by the cat below)
+            wrap = lambda data: YuvFrames(data, H, Wd, layout, matrix, chroma)  # noqa: E731
+            T = len(src)
+            if T == 0:
+                raise ValueError("align_driving: the clip holds no frames")
+            wrap(part(0, 1))  # layout, matrix and chroma are refused before anything runs
+            size = int(self.opt.input_size)
+            self.to_target()
+            rects = self._driving_clip_rects(T, H, Wd, rects, crop, detect_every, smooth, margin, index,
+                                             lambda idx: (wrap(torch.cat([one(i, i + 1) for i in idx])), list(range(len(idx)))))
+            dev = torch.device("cuda", self.rank) if isinstance(self.rank, int) else torch.device(self.rank)
+            out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=dev)
+            buf = None
+            for at in range(0, T, chunk):
+                data = part(at, min(T, at + chunk))
+                if not data.is_cuda:  # one device buffer for the whole clip; copies and kernels are ordered by the stream
+                    if buf is None:
+                        buf = torch.empty((min(chunk, T), 3 * H // 2, Wd), dtype=torch.uint8, device=dev)
+                    data = buf[:data.shape[0]].copy_(data, non_blocking=True)
+                front_frames_device(wrap(data), rects[at:at + chunk], size, size, out=out[at:at + data.shape[0]])
+            return out, rects
+        finally:
+            if opened is not None:
+                opened.close()
+
     @torch.no_grad()
-    def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32, entropy=None):
+    def align_driving(self, video, crop="fixed", detect_every=5, smooth=25, margin=None, index=1, rects=None, chunk=32, entropy=None,
+                      src_matrix=None, src_chroma=None):
         """A raw driving video -> the frames drive_device takes: video (T, H, W, 3|4), fp32 in [0, 1] or uint8, on the host or on
         the device -> (frames_u8 (T, size, size, 3) uint8 on the device, rects = T tuples (x, y, w, h) in source coordinates).
         Frame t is bitwise host_models.resize_rgb8(host_models.image_to_rgb8(video[t], ...), rects[t], size, size)
@@ -699,8 +754,19 @@ class InferenceAgent:
         time, float_jpg_decode makes the uint8 frames in the reused device buffer, and the result is bit for bit align_driving on
         host_models.jpeg_decode_rgb8 of every frame.  A damaged frame (a non-zero status word) is a ValueError naming it.
         entropy: jpeg.decode_jpeg_device's, for such a clip - "sync" or "auto" spread a frame WITHOUT restart markers (ffmpeg's
-        and most cameras' files) over up to 1024 lanes, where None decodes it on one; the frames are the same bytes."""
+        and most cameras' files) over up to 1024 lanes, where None decodes it on one; the frames are the same bytes.
+        video may also be 8-bit YUV 4:2:0 as decoders, cameras and `ffmpeg -pix_fmt yuv420p` deliver it - an image.YuvFrames (I420
+        or NV12, host or device), a host_models.Y4MReader or the path of a .y4m file: the planes cross PCIe as they are, half the
+        bytes of uint8 RGB, and float_img_front_frames_yuv converts, crops and resizes in one pass; frame t is bitwise
+        host_models.resize_rgb8(host_models.yuv420_to_rgb8(frame t, layout, matrix, chroma), rects[t], size, size).  src_matrix /
+        src_chroma: the matrix the source was made with (host_models.yuv_matrix_id; "auto" goes by the source's size) and how
+        luma samples get their chroma ("nearest" | "centre"); None leaves what the YuvFrames carries, and for a Y4M file BT.601
+        in the header's range and "nearest".  With any other video they must be None (ValueError)."""
         jpeg.entropy_id(entropy)
+        if self._is_yuv_video(video):
+            return self._align_driving_yuv(video, crop, detect_every, smooth, margin, index, rects, max(1, int(chunk)), src_matrix, src_chroma)
+        if src_matrix is not None or src_chroma is not None:
+            raise ValueError("align_driving: src_matrix and src_chroma apply to YUV 4:2:0 video only (a YuvFrames, a Y4MReader or a .y4m path)")
         o = self.opt
         size = int(o.input_size)
         rgba, bkg = getattr(o, "rgba_conversion", "blend_with_color"), getattr(o, "bkg_color_hex", "#000000")
@@ -727,16 +793,19 @@ class InferenceAgent:
 
     @torch.no_grad()
     def drive_video(self, ref_img, video, mode="relative", no_crop=True, crop="fixed", detect_every=5, smooth=25, margin=None, index=1,
-                    rects=None, chunk=32, out=None, out_dtype=None, out_format=None, matrix=None, entropy=None):
+                    rects=None, chunk=32, out=None, out_dtype=None, out_format=None, matrix=None, entropy=None, src_matrix=None,
+                    src_chroma=None):
         """drive_device from raw inputs: the portrait ref_img (a ComfyUI IMAGE item) goes through host_inputs' image half
         (no_crop as there), the raw driving video through align_driving (crop ... chunk as there), and the two through
         drive_device (mode, out, out_dtype, out_format, matrix as there).  With rects= given it is bit for bit drive_device on
         the definition's crops of the video.  video: a tensor of raw frames, or a Motion-JPEG clip (JpegFrames, AviMjpegReader,
-        the path of an .avi) that is decoded on the device - align_driving has the details, and takes `entropy`."""
+        the path of an .avi) that is decoded on the device - align_driving has the details, and takes `entropy`; or 8-bit YUV
+        4:2:0 (an image.YuvFrames, a Y4MReader, the path of a .y4m), converted in the cropping kernel - src_matrix and src_chroma
+        say how, as in align_driving (`matrix` is the OUTPUT's)."""
         self._crop_matrix("drive_video", out, out_dtype, out_format, matrix)  # a contradiction is refused before anything runs
         silence = {"waveform": torch.zeros(1, 1, 16), "sample_rate": self.opt.sampling_rate}  # _host_inputs' audio half: unused
         s = self._host_inputs(ref_img, silence, no_crop, False)[0]
-        frames_u8, _ = self.align_driving(video, crop, detect_every, smooth, margin, index, rects, chunk, entropy)
+        frames_u8, _ = self.align_driving(video, crop, detect_every, smooth, margin, index, rects, chunk, entropy, src_matrix, src_chroma)
         return self.drive_device(s, frames_u8, mode, out, out_dtype, out_format, matrix)
 
     def stream_device(self, s, a, a_cfg_scale=2.0, r_cfg_scale=1.0, e_cfg_scale=1.0, emo="S2E", seed=25, out_dtype=None,

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
+/* Stays 6: float_img_front_frames_yuv (the frame-stacked image front end reading 8-bit YUV 4:2:0, I420 or NV12), float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
  * decoded to 8-bit RGB frames on the device), float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
@@ -660,6 +660,29 @@ enum { FLOAT_IMG_SRC_F32 = 0, FLOAT_IMG_SRC_U8 = 1 };
 int float_img_front_frames(const void* frames, int32_t n_frames, int32_t src_h, int32_t src_w, int32_t channels, int32_t src_type,
                            const int32_t* rects, int32_t scale_num, int32_t scale_den, int32_t rgba_mode, int32_t bkg_r, int32_t bkg_g,
                            int32_t bkg_b, uint8_t* out, int32_t dst_h, int32_t dst_w, void* stream);
+
+/* The same call on 8-bit YUV 4:2:0 frames, as decoders, cameras and `ffmpeg -pix_fmt yuv420p | nv12` deliver them: colour
+ * conversion, crop and resize in the one pass, 1.5 bytes read per source pixel.
+ *   frames: (n_frames, 3 src_h / 2, src_w) uint8 contiguous in HBM, any alignment; src_h and src_w even, 2 ... 16384.
+ *     layout FLOAT_IMG_YUV_I420: the Y plane, then U and V at src_h / 2 x src_w / 2 each (what float_dec_frames_i420 and
+ *     float_img_paste_i420 write); FLOAT_IMG_YUV_NV12: the Y plane, then src_h / 2 rows of src_w bytes of interleaved U, V.
+ *   matrix: FLOAT_DEC_MATRIX_* - the id of the matrix the frames were made with.  Its inverse in 14-bit fixed point
+ *     (host_models.YUV_INVERSE; rows yoff, cy, crv, cgu, cgv, cbu), with y = Y - yoff, u = U - 128, v = V - 128 in int32:
+ *       R = clamp8((cy y + crv v + 8192) >> 14), G = clamp8((cy y - cgu u - cgv v + 8192) >> 14), B = clamp8((cy y + cbu u + 8192) >> 14)
+ *   chroma: how a luma sample gets its U and V.  FLOAT_IMG_CHROMA_NEAREST: the sample of its 2 x 2 block (OpenCV's and swscale's
+ *     unscaled conversions); FLOAT_IMG_CHROMA_CENTRE: libjpeg's h2v2 triangle rule with replicated edges, as float_jpg_decode
+ *     applies it to 4:2:0 files (replication where src_w <= 4) - the inverse siting of the block means the I420 outputs hold.
+ *   rects, scale_num / scale_den, out, limits and checks: as float_img_front_frames.  Frame t is bitwise
+ *     host_models.resize_rgb8(host_models.yuv420_to_rgb8(frame t, layout, matrix, chroma), rects[t], dst_h, dst_w, scale);
+ *     window samples outside the image are RGB zero, not a conversion of absent YUV.
+ * One fused kernel per block of 16 frames - float_img_front_frames' kernel with another staging stage (csrc/imgy_kernels.hpp):
+ * no scratch, chroma rows kept in LDS across luma rows.  No atomics, two calls give equal bytes; allocates nothing, synchronises
+ * nothing; kernel launches only (no test captures it). */
+enum { FLOAT_IMG_YUV_I420 = 0, FLOAT_IMG_YUV_NV12 = 1 };
+enum { FLOAT_IMG_CHROMA_NEAREST = 0, FLOAT_IMG_CHROMA_CENTRE = 1 };
+int float_img_front_frames_yuv(const uint8_t* frames, int32_t n_frames, int32_t src_h, int32_t src_w, int32_t layout, int32_t matrix,
+                               int32_t chroma, const int32_t* rects, int32_t scale_num, int32_t scale_den, uint8_t* out, int32_t dst_h,
+                               int32_t dst_w, void* stream);
 
 /* ---------------------------------------------------------------- paste back -- */
 /* The step after the decoder: n_frames generated 8-bit frames (n_frames, fr_h, fr_w, 3) - the buffer float_dec_frames_u8 writes -
