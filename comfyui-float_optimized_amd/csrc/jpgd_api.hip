@@ -67,6 +67,7 @@ int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t
   const unsigned idct = (unsigned)((L.nblocks + kJpgdIdctBlocks - 1) / kJpgdIdctBlocks);
   const unsigned cols = (unsigned)(((W + 3) / 4 + kJpgdRgbThreads - 1) / kJpgdRgbThreads);
   const unsigned sync = (unsigned)((jpgd_work(plan_host).sync_lanes + kJpgdLanes - 1) / kJpgdLanes);  // 0: no frame on the sync route
+  const unsigned split = (unsigned)((jpgd_work(plan_host).split_lanes + kJpgdLanes - 1) / kJpgdLanes);  // the same for the split route
   for (int f0 = 0; f0 < n_frames; f0 += group) {  // groups share `work` in stream order
     L.frame0 = f0, L.frames = std::min(group, n_frames - f0);
     const unsigned nf = (unsigned)L.frames;
@@ -74,9 +75,18 @@ int float_jpg_decode(const uint8_t* files, const int64_t* offsets, const int32_t
                        (uint8_t*)work, (int*)status);
     hipLaunchKernelGGL(jpgd_entropy_kernel, dim3(lanes, nf), dim3(kJpgdLanes), 0, s, files, (const long long*)offsets, (const int*)plan, L,
                        (uint8_t*)work, (int*)status);
-    bool any = false;
-    for (int f = f0; f < f0 + L.frames; ++f) any = any || plan_host[plan_host[JPGD_P_FRAMES] + f * JPGD_F_INTS + JPGD_F_ROUTE];
-    if (any) {  // each returns at once for a frame on the interval route, as jpgd_entropy_kernel does for the others
+    bool any = false, any_split = false;
+    for (int f = f0; f < f0 + L.frames; ++f) {
+      const int32_t route = plan_host[plan_host[JPGD_P_FRAMES] + f * JPGD_F_INTS + JPGD_F_ROUTE];
+      any = any || route > 0, any_split = any_split || route < 0;
+    }
+    if (any_split) {  // the same three steps with the chains cut at the restart markers; each returns at once for any other frame
+      hipLaunchKernelGGL(jpgd_split_unstuff_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, files, (const long long*)offsets, (const int*)plan, L,
+                         (uint8_t*)work);
+      hipLaunchKernelGGL(jpgd_split_relax_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, (const int*)plan, L, (uint8_t*)work);
+      hipLaunchKernelGGL(jpgd_split_write_kernel, dim3(split, nf), dim3(kJpgdLanes), 0, s, (const int*)plan, L, (uint8_t*)work, (int*)status);
+    }
+    if (any) {  // each returns at once for a frame on another route, as jpgd_entropy_kernel does for the others
       hipLaunchKernelGGL(jpgd_unstuff_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, files, (const long long*)offsets, (const int*)plan, L,
                          (uint8_t*)work);
       hipLaunchKernelGGL(jpgd_relax_kernel, dim3(nf), dim3(kJpgdSyncLanes), 0, s, (const int*)plan, L, (uint8_t*)work);

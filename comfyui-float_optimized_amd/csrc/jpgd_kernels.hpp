@@ -6,7 +6,9 @@
 //                        block in an LDS row of its own (33 dwords apart: lanes fall into different banks) and hands it to the
 //                        coefficient buffer as eight 16-byte stores.
 //   (frames on the sync route - a scan without restart markers over up to 1024 lanes - are skipped by it and go through
-//   jpgd_unstuff_kernel, jpgd_relax_kernel and jpgd_sync_write_kernel instead: three more launches, described where they are)
+//   jpgd_unstuff_kernel, jpgd_relax_kernel and jpgd_sync_write_kernel instead: three more launches, described where they are;
+//   frames on the split route - the intervals of a scan WITH restart markers over up to 1024 lanes - through the jpgd_split_*
+//   forms of the three)
 //   jpgd_idct_kernel     32 blocks per workgroup: coefficients into LDS by 16-byte loads, pass 1 down the columns (dequantising),
 //                        the block transposed through LDS, pass 2 along the rows, 8 samples per lane as one 8-byte store.
 //   jpgd_rgb_kernel      4 pixels per lane: fancy upsampling from the chroma planes, colour conversion, one 12-byte store.
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_unstuff_kernel(const uint
   __shared__ int wave_cnt[2][kWaves];  // iteration k + 2 writes a row only behind iteration k + 1's barrier: all have read k's
   const int f = L.frame0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int* fr = jpgd_frame(plan, f);
-  if (!fr[JPGD_F_ROUTE]) return;
+  if (fr[JPGD_F_ROUTE] <= 0) return;  // the interval route's frame, or the split route's
   uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
   const int* seg = (const int*)(mine + L.seg);
   const uint8_t* file = files + offsets[f];
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_relax_kernel(const int* _
   __shared__ int xj[kJpgdSyncLanes], xd[3][kJpgdSyncLanes];
   const int f = L.frame0 + blockIdx.x, i = threadIdx.x;
   const int* fr = jpgd_frame(plan, f);
-  if (!fr[JPGD_F_ROUTE]) return;
+  if (fr[JPGD_F_ROUTE] <= 0) return;  // the interval route's frame, or the split route's
   const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
   for (int k = i; k < kJpgdSetInts; k += kJpgdSyncLanes) set[k] = gset[k];
   uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(kJpgdLanes) void jpgd_sync_write_kernel(const int* 
   __shared__ jpgd_word rows[kJpgdLanes * kJpgdRowDwords];
   const int f = L.frame0 + blockIdx.y, lane = threadIdx.x;
   const int* fr = jpgd_frame(plan, f);
-  if (!fr[JPGD_F_ROUTE]) return;
+  if (fr[JPGD_F_ROUTE] <= 0) return;  // the interval route's frame, or the split route's
   const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
   for (int k = lane; k < kJpgdSetInts; k += kJpgdLanes) set[k] = gset[k];
   __syncthreads();
@@ -288,6 +290,218 @@ __global__ __launch_bounds__(kJpgdLanes) void jpgd_sync_write_kernel(const int* 
   for (long long g = zero_from + i; g < L.nblocks; g += (long long)gridDim.x * kJpgdLanes)
 #pragma unroll
     for (int w = 0; w < 8; ++w) ((uint4*)(coef + (size_t)g * 64))[w] = zero4;
+}
+
+// ---------------------------------------------------------------- the split route (jpgd_rule.hpp): frames whose ROUTE word is negative
+// jpgd_unstuff_kernel over every segment of the interval table in turn, into one copy: interval k's bytes follow interval
+// k - 1's, and its record gets (first byte, bytes).  The lengths are known only now, so the lanes are dealt out here: S from
+// the copy's length and the number of segments, then a record's lane count from its length.  No segment: -1 bytes, no lane.
+__global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_split_unstuff_kernel(const uint8_t* __restrict__ files, const long long* __restrict__ offsets,
+                                                                           const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {
+  constexpr int kWaves = kJpgdSyncLanes / 64;
+  __shared__ int wave_cnt[2][kWaves];  // as in jpgd_unstuff_kernel; `it` goes on from one segment to the next
+  __shared__ int lens[kJpgdSplitIntervals];
+  const int f = L.frame0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int* fr = jpgd_frame(plan, f);
+  if (fr[JPGD_F_ROUTE] >= 0) return;
+  uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
+  const int* seg = (const int*)(mine + L.seg);
+  const uint8_t* file = files + offsets[f];
+  uint8_t* u = mine + L.unst;
+  int* tab = (int*)(mine + L.table);
+  int* iv = tab + kJpgdSplitIntAt;
+  const int n_int = fr[JPGD_F_NINT];
+  int total = 0, present = 0, it = 0;  // bytes kept and segments so far, the same in every lane
+  for (int k = 0; k < n_int; ++k) {
+    const int b0 = seg[2 * k], b1 = seg[2 * k + 1], start = total;
+    present += b0 >= 0;
+    for (int base = b0; b0 >= 0 && base < b1; base += kJpgdSyncLanes, it ^= 1) {
+      const int q = base + tid;
+      const uint8_t v = q < b1 ? file[q] : 0;
+      const bool keep = q < b1 && !(v == 0 && q > b0 && file[q - 1] == 0xFF);
+      const unsigned long long vote = __ballot(keep);
+      if (lane == 0) wave_cnt[it][wave] = __popcll(vote);
+      __syncthreads();
+      int before = total, all = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) {
+        const int c = wave_cnt[it][w];
+        before += w < wave ? c : 0;
+        all += c;
+      }
+      if (keep) u[before + __popcll(vote & ((1ull << lane) - 1ull))] = v;
+      total += all;
+    }
+    if (tid == 0) iv[JPGD_X_INT * k] = start, iv[JPGD_X_INT * k + 1] = lens[k] = b0 >= 0 ? total - start : -1;
+  }
+  __syncthreads();
+  const uint32_t S = jpgd_split_sub((uint32_t)total, (uint32_t)present, (uint32_t)-fr[JPGD_F_ROUTE]);
+  if (tid < n_int) iv[JPGD_X_INT * tid + 2] = lens[tid] >= 0 ? (int)jpgd_split_lanes((uint32_t)lens[tid], S) : 0;
+  if (tid == 0) tab[JPGD_T_LEN] = total, tab[JPGD_T_S] = (int)S;
+}
+
+// jpgd_relax_kernel with the chains cut at the markers.  An inclusive prefix of the records' lane counts sits in LDS; lane i
+// looks its interval k up there (a binary search) and is lane q of it.  Lane q = 0 enters at the true (0, 0) and is final from
+// round 0; a lane takes its predecessor's exit for q > 0 only, a dead one in round q and not before.  All intervals relax in
+// the same rounds, so the loop ends after the longest interval's lane count at the latest.  The prefix over block counts and
+// DC sums adds a neighbour's value only from inside the interval.  The last lane of an interval knows whether its chain died
+// inside the data and from which of the interval's blocks on all are zero; a record without lanes is zero from block 0.
+__global__ __launch_bounds__(kJpgdSyncLanes) void jpgd_split_relax_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {
+  __shared__ int set[kJpgdSetInts];
+  __shared__ uint32_t xp[kJpgdSyncLanes], xn[kJpgdSyncLanes];
+  __shared__ int xj[kJpgdSyncLanes], xd[3][kJpgdSyncLanes];
+  __shared__ int lane0[kJpgdSplitIntervals + 1];  // interval k has lanes lane0[k] ... lane0[k + 1] - 1
+  __shared__ int most;                            // the longest interval's lanes
+  const int f = L.frame0 + blockIdx.x, i = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  if (fr[JPGD_F_ROUTE] >= 0) return;
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  for (int k = i; k < kJpgdSetInts; k += kJpgdSyncLanes) set[k] = gset[k];
+  uint8_t* mine = work + (size_t)blockIdx.x * L.frame;
+  int* tab = (int*)(mine + L.table);
+  int* iv = tab + kJpgdSplitIntAt;
+  const uint32_t S = (uint32_t)tab[JPGD_T_S];
+  const int n_int = fr[JPGD_F_NINT], hv = plan[JPGD_P_HS] * plan[JPGD_P_VS], bpm = plan[JPGD_P_BPM];
+  const int own_cnt = i < n_int ? iv[JPGD_X_INT * i + 2] : 0;
+  xn[i] = (uint32_t)own_cnt;  // n_int <= kJpgdSplitIntervals: the upper half stays 0
+  if (i == 0) most = 0, lane0[0] = 0;
+  __syncthreads();
+  atomicMax(&most, own_cnt);
+  for (int off = 1; off < kJpgdSplitIntervals; off <<= 1) {
+    const uint32_t a = i >= off ? xn[i - off] : 0u;
+    __syncthreads();
+    xn[i] += a;
+    __syncthreads();
+  }
+  if (i < kJpgdSplitIntervals) lane0[i + 1] = (int)xn[i];
+  __syncthreads();
+  const int nsub = lane0[n_int], longest = most;
+  const bool active = i < nsub;
+  int k = 0;
+  for (int hi = n_int; hi - k > 1;) {  // the last k with lane0[k] <= i: of equal ones the one that has lanes
+    const int mid = (k + hi) >> 1;
+    if (lane0[mid] <= i) k = mid;
+    else hi = mid;
+  }
+  const int q = active ? i - lane0[k] : 0, cnt = lane0[k + 1] - lane0[k];
+  const uint32_t len = active ? (uint32_t)iv[JPGD_X_INT * k + 1] : 0u;
+  const uint8_t* u = mine + L.unst + (active ? iv[JPGD_X_INT * k] : 0);
+  const uint32_t end = jpgd_sync_end((uint32_t)q, S, len);
+  uint32_t entry_p = 8u * (uint32_t)q * S;
+  int entry_j = 0, rounds = 0;
+  xp[i] = kJpgdDead, xj[i] = 0, xn[i] = 0, xd[0][i] = 0, xd[1][i] = 0, xd[2][i] = 0;
+  __syncthreads();
+  bool need = active, wait = false;
+  for (int r = 0; r < longest; ++r) {
+    bool changed = wait;
+    if (need) {
+      JpgdRun x{entry_p, entry_j, 0u, {0, 0, 0}};
+      JpgdRaw b;
+      jpgd_sync_run(b, u, len, end, false, 0xFFFFFFFFu, hv, bpm, x, [&](JpgdRaw& bits, int c, int32_t& pred, uint32_t) {
+        return jpgd_block(bits, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pred, JpgdNoCoef());
+      });
+      changed = r == 0 || x.p != xp[i] || x.j != xj[i];
+      xp[i] = x.p, xj[i] = x.j, xn[i] = x.n, xd[0][i] = x.dc[0], xd[1][i] = x.dc[1], xd[2][i] = x.dc[2];
+    }
+    ++rounds;
+    if (!__syncthreads_or(changed)) break;
+    need = wait = false;
+    if (active && q > 0 && (xp[i - 1] != entry_p || xj[i - 1] != entry_j)) {
+      if (xp[i - 1] == kJpgdDead && r + 1 < q) wait = true;  // not final before round q
+      else entry_p = xp[i - 1], entry_j = xj[i - 1], need = true;
+    }
+    __syncthreads();  // every exit is read before the round rewrites it
+  }
+  __syncthreads();
+  const uint32_t own_n = xn[i];
+  const int own_d[3] = {xd[0][i], xd[1][i], xd[2][i]};
+  for (int off = 1; off < longest; off <<= 1) {  // inclusive prefix inside the interval, in place
+    const bool has = active && q >= off;
+    const uint32_t an = has ? xn[i - off] : 0u;
+    const int a0 = has ? xd[0][i - off] : 0, a1 = has ? xd[1][i - off] : 0, a2 = has ? xd[2][i - off] : 0;
+    __syncthreads();
+    xn[i] += an, xd[0][i] = jpgd_add(xd[0][i], a0), xd[1][i] = jpgd_add(xd[1][i], a1), xd[2][i] = jpgd_add(xd[2][i], a2);
+    __syncthreads();
+  }
+  if (active) {
+    int* e = tab + kJpgdSplitLaneAt + i * JPGD_X_LANE;
+    e[0] = (int)entry_p, e[1] = entry_j, e[2] = (int)(xn[i] - own_n);
+    e[3] = jpgd_sub(xd[0][i], own_d[0]), e[4] = jpgd_sub(xd[1][i], own_d[1]), e[5] = jpgd_sub(xd[2][i], own_d[2]);
+    e[6] = k, e[7] = q;
+    if (q == cnt - 1) {  // a chain that died inside the data: every block of the interval from the bad one on is zero
+      const uint32_t blocks = jpgd_split_blocks(k, fr[JPGD_F_SPAN], plan[JPGD_P_MCUX] * plan[JPGD_P_MCUY], bpm);
+      iv[JPGD_X_INT * k + 3] = (int)(xp[i] == kJpgdDead && xn[i] < blocks ? xn[i] : blocks);
+    }
+  }
+  if (i < n_int && own_cnt == 0) iv[JPGD_X_INT * i + 3] = 0;
+  if (i == 0) tab[JPGD_T_NSUB] = nsub, tab[JPGD_T_ROUNDS] = rounds;
+}
+
+// jpgd_sync_write_kernel with an interval's block budget in the place of the frame's: a lane decodes its owned blocks from
+// its table entry into the interval's share of the coefficient buffer and stops at the interval's last block, so surplus bytes
+// in front of a marker are nobody's.  An interval's last lane goes on past the interval's bytes on zero bits, never into the
+// next interval's.  The blocks behind a dead chain's last good one are zeroed to the interval's end: by the lane that died
+// behind the data, else - and for an interval without a segment - by lane k of the launch for interval k.
+__global__ __launch_bounds__(kJpgdLanes) void jpgd_split_write_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work,
+                                                                     int* __restrict__ status) {
+  __shared__ int set[kJpgdSetInts];
+  __shared__ jpgd_word rows[kJpgdLanes * kJpgdRowDwords];
+  const int f = L.frame0 + blockIdx.y, lane = threadIdx.x;
+  const int* fr = jpgd_frame(plan, f);
+  if (fr[JPGD_F_ROUTE] >= 0) return;
+  const int* gset = plan + plan[JPGD_P_SETS] + fr[JPGD_F_SET] * kJpgdSetInts;
+  for (int k = lane; k < kJpgdSetInts; k += kJpgdLanes) set[k] = gset[k];
+  __syncthreads();
+  uint8_t* mine = work + (size_t)blockIdx.y * L.frame;
+  const int* tab = (const int*)(mine + L.table);
+  const int* iv = tab + kJpgdSplitIntAt;
+  int16_t* coef = (int16_t*)(mine + L.coef);
+  const uint32_t S = (uint32_t)tab[JPGD_T_S];
+  const int nsub = tab[JPGD_T_NSUB], i = blockIdx.x * kJpgdLanes + lane;
+  const int n_int = fr[JPGD_F_NINT], span = fr[JPGD_F_SPAN], nmcu = plan[JPGD_P_MCUX] * plan[JPGD_P_MCUY], bpm = plan[JPGD_P_BPM];
+  const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
+  if (i < nsub) {
+    const int* e = tab + kJpgdSplitLaneAt + i * JPGD_X_LANE;
+    const int k = e[6], q = e[7];
+    const int* rec = iv + JPGD_X_INT * k;
+    const uint32_t len = (uint32_t)rec[1], blocks = jpgd_split_blocks(k, span, nmcu, bpm), first = (uint32_t)e[2];
+    int16_t* mine_coef = coef + (size_t)k * span * bpm * 64;  // the interval's block 0
+    if ((uint32_t)e[0] != kJpgdDead && first < blocks) {
+      jpgd_word* row = rows + lane * kJpgdRowDwords;
+      JpgdRun x{(uint32_t)e[0], e[1], 0u, {e[3], e[4], e[5]}};
+      JpgdRaw b;
+      bool bad = false;
+      jpgd_sync_run(b, mine + L.unst + rec[0], len, jpgd_sync_end((uint32_t)q, S, len), q == rec[2] - 1, blocks - first, plan[JPGD_P_HS] * plan[JPGD_P_VS], bpm, x,
+                    [&](JpgdRaw& bits, int c, int32_t& pred, uint32_t n) {
+                      jpgd_word* r = row;  // the captured pointer, once
+#pragma unroll
+                      for (int w = 0; w < 32; ++w) r[w] = 0;
+                      if (!jpgd_block(bits, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pred, (jpgd_half*)r)) {
+                        bad = true;
+                        return false;
+                      }
+                      uint4* dst = (uint4*)(mine_coef + (size_t)(first + n) * 64);
+#pragma unroll
+                      for (int w = 0; w < 8; ++w) dst[w] = uint4{(unsigned)r[4 * w], (unsigned)r[4 * w + 1], (unsigned)r[4 * w + 2], (unsigned)r[4 * w + 3]};
+                      return true;
+                    });
+      int st = jpgd_past_end(b) ? JPGD_ST_PAST_END : 0;
+      if (bad) {
+        st |= JPGD_ST_BAD_CODE;
+        if ((uint32_t)rec[3] == blocks)  // died behind the data
+          for (uint32_t g = first + x.n; g < blocks; ++g)
+#pragma unroll
+            for (int w = 0; w < 8; ++w) ((uint4*)(mine_coef + (size_t)g * 64))[w] = zero4;
+      }
+      if (st) atomicOr(status + f, st);
+    }
+  }
+  for (int k = i; k < n_int; k += (int)gridDim.x * kJpgdLanes) {
+    int16_t* mine_coef = coef + (size_t)k * span * bpm * 64;
+    for (uint32_t g = (uint32_t)iv[JPGD_X_INT * k + 3], blocks = jpgd_split_blocks(k, span, nmcu, bpm); g < blocks; ++g)
+#pragma unroll
+      for (int w = 0; w < 8; ++w) ((uint4*)(mine_coef + (size_t)g * 64))[w] = zero4;
+  }
 }
 
 __global__ __launch_bounds__(kJpgdIdctBlocks * 8) void jpgd_idct_kernel(const int* __restrict__ plan, JpgdLaunch L, uint8_t* __restrict__ work) {

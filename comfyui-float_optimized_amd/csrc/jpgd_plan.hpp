@@ -189,8 +189,9 @@ struct JpgdWork {
   size_t seg, coef, plane[3], frame;  // byte offsets inside a frame's share, and its size
   int pw, ph, cw, ch;                 // the planes' allocated sizes: whole blocks
   long long nblocks;
-  size_t unst, table;  // with a frame on the sync route: the longest such scan without its stuffing, the lane table
-  int sync_lanes;      // the most lanes such a frame can need: the stuffed length bounds the true one.  0: no such frame
+  size_t unst, table;  // with a frame on the sync or the split route: the longest such scan without its stuffing, the lane table
+  int sync_lanes;      // the most lanes a frame on the sync route can need: the stuffed length bounds the true one.  0: no such frame
+  int split_lanes;     // the same for the split route, whose table is the longer one
 };
 inline size_t jpgd_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline JpgdWork jpgd_work(const int32_t* plan) {
@@ -210,23 +211,26 @@ inline JpgdWork jpgd_work(const int32_t* plan) {
     if (!r[JPGD_F_ROUTE]) continue;
     const long long bytes = r[JPGD_F_SCAN1] - r[JPGD_F_SCAN0];
     scan = std::max(scan, bytes);
-    k.sync_lanes = (int)std::max<long long>(k.sync_lanes, std::min<long long>(kJpgdSyncLanes, std::max<long long>(1, (bytes + r[JPGD_F_ROUTE] - 1) / r[JPGD_F_ROUTE])));
+    if (r[JPGD_F_ROUTE] > 0)
+      k.sync_lanes = (int)std::max<long long>(k.sync_lanes, std::min<long long>(kJpgdSyncLanes, std::max<long long>(1, (bytes + r[JPGD_F_ROUTE] - 1) / r[JPGD_F_ROUTE])));
+    else  // a lane per interval and the bytes' share: jpgd_split_sub
+      k.split_lanes = (int)std::max<long long>(k.split_lanes, std::min<long long>(kJpgdSyncLanes, r[JPGD_F_NINT] + (bytes - r[JPGD_F_ROUTE] - 1) / -r[JPGD_F_ROUTE]));
   }
-  if (k.sync_lanes) {
+  if (k.sync_lanes || k.split_lanes) {
     k.unst = k.frame;
     k.table = k.unst + jpgd_align16((size_t)scan);
-    k.frame = k.table + jpgd_align16(kJpgdTableInts * sizeof(int32_t));
+    k.frame = k.table + jpgd_align16((k.split_lanes ? kJpgdSplitTableInts : kJpgdTableInts) * sizeof(int32_t));
   }
   return k;
 }
 inline bool jpgd_plan_ok(const int32_t* plan) { return plan && plan[JPGD_P_MAGIC] == kJpgdMagic && plan[JPGD_P_N] >= 1; }
 
 // n files in host memory -> the plan.  1 with the reason (and the frame) in err.  entropy: 0 every frame on the interval route,
-// 1 the sync route for every frame with one interval, 2 for those whose scan has at least kJpgdSyncLanes kJpgdSyncBytes bytes;
-// sync_bytes: the shortest subsequence (0: kJpgdSyncBytes).
+// 1 the sync route for every frame with one interval, 2 for those whose scan has at least kJpgdSyncLanes kJpgdSyncBytes bytes,
+// 3 the split route for every frame with at most kJpgdSplitIntervals intervals; sync_bytes: the shortest subsequence (0: kJpgdSyncBytes).
 inline int jpgd_build_plan(const uint8_t* files, const int64_t* offsets, int32_t n, int32_t* plan, size_t plan_ints, char* err, size_t errn,
                            int32_t entropy = 0, int32_t sync_bytes = 0) {
-  if (entropy < 0 || entropy > 2) return jpgd_fail(err, errn, "entropy (%d) must be 0 (interval), 1 (sync) or 2 (auto)", entropy);
+  if (entropy < 0 || entropy > 3) return jpgd_fail(err, errn, "entropy (%d) must be 0 (interval), 1 (sync), 2 (auto) or 3 (split)", entropy);
   if (sync_bytes < 0 || sync_bytes > kJpgdSyncMaxBytes) return jpgd_fail(err, errn, "sync_bytes (%d) must be 0 (the default, %d) or 1 ... %d", sync_bytes, kJpgdSyncBytes, kJpgdSyncMaxBytes);
   if (plan_ints < jpgd_plan_ints(n)) return jpgd_fail(err, errn, "plan_ints %zu < float_jpg_decode_plan_ints(%d) = %zu", plan_ints, n, jpgd_plan_ints(n));
   memset(plan, 0, JPGD_P_HEADER * sizeof(int32_t));
@@ -258,8 +262,11 @@ inline int jpgd_build_plan(const uint8_t* files, const int64_t* offsets, int32_t
     r[JPGD_F_SCAN0] = (int32_t)f.scan0, r[JPGD_F_SCAN1] = (int32_t)f.scan1, r[JPGD_F_SPAN] = span, r[JPGD_F_NINT] = (nmcu + span - 1) / span;
     r[JPGD_F_SET] = set;
     const long long scan = f.scan1 - f.scan0;
-    if (entropy && r[JPGD_F_NINT] == 1 && scan < kJpgdSyncScan && (entropy == 1 || scan >= kJpgdSyncLanes * kJpgdSyncBytes))
+    if (entropy == 3) {
+      if (r[JPGD_F_NINT] <= kJpgdSplitIntervals && scan < kJpgdSyncScan) r[JPGD_F_ROUTE] = -(sync_bytes ? sync_bytes : kJpgdSyncBytes);
+    } else if (entropy && r[JPGD_F_NINT] == 1 && scan < kJpgdSyncScan && (entropy == 1 || scan >= kJpgdSyncLanes * kJpgdSyncBytes)) {
       r[JPGD_F_ROUTE] = sync_bytes ? sync_bytes : kJpgdSyncBytes;
+    }
     maxint = std::max(maxint, r[JPGD_F_NINT]);
   }
   plan[JPGD_P_MAGIC] = kJpgdMagic, plan[JPGD_P_N] = n, plan[JPGD_P_NSETS] = nsets, plan[JPGD_P_MAXINT] = maxint;
@@ -272,11 +279,12 @@ inline int jpgd_build_plan(const uint8_t* files, const int64_t* offsets, int32_t
 // ---------------------------------------------------------------- the host path: frame i of the plan through the rule header
 // The sync route over the segment [p, end), the kernels' steps with the lanes as a plain loop: unstuff, relax until no exit
 // changes (n_sub rounds at most), prefix, write.  coef: nblocks zeroed blocks.  Returns the BAD_CODE and PAST_END bits.
-inline int jpgd_host_sync(const uint8_t* p, const uint8_t* end, const int32_t* set, int hv, int bpm, uint32_t sync_bytes, long long nblocks, int16_t* coef) {
-  std::vector<uint8_t> u;
+inline void jpgd_host_unstuff(const uint8_t* p, const uint8_t* end, std::vector<uint8_t>& u) {
   for (const uint8_t* q = p; q < end; ++q)
     if (!(*q == 0 && q > p && q[-1] == 0xFF)) u.push_back(*q);
-  const uint32_t len = (uint32_t)u.size(), S = jpgd_sync_sub(len, sync_bytes), nsub = jpgd_sync_lanes(len, S);
+}
+// one chain: `len` bytes without stuffing as nsub subsequences of S bytes, nblocks blocks from coef on
+inline int jpgd_host_lanes(const uint8_t* u, uint32_t len, uint32_t S, uint32_t nsub, const int32_t* set, int hv, int bpm, long long nblocks, int16_t* coef) {
   std::vector<JpgdRun> entry(nsub), exit(nsub);
   const auto skip = [&](JpgdRaw& b, int c, int32_t& pred, uint32_t) { return jpgd_block(b, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pred, JpgdNoCoef()); };
   JpgdRaw b;
@@ -290,7 +298,7 @@ inline int jpgd_host_sync(const uint8_t* p, const uint8_t* end, const int32_t* s
         continue;
       } else entry[i].p = exit[i - 1].p, entry[i].j = exit[i - 1].j;
       JpgdRun x = entry[i];
-      jpgd_sync_run(b, u.data(), len, jpgd_sync_end(i, S, len), false, 0xFFFFFFFFu, hv, bpm, x, skip);
+      jpgd_sync_run(b, u, len, jpgd_sync_end(i, S, len), false, 0xFFFFFFFFu, hv, bpm, x, skip);
       changed = changed || r == 0 || x.p != exit[i].p || x.j != exit[i].j;
       exit[i] = x;
     }
@@ -302,7 +310,7 @@ inline int jpgd_host_sync(const uint8_t* p, const uint8_t* end, const int32_t* s
   for (uint32_t i = 0; i < nsub && first < nblocks && entry[i].p != kJpgdDead; ++i) {  // a dead entry: the chain ended, the rest keeps its zeros
     JpgdRun x{entry[i].p, entry[i].j, 0u, {pred[0], pred[1], pred[2]}};
     bool bad = false;
-    jpgd_sync_run(b, u.data(), len, jpgd_sync_end(i, S, len), i == nsub - 1, (uint32_t)(nblocks - first), hv, bpm, x, [&](JpgdRaw& bits, int c, int32_t& pr, uint32_t k) {
+    jpgd_sync_run(b, u, len, jpgd_sync_end(i, S, len), i == nsub - 1, (uint32_t)(nblocks - first), hv, bpm, x, [&](JpgdRaw& bits, int c, int32_t& pr, uint32_t k) {
       int16_t* blk = coef + (size_t)(first + k) * 64;
       if (jpgd_block(bits, jpgd_huff(set, c, 0), jpgd_huff(set, c, 1), pr, blk)) return true;
       memset(blk, 0, 128);
@@ -315,6 +323,33 @@ inline int jpgd_host_sync(const uint8_t* p, const uint8_t* end, const int32_t* s
     first += exit[i].n;
     for (int c = 0; c < 3; ++c) pred[c] = jpgd_add(pred[c], exit[i].dc[c]);
     if (bad) break;
+  }
+  return st;
+}
+inline int jpgd_host_sync(const uint8_t* p, const uint8_t* end, const int32_t* set, int hv, int bpm, uint32_t sync_bytes, long long nblocks, int16_t* coef) {
+  std::vector<uint8_t> u;
+  jpgd_host_unstuff(p, end, u);
+  const uint32_t len = (uint32_t)u.size(), S = jpgd_sync_sub(len, sync_bytes);
+  return jpgd_host_lanes(u.data(), len, S, jpgd_sync_lanes(len, S), set, hv, bpm, nblocks, coef);
+}
+// The split route over the interval table seg[2 n_int] (-1: no segment): every segment into one copy, the lanes dealt out by
+// jpgd_split_sub, then interval by interval a chain of its own - the kernels relax all intervals in the same rounds.
+inline int jpgd_host_split(const uint8_t* file, const int32_t* seg, int n_int, int span, int nmcu, const int32_t* set, int hv, int bpm, uint32_t sync_bytes,
+                           int16_t* coef) {
+  std::vector<uint8_t> u;
+  std::vector<uint32_t> start((size_t)n_int + 1, 0);
+  uint32_t present = 0;
+  for (int k = 0; k < n_int; ++k) {
+    if (seg[2 * k] >= 0) jpgd_host_unstuff(file + seg[2 * k], file + seg[2 * k + 1], u), ++present;
+    start[k + 1] = (uint32_t)u.size();
+  }
+  const uint32_t S = jpgd_split_sub((uint32_t)u.size(), present, sync_bytes);
+  int st = 0;
+  for (int k = 0; k < n_int; ++k) {
+    if (seg[2 * k] < 0) continue;
+    const uint32_t len = start[k + 1] - start[k];
+    st |= jpgd_host_lanes(u.data() + start[k], len, S, jpgd_split_lanes(len, S), set, hv, bpm, jpgd_split_blocks(k, span, nmcu, bpm),
+                          coef + (size_t)k * span * bpm * 64);
   }
   return st;
 }
@@ -342,7 +377,8 @@ inline void jpgd_host_frame(const uint8_t* files, const int64_t* offsets, const 
   if (cnt != n_int - 1) st |= JPGD_ST_RESTARTS;
   // entropy decode
   std::vector<int16_t> coef((size_t)k.nblocks * 64, 0);
-  if (fr[JPGD_F_ROUTE]) st |= jpgd_host_sync(file + seg[0], file + seg[1], set, hs * vs, bpm, (uint32_t)fr[JPGD_F_ROUTE], k.nblocks, coef.data());
+  if (fr[JPGD_F_ROUTE] < 0) st |= jpgd_host_split(file, seg.data(), n_int, span, nmcu, set, hs * vs, bpm, (uint32_t)-fr[JPGD_F_ROUTE], coef.data());
+  if (fr[JPGD_F_ROUTE] > 0) st |= jpgd_host_sync(file + seg[0], file + seg[1], set, hs * vs, bpm, (uint32_t)fr[JPGD_F_ROUTE], k.nblocks, coef.data());
   for (int iv = 0; iv < n_int && !fr[JPGD_F_ROUTE]; ++iv) {
     if (seg[2 * iv] < 0) continue;  // no segment: the interval keeps its zeros
     JpgdBits b;

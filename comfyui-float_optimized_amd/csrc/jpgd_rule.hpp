@@ -33,8 +33,8 @@ enum {
   JPGD_P_SETS,     // word index of table set 0
   JPGD_P_HEADER = 16
 };
-// scan bytes [SCAN0, SCAN1) of the file; MCUs per interval; ROUTE: 0 = one lane per restart interval, else the sync route (below) with
-// that many bytes as its shortest subsequence
+// scan bytes [SCAN0, SCAN1) of the file; MCUs per interval; ROUTE: 0 = one lane per restart interval, above 0 the sync route (below)
+// with that many bytes as its shortest subsequence, below 0 the split route (further below) with minus that many
 enum { JPGD_F_SCAN0 = 0, JPGD_F_SCAN1, JPGD_F_SPAN, JPGD_F_NINT, JPGD_F_SET, JPGD_F_ROUTE, JPGD_F_INTS = 8 };
 constexpr int32_t kJpgdMagic = 0x4A504744;
 // a Huffman table: look[512] uint16 (length << 8 | symbol of every 9-bit prefix, 0: longer or none), maxcode[18], valoff[18], vals[256] uint8
@@ -218,6 +218,34 @@ JPGD_HD void jpgd_sync_run(JpgdRaw& b, const uint8_t* u, uint32_t len, uint32_t 
     x.j = x.j + 1 == bpm ? 0 : x.j + 1;
     x.p = jpgd_raw_pos(b);
   }
+}
+
+// ---------------------------------------------------------------- the split route: a scan WITH restart markers, many lanes
+// A restart marker is a point where the serial state is known: a byte boundary, block 0 of an MCU, predictions 0.  So every
+// interval's segment is copied without its stuffing into one buffer per frame, interval k becomes jpgd_split_lanes(len_k, S)
+// subsequences of S = jpgd_split_sub(...) bytes - the frame's kJpgdSyncLanes lanes dealt out by length -, and the sync route's
+// relaxation runs inside each interval: positions are bit offsets from the interval's first byte, the interval's first lane
+// enters at the true (0, 0), a lane takes its predecessor's exit inside its interval only, and block counts and DC sums are
+// prefixed per interval.  An interval without a segment (too few markers) has no lane and keeps its zeros.  The frame's ROUTE
+// word is minus the shortest subsequence.
+constexpr int kJpgdSplitIntervals = kJpgdSyncLanes / 2;  // frames with more intervals stay on the interval route
+// the table in `work`: the sync route's header, then per lane (entry p, entry j, first block inside the interval, pred[3],
+// interval, lane inside the interval), then per interval (first byte in the copy, bytes, lanes, first block to zero inside it)
+enum { JPGD_X_LANE = 8, JPGD_X_INT = 4 };
+constexpr int kJpgdSplitLaneAt = JPGD_T_HEADER, kJpgdSplitIntAt = kJpgdSplitLaneAt + kJpgdSyncLanes * JPGD_X_LANE;
+constexpr int kJpgdSplitTableInts = kJpgdSplitIntAt + kJpgdSplitIntervals * JPGD_X_INT;
+
+// S: `present` <= kJpgdSplitIntervals intervals have a segment, `total` bytes in all.  Every such interval gets a lane, the
+// bytes share the rest: sum of jpgd_split_lanes <= present + total / S <= kJpgdSyncLanes.
+JPGD_HD uint32_t jpgd_split_sub(uint32_t total, uint32_t present, uint32_t sync_bytes) {
+  const uint32_t room = (uint32_t)kJpgdSyncLanes - present, s = (total + room - 1) / room;
+  return s > sync_bytes ? s : sync_bytes;
+}
+JPGD_HD uint32_t jpgd_split_lanes(uint32_t len, uint32_t S) { return len ? (len + S - 1) / S : 1u; }
+// the blocks of interval k: `span` MCUs, fewer in the frame's last
+JPGD_HD uint32_t jpgd_split_blocks(int k, int span, int nmcu, int bpm) {
+  const long long m0 = (long long)k * span, m1 = m0 + span < nmcu ? m0 + span : nmcu;
+  return (uint32_t)((m1 - m0) * bpm);
 }
 
 // ---------------------------------------------------------------- jidctint.c ("islow"): one 8-point pass

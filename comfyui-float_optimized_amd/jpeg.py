@@ -135,16 +135,18 @@ def host_files(files):
     return data, torch.tensor(edges, dtype=torch.int64)
 
 
-ENTROPY = {None: 0, "interval": 0, "sync": 1, "auto": 2}
+ENTROPY = {None: 0, "interval": 0, "sync": 1, "auto": 2, "split": 3}
 
 
 def entropy_id(entropy, sync_bytes=None):
     """(entropy, sync_bytes) of the decode calls -> float_jpg_decode_plan_entropy's two integers.  entropy: None or "interval" (a
     lane per restart interval), "sync" (every frame WITHOUT restart markers has its scan cut into up to 1024 subsequences that
-    as many lanes decode, bit for bit the serial result) or "auto" (sync for such frames from 64 KB of scan on).  sync_bytes:
-    the shortest subsequence, 1 ... 65536; None is the library's default."""
+    as many lanes decode, bit for bit the serial result), "auto" (sync for such frames from 64 KB of scan on) or "split" (every
+    frame with at most 512 restart intervals has its intervals cut into subsequences, up to 1024 per frame dealt out by the
+    intervals' lengths, and the chains never cross a marker; a frame without markers is one interval and decodes as under
+    "sync").  sync_bytes: the shortest subsequence, 1 ... 65536; None is the library's default."""
     if entropy not in ENTROPY:
-        raise ValueError("entropy must be None, \"interval\", \"sync\" or \"auto\" (got %r)" % (entropy,))
+        raise ValueError("entropy must be None, \"interval\", \"sync\", \"auto\" or \"split\" (got %r)" % (entropy,))
     if sync_bytes is not None and (isinstance(sync_bytes, bool) or not isinstance(sync_bytes, int) or not 1 <= sync_bytes <= 65536):
         raise ValueError("sync_bytes must be None or an int in 1 ... 65536 (got %r)" % (sync_bytes,))
     return ENTROPY[entropy], 0 if sync_bytes is None else sync_bytes
@@ -154,7 +156,7 @@ class JpegPlan:
     """float_jpg_decode_plan of n files in host memory (data, offsets as host_files gives them): `.ints` the plan as an int32 host
     tensor cut to the words in use, and n, h, w, components, sampling, group.  No GPU is needed; what float_jpg_decode_plan
     refuses is a ValueError naming the frame.  entropy, sync_bytes: entropy_id's; anything but None / "interval" goes through
-    float_jpg_decode_plan_entropy, and a plan in which no frame takes the sync route is the plain plan word for word."""
+    float_jpg_decode_plan_entropy, and a plan in which no frame takes the sync or the split route is the plain plan word for word."""
 
     def __init__(self, data, offsets, entropy=None, sync_bytes=None):
         route, sync = entropy_id(entropy, sync_bytes)
@@ -176,7 +178,7 @@ class JpegPlan:
 
 def decode_jpeg_host(files, entropy=None, sync_bytes=None):
     """float_jpg_decode_host: the kernels' rule run on the host, no GPU -> ((n, H, W, 3) uint8 host tensor, (n,) int32 status).
-    entropy, sync_bytes: as in decode_jpeg_device; the sync route's steps then run with its lanes as a loop."""
+    entropy, sync_bytes: as in decode_jpeg_device; the sync and split routes' steps then run with their lanes as a loop."""
     data, offsets = host_files(files)
     plan = JpegPlan(data, offsets, entropy, sync_bytes)
     out = torch.empty(plan.n, plan.h, plan.w, 3, dtype=torch.uint8)
@@ -220,7 +222,10 @@ def decode_jpeg_device(files, offsets=None, strict=True, out=None, device=None, 
     entropy: None or "interval" gives every restart interval a lane, so a file without restart markers - what ffmpeg, Pillow
     and most cameras write - is decoded by a single lane; "sync" cuts such a file's scan into up to 1024 subsequences, decoded
     by as many lanes that fall into step with the serial decode (entropy_id; three more launches per group, the same bytes);
-    "auto" does so from 64 KB of scan on.  Files with restart markers take the interval route whatever entropy says.
+    "auto" does so from 64 KB of scan on.  Files with restart markers take the interval route under these.  "split" (opt-in)
+    cuts the intervals of a file with up to 512 of them into subsequences as well, up to 1024 lanes per frame whose chains stop
+    at the markers: for files with a marker every few MCU rows, which the interval route decodes on a handful of lanes; files
+    with more intervals keep a lane per interval, files without markers decode as under "sync".
     sync_bytes: the shortest subsequence (None: the library's default).
     strict: a frame whose status word is not 0 raises ValueError naming the first such frame (one read-back of T words, which
     synchronises); strict=False returns the definition's pixels for damaged frames too and reads nothing back.

@@ -754,7 +754,8 @@ class InferenceAgent:
         time, float_jpg_decode makes the uint8 frames in the reused device buffer, and the result is bit for bit align_driving on
         host_models.jpeg_decode_rgb8 of every frame.  A damaged frame (a non-zero status word) is a ValueError naming it.
         entropy: jpeg.decode_jpeg_device's, for such a clip - "sync" or "auto" spread a frame WITHOUT restart markers (ffmpeg's
-        and most cameras' files) over up to 1024 lanes, where None decodes it on one; the frames are the same bytes.
+        and most cameras' files) over up to 1024 lanes, where None decodes it on one; "split" does so for frames WITH
+        restart markers too (up to 512 intervals, capture cards' one marker every few MCU rows); the frames are the same bytes.
         video may also be 8-bit YUV 4:2:0 as decoders, cameras and `ffmpeg -pix_fmt yuv420p` deliver it - an image.YuvFrames (I420
         or NV12, host or device), a host_models.Y4MReader or the path of a .y4m file: the planes cross PCIe as they are, half the
         bytes of uint8 RGB, and float_img_front_frames_yuv converts, crops and resizes in one pass; frame t is bitwise

@@ -859,8 +859,8 @@ int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, in
  * only: allocates nothing, synchronises nothing, and the only atomics are ORs into the status words, so two calls give equal
  * bytes.  float_jpg_decode_host runs the same rule on the host (everything in host memory; the test and sanitizer path).
  *
- * float_jpg_decode_plan_entropy is float_jpg_decode_plan with a choice of the entropy route for frames WITHOUT restart markers
- * (one interval; what ffmpeg, Pillow and most cameras write).  entropy 0: the interval route for every frame, the plan of
+ * float_jpg_decode_plan_entropy is float_jpg_decode_plan with a choice of the entropy route: 1 and 2 for frames WITHOUT restart
+ * markers (one interval; what ffmpeg, Pillow and most cameras write), 3 for frames with up to 512 intervals.  entropy 0: the interval route for every frame, the plan of
  * float_jpg_decode_plan word for word.  1: the sync route for every frame with one interval and a scan below 256 MiB.  2: for
  * those whose scan has at least 1024 x 64 bytes.  Frames with more intervals stay on the interval route, and a plan in which no
  * frame takes the sync route is entropy 0's: the same words, work size and launches.  sync_bytes: the shortest subsequence,
@@ -872,7 +872,18 @@ int float_jpg_encode_padded(const uint8_t* rgb8, int32_t n_frames, int32_t h, in
  * launch decodes once more into the coefficient buffer.  Pixels and status words are the interval route's, bit for bit, for
  * damaged scans too.  Three more kernels per group that holds such a frame; `work` grows by the longest such scan and a lane
  * table of 24 KB per frame of a group (float_jpg_decode_work_bytes says so); float_jpg_decode_host follows the plan's route with
- * the lanes as a loop.  An entropy or sync_bytes outside these values is FLOAT_E_INVALID. */
+ * the lanes as a loop.
+ * entropy 3, the split route, is for frames WITH restart markers whose intervals are few and long (a marker every few MCU rows):
+ * every frame with at most 512 intervals and a scan below 256 MiB takes it, one interval included; a frame with more keeps
+ * the interval route, and a plan in which none takes it is entropy 0's.  All segments of a frame are copied without stuffing
+ * into one buffer; with `present` segments of `total` bytes, S = max(sync_bytes, ceil(total / (1024 - present))) and interval i
+ * gets max(1, ceil(len_i / S)) lanes, at most 1024 in all, dealt out on the device; an interval without a segment (too few
+ * markers) gets none and stays zero.  The relaxation runs inside each interval: its first lane enters at the interval's first
+ * bit, block 0 of an MCU, predictions 0; no lane takes an exit from another interval; the prefix is per interval; the longest
+ * interval's lane count bounds the loop.  The write pass stops a lane at its interval's last block and feeds an interval's
+ * last lane zero bits past the interval's end.  Pixels and status words are the interval route's, bit for bit, for damaged
+ * scans too.  Three kernels per group that holds such a frame; the table is 40 KB per frame of a group.
+ * An entropy or sync_bytes outside these values is FLOAT_E_INVALID. */
 size_t float_jpg_decode_plan_ints(int32_t n_frames);
 int float_jpg_decode_plan(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints);
 int float_jpg_decode_plan_entropy(const uint8_t* files, const int64_t* offsets, int32_t n_frames, int32_t* plan, size_t plan_ints, int32_t entropy,

@@ -8,7 +8,10 @@ markers.  All routes interleaved in one process, medians of JPEGDEC_REPS (10) re
 Bytes across PCIe: the files against T x 1080 x 1920 x 3.  JPEGDEC_FRAMES / JPEGDEC_REPS shrink the run for a rehearsal.
 --entropy sync|auto adds, interleaved with the others: to (a) the clip without restart markers through that entropy route, once per
 value of --sync-bytes (a comma list, default: the library's), with the relaxation's rounds over the last group's frames; to (b)
-drive_video from that clip with entropy= set."""
+drive_video from that clip with entropy= set.
+--entropy split adds a third clip with one restart marker every 17 MCU rows (4 intervals a frame, a capture card's shape) and,
+interleaved with the others: to (a) that clip without it, both clips WITH markers through the split route once per value of
+--sync-bytes, and the clip without markers under "auto" for comparison; to (b) drive_video from the three."""
 import argparse
 import importlib
 import io
@@ -27,7 +30,7 @@ from tests.util import load_pkg  # noqa: E402
 pkg = load_pkg()
 J, Wt = pkg.jpeg, pkg.weights
 ap = argparse.ArgumentParser()
-ap.add_argument("--entropy", choices=("sync", "auto"), default=None)
+ap.add_argument("--entropy", choices=("sync", "auto", "split"), default=None)
 ap.add_argument("--sync-bytes", default="")
 args = ap.parse_args()
 SYNC = [int(v) for v in args.sync_bytes.split(",") if v] or [None]
@@ -42,7 +45,8 @@ for t in range(T):
     base = torch.stack([128 + 100 * torch.sin((xx + 3 * t) / 70.0 + c) * torch.cos(yy / 50.0 - c) for c in range(3)], -1)
     frames[t] = (base + 6 * torch.randn(H, W, 3, device="cuda", generator=g)).clamp_(0, 255).to(torch.uint8)
 clips = {}
-for name, restart in (("restart per MCU row", None), ("no restart markers", 0)):
+COARSE = "restart every 17 MCU rows"
+for name, restart in (("restart per MCU row", None), ("no restart markers", 0)) + (((COARSE, 17 * -(-W // 16)),) if args.entropy == "split" else ()):
     data, offsets = J.encode_jpeg_device(frames, 90, restart, pad="edge")
     clips[name] = J.to_host(data, offsets.cpu())
 del frames
@@ -72,7 +76,10 @@ def wall_ms(fn):
 # (a) the decode launches alone
 resident = {}
 variants = [(name, name, None, None) for name in clips]
-if args.entropy:
+if args.entropy == "split":
+    variants += [("%s, split%s" % (c, "" if S is None else " S=%d" % S), c, "split", S) for c in ("restart per MCU row", COARSE) for S in SYNC]
+    variants += [("no restart markers, auto", "no restart markers", "auto", None)]
+elif args.entropy:
     variants += [("no restart markers, %s%s" % (args.entropy, "" if S is None else " S=%d" % S), "no restart markers", args.entropy, S) for S in SYNC]
 for name, clip, entropy, S in variants:
     data, edges = J.host_files(clips[clip])
@@ -87,12 +94,13 @@ for r in range(WARM + REPS):
             ta[k].append(ms)
 for k, v in ta.items():
     m = statistics.median(v)
-    print("(a) decode, %-20s %9.2f ms per clip (spread %.2f) | %.1f GB/s of pixels | equal to the other clip's frames: %s" % (
+    print("(a) decode, %-34s %9.2f ms per clip (spread %.2f) | %.1f GB/s of pixels | equal to the other clip's frames: %s" % (
         k, m, max(v) - min(v), T * H * W * 3 / m / 1e6, torch.equal(resident[k][3], next(iter(resident.values()))[3])))
     plan, work = resident[k][2], resident[k][5]
-    if int(plan.ints[16:16 + 8 * plan.n].view(-1, 8)[:, 5].max()):  # frames on the sync route: the lane table ends a frame's share of `work`
-        per = plan.work_bytes // min(plan.n, plan.group)
-        rounds = work[:plan.work_bytes].view(-1, per)[:(plan.n - 1) % plan.group + 1, per - 24608:][:, 8:20].contiguous().view(torch.int32).cpu()
+    route = plan.ints[16:16 + 8 * plan.n].view(-1, 8)[:, 5]
+    if int(route.abs().max()):  # frames on the sync or the split route: the lane table ends a frame's share of `work`
+        per, table = plan.work_bytes // min(plan.n, plan.group), 40992 if int(route.min()) < 0 else 24608
+        rounds = work[:plan.work_bytes].view(-1, per)[:(plan.n - 1) % plan.group + 1, per - table:][:, 8:20].contiguous().view(torch.int32).cpu()
         print("    relaxation: %s lanes, rounds min %d median %d max %d (the last group's frames)" % (
             sorted(set(rounds[:, 0].tolist())), rounds[:, 2].min(), rounds[:, 2].median(), rounds[:, 2].max()))
 del resident
@@ -119,7 +127,12 @@ routes = {"mjpeg, restart per MCU row": lambda: drive(clips["restart per MCU row
           "mjpeg, no restart markers": lambda: drive(clips["no restart markers"]),
           "raw pageable uint8 video": lambda: drive(video8),
           **({"mjpeg, no restart markers, " + args.entropy: lambda: agent.drive_video(portrait, clips["no restart markers"], rects=RECT, out_dtype=torch.uint8,
-                                                                                      entropy=args.entropy)} if args.entropy else {}),
+                                                                                      entropy=args.entropy)} if args.entropy in ("sync", "auto") else {}),
+          **({"mjpeg, restart per MCU row, split": lambda: agent.drive_video(portrait, clips["restart per MCU row"], rects=RECT, out_dtype=torch.uint8, entropy="split"),
+              "mjpeg, " + COARSE: lambda: drive(clips[COARSE]),
+              "mjpeg, " + COARSE + ", split": lambda: agent.drive_video(portrait, clips[COARSE], rects=RECT, out_dtype=torch.uint8, entropy="split"),
+              "mjpeg, no restart markers, auto": lambda: agent.drive_video(portrait, clips["no restart markers"], rects=RECT, out_dtype=torch.uint8, entropy="auto")}
+             if args.entropy == "split" else {}),
           "pillow loop + raw route": lambda: drive(pillow_loop()),
           "pillow loop alone": pillow_loop}
 tb = {k: [] for k in routes}
@@ -129,4 +142,4 @@ for r in range(1 + REPS):
         if r >= 1:
             tb[k].append(ms)
 for k, v in tb.items():
-    print("(b) %-28s %9.1f ms per clip (spread %.1f)" % (k, statistics.median(v), max(v) - min(v)))
+    print("(b) %-42s %9.1f ms per clip (spread %.1f)" % (k, statistics.median(v), max(v) - min(v)))

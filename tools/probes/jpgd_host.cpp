@@ -1,12 +1,13 @@
 // Stand-alone run of the JPEG decoder's rule on the host (csrc/jpgd_rule.hpp through csrc/jpgd_plan.hpp's host path), for a
 // sanitizer build: no HIP, no Python.
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/probes/jpgd_host.cpp -o jpgd_host
-//   jpgd_host [--selftest] [--mangle] [--sync S] file.jpg ...
+//   jpgd_host [--selftest] [--mangle] [--sync S | --split S] file.jpg ...
 // Every file is planned and decoded as given; FILE.rgb beside it, when present, must hold the decoded bytes (host_models.
 // jpeg_decode_rgb8's).  --mangle: also every file cut at 64 places and with a bit flipped at 256 places, header and scan alike:
 // a refusal by the plan or a decode with a status word, never an access outside the file's bytes.  Each mangled copy lives in a
 // heap block of exactly its size, so that the sanitizer sees one byte too far.  --sync S (before the files): every decode runs a
-// second time with the sync entropy route and subsequences of S bytes, and must give the interval route's bytes and status word.
+// second time with the sync entropy route and subsequences of S bytes, and must give the interval route's bytes and status word;
+// --split S: the same with the split route, which also takes files with restart markers.
 #include <stdlib.h>
 
 #include <string>
@@ -23,7 +24,7 @@ static std::vector<uint8_t> slurp(const std::string& path) {
   return v;
 }
 
-static int g_sync = 0, g_sync_differs = 0;
+static int g_sync = 0, g_sync_differs = 0, g_entropy = 1;
 
 // 0 decoded, 1 refused; rgb and status filled when decoded
 static int decode(const uint8_t* bytes, size_t n, std::vector<uint8_t>* rgb, int32_t* status, std::string* why) {
@@ -39,7 +40,7 @@ static int decode(const uint8_t* bytes, size_t n, std::vector<uint8_t>* rgb, int
     if (g_sync) {
       std::vector<uint8_t> again(rgb->size(), 0);
       int32_t st = -1;
-      if (jpgd_build_plan(exact, offsets, 1, plan.data(), plan.size(), err, sizeof(err), 1, g_sync)) st = -2;
+      if (jpgd_build_plan(exact, offsets, 1, plan.data(), plan.size(), err, sizeof(err), g_entropy, g_sync)) st = -2;
       else jpgd_host_frame(exact, offsets, plan.data(), 0, again.data(), &st);
       g_sync_differs += st != *status || again != *rgb;
     }
@@ -134,7 +135,8 @@ int main(int argc, char** argv) {
       mangle = true;
       continue;
     }
-    if (std::string(argv[a]) == "--sync" && a + 1 < argc) {
+    if ((std::string(argv[a]) == "--sync" || std::string(argv[a]) == "--split") && a + 1 < argc) {
+      g_entropy = std::string(argv[a]) == "--split" ? 3 : 1;
       g_sync = atoi(argv[++a]);
       continue;
     }
@@ -164,6 +166,6 @@ int main(int argc, char** argv) {
   }
   printf("%d files; mangled copies: %d refused, %d decoded with a status, %d decoded clean; %d differ from their .rgb\n", files, refused, flagged,
          clean, wrong);
-  if (g_sync) printf("--sync %d: %d decodes differ from the interval route\n", g_sync, g_sync_differs);
+  if (g_sync) printf("%s %d: %d decodes differ from the interval route\n", g_entropy == 3 ? "--split" : "--sync", g_sync, g_sync_differs);
   return wrong || g_sync_differs ? 1 : 0;
 }
