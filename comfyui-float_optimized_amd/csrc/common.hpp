@@ -405,6 +405,17 @@ __device__ __forceinline__ unsigned fh_yuv_to_rgb(const FhYuvInv& t, int Y, int 
   const int r = (y + t.crv * v) >> 14, g = (y - t.cgu * u - t.cgv * v) >> 14, b = (y + t.cbu * u) >> 14;
   return (unsigned)min(max(r, 0), 255) | ((unsigned)min(max(g, 0), 255) << 8) | ((unsigned)min(max(b, 0), 255) << 16);
 }
+// The same pixel from samples of depth 8 + s (host_models.yuv_planes_to_rgb8): offsets and the rounding term scale by 2^s and the
+// shift grows by s, so s = 0 is fh_yuv_to_rgb word for word.  BITS is the stored width: at 8 s is 0 at compile time, at 16 it is a
+// uniform argument (2 or 4).  At 12 bits the largest sum is 19077 * 4095 + 34610 * 2048 < 1.6e8: int32 holds it; 16-bit samples
+// would not fit and are refused by the callers.
+template <int BITS>
+__device__ __forceinline__ unsigned fh_yuv_to_rgb_deep(const FhYuvInv& t, int s, int Y, int U, int V) {
+  if (BITS == 8) s = 0;
+  const int y = t.cy * (Y - (t.yoff << s)) + (1 << (13 + s)), u = U - (128 << s), v = V - (128 << s);
+  const int r = (y + t.crv * v) >> (14 + s), g = (y - t.cgu * u - t.cgv * v) >> (14 + s), b = (y + t.cbu * u) >> (14 + s);
+  return (unsigned)min(max(r, 0), 255) | ((unsigned)min(max(g, 0), 255) << 8) | ((unsigned)min(max(b, 0), 255) << 16);
+}
 
 // ---------------------------------------------------------------- cross-lane reductions without LDS
 // __shfl_xor compiles to ds_bpermute_b32: an LDS-pipe round trip and an s_waitcnt lgkmcnt(0) per butterfly step.  The forms

@@ -23,6 +23,7 @@ this package).  What is left is tensor plumbing:
     definition the kernels of `float_sfd_*` (face.py in this package) are held to, and the FLOAT_AMD_FACE_DETECTOR switch of
     process_img
 """
+import collections
 import fractions
 import logging
 import math
@@ -1200,6 +1201,113 @@ def yuv420_to_rgb8(frames_yuv, layout="i420", matrix=None, chroma="nearest"):
     y, u, v = cy * (y - yoff) + 8192, u - 128, v - 128
     out = torch.stack([(y + crv * v) >> 14, (y - cgu * u - cgv * v) >> 14, (y + cbu * u) >> 14], dim=-1).clamp(0, 255).to(torch.uint8)
     return out[0] if single else out
+
+
+YUV_SUBSAMPLING = {"420": (2, 2), "422": (2, 1), "444": (1, 1)}  # sub -> (hs, vs)
+# Where the planes of a frame lie, everything resolved to integers (bytes): what yuv_planes_to_rgb8 reads, what image.PlanarYuv
+# carries and the fields of float_img_planes_t.  last_end: the byte after a frame's last plane.  matrix: an id; chroma: a name.
+YuvPlanes = collections.namedtuple("YuvPlanes", "h w hs vs depth shift y_off u_off v_off y_pitch c_pitch c_step frame_stride last_end "
+                                                "matrix chroma")
+
+
+def yuv_planes_format(h, w, sub="420", depth=8, shift=0, semi=False, swap_uv=False, y_pitch=None, c_pitch=None, frame_stride=None,
+                      y_off=0, u_off=None, v_off=None, matrix=None, chroma="nearest"):
+    """The YuvPlanes record of h x w frames (odd sides allowed).  sub "420" | "422" | "444"; depth 8 | 10 | 12 (a sample is a byte,
+    or a 16-bit little-endian word read as (word >> shift) & (2^depth - 1): shift 0 is ffmpeg's ...p10le, 16 - depth is P010);
+    semi: U and V interleaved in one plane; swap_uv: V first (NV21, YV12).  Pitches, stride and offsets in bytes; None means
+    packed, in the order Y, U, V (Y, UV when semi).  ValueError where a pitch does not cover a row, planes overlap or leave the
+    frame stride, an offset, pitch or stride of 16-bit planes is odd, or sub, depth, shift or chroma is unknown.  Depth 16 is
+    refused: the int32 colour arithmetic would overflow."""
+    what = "yuv_planes_format"
+    if sub not in YUV_SUBSAMPLING:
+        raise ValueError("%s: sub must be one of %s (got %r)" % (what, sorted(YUV_SUBSAMPLING), sub))
+    if depth not in (8, 10, 12):
+        raise ValueError("%s: depth must be 8, 10 or 12 (got %r; 16-bit samples would overflow the int32 arithmetic)" % (what, depth))
+    if chroma not in YUV_CHROMA:
+        raise ValueError("%s: chroma must be one of %s (got %r)" % (what, YUV_CHROMA, chroma))
+    h, w, shift = int(h), int(w), int(shift)
+    if h < 1 or w < 1:
+        raise ValueError("%s: frames of %d x %d" % (what, h, w))
+    b = 1 if depth == 8 else 2
+    if not 0 <= shift <= 8 * b - depth:
+        raise ValueError("%s: shift must be 0 ... %d at depth %d (got %d)" % (what, 8 * b - depth, depth, shift))
+    hs, vs = YUV_SUBSAMPLING[sub]
+    cw, ch = -(-w // hs), -(-h // vs)
+    c_step = 2 * b if semi else b
+    y_row, c_row = w * b, cw * c_step  # bytes of a row; a semi-planar row holds both
+    y_pitch = y_row if y_pitch is None else int(y_pitch)
+    c_pitch = c_row if c_pitch is None else int(c_pitch)
+    if y_pitch < y_row or c_pitch < c_row:
+        raise ValueError("%s: pitches (%d, %d) must cover a row (%d, %d bytes)" % (what, y_pitch, c_pitch, y_row, c_row))
+    y_off = int(y_off)
+    first = y_off + h * y_pitch  # packed: the chroma follows the luma rows
+    if semi:
+        lo = first if u_off is None and v_off is None else min(int(o) for o in (u_off, v_off) if o is not None)
+        u_off, v_off = (lo + b, lo) if swap_uv else (lo, lo + b)
+    else:
+        a, c = (v_off, u_off) if swap_uv else (u_off, v_off)
+        a = first if a is None else int(a)
+        c = a + ch * c_pitch if c is None else int(c)
+        u_off, v_off = (c, a) if swap_uv else (a, c)
+    c_len = (ch - 1) * c_pitch + (cw - 1) * c_step + b
+    ext = [(y_off, y_off + (h - 1) * y_pitch + y_row)]
+    ext += [(min(u_off, v_off), min(u_off, v_off) + c_len + b)] if semi else [(u_off, u_off + c_len), (v_off, v_off + c_len)]
+    ext.sort()
+    if ext[0][0] < 0 or any(p[1] > q[0] for p, q in zip(ext, ext[1:])):
+        raise ValueError("%s: planes overlap or begin before the frame (bytes %s)" % (what, ext))
+    last_end = ext[-1][1]
+    frame_stride = last_end + (last_end & 1 if b == 2 else 0) if frame_stride is None else int(frame_stride)
+    if frame_stride < last_end:
+        raise ValueError("%s: frame_stride (%d) is below the last plane's end (%d)" % (what, frame_stride, last_end))
+    if b == 2 and (y_off | u_off | v_off | y_pitch | c_pitch | frame_stride) & 1:
+        raise ValueError("%s: offsets, pitches and the frame stride of 16-bit planes must be even" % what)
+    return YuvPlanes(h, w, hs, vs, depth, shift, y_off, u_off, v_off, y_pitch, c_pitch, c_step, frame_stride, last_end,
+                     yuv_matrix_id(matrix, w, h), chroma)
+
+
+def yuv_planes_frames(n_bytes, fmt):
+    """How many frames of `fmt` a buffer of n_bytes holds: (T - 1) frame_stride + last_end <= n_bytes.  ValueError for none."""
+    if n_bytes < fmt.last_end:
+        raise ValueError("yuv planes: a frame's planes end at byte %d, the buffer holds %d" % (fmt.last_end, n_bytes))
+    return (n_bytes - fmt.last_end) // fmt.frame_stride + 1
+
+
+def yuv_planes_to_rgb8(data, fmt):
+    """data: a flat uint8 tensor, the caller's buffer as it lies in memory; fmt: a YuvPlanes (yuv_planes_format) -> (T, h, w, 3)
+    uint8 RGB, T = yuv_planes_frames(data.numel(), fmt): the definition of float_img_front_frames_planes' colour conversion.  In
+    int32 at depth d, s = d - 8:
+      sample  (word >> shift) & (2^d - 1); words are 16-bit little-endian for d > 8, bytes for d = 8.
+      chroma  planes of ceil(w / hs) x ceil(h / vs).  "nearest" replicates a sample; "centre" is jpeg_upsample_plane on the d-bit
+              samples - libjpeg's h2v2 triangle rule for 4:2:0, h2v1 (3 : 1 horizontally) for 4:2:2, replication where the plane is
+              at most 2 samples wide, nothing for 4:4:4 - cropped to h x w.
+      colour  the rows of YUV_INVERSE: y = cy (Y - (yoff << s)) + (1 << (13 + s)), u = U - (128 << s), v = V - (128 << s),
+              R = clamp8((y + crv v) >> (14 + s)), G = clamp8((y - cgu u - cgv v) >> (14 + s)), B = clamp8((y + cbu u) >> (14 + s)).
+    At d = 8 this is yuv420_to_rgb8's arithmetic word for word.  Depths 8, 10 and 12 fit int32 (at 12 bits the largest sum is
+    below 1.6e8); 16-bit samples would overflow, so yuv_planes_format refuses them.  Works on any device; "centre" forms its planes
+    on the host."""
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError("yuv_planes_to_rgb8 takes a flat contiguous uint8 tensor, got %s %s"
+                         % (getattr(data, "dtype", type(data).__name__), tuple(getattr(data, "shape", ()))))
+    T = yuv_planes_frames(data.numel(), fmt)
+    h, w, hs, vs, s = fmt.h, fmt.w, fmt.hs, fmt.vs, fmt.depth - 8
+    cw, ch = -(-w // hs), -(-h // vs)
+
+    def plane(off, rows, cols, pitch, step):
+        at = lambda o: torch.as_strided(data, (T, rows, cols), (fmt.frame_stride, pitch, step), data.storage_offset() + o).to(torch.int32)  # noqa: E731
+        word = at(off) if fmt.depth == 8 else at(off) | (at(off + 1) << 8)
+        return (word >> fmt.shift) & ((1 << fmt.depth) - 1)
+
+    y = plane(fmt.y_off, h, w, fmt.y_pitch, 1 if fmt.depth == 8 else 2)
+    u, v = (plane(o, ch, cw, fmt.c_pitch, fmt.c_step) for o in (fmt.u_off, fmt.v_off))
+    if fmt.chroma == "centre":
+        up = lambda c: torch.from_numpy(jpeg_upsample_plane(c.cpu().numpy(), hs, vs)).to(data.device)  # noqa: E731
+        u, v = (torch.stack([up(c[t]) for t in range(T)]) for c in (u, v))
+    else:
+        u, v = (c.repeat_interleave(vs, dim=1).repeat_interleave(hs, dim=2) for c in (u, v))
+    u, v = u[:, :h, :w], v[:, :h, :w]
+    yoff, cy, crv, cgu, cgv, cbu = YUV_INVERSE[fmt.matrix]
+    y, u, v = cy * (y - (yoff << s)) + (1 << (13 + s)), u - (128 << s), v - (128 << s)
+    return torch.stack([(y + crv * v) >> (14 + s), (y - cgu * u - cgv * v) >> (14 + s), (y + cbu * u) >> (14 + s)], dim=-1).clamp(0, 255).to(torch.uint8)
 
 
 class Y4MReader:

@@ -156,6 +156,111 @@ class YuvFrames:
         return host_models.yuv420_to_rgb8(self.data, self.layout, self.matrix, self.chroma)
 
 
+# ffmpeg's pixel-format names (and the FOURCCs YV12 and NV21's kin) -> PlanarYuv's keywords
+PLANAR_YUV_NAMES = {
+    "yuv420p": dict(sub="420"), "yuv422p": dict(sub="422"), "yuv444p": dict(sub="444"),
+    "yuvj420p": dict(sub="420"), "yuvj422p": dict(sub="422"), "yuvj444p": dict(sub="444"),  # the same planes; the caller states the matrix
+    "yv12": dict(sub="420", swap_uv=True),
+    "nv12": dict(sub="420", semi=True), "nv21": dict(sub="420", semi=True, swap_uv=True),
+    "nv16": dict(sub="422", semi=True), "nv24": dict(sub="444", semi=True), "nv42": dict(sub="444", semi=True, swap_uv=True),
+    "yuv420p10le": dict(sub="420", depth=10), "yuv422p10le": dict(sub="422", depth=10), "yuv444p10le": dict(sub="444", depth=10),
+    "yuv420p12le": dict(sub="420", depth=12), "yuv422p12le": dict(sub="422", depth=12), "yuv444p12le": dict(sub="444", depth=12),
+    "p010": dict(sub="420", depth=10, shift=6, semi=True), "p010le": dict(sub="420", depth=10, shift=6, semi=True),
+    "p012": dict(sub="420", depth=12, shift=4, semi=True), "p012le": dict(sub="420", depth=12, shift=4, semi=True),
+    "p210": dict(sub="422", depth=10, shift=6, semi=True), "p210le": dict(sub="422", depth=10, shift=6, semi=True),
+    "p410": dict(sub="444", depth=10, shift=6, semi=True), "p410le": dict(sub="444", depth=10, shift=6, semi=True),
+}
+
+
+class PlanarYuv:
+    """A stack of planar or semi-planar YUV frames as a decoder hands them out, for front_frames_device and
+    InferenceAgent.align_driving: data, a contiguous uint8 tensor on the host or the device, read as flat bytes exactly as it lies in
+    memory, and where the h x w frames' planes are in it - host_models.yuv_planes_format has the keywords (sub "420" | "422" |
+    "444", depth 8 | 10 | 12, shift, semi, swap_uv; pitches, frame_stride and offsets in bytes, None = packed in the order Y, U, V;
+    matrix as host_models.yuv_matrix_id reads it, "auto" by w x h; chroma "nearest" | "centre").  Odd sides are allowed.  Everything
+    is checked here (ValueError).  len() is the number of frames the buffer holds: (T - 1) frame_stride + the last plane's end <=
+    data.numel().  frames[a:b] (step 1) and take(idx) are PlanarYuv objects of their own; to_rgb8() is the definition's frames.
+    PlanarYuv.of(name, data, h, w, **more) builds one from an ffmpeg pixel-format name (PLANAR_YUV_NAMES)."""
+
+    def __init__(self, data, h, w, *, sub="420", depth=8, shift=0, semi=False, swap_uv=False, y_pitch=None, c_pitch=None, frame_stride=None,
+                 y_off=0, u_off=None, v_off=None, matrix=None, chroma="nearest"):
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or not data.is_contiguous():
+            raise ValueError("PlanarYuv: data must be a contiguous uint8 tensor, got %s %s"
+                             % (getattr(data, "dtype", type(data).__name__), tuple(getattr(data, "shape", ()))))
+        self.fmt = host_models.yuv_planes_format(h, w, sub, depth, shift, semi, swap_uv, y_pitch, c_pitch, frame_stride, y_off, u_off, v_off,
+                                                 matrix, chroma)
+        self.data = data.reshape(-1)
+        self._n = host_models.yuv_planes_frames(self.data.numel(), self.fmt)
+
+    @classmethod
+    def of(cls, name, data, h, w, **more):
+        """A PlanarYuv from an ffmpeg pixel-format name: PlanarYuv.of("yuv422p10le", data, h, w, y_pitch=..., c_pitch=...)."""
+        if name not in PLANAR_YUV_NAMES:
+            raise ValueError("PlanarYuv.of: %r is not one of %s" % (name, sorted(PLANAR_YUV_NAMES)))
+        return cls(data, h, w, **dict(PLANAR_YUV_NAMES[name], **more))
+
+    def like(self, data, matrix=None, chroma=None):
+        """The same layout over another buffer (a chunk of this one's frames, or its copy on the device); matrix and chroma
+        replace this one's where given."""
+        if chroma is not None and chroma not in host_models.YUV_CHROMA:
+            raise ValueError("PlanarYuv: chroma must be one of %s (got %r)" % (host_models.YUV_CHROMA, chroma))
+        new = object.__new__(PlanarYuv)
+        new.fmt = self.fmt._replace(matrix=self.fmt.matrix if matrix is None else host_models.yuv_matrix_id(matrix, self.w, self.h),
+                                    chroma=self.fmt.chroma if chroma is None else chroma)
+        new.data = data.reshape(-1)
+        new._n = host_models.yuv_planes_frames(new.data.numel(), new.fmt)
+        return new
+
+    h, w, matrix, chroma = (property(lambda self, k=k: getattr(self.fmt, k)) for k in ("h", "w", "matrix", "chroma"))
+
+    def __len__(self):
+        return self._n
+
+    def frame_bytes(self, a, b):
+        """The bytes of frames a ... b - 1, a view: from frame a's first byte to the end of frame b - 1's last plane."""
+        if not 0 <= a < b <= self._n:
+            raise ValueError("PlanarYuv: frames %d ... %d of %d" % (a, b - 1, self._n))
+        return self.data[a * self.fmt.frame_stride:(b - 1) * self.fmt.frame_stride + self.fmt.last_end]
+
+    def __getitem__(self, key):
+        if not isinstance(key, slice) or key.step not in (None, 1):
+            raise TypeError("PlanarYuv: frames are taken by range, frames[a:b]")
+        a, b, _ = key.indices(self._n)
+        return self.like(self.frame_bytes(a, b))
+
+    def take(self, idx):
+        """The frames `idx` (a list of indices) as a PlanarYuv of their own, each copied up to its last plane's end."""
+        fmt = self.fmt
+        stride = fmt.last_end + (fmt.last_end & 1)
+        new = self.like(torch.stack([torch.nn.functional.pad(self.frame_bytes(int(i), int(i) + 1), (0, stride - fmt.last_end)) for i in idx]))
+        new.fmt = new.fmt._replace(frame_stride=stride)
+        new._n = len(idx)
+        return new
+
+    def to_rgb8(self):
+        """The definition's frames: host_models.yuv_planes_to_rgb8 -> (T, h, w, 3) uint8 on the data's device."""
+        return host_models.yuv_planes_to_rgb8(self.data, self.fmt)
+
+
+def _front_frames_planes(frames, r, dst_h, dst_w, out, sn, sd, device):
+    """front_frames_device for a PlanarYuv: float_img_front_frames_planes on the buffer as it is"""
+    device = torch.device(device if device is not None else (frames.data.device if frames.data.is_cuda else "cuda:0"))
+    x = frames.data.detach().to(device, non_blocking=True)
+    T, f = len(frames), frames.fmt
+    shape = (T, dst_h, dst_w, 3)
+    planes = native.ImgPlanes(f.hs, f.vs, f.depth, f.shift, f.y_off, f.u_off, f.v_off, f.y_pitch, f.c_pitch, f.c_step, f.frame_stride)
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != x.device or not out.is_contiguous():
+            raise ValueError("front_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
+                             % (shape, x.device, out.dtype, tuple(out.shape), out.device))
+        native.check(native.lib().float_img_front_frames_planes(
+            C.c_void_p(x.data_ptr()), x.numel(), T, f.h, f.w, C.byref(planes), f.matrix, native.YUV_CHROMA[f.chroma],
+            C.cast(r.data_ptr(), C.POINTER(C.c_int32)), sn, sd, C.c_void_p(out.data_ptr()), dst_h, dst_w, native.stream_ptr(x.device)))
+    return out
+
+
 def _front_frames_yuv(frames, r, dst_h, dst_w, out, sn, sd, device):
     """front_frames_device for a YuvFrames: float_img_front_frames_yuv"""
     device = torch.device(device if device is not None else (frames.data.device if frames.data.is_cuda else "cuda:0"))
@@ -184,8 +289,10 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
     nothing synchronises.  out: a contiguous (T, dst_h, dst_w, 3) uint8 tensor on that device to write into.
     frames may also be a YuvFrames (8-bit YUV 4:2:0, I420 or NV12): float_img_front_frames_yuv converts, crops and resizes in the
     same single pass, frame t bitwise host_models.resize_rgb8(host_models.yuv420_to_rgb8(frame t, layout, matrix, chroma),
-    rects[t], dst_h, dst_w, scale); YUV has no alpha, so rgba_conversion and bkg_color_hex are not read."""
-    yuv = isinstance(frames, YuvFrames)
+    rects[t], dst_h, dst_w, scale); YUV has no alpha, so rgba_conversion and bkg_color_hex are not read.
+    frames may also be a PlanarYuv (any planar YUV: 10 / 12 bits, 4:2:2, 4:4:4, odd sides, pitched): float_img_front_frames_planes
+    reads the buffer as it lies, frame t bitwise host_models.resize_rgb8(frames.to_rgb8()[t], rects[t], dst_h, dst_w, scale)."""
+    yuv = isinstance(frames, (YuvFrames, PlanarYuv))
     x = None if yuv else frames_to_device(frames, device)
     T, H, W, ch = (len(frames), frames.h, frames.w, 3) if yuv else (int(v) for v in x.shape)
     r = torch.as_tensor(rects, dtype=torch.int32, device="cpu").reshape(-1, 4)
@@ -196,7 +303,7 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
     r = r.contiguous()
     sn, sd = (0, 0) if scale is None else (int(scale[0]), int(scale[1]))
     if yuv:
-        return _front_frames_yuv(frames, r, int(dst_h), int(dst_w), out, sn, sd, device)
+        return (_front_frames_planes if isinstance(frames, PlanarYuv) else _front_frames_yuv)(frames, r, int(dst_h), int(dst_w), out, sn, sd, device)
     bkg = host_models.hex_to_rgb8(bkg_color_hex)
     mode = _rgba_mode(rgba_conversion)
     dst_h, dst_w = int(dst_h), int(dst_w)
@@ -217,8 +324,9 @@ def front_frames_device(frames, rects, dst_h, dst_w, rgba_conversion="blend_with
 def detector_views_device(frames, view_h=360, rgba_conversion="blend_with_color", bkg_color_hex="#000000", out=None, device=None):
     """The detector's view of every frame in one call: (T, view_h, round(W view_h / H), 3) uint8 on the device; view t is bitwise
     detector_view_device(frames[t], view_h, ...) - the whole image as every rect, both axes at the one scale H / view_h.  For a
-    YuvFrames view t is bitwise resize_rgb8(yuv420_to_rgb8(frame t, ...), None, view_h, columns, scale=(H, view_h))."""
-    H, W = (frames.h, frames.w) if isinstance(frames, YuvFrames) else (int(frames.shape[1]), int(frames.shape[2]))
+    YuvFrames view t is bitwise resize_rgb8(yuv420_to_rgb8(frame t, ...), None, view_h, columns, scale=(H, view_h)), and for a
+    PlanarYuv the same on its to_rgb8()."""
+    H, W = (frames.h, frames.w) if isinstance(frames, (YuvFrames, PlanarYuv)) else (int(frames.shape[1]), int(frames.shape[2]))
     vh, vw = detector_view_size(H, W, view_h)
     g = math.gcd(H, vh)
     return front_frames_device(frames, (0, 0, W, H), vh, vw, rgba_conversion, bkg_color_hex, out, (H // g, vh // g), device)

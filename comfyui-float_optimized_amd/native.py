@@ -69,6 +69,11 @@ class SfdCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dtype", "max_h", "max_w", "max_candidates", "max_boxes")]
 
 
+class ImgPlanes(C.Structure):  # float_img_planes_t
+    _fields_ = [(n, C.c_int32) for n in ("hs", "vs", "depth", "shift")] + [(n, C.c_int64) for n in ("y_off", "u_off", "v_off")] + \
+               [(n, C.c_int32) for n in ("y_pitch", "c_pitch", "c_step")] + [("frame_stride", C.c_int64)]
+
+
 class AudCfg(C.Structure):
     _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8)] + \
                [(n, C.c_int32) for n in ("hidden", "layers", "heads", "intermediate", "pos_k", "pos_groups", "dim_w", "only_last",
@@ -164,6 +169,8 @@ _SIGNATURES = {
                                [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "float_img_front_frames_yuv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_int32)] + [C.c_int32] * 2 +
                                    [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "float_img_front_frames_planes": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_int32] * 3 + [C.POINTER(ImgPlanes)] + [C.c_int32] * 2 +
+                                      [C.POINTER(C.c_int32)] + [C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "float_img_paste": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p]),
     "float_img_paste_i420": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]),
     "float_img_resample_plan_ints": (C.c_size_t, [C.c_int32] * 4),

@@ -12,7 +12,7 @@ from ...audio import Audio2EmotionHIP, AudioEncoderHIP, preprocess_audio_device
 from ...config import AudioConfig, FmtConfig, emotion_audio_config, small_audio_config, small_emotion_config
 from ...encoder import EncoderHIP
 from ...face import FaceDetectorHIP, find_sfd_weights, load_sfd_state
-from ...image import (YuvFrames, detector_view_device, detector_views_device, front_frames_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
+from ...image import (PlanarYuv, YuvFrames, detector_view_device, detector_views_device, front_frames_device, front_takes, image_front_device, image_to_device, paste_format, preprocess_image_device, require_even_sides,
                       require_jpeg_sides, source_rgb8_device)
 from ...pipeline import FloatHotPath, Placement, resolve_out_format, precision_policy, report_precision, report_range, verify_frames_default
 from . import SYNTHETIC_MODEL, main_logger
@@ -599,7 +599,7 @@ class InferenceAgent:
         face = self._face_handle(path) if fa is None else None
         rows = []
         for at in range(0, len(idx), 16):
-            if isinstance(video, YuvFrames):  # the same kernel on the planes; 360 rows or less: the definition's frames on the host
+            if isinstance(video, (YuvFrames, PlanarYuv)):  # the same kernel on the planes; 360 rows or less: the definition's frames on the host
                 group = video.take(idx[at:at + 16])
                 if video.h > 360:
                     views = detector_views_device(group, 360, device=self.rank)
@@ -690,7 +690,7 @@ class InferenceAgent:
 
     @staticmethod
     def _is_yuv_video(video):
-        return isinstance(video, (YuvFrames, host_models.Y4MReader)) or (
+        return isinstance(video, (YuvFrames, PlanarYuv, host_models.Y4MReader)) or (
             isinstance(video, (str, os.PathLike)) and os.fspath(video).lower().endswith(".y4m"))
 
     def _align_driving_yuv(self, video, crop, detect_every, smooth, margin, index, rects, chunk, src_matrix, src_chroma):
@@ -698,7 +698,27 @@ class InferenceAgent:
         of _align_driving_files.  `chunk` frames of planes cross PCIe into one reused device buffer (1.5 bytes per pixel; a reader
         or a path is read from the file chunk by chunk), float_img_front_frames_yuv writes the crops, and the frames the detector
         is to see go through detector_views_device on the same kernel.  src_matrix / src_chroma override what the YuvFrames
-        carries; a Y4M file is BT.601 in the range its header states and "nearest" unless they say otherwise."""
+        carries; a Y4M file is BT.601 in the range its header states and "nearest" unless they say otherwise.
+        An image.PlanarYuv (any planar YUV, pitched) takes the same steps on its bytes as they lie: chunks of frame_stride bytes per
+        frame into one reused device buffer, float_img_front_frames_planes on each."""
+        if isinstance(video, PlanarYuv):
+            src = video.like(video.data, src_matrix, src_chroma)  # an unknown matrix or chroma is refused before anything runs
+            T, size = len(src), int(self.opt.input_size)
+            self.to_target()
+            rects = self._driving_clip_rects(T, src.h, src.w, rects, crop, detect_every, smooth, margin, index,
+                                             lambda idx: (src.take(idx), list(range(len(idx)))))
+            dev = torch.device("cuda", self.rank) if isinstance(self.rank, int) else torch.device(self.rank)
+            out = torch.empty(T, size, size, 3, dtype=torch.uint8, device=dev)
+            buf = None
+            for at in range(0, T, chunk):
+                n = min(chunk, T - at)
+                data = src.frame_bytes(at, at + n)
+                if not data.is_cuda:  # one device buffer for the whole clip; copies and kernels are ordered by the stream
+                    if buf is None:
+                        buf = torch.empty(src.frame_bytes(0, min(chunk, T)).numel(), dtype=torch.uint8, device=dev)
+                    data = buf[:data.numel()].copy_(data, non_blocking=True)
+                front_frames_device(src.like(data), rects[at:at + n], size, size, out=out[at:at + n])
+            return out, rects
         opened = host_models.Y4MReader(video) if isinstance(video, (str, os.PathLike)) else None
         try:
             src = video if opened is None else opened
@@ -762,7 +782,10 @@ class InferenceAgent:
         host_models.resize_rgb8(host_models.yuv420_to_rgb8(frame t, layout, matrix, chroma), rects[t], size, size).  src_matrix /
         src_chroma: the matrix the source was made with (host_models.yuv_matrix_id; "auto" goes by the source's size) and how
         luma samples get their chroma ("nearest" | "centre"); None leaves what the YuvFrames carries, and for a Y4M file BT.601
-        in the header's range and "nearest".  With any other video they must be None (ValueError)."""
+        in the header's range and "nearest".  With any other video they must be None (ValueError).
+        video may also be an image.PlanarYuv - planar or semi-planar YUV of 8, 10 or 12 bits at 4:2:0, 4:2:2 or 4:4:4, odd sides,
+        pitched rows, as a decoder's frames lie in memory: float_img_front_frames_planes reads the bytes as they are, frame t
+        bitwise host_models.resize_rgb8(video.to_rgb8()[t], rects[t], size, size); src_matrix / src_chroma override as above."""
         jpeg.entropy_id(entropy)
         if self._is_yuv_video(video):
             return self._align_driving_yuv(video, crop, detect_every, smooth, margin, index, rects, max(1, int(chunk)), src_matrix, src_chroma)

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_front_frames_yuv (the frame-stacked image front end reading 8-bit YUV 4:2:0, I420 or NV12), float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
+/* Stays 6: float_img_front_frames_planes (the same front end reading any planar YUV: 10 / 12 bits, 4:2:2, 4:4:4, pitched), float_img_front_frames_yuv (the frame-stacked image front end reading 8-bit YUV 4:2:0, I420 or NV12), float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
  * decoded to 8-bit RGB frames on the device), float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
@@ -683,6 +683,41 @@ enum { FLOAT_IMG_CHROMA_NEAREST = 0, FLOAT_IMG_CHROMA_CENTRE = 1 };
 int float_img_front_frames_yuv(const uint8_t* frames, int32_t n_frames, int32_t src_h, int32_t src_w, int32_t layout, int32_t matrix,
                                int32_t chroma, const int32_t* rects, int32_t scale_num, int32_t scale_den, uint8_t* out, int32_t dst_h,
                                int32_t dst_w, void* stream);
+
+/* The same call on whatever planar or semi-planar YUV a decoder hands out, as it lies in memory: 8, 10 or 12 bits, 4:2:0, 4:2:2 or
+ * 4:4:4, odd sides, rows with a pitch, planes at any offset of a frame, frames at any stride.  Nothing is packed, shifted or
+ * resampled on the host first.
+ *   data, data_bytes: the caller's buffer in HBM, any alignment, and its length; no byte outside it is read.
+ *   fmt: where the samples are (all in bytes; a HOST struct, read before the call returns)
+ *     hs, vs       chroma geometry: 2, 2 = 4:2:0; 2, 1 = 4:2:2; 1, 1 = 4:4:4.  Chroma planes are ceil(src_w / hs) x ceil(src_h / vs).
+ *     depth        8, 10 or 12.  8: a sample is a byte.  10, 12: a 16-bit little-endian word, sample = (word >> shift) & (2^depth - 1);
+ *     shift        0 for ffmpeg's ...p10le / ...p12le, 16 - depth for P010 / P012 / P210; 0 at depth 8.  (16-bit samples are
+ *                  refused: the int32 arithmetic below would overflow.)
+ *     y_off, u_off, v_off   the first sample of each plane in a frame;  y_pitch, c_pitch   from one row to the next;
+ *     c_step       from one sample of a chroma plane to the next: 1 (2 at 16 bits) planar, 2 (4) semi-planar, where U and V are one
+ *                  sample apart and u_off / v_off say which comes first (NV12 / NV21);
+ *     frame_stride from one frame to the next.
+ *     Refused (FLOAT_E_INVALID, before any HIP call): a pitch below a row, planes that overlap or leave the frame stride or
+ *     data_bytes, odd offsets, pitches or stride at 16 bits, any other geometry, depth or step.
+ *   matrix, chroma: as float_img_front_frames_yuv, at depth d = 8 + s in int32:
+ *       y = cy (Y - (yoff << s)) + (1 << (13 + s)), u = U - (128 << s), v = V - (128 << s),
+ *       R = clamp8((y + crv v) >> (14 + s)), G = clamp8((y - cgu u - cgv v) >> (14 + s)), B = clamp8((y + cbu u) >> (14 + s)).
+ *     FLOAT_IMG_CHROMA_CENTRE is libjpeg's triangle rule applied to the d-bit samples before the matrix: h2v2 for 4:2:0, h2v1 for
+ *     4:2:2 (replication where the chroma plane is at most 2 samples wide), nothing for 4:4:4.
+ *   src_h, src_w 1 ... 16384, odd values allowed; rects, scale, out, the other limits and checks: as float_img_front_frames.
+ *   Frame t is bitwise host_models.resize_rgb8(host_models.yuv_planes_to_rgb8(data, fmt)[t], rects[t], dst_h, dst_w, scale).
+ * One fused kernel per block of 16 frames - float_img_front_frames' kernel with the staging stage of csrc/imgx_kernels.hpp: no
+ * scratch; 4:2:0 chroma rows kept in LDS, 4:2:2 neighbours exchanged between lanes, 4:4:4 loaded like luma.  No atomics, two calls
+ * give equal bytes; allocates nothing, synchronises nothing; kernel launches only (no test captures it). */
+typedef struct {
+  int32_t hs, vs, depth, shift;
+  int64_t y_off, u_off, v_off;
+  int32_t y_pitch, c_pitch, c_step;
+  int64_t frame_stride;
+} float_img_planes_t;
+int float_img_front_frames_planes(const uint8_t* data, uint64_t data_bytes, int32_t n_frames, int32_t src_h, int32_t src_w,
+                                  const float_img_planes_t* fmt, int32_t matrix, int32_t chroma, const int32_t* rects, int32_t scale_num,
+                                  int32_t scale_den, uint8_t* out, int32_t dst_h, int32_t dst_w, void* stream);
 
 /* ---------------------------------------------------------------- paste back -- */
 /* The step after the decoder: n_frames generated 8-bit frames (n_frames, fr_h, fr_w, 3) - the buffer float_dec_frames_u8 writes -

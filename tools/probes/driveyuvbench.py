@@ -5,7 +5,8 @@ interleaved in one process, medians of DRIVEYUV_REPS = 20 after 3 warm-up rounds
   (b) the bytes the windows hold (3 or 1.5 per pixel) over those times, against float_probe_peaks' streaming read of this box.
   (c) InferenceAgent.drive_video from a pageable host clip, uint8 RGB against the YUV form (512-px synthetic model, wall clock
       around a synchronise, DRIVEYUV_C_REPS = 5 repetitions).
-Also: the YUV crops are compared with the definition on frame 0.  DRIVEYUV_FRAMES shrinks the run for a rehearsal."""
+Also: the YUV crops are compared with the definition on frame 0.  DRIVEYUV_FRAMES shrinks the run for a rehearsal.
+--format NAME [--pitch BYTES] measures image.PlanarYuv (any planar YUV) instead of the above: planar() below says what."""
 import argparse
 import importlib
 import os
@@ -20,7 +21,10 @@ from tests.util import load_pkg  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--src", choices=("i420", "nv12"), default="i420")
-SRC = ap.parse_args().src
+ap.add_argument("--format", default=None, help="an image.PLANAR_YUV_NAMES name: measure image.PlanarYuv instead (see planar())")
+ap.add_argument("--pitch", type=int, default=None, help="with --format: bytes from one luma row to the next (chroma rows get the same padding)")
+ARGS = ap.parse_args()
+SRC = ARGS.src
 pkg = load_pkg()
 N, I, hm = pkg.native, pkg.image, pkg.host_models
 T, REPS, WARM = int(os.environ.get("DRIVEYUV_FRAMES", 250)), int(os.environ.get("DRIVEYUV_REPS", 20)), 3
@@ -61,6 +65,103 @@ def front(key, frames):
     out[key] = I.front_frames_device(frames, RECT, 512, 512, out=out.get(key))
 
 
+def planar_clip(name, pitch):
+    """The I420 content as a PlanarYuv `name` on the device: samples << (depth - 8), chroma rows / columns repeated for 4:2:2 / 4:4:4,
+    luma rows `pitch` bytes apart (None: packed) and chroma rows with the same padding."""
+    kw = I.PLANAR_YUV_NAMES[name]
+    hs, vs = hm.YUV_SUBSAMPLING[kw["sub"]]
+    depth, semi = kw.get("depth", 8), kw.get("semi", False)
+    b = 1 if depth == 8 else 2
+    pad = 0 if pitch is None else pitch - W * b
+    pitches = dict(y_pitch=W * b + pad, c_pitch=W // hs * b * (2 if semi else 1) + pad)
+    f = hm.yuv_planes_format(H, W, matrix="bt709", **dict(kw, **pitches))
+    buf = torch.zeros((T - 1) * f.frame_stride + f.last_end, dtype=torch.uint8, device="cuda")
+    words = buf.view(torch.int16) if b == 2 else buf
+    c = yuv_d[:, H:].reshape(T, 2, H // 2, W // 2)
+    for off, plane, pitch_, step in ((f.y_off, yuv_d[:, :H], f.y_pitch, b), (f.u_off, c[:, 0], f.c_pitch, f.c_step), (f.v_off, c[:, 1], f.c_pitch, f.c_step)):
+        if plane.shape[1] != H:
+            plane = plane.repeat_interleave(2 // vs, dim=1).repeat_interleave(2 // hs, dim=2)
+        dst = torch.as_strided(words, tuple(plane.shape), (f.frame_stride // b, pitch_ // b, step // b), off // b)
+        dst.copy_(plane.to(words.dtype) << (depth - 8 + kw.get("shift", 0)))
+    return I.PlanarYuv.of(name, buf, H, W, matrix="bt709", **pitches)
+
+
+def planar():
+    """--format NAME [--pitch BYTES]: (a) the launches alone, frames in HBM, interleaved: `yuv420p` through the EXISTING
+    float_img_front_frames_yuv (the yardstick), `yuv422p10le` and `p010` through float_img_front_frames_planes, both chroma rules;
+    (c) drive_video from a pageable pitched NAME clip as an image.PlanarYuv, against the route without it: pack the rows, shift to
+    8 bits and drop every second chroma row on the host with torch, then image.YuvFrames."""
+    clips = {n: planar_clip(n, None) for n in ("yuv422p10le", "p010")}
+    forms = {}
+    for chroma in ("nearest", "centre"):
+        forms["yuv420p %s (yuv call)" % chroma] = lambda c=chroma: front("y" + c, I.YuvFrames(yuv_d, H, W, "i420", "bt709", c))
+        for n, clip in clips.items():
+            forms["%s %s" % (n, chroma)] = lambda n=n, clip=clip, c=chroma: front(n + c, clip.like(clip.data, chroma=c))
+    ts = {k: [] for k in forms}
+    for r in range(WARM + REPS):
+        for k, fn in forms.items():
+            t = timed(fn)
+            if r >= WARM:
+                ts[k].append(t)
+    print("%d frames of %d x %d in HBM, window %s -> 512 px" % (T, W, H, RECT))
+    for k, v in ts.items():
+        print("(a) %-30s %8.3f ms per clip (spread %.3f)" % (k, statistics.median(v), max(v) - min(v)))
+    for n, clip in clips.items():
+        one = clip[0:1]
+        want = hm.resize_rgb8(one.like(one.data.cpu(), chroma="centre").to_rgb8()[0], RECT, 512, 512)
+        print("frame 0, %s centre: equal to the definition: %s" % (n, torch.equal(out[n + "centre"][0].cpu(), want)))
+    clips.clear()
+    out.clear()
+    dev = planar_clip(ARGS.format, ARGS.pitch)
+    f = dev.fmt
+    host = dev.like(dev.data.cpu())  # pageable
+    del dev
+
+    def todays_route():
+        if f.depth == 8 or f.c_step != 2:
+            raise SystemExit("driveyuvbench: the host route is written for planar 16-bit formats (got %s)" % ARGS.format)
+        w16 = host.data.view(torch.int16)
+        cw, ch = -(-W // f.hs), -(-H // f.vs)
+        pl = lambda off, rows, cols, pitch: (torch.as_strided(w16, (T, rows, cols), (f.frame_stride // 2, pitch // 2, 1), off // 2)  # noqa: E731
+                                             >> (f.shift + f.depth - 8)).to(torch.uint8)
+        y, u, v = pl(f.y_off, H, W, f.y_pitch), pl(f.u_off, ch, cw, f.c_pitch), pl(f.v_off, ch, cw, f.c_pitch)
+        u, v = (c[:, ::2 // f.vs, ::2 // f.hs].reshape(T, H // 4, W) for c in (u, v))
+        return I.YuvFrames(torch.cat([y, u, v], dim=1), H, W, "i420", "bt709", "nearest")
+
+    agent, portrait = make_agent()
+    tc = {"PlanarYuv %s" % ARGS.format: [], "host pack + shift + drop rows, YuvFrames": []}
+    for r in range(1 + C_REPS):
+        for k, video in zip(tc, (lambda: host, todays_route)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            agent.drive_video(portrait, video(), rects=RECT, out_dtype=torch.uint8)
+            torch.cuda.synchronize()
+            if r >= 1:
+                tc[k].append((time.perf_counter() - t0) * 1e3)
+    for k, v in tc.items():
+        print("(c) drive_video %-42s %8.1f ms per clip (spread %.1f), pageable host clip of %.0f MB, luma pitch %d"
+              % (k, statistics.median(v), max(v) - min(v), host.data.numel() / 1e6, f.y_pitch))
+
+
+def make_agent():
+    gen = importlib.import_module(pkg.__name__ + ".src.nodes.generate")
+    opt = importlib.import_module(pkg.__name__ + ".src.nodes.options.base_options").BaseOptions()
+    opt.input_size = 512
+    acfg = pkg.config.small_audio_config()
+    acfg.dim_w = opt.dim_w
+    Wt = pkg.weights
+    parts = dict(enc=Wt.synth_encoder_state(512, seed=31), dec=Wt.synth_decoder_state(512, seed=31),
+                 fmt=Wt.synth_fmt_state(pkg.config.FmtConfig.from_options(opt), seed=31), audio_encoder=(Wt.synth_audio_state(acfg, seed=31), acfg))
+    return gen.InferenceAgent(opt, parts, "cuda:0"), torch.rand(1, 512, 512, 3, generator=torch.Generator().manual_seed(3))
+
+
+if ARGS.format:
+    if ARGS.format not in I.PLANAR_YUV_NAMES:
+        sys.exit("driveyuvbench: --format must be one of %s" % sorted(I.PLANAR_YUV_NAMES))
+    del rgb_d, rgb_h, yuv_h
+    planar()
+    sys.exit(0)
+
 forms = {"rgb8": lambda: front("rgb8", rgb_d),
          "yuv nearest": lambda: front("yn", I.YuvFrames(yuv_d, H, W, SRC, "bt709", "nearest")),
          "yuv centre": lambda: front("yc", I.YuvFrames(yuv_d, H, W, SRC, "bt709", "centre"))}
@@ -84,16 +185,7 @@ for key, chroma in (("yn", "nearest"), ("yc", "centre")):
 # (c) through the agent
 del rgb_d, yuv_d
 out.clear()
-gen = importlib.import_module(pkg.__name__ + ".src.nodes.generate")
-opt = importlib.import_module(pkg.__name__ + ".src.nodes.options.base_options").BaseOptions()
-opt.input_size = 512
-acfg = pkg.config.small_audio_config()
-acfg.dim_w = opt.dim_w
-Wt = pkg.weights
-parts = dict(enc=Wt.synth_encoder_state(512, seed=31), dec=Wt.synth_decoder_state(512, seed=31),
-             fmt=Wt.synth_fmt_state(pkg.config.FmtConfig.from_options(opt), seed=31), audio_encoder=(Wt.synth_audio_state(acfg, seed=31), acfg))
-agent = gen.InferenceAgent(opt, parts, "cuda:0")
-portrait = torch.rand(1, 512, 512, 3, generator=torch.Generator().manual_seed(3))
+agent, portrait = make_agent()
 yuv_clip = I.YuvFrames(yuv_h, H, W, SRC, "bt709", "nearest")
 tc = {"rgb8": [], SRC: []}
 for r in range(1 + C_REPS):
