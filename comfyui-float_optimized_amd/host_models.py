@@ -11,6 +11,8 @@ this package).  What is left is tensor plumbing:
     `float_img_front` (image.py in this package) are held to bit for bit
   * the paste of the generated frames back into the source portrait (paste_alpha, paste_rgb8): the definition the kernel of
     `float_img_paste` is held to bit for bit
+  * the multi-band (Laplacian pyramid) form of that paste in int32 (blend_reduce, blend_expand, blend_masks,
+    paste_multiband_rgb8): the definition the kernels of `float_img_blend` are held to bit for bit, what `blend="multiband"` selects
   * bicubic and Lanczos resampling of 8-bit frames in Pillow's fixed-point arithmetic (resample_coeffs, resample_rgb8): the
     definition the kernels of `float_img_resample` are held to bit for bit, and what `resample=` selects on the paste routes
   * the planar YUV 4:2:0 frame format in torch integer ops (the definition the decoder's I420 kernels are held to) and a Y4M
@@ -412,6 +414,125 @@ def paste_rgb8(src8, frames8, rect, feather, resample=None):
         else:
             face = resize_rgb8(frames8[t], None, h, w)[ya - y0:yb - y0, xa - x0:xb - x0].to(torch.int64)
         out[t, ya:yb, xa:xb] = ((a * face + (255 - a) * s + 127) // 255).to(torch.uint8)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# multi-band (Laplacian pyramid, Burt-Adelson) blending of the face into the portrait: the definition `float_img_blend` is held to
+# ---------------------------------------------------------------------------------------------------------------------------
+BLEND_MAX_LEVELS = 8
+
+
+def blend_levels(what, inset, levels=None):
+    """The pyramid depth of a multi-band paste: None = max(1, floor(log2(max(inset, 2))) - 1), so that 2^levels <= inset / 2 - the
+    widest band still ends inside the box (and at most 8, from an inset of 1024 on); 1 ... 8, anything else is a ValueError."""
+    if levels is None:
+        levels = max(1, min(BLEND_MAX_LEVELS, max(int(inset), 2).bit_length() - 2))
+    if isinstance(levels, bool) or int(levels) != levels or not 1 <= int(levels) <= BLEND_MAX_LEVELS:
+        raise ValueError("%s: levels must be 1 ... %d (got %r)" % (what, BLEND_MAX_LEVELS, levels))
+    return int(levels)
+
+
+def blend_sizes(n, levels):
+    """[n_0 ... n_levels] with n_{l+1} = (n_l + 1) // 2"""
+    sizes = [int(n)]
+    for _ in range(levels):
+        sizes.append((sizes[-1] + 1) // 2)
+    return sizes
+
+
+def _blend_taps(A, axis, idx):
+    import numpy as np
+    return np.take(A, np.clip(idx, 0, A.shape[axis] - 1), axis=axis)
+
+
+def blend_reduce(A):
+    """One pyramid level down over the two leading axes of an int32 array: (sum k_i k_j A[2y + i, 2x + j] + 128) >> 8 with k = 1,
+    4, 6, 4, 1 and indices clamped to A's extent (separable, one rounding)."""
+    import numpy as np
+    for axis in (0, 1):
+        c = 2 * np.arange((A.shape[axis] + 1) // 2)
+        A = sum(k * _blend_taps(A, axis, c + i) for i, k in zip(range(-2, 3), (1, 4, 6, 4, 1)))
+    return (A + 128) >> 8
+
+
+def blend_expand(B, h, w):
+    """One pyramid level up to h x w: per axis with c = x >> 1, even x: B[c - 1] + 6 B[c] + B[c + 1], odd x: 4 B[c] + 4 B[c + 1]
+    (indices clamped to B's extent); the product of the two axes, then (sum + 32) >> 6."""
+    import numpy as np
+    for axis, n in ((0, h), (1, w)):
+        c = np.arange(n) >> 1
+        odd = (np.arange(n) & 1).astype(bool).reshape([-1 if a == axis else 1 for a in range(B.ndim)])
+        even = _blend_taps(B, axis, c - 1) + 6 * _blend_taps(B, axis, c) + _blend_taps(B, axis, c + 1)
+        B = np.where(odd, 4 * _blend_taps(B, axis, c) + 4 * _blend_taps(B, axis, c + 1), even)
+    return (B + 32) >> 6
+
+
+def blend_masks(H, W, rect, inset, levels):
+    """The mask pyramid of a multi-band paste, [M_0 ... M_levels] as int32 arrays over the window (box & image) and its halvings:
+    M_0 = 256 where the cell's distance d to the nearest OPEN side of the unclipped box (paste_alpha's rule) is >= inset, else 0;
+    M_{l+1} = blend_reduce(M_l).  None when the box misses the image."""
+    import numpy as np
+    x0, y0, w, h = (int(v) for v in rect)
+    ya, yb, xa, xb = max(0, y0), min(H, y0 + h), max(0, x0), min(W, x0 + w)
+    if yb <= ya or xb <= xa:
+        return None
+    big = 1 << 30
+
+    def axis(n, lo_open, hi_open):
+        u = np.arange(n, dtype=np.int64)
+        return np.minimum(u if lo_open else np.full(n, big), (n - 1 - u) if hi_open else np.full(n, big))
+
+    d = np.minimum(axis(h, y0 > 0, y0 + h < H)[ya - y0:yb - y0, None], axis(w, x0 > 0, x0 + w < W)[None, xa - x0:xb - x0])
+    masks = [np.where(d >= int(inset), 256, 0).astype(np.int32)]
+    for _ in range(levels):
+        masks.append(blend_reduce(masks[-1]))
+    return masks
+
+
+def paste_multiband_rgb8(src8, frames8, rect, inset=None, levels=None, resample=None):
+    """The generated frames back in the source portrait by a multi-band blend: as paste_rgb8, but the face F and the portrait's
+    window S (box & image) are joined per spatial frequency instead of by one ramp -> (T, H, W, 3) uint8.
+      F        paste_rgb8(S, frames8, the box in the window's coordinates, feather=0, resample): the face of every paste route
+      M_l      blend_masks: a hard mask `inset` pixels inside the box's open sides (None = default_feather(rect)), halved `levels`
+               times (None = blend_levels' default; 1 ... 8)
+      D_0 = 16 (F - S), D_{l+1} = reduce(D_l), Lap_l = D_l - expand(D_{l+1}): the pyramid of the DIFFERENCE image, int32
+      B_l = (M_l Lap_l + 128) >> 8 for l < levels, B_L = (M_L D_L + 128) >> 8;  R_L = B_L, R_l = B_l + expand(R_{l+1})
+      out = clamp(S + ((R_0 + 8) >> 4), 0, 255) in the window, the portrait outside it.
+    >> is the arithmetic shift.  Where every mask value in a pixel's support is 256 the pyramid collapses to D_0 and out == F; where
+    all are 0, out == S.  A box that misses the image gives the portrait T times.  `float_img_blend`
+    (image.paste_frames_device(..., blend="multiband")) is held to this bit for bit."""
+    import numpy as np
+    if inset is None:
+        inset = default_feather(rect)
+    if isinstance(inset, bool) or int(inset) != inset or not 0 <= int(inset) <= 16384:
+        raise ValueError("paste_multiband_rgb8: inset must be 0 ... 16384 (got %r)" % (inset,))
+    inset = int(inset)
+    levels = blend_levels("paste_multiband_rgb8", inset, levels)
+    if len(rect) != 4:
+        raise ValueError("paste_multiband_rgb8: rect must be (x0, y0, w, h), got %r" % (rect,))
+    x0, y0, w, h = (int(v) for v in rect)
+    if src8.dtype != torch.uint8 or src8.dim() != 3 or src8.shape[-1] != 3 or 0 in src8.shape:
+        raise ValueError("paste_multiband_rgb8 takes an (H, W, 3) uint8 source, got %s %s" % (src8.dtype, tuple(src8.shape)))
+    H, W = int(src8.shape[0]), int(src8.shape[1])
+    src8, frames8 = src8.cpu(), frames8.cpu()
+    ya, yb, xa, xb = max(0, y0), min(H, y0 + h), max(0, x0), min(W, x0 + w)
+    if yb <= ya or xb <= xa:
+        return paste_rgb8(src8, frames8, rect, 0, resample)  # the box misses the image: the portrait T times
+    face = paste_rgb8(src8[ya:yb, xa:xb].contiguous(), frames8, (x0 - xa, y0 - ya, w, h), 0, resample)
+    masks = blend_masks(H, W, (x0, y0, w, h), inset, levels)
+    hs, ws = blend_sizes(yb - ya, levels), blend_sizes(xb - xa, levels)
+    S = src8[ya:yb, xa:xb].numpy().astype(np.int32)
+    out = src8[None].repeat(frames8.shape[0], 1, 1, 1)
+    for t in range(frames8.shape[0]):
+        D = [16 * (face[t].numpy().astype(np.int32) - S)]
+        for _ in range(levels):
+            D.append(blend_reduce(D[-1]))
+        R = (masks[levels][:, :, None] * D[levels] + 128) >> 8
+        for l in range(levels - 1, -1, -1):
+            lap = D[l] - blend_expand(D[l + 1], hs[l], ws[l])
+            R = ((masks[l][:, :, None] * lap + 128) >> 8) + blend_expand(R, hs[l], ws[l])
+        out[t, ya:yb, xa:xb] = torch.from_numpy(np.clip(S + ((R + 8) >> 4), 0, 255).astype(np.uint8))
     return out
 
 

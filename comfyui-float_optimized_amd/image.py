@@ -420,12 +420,13 @@ def _resample_tables_device(device, fr_h, fr_w, h, w, filter, window):
 
 
 class ResampleScratch:
-    """The device memory one resampled paste needs besides its output: `face`, the box-sized window of n frames, and `work`, the
-    intermediate of float_img_resample.  Made once by paste_scratch for the largest group of frames and handed to every
-    paste_frames_device(..., resample=, scratch=) of a clip."""
+    """The device memory one resampled or multi-band paste needs besides its output: `face`, the box-sized window of n frames,
+    `work`, the intermediate of float_img_resample (None without resample=), and for blend="multiband" `crop`, the portrait's
+    window that float_img_paste forms the face on, and `blend_work`, the pyramids of float_img_blend.  Made once by paste_scratch
+    for the largest group of frames and handed to every paste_frames_device(..., scratch=) of a clip."""
 
-    def __init__(self, face, work):
-        self.face, self.work = face, work
+    def __init__(self, face, work, crop=None, blend_work=None):
+        self.face, self.work, self.crop, self.blend_work = face, work, crop, blend_work
 
 
 def paste_window(H, W, rect):
@@ -444,20 +445,98 @@ def _resample_work_bytes(n, fr_h, fr_w, h, w, fid, window):
     return need
 
 
-def paste_scratch(src_hw, frame_hw, rect, n, resample, device):
-    """The ResampleScratch of pasting up to n frames of frame_hw at `rect` into a portrait of src_hw with resample=`resample`;
-    None when there is nothing to resample (resample None, or a box that misses the image)."""
-    if resample is None:
+def paste_scratch(src_hw, frame_hw, rect, n, resample, device, blend=None, inset=None, levels=None):
+    """The ResampleScratch of pasting up to n frames of frame_hw at `rect` into a portrait of src_hw with resample=`resample` and
+    blend=`blend`; None when neither needs one (both None, or a box that misses the image)."""
+    spec = blend_spec("paste_scratch", blend, inset, levels, rect)
+    if resample is None and spec is None:
         return None
-    fid = host_models.resample_filter_id("paste_scratch", resample)
     win = paste_window(int(src_hw[0]), int(src_hw[1]), rect)
     if win is None:
         return None
     xa, ya, xb, yb = win
     x0, y0, w, h = (int(v) for v in rect)
-    need = _resample_work_bytes(int(n), int(frame_hw[0]), int(frame_hw[1]), h, w, fid, (xa - x0, ya - y0, xb - xa, yb - ya))
-    return ResampleScratch(torch.empty(int(n), yb - ya, xb - xa, 3, dtype=torch.uint8, device=device),
-                           torch.empty((need + 3) // 4, dtype=torch.int32, device=device))
+    work = crop = blend_work = None
+    if resample is not None:
+        fid = host_models.resample_filter_id("paste_scratch", resample)
+        need = _resample_work_bytes(int(n), int(frame_hw[0]), int(frame_hw[1]), h, w, fid, (xa - x0, ya - y0, xb - xa, yb - ya))
+        work = torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+    if spec is not None:
+        crop = torch.empty(yb - ya, xb - xa, 3, dtype=torch.uint8, device=device)
+        blend_work = torch.empty((_blend_work_bytes(int(n), yb - ya, xb - xa, spec[1]) + 3) // 4, dtype=torch.int32, device=device)
+    return ResampleScratch(torch.empty(int(n), yb - ya, xb - xa, 3, dtype=torch.uint8, device=device), work, crop, blend_work)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# multi-band blending of the face into the portrait (`float_img_blend`, include/float_hip.h): what `blend="multiband"` selects
+# ---------------------------------------------------------------------------------------------------------------------------
+BLEND_MODES = ("multiband",)
+BLEND_PLANS_KEPT = 8  # (sizes, rect, inset, levels, device) entries of the mask cache: a clip uses one
+_blend_plans = collections.OrderedDict()
+
+
+def blend_spec(what, blend, inset=None, levels=None, rect=None, feather=None, out_format=None):
+    """The checked form of a paste route's blend=, inset=, levels=: None (the feathered paste), or (inset, levels) with their
+    defaults filled in from `rect` (host_models.default_feather, host_models.blend_levels; without a rect they stay as given).
+    ValueError: an unknown blend; inset or levels without blend; with blend="multiband" a feather (the pyramid has no ramp), I420
+    frames, an inset outside 0 ... 16384, levels outside 1 ... 8."""
+    if blend is None:
+        if inset is not None or levels is not None:
+            raise ValueError("%s: inset and levels belong to blend=\"multiband\" (blend is None)" % what)
+        return None
+    if blend not in BLEND_MODES:
+        raise ValueError("%s: blend must be None or \"multiband\" (got %r)" % (what, blend))
+    if feather is not None:
+        raise ValueError("%s: blend=\"multiband\" takes no feather (got %r): its width is inset=" % (what, feather))
+    if out_format == "i420":
+        raise ValueError("%s: blend=\"multiband\" leaves RGB frames in this version; convert them (host_models.rgb8_to_i420) or "
+                         "paste with blend=None" % what)
+    if inset is None and rect is not None:
+        inset = host_models.default_feather(rect)
+    if inset is not None:
+        if isinstance(inset, bool) or int(inset) != inset or not 0 <= int(inset) <= 16384:
+            raise ValueError("%s: inset must be 0 ... 16384 (got %r)" % (what, inset))
+        inset = int(inset)
+    if levels is not None or inset is not None:
+        levels = host_models.blend_levels(what, inset if inset is not None else 0, levels)
+    return inset, levels
+
+
+def blend_plan(H, W, rect, inset, levels):
+    """float_img_blend_plan: the mask pyramid of a multi-band paste of the box `rect` into an H x W portrait -> (flat int16 host
+    tensor, [(h_l, w_l)]): levels + 1 levels over the window back to back, integer for integer host_models.blend_masks.  Host
+    arithmetic in the library; no GPU is touched.  The library's refusals are ValueErrors."""
+    x0, y0, w, h = (int(v) for v in rect)
+    win = paste_window(int(H), int(W), (x0, y0, w, h))
+    L = native.lib()
+    ints = int(L.float_img_blend_plan_ints(win[3] - win[1], win[2] - win[0], int(levels))) if win is not None else 0
+    table = torch.empty(max(ints, 1), dtype=torch.int16)
+    native.check(L.float_img_blend_plan(int(H), int(W), x0, y0, w, h, int(inset), int(levels), C.cast(table.data_ptr(), C.POINTER(C.c_int16)),
+                                        ints))
+    sizes = list(zip(host_models.blend_sizes(win[3] - win[1], int(levels)), host_models.blend_sizes(win[2] - win[0], int(levels))))
+    return table[:ints], sizes
+
+
+def _blend_plan_device(device, H, W, rect, inset, levels):
+    """the plan on the device: made and uploaded once per (sizes, rect, inset, levels, device) and kept for the next call"""
+    key = (str(device), H, W, tuple(rect), inset, levels)
+    plan = _blend_plans.get(key)
+    if plan is None:
+        plan = blend_plan(H, W, rect, inset, levels)[0].to(device)  # a blocking copy: complete on return
+        _blend_plans[key] = plan
+        while len(_blend_plans) > BLEND_PLANS_KEPT:
+            _blend_plans.popitem(last=False)
+    else:
+        _blend_plans.move_to_end(key)
+    return plan
+
+
+def _blend_work_bytes(n, hc, wc, levels):
+    need = int(native.lib().float_img_blend_work_bytes(n, hc, wc, levels))
+    if not need:
+        raise ValueError("blend: %d frames over a window of %d x %d with %d levels are outside float_img_blend's limits (sides 1 ... "
+                         "16384, levels 1 ... 8)" % (n, hc, wc, levels))
+    return need
 
 
 @torch.no_grad()
@@ -498,7 +577,8 @@ def resample_frames_device(frames8, h, w, filter, window=None, out=None, work=No
 
 
 @torch.no_grad()
-def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None, matrix=None, resample=None, scratch=None):
+def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=None, matrix=None, resample=None, scratch=None, blend=None,
+                        inset=None, levels=None):
     """float_img_paste: frames8 (T, h, w, 3) uint8 - what the decoder's decode_u8 leaves in HBM - back in the portrait src8 (H, W,
     3) uint8 at the box rect = (x0, y0, w, h) in source coordinates (what InferenceAgent.host_inputs_placed returns; it may reach
     outside the image) -> (T, H, W, 3) uint8 on the device, bitwise host_models.paste_rgb8(src8, frames8, rect, feather).
@@ -515,8 +595,16 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
     box that lies in the image (two more launches, tables uploaded once per sizes), and the paste kernel above gets that window
     as its frames, the clipped box as its rect and the feather of the unclipped one: its resize at equal sizes is the identity
     and clipping moves no open side, so the bytes are the definition's.  A box that misses the image launches nothing new.
-    scratch: a ResampleScratch of paste_scratch for at least T frames (default: torch's allocator, per call)."""
+    scratch: a ResampleScratch of paste_scratch for at least T frames (default: torch's allocator, per call).
+    blend: None as above; "multiband": float_img_blend joins face and portrait by a Laplacian pyramid instead of the feathered
+    ramp - bitwise host_models.paste_multiband_rgb8(src8, frames8, rect, inset, levels, resample).  inset: how far inside the box's
+    open sides the hard mask starts (None = host_models.default_feather(rect)); levels: the pyramid's depth, 1 ... 8 (None =
+    host_models.blend_levels).  feather must be None and the frames RGB (ValueError).  The face over the window (box & image) is
+    formed as the definition forms it - float_img_paste with feather 0 on the window's crop of the portrait, or float_img_resample
+    alone when resample= is given (that paste would copy its result) - then 2 levels launches; the mask pyramid is made by
+    float_img_blend_plan and kept on the device per (sizes, rect, inset, levels).  A box that misses the image is the plain paste."""
     fmt = paste_format("paste_frames_device", out_format)
+    spec = blend_spec("paste_frames_device", blend, inset, levels, rect if len(rect) == 4 else None, feather, fmt)
     if resample is not None:
         host_models.resample_filter_id("paste_frames_device", resample)  # refused before anything is uploaded
     if fmt != "i420":
@@ -544,15 +632,33 @@ def paste_frames_device(src8, frames8, rect, feather=None, out=None, out_format=
             raise ValueError("paste_frames_device: out must be a contiguous %s uint8 tensor on %s, got %s %s on %s"
                              % (shape, device, out.dtype, tuple(out.shape), out.device))
         L = native.lib()
-        win = paste_window(H, W, (x0, y0, w, h)) if resample is not None else None
+        win = paste_window(H, W, (x0, y0, w, h)) if resample is not None or spec is not None else None
         if win is not None:
             xa, ya, xb, yb = win
             if scratch is None:
-                scratch = paste_scratch((H, W), f.shape[1:3], (x0, y0, w, h), T, resample, device)
-            elif scratch.face.shape[0] < T or tuple(scratch.face.shape[1:]) != (yb - ya, xb - xa, 3) or scratch.face.device != device:
+                scratch = paste_scratch((H, W), f.shape[1:3], (x0, y0, w, h), T, resample, device, blend, *(spec or (None, None)))
+            elif scratch.face.shape[0] < T or tuple(scratch.face.shape[1:]) != (yb - ya, xb - xa, 3) or scratch.face.device != device \
+                    or (resample is not None and scratch.work is None):
                 raise ValueError("paste_frames_device: scratch was made for another paste (%s for %d frames of the window %r)"
                                  % (tuple(scratch.face.shape), T, win))
-            f = resample_frames_device(f, h, w, resample, (xa - x0, ya - y0, xb - xa, yb - ya), out=scratch.face[:T], work=scratch.work)
+            if resample is not None:
+                f = resample_frames_device(f, h, w, resample, (xa - x0, ya - y0, xb - xa, yb - ya), out=scratch.face[:T], work=scratch.work)
+        if win is not None and spec is not None:
+            hc, wc = yb - ya, xb - xa
+            need = _blend_work_bytes(T, hc, wc, spec[1])
+            if scratch.crop is None or scratch.blend_work is None or scratch.blend_work.numel() * 4 < need:
+                raise ValueError("paste_frames_device: scratch was made for another paste (blend=%r, %d levels, %d frames)" % (blend, spec[1], T))
+            if resample is None:  # the face over the window: the plain paste at full weight on the window's crop of the portrait
+                scratch.crop.copy_(s[ya:yb, xa:xb])
+                native.check(L.float_img_paste(C.c_void_p(scratch.crop.data_ptr()), hc, wc, C.c_void_p(f.data_ptr()), T, int(f.shape[1]),
+                                               int(f.shape[2]), x0 - xa, y0 - ya, w, h, 0, C.c_void_p(scratch.face.data_ptr()),
+                                               native.stream_ptr(device)))
+            mask = _blend_plan_device(device, H, W, (x0, y0, w, h), *spec)
+            native.check(L.float_img_blend(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(scratch.face.data_ptr()), T, xa, ya, hc, wc, spec[1],
+                                           C.c_void_p(mask.data_ptr()), C.c_void_p(scratch.blend_work.data_ptr()),
+                                           scratch.blend_work.numel() * 4, C.c_void_p(out.data_ptr()), native.stream_ptr(device)))
+            return out
+        if win is not None:
             x0, y0, w, h = xa, ya, xb - xa, yb - ya  # `feather` stays the unclipped box's
         if fmt == "i420":
             native.check(L.float_img_paste_i420(C.c_void_p(s.data_ptr()), H, W, C.c_void_p(f.data_ptr()), T, int(f.shape[1]), int(f.shape[2]),

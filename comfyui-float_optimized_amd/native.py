@@ -177,6 +177,11 @@ _SIGNATURES = {
     "float_img_resample_plan": (C.c_int, [C.c_int32] * 5 + [C.POINTER(C.c_int32), C.c_size_t]),
     "float_img_resample_work_bytes": (C.c_size_t, [C.c_int32] * 10),
     "float_img_resample": (C.c_int, [C.c_void_p] + [C.c_int32] * 10 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "float_img_blend_plan_ints": (C.c_size_t, [C.c_int32] * 3),
+    "float_img_blend_plan": (C.c_int, [C.c_int32] * 8 + [C.POINTER(C.c_int16), C.c_size_t]),
+    "float_img_blend_work_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "float_img_blend": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p]),
     "float_jpg_work_bytes": (C.c_size_t, [C.c_int32] * 4),
     "float_jpg_encode": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "float_jpg_work_bytes_padded": (C.c_size_t, [C.c_int32] * 4),

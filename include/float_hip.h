@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-/* Stays 6: float_img_front_frames_planes (the same front end reading any planar YUV: 10 / 12 bits, 4:2:2, 4:4:4, pitched), float_img_front_frames_yuv (the frame-stacked image front end reading 8-bit YUV 4:2:0, I420 or NV12), float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
+/* Stays 6: float_img_blend / float_img_blend_work_bytes / float_img_blend_plan / float_img_blend_plan_ints (the pasted face joined to the portrait by a multi-band blend on the device), float_img_front_frames_planes (the same front end reading any planar YUV: 10 / 12 bits, 4:2:2, 4:4:4, pitched), float_img_front_frames_yuv (the frame-stacked image front end reading 8-bit YUV 4:2:0, I420 or NV12), float_jpg_decode_plan_entropy (a scan without restart markers decoded by up to 1024 lanes), float_jpg_decode / float_jpg_decode_plan / float_jpg_decode_plan_ints / float_jpg_decode_work_bytes / float_jpg_decode_host (baseline JPEG files
  * decoded to 8-bit RGB frames on the device), float_img_front_frames (the image front end over a stack of frames, one window per frame), float_sfd_reserve_batch / float_sfd_maps_batch / float_sfd_post_batch / float_sfd_detect_batch / float_sfd_dense_batch
  * (the face detector on n stacked views in one pass), float_aud_reserve_segments / float_aud_classify_segments / float_aud_expand_rows (dynamic emotion: all chunks of a
  * clip through one stacked speech-emotion pass), float_img_resample / float_img_resample_work_bytes / float_img_resample_plan / float_img_resample_plan_ints (bicubic and
@@ -815,6 +815,45 @@ size_t float_img_resample_work_bytes(int32_t n_frames, int32_t fr_h, int32_t fr_
 int float_img_resample(const uint8_t* frames8, int32_t n_frames, int32_t fr_h, int32_t fr_w, int32_t box_h, int32_t box_w,
                        int32_t filter, int32_t win_x, int32_t win_y, int32_t win_w, int32_t win_h, const int32_t* tab_x,
                        const int32_t* tab_y, void* work, size_t work_bytes, uint8_t* out, void* stream);
+
+/* ---------------------------------------------------------------- multi-band blend -- */
+/* The face joined to the portrait per spatial frequency (Burt-Adelson) instead of by float_img_paste's one ramp: low frequencies
+ * mix over a wide zone, fine detail over a narrow one.  The window is box & image, win_h x win_w at win_x, win_y of the portrait;
+ * face8 (n_frames, win_h, win_w, 3) uint8 holds the face over it - what float_img_paste writes with feather 0 for the window's crop
+ * of the portrait, or float_img_resample for that window.  out is (n_frames, src_h, src_w, 3) uint8: the blend inside the window,
+ * the portrait's bytes outside it.  Bitwise host_models.paste_multiband_rgb8 in the host mirror.  In int32 per channel, with >>
+ * the arithmetic shift and every index clamped to its level's own extent; level l is h_l x w_l, n_{l+1} = (n_l + 1) / 2:
+ *     reduce(A)[y, x] = (sum_{i, j = -2 ... 2} k_i k_j A[2 y + i, 2 x + j] + 128) >> 8,  k = 1, 4, 6, 4, 1
+ *     expand(B), per axis with c = x >> 1: even x: B[c - 1] + 6 B[c] + B[c + 1], odd x: 4 B[c] + 4 B[c + 1]; the product of the
+ *                two axes, then (sum + 32) >> 6
+ *     D_0 = 16 (F - S) (S: the portrait's window),  D_{l+1} = reduce(D_l),  Lap_l = D_l - expand(D_{l+1}) for l < levels
+ *     B_l = (M_l Lap_l + 128) >> 8,  B_L = (M_L D_L + 128) >> 8,  R_L = B_L,  R_l = B_l + expand(R_{l+1})
+ *     out = clamp(S + ((R_0 + 8) >> 4), 0, 255)
+ * Where the mask is 256 over a pixel's whole support out == F, where it is 0 out == S.
+ *
+ * The mask pyramid is the same for every frame and comes from the host (float_img_blend_plan; plain C, no HIP call, usable without
+ * a GPU): M_0 = 256 where the cell's distance d to the nearest OPEN side of the unclipped box (float_img_paste's rule for d and
+ * for open) is >= inset, else 0 - all 256 without an open side; M_{l+1} = reduce(M_l).  `table` receives the levels + 1 levels
+ * over the window back to back as int16 (0 ... 256), float_img_blend_plan_ints values in all (0 for sizes the planner refuses).
+ * Refused (FLOAT_E_INVALID): sides outside 1 ... 16384, |rect_x|, |rect_y| > 2^30, inset outside 0 ... 16384, levels outside 1 ... 8,
+ * a box that misses the image, a short table.
+ *
+ *   mask      DEVICE copy of that table for the same window and levels, 2-byte aligned.  The kernels trust its size.
+ *   work      DEVICE scratch of at least float_img_blend_work_bytes(...) bytes (0 for arguments the call refuses), 16-byte aligned,
+ *             no zeroing needed: per frame D_1 ... D_L as int16 and R_1 ... R_{L-1} as int32, about 1/3 of the window each.
+ * Limits: source sides 1 ... 16384, the window inside the image, levels 1 ... 8, n_frames >= 1.  src8, face8 and out are DEVICE
+ * pointers to contiguous HWC bytes of any alignment; out must not overlap the inputs.  A lane forms four neighbouring pixels; with
+ * src_w % 4 == 0 and out 4-byte aligned it stores them as three dwords, otherwise as bytes; the bytes stored are the same.
+ * Enqueues 2 levels kernels on `stream` (per 65535 frames; the frame is the grid's z, the last kernel also copies the portrait
+ * outside the window); no atomics, allocates nothing, synchronises nothing, two calls give equal bytes.  An argument outside
+ * these rules returns FLOAT_E_INVALID, with a message naming the function and the argument, before any HIP call. */
+size_t float_img_blend_plan_ints(int32_t win_h, int32_t win_w, int32_t levels);
+int float_img_blend_plan(int32_t src_h, int32_t src_w, int32_t rect_x, int32_t rect_y, int32_t rect_w, int32_t rect_h, int32_t inset,
+                         int32_t levels, int16_t* table, size_t table_ints);
+size_t float_img_blend_work_bytes(int32_t n_frames, int32_t win_h, int32_t win_w, int32_t levels);
+int float_img_blend(const uint8_t* src8, int32_t src_h, int32_t src_w, const uint8_t* face8, int32_t n_frames, int32_t win_x,
+                    int32_t win_y, int32_t win_h, int32_t win_w, int32_t levels, const int16_t* mask, void* work, size_t work_bytes,
+                    uint8_t* out, void* stream);
 
 /* ---------------------------------------------------------------- JPEG encoder -- */
 /* n_frames 8-bit RGB frames in HBM - the (n, h, w, 3) buffer float_dec_frames_u8 writes - -> n complete baseline JPEG files

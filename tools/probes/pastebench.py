@@ -25,6 +25,13 @@ two more launches with the paste launches: `resample`, the two kernels of float_
 the box that lies in the image; held to the bytes they move - the crops read, the 8-bit intermediate written and read, the window
 written - over the same copy peak), and `rgb_r`, the paste with resample=NAME whole (three kernels), compared with the definition.
 The 1080-line JPEG loop is left out of such a run.
+--blend multiband: one more form, pasted_b = infer_pasted(blend="multiband") with the default inset and levels, takes turns with
+the others and reports `minus_default_ms` against `pasted`; and two more launches with the paste launches: `rgb_b`, the multi-band
+paste whole (float_img_paste at full weight into the window, then the 2 levels kernels of float_img_blend), compared with the
+definition and reporting `minus_rgb_ms`, and `blend`, float_img_blend alone, held to the bytes the pyramid moves - the frame written,
+the portrait outside the window read, face and portrait of the window read TWICE (D_0 is never stored), the mask levels, D_l as
+int16 (written, read by the next level down and twice on the way up) and R_l as int32 (written and read) - over the same copy
+peak.  The 1080-line JPEG loop is left out of such a run.
 Environment: REPS, WARMUP, LAUNCH_REPS, QUALITY."""
 import argparse
 import importlib
@@ -45,7 +52,8 @@ hm = pkg.host_models
 ap = argparse.ArgumentParser()
 ap.add_argument("--matrix", default=None, help="a second colour matrix to interleave with id 0 (2, 4, 6 or a name)")
 ap.add_argument("--resample", default=None, help="a resampling filter of the paste to interleave with the default route (bicubic, lanczos)")
-MATRIX, RESAMPLE = ap.parse_args().matrix, ap.parse_args().resample
+ap.add_argument("--blend", default=None, choices=("multiband",), help="the multi-band paste to interleave with the feathered one")
+MATRIX, RESAMPLE, BLEND = ap.parse_args().matrix, ap.parse_args().resample, ap.parse_args().blend
 if RESAMPLE is not None:
     hm.resample_filter_id("pastebench", RESAMPLE)
 MATRIX = None if MATRIX is None else hm.yuv_matrix_id(int(MATRIX) if MATRIX.lstrip("-").isdigit() else MATRIX)
@@ -79,7 +87,7 @@ parts = dict(enc=pkg.weights.synth_encoder_state(SIZE, seed=1), dec=pkg.weights.
 agent = gen.InferenceAgent(opt, parts, dev, max_frames=MAX_FRAMES, use_graph=2)
 audio = {"waveform": pkg.weights.synth_waveform(SECONDS, seed=1).reshape(1, 1, -1).cpu(), "sample_rate": 16000}
 FORMS = ("u8", "pasted", "i420", "jpeg") + (("i420_m",) if MATRIX is not None else ()) + \
-    (("pasted_r", "i420_r", "jpeg_r") if RESAMPLE is not None else ())
+    (("pasted_r", "i420_r", "jpeg_r") if RESAMPLE is not None else ()) + (("pasted_b",) if BLEND is not None else ())
 KW = dict(emo="neutral", seed=15)
 last = {}
 
@@ -96,6 +104,8 @@ def run(form, img, pad=None):
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", matrix=MATRIX, **KW)
     elif form == "pasted_r":
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, resample=RESAMPLE, **KW)
+    elif form == "pasted_b":
+        last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, blend=BLEND, **KW)
     elif form == "i420_r":
         last[form] = agent.infer_pasted(img, audio, 2.0, 1.0, 1.0, no_crop=False, out_format="i420", resample=RESAMPLE, **KW)
     elif form == "jpeg_r":
@@ -137,6 +147,14 @@ def launch_alone(place, peaks):
         scratch = pkg.image.paste_scratch((H, W), (SIZE, SIZE), place.rect, n, RESAMPLE, torch.device(dev))
         outs["rgb_r"] = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
         outs["resample"] = scratch.face
+    if BLEND is not None:
+        import ctypes as C
+        bxa, bya, bxb, byb = pkg.image.paste_window(H, W, place.rect)
+        inset, levels = pkg.image.blend_spec("pastebench", BLEND, rect=place.rect)
+        bscratch = pkg.image.paste_scratch((H, W), (SIZE, SIZE), place.rect, n, None, torch.device(dev), BLEND)
+        mask = pkg.image._blend_plan_device(torch.device(dev), H, W, tuple(place.rect), inset, levels)
+        outs["rgb_b"] = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+        outs["blend"] = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
     ms = {fmt: [] for fmt in outs}
     for i in range(3 + LAUNCH_REPS):
         for fmt, out in outs.items():
@@ -146,6 +164,13 @@ def launch_alone(place, peaks):
                 pkg.image.resample_frames_device(crops, place.rect[3], place.rect[2], RESAMPLE, win, out=out, work=scratch.work)
             elif fmt == "rgb_r":
                 pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out, resample=RESAMPLE, scratch=scratch)
+            elif fmt == "rgb_b":
+                pkg.image.paste_frames_device(place.src8, crops, place.rect, out=out, blend=BLEND, scratch=bscratch)
+            elif fmt == "blend":  # on the face rgb_b has left in the scratch
+                pkg.native.check(pkg.native.lib().float_img_blend(
+                    C.c_void_p(place.src8.data_ptr()), H, W, C.c_void_p(bscratch.face.data_ptr()), n, bxa, bya, byb - bya, bxb - bxa, levels,
+                    C.c_void_p(mask.data_ptr()), C.c_void_p(bscratch.blend_work.data_ptr()), bscratch.blend_work.numel() * 4,
+                    C.c_void_p(out.data_ptr()), pkg.native.stream_ptr(torch.device(dev))))
             else:
                 kw = dict(out_format="i420", matrix=MATRIX) if fmt == "i420_m" else dict(out_format=fmt)
                 pkg.image.paste_frames_device(place.src8, crops, place.rect, feather, out=out, **kw)
@@ -174,6 +199,20 @@ def launch_alone(place, peaks):
                                                                                     resample=RESAMPLE))))
             res[fmt] = r
             continue
+        if fmt in ("rgb_b", "blend"):
+            r = stats(ms[fmt])
+            hw = (byb - bya) * (bxb - bxa)
+            cells = [a * b for a, b in zip(hm.blend_sizes(byb - bya, levels), hm.blend_sizes(bxb - bxa, levels))]
+            pyramid = 12 * hw + 2 * sum(cells) + sum(6 * c * (4 if l < levels else 2) for l, c in enumerate(cells) if l) + \
+                sum(24 * c for l, c in enumerate(cells) if 0 < l < levels)
+            moved = n * (3 * H * W + 3 * (H * W - hw) + pyramid)
+            r.update(frames=n, inset=inset, levels=levels, window=[bxa, bya, bxb - bxa, byb - bya], minus_rgb_ms=round(r["median"] - statistics.median(ms["rgb"]), 3),
+                     equals_definition=bool(torch.equal(out[:1].cpu(), hm.paste_multiband_rgb8(place.src8.cpu(), crops[:1].cpu(), place.rect))))
+            if fmt == "blend":
+                r.update(pyramid_bytes_per_frame=pyramid, bytes_moved=moved, GBps=round(moved / 1e9 / (r["median"] * 1e-3), 1),
+                         fraction_of_copy_peak=round(moved / 1e9 / (r["median"] * 1e-3) / peaks["hbm_copy_GBps"], 3))
+            res[fmt] = r
+            continue
         moved = n * out[0].numel() + n * H * W * 3 + n * SIZE * SIZE * 3
         r = stats(ms[fmt])
         r.update(frames=n, bytes_moved=moved, GBps=round(moved / 1e9 / (r["median"] * 1e-3), 1),
@@ -188,7 +227,7 @@ def launch_alone(place, peaks):
 
 
 peaks = pkg.native.probe_peaks(dev)
-res = dict(probe="pastebench", matrix=MATRIX, resample=RESAMPLE, size=SIZE, frames=250, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP, quality=QUALITY, peaks=peaks)
+res = dict(probe="pastebench", matrix=MATRIX, resample=RESAMPLE, blend=BLEND, size=SIZE, frames=250, nfe=NFE, max_frames=MAX_FRAMES, reps=REPS, warmup=WARMUP, quality=QUALITY, peaks=peaks)
 for H, W in ((1024, 1024), (1088, 1920)):
     img = torch.from_numpy(np.random.RandomState(H).rand(1, H, W, 3).astype("float32"))
     for _ in range(WARMUP):
@@ -209,12 +248,15 @@ for H, W in ((1024, 1024), (1088, 1920)):
         for form, base in (("pasted_r", "pasted"), ("i420_r", "i420"), ("jpeg_r", "jpeg")):
             out[form]["minus_default_ms"] = round(out[form]["median"] - out[base]["median"], 3)
             out[form]["fraction_of_default"] = round(out[form]["median"] / out[base]["median"] - 1.0, 4)
+    if BLEND is not None:
+        out["pasted_b"]["minus_default_ms"] = round(out["pasted_b"]["median"] - out["pasted"]["median"], 3)
+        out["pasted_b"]["fraction_of_default"] = round(out["pasted_b"]["median"] / out["pasted"]["median"] - 1.0, 4)
     _, _, place = agent.host_inputs_placed(img, audio, no_crop=False)
     out["rect"] = list(place.rect)
     out["bytes_to_host"] = dict(u8=last["u8"].numel(), pasted=last["pasted"].numel(), i420=last["i420"].numel(), jpeg=last["jpeg"].nbytes)
     out["paste_launch_50_frames"] = launch_alone(place, peaks)
     res["%dx%d" % (W, H)] = out
-if RESAMPLE is not None:
+if RESAMPLE is not None or BLEND is not None:
     print(json.dumps(res))
     sys.exit(0)
 img1088 = torch.from_numpy(np.random.RandomState(1088).rand(1, 1088, 1920, 3).astype("float32"))
